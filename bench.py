@@ -12,9 +12,13 @@ whole batch (model_utils/tester.py:85-90) -- is measured beside it as `from_root
 gather (fullycnnspeechenhancement_amd/dist.py).
 A "step" = one forward of the hot path (model_utils/model.py:93-96 via the C ABI) over one batch of
 B x T x 129 synthetic magnitude frames already resident in HBM.
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel vs the fp32 MFMA/VALU peak, HIP events inside
-the timed region), `cpu_baseline` (the CPU restatement timed on this box's cores) and, at N = 1, `secondary`
-(BASELINE configs 2, 5 and 1, R-CED V1 / V2 in fp32 at config 3's shape, and the PCM -> PCM pipeline, under the same clock).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps and prints the headline (`value`,
+`ms_per_step`, ...); nothing else.  --full adds `roofline` (dominant kernel vs the peak of the pipes it runs on, HIP events
+over a pass of its own after the timed steps), `cpu_baseline` (the CPU restatement timed on this box's cores), at N = 1
+`host_buffers` and `secondary` (BASELINE configs 2, 5 and 1, R-CED V1 / V2 in fp32 at config 3's shape, and the
+PCM -> PCM pipeline, under the same clock), and at N > 1 `from_root`.
+--dump-outputs DIR writes the masks the timed steps computed (the last step's; a seeded sample when large) as
+DIR/mask.npy: inputs and weights are seeded, so the same arguments give the same inputs on every run.
 """
 
 import argparse
@@ -42,6 +46,8 @@ BF16_PEAK_TFLOPS = 2500.0  # dense bf16 MFMA (same table); only for bf16 lines
 PIPE_CEILING_TFLOPS = {"mfma_f32": FP32_PEAK_TFLOPS, "mfma_bf16x6": BF16_PEAK_TFLOPS / 6.0, "mfma_bf16": BF16_PEAK_TFLOPS}
 MEASURED_CEILING_TFLOPS = {"mfma_bf16x6": 386.0}
 NET_WORK = {1: "FullyCNN", 2: "FullyCNNV2", 3: "FullyCNNV3"}
+DUMP_BUDGET_BYTES = 32 << 20   # --dump-outputs: larger outputs are sampled down to this (config 3's masks are 67.6 MB)
+DUMP_SAMPLE_SEED = 20240607
 
 
 def pipe_roofline(flop_by_pipe, seconds):
@@ -108,10 +114,16 @@ def parse_args():
     ap.add_argument("--frames", type=int, default=512, help="time frames per utterance (config 3: 512)")
     ap.add_argument("--variant", type=int, default=3, choices=(1, 2, 3))
     ap.add_argument("--path", default="auto", choices=("auto", "layerwise", "fused"))
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget (0 = skip)")
-    ap.add_argument("--no-profile", action="store_true", help="do not time the dominant kernel with HIP events")
     ap.add_argument("--dtype", default="f32", choices=("f32", "bf16"),
                     help="bf16: R-CED V1/V2 only (BASELINE config 2); never the default, never the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the masks of the last timed step as DIR/mask.npy (float32; a seeded sample of frames when "
+                         "they exceed %d MiB)" % (DUMP_BUDGET_BYTES >> 20))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline, cpu_baseline, host_buffers and the secondary "
+                         "configs (N = 1), from_root (N > 1).  The options below apply to --full runs only")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget (0 = skip)")
+    ap.add_argument("--no-profile", action="store_true", help="do not time the dominant kernel with HIP events")
     ap.add_argument("--no-secondary", action="store_true", help="skip the config 2 / config 5 entries (N = 1 only)")
     ap.add_argument("--from-root-steps", type=int, default=5, help="timed forward_from_root calls at N > 1 (0 = skip)")
     ap.add_argument("--from-root-chunks", type=int, default=8, help="pipeline depth of forward_from_root")
@@ -120,7 +132,10 @@ def parse_args():
                          "first and `launch_ranks` relays it whatever the status; 0 = report the stall in the line only)")
     ap.add_argument("--from-root-timeout", type=int, default=150,
                     help="seconds after which a stalled forward_from_root is abandoned and the line printed without it")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_ranks(args):
@@ -233,11 +248,28 @@ def synthetic_magnitudes(shape, seed):
     return np.abs(x, out=x)
 
 
-def forward_line(args, torch, model, spec, _lib, variant, dtype, B, T, steps, warmup, world, rank, profile, ctl="cuda"):
-    """Time `steps` forwards of one resident batch; returns (elapsed_s, per-kind HIP-event times or None)."""
+def dump_outputs(out_dir, y):
+    """--dump-outputs: the masks `y` ([B, T, 129, 1]) as out_dir/mask.npy, float32.  Above DUMP_BUDGET_BYTES a fixed sample is
+    written instead: frames (rows of 129 bins) drawn with DUMP_SAMPLE_SEED, in batch-major order, shape [frames, 129]."""
+    import numpy as np
+    y = y.float().cpu().numpy()
+    if y.nbytes > DUMP_BUDGET_BYTES:
+        rows = y.reshape(-1, y.shape[2] * y.shape[3])
+        keep = DUMP_BUDGET_BYTES // rows[0].nbytes
+        y = rows[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows.shape[0], keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "mask.npy"), np.ascontiguousarray(y, dtype=np.float32))
+
+
+def forward_line(args, torch, model, spec, _lib, variant, dtype, B, T, steps, warmup, world, rank, profile, ctl="cuda", xy=None):
+    """Time `steps` forwards of one resident batch (`xy` = (x, y) of an earlier call, or a new one); returns (elapsed_s,
+    per-kind HIP-event times or None, (x, y))."""
     import torch.distributed as dist
-    x = torch.from_numpy(synthetic_magnitudes((B, T, spec.FEATURE_DIM, 1), 1234 + rank)).cuda()   # resident before the clock starts
-    y = torch.empty_like(x)
+    if xy is None:
+        x = torch.from_numpy(synthetic_magnitudes((B, T, spec.FEATURE_DIM, 1), 1234 + rank)).cuda()   # resident before the clock starts
+        y = torch.empty_like(x)
+    else:
+        x, y = xy
     model.reserve(B, T)
     lib = _lib.load()
     stream = torch.cuda.current_stream()
@@ -685,8 +717,16 @@ def main():
                         dtype="bfloat16" if args.dtype == "bf16" else "float32")
     model.set_path(args.path)
     B, T = args.batch, args.frames
-    elapsed, times, (x, y) = forward_line(args, torch, model, spec, _lib, variant, args.dtype, B, T, args.steps,
-                                          args.warmup, world, rank, not args.no_profile, ctl)
+    elapsed, _, (x, y) = forward_line(args, torch, model, spec, _lib, variant, args.dtype, B, T, args.steps,
+                                      args.warmup, world, rank, False, ctl)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, y)
+    times = None
+    if args.full and not args.no_profile:
+        # the roofline's HIP events around every launch: a pass of its own over the same batch, so that they are never
+        # inside the headline's clock
+        _, times, _ = forward_line(args, torch, model, spec, _lib, variant, args.dtype, B, T, args.steps, 0, world, rank,
+                                   True, ctl, xy=(x, y))
 
     frames_total = world * B * T * args.steps
     flops_frame = spec.flops_per_frame(variant)
@@ -705,12 +745,13 @@ def main():
                    "rccl_world_size": rccl_world, "weights": "random-init (glorot, seed 42)",
                    "input": "|N(0,1)| float32, numpy default_rng(1234 + rank), resident in HBM before the timed region",
                    "library": _lib.version()},
-        "from_root": None,
     }
     if rehearse:
         out["config"]["rehearsal"] = ("RCED_BENCH_REHEARSE=1: %d ranks on %d GPU(s), gloo control plane -- a test of the N > 1 "
                                       "control flow, NOT a measurement" % (world, torch.cuda.device_count()))
-    if rank == 0:
+    if args.full:
+        out["from_root"] = None
+    if rank == 0 and args.full:
         roof = None
         if times is not None:
             dom = max(times, key=lambda k: times[k][0])
@@ -753,7 +794,7 @@ def main():
     # the line as it is (from_root.error = the timeout) and every rank EXITS (never restarts or re-execs) with
     # --from-root-fail-status, 3 by default: a stalled scatter must not read as success to a caller that gates on the
     # status.  The line is on stdout before the exit, and `launch_ranks` relays it whatever the status.
-    if world > 1 and args.from_root_steps > 0:
+    if args.full and world > 1 and args.from_root_steps > 0:
         import threading
 
         def give_up():
@@ -785,15 +826,16 @@ def main():
             out["from_root"] = {"error": "%s: %s" % (type(e).__name__, e)}
         timer.cancel()
     host_line = None
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         try:
             host_line = host_buffers_line(model, x)
         except Exception as e:
             host_line = {"error": "%s: %s" % (type(e).__name__, e)}
-    out["host_buffers"] = host_line
+    if args.full:
+        out["host_buffers"] = host_line
     del x, y
     model.close()
-    if rank == 0:
+    if rank == 0 and args.full:
         # the CPU restatement and the secondary configs run on rank 0 of the 1-GPU run only
         out["cpu_baseline"] = (cpu_baseline(variant, weights, T, args.cpu_seconds)
                                if args.cpu_seconds > 0 and world == 1 else None)
@@ -813,6 +855,7 @@ def main():
                     sec.append({"config": fn.__doc__.split(":")[0].strip(), "error": "%s: %s" % (type(e).__name__, e)})
                 torch.cuda.empty_cache()
             out["secondary"] = sec
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         # the line is out; a peer that is gone must not turn the run into a watchdog abort while everybody says goodbye

@@ -829,7 +829,7 @@ def _run_bench_rehearsal(extra_env, timeout_s, *args):
     from conftest import ROOT
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update({"RCED_BENCH_REHEARSE": "1"}, **extra_env)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
                         "--cpu-seconds", "0", "--no-secondary", "--batch", "8", "--frames", "64"] + list(args),
                        env=env, capture_output=True, text=True, timeout=timeout_s)
     lines = [l for l in r.stdout.splitlines() if l.lstrip().startswith("{")]
@@ -864,6 +864,38 @@ def test_bench_line_survives_a_from_root_that_never_returns():
     r, d = _run_bench_rehearsal({"RCED_BENCH_REHEARSE_HANG": "1"}, 600, "--from-root-timeout", "5", "--from-root-fail-status", "0")
     assert r.returncode == 0, r.stderr[-3000:]
     assert d is not None and "timeout" in d["from_root"]["error"]
+
+
+def test_plain_bench_line_and_dumped_masks(built, tmp_path):
+    """A plain `bench.py --gpus 1` run prints the headline and nothing measured beside it (that is --full's), times exactly
+    --steps steps, and --dump-outputs writes the masks of the timed path: those of the oracle on bench.py's own seeded inputs,
+    and the same on a second run."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    from fullycnnspeechenhancement_amd import weights
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    B, T, steps = 3, 40, 4
+    masks = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT_DIR, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                            "--batch", str(B), "--frames", str(T), "--dump-outputs", str(tmp_path / run)],
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout[-3000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == steps and d["warmup"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+        assert d["unit"] == "frames/s" and d["ms_per_step"] > 0
+        assert abs(d["value"] - B * T * steps / (d["ms_per_step"] * steps * 1e-3)) < 1e-6 * d["value"]
+        assert not {"roofline", "cpu_baseline", "host_buffers", "secondary", "from_root"} & set(d), sorted(d)
+        y = np.load(str(tmp_path / run / "mask.npy"))
+        assert y.dtype == np.float32 and y.shape == (B, T, 129, 1)
+        masks.append(y)
+    x = bench.synthetic_magnitudes((B, T, 129, 1), 1234)
+    check_parity(masks[0], rced_c.forward("FullyCNNV3", weights.synthetic_weights(3, seed=42), x, np.float64), what="bench dump")
+    assert np.array_equal(masks[0], masks[1])
 
 
 def _copy_gpu_worker(rank, world, port, out_path):

@@ -158,3 +158,24 @@ def test_host_output_pool_hands_out_fresh_looking_arrays():
     e = pool.take((2, 3, 4))                                              # b, c, d held, the cap (three buffers) reached: numpy.empty
     assert e.base is None and e.shape == (2, 3, 4) and e.dtype == np.float32
     assert pool.take((5, 1, 129, 1)).shape == (5, 1, 129, 1)
+
+
+def test_bench_dump_outputs_is_whole_when_small_and_a_fixed_sample_when_large(tmp_path):
+    """bench.py --dump-outputs: a small output is written whole; a large one as the same seeded sample of whole frames on every run,
+    taken from the output in batch-major order and within the dump's budget (64 MB at most in all)."""
+    import torch
+    import bench
+    y = torch.rand((3, 5, 129, 1), generator=torch.Generator().manual_seed(1))
+    bench.dump_outputs(str(tmp_path / "small"), y)
+    got = np.load(str(tmp_path / "small" / "mask.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, y.numpy())
+    n, t = 32, (bench.DUMP_BUDGET_BYTES // (129 * 4)) // 32 + 7             # one batch a little over the budget
+    y = torch.arange(n * t * 129, dtype=torch.float32).reshape(n, t, 129, 1)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), y)
+    a, b = (np.load(str(tmp_path / run / "mask.npy")) for run in ("a", "b"))
+    assert a.dtype == np.float32 and a.ndim == 2 and a.shape[1] == 129 and np.array_equal(a, b)
+    assert a.nbytes <= bench.DUMP_BUDGET_BYTES <= 64 * 10 ** 6 and a.shape[0] > 0.9 * bench.DUMP_BUDGET_BYTES // (129 * 4)
+    frames = a[:, 0] / 129                                                  # row r of the [n*t, 129] view starts at r * 129
+    assert np.array_equal(frames, np.round(frames)) and np.all(np.diff(frames) > 0)
+    assert np.array_equal(a, y.numpy().reshape(-1, 129)[frames.astype(np.int64)])

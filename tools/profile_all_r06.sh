@@ -4,9 +4,10 @@
 # one launch: kernels_frame16.h), the training step, the audio kernels.  Outputs under gpurun_out/prof_r06* (the summaries are copied into
 # profiles/ by hand, ONE capture commit).
 set -u
+LINES=${BENCH_LINES_DIR:?set BENCH_LINES_DIR to the directory the two bench lines are written to}
 python3 __graft_entry__.py > /dev/null 2>&1
-python3 bench.py > gpurun_out/r06_bench_default.json 2> gpurun_out/r06_bench_default.err
-python3 bench.py --variant 2 --dtype bf16 --batch 64 --steps 200 --cpu-seconds 0 --no-secondary > gpurun_out/r06_bench_config2.json 2> /dev/null
+python3 bench.py --full > "$LINES/r06_bench_default.json" 2> "$LINES/r06_bench_default.err"
+python3 bench.py --full --variant 2 --dtype bf16 --batch 64 --steps 200 --cpu-seconds 0 --no-secondary > "$LINES/r06_bench_config2.json" 2> /dev/null
 bash tools/profile.sh r06v3 > /dev/null 2>&1
 TRACE_STEPS=300 TRACE_WARMUP=100 bash tools/profile.sh r06c2 --variant 2 --dtype bf16 --batch 64 > /dev/null 2>&1   # a 0.5-ms kernel: 13 launches run on idle clocks
 bash tools/profile_train.sh r06 > /dev/null 2>&1
