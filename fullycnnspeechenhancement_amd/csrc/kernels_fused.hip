@@ -573,7 +573,7 @@ int upload(float** dev, const std::vector<float>& host) {   // *dev is set only 
 }  // namespace
 
 // tools/summarize_prof.py prints these next to a profile (the kernel-trace CSV reports 0 for dynamic LDS)
-static_assert(v3::MapA::kLdsBytes == 159024 && v3::MapF32::kLdsBytes == 163024, "update DYNAMIC_LDS in tools/summarize_prof.py");
+static_assert(v3::MapA::kLdsBytes == 160448 && v3::MapF32::kLdsBytes == 163024, "update DYNAMIC_LDS in tools/summarize_prof.py");
 #if RCED_V3_LEGACY_FORMS
 static_assert(v3::MapT::kLdsBytes == 163792 && v3::MapX6::kLdsBytes == 162976, "update DYNAMIC_LDS in tools/summarize_prof.py");
 #endif

@@ -276,7 +276,8 @@ static_assert(kW1 + kFin128 <= kWRegion && (kW1 % 4) == 0, "F32 form: the bin-12
 // every P value is added into the output accumulators of this tile and of one neighbour with DPP row shifts (v_add_f32_dpp,
 // 34 per lane and tile: beside bf16 MFMAs nearly free).  What the fp32 form spends on layer 3 -- 75 fp32 MFMAs of 32 cycles
 // per 32 pixels, the [pixel][30] stores and their re-reads, a barrier -- becomes 30 bf16 MFMAs of 16 cycles per 16 pixels.
-// Tiles are FRAME-ALIGNED here (frame f = waves f and f + 4: tiles 0..3 and 4..8 of its 129 bins; tile 8 has one real pixel):
+// Tiles are FRAME-ALIGNED here (frame f = waves f and f + 4: tiles 0..3 and 4..8 of its 129 bins; tile 8 has one real pixel -- in
+// the all-x6 form waves f + 4 take tiles 4..7 only and bin 128 of the four frames is one shared job, layer23):
 // no tile straddles a gap, the 4 zero gap pixels absorb every shift across frames, and the only partial sums that cross
 // waves are the two at the middle of each frame (LDS scratch + tagged flags, as the split tiles of the other forms).
 constexpr int kL3MT = 5;                                   // M-tiles of layer-3 weights (ten taps, the tenth zero)
@@ -353,7 +354,11 @@ struct Map<3> {
   static constexpr int kHOff = kB8Off, kFin128Off = kB8Off;                     // (other forms' buffers: make_lane's unused addresses)
   static constexpr int kEdgeOff = kX0Off + kX0Floats;
   static constexpr int kEdgeFlagOff = kEdgeOff + 4 * 2 * 128;
-  static constexpr int kLdsFloats = kEdgeFlagOff + 8;
+  // bin 128's shared tail (layer23): layer 2's split [M-tile 2][part 3][kq 4][frame 4] x 8 B, layer 3's partials [frame 4][tap 4..8][kq 4]
+  // x 8 B, four flags
+  static constexpr int kTailOff = kEdgeFlagOff + 8;
+  static constexpr int kTailFloats = (2 * 3 * 16 * 8 + 4 * 5 * 4 * 8 + 16) / 4;
+  static constexpr int kLdsFloats = kTailOff + kTailFloats;
   static constexpr int kLdsBytes = kLdsFloats * 4;
   static_assert(kLdsBytes <= 160 * 1024, "LDS budget");
   static_assert((kB18Off * 4) % 16 == 0 && (kWOff * 4) % 16 == 0 && (kW3TOff * 4) % 16 == 0 && (kW1Off * 4) % 16 == 0 && (kFinTOff * 4) % 16 == 0 &&
@@ -628,7 +633,8 @@ __device__ __forceinline__ Lane make_lane(float* lds, int wave, int lane, int xr
     if constexpr (M::kFused) L.wr1r = PL + M::kRemOff + (rpx + 2 * kq + kB18Pad) * 4;   // [c16 c17] of the h part; m, l: + the part stride
     // layer 2: wave (g = M-tile, j) walks tiles j + 4t; px2 = this lane's pixel of tile j
     // chunk c: tap 2c + (kq >> 1) = pixel px2 - 2 + tap = row px2 + tap, channels 8 (kq & 1)..+7
-    // (fused form: frame-aligned tiles -- waves 0..3: tiles 0..3 of frame `wave`, waves 4..7: tiles 4..8 of frame `wave - 4`)
+    // (fused form: frame-aligned tiles -- waves 0..3: tiles 0..3 of frame `wave`, waves 4..7: tiles 4..8 of frame `wave - 4`; all-x6
+    // form: tiles 4..7, bin 128 in layer23's shared tail)
     const int px2 = M::kFused ? kS * (wave & 3) + 64 * (wave >> 2) + n : RCED_L2_BOTH ? px0 : 16 * (wave & 3) + n;
     L.rd2m = PL + (px2 + (kq >> 1)) * 32 + (kq & 1) * 16;
     if constexpr (M::kAllX6) L.rd2m = PL + (kq & 1) * M::kHalfBytes + (px2 + (kq >> 1)) * 16;

@@ -7,7 +7,8 @@
 //   Y: layer 3, five M-tiles of (cout, tap) rows x six products                = 30 MFMAs  -> P[j] (lane (kq, n): couts 2kq, 2kq+1 x taps 2j, 2j+1)
 //      shift-add: out[p] += P_t[p + t - 4], 34 v_add_f32_dpp
 // Layer 3 runs for TWO tiles at a time (YY): one set of A fragments from LDS per M-tile and pair -- read per tile they were a fifth of
-// the forward's time -- and two independent accumulation chains per slot.  Order: X0 X1 X2 YY01 X3 [X4] YY23 [Y4]; tile t's split
+// the forward's time -- and two independent accumulation chains per slot.  Order: X0 X1 X2 YY01 X3 [X4] YY23 [Y4] (X4, Y4: a frame's
+// ninth tile on waves 4..7, legacy fused form only; the all-x6 form runs 4 + 4 tiles and bin 128 as a shared tail, see layer23); tile t's split
 // runs between the MFMAs of X(t+1), a pair's shift-adds between its own MFMAs, one M-tile behind.  Output accumulators
 // W / X / Y / Z = the pixels of the tile in front of the pair, of its two tiles and of the tile behind it; after a pair, W and X are
 // complete (epilogue: shift, ReLU, block skips, one 8-byte store per lane) and Y, Z become the next pair's W, X.
@@ -18,8 +19,14 @@
                          // there anyway) when the phase starts: eight waves x 9 KB less on the vector-memory path during layer 1
 #endif
 #ifndef RCED_T_PRIO
-#define RCED_T_PRIO 1    // the waves with five tiles (4..7) run this phase at raised priority: their SIMD partners (four tiles) are the older
-                         // waves, which the issue arbiter prefers -- left alone they finish at two thirds of the phase and the rest runs single
+#define RCED_T_PRIO 1    // waves 4..7 run this phase at raised priority: their SIMD partners are the older waves, which the issue arbiter prefers.
+                         // Legacy fused form: waves 4..7 have five tiles against four -- left alone they finish at two thirds of the phase and
+                         // the rest runs single.  All-x6 form: 4 + 4 tiles, and waves 4..7 also carry bin 128's shared tail (RCED_T_TAILW) and
+                         // wait for the partials it hands over; without the raised priority 5.875 ms against 5.735 (profiles/NOTES.md)
+#endif
+#ifndef RCED_T_TAILW
+#define RCED_T_TAILW 4   // all-x6 form: the waves that run bin 128's shared tail: 4 = waves 4..7 (raised priority, RCED_T_PRIO), 0 = waves 0..3
+                         // (measured: 5.759 against 5.735 ms)
 #endif
 #ifndef RCED_T_A3D
 #define RCED_T_A3D 1     // (2 measured: no gain -- it is not their latency) layer 3's A fragments are read this many slots ahead of their use (ring of RCED_T_A3D + 1)
@@ -34,7 +41,9 @@
 #define RCED_T_EXP 0   // timing experiments only (WRONG RESULTS): 1 = no shift-adds, 2 = layer 3's A fragments read once (round 5: this build's
                        // 10 % are not the reads -- with equal fragments hipcc merges the MFMAs of M-tiles 2..4 into those of 0, 1: 252 of the
                        // kernel's 1,218 static MFMAs disappear), 4 = no split arithmetic, 8 = layer 2's B fragments read once per tile,
-                       // 256 = a third of layer 1's B reads, 512 = no weight transfers, 4096 = layer 1 without its main tiles' epilogues, 8192 = layer 1's pair jobs only
+                       // 256 = a third of layer 1's B reads, 512 = no weight transfers, 1024 = all-x6 form without bin 128's shared tail (its
+                       // three jobs and the hand-off; bin 128's epilogue still runs: prices the tail).  The step-0 bound (-6.2 %) was measured
+                       // with an EARLIER form of this bit, before the tail existed: waves 4..7 kept tiles 4..8 and skipped X4, Y4 and finish(4), 4096 = layer 1 without its main tiles' epilogues, 8192 = layer 1's pair jobs only
 #endif
 #if (RCED_T_EXP != 0 || RCED_X6_EXP != 0) && !defined(RCED_TIMING_ONLY)
 #error "RCED_T_EXP / RCED_X6_EXP builds compute wrong results: timing experiments only (tools/mkexp.sh ... -DRCED_TIMING_ONLY -DRCED_T_EXP=...)"
@@ -104,6 +113,11 @@ __device__ __forceinline__ void shift_add(f32x4 pj, float& p0, float& p1, float&
   if constexpr (2 * J + 1 < 9) tap_add<3 - 2 * J>(pj.w, p1, c1, n1);
 }
 
+template <class M>
+constexpr int tail_off() {   // all-x6 form: the shared tail's LDS area (see layer23)
+  if constexpr (M::kAllX6) return M::kTailOff;
+  else return 0;
+}
 // `sp(IC<j>)`, j < 5: called once from each layer-3 slot of the wave's LAST job (by then layer 2's operand registers are free):
 // the register-bound loads of what comes next.
 // `dma1()`: called once, behind the first operand reads (RCED_T_L1X6: the next layer 1's images, LDS-DMA'd into areas that are dead now)
@@ -351,13 +365,98 @@ __device__ __forceinline__ void layer23(const Params& P, const Lane& L, unsigned
   const IC<3> i3;
   const IC<4> i4;
 
+  // ---- all-x6 form: bin 128 of the block's four frames as ONE shared tail (a frame's last tile has one real pixel; as a tile of its
+  // own it cost its right wave 36 + 30 MFMAs).  One 16-column job, column n = frame n & 3 (columns 4..15 repeat 0..3: MFMA columns
+  // are independent, their results are dropped): lane (kq, n) reads what lane (kq, 0) of wave (n & 3) + 4 read for tile 8, so every
+  // frame's column gets the same products in the same order as before.  The tail's waves (RCED_T_TAILW + 0..3): the first two run
+  // layer 2's M-tile 0 / 1, ReLU, split -> LDS, at the phase's start; the other two layer 3's M-tiles 2, 3 / 4 behind their first job (taps 4..8: the only taps of pixel 128 that reach a real output, 124..128) -> LDS; wave
+  // f + 4 adds frame f's partials where the tile's own layer-3 job added them (behind everything else, one per output: no result
+  // bit changes).  At most 18 of the tail's 54 MFMAs per SIMD.
+  const int tln = (int)(L.a4 >> 2), tn = tln & 15, tkq = tln >> 4, tf = tn & 3;
+  const unsigned tb = lds0 + 4 * tail_off<M>();
+  constexpr int kT3 = 2 * 3 * 16 * 8, kTFlag = kT3 + 4 * 5 * 4 * 8;   // byte offsets: layer 3's partials [frame][tap - 4][kq] x 8 B, the four flags
+  // (the unnamed `auto` makes the lambda a template: its body, which names members only Map<3> has, is instantiated where it is
+  // called, inside `if constexpr (M::kAllX6)`)
+  auto tail2 = [&](auto, int mt) {   // layer 2's M-tile mt -> its split pieces 2 mt, 2 mt + 1: [mt][part][kq][frame] x 8 B
+    const unsigned PL = lds0 + 4 * M::kB18Off, px = kS * tf + 64;
+    const unsigned rm = PL + (tkq & 1) * M::kHalfBytes + (px + (tkq >> 1)) * 16;
+    const unsigned rc = tkq < 2 ? rm + 64 + 4 * M::kTileB18 : PL + M::kRemOff + (px + 4 * (tkq & 1)) * 4 + 4 * 64;
+    const unsigned am = a2 + (unsigned)mt * 3072u;
+    f32x4 acc = mt ? sh2[1] : sh2[0];
+    static_for<0, 3>([&](auto cc) {
+      constexpr int c = decltype(cc)::value;
+      Parts b;
+      if constexpr (c < 2) {
+        b.h = lds_ld<s16x8>(rm, 4 * M::kTileB18 + 32 * c);
+        b.m = lds_ld<s16x8>(rm, 4 * M::kTileB18 + 32 * c + M::kPlaneBytes);
+        b.l = lds_ld<s16x8>(rm, 4 * M::kTileB18 + 32 * c + 2 * M::kPlaneBytes);
+      } else {
+        u32x4 h, m, l;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          h[i] = lds_ld<unsigned>(rc, 4 * i);
+          m[i] = lds_ld<unsigned>(rc, 4 * i + M::kPlaneBytes);
+          l[i] = lds_ld<unsigned>(rc, 4 * i + 2 * M::kPlaneBytes);
+        }
+        b.h = __builtin_bit_cast(s16x8, h);
+        b.m = __builtin_bit_cast(s16x8, m);
+        b.l = __builtin_bit_cast(s16x8, l);
+      }
+      s16x8 a[3];
+#pragma unroll
+      for (int q = 0; q < 3; ++q) a[q] = lds_ld<s16x8>(am, (6 * c + q) * 1024);
+      acc = l2x_mma(a, b, acc);
+    });
+    const P3 p0 = split2(relu1(acc.x), relu1(acc.y)), p1 = split2(relu1(acc.z), relu1(acc.w));
+    const unsigned r = tb + (unsigned)(mt * 3 * 16 + tkq * 4 + tf) * 8u;
+    lds_st<u32x2>(r, 0, u32x2{p0.h, p1.h});
+    lds_st<u32x2>(r, 16 * 8, u32x2{p0.m, p1.m});
+    lds_st<u32x2>(r, 32 * 8, u32x2{p0.l, p1.l});
+    cbar();
+    if (L.a4 == 0) lds_poke_a(tb + kTFlag + 4 * mt, tag);
+  };
+  auto tail3 = [&](auto j0c, auto j1c) {   // layer 3's M-tiles j0 .. j1 - 1
+    constexpr int j0 = decltype(j0c)::value, j1 = decltype(j1c)::value;
+    flag_wait(tb + kTFlag, tag, P.err, 8u);
+    flag_wait(tb + kTFlag + 4, tag, P.err, 8u);
+    const unsigned r = tb + (unsigned)(tkq * 4 + tf) * 8u;
+    Parts b;
+    const u32x2 h0 = lds_ld<u32x2>(r, 0), m0 = lds_ld<u32x2>(r, 16 * 8), l0 = lds_ld<u32x2>(r, 32 * 8);
+    const u32x2 h1 = lds_ld<u32x2>(r, 48 * 8), m1 = lds_ld<u32x2>(r, 64 * 8), l1 = lds_ld<u32x2>(r, 80 * 8);
+    b.h = __builtin_bit_cast(s16x8, u32x4{h0[0], h0[1], h1[0], h1[1]});
+    b.m = __builtin_bit_cast(s16x8, u32x4{m0[0], m0[1], m1[0], m1[1]});
+    b.l = __builtin_bit_cast(s16x8, u32x4{l0[0], l0[1], l1[0], l1[1]});
+    static_for<j0, j1>([&](auto jc) {
+      constexpr int j = decltype(jc)::value;
+      s16x8 a[3];
+#pragma unroll
+      for (int q = 0; q < 3; ++q) a[q] = lds_ld<s16x8>(a3, (j * 3 + q) * 1024);
+      const f32x4 p = l2x_mma(a, b, zero4);
+      const unsigned o = tb + kT3 + (unsigned)((tf * 5 + 2 * j - 4) * 4 + tkq) * 8u;
+      lds_st<f32x2>(o, 0, f32x2{p.x, p.z});                       // tap 2j: couts 2kq, 2kq + 1
+      if constexpr (2 * j + 1 < 9) lds_st<f32x2>(o, 32, f32x2{p.y, p.w});   // tap 2j + 1 (tap 9 is padding)
+    });
+    cbar();
+    if (L.a4 == 0) lds_poke_a(tb + kTFlag + 8 + 4 * (j0 == 2 ? 0 : 1), tag);
+  };
+  const bool tail = M::kAllX6 && !(RCED_T_EXP & 1024);
+
   if (RCED_T_PRIO && right) __builtin_amdgcn_s_setprio(RCED_T_PRIO);
-  // ---- the stream.  Waves 0..3: tiles 0..3 of frame fr (X0 X1 X2 YY01 X3 YY23); waves 4..7: tiles 4..8 (X0 X1 X2 YY01 X3 X4 YY23 Y4)
+  // ---- the stream.  Waves 0..3: tiles 0..3 of frame fr (X0 X1 X2 YY01 X3 YY23); waves 4..7: tiles 4..8 (X0 X1 X2 YY01 X3 X4 YY23 Y4),
+  // all-x6 form: tiles 4..7 (X0 X1 X2 YY01 X3 YY23) and the shared tail's partials of bin 128
+  const int tw = wave - RCED_T_TAILW;   // the tail's waves: 0, 1 layer 2, 2, 3 layer 3
+  if constexpr (M::kAllX6) {
+    if (tail && (tw == 0 || tw == 1)) tail2(i0, tw);
+  }
   ldX(i0, i0);
   pin();
   if (!(RCED_T_EXP & 512)) dma1();   // (512: timing experiment, wrong results: no weight transfers at all)
   pin();
   runX(i0, i0, none);
+  if constexpr (M::kAllX6) {
+    if (tail && tw == 2) tail3(i2, i4);
+    else if (tail && tw == 3) tail3(i4, IC<5>{});
+  }
   runX(i1, i0, none);
   runX(i2, i1, none);
   DET(0);
@@ -372,6 +471,30 @@ __device__ __forceinline__ void layer23(const Params& P, const Lane& L, unsigned
     publish(0, x0, x1);
     const f32x2 e = fetch(1);                              // published behind the right wave's FIRST pair: long there
     finish(i3, w0 + e.x, w1 + e.y);
+  } else if (M::kAllX6) {
+    runX(i3, i1, [&] { tail_pair(i0); });
+    DET(2);
+    static_for<0, 4>([&](auto qc) { split_piece(i3, qc); });
+    runY(i2, i1, i2, i0, i0, none);                        // YY23, the wave's last job
+    tail_pair(i2);                                         // w = local tile 3, x = its share of bin 128
+    if (tail) {   // bin 128's taps 4..8: tap 4 into bin 128 (lane 0), taps 8..5 into bins 124..127 (lanes 12..15)
+      flag_wait(tb + kTFlag + 8, tag, P.err, 8u);
+      flag_wait(tb + kTFlag + 12, tag, P.err, 8u);
+      const int ti = tn >= 12 ? 16 - tn : 0;
+      const f32x2 r = lds_ld<f32x2>(tb + kT3 + (unsigned)((fr * 5 + ti) * 4 + tkq) * 8u, 0);
+      if (tn >= 12) {
+        w0 += r.x;
+        w1 += r.y;
+      } else if (tn == 0) {
+        x0 += r.x;
+        x1 += r.y;
+      }
+    }
+    finish(i3, w0, w1);
+    finish(i4, x0, x1);
+    const f32x2 e = fetch(0);
+    finish(i0, hold.x + e.x, hold.y + e.y);
+    if (RCED_T_PRIO) __builtin_amdgcn_s_setprio(0);
   } else {
     runX(i3, i0, [&] { tail_pair(i0); });
     runX(i4, i1, none);
