@@ -10,7 +10,7 @@ from .model import (FullyCNNSEModel, FullyCNNSEModelV2, FullyCNNSEModelV3, build
                     conv_bn_relu)
 from .engine import FullyCNNTester, InferenceEngine  # noqa: F401
 from .trainer import FullyCNNTrainer  # noqa: F401
-from . import audio, spec, weights  # noqa: F401
+from . import audio, loader, metrics, spec, weights  # noqa: F401
 
 __all__ = ["FullyCNNSEModel", "FullyCNNSEModelV2", "FullyCNNSEModelV3", "build_model", "conv_bn_relu",
-           "FullyCNNTester", "InferenceEngine", "FullyCNNTrainer", "audio", "spec", "weights"]
+           "FullyCNNTester", "InferenceEngine", "FullyCNNTrainer", "audio", "loader", "metrics", "spec", "weights"]

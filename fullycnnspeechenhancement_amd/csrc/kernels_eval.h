@@ -1,0 +1,298 @@
+// Evaluation-loop kernels (include/rced.h, "evaluation" section): AudioParser.add_noise for a ragged batch in closed form,
+// and the per-utterance SDR.  Both are streaming reductions over ragged rows.
+//
+// One mapping for every kernel here: an utterance is cut into slices of kSlice samples; inside a slice, lane t of the
+// workgroup owns the 16-byte groups t and t + kThreads (samples 4g .. 4g+3 of the slice).  Which lane and slice an element
+// lands in therefore depends on its index inside its utterance only -- not on the batch, the row, the stride or the
+// alignment -- and every sum is taken in one fixed order: per lane over its elements in index order, across the wave by
+// an xor butterfly, across the four waves through LDS in wave order, across slices (second pass) in the same shape.
+// Row alignment picks the load WIDTH (dwordx4 when the row base is 16-byte aligned, dword otherwise), never the order.
+// No atomics: slice partials go to a workspace [N, slices, 2] with plain vector stores.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace rced {
+namespace eval {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kGroupsPerLane = 2;
+constexpr int kSlice = kThreads * 4 * kGroupsPerLane;   // 2048 samples per workgroup
+constexpr int kQTable = 160;                            // gain products kept in LDS: a slice spans <= kSlice / ln + 2 tiles
+constexpr int kMaxLen = 1 << 30;                        // index math is 32-bit
+
+__host__ __device__ inline int num_slices(int len) { return (len + kSlice - 1) / kSlice; }
+
+__device__ inline double wave_sum(double v) {   // every lane ends with the same bits: a + b and b + a are the same sum
+#pragma unroll
+  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// (a, b) summed over the workgroup, the result in every thread.  Safe to call again on the same scratch.
+template <int NW>
+__device__ inline void block_sum2(double& a, double& b, double (*sh)[2]) {
+  a = wave_sum(a);
+  b = wave_sum(b);
+  if (NW > 1) {
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+      sh[threadIdx.x >> 6][0] = a;
+      sh[threadIdx.x >> 6][1] = b;
+    }
+    __syncthreads();
+    a = sh[0][0];
+    b = sh[0][1];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) {
+      a += sh[w][0];
+      b += sh[w][1];
+    }
+  }
+}
+
+__device__ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// row[p .. p+3] with everything at or past `limit` read as 0; p is a multiple of 4 whenever vec is set
+__device__ inline void load4(const float* row, int p, int limit, bool vec, float v[4]) {
+  if (vec && p + 4 <= limit) {
+    const float4 t = *reinterpret_cast<const float4*>(row + p);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = p + k < limit ? row[p + k] : 0.f;
+  }
+}
+
+__device__ inline int clamp_len(const int* lens, int n, int cap) {
+  const int v = lens ? lens[n] : cap;
+  return v < 0 ? 0 : (v > cap ? cap : v);
+}
+
+// ---- SDR ---------------------------------------------------------------------------------------------------------
+
+// grid (slices, N): ws[n][s] = (sum y^2, sum (y_pred - y)^2) over slice s of utterance n
+__global__ __launch_bounds__(kThreads) void sdr_partial_kernel(const float* __restrict__ ref, int ref_stride,
+                                                               const float* __restrict__ est, int est_stride,
+                                                               const int* __restrict__ lengths, int cap,
+                                                               double* __restrict__ ws, int slices) {
+  __shared__ double red[kWaves][2];
+  const int n = blockIdx.y, s = blockIdx.x;
+  const int len = clamp_len(lengths, n, cap);
+  const int base = s * kSlice;
+  if (base >= len) return;
+  const float* r = ref + (size_t)n * ref_stride;
+  const float* e = est + (size_t)n * est_stride;
+  const bool rvec = aligned16(r), evec = aligned16(e);
+  double sy = 0.0, se = 0.0;
+#pragma unroll
+  for (int j = 0; j < kGroupsPerLane; ++j) {
+    const int p = base + (j * kThreads + threadIdx.x) * 4;
+    if (p < len) {
+      float a[4], b[4];
+      load4(r, p, len, rvec, a);
+      load4(e, p, len, evec, b);
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (p + k < len) {
+          const double y = a[k], d = (double)b[k] - y;
+          sy += y * y;
+          se += d * d;
+        }
+    }
+  }
+  block_sum2<kWaves>(sy, se, red);
+  if (threadIdx.x == 0) *reinterpret_cast<double2*>(ws + ((size_t)n * slices + s) * 2) = make_double2(sy, se);
+}
+
+// partials of utterance n summed in slice order: lane t takes slices t, t + blockDim, ..., then block_sum2
+template <int NW>
+__device__ inline void sum_partials(const double* __restrict__ ws, int n, int slices, int nsl, double& a, double& b,
+                                    double (*sh)[2]) {
+  a = 0.0;
+  b = 0.0;
+  for (int j = threadIdx.x; j < nsl; j += NW * 64) {
+    const double2 v = *reinterpret_cast<const double2*>(ws + ((size_t)n * slices + j) * 2);
+    a += v.x;
+    b += v.y;
+  }
+  block_sum2<NW>(a, b, sh);
+}
+
+// grid (N), one wave: SDR.sdr's last line.  y_en = 0 gives -inf, as numpy's log10(0) does.
+__global__ __launch_bounds__(64) void sdr_final_kernel(const double* __restrict__ ws, const int* __restrict__ lengths,
+                                                       int cap, int slices, double* __restrict__ sdr,
+                                                       double* __restrict__ energies) {
+  const int n = blockIdx.x;
+  const int len = clamp_len(lengths, n, cap);
+  double sy, se;
+  sum_partials<1>(ws, n, slices, num_slices(len), sy, se, nullptr);
+  if (threadIdx.x == 0) {
+    sdr[n] = 10.0 * log10(sy / (se + 1.1920928955078125e-07));   // np.finfo(np.float32).eps = 2^-23
+    if (energies) *reinterpret_cast<double2*>(energies + (size_t)n * 2) = make_double2(sy, se);
+  }
+}
+
+// ---- add_noise ---------------------------------------------------------------------------------------------------
+
+// The noise the reference lays under sample p of an utterance (speech length ls, noise length ln):
+//   ls >= ln: the buffer that doubles ceil((ls-ln)/ln) times, noise = (noise, noise * u_i): position p = q * ln + r holds
+//             noise[r] * prod(u_k for every bit k set in q);
+//   ls <  ln: noise[start + p].
+struct NoiseTile {
+  const float* row;
+  const double* gains;
+  const double* qtab;
+  int ls, ln, start, n_gains, q_lo;
+  bool tile, vec, table;
+
+  __device__ double gain_prod(int q) const {
+    double g = 1.0;
+    for (int k = 0; k < n_gains && (q >> k); ++k)
+      if ((q >> k) & 1) g *= gains[k];
+    return g;
+  }
+  __device__ double gain(int q) const { return table ? qtab[q - q_lo] : gain_prod(q); }
+
+  // Called by every thread of the workgroup (it holds a barrier); base = first sample of the slice, base < ls.
+  __device__ void init(const float* noise_row, int ls_, int ln_, int start_, const double* gains_row, int n_gains_,
+                       int base, double* qtab_lds) {
+    row = noise_row; ls = ls_; ln = ln_; gains = gains_row; n_gains = gains_row ? n_gains_ : 0; qtab = qtab_lds;
+    tile = ls >= ln;
+    vec = aligned16(noise_row);
+    start = 0; q_lo = 0; table = false;
+    if (!tile) {
+      const int room = ln - ls;
+      start = start_ < 0 ? 0 : (start_ > room ? room : start_);
+    } else if (ln > 0) {
+      const int end = base + kSlice < ls ? base + kSlice : ls;
+      q_lo = base / ln;
+      const int nq = (end - 1) / ln - q_lo + 1;
+      table = nq <= kQTable;     // otherwise ln is tiny: multiply out from the bits per element
+      if (table)
+        for (int j = threadIdx.x; j < nq; j += kThreads) qtab_lds[j] = gain_prod(q_lo + j);
+    }
+    __syncthreads();
+  }
+
+  // w[k] = the noise under sample p + k (fp64, exact products of an fp32 and the fp64 gain product); 0 past ls
+  __device__ void get4(int p, double w[4]) const {
+    if (!tile) {
+      float v[4];
+      const int i = start + p;
+      load4(row, i, start + ls, vec && (i & 3) == 0, v);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) w[k] = v[k];
+    } else if (ln <= 0) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) w[k] = 0.0;
+    } else {
+      int q = p / ln, r = p - q * ln;      // the one division of this 16-byte group
+      if (vec && (r & 3) == 0 && r + 4 <= ln) {
+        const float4 t = *reinterpret_cast<const float4*>(row + r);
+        const double g = gain(q);
+        w[0] = t.x * g; w[1] = t.y * g; w[2] = t.z * g; w[3] = t.w * g;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          w[k] = p + k < ls ? (double)row[r] * gain(q) : 0.0;
+          if (++r == ln) { r = 0; ++q; }
+        }
+      }
+    }
+  }
+};
+
+// grid (slices of Ls, N): ws[n][s] = (sum speech^2, sum tiled_noise^2) over slice s of [0, ls)
+__global__ __launch_bounds__(kThreads) void mix_partial_kernel(const float* __restrict__ speech, const int* __restrict__ speech_len,
+                                                               int Ls, const float* __restrict__ noise,
+                                                               const int* __restrict__ noise_len, int Ln,
+                                                               const int* __restrict__ start, const double* __restrict__ gains,
+                                                               int n_gains, double* __restrict__ ws, int slices) {
+  __shared__ double red[kWaves][2];
+  __shared__ double qtab[kQTable];
+  const int n = blockIdx.y, s = blockIdx.x;
+  const int ls = clamp_len(speech_len, n, Ls), ln = clamp_len(noise_len, n, Ln);
+  const int base = s * kSlice;
+  if (base >= ls) return;
+  const float* srow = speech + (size_t)n * Ls;
+  const bool svec = aligned16(srow);
+  NoiseTile nt;
+  nt.init(noise + (size_t)n * Ln, ls, ln, start && ls < ln ? start[n] : 0, gains ? gains + (size_t)n * n_gains : nullptr,
+          n_gains, base, qtab);
+  double ps = 0.0, pb = 0.0;
+#pragma unroll
+  for (int j = 0; j < kGroupsPerLane; ++j) {
+    const int p = base + (j * kThreads + threadIdx.x) * 4;
+    if (p < ls) {
+      float a[4];
+      double w[4];
+      load4(srow, p, ls, svec, a);
+      nt.get4(p, w);
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (p + k < ls) {
+          const double y = a[k];
+          ps += y * y;
+          pb += w[k] * w[k];
+        }
+    }
+  }
+  block_sum2<kWaves>(ps, pb, red);
+  if (threadIdx.x == 0) *reinterpret_cast<double2*>(ws + ((size_t)n * slices + s) * 2) = make_double2(ps, pb);
+}
+
+// grid (slices of Ls, N): every workgroup sums its utterance's partials itself (in slice order), then
+// mix = speech + sqrt(p_sig / 10^(snr/10) / p_back) * tiled_noise in fp64, rounded once at the fp32 store; 0 past ls.
+__global__ __launch_bounds__(kThreads) void mix_apply_kernel(const float* __restrict__ speech, const int* __restrict__ speech_len,
+                                                             int Ls, const float* __restrict__ noise,
+                                                             const int* __restrict__ noise_len, int Ln,
+                                                             const int* __restrict__ start, const double* __restrict__ gains,
+                                                             int n_gains, const double* __restrict__ ws, int slices,
+                                                             double snr_lin, float* __restrict__ mix) {
+  __shared__ double red[kWaves][2];
+  __shared__ double qtab[kQTable];
+  const int n = blockIdx.y, s = blockIdx.x;
+  const int ls = clamp_len(speech_len, n, Ls), ln = clamp_len(noise_len, n, Ln);
+  const int base = s * kSlice;
+  const float* srow = speech + (size_t)n * Ls;
+  float* orow = mix + (size_t)n * Ls;
+  const bool svec = aligned16(srow), ovec = aligned16(orow);
+  const bool live = base < ls;                      // uniform over the workgroup
+  double scale = 0.0;
+  NoiseTile nt;
+  if (live) {
+    double ps, pb;
+    sum_partials<kWaves>(ws, n, slices, num_slices(ls), ps, pb, red);
+    scale = sqrt(ps / snr_lin / pb);                // IEEE like numpy: p_back = 0 gives inf or nan
+    nt.init(noise + (size_t)n * Ln, ls, ln, start && ls < ln ? start[n] : 0, gains ? gains + (size_t)n * n_gains : nullptr,
+            n_gains, base, qtab);
+  }
+#pragma unroll
+  for (int j = 0; j < kGroupsPerLane; ++j) {
+    const int p = base + (j * kThreads + threadIdx.x) * 4;
+    if (p >= Ls) continue;
+    float o[4] = {0.f, 0.f, 0.f, 0.f};
+    if (live && p < ls) {
+      float a[4];
+      double w[4];
+      load4(srow, p, ls, svec, a);
+      nt.get4(p, w);
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (p + k < ls) o[k] = (float)((double)a[k] + scale * w[k]);
+    }
+    if (ovec && p + 4 <= Ls) {
+      *reinterpret_cast<float4*>(orow + p) = make_float4(o[0], o[1], o[2], o[3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (p + k < Ls) orow[p + k] = o[k];
+    }
+  }
+}
+
+}  // namespace eval
+}  // namespace rced

@@ -12,6 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib, model as _model, spec, weights as _weights
+from .metrics import AverageMeter
 
 
 class FullyCNNTrainer(object):
@@ -26,6 +27,7 @@ class FullyCNNTrainer(object):
         self.lr = float(lr)                        # fed for the next step (trainer.py:27)
         self.warmup_steps = float(warmup_steps)    # [training] warmup_steps
         self.device = int(device)
+        self.sdr_score = AverageMeter()            # trainer.py:34; valid() adds to it and never resets it, as there
         w = weights if weights is not None else _weights.initial_weights(self.variant, seed)
         self._blob_n = spec.num_weights(self.variant)
         # creat_graph (trainer.py:165-172): self.model = Model(is_training=True); self.pred = self.model(self.input_x).
@@ -70,6 +72,22 @@ class FullyCNNTrainer(object):
         tensor in -> cuda tensor out.  (The inference graph of tester.py / infer.py, which normalises with the moving
         statistics, is `build_model(net_work, False, weights=trainer.variables())`.)"""
         return self.model(input_x)
+
+    def valid(self, valid_loader, epoch, logger=None, nfft=512):
+        """trainer.py:252-338 over anything that yields the reference's 4-tuple (batch_mix, batch_clean, mix_sig,
+        clean_sig): engine.evaluate_pcm with valid_step as the forward (BatchNorm with each batch's own statistics),
+        every utterance's SDR into self.sdr_score; prints -- and logs, given a logger -- the reference's line with its
+        SDR field and returns the average.  PESQ, STOI and the wav files are not built."""
+        from .engine import evaluate_pcm
+        for _batch_mix, _batch_clean, mix_sig, clean_sig in valid_loader:
+            _, sdr = evaluate_pcm(self.valid_step, mix_sig, clean_sig, nfft, self.device)
+            for score in sdr:
+                self.sdr_score.update(float(score))
+        line = "Epoch: {}, Average sd_score: {:.4f}.\n".format(epoch, self.sdr_score.avg)
+        print(line)
+        if logger is not None:
+            logger.info(line)
+        return self.sdr_score.avg
 
     def fit_step(self, input_x, target_y):
         """One iteration of the loop body of trainer.py:212-215: step, then set lr for the next step."""

@@ -163,6 +163,39 @@ int rced_stft_ex(const float* pcm_dev, const int* lengths_dev, int N, int L, int
 int rced_istft_ex(const float* mag_dev, const float* phase_dev, int N, int T, int nfft, float* audio_dev,
                   int device, void* stream, int kernels);
 
+/* ---- evaluation loop (tester.py:92-167, trainer.py:252-338): the two numpy pieces around the rebuilt audio, for a
+ * ragged batch.  Streaming reductions without atomics: results are bit-identical run to run, and utterance n's result
+ * does not depend on N, on its neighbours, on its row index or on the row strides (kernels_eval.h).  Both keep a slice
+ * workspace per (device, stream) that only grows: after one call of a shape they allocate nothing and can be
+ * stream-captured. ---- */
+
+/* SDR.sdr (model_utils/utils.py:68-86) per utterance over its own length:
+ *   10 * log10( sum(y^2) / ( sum((y_pred - y)^2) + eps ) ),  eps = np.finfo(np.float32).eps = 2^-23.
+ * ref_dev [N, ref_stride] (y), est_dev [N, est_stride] (y_pred) float32, row n holds utterance n from column 0 -- two
+ * strides because the estimate is rced_istft's [N, (T+1)*128] buffer and the clean signals are [N, Lmax]: trimming is
+ * done by the length, never by a copy.  lengths_dev [N] int32 (device) or NULL (= min(ref_stride, est_stride) each); a
+ * length outside [0, min(ref_stride, est_stride)] is clamped into it.  sdr_dev [N] double (dB).  energies_dev: NULL or
+ * [N, 2] double receiving sum(y^2), sum((y_pred - y)^2).  Differences and sums in fp64.  y = 0 gives -inf, y_pred == y
+ * gives 10*log10(sum(y^2) / 2^-23), a length of 0 gives -inf, as numpy does.  Asynchronous. */
+int rced_sdr(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride,
+             const int* lengths_dev, int N, double* sdr_dev, double* energies_dev, int device, void* stream);
+
+/* AudioParser.add_noise (data_utils/data_loader.py:35-52) for a batch, in closed form (no doubling buffer):
+ *   speech_dev [N, Ls] + speech_len_dev [N] int32 (or NULL = Ls each); noise_dev [N, Ln] + noise_len_dev [N] (or NULL);
+ *   start_dev [N] int32: the crop offset np.random.randint(0, ln - ls) drew, read only where noise_len > speech_len
+ *     (NULL = 0; clamped into [0, ln - ls]);
+ *   gains_dev [N, n_gains] double: the np.random.uniform(0, 2) draws u_0.., read only where speech_len >= noise_len.
+ * The noise under sample p of an utterance with ls >= ln is noise[p % ln] * prod(u_k for every bit k set in p / ln)
+ * (only the first bit_length((ls-1)/ln) gains can matter; bits at or above n_gains count as gain 1), with ls < ln it is
+ * noise[start + p].  Then p_sig = sum(speech^2), p_back = sum(noise^2) over [0, ls) and
+ *   mix = speech + sqrt(p_sig / 10^(snr_db/10) / p_back) * noise,
+ * sums, gain products and the scale in fp64, one rounding at the fp32 store.  p_back = 0 follows IEEE (inf / nan) as
+ * numpy does.  mix_dev [N, Ls] float32, columns past speech_len written as 0.  Asynchronous. */
+int rced_mix_snr(const float* speech_dev, const int* speech_len_dev, int N, int Ls,
+                 const float* noise_dev, const int* noise_len_dev, int Ln,
+                 const int* start_dev, const double* gains_dev, int n_gains,
+                 double snr_db, float* mix_dev, int device, void* stream);
+
 /* ---- training step: FullyCNNTrainer.creat_graph + train_step,
  * model_utils/trainer.py:156-192, over Model(is_training=True).  Layer-by-layer, correctness first. ---- */
 typedef struct rced_trainer rced_trainer;

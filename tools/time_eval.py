@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""Times the evaluation loop's device pieces at BASELINE config-3 scale (256 utterances x 512 frames = 65,664 samples):
+rced_mix_snr and rced_sdr through the C ABI with HIP events on the launch stream (>= 20 warm-ups, >= 100 runs, the median
+of per-run times), beside the HBM floor their byte counts imply; and FullyCNNTester.evaluate_pcm's device part against
+the same chain without the score (stft_batch -> model -> istft_batch): the difference is what scoring costs.
+Prints one JSON line."""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+from fullycnnspeechenhancement_amd import audio, build_model  # noqa: E402
+from fullycnnspeechenhancement_amd import weights as _weights  # noqa: E402
+
+N, T = 256, 512
+L = (T - 1) * 128 + 256
+COPY_TBPS = 6.29          # measured device copy rate (read + write bytes)
+WARMUP, RUNS = 20, 100
+
+
+def timed_us(fn):
+    """Median device time of fn() in microseconds: one event pair per run, the L2 / Infinity Cache left as the previous run left it."""
+    for _ in range(WARMUP):
+        fn()
+    torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(RUNS)]
+    for a, b in ev:
+        a.record()
+        fn()
+        b.record()
+    torch.cuda.synchronize()
+    ts = sorted(a.elapsed_time(b) * 1e3 for a, b in ev)
+    return {"median_us": ts[len(ts) // 2], "min_us": ts[0], "p90_us": ts[int(0.9 * len(ts))]}
+
+
+def main():
+    g = torch.Generator(device="cuda").manual_seed(1)
+    speech = torch.randn((N, L), device="cuda", generator=g) * 0.1
+    noise = torch.randn((N, L), device="cuda", generator=g) * 0.05
+    out = {"N": N, "L": L}
+
+    # the mix reads speech and noise twice and writes once; the SDR reads two signals once
+    mix_bytes, sdr_bytes = 5 * N * L * 4, 2 * N * L * 4
+    r = timed_us(lambda: audio.mix_snr_batch(speech, noise, 5.0))
+    r.update(bytes=mix_bytes, floor_us=mix_bytes / COPY_TBPS / 1e6)
+    r["fraction_of_floor"] = r["floor_us"] / r["median_us"]
+    out["mix_snr_equal_lengths"] = r
+
+    short = noise[:, :24000].contiguous()                      # tiled: ls / ln = 2.7, two gains
+    gains = torch.rand((N, 2), dtype=torch.float64, device="cuda") * 2
+    r = timed_us(lambda: audio.mix_snr_batch(speech, short, 5.0, gains=gains))
+    r.update(bytes=(3 * N * L + 2 * N * 24000) * 4)
+    out["mix_snr_tiled_noise"] = r
+
+    mix = audio.mix_snr_batch(speech, noise, 5.0)
+    r = timed_us(lambda: audio.sdr_batch(speech, mix))
+    r.update(bytes=sdr_bytes, floor_us=sdr_bytes / COPY_TBPS / 1e6)
+    r["fraction_of_floor"] = r["floor_us"] / r["median_us"]
+    out["sdr"] = r
+
+    one = speech[:1].contiguous()                              # N = 1: a long signal alone (33 workgroups)
+    out["sdr_single_utterance"] = timed_us(lambda: audio.sdr_batch(one, mix[:1]))
+
+    model = build_model("FullyCNNV3", False, weights=_weights.synthetic_weights(3, seed=42))
+    lens = [L] * N
+
+    def chain():
+        mag, ph = audio.stft_batch(mix, lens)
+        return audio.istft_batch(model(mag), ph)
+
+    out["chain_stft_model_istft"] = timed_us(chain)
+    out["chain_with_sdr"] = timed_us(lambda: audio.denoise_and_score(model, mix, speech, lens))
+    out["scoring_cost_us"] = out["chain_with_sdr"]["median_us"] - out["chain_stft_model_istft"]["median_us"]
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
