@@ -127,19 +127,30 @@ void pack_v3(const rced_model* m, int form, std::vector<float>* wpack) {
       for (int lane = 0; lane < 64; ++lane)
         for (int e = 0; e < 8; ++e) {
           const int i = lane & 15, kq = lane >> 4;
-          for (int c = 0; c < 3; ++c) {
+          for (int c = 0; c < (allx6 ? 2 : 3); ++c) {
             const int tap = 4 * c + kq;
             const size_t base = (size_t)(c * 3) * 512 + lane * 8 + e;
             split3(tap < 9 ? w1x(tap, e, i) : 0.f, &d16[base], &d16[base + 512], &d16[base + 1024]);
           }
+          if (allx6) {
+            // tap 8 folded: pieces 6, 7 = the fragments F1, F2 whose k-quad selects a three-part PRODUCT (layer1_x6l): the part of
+            // W[tap 8] that lane (kq, row) multiplies with the input's part (h, h, m, l)[kq]: F1 = (l, m, m, h), F2 = (h, 0, h, 0)
+            unsigned short part[3];   // h, m, l
+            split3(w1x(8, e, i), &part[0], &part[1], &part[2]);
+            const size_t base = (size_t)6 * 512 + lane * 8 + e;
+            const int f1[4] = {2, 1, 1, 0};
+            d16[base] = part[f1[kq]];
+            d16[base + 512] = (kq & 1) ? (unsigned short)0 : part[0];
+          }
+          const int rem0 = allx6 ? 8 : 9;   // the remainder pass's first piece
           for (int c = 0; c < 4; ++c) {
             const int r = i >> 1, co = 16 + (i & 1), tap = 4 * c + kq - r;
-            const size_t base = (size_t)(9 + c * 3) * 512 + lane * 8 + e;
+            const size_t base = (size_t)(rem0 + c * 3) * 512 + lane * 8 + e;
             split3((tap >= 0 && tap < 9) ? w1x(tap, e, co) : 0.f, &d16[base], &d16[base + 512], &d16[base + 1024]);
           }
         }
-      put_shift(dst + v3::kG1XMain + v3::kG1XRem, 3 * blk + 0);
-      dst += v3::kG1X;
+      put_shift(dst + (allx6 ? v3::kG1AMain : v3::kG1XMain) + v3::kG1XRem, 3 * blk + 0);
+      dst += allx6 ? v3::kG1A : v3::kG1X;
     } else if (x6) {
       // register images [j][lane][4 floats]: float 4j + q of a lane = its fragment of K-step 4j + q (block 0) or element
       // (4j + q) & 1 of K-step (4j + q) >> 1 (blocks 1..4)
@@ -573,7 +584,7 @@ int upload(float** dev, const std::vector<float>& host) {   // *dev is set only 
 }  // namespace
 
 // tools/summarize_prof.py prints these next to a profile (the kernel-trace CSV reports 0 for dynamic LDS)
-static_assert(v3::MapA::kLdsBytes == 160448 && v3::MapF32::kLdsBytes == 163024, "update DYNAMIC_LDS in tools/summarize_prof.py");
+static_assert(v3::MapA::kLdsBytes == 159424 && v3::MapF32::kLdsBytes == 163024, "update DYNAMIC_LDS in tools/summarize_prof.py");
 #if RCED_V3_LEGACY_FORMS
 static_assert(v3::MapT::kLdsBytes == 163792 && v3::MapX6::kLdsBytes == 162976, "update DYNAMIC_LDS in tools/summarize_prof.py");
 #endif

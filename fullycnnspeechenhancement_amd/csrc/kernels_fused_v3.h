@@ -324,7 +324,13 @@ constexpr int kHZeroRow = kHRows - 1;            // the zero row out-of-range ta
 constexpr int kFinTRows = 160;                   // table rows: tap t at row t + 15, t = -15 .. 144
 constexpr int kFinTPart = kFinTRows * 16;        // bytes per part
 constexpr int kFinTFloats = 3 * kFinTPart / 4;   // 1,920
-constexpr int kATotal = 5 * kTBlockX;            // the weight stream of this form: every block in the bf16-pipe format
+// Layer 1's image in this form: the main pass's third chunk (tap 8 and three zero taps) is folded into TWO fragments whose k-quad selects
+// a PRODUCT of tap 8 instead of a tap (layer1_x6l): [chunk 0: 3 parts][chunk 1: 3 parts][F1][F2] = 8 pieces, then the remainder pass's 12
+constexpr int kG1AMain = 8 * 256;
+constexpr int kG1A = kG1AMain + kG1XRem + kShiftPerLayer;
+constexpr int kG1APieces = (kG1AMain + kG1XRem) / 256;   // 20 one-KiB pieces, the shifts behind them
+constexpr int kTBlockA = kG1A + kG2 + kW3T;
+constexpr int kATotal = 5 * kTBlockA;            // the weight stream of this form: every block in the bf16-pipe format
 template <>
 struct Map<3> {
   static constexpr bool X6 = true, kX6 = true, kFused = true, kAllX6 = true, kL1X6 = true;
@@ -348,8 +354,8 @@ struct Map<3> {
   static constexpr int kW3TOff = kWOff + kG2;
   static constexpr int kWRegions = 1;
   static constexpr int kB30Off = kWOff;
-  static constexpr int kW1Off = kW3TOff + kW3T;                                 // layer 1's image of the block (21 pieces + shifts)
-  static constexpr int kFinTOff = kW1Off + kG1X;                                // decode_final's tap table
+  static constexpr int kW1Off = kW3TOff + kW3T;                                 // layer 1's image of the block (20 pieces + shifts)
+  static constexpr int kFinTOff = kW1Off + kG1A;                                // decode_final's tap table
   static constexpr int kX0Off = kFinTOff + kFinTFloats;                         // the next tile's input rows, fp32 (convert_x0's source)
   static constexpr int kHOff = kB8Off, kFin128Off = kB8Off;                     // (other forms' buffers: make_lane's unused addresses)
   static constexpr int kEdgeOff = kX0Off + kX0Floats;
@@ -585,6 +591,7 @@ struct Lane {
   unsigned wr1rl;
   unsigned rd2, rd2b, rd2t, rd2tb, wr2; // layer 2 tile `wave` (/ + 8): B18 window start (b64 steps / tail), B30 output (F32 form)
   unsigned rd2m, rd2r, rd2rl;           // X6 form: this lane's fragment of chunk 0 in the h plane; its remainder rows ([h m] / [l])
+  unsigned rd1f;                        // all-x6 form: the row of tap 8 of main tile `role` in the plane of this lane's k-quad (layer1_x6l's folded fragments)
   unsigned rd1x, rd1xb, rd1xr, wr3p;    // fused form, layer 1 on the bf16 pipe: B8 plane row of main tile `role` (/ + 8) / remainder tile xr0, chunk 0; layers 2 + 3's output row
   unsigned rd2c, rd2cs;                 // fused form: this lane's four dwords of the last chunk (h part) and their byte stride from tile to tile
   unsigned rd3, rd3b, rd3t, rd3tb, wr3; // layer 3 pair tile `wave` (/ + 8): B30 window start (b64 steps / tail), B8 output
@@ -668,7 +675,11 @@ __device__ __forceinline__ Lane make_lane(float* lds, int wave, int lane, int xr
     L.rd1xb = L.rd1x + 128 * 16;
     L.rd1xr = B8P + (rpx - 4 + kq + kB8Pad) * 16;
     L.wr3p = B8P + (kS * (wave & 3) + 64 * (wave >> 2) + n + kB8Pad) * 16 + 4 * kq;
-    asm volatile("" : "+v"(L.rd1x), "+v"(L.rd1xb), "+v"(L.rd1xr), "+v"(L.wr3p));
+    // tap 8's folded fragments: every k-quad reads the SAME row (pixel + 8 - 4), each from the plane of its product's B part: h, h, m, l.
+    // Lanes of k-quads 0 and 1 share the read's lane groups, as do 2 and 3: equal planes are conflict-free, m and l (8,640 B = 12 slots
+    // of 16 bytes mod 16 apart) meet two-way on four slots
+    L.rd1f = L.rd1x + (8 - kq) * 16 + (kq < 2 ? 0 : kq - 1) * kB8PlaneBytes;
+    asm volatile("" : "+v"(L.rd1x), "+v"(L.rd1xb), "+v"(L.rd1xr), "+v"(L.wr3p), "+v"(L.rd1f));
   }
   {
     const unsigned H = lds_addr(lds + M::kHOff);
@@ -1729,7 +1740,7 @@ __global__ __launch_bounds__(RCED_V3_LB) __attribute__((target("no-packed-fp32-o
         // What is fetched for later once the layer's first operand reads are in flight.  F32 form: layer 2's packet.  X6 form:
         // layer 3's packet (its one LDS region is dead until then).
         auto dma = [&] {
-          if constexpr (M::kFused) packet_dma<kG2 + kW3T>(wsrc + (M::kAllX6 || (kL1X && blk > 0) ? kG1X : kG1), WREG(0), wave, lane);   // layer 2's and layer 3's images, adjacent in the stream
+          if constexpr (M::kFused) packet_dma<kG2 + kW3T>(wsrc + (M::kAllX6 ? kG1A : kL1X && blk > 0 ? kG1X : kG1), WREG(0), wave, lane);   // layer 2's and layer 3's images, adjacent in the stream
           else if constexpr (M::kX6) packet_dma<kW3>(wsrc + kG1 + kG2, WREG(0), wave, lane);
           else packet_dma<kW2>(wsrc + kW1, WREG(wcur ^ 1), wave, lane);
         };
@@ -1757,7 +1768,7 @@ __global__ __launch_bounds__(RCED_V3_LB) __attribute__((target("no-packed-fp32-o
         };
         auto sp1x = [&](auto kc) {   // blocks 1..4 with layer 1 on the bf16 pipe: k = 12..20: layer 2's M-tile 0 (three loads per slot)
           constexpr int k = decltype(kc)::value;
-          if constexpr (kL1X && k >= 12 && k < 21 && (RCED_T_A2REG == 1 || RCED_T_A2REG == 2)) wload(IC<k - 12 + 7>{}, gofs, voff1, kG1X);
+          if constexpr (kL1X && k >= 12 && k < 21 && (RCED_T_A2REG == 1 || RCED_T_A2REG == 2)) wload(IC<k - 12 + 7>{}, gofs, voff1, M::kAllX6 ? kG1A : kG1X);
         };
         if constexpr (kL1X) {
           if constexpr (which == 1) layer1<M, true>(L, wb, A1, A1r, w1, dma, sp1, late DET_PASS);
@@ -1820,7 +1831,7 @@ __global__ __launch_bounds__(RCED_V3_LB) __attribute__((target("no-packed-fp32-o
           }
         };
         auto dma1 = [&] {   // layer 1 on the bf16 pipe: the next block's layer-1 image into the (now dead) input-row area and the H image's bins
-          if constexpr (kL1X) a1x_dma<M>(wsrc + (blk == 0 && !M::kAllX6 ? kTBlock : kTBlockX), lds, wave, lane);
+          if constexpr (kL1X) a1x_dma<M>(wsrc + (M::kAllX6 ? kTBlockA : blk == 0 ? kTBlock : kTBlockX), lds, wave, lane);
         };
         layer23<M, false>(P, L, lds0, lds_addr(WREG(0)), A2, blk, wave, 0x80000000u | epoch, sk1, sk2, sp, dma1 DET_PASS);
         STAMP_MATH(2);
@@ -1847,8 +1858,8 @@ __global__ __launch_bounds__(RCED_V3_LB) __attribute__((target("no-packed-fp32-o
         layer_end_sync();
         STAMP_WAIT(2);
       }
-      wsrc += M::kAllX6 || (kL1X && blk > 0) ? kTBlockX : kBlockFloats;
-      gofs += M::kAllX6 || (kL1X && blk > 0) ? kTBlockX : kBlockFloats;
+      wsrc += M::kAllX6 ? kTBlockA : kL1X && blk > 0 ? kTBlockX : kBlockFloats;
+      gofs += M::kAllX6 ? kTBlockA : kL1X && blk > 0 ? kTBlockX : kBlockFloats;
     }
     FinA finA;
     if constexpr (M::kAllX6) {   // ---- block 4's layers 2 + 3 (its output goes to decode_final's image H'), then decode_final and the next tile's planes

@@ -43,7 +43,9 @@
                        // kernel's 1,218 static MFMAs disappear), 4 = no split arithmetic, 8 = layer 2's B fragments read once per tile,
                        // 256 = a third of layer 1's B reads, 512 = no weight transfers, 1024 = all-x6 form without bin 128's shared tail (its
                        // three jobs and the hand-off; bin 128's epilogue still runs: prices the tail).  The step-0 bound (-6.2 %) was measured
-                       // with an EARLIER form of this bit, before the tail existed: waves 4..7 kept tiles 4..8 and skipped X4, Y4 and finish(4), 4096 = layer 1 without its main tiles' epilogues, 8192 = layer 1's pair jobs only
+                       // with an EARLIER form of this bit, before the tail existed: waves 4..7 kept tiles 4..8 and skipped X4, Y4 and finish(4), 4096 = layer 1 without its main tiles' epilogues, 8192 = layer 1's pair jobs only,
+                       // 32768 = all-x6 form, layer 1's main pass without tap 8 (its folded chunk, F1 and F2, and their B read: 12 MFMAs per tile; measured on the
+                       // unfolded kernel, without its third chunk, it was the bound of the fold: profiles/NOTES.md)
 #endif
 #if (RCED_T_EXP != 0 || RCED_X6_EXP != 0) && !defined(RCED_TIMING_ONLY)
 #error "RCED_T_EXP / RCED_X6_EXP builds compute wrong results: timing experiments only (tools/mkexp.sh ... -DRCED_TIMING_ONLY -DRCED_T_EXP=...)"
@@ -113,6 +115,10 @@ __device__ __forceinline__ void shift_add(f32x4 pj, float& p0, float& p1, float&
   if constexpr (2 * J + 1 < 9) tap_add<3 - 2 * J>(pj.w, p1, c1, n1);
 }
 
+template <class M>
+struct MapTag {
+  typedef M type;
+};
 template <class M>
 constexpr int tail_off() {   // all-x6 form: the shared tail's LDS area (see layer23)
   if constexpr (M::kAllX6) return M::kTailOff;
@@ -375,28 +381,29 @@ __device__ __forceinline__ void layer23(const Params& P, const Lane& L, unsigned
   const int tln = (int)(L.a4 >> 2), tn = tln & 15, tkq = tln >> 4, tf = tn & 3;
   const unsigned tb = lds0 + 4 * tail_off<M>();
   constexpr int kT3 = 2 * 3 * 16 * 8, kTFlag = kT3 + 4 * 5 * 4 * 8;   // byte offsets: layer 3's partials [frame][tap - 4][kq] x 8 B, the four flags
-  // (the unnamed `auto` makes the lambda a template: its body, which names members only Map<3> has, is instantiated where it is
-  // called, inside `if constexpr (M::kAllX6)`)
-  auto tail2 = [&](auto, int mt) {   // layer 2's M-tile mt -> its split pieces 2 mt, 2 mt + 1: [mt][part][kq][frame] x 8 B
-    const unsigned PL = lds0 + 4 * M::kB18Off, px = kS * tf + 64;
-    const unsigned rm = PL + (tkq & 1) * M::kHalfBytes + (px + (tkq >> 1)) * 16;
-    const unsigned rc = tkq < 2 ? rm + 64 + 4 * M::kTileB18 : PL + M::kRemOff + (px + 4 * (tkq & 1)) * 4 + 4 * 64;
+  // (the map comes in through the lambda's own template parameter: its body, which names members only Map<3> has, is then looked up
+  // where it is called, inside `if constexpr (M::kAllX6)` -- named as M they are looked up with layer23<Map<2>> too)
+  auto tail2 = [&](auto mapc, int mt) {   // layer 2's M-tile mt -> its split pieces 2 mt, 2 mt + 1: [mt][part][kq][frame] x 8 B
+    using MA = typename decltype(mapc)::type;
+    const unsigned PL = lds0 + 4 * MA::kB18Off, px = kS * tf + 64;
+    const unsigned rm = PL + (tkq & 1) * MA::kHalfBytes + (px + (tkq >> 1)) * 16;
+    const unsigned rc = tkq < 2 ? rm + 64 + 4 * MA::kTileB18 : PL + MA::kRemOff + (px + 4 * (tkq & 1)) * 4 + 4 * 64;
     const unsigned am = a2 + (unsigned)mt * 3072u;
     f32x4 acc = mt ? sh2[1] : sh2[0];
     static_for<0, 3>([&](auto cc) {
       constexpr int c = decltype(cc)::value;
       Parts b;
       if constexpr (c < 2) {
-        b.h = lds_ld<s16x8>(rm, 4 * M::kTileB18 + 32 * c);
-        b.m = lds_ld<s16x8>(rm, 4 * M::kTileB18 + 32 * c + M::kPlaneBytes);
-        b.l = lds_ld<s16x8>(rm, 4 * M::kTileB18 + 32 * c + 2 * M::kPlaneBytes);
+        b.h = lds_ld<s16x8>(rm, 4 * MA::kTileB18 + 32 * c);
+        b.m = lds_ld<s16x8>(rm, 4 * MA::kTileB18 + 32 * c + MA::kPlaneBytes);
+        b.l = lds_ld<s16x8>(rm, 4 * MA::kTileB18 + 32 * c + 2 * MA::kPlaneBytes);
       } else {
         u32x4 h, m, l;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           h[i] = lds_ld<unsigned>(rc, 4 * i);
-          m[i] = lds_ld<unsigned>(rc, 4 * i + M::kPlaneBytes);
-          l[i] = lds_ld<unsigned>(rc, 4 * i + 2 * M::kPlaneBytes);
+          m[i] = lds_ld<unsigned>(rc, 4 * i + MA::kPlaneBytes);
+          l[i] = lds_ld<unsigned>(rc, 4 * i + 2 * MA::kPlaneBytes);
         }
         b.h = __builtin_bit_cast(s16x8, h);
         b.m = __builtin_bit_cast(s16x8, m);
@@ -446,7 +453,7 @@ __device__ __forceinline__ void layer23(const Params& P, const Lane& L, unsigned
   // all-x6 form: tiles 4..7 (X0 X1 X2 YY01 X3 YY23) and the shared tail's partials of bin 128
   const int tw = wave - RCED_T_TAILW;   // the tail's waves: 0, 1 layer 2, 2, 3 layer 3
   if constexpr (M::kAllX6) {
-    if (tail && (tw == 0 || tw == 1)) tail2(i0, tw);
+    if (tail && (tw == 0 || tw == 1)) tail2(MapTag<M>{}, tw);
   }
   ldX(i0, i0);
   pin();
@@ -517,7 +524,7 @@ __device__ __forceinline__ void layer23(const Params& P, const Lane& L, unsigned
 // Input: the 8-channel tensor as three bf16 planes [pixel][8] (16-byte rows: one pixel's channels = one octet of the K axis),
 // written by layers 2 + 3's epilogue.  K = 72 in three K = 32 chunks: k-slot 8kq + e = tap 4c + kq, channel e (taps 9..11: zero
 // weights): a lane's B fragment of a chunk is ONE aligned ds_read_b128 per part.  Channels 0..15 = one M-tile, 18 MFMAs per
-// 16-pixel tile; channels 16, 17 by the remainder pass (rows = 8 pixel phases x 2 channels, K = 16 window taps x 8 channels = four
+// 16-pixel tile (all-x6 form: 14, the third chunk folded into two MFMAs, see layer1_x6l); channels 16, 17 by the remainder pass (rows = 8 pixel phases x 2 channels, K = 16 window taps x 8 channels = four
 // chunks, 24 MFMAs per tile of 16 columns x SEVEN pixels: phase 7's rows are dropped -- a column stride of 7 rows = 112 bytes keeps
 // its reads free of bank conflicts (make_lane), 8 rows = 128 bytes made every one of them 8-way conflicted).
 __device__ __forceinline__ Parts b8_load(unsigned rd, int off) {
@@ -533,12 +540,12 @@ __device__ __forceinline__ Parts b8_load(unsigned rd, int off) {
 }
 
 // ---- its A fragments live in LDS ---------------------------------------------------------------------------------------------
-// The 21 one-KiB pieces of a block's layer-1 image (main pass 9, remainder pass 12) + its shifts are LDS-DMA'd during the PREVIOUS
+// The 21 one-KiB pieces of a block's layer-1 image (main pass 9, remainder pass 12; all-x6 form: 8 + 12, see layer1_x6l) + its shifts are LDS-DMA'd during the PREVIOUS
 // block's layers 2 + 3 into areas that are dead from then until this layer 1 has run: the input rows of the first layer (pieces 0..4 +
 // the shifts) and the bins of decode_final's image (four pieces per frame; its zero pads are not touched).  No weight registers at
 // all: a version with the fragments in registers (42 + 48, loaded from global memory like the first layer's) was parity-exact and
 // spilled (192 .. 336 B, the skip arrays reloaded inside the fused phase's epilogues: 7.7 ms against 6.15 for this one).
-// (All-x6 form: a region of its own, the 21 pieces back to back and the shifts behind them.)
+// (All-x6 form: a region of its own, the 20 pieces back to back and the shifts behind them.)
 template <class M>
 constexpr int a1x_off(int i) {   // byte offset of piece i from the start of LDS
   if constexpr (M::kAllX6) return M::kW1Off * 4 + i * 1024;
@@ -547,7 +554,7 @@ constexpr int a1x_off(int i) {   // byte offset of piece i from the start of LDS
 }
 template <class M>
 constexpr int a1x_shift_off() {
-  if constexpr (M::kAllX6) return M::kW1Off * 4 + 21 * 1024;
+  if constexpr (M::kAllX6) return M::kW1Off * 4 + kG1APieces * 1024;
   else return M::kX0Off * 4 + 5 * 1024;
 }
 #if RCED_V3_LEGACY_FORMS
@@ -555,17 +562,19 @@ static_assert(a1x_shift_off<MapT>() + 128 <= (MapT::kX0Off + kX0Floats) * 4 && a
               a1x_off<MapT>(8) % 16 == 0 && a1x_off<MapT>(9) % 16 == 0 && a1x_off<MapT>(13) % 16 == 0 && a1x_off<MapT>(17) % 16 == 0,
               "layer 1's LDS-resident images: inside the input-row area / the real bins of the H image, 16-byte aligned");
 #endif
-// the DMA of one block's image (src = its first float in the weight stream): 22 chunks over the 8 waves
+// the DMA of one block's image (src = its first float in the weight stream): its pieces + the shifts = 22 chunks (all-x6 form: 21)
+// over the 8 waves
 template <class M>
 __device__ __forceinline__ void a1x_dma(const float* src, float* lds, int wave, int lane) {
+  constexpr int kPieces = M::kAllX6 ? kG1APieces : 21;
   lane = opaque(lane);
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const int ci = wave + 8 * k;
-    if (ci < 21) {
+    if (ci < kPieces) {
       lds_dma16s(src + ci * 256, (unsigned)lane * 16u, lds + a1x_off<M>(ci) / 4);
-    } else if (ci == 21) {
-      if (lane < 8) lds_dma16s(src + 21 * 256, (unsigned)lane * 16u, lds + a1x_shift_off<M>() / 4);
+    } else if (ci == kPieces) {
+      if (lane < 8) lds_dma16s(src + kPieces * 256, (unsigned)lane * 16u, lds + a1x_shift_off<M>() / 4);
     }
   }
 }
@@ -592,16 +601,106 @@ __device__ __forceinline__ void layer1_x6l(const Lane& L, unsigned lds0, int rol
   // issuing its reads waits a full LDS round trip with nothing of its own to issue (the single-tile and remainder jobs ran at a third
   // of their MFMA rate); behind 26 .. 52 VALU of split + stores the reads have landed when the job begins.
   constexpr bool kPF = M::kAllX6 && RCED_T_L1PF;
+  // All-x6 form: the main pass's third chunk is FOLDED.  Tap 8's six three-part products are 6 x 8 = 48 k-slots; with the k-quad selecting
+  // the product instead of the tap they fill two K = 32 MFMAs (the chunk as it was: six, each with one useful k-quad of four):
+  //             kq 0    kq 1    kq 2    kq 3        B fragment: the row of pixel n + tap 8 in plane (h, h, m, l)[kq] -- ONE ds_read_b128
+  //   F1  A =   l       m       m       h           (L.rd1f) serves both; where F2's A is zero its lanes still read that pixel's row, so a
+  //   F2  A =   h       0       h       0           non-finite input reaches the same tiles as before
+  // in the order of l2x_mma (m.m, l.h, h.l, m.h | h.m, h.h: small products first).  Pieces 6, 7 of the image (pack_v3); the remainder
+  // pass's start at 8.  A main tile: 14 MFMAs instead of 18.
+  constexpr bool kFold = M::kAllX6;
+  constexpr int kRemPiece = kFold ? 8 : 9;
+  auto ldar = [&](auto cc, s16x8 (&a)[3]) {   // the remainder pass's fragments of chunk c
+    constexpr int c = decltype(cc)::value;
+    a[0] = a1x_ld<M, kRemPiece + 3 * c>(aX, aH);
+    a[1] = a1x_ld<M, kRemPiece + 3 * c + 1>(aX, aH);
+    a[2] = a1x_ld<M, kRemPiece + 3 * c + 2>(aX, aH);
+  };
   const bool has_single = role < 2 || role == 7, has_rem = role >= 4;
   const unsigned rd_single = L.rd1x + (role == 0 ? 32 : role == 1 ? 30 : 16) * 256;
   Parts nb;
   s16x8 na[3];
-  auto prefetch = [&](unsigned rd, int aoff) {   // aoff: byte offset of the job's first piece group (single tile: pieces 0..2, remainder: 9..11)
+  auto prefetch = [&](unsigned rd, int aoff) {   // aoff: byte offset of the job's first piece group (single tile: pieces 0..2, remainder: its first three)
     nb = b8_load(rd, 0);
 #pragma unroll
     for (int q = 0; q < 3; ++q) na[q] = lds_ld<s16x8>(aX + aoff, q * 1024);
   };
-  {
+  if constexpr (kFold) {   // pair jobs, folded form: per pair a slot of 12 MFMAs (chunk 0) and one of 16 (chunk 1, then F1 and F2)
+    Parts b[2][2];     // [chunk][tile]
+    s16x8 bf[2];       // tap 8's B fragment of the two tiles
+    s16x8 a[2][3], af[2];   // the main pass's eight fragments, read once per job
+    f32x4 acc[2][2];   // [pair][tile]
+    const bool two = role != 7;
+    const bool g1 = tile_has_gap(role + 8), g2 = tile_has_gap(role + 16), g3 = tile_has_gap(role + 24);
+    auto ld = [&](auto ic) {   // slot i = (pair p, chunk c)'s operands; chunk 1's come with the folded chunk's
+      constexpr int i = decltype(ic)::value, p = i / 2, c = i % 2;
+      if constexpr (p == 0) lda(IC<c>{}, a[c]);
+      b[c][0] = b8_load(L.rd1x, 2 * p * kTR + 64 * c);
+      b[c][1] = b8_load(L.rd1xb, 2 * p * kTR + 64 * c);
+      if constexpr (c == 1) {
+        if constexpr (p == 0) {
+          af[0] = a1x_ld<M, 6>(aX, aH);
+          af[1] = a1x_ld<M, 7>(aX, aH);
+        }
+        if (RCED_T_EXP & 32768) return;
+        bf[0] = lds_ld<s16x8>(L.rd1f, 2 * p * kTR);
+        bf[1] = lds_ld<s16x8>(L.rd1f, 2 * p * kTR + 128 * 16);
+      }
+    };
+    auto slot = [&](auto ic) {
+      constexpr int i = decltype(ic)::value, p = i / 2, c = i % 2;
+      if constexpr (c == 0) acc[p][0] = acc[p][1] = sh;
+      mma2(a[c], b[c][0], acc[p][0], a[c], b[c][1], acc[p][1]);
+      if (c == 1 && !(RCED_T_EXP & 32768)) {   // the two tiles' chains in lockstep, as in mma2
+        acc[p][0] = mfma32(af[0], bf[0], acc[p][0]);
+        acc[p][1] = mfma32(af[0], bf[1], acc[p][1]);
+        acc[p][0] = mfma32(af[1], bf[0], acc[p][0]);
+        acc[p][1] = mfma32(af[1], bf[1], acc[p][1]);
+      }
+      if constexpr (p == 0) static_for<0, (c == 0 ? 4 : 5)>([&](auto qc) { sp(IC<12 + 4 * c + decltype(qc)::value>{}); });
+      if constexpr (i == 2) l1_store<M>(L, acc[0][0], L.wr1, 0, false, kVMain);
+      if constexpr (i == 3) l1_store<M>(L, acc[0][1], L.wr1, kTW, g1, kVMain + 1);
+      interleave<(c == 1 && !(RCED_T_EXP & 32768) ? 16 : 12), 3>();
+    };
+    ld(IC<0>{});
+    pin();
+    if (!(RCED_T_EXP & 512)) pre();
+    pin();
+    static_for<0, 2>([&](auto ic) {
+      constexpr int i = decltype(ic)::value;
+      if constexpr (i < 1) ld(IC<i + 1>{});
+      else if (two) ld(IC<2>{});
+      pin();
+      slot(ic);
+      pin();
+      DETX(i);
+    });
+    if (two) {
+      static_for<2, 4>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        if constexpr (i < 3) ld(IC<i + 1>{});
+        pin();
+        slot(ic);
+        pin();
+        DETX(i);
+      });
+      if constexpr (kPF) {
+        if (has_single) prefetch(rd_single, 0);
+        else if (has_rem) prefetch(L.rd1xr, kRemPiece * 1024);
+        pin();
+      }
+      l1_store<M>(L, acc[1][0], L.wr1, 2 * kTW, g2, kVMain + 2);
+      l1_store<M>(L, acc[1][1], L.wr1, 3 * kTW, g3, kVMain + 3);
+      DETX(6);
+    } else {
+      if constexpr (kPF) {
+        prefetch(rd_single, 0);   // role 7: its single tile is next
+        pin();
+      }
+      l1_store<M>(L, acc[0][0], L.wr1, 0, false, 0);
+      l1_store<M>(L, acc[0][1], L.wr1, kTW, false, 0);
+    }
+  } else {   // pair jobs, legacy fused form: three chunks of 12 MFMAs per pair
     Parts b[2][2];
     s16x8 a[3][3];     // the main pass's nine fragments, read once per job
     f32x4 acc[2][2];   // [pair][tile]
@@ -646,7 +745,7 @@ __device__ __forceinline__ void layer1_x6l(const Lane& L, unsigned lds0, int rol
       });
       if constexpr (kPF) {
         if (has_single) prefetch(rd_single, 0);
-        else if (has_rem) prefetch(L.rd1xr, 9 * 1024);
+        else if (has_rem) prefetch(L.rd1xr, kRemPiece * 1024);
         pin();
       }
       l1_store<M>(L, acc[1][0], L.wr1, 2 * kTW, g2, kVMain + 2);
@@ -681,16 +780,26 @@ __device__ __forceinline__ void layer1_x6l(const Lane& L, unsigned lds0, int rol
     pin();
     static_for<0, 3>([&](auto cc) {
       constexpr int c = decltype(cc)::value;
-      if constexpr (c < 2) {
+      if constexpr (kFold && c == 1) {   // the folded chunk: one B read, two fragments
+        if (!(RCED_T_EXP & 32768)) b[0].h = lds_ld<s16x8>(L.rd1f + dt * 256, 0);
+        a[0][0] = a1x_ld<M, 6>(aX, aH);
+        a[0][1] = a1x_ld<M, 7>(aX, aH);
+      } else if constexpr (c < 2) {
         b[(c + 1) & 1] = b8_load(rd, 64 * (c + 1));
         lda(IC<c + 1>{}, a[(c + 1) & 1]);
       }
       pin();
-      acc = l2x_mma(a[c & 1], b[c & 1], acc);
+      if ((RCED_T_EXP & 32768) && c == 2) {
+      } else if constexpr (kFold && c == 2) {
+        acc = mfma32(a[0][0], b[0].h, acc);
+        acc = mfma32(a[0][1], b[0].h, acc);
+      } else {
+        acc = l2x_mma(a[c & 1], b[c & 1], acc);
+      }
       pin();
     });
     if constexpr (kPF) {
-      if (has_rem) prefetch(L.rd1xr, 9 * 1024);   // role 7: its first remainder tile is next
+      if (has_rem) prefetch(L.rd1xr, kRemPiece * 1024);   // role 7: its first remainder tile is next
       pin();
     }
     l1_store<M>(L, acc, L.wr1 + dt * M::kTileB18, 0, false, 0);
@@ -713,14 +822,14 @@ __device__ __forceinline__ void layer1_x6l(const Lane& L, unsigned lds0, int rol
         a[0][2] = na[2];
       } else {
         b[0] = b8_load(rdr, 0);
-        lda(IC<3>{}, a[0]);
+        ldar(IC<0>{}, a[0]);
       }
       pin();
       static_for<0, 4>([&](auto cc) {
         constexpr int c = decltype(cc)::value;
         if constexpr (c < 3) {
           b[(c + 1) & 1] = b8_load(rdr, 64 * (c + 1));
-          lda(IC<3 + c + 1>{}, a[(c + 1) & 1]);
+          ldar(IC<c + 1>{}, a[(c + 1) & 1]);
         }
         pin();
         acc = l2x_mma(a[c & 1], b[c & 1], acc);

@@ -7,7 +7,7 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 name=$1; units=$2; shift 2
 mkdir -p $R/exp/obj_$name
 objs=""
-for u in rced_api kernels_fused audio_api train_api train_mfma_v2; do
+for u in rced_api kernels_fused audio_api eval_api train_api train_mfma_v2; do
   if [[ " $units " == *" $u "* ]]; then
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function "$@" -c -o $R/exp/obj_$name/$u.o $R/fullycnnspeechenhancement_amd/csrc/$u.hip &
     objs="$objs $R/exp/obj_$name/$u.o"

@@ -83,7 +83,7 @@ def code_object_resources():
 
 # dynamic LDS of the CR-CED kernels (bytes): the launch's third parameter = Map<FORM>::kLdsBytes of kernels_fused_v3.h; kept here by hand and
 # pinned by static_asserts in kernels_fused.hip ("tools/summarize_prof.py prints these")
-DYNAMIC_LDS = {"Map<3>": 160448, "Map<2>": 163792, "Map<1>": 162976, "Map<0>": 163024}
+DYNAMIC_LDS = {"Map<3>": 159424, "Map<2>": 163792, "Map<1>": 162976, "Map<0>": 163024}
 
 WARMUP_DISPATCHES = int(os.environ.get("TRACE_WARMUP", "3"))   # the trace pass's --warmup (tools/profile.sh)
 
