@@ -133,6 +133,41 @@ def sdr_batch(clean, estimate, lengths=None):
     return out
 
 
+STOI_RATES = (8000, 10000)
+
+
+def stoi_batch(clean, estimate, lengths=None, sample_rate=8000, detail=False):
+    """STOI (Taal et al. 2011; the reference's pystoi.stoi(clean, denoise, sr, extended=False), tester.py:92-167) per utterance
+    on the device, as DESIGN.md "STOI" specifies it.  clean [N, Lc], estimate [N, Le], lengths: as in sdr_batch (the estimate
+    may be istft_batch's buffer as it is).  sample_rate: 8000 (resampled to 10 kHz on the device) or 10000.
+    Returns torch.float64 [N] on the device, current stream; with detail=True also torch.int32 [N, 3]: frames at 10 kHz,
+    frames kept by the 40 dB silent-frame removal, 30-frame segments (0 segments: the score is 1e-5)."""
+    import torch
+    if int(sample_rate) not in STOI_RATES:
+        raise ValueError("sample_rate must be 8000 or 10000, got %r" % (sample_rate,))
+    clean, estimate = _rows(clean, "clean"), _rows(estimate, "estimate")
+    n = int(clean.shape[0])
+    if int(estimate.shape[0]) != n or estimate.device != clean.device:
+        raise ValueError("clean and estimate must hold the same number of utterances on one device")
+    dev = clean.device
+    cap = min(int(clean.shape[1]), int(estimate.shape[1]))
+    lens = _host_ints(lengths, n, "lengths")
+    if lens is not None and any(v < 0 or v > cap for v in lens):
+        raise ValueError("lengths must lie in [0, %d]" % cap)
+    sc, se = _row_stride(clean), _row_stride(estimate)
+    if lens is None and min(sc, se) != cap:
+        lens = [cap] * n                                  # a strided view: the row's width, not its stride, bounds it
+    ldev = torch.tensor(lens, dtype=torch.int32, device=dev) if lens is not None else None
+    out = torch.empty((n,), dtype=torch.float64, device=dev)
+    det = torch.empty((n, 3), dtype=torch.int32, device=dev) if detail else None
+    if n:
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.load().rced_stoi(clean.data_ptr(), sc, estimate.data_ptr(), se,
+                                         ldev.data_ptr() if ldev is not None else None, n, int(sample_rate), out.data_ptr(),
+                                         det.data_ptr() if det is not None else None, dev.index, st))
+    return (out, det) if detail else out
+
+
 def gains_needed(len_speech, len_noise):
     """How many of add_noise's uniform(0, 2) draws can reach the first len_speech samples: bit_length((ls - 1) // ln)."""
     if len_speech < len_noise or len_speech < 1:
@@ -196,14 +231,18 @@ def mix_snr_batch(speech, noise, snr, speech_lengths=None, noise_lengths=None, s
     return mix
 
 
-def denoise_and_score(forward, mix, clean, lengths, nfft=512, kernels="x6"):
-    """The device core of the evaluation loop (tester.py:100-146 / trainer.py:260-307 without PESQ / STOI / wav files):
-    STFT of the mixtures -> forward (device [N, T, 129, 1] -> same) -> ISTFT rebuild -> SDR of every rebuilt row against
-    its clean row over its own length.  mix, clean: torch.cuda float32 [N, L] zero-padded; lengths: N sample counts.
-    Returns (audio [N, (T+1)*128] on the device -- the caller trims row n to lengths[n] --, sdr torch.float64 [N])."""
+def denoise_and_score(forward, mix, clean, lengths, nfft=512, kernels="x6", stoi=False):
+    """The device core of the evaluation loop (tester.py:100-146 / trainer.py:260-307 without PESQ / wav files):
+    STFT of the mixtures -> forward (device [N, T, 129, 1] -> same) -> ISTFT rebuild -> SDR (and, with stoi=True, STOI) of
+    every rebuilt row against its clean row over its own length.  mix, clean: torch.cuda float32 [N, L] zero-padded;
+    lengths: N sample counts.
+    Returns (audio [N, (T+1)*128] on the device -- the caller trims row n to lengths[n] --, sdr torch.float64 [N]), with
+    stoi=True (audio, sdr, stoi torch.float64 [N])."""
     mag, phase = stft_batch(mix, lengths, kernels=kernels)
     pred = forward(mag)
     out = istft_batch(pred, phase, nfft, kernels=kernels)
+    if stoi:
+        return out, sdr_batch(clean, out, lengths), stoi_batch(clean, out, lengths, SAMPLE_RATE)
     return out, sdr_batch(clean, out, lengths)
 
 

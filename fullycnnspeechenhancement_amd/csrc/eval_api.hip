@@ -2,11 +2,14 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstring>
 #include <map>
 #include <mutex>
+#include <vector>
 
 #include "../../include/rced.h"
 #include "kernels_eval.h"
+#include "kernels_stoi.h"
 #include "rced_internal.h"
 
 using namespace rced;
@@ -29,7 +32,8 @@ struct Workspace {
   double* p = nullptr;
   size_t bytes = 0;
 };
-std::map<void*, Workspace> g_ws[kMaxDevices];
+enum { kWsSlices = 0, kWsStoi = 1 };      // STOI keeps a buffer of its own: it never moves the one SDR / the mix captured
+std::map<void*, Workspace> g_ws[2][kMaxDevices];
 std::mutex g_mu;
 
 int check_device(int device) {
@@ -40,9 +44,9 @@ int check_device(int device) {
   return RCED_OK;
 }
 
-int workspace(int device, void* stream, size_t bytes, double** out) {
+int workspace(int device, void* stream, size_t bytes, double** out, int which = kWsSlices) {
   std::lock_guard<std::mutex> lk(g_mu);
-  Workspace& w = g_ws[device][stream];
+  Workspace& w = g_ws[which][device][stream];
   if (w.bytes < bytes) {
     if (w.p) {
       HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));   // an earlier call may still read it
@@ -66,9 +70,173 @@ struct DeviceGuard {
   ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
+// ---- STOI tables: built on the host once per process, uploaded once per device ---------------------------------------------------
+struct StoiTables {
+  double* tab = nullptr;             // resampler taps [0, 365), first window [368, 624)
+  unsigned short* apack = nullptr;   // the windowed DFT matrix, three bf16 parts, MFMA fragment order
+};
+StoiTables g_stoi[kMaxDevices];
+std::mutex g_stoi_mu;
+
+double bessel_i0(double x) {         // power series: converges to the last bit in < 30 terms for x <= 6
+  double s = 1.0, t = 1.0;
+  const double q = x * x / 4.0;
+  for (int k = 1; k < 60; ++k) {
+    t *= q / ((double)k * k);
+    s += t;
+    if (t < 1e-18 * s) break;
+  }
+  return s;
+}
+
+// np.hanning(258)[1:-1]
+double stoi_window(int k) { return 0.5 - 0.5 * std::cos(2.0 * M_PI * (k + 1) / (stoi::kFrame + 1)); }
+
+// 5 * h / sum(h), h = kaiser(365, 0.1102 (60 - 8.7)) * 2 p fc sinc(2 fc t), p = 5, fc = 1 / 10, t = -182 .. 182
+std::vector<double> stoi_taps() {
+  const int L = stoi::kTapHalf;
+  const double beta = 0.1102 * (60.0 - 8.7), fc = 1.0 / 10.0;
+  std::vector<double> h(stoi::kTaps);
+  double sum = 0.0;
+  for (int i = 0; i < stoi::kTaps; ++i) {
+    const double t = i - L, a = t / L;
+    const double kaiser = bessel_i0(beta * std::sqrt(1.0 - a * a)) / bessel_i0(beta);
+    const double px = M_PI * 2.0 * fc * t;
+    const double sinc = t == 0.0 ? 1.0 : std::sin(px) / px;
+    h[i] = kaiser * (2.0 * 5.0 * fc * sinc);
+    sum += h[i];
+  }
+  for (double& v : h) v = v / sum * 5.0;
+  return h;
+}
+
+unsigned short bf16_rne(float f) {
+  unsigned u;
+  std::memcpy(&u, &f, 4);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (unsigned short)(u >> 16);
+}
+float bf16_f(unsigned short b) {
+  const unsigned u = (unsigned)b << 16;
+  float f;
+  std::memcpy(&f, &u, 4);
+  return f;
+}
+
+// row 4 q + {0, 1, 2, 3} = re, im of the first bin of pair slot q, re, im of its second (kernels_stoi.h); k = sample 0 .. 255
+double stoi_coef(int row, int k) {
+  const int q = row >> 2, second = (row >> 1) & 1, im = row & 1;
+  if (q >= stoi::kSlots) return 0.0;
+  int band = 0;
+  while (stoi::band_slot(band + 1) <= q) ++band;
+  const int bin = stoi::band_lo(band) + 2 * (q - stoi::band_slot(band)) + second;
+  if (bin >= stoi::band_lo(band + 1)) return 0.0;
+  const double th = 2.0 * M_PI * ((bin * k) % 512) / 512.0;
+  return stoi_window(k) * (im ? -std::sin(th) : std::cos(th));
+}
+
+int stoi_tables(int device, StoiTables** out) {
+  std::lock_guard<std::mutex> lk(g_stoi_mu);
+  StoiTables& t = g_stoi[device];
+  if (!t.tab) {
+    std::vector<double> tab(stoi::kTabLen, 0.0);
+    const std::vector<double> taps = stoi_taps();
+    std::copy(taps.begin(), taps.end(), tab.begin());
+    for (int k = 0; k < stoi::kFrame; ++k) tab[stoi::kTabWin + k] = stoi_window(k);
+    // [mt][chunk][part][lane][8] bf16, k = 32 chunk + 8 (lane >> 4) + e, row = 16 mt + (lane & 15)
+    std::vector<unsigned short> pack((size_t)stoi::kPack, 0);
+    for (int mt = 0; mt < stoi::kMTiles; ++mt)
+      for (int c = 0; c < stoi::kChunks; ++c)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int e = 0; e < 8; ++e) {
+            const float v = (float)stoi_coef(16 * mt + (lane & 15), 32 * c + 8 * (lane >> 4) + e);
+            const size_t at = (size_t)mt * stoi::kPackPerMT + ((size_t)(c * 3) * 64 + lane) * 8 + e;
+            pack[at] = bf16_rne(v);
+            const float r1 = v - bf16_f(pack[at]);
+            pack[at + 512] = bf16_rne(r1);
+            pack[at + 1024] = bf16_rne(r1 - bf16_f(pack[at + 512]));
+          }
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(stoi::band_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                stoi::kBandLdsBytes));
+    double* dt = nullptr;
+    unsigned short* dp = nullptr;
+    HIP_TRY(hipMalloc(&dt, tab.size() * sizeof(double)));
+    hipError_t e = hipMalloc(&dp, pack.size() * sizeof(unsigned short));
+    if (e == hipSuccess) e = hipMemcpy(dt, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dp, pack.data(), pack.size() * sizeof(unsigned short), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(dt);
+      if (dp) (void)hipFree(dp);
+      return rced_fail(e == hipErrorOutOfMemory ? RCED_ERR_ALLOC : RCED_ERR_HIP, "STOI tables: %s", hipGetErrorString(e));
+    }
+    t.apack = dp;
+    t.tab = dt;
+  }
+  *out = &t;
+  return RCED_OK;
+}
+
+size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
 }  // namespace
 
 extern "C" {
+
+int rced_stoi(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N, int fs_sig,
+              double* stoi_dev, int* detail_dev, int device, void* stream) {
+  if (N < 0 || ref_stride < 0 || est_stride < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
+  if (!ref_dev || !est_dev || !stoi_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
+  if (fs_sig != 8000 && fs_sig != stoi::kFs) return rced_fail(RCED_ERR_ARG, "fs_sig must be 8000 or 10000, got %d", fs_sig);
+  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
+  const int cap = ref_stride < est_stride ? ref_stride : est_stride;
+  if (cap > stoi::kMaxLen) return rced_fail(RCED_ERR_ARG, "rows longer than 2^28 samples");
+  if (N == 0) return RCED_OK;
+  if (int rc = check_device(device)) return rc;
+  DeviceGuard g(device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  StoiTables* t = nullptr;
+  if (int rc = stoi_tables(device, &t)) return rc;
+  // workspace: r [N][2][rstride] f64 | e [N][fcap] f64 | tob [N][2][fcap][16] f64 | dseg [N][mcap] f64 | kept [N][fcap] i32 | cnt [N][4] i32
+  const int l10 = stoi::len10k(cap, fs_sig);
+  const int fcap = stoi::num_frames(l10) > 0 ? stoi::num_frames(l10) : 1;
+  const int mcap = fcap > stoi::kSeg ? fcap - stoi::kSeg : 1;
+  const int rstride = (l10 + 1) & ~1;
+  const size_t o_r = 0, o_e = o_r + align256((size_t)N * 2 * rstride * 8), o_tob = o_e + align256((size_t)N * fcap * 8),
+               o_d = o_tob + align256((size_t)N * 2 * fcap * 16 * 8), o_kept = o_d + align256((size_t)N * mcap * 8),
+               o_cnt = o_kept + align256((size_t)N * fcap * 4), total = o_cnt + align256((size_t)N * 4 * 4);
+  double* ws = nullptr;
+  if (int rc = workspace(device, stream, total, &ws, kWsStoi)) return rc;
+  char* base = reinterpret_cast<char*>(ws);
+  double* r = reinterpret_cast<double*>(base + o_r);
+  double* e = reinterpret_cast<double*>(base + o_e);
+  double* tob = reinterpret_cast<double*>(base + o_tob);
+  double* dseg = reinterpret_cast<double*>(base + o_d);
+  int* kept = reinterpret_cast<int*>(base + o_kept);
+  int* cnt = reinterpret_cast<int*>(base + o_cnt);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (l10 > 0) {
+    hipLaunchKernelGGL(stoi::resample_kernel, dim3((l10 + 255) / 256, 2, N), dim3(256), 0, st, ref_dev, ref_stride, est_dev,
+                       est_stride, lengths_dev, cap, fs_sig, (const double*)t->tab, r, rstride);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(stoi::energy_kernel, dim3((fcap + 3) / 4, N), dim3(256), 0, st, (const double*)r, rstride, lengths_dev, cap,
+                     fs_sig, (const double*)t->tab, e, fcap);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(stoi::mask_kernel, dim3(N), dim3(64), 0, st, (const double*)e, lengths_dev, cap, fs_sig, fcap, kept, cnt);
+  HIP_TRY(hipGetLastError());
+  if (fcap - 1 >= stoi::kSeg) {
+    hipLaunchKernelGGL(stoi::band_kernel, dim3((fcap - 1 + stoi::kBlockFrames - 1) / stoi::kBlockFrames, 2, N), dim3(stoi::kThreads),
+                       stoi::kBandLdsBytes, st, (const double*)r, rstride, (const int*)kept, (const int*)cnt, fcap,
+                       (const unsigned short*)t->apack, (const double*)t->tab, tob);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(stoi::segment_kernel, dim3((mcap + 15) / 16, N), dim3(256), 0, st, (const double*)tob, (const int*)cnt, fcap,
+                       mcap, 1.0 + std::pow(10.0, 15.0 / 20.0), dseg);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(stoi::final_kernel, dim3(N), dim3(256), 0, st, (const double*)dseg, (const int*)cnt, mcap, stoi_dev, detail_dev);
+  HIP_TRY(hipGetLastError());
+  return RCED_OK;
+}
 
 int rced_sdr(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N,
              double* sdr_dev, double* energies_dev, int device, void* stream) {

@@ -3,8 +3,8 @@
 Reference: BaseTester / FullyCNNTester (model_utils/tester.py:18-90) and InferenceEngine
 (infer.py:19-52): read cfg -> creat_graph() -> _init_session() -> _load_checkpoint() ->
 test_step(ndarray[N,T,129,1]) -> ndarray[N,T,129,1], and the evaluation loop over it (tester.py:92-167):
-`evaluate_pcm` / `test` take ragged PCM through STFT -> net -> ISTFT rebuild -> SDR on the device.  PESQ / STOI
-scoring, wav files and the manifest-driven DataLoader are not mirrored.
+`evaluate_pcm` / `test` take ragged PCM through STFT -> net -> ISTFT rebuild -> SDR (and STOI, on request) on the device.
+PESQ scoring, wav files and the manifest-driven DataLoader are not mirrored.
 """
 
 import numpy as np
@@ -43,6 +43,7 @@ class FullyCNNTester(object):
             raise ValueError("feature_dim must be %d (nfft 256), got %d" % (spec.FEATURE_DIM, self.feature_dim))
         self._weights = weights
         self.sdr_score = AverageMeter()     # tester.py:63; test() adds to it and never resets it, as there
+        self.stoi_score = AverageMeter()    # tester.py:62; filled by test(..., stoi=True)
         self.creat_graph()
         self._load_checkpoint()
 
@@ -81,34 +82,43 @@ class FullyCNNTester(object):
             pool[2] ^= 1
         return self.model(input_x, out=out) if out is not None else self.model(input_x)
 
-    def evaluate_pcm(self, mix_sig, clean_sig, nfft=512, model=None, lengths=None, kernels="x6"):
+    def evaluate_pcm(self, mix_sig, clean_sig, nfft=512, model=None, lengths=None, kernels="x6", stoi=False):
         """One batch of the evaluation loop (tester.py:100-146) from PCM, on the device: the module's evaluate_pcm with
         this engine's network, or with `model` (a callable, device [N, T, 129, 1] -> same) in its place."""
-        return evaluate_pcm(model if model is not None else self.model, mix_sig, clean_sig, nfft, self.device, lengths, kernels)
+        return evaluate_pcm(model if model is not None else self.model, mix_sig, clean_sig, nfft, self.device, lengths, kernels,
+                            stoi=stoi)
 
-    def test(self, valid_loader):
+    def test(self, valid_loader, stoi=False):
         """tester.py:92-167 over anything that yields the reference's 4-tuple (batch_mix, batch_clean, mix_sig,
         clean_sig): every batch goes through evaluate_pcm(mix_sig, clean_sig), every utterance's SDR into
         self.sdr_score (an AverageMeter); prints the reference's summary line with its SDR field and returns the
         average.  The spectrogram is recomputed on the device from mix_sig (equal to batch_mix within the STFT's
-        pinned 2e-6 of the scale), so batch_mix / batch_clean are not read.  PESQ, STOI and the wav files the reference
-        writes next to the scores are not built."""
+        pinned 2e-6 of the scale), so batch_mix / batch_clean are not read.  With stoi=True every utterance's STOI goes
+        into self.stoi_score as well and the line gains the reference's st_score field, in the reference's order.
+        PESQ and the wav files the reference writes next to the scores are not built."""
         for _batch_mix, _batch_clean, mix_sig, clean_sig in valid_loader:
-            _, sdr = self.evaluate_pcm(mix_sig, clean_sig)
-            for score in sdr:
+            scores = self.evaluate_pcm(mix_sig, clean_sig, stoi=stoi)
+            for score in scores[1]:
                 self.sdr_score.update(float(score))
-        print("Average sd_score: {:.4f}.\n".format(self.sdr_score.avg))
+            if stoi:
+                for score in scores[2]:
+                    self.stoi_score.update(float(score))
+        if stoi:
+            print("Average st_score: {:.4f}; Average sd_score: {:.4f}.\n".format(self.stoi_score.avg, self.sdr_score.avg))
+        else:
+            print("Average sd_score: {:.4f}.\n".format(self.sdr_score.avg))
         return self.sdr_score.avg
 
 
-def evaluate_pcm(forward, mix_sig, clean_sig, nfft=512, device=0, lengths=None, kernels="x6"):
+def evaluate_pcm(forward, mix_sig, clean_sig, nfft=512, device=0, lengths=None, kernels="x6", stoi=False):
     """What FullyCNNTester.test and FullyCNNTrainer.valid do with one batch (tester.py:104-146, trainer.py:264-307), each
     with its own forward (device [N, T, 129, 1] -> same): one upload, STFT with the lengths -> forward -> ISTFT rebuild
     (AudioReBuild(nfft), 512 as the reference ships it) -> SDR against the clean rows; the audio and N scores come back.
     mix_sig, clean_sig: lists of 1-D float arrays of ragged lengths (utterance i is scored over len(clean_sig[i]), the
     reference's sig_length_list), or two zero-padded device tensors [N, L] with `lengths`.  kernels: the STFT / ISTFT
     kernel family, as in audio.stft_batch.
-    Returns (denoise: list of numpy float32, row i trimmed to its length; sdr: numpy float64 [N])."""
+    Returns (denoise: list of numpy float32, row i trimmed to its length; sdr: numpy float64 [N]); with stoi=True a third
+    element, STOI per utterance (numpy float64 [N], audio.stoi_batch of the rebuilt audio against the clean rows)."""
     import torch
     from . import audio
     if hasattr(mix_sig, "is_cuda"):
@@ -121,16 +131,16 @@ def evaluate_pcm(forward, mix_sig, clean_sig, nfft=512, device=0, lengths=None, 
         if len(mix_sig) != len(lens) or any(len(m) != n for m, n in zip(mix_sig, lens)):
             raise ValueError("mix_sig and clean_sig must pair up, utterance by utterance and sample by sample")
         if not lens:
-            return [], np.zeros(0, np.float64)
+            return ([], np.zeros(0, np.float64), np.zeros(0, np.float64)) if stoi else ([], np.zeros(0, np.float64))
         both = np.zeros((2, len(lens), max(lens)), np.float32)
         for i, n in enumerate(lens):
             both[0, i, :n] = mix_sig[i]
             both[1, i, :n] = clean_sig[i]
         both = torch.as_tensor(both, device="cuda:%d" % device)
         mix, clean = both[0], both[1]
-    out, sdr = audio.denoise_and_score(forward, mix, clean, lens, nfft, kernels)
-    audio_host = out.cpu().numpy()
-    return [audio_host[i, :lens[i]].copy() for i in range(len(lens))], sdr.cpu().numpy()
+    scored = audio.denoise_and_score(forward, mix, clean, lens, nfft, kernels, stoi=stoi)
+    audio_host = scored[0].cpu().numpy()
+    return ([audio_host[i, :lens[i]].copy() for i in range(len(lens))],) + tuple(s.cpu().numpy() for s in scored[1:])
 
 
 class InferenceEngine(FullyCNNTester):

@@ -2,7 +2,9 @@
 
 AverageMeter is plain Python.  SDR keeps the reference's call surface -- `SDR()(y, y_pred)`, numpy 1-D in, Python float
 out -- and computes on the device (rced_sdr); a batch is scored without leaving the device by `audio.sdr_batch`.
-PESQ and STOI are not built (the reference takes them from pypesq / pystoi).
+STOI does the same over rced_stoi / `audio.stoi_batch`; the reference takes it from pystoi, which this project cannot
+reach: parity is pinned to the restatement of the published algorithm in tests/stoi_np.py (DESIGN.md "STOI").
+PESQ is not built (the reference takes it from pypesq).
 """
 
 import numpy as np
@@ -47,3 +49,31 @@ class SDR(object):
 
     def __call__(self, x, y):
         return self.sdr(x, y)
+
+
+class STOI(object):
+    """The reference's `stoi(clean, denoise, sr, extended=False)` (tester.py:92-167) with SDR's call surface:
+    `STOI(sr)(clean, processed)`, numpy 1-D in, Python float out, computed on the device (rced_stoi)."""
+
+    def __init__(self, sr=8000, device=0):
+        from . import audio
+        if sr not in audio.STOI_RATES:
+            raise ValueError("sr must be 8000 or 10000, got %r" % (sr,))
+        self.sr, self.device = int(sr), device
+
+    def stoi(self, x, y):
+        import torch
+        from . import audio
+        x, y = np.asarray(x), np.asarray(y)
+        if len(x.shape) != 1 or len(y.shape) != 1:
+            raise ValueError("x and y must be 1-D signals, got shapes %s and %s" % (x.shape, y.shape))
+        if len(x) != len(y):
+            raise ValueError("x and y must have the same length, got %d and %d" % (len(x), len(y)))
+        if len(x) == 0:
+            return 1e-5
+        dev = "cuda:%d" % self.device
+        both = torch.as_tensor(np.stack([x.astype(np.float32), y.astype(np.float32)]), device=dev)
+        return float(audio.stoi_batch(both[0:1], both[1:2], sample_rate=self.sr)[0])
+
+    def __call__(self, x, y):
+        return self.stoi(x, y)

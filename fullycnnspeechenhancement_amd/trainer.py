@@ -28,6 +28,7 @@ class FullyCNNTrainer(object):
         self.warmup_steps = float(warmup_steps)    # [training] warmup_steps
         self.device = int(device)
         self.sdr_score = AverageMeter()            # trainer.py:34; valid() adds to it and never resets it, as there
+        self.stoi_score = AverageMeter()           # trainer.py:33; filled by valid(..., stoi=True)
         w = weights if weights is not None else _weights.initial_weights(self.variant, seed)
         self._blob_n = spec.num_weights(self.variant)
         # creat_graph (trainer.py:165-172): self.model = Model(is_training=True); self.pred = self.model(self.input_x).
@@ -73,17 +74,25 @@ class FullyCNNTrainer(object):
         statistics, is `build_model(net_work, False, weights=trainer.variables())`.)"""
         return self.model(input_x)
 
-    def valid(self, valid_loader, epoch, logger=None, nfft=512):
+    def valid(self, valid_loader, epoch, logger=None, nfft=512, stoi=False):
         """trainer.py:252-338 over anything that yields the reference's 4-tuple (batch_mix, batch_clean, mix_sig,
         clean_sig): engine.evaluate_pcm with valid_step as the forward (BatchNorm with each batch's own statistics),
         every utterance's SDR into self.sdr_score; prints -- and logs, given a logger -- the reference's line with its
-        SDR field and returns the average.  PESQ, STOI and the wav files are not built."""
+        SDR field and returns the average.  With stoi=True every utterance's STOI goes into self.stoi_score as well and
+        the line gains the reference's st_score field, in the reference's order.  PESQ and the wav files are not built."""
         from .engine import evaluate_pcm
         for _batch_mix, _batch_clean, mix_sig, clean_sig in valid_loader:
-            _, sdr = evaluate_pcm(self.valid_step, mix_sig, clean_sig, nfft, self.device)
-            for score in sdr:
+            scores = evaluate_pcm(self.valid_step, mix_sig, clean_sig, nfft, self.device, stoi=stoi)
+            for score in scores[1]:
                 self.sdr_score.update(float(score))
-        line = "Epoch: {}, Average sd_score: {:.4f}.\n".format(epoch, self.sdr_score.avg)
+            if stoi:
+                for score in scores[2]:
+                    self.stoi_score.update(float(score))
+        if stoi:
+            line = "Epoch: {}, Average st_score: {:.4f}; Average sd_score: {:.4f}.\n".format(epoch, self.stoi_score.avg,
+                                                                                             self.sdr_score.avg)
+        else:
+            line = "Epoch: {}, Average sd_score: {:.4f}.\n".format(epoch, self.sdr_score.avg)
         print(line)
         if logger is not None:
             logger.info(line)

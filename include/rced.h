@@ -196,6 +196,19 @@ int rced_mix_snr(const float* speech_dev, const int* speech_len_dev, int N, int 
                  const int* start_dev, const double* gains_dev, int n_gains,
                  double snr_db, float* mix_dev, int device, void* stream);
 
+/* STOI (Taal, Hendriks, Heusdens, Jensen 2011; the reference takes it from pystoi, tester.py:92-167) per utterance over
+ * its own length: stoi(x = ref row, y = est row, fs_sig), exactly as DESIGN.md "STOI" specifies it -- polyphase resampling
+ * to 10 kHz (fs_sig = 8000; fs_sig = 10000 skips it; any other rate is RCED_ERR_ARG), removal of the frames more than
+ * 40 dB under the loudest clean frame, 512-point spectra in 15 one-third-octave bands, 30-frame segments.  Pointers,
+ * strides, lengths_dev and their clamping as in rced_sdr.  stoi_dev [N] double; detail_dev: NULL or [N, 3] int32
+ * receiving F (frames at 10 kHz), K (frames kept), M (segments).  Fewer than 30 spectral frames (K - 1 < 30, a length of
+ * 0 included) give 1e-5; an all-zero clean signal gives 0.  Everything is fp64 from the fp32 inputs except the products
+ * of the DFT, which run as three-part bf16 on the matrix pipe (fp32 quality).  No atomics, fixed summation order: the
+ * invariants stated above hold; the workspace (per device and stream, growing only) is separate from rced_sdr's.
+ * Asynchronous. */
+int rced_stoi(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride,
+              const int* lengths_dev, int N, int fs_sig, double* stoi_dev, int* detail_dev, int device, void* stream);
+
 /* ---- training step: FullyCNNTrainer.creat_graph + train_step,
  * model_utils/trainer.py:156-192, over Model(is_training=True).  Layer-by-layer, correctness first. ---- */
 typedef struct rced_trainer rced_trainer;

@@ -3,6 +3,8 @@
 rced_mix_snr and rced_sdr through the C ABI with HIP events on the launch stream (>= 20 warm-ups, >= 100 runs, the median
 of per-run times), beside the HBM floor their byte counts imply; and FullyCNNTester.evaluate_pcm's device part against
 the same chain without the score (stft_batch -> model -> istft_batch): the difference is what scoring costs.
+STOI (rced_stoi) is timed at the same shape, beside the wall time of its float64 numpy / scipy restatement
+(tests/stoi_np.py) for the same batch on 16 host processes.  `python tools/time_eval.py stoi` times STOI alone.
 Prints one JSON line."""
 import json
 import os
@@ -36,11 +38,48 @@ def timed_us(fn):
     return {"median_us": ts[len(ts) // 2], "min_us": ts[0], "p90_us": ts[int(0.9 * len(ts))]}
 
 
+HOST_PROCS = 16
+
+
+def _host_stoi(seed):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import numpy as np
+    import stoi_np
+    rng = np.random.default_rng(seed)
+    x = 0.1 * rng.standard_normal(L)
+    return stoi_np.stoi(x, x + 0.05 * rng.standard_normal(L), 8000)
+
+
+def host_stoi_seconds():
+    """Wall time of the restatement over N utterances of L samples on HOST_PROCS processes (forked before the GPU is touched)."""
+    import multiprocessing
+    import time
+    with multiprocessing.get_context("fork").Pool(HOST_PROCS) as pool:
+        pool.map(_host_stoi, range(HOST_PROCS))              # imports and first-call costs
+        t0 = time.perf_counter()
+        pool.map(_host_stoi, range(N), chunksize=1)
+        return time.perf_counter() - t0
+
+
+def stoi_timings(speech, mix):
+    r = timed_us(lambda: audio.stoi_batch(speech, mix))
+    one = timed_us(lambda: audio.stoi_batch(speech[:1], mix[:1]))
+    return r, one
+
+
 def main():
+    only_stoi = sys.argv[1:] == ["stoi"]
+    host_s = host_stoi_seconds()                                 # first: it forks
     g = torch.Generator(device="cuda").manual_seed(1)
     speech = torch.randn((N, L), device="cuda", generator=g) * 0.1
     noise = torch.randn((N, L), device="cuda", generator=g) * 0.05
     out = {"N": N, "L": L}
+    if only_stoi:
+        mix = audio.mix_snr_batch(speech, noise, 5.0)
+        out["stoi"], out["stoi_single_utterance"] = stoi_timings(speech, mix)
+        out["stoi_host_restatement_s"] = {"seconds": host_s, "processes": HOST_PROCS}
+        print(json.dumps(out))
+        return
 
     # the mix reads speech and noise twice and writes once; the SDR reads two signals once
     mix_bytes, sdr_bytes = 5 * N * L * 4, 2 * N * L * 4
@@ -63,6 +102,9 @@ def main():
 
     one = speech[:1].contiguous()                              # N = 1: a long signal alone (33 workgroups)
     out["sdr_single_utterance"] = timed_us(lambda: audio.sdr_batch(one, mix[:1]))
+
+    out["stoi"], out["stoi_single_utterance"] = stoi_timings(speech, mix)
+    out["stoi_host_restatement_s"] = {"seconds": host_s, "processes": HOST_PROCS}
 
     model = build_model("FullyCNNV3", False, weights=_weights.synthetic_weights(3, seed=42))
     lens = [L] * N
