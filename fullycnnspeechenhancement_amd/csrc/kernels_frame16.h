@@ -1,4 +1,4 @@
-// R-CED V1 / V2 forward in bf16 (BASELINE config 2: "R-CED V2 forward, batch 64, 129x512, bf16"): ALL layers, the 1x129 output
+// R-CED V1 / V2 (and, further down, CR-CED) forward in bf16 (BASELINE config 2: "R-CED V2 forward, batch 64, 129x512, bf16"): ALL layers, the 1x129 output
 // layer included, in ONE kernel on v_mfma_f32_16x16x32_bf16.  Round 6's rebuild of kernels_fused_chain16.h, whose 3-frame tiles
 // crossed fifteen workgroup barriers with 4-17 half-rate MFMAs per tile and layer between them (0.107 of the bf16 peak for four
 // rounds; this kernel: 0.225).  Reference: model_utils/model.py:6-61 over module.py:11-34 (conv -> BN -> +skip -> ReLU).
@@ -33,9 +33,14 @@
 //   * Weights: per layer a packet of 1-KiB A fragments [step][M-tile][lane] x 8 bf16 (+ 32 fp32 shifts per layer, resident),
 //     LDS-DMA'd a group ahead into a two-slot ring; a layer reads its fragments ONCE, into registers.
 //   * The output layer (run_final) is a Toeplitz GEMM over tap tables in its packet and images the last hidden layer writes.
-// Precision contract: tests/test_forward_gpu.py against the test suite's bf16 emulation, which rounds at the same places (input,
-// every folded kernel, every layer's output), and tests/tools/fuzz_bf16.py.  NOT within the fp32 path's 1e-4 bar: opt-in
-// (option "bf16").
+//   * CR-CED (chain::NetV3F16, option "v3_bf16") runs through the same template.  Its only skips are the 8-channel outputs of blocks
+//     CE2 / CE1, added to CD1's / CD2's BEHIND the ReLU (model.py:75-76): both wait in registers (2 x 18 VGPRs) and are added in the
+//     epilogue in fp32 -- max(acc, 0) + skip, then the layer's one rounding -- not through the identity MFMA, so this net has no
+//     global scratch, no skip in LDS and no 16x16x16 MFMA at all.  Its output layer reads 8 channels: the octet-0 part of run_final
+//     alone (36 K-steps, table TA).  115 + 36 MFMAs per 16-pixel tile against V2's 104 + 45.
+// Precision contract: tests/test_forward_gpu.py (R-CED) and tests/test_v3_bf16_gpu.py (CR-CED) against the test suite's bf16
+// emulation, which rounds at the same places (input, every folded kernel, every layer's output), and tests/tools/fuzz_bf16.py.  NOT
+// within the fp32 path's 1e-4 bar: opt-in (options "bf16", "v3_bf16").
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -66,6 +71,13 @@
 #define RCED_F16_STAMPS 0   // diagnostic build: s_memtime stamps of workgroup 0 / wave 0 on its second tile (tools/stamps16.py)
 #endif
 
+#ifndef RCED_F16_RESMASK
+#define RCED_F16_RESMASK 0xffff   // saving layers whose skip fragments may wait in registers (Res)
+#endif
+#ifndef RCED_F16_MAXRES
+#define RCED_F16_MAXRES 4
+#endif
+
 namespace rced {
 namespace frame16 {
 
@@ -88,13 +100,14 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int kRowPad = 8;                // bin f lives at row f + kRowPad
 constexpr int kPlanes = 4;                // 32 channels at most (V1's 24 -> 32 layer, V2's 23 -> 25)
 constexpr int kTiles = 9;                 // 16-pixel tiles per frame
+constexpr int kMaxRes = RCED_F16_MAXRES;  // skips that wait in registers (Res)
 
 struct Params {
   const float* x;            // [N, T, 129]
   float* y;                  // [N, T, 129]: the masks
   float fin_bias;            // the output layer's bias
   const unsigned* wpack;     // Geo::kWBytes
-  unsigned* scratch;         // gridDim.x * kWaves * Geo::kScratchBytesPerWave (skip fragments)
+  unsigned* scratch;         // gridDim.x * kWaves * Geo::kScratchBytesPerWave (skip fragments); null for a net whose skips all wait in registers
   int N, T;
   int tiles_per_utt;         // ceil(T / 4)
   int total_tiles;
@@ -124,15 +137,19 @@ struct Geo {
   //     of a read land 2,560 bytes apart (the same bank slots: the lane groups of a ds_read_b128 stay conflict-free);
   //   TB[RB copies c][k][RB positions j][CB channels]: tap RB k + c + j - 15 of channels 8 .. 8 + CB - 1 -- copy c serves the
   //     lanes whose bin phase leaves the remainder c, so that every read is 16-byte aligned.
+  // A net whose output layer reads 8 channels (CR-CED) has the octet-0 part alone: no TB, no H2, 36 K-steps.
+  static constexpr bool kFinB = N::kFinalCh > 8;
   static constexpr int kFinCB = N::kFinalCh <= 10 ? 2 : 4;
   static constexpr int kFinRB = 8 / kFinCB;
-  static constexpr int kFinStepsA = 36, kFinStepsB = 36 / kFinRB;
+  static constexpr int kFinStepsA = 36, kFinStepsB = kFinB ? 36 / kFinRB : 0;
   static constexpr int kTARows = 160, kTACopy = kTARows * 16;
   static constexpr int kTBOff = 4 * kTACopy;
-  static constexpr int kTBRows = 4 * (kFinStepsB - 1) + 3 + 15 / kFinRB + 1;     // k values a read reaches
+  static constexpr int kTBRows = kFinB ? 4 * (kFinStepsB - 1) + 3 + 15 / kFinRB + 1 : 0;     // k values a read reaches
   static constexpr int kTBCopy = kFinRB == 4 ? 704 : 1408;                        // 12 / 8 bank slots (mod 16) from copy to copy
-  static constexpr int kFinPacket = 13 * 1024;
-  static_assert(N::kFinalCh > 8 && N::kFinalCh <= 12 && kTBRows * 16 <= kTBCopy && kTBOff + kFinRB * kTBCopy <= kFinPacket, "tap tables fit");
+  static constexpr int kFinPacket = (kFinB ? 13 : 10) * 1024;
+  static_assert(kFinB ? N::kFinalCh <= 12 && kTBRows * 16 <= kTBCopy && kTBOff + kFinRB * kTBCopy <= kFinPacket
+                      : N::kFinalCh == 8 && kTBOff <= kFinPacket,
+                "tap tables fit");
   static constexpr int packet_bytes(int l) { return l == kLayers ? kFinPacket : frags(l) * 1024; }
   static constexpr int packet_off(int l) {
     int o = 0;
@@ -147,11 +164,11 @@ struct Geo {
     for (int l = 0; l <= kLayers; ++l) m = packet_bytes(l) > m ? packet_bytes(l) : m;
     return m;
   }
-  static constexpr int kWRegion = maxpacket();
+  static constexpr int kWRegion = maxpacket() > N::kRingBytes ? maxpacket() : N::kRingBytes;   // a ring slot
   // Consecutive layers whose packets fit one ring slot TOGETHER travel as one transfer and run back to back: the barrier at a
   // layer's end is the weight ring's alone (who has read the slot the next transfer overwrites, whose pieces have landed), so inside
   // a group there is none.  Greedy from layer 0 -- V2: {0..3} {4,5} {6} {7} {8} {9,10} {11..14} {output layer}: 8 barriers per tile
-  // instead of 16.
+  // instead of 16.  CR-CED (17-KiB slots): {0,1} {2,3} {4,5} {6,7} {8,9} {10,11} {12,13} {14} {output layer}.
   static constexpr int group_first(int l) {
     int f = 0, bytes = 0;
     for (int i = 0; i <= l; ++i) {
@@ -218,9 +235,21 @@ struct Geo {
   static constexpr int kH2Stride = kFinRB == 4 ? 96 : 160;
   static constexpr int kH2Block = 16 * 2 * kFinCB;    // bytes of a block's sixteen bins
   static constexpr int kZOff = 3 * kPlane + (kRowPad + kF) * 16;
+  // A last layer that reads plane 2 itself (CR-CED: 30 channels in) writes H over rows it has read: run_layer stores the first two
+  // tiles of group g - 1 (H rows up to 18 (3 g - 2) + 15) while group g's reads (rows 48 g + kRowPad - pad and up) are outstanding, and
+  // the third (up to row 18 (3 g - 1) + 15) once group g + 1's first slot is issued (slot 1 reads rows 48 (g + 1) + kRowPad - pad +
+  // 4 / octets and up).  Such a net has no H2: plane 3 keeps its activations.
+  static constexpr bool h_in_place() {
+    const int l = kLayers - 1;
+    if (oct_in(l) <= 2) return true;
+    if (kFinB || steps(l) < 2) return false;
+    for (int g = 1; g < kTiles / 3; ++g)
+      if (18 * (3 * g - 2) + 15 >= 48 * g + kRowPad - pad(l) || 18 * (3 * g - 1) + 15 >= 48 * (g + 1) + kRowPad - pad(l) + 4 / oct_in(l)) return false;
+    return true;
+  }
   static_assert(8 * kHStride + 16 * 16 <= kPlane && kH2Off + 8 * kH2Stride + kH2Block <= kZOff && kZOff + 64 <= kRegion &&
-                    oct_in(kLayers - 1) <= 2 && MT(kLayers - 1) == 1,
-                "H, H2 and the zero rows fit planes 2, 3; the last layer reads planes 0, 1 only");
+                    h_in_place() && MT(kLayers - 1) == 1,
+                "H, H2 and the zero rows fit planes 2, 3; the last layer reads planes 0, 1 only, or reads H's rows before it writes them");
   // skip scratch, per wave: per (saving layer, M-tile) and group of three tiles a 1-KiB unit -- the group's first two fragments,
   // 16 bytes per lane -- and a 512-byte one for the third.  Only the lanes whose four channels exist are stored and loaded
   // (k-quads 0 .. quads - 1: whole 256-byte runs), so an M-tile with 3 real channels moves a quarter of its unit.
@@ -235,7 +264,17 @@ struct Geo {
     const int q = (N::layer[l].cout + 3) / 4 - 4 * mt;
     return q > 4 ? 4 : q;
   }
-  static constexpr size_t kScratchBytesPerWave = (size_t)skip_off(kLayers, 0);
+  // ... none at all when every saved fragment waits in registers (Res::slot's rule: one M-tile, among the first kMaxRes such layers)
+  static constexpr bool skips_in_memory() {
+    int k = 0;
+    for (int l = 0; l < kLayers; ++l) {
+      if (!N::layer[l].saves_skip) continue;
+      if (MT(l) != 1 || !((RCED_F16_RESMASK >> l) & 1) || k >= kMaxRes) return true;
+      ++k;
+    }
+    return false;
+  }
+  static constexpr size_t kScratchBytesPerWave = skips_in_memory() ? (size_t)skip_off(kLayers, 0) : 0;
 };
 
 __device__ __forceinline__ f32x4 mfma32(u32x4 a, u32x4 b, f32x4 c) {
@@ -330,13 +369,6 @@ __device__ __forceinline__ void x_store(const XRows& r, char* region, int lane) 
 
 // Skip fragments that never leave the register file: the one-M-tile encoder layers' (V2: encode_1..4, V1: encode_1..2),
 // two registers per tile, 72 / 36 in all.  The other saving layers' fragments go through the global scratch.
-#ifndef RCED_F16_RESMASK
-#define RCED_F16_RESMASK 0xffff
-#endif
-#ifndef RCED_F16_MAXRES
-#define RCED_F16_MAXRES 4
-#endif
-constexpr int kMaxRes = RCED_F16_MAXRES;
 template <class N>
 struct Res {
   static constexpr int slot(int l) {   // register slot of saving layer l, or -1
@@ -377,11 +409,14 @@ __device__ __forceinline__ void run_layer(const Params& P, char* region, const c
   constexpr int SF = D.skip_from >= 0 ? D.skip_from : 0;
   constexpr int kResIn = D.skip_from >= 0 ? Res<N>::slot(SF) : -1;     // the skip comes out of registers
   constexpr int kResOut = D.saves_skip ? Res<N>::slot(L) : -1;         // ... goes into registers
+  constexpr bool kPost = D.skip_from >= 0 && D.skip_post;              // the skip is added behind the ReLU, in the epilogue (fragment)
+  static_assert(!kPost || kResIn >= 0, "a post-ReLU skip comes out of registers");
   constexpr bool kSkipMem = D.skip_from >= 0 && kResIn < 0 && !(RCED_F16_EXP & 2);
   constexpr bool kSaveMem = D.saves_skip && kResOut < 0 && !(RCED_F16_EXP & 1);
   constexpr bool kSaveLds = kSaveMem && L == G::kSkipLdsLayer;             // ... its M-tile 0 goes to LDS
   constexpr bool kSkipLds = kSkipMem && SF == G::kSkipLdsLayer && G::kSkipLdsLayer >= 0;
   constexpr int kMemMT = MT - (kSaveLds ? 1 : 0);                          // M-tiles whose skip fragments go to the global scratch
+  static_assert(!(kSkipMem || kSaveMem) || G::kScratchBytesPerWave > 0, "a net with skips in memory has a scratch");
   static_assert(STEPS >= 2 && kTiles == GT * NG, "the third tile of a group is stored in the next group's last slot");
   constexpr int kPer = (2 * MT + STEPS - 2) / (STEPS - 1);   // fragments of the previous group per slot (slots 0 .. STEPS - 2)
   static_assert(kPer <= (GT * MT + 1) / 2 && MT <= (GT * MT + 1) / 2, "one fragment behind every second MFMA of a slot");
@@ -414,7 +449,7 @@ __device__ __forceinline__ void run_layer(const Params& P, char* region, const c
 #pragma unroll
     for (int t = 0; t < kTiles; ++t) skip[t][0] = *reinterpret_cast<const u32x2*>(skl + t * 512 + lane * 8);
   }
-  if constexpr (kLast) {   // plane 3 holds an earlier layer's activations: H2's block 8 is zero behind bin 128
+  if constexpr (kLast && G::kFinB) {   // plane 3 holds an earlier layer's activations: H2's block 8 is zero behind bin 128
     if (lane < G::kH2Block / 16) *reinterpret_cast<u32x4*>(region + G::kH2Off + 8 * G::kH2Stride + lane * 16) = u32x4{0u, 0u, 0u, 0u};
   }
   int base[NB];
@@ -449,7 +484,19 @@ __device__ __forceinline__ void run_layer(const Params& P, char* region, const c
   }
   u32x2 pair[MT];                                   // a group's first tile, until its second completes the 16-byte skip store
   auto fragment = [&](const f32x4 v, int t, int mt) {
-    const u32x2 hq = {relu2(pack2(v.x, v.y)), relu2(pack2(v.z, v.w))};
+    u32x2 hq;
+    if constexpr (kPost) {
+      // module-level skip of CR-CED (model.py:75-76): max(acc + shift, 0) + skip in fp32 -- the saved fragment holds the same
+      // channels of the same pixel in this lane, and a bf16 is exact in fp32 -- then the layer's ONE rounding; no ReLU behind it
+      const u32x2 sk = res.v[kResIn >= 0 ? kResIn : 0][t];
+      const float r0 = __builtin_fmaxf(v.x, 0.f) + __builtin_bit_cast(float, sk.x << 16);
+      const float r1 = __builtin_fmaxf(v.y, 0.f) + __builtin_bit_cast(float, sk.x & 0xffff0000u);
+      const float r2 = __builtin_fmaxf(v.z, 0.f) + __builtin_bit_cast(float, sk.y << 16);
+      const float r3 = __builtin_fmaxf(v.w, 0.f) + __builtin_bit_cast(float, sk.y & 0xffff0000u);
+      hq = u32x2{pack2(r0, r1), pack2(r2, r3)};
+    } else {
+      hq = u32x2{relu2(pack2(v.x, v.y)), relu2(pack2(v.z, v.w))};
+    }
     if constexpr (kResOut >= 0) res.v[kResOut >= 0 ? kResOut : 0][t] = hq;
     if constexpr (!kLast) {
       if (t < kTiles - 1) *reinterpret_cast<u32x2*>(out + 2 * mt * G::kPlane + t * 256) = hq;
@@ -458,7 +505,7 @@ __device__ __forceinline__ void run_layer(const Params& P, char* region, const c
       // the output layer's images (Geo::kHOff, kH2Off): k-quads 0, 1 hold octet 0 of bin 16 t + n, k-quad 2 channels 8 .. 11
       if (t < kTiles - 1 || n == 0) {
         if (kq < 2) *reinterpret_cast<u32x2*>(region + G::kHOff + t * G::kHStride + n * 16 + kq * 8) = hq;
-        else if (kq == 2) {
+        else if (G::kFinB && kq == 2) {
           char* const h2 = region + G::kH2Off + t * G::kH2Stride + n * (2 * G::kFinCB);
           if constexpr (G::kFinCB == 2) *reinterpret_cast<unsigned*>(h2) = hq.x;
           else *reinterpret_cast<u32x2*>(h2) = hq;
@@ -540,7 +587,7 @@ __device__ __forceinline__ void run_layer(const Params& P, char* region, const c
         }
       pin();
     }
-    if constexpr (D.skip_from >= 0 && !(RCED_F16_EXP & (2 | 128))) {
+    if constexpr (D.skip_from >= 0 && !kPost && !(RCED_F16_EXP & (2 | 128))) {
       // HAZARD (found the hard way, round 6): a v_mfma_f32_16x16x16_bf16 issued DIRECTLY behind the v_mfma_f32_16x16x32_bf16
       // that wrote its srcC -- same registers as vdst, the ordinary accumulation chain, but two opcodes of different pass
       // counts -- read a stale accumulator on this part (one tile's skip landed on the previous K-step's sum; deterministic),
@@ -606,7 +653,7 @@ __device__ __forceinline__ void run_final(const Params& P, const char* region, c
   const int n = lane & 15, kq = lane >> 4;
   constexpr int RB = G::kFinRB, NA = G::kFinStepsA, NT = NA + G::kFinStepsB;
   int ta = kq * G::kTACopy + (15 - n) * 16;
-  int tb = G::kTBOff + ((15 - n) % RB) * G::kTBCopy + (kq + (15 - n) / RB) * 16;
+  int tb = G::kFinB ? G::kTBOff + ((15 - n) % RB) * G::kTBCopy + (kq + (15 - n) / RB) * 16 : 0;   // (no second part: never read)
   asm volatile("" : "+v"(ta), "+v"(tb));
   const char* const ap = tt + ta;
   const char* const bp = tt + tb;
@@ -619,7 +666,7 @@ __device__ __forceinline__ void run_final(const Params& P, const char* region, c
     for (int e = 0; e < SS; ++e) {
       const int s = SS * slot + e;
       const bool first = s < NA;                      // octet 0 / the packed channels
-      const int t = first ? s : s - NA, spb = first ? 4 : 4 / RB;   // steps per 16-bin block
+      const int t = first ? s : s - NA, spb = first || !G::kFinB ? 4 : 4 / RB;   // steps per 16-bin block
       const int q = t / spb, i = t % spb;
       const int blk = n - 4 + q;
       const bool ok = n <= 8 && blk >= 0 && blk <= 8;
@@ -710,8 +757,9 @@ __global__ __launch_bounds__(W * 64, W == 4 ? 2 : 1) void frame16_kernel(Params 
   int wcur = 0;
   XRows xr = x_load<W>(P, first, wave, lane);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  // (a net without skips in memory: a null resource of no records, which nothing dereferences)
   const __amdgpu_buffer_rsrc_t scratch = __builtin_amdgcn_make_buffer_rsrc(
-      reinterpret_cast<char*>(P.scratch) + ((size_t)blockIdx.x * kWaves + wave) * G::kScratchBytesPerWave, 0,
+      G::kScratchBytesPerWave ? reinterpret_cast<char*>(P.scratch) + ((size_t)blockIdx.x * kWaves + wave) * G::kScratchBytesPerWave : nullptr, 0,
       (int)G::kScratchBytesPerWave, 0x00020000);
   layer_end_sync();
   for (int tile = first; tile < last; ++tile) {

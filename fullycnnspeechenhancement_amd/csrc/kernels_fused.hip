@@ -48,9 +48,10 @@ struct rced_fused {
   size_t h_bytes = 0;
   unsigned long long* stamps = nullptr;  // diagnostic builds (RCED_STAMPS) only
   int bf16 = 0;               // option "bf16" (V1/V2): bf16 activations + weights, one launch (kernels_frame16.h)
+  int v3_bf16 = 0;            // option "v3_bf16" (CR-CED): the same kernel over chain::NetV3F16; 0 = the v3_l2x6 form selected
   unsigned* wpack16 = nullptr;   // its packet stream (built when the option is first set)
   unsigned short* fin_apack_x6 = nullptr;  // ... as three bf16 parts per value: fp32 quality on the bf16 pipe (x6::final_gemm_x6_kernel)
-  unsigned* scratch16 = nullptr; // its skip fragments, per wave (2 workgroups per CU x 4 waves)
+  unsigned* scratch16 = nullptr; // its skip fragments, per wave (2 workgroups per CU x 4 waves); CR-CED: none (they wait in registers)
   int bf16_wgs_per_cu = 1;
   int bf16_frames = 0;        // option "bf16_frames": frames per workgroup of the bf16 kernel (0 = chosen per call, 4, 8)
   int grid_limit = 0;         // option "fused_grid": workgroups of the persistent kernel (0 = #CUs)
@@ -485,6 +486,7 @@ void pack_frame16(const rced_model* m, std::vector<unsigned>* wpack) {
   }
   // the output layer's tap tables (frame16::Geo's packet comment): TA[kq][r] = tap r + kq - 15 of channels 0 .. 7;
   // TB[c][k][j] = tap RB k + c + j - 15 of channels 8 .. 8 + CB - 1; zero outside taps 0 .. 128
+  // (CR-CED's 8 channels: TA alone)
   constexpr int CH = N::kFinalCh, RB = G::kFinRB, CB = G::kFinCB;
   const rced_layer_dev& lf = m->layers[N::kLayers];
   unsigned char* tt = reinterpret_cast<unsigned char*>(wpack->data()) + G::packet_off(N::kLayers);
@@ -493,7 +495,7 @@ void pack_frame16(const rced_model* m, std::vector<unsigned>* wpack) {
     for (int r = 0; r < G::kTARows; ++r)
       for (int c = 0; c < 8; ++c)
         reinterpret_cast<unsigned short*>(tt + kq * G::kTACopy)[r * 8 + c] = tapw(r + kq - 15, c);
-  for (int c = 0; c < RB; ++c)
+  for (int c = 0; G::kFinB && c < RB; ++c)
     for (int k = 0; k < G::kTBRows; ++k)
       for (int j = 0; j < RB; ++j)
         for (int e = 0; e < CB; ++e)
@@ -525,7 +527,8 @@ int frame16_enable(rced_model* m, rced_fused* f) {
   int one = 1;
   if (int rc = frame16_prepare<N, 8>(m, &one)) { (void)hipFree(wdev); return rc; }
   static_assert(G::kScratchBytesPerWave == frame16::Geo<N, 8>::kScratchBytesPerWave, "one scratch serves both forms");
-  if (!f->scratch16 && hipMalloc(&f->scratch16, (size_t)8 * m->num_cus * G::kScratchBytesPerWave) != hipSuccess) {   // 8 waves per CU either way
+  if (G::kScratchBytesPerWave && !f->scratch16 &&
+      hipMalloc(&f->scratch16, (size_t)8 * m->num_cus * G::kScratchBytesPerWave) != hipSuccess) {   // 8 waves per CU either way
     (void)hipFree(wdev);
     return rced_fail(RCED_ERR_HIP, "hipMalloc(bf16 skip scratch)");
   }
@@ -725,6 +728,7 @@ int fused_forward(rced_model* m, const float* x, float* y, int N, int T, hipStre
     return f->bf16 ? frame16_forward<chain::NetV2>(m, f, x, y, N, T, st)
                    : chain_forward<chain::NetV2>(m, f, x, y, N, T, st);
   if (int rc = fused_check(m)) return rc;   // a hand-off flag that never came in an EARLIER launch: refuse to go on
+  if (f->v3_bf16) return frame16_forward<chain::NetV3F16>(m, f, x, y, N, T, st);   // (no hand-offs of its own: one wave per frame)
   v3::Params P;
   P.err = f->err_dev;
   P.x = x;
@@ -782,7 +786,8 @@ int fused_set_option(rced_model* m, const char* key, int value) {
     return RCED_OK;
   }
   if (!strcmp(key, "bf16")) {
-    if (m->variant == RCED_V3) return value ? rced_fail(RCED_ERR_ARG, "bf16 is built for R-CED V1 / V2 only") : RCED_OK;
+    if (m->variant == RCED_V3)
+      return value ? rced_fail(RCED_ERR_ARG, "bf16 is the R-CED V1 / V2 option; CR-CED's bf16 kernel is option \"v3_bf16\"") : RCED_OK;
     if (value) {
       if (int rc = m->variant == RCED_V1 ? frame16_enable<chain::NetV1>(m, m->fused) : frame16_enable<chain::NetV2>(m, m->fused))
         return rc;
@@ -790,8 +795,16 @@ int fused_set_option(rced_model* m, const char* key, int value) {
     m->fused->bf16 = value != 0;
     return RCED_OK;
   }
-  if (!strcmp(key, "bf16_frames")) {
-    if (m->variant == RCED_V3) return rced_fail(RCED_ERR_ARG, "bf16_frames selects the form of the bf16 R-CED V1 / V2 kernel only");
+  if (!strcmp(key, "v3_bf16")) {
+    if (m->variant != RCED_V3) return rced_fail(RCED_ERR_ARG, "v3_bf16 selects CR-CED's bf16 kernel; R-CED V1 / V2 take option \"bf16\"");
+    if (value != 0 && value != 1) return rced_fail(RCED_ERR_ARG, "v3_bf16 takes 0 or 1, got %d", value);
+    if (value) {
+      if (int rc = frame16_enable<chain::NetV3F16>(m, m->fused)) return rc;
+    }
+    m->fused->v3_bf16 = value;
+    return RCED_OK;
+  }
+  if (!strcmp(key, "bf16_frames")) {   // (takes effect in the bf16 modes: "bf16", CR-CED's "v3_bf16")
     if (value != 0 && value != 4 && value != 8) return rced_fail(RCED_ERR_ARG, "bf16_frames takes 0 (chosen per call), 4 or 8, got %d", value);
     m->fused->bf16_frames = value;
     return RCED_OK;
@@ -848,6 +861,10 @@ int fused_get_option(rced_model* m, const char* key, int* value) {
   }
   if (!strcmp(key, "bf16")) {
     *value = m->fused->bf16;
+    return RCED_OK;
+  }
+  if (!strcmp(key, "v3_bf16")) {
+    *value = m->fused->v3_bf16;
     return RCED_OK;
   }
   if (!strcmp(key, "latency_form")) {

@@ -57,6 +57,7 @@ struct LayerDesc {
   int cout, coutp;  // true / even-padded output channels
   int skip_from;    // layer whose output is added before the ReLU, or -1
   int saves_skip;   // 1 if a later layer adds this layer's output
+  int skip_post = 0;   // 1: the skip is added AFTER the ReLU, no ReLU behind it (CR-CED's block skips, model.py:75-76; frame16 only)
 };
 
 constexpr int even(int c) { return (c + 1) & ~1; }
@@ -68,6 +69,7 @@ struct NetV1 {
   static constexpr int kTF = 3;              // frames per tile
   static constexpr int kGap = 6;             // >= half width of the widest kernel (13)
   static constexpr int kFinalCh = 12;
+  static constexpr int kRingBytes = 0;       // frame16's weight-ring slot: 0 = the largest packet
   static constexpr LayerDesc layer[kMaxLayers] = {
       // channel strides 16 and 32 would put a tile's 16 pixels on 4 resp. 2 distinct LDS bank groups (4- / 8-way
       // conflicts on every B-operand read); 18 and 34 spread them over all banks at the price of 2 zero-weight
@@ -82,12 +84,30 @@ struct NetV2 {
   static constexpr int kTF = 3;
   static constexpr int kGap = 5;             // widest kernel 11
   static constexpr int kFinalCh = 10;
+  static constexpr int kRingBytes = 0;
   static constexpr LayerDesc layer[kMaxLayers] = {
       {1, 1, 11, 10, 10, -1, 1},   {10, 10, 7, 12, 12, -1, 1},  {12, 12, 5, 14, 14, -1, 1},
       {14, 14, 5, 15, 16, -1, 1},  {15, 16, 5, 19, 20, -1, 1},  {19, 20, 5, 21, 22, -1, 1},
       {21, 22, 7, 23, 24, -1, 1},  {23, 24, 11, 25, 26, -1, 0}, {25, 26, 7, 23, 24, 6, 0},
       {23, 24, 5, 21, 22, 5, 0},   {21, 22, 5, 19, 20, 4, 0},   {19, 20, 5, 15, 16, 3, 0},
       {15, 16, 5, 14, 14, 2, 0},   {14, 14, 7, 12, 12, 1, 0},   {12, 12, 11, 10, 10, 0, 0}};
+};
+
+// CR-CED's fifteen hidden layers (model.py:64-96: five blocks of 9 -> 18, 5 -> 30, 9 -> 8) for the bf16 wave-per-frame kernel
+// (kernels_frame16.h) ONLY: no tile geometry (kTF, kGap), so the fp32 chain kernel above does not take it -- CR-CED's fp32-quality
+// kernel is kernels_fused_v3.h.  CE2's and CE1's block outputs (layers 5, 2) are added to CD1's and CD2's (layers 11, 14) behind
+// the ReLU.  The three packets of a block are 6 + 8 + 9 KiB: a 17-KiB ring slot pairs them up (nine barriers per tile, not sixteen).
+struct NetV3F16 {
+  static constexpr int kVariant = 3;
+  static constexpr int kLayers = 15;         // decode_final (1x129) is the kernel's output layer
+  static constexpr int kFinalCh = 8;
+  static constexpr int kRingBytes = 17 * 1024;
+  static constexpr LayerDesc layer[kMaxLayers] = {
+      {1, 1, 9, 18, 18, -1, 0},     {18, 18, 5, 30, 30, -1, 0},   {30, 30, 9, 8, 8, -1, 1},
+      {8, 8, 9, 18, 18, -1, 0},     {18, 18, 5, 30, 30, -1, 0},   {30, 30, 9, 8, 8, -1, 1},
+      {8, 8, 9, 18, 18, -1, 0},     {18, 18, 5, 30, 30, -1, 0},   {30, 30, 9, 8, 8, -1, 0},
+      {8, 8, 9, 18, 18, -1, 0},     {18, 18, 5, 30, 30, -1, 0},   {30, 30, 9, 8, 8, 5, 0, 1},
+      {8, 8, 9, 18, 18, -1, 0},     {18, 18, 5, 30, 30, -1, 0},   {30, 30, 9, 8, 8, 2, 0, 1}};
 };
 
 // The same net with another number of frames per tile: geometry only (the packets do not depend on it).  Used by the fp32 kernel's

@@ -269,7 +269,9 @@ def build_model(net_work, is_training=False, dtype="float32", **kw):
     """The selection block of tester.py:76-82 / infer.py:45-51.
 
     dtype="bfloat16" (R-CED V1 / V2 only; BASELINE config 2) switches the fused kernel to bf16 activations and
-    weights -- outside the 1e-4 fp32 bar; the default is the reference's float32."""
+    weights -- outside the 1e-4 fp32 bar; the default is the reference's float32.  CR-CED ("FullyCNNV3") refuses
+    this dtype: its bf16 kernel is a per-handle option of the float32 model, `build_model("FullyCNNV3").set_option("v3_bf16", 1)`
+    (0 returns to the fp32-quality kernel)."""
     if net_work == "FullyCNNV2":
         m = FullyCNNSEModelV2(is_training, **kw)
     elif net_work == "FullyCNNV3":
