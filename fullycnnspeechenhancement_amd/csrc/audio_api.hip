@@ -16,14 +16,6 @@
 
 using namespace rced;
 
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess)                                                                      \
-      return rced_fail(e_ == hipErrorOutOfMemory ? RCED_ERR_ALLOC : RCED_ERR_HIP, "%s: %s", #expr, \
-                       hipGetErrorString(e_));                                                 \
-  } while (0)
-
 namespace {
 
 constexpr int kMaxDevices = 16;
@@ -36,6 +28,11 @@ struct AudioTables {   // per device, built once
   unsigned short* istft_x6[2] = {nullptr, nullptr};   // [nfft == 512]
   float* cim[2] = {nullptr, nullptr};
   float* chead[2] = {nullptr, nullptr};
+  void release() {   // of a build that failed half way
+    for (void* p : {(void*)stft, (void*)istft512, (void*)istft256, (void*)stft_x6}) (void)hipFree(p);
+    for (int v = 0; v < 2; ++v)
+      for (void* p : {(void*)istft_x6[v], (void*)cim[v], (void*)chead[v]}) (void)hipFree(p);
+  }
 };
 AudioTables g_tab[kMaxDevices];
 std::mutex g_mu;
@@ -75,20 +72,6 @@ std::vector<float> pack_istft(int nfft) {   // [st][mt][lane][e]; row = sample n
   return p;
 }
 
-inline unsigned short bf16_rne(float f) {
-  unsigned u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-inline void split3(float v, unsigned short* h, unsigned short* mm, unsigned short* l) {   // v = h + m + l to 2^-24
-  auto b2f = [](unsigned short b) { const unsigned u = (unsigned)b << 16; float f; memcpy(&f, &u, 4); return f; };
-  *h = bf16_rne(v);
-  const float r1 = v - b2f(*h);
-  *mm = bf16_rne(r1);
-  *l = bf16_rne(r1 - b2f(*mm));
-}
 // [mt][chunk][part][lane][8] bf16 from a coefficient function coef(row, k), k = 32 chunk + 8 (lane >> 4) + e
 template <class F>
 std::vector<unsigned short> pack_x6(int mtiles, F coef) {
@@ -99,7 +82,7 @@ std::vector<unsigned short> pack_x6(int mtiles, F coef) {
         for (int e = 0; e < 8; ++e) {
           const int row = 16 * mt + (lane & 15), k = 32 * c + 8 * (lane >> 4) + e;
           const size_t at = (size_t)mt * audio::x6::kPackPerMT + ((size_t)(c * 3) * 64 + lane) * 8 + e;
-          split3((float)coef(row, k), &p[at], &p[at + 512], &p[at + 1024]);
+          put3(p.data(), at, (float)coef(row, k));
         }
   return p;
 }
@@ -119,32 +102,21 @@ double istft_coef(int nfft, int n, int b, int c) {
   return (edge ? 1.0 : 2.0) / nfft / hamming(n) * (c ? -std::sin(th) : std::cos(th));
 }
 
-template <class T>
-int upload_raw(T** dev, const std::vector<T>& host) {
-  T* p = nullptr;
-  HIP_TRY(hipMalloc(&p, host.size() * sizeof(T)));
-  const hipError_t e = hipMemcpy(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(p);
-    return rced_fail(RCED_ERR_HIP, "hipMemcpy(audio tables): %s", hipGetErrorString(e));
-  }
-  *dev = p;
-  return RCED_OK;
-}
+constexpr const char* kWhat = "audio tables";
 
 int build_x6(AudioTables& t) {
-  if (int rc = upload_raw(&t.stft_x6, pack_x6(audio::x6::kStftMTx, stft_coef))) return rc;
+  if (int rc = upload(&t.stft_x6, pack_x6(audio::x6::kStftMTx, stft_coef), kWhat)) return rc;
   for (int v = 0; v < 2; ++v) {
     const int nfft = v ? 512 : 256;
     // rows = samples 128..255; slot k = 2b + c, slot 1 = re of bin 128
     auto coef = [&](int row, int k) { return k == 1 ? istft_coef(nfft, 128 + row, 128, 0) : istft_coef(nfft, 128 + row, k >> 1, k & 1); };
-    if (int rc = upload_raw(&t.istft_x6[v], pack_x6(audio::x6::kIstftMTx, coef))) return rc;
+    if (int rc = upload(&t.istft_x6[v], pack_x6(audio::x6::kIstftMTx, coef), kWhat)) return rc;
     std::vector<float> cim(128), head((size_t)2 * audio::kBins * 128);
     for (int r = 0; r < 128; ++r) cim[r] = (float)istft_coef(nfft, 128 + r, 128, 1);
     for (int k = 0; k < 2 * audio::kBins; ++k)
       for (int n = 0; n < 128; ++n) head[(size_t)k * 128 + n] = (float)istft_coef(nfft, n, k >> 1, k & 1);
-    if (int rc = upload_raw(&t.cim[v], cim)) return rc;
-    if (int rc = upload_raw(&t.chead[v], head)) return rc;
+    if (int rc = upload(&t.cim[v], cim, kWhat)) return rc;
+    if (int rc = upload(&t.chead[v], head, kWhat)) return rc;
   }
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(audio::x6::istft_x6_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      audio::x6::kIstftLdsBytes);
@@ -163,38 +135,30 @@ int range_split(int N, int T) {
   return s < nblk ? s : nblk;
 }
 
-int upload(float** dev, const std::vector<float>& host) {
-  HIP_TRY(hipMalloc(dev, host.size() * sizeof(float)));
-  HIP_TRY(hipMemcpy(*dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-  return RCED_OK;
+int build_tables(AudioTables& t) {
+  if (int rc = upload(&t.stft, pack_stft(), kWhat)) return rc;
+  if (int rc = upload(&t.istft512, pack_istft(512), kWhat)) return rc;
+  if (int rc = upload(&t.istft256, pack_istft(256), kWhat)) return rc;
+  return build_x6(t);
 }
 
+// A device's tables are built into a local and published last: g_tab[device].stft != nullptr means "all of them, and the LDS
+// attributes"; a failure half way frees what was built and leaves the entry empty for the next call to try again.
 int tables(int device, AudioTables** out) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-    return rced_fail(RCED_ERR_HIP, "no HIP device visible (this library has no CPU fallback)");
-  if (device < 0 || device >= n || device >= kMaxDevices) return rced_fail(RCED_ERR_ARG, "device %d out of range", device);
+  if (int rc = check_device(device, kMaxDevices)) return rc;
   std::lock_guard<std::mutex> lk(g_mu);
-  AudioTables& t = g_tab[device];
-  if (!t.stft) {
-    if (int rc = upload(&t.stft, pack_stft())) return rc;
-    if (int rc = upload(&t.istft512, pack_istft(512))) return rc;
-    if (int rc = upload(&t.istft256, pack_istft(256))) return rc;
-    if (int rc = build_x6(t)) return rc;
+  AudioTables& pub = g_tab[device];
+  if (!pub.stft) {
+    AudioTables t;
+    if (int rc = build_tables(t)) {
+      t.release();
+      return rc;
+    }
+    pub = t;
   }
-  *out = &t;
+  *out = &pub;
   return RCED_OK;
 }
-
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) { prev = -1; return; }
-    ok = (prev == dev) || (hipSetDevice(dev) == hipSuccess);
-  }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
 }  // namespace
 

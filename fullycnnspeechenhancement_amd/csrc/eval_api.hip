@@ -2,7 +2,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstring>
 #include <map>
 #include <mutex>
 #include <vector>
@@ -13,14 +12,6 @@
 #include "rced_internal.h"
 
 using namespace rced;
-
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess)                                                                      \
-      return rced_fail(e_ == hipErrorOutOfMemory ? RCED_ERR_ALLOC : RCED_ERR_HIP, "%s: %s", #expr, \
-                       hipGetErrorString(e_));                                                 \
-  } while (0)
 
 namespace {
 
@@ -35,14 +26,6 @@ struct Workspace {
 enum { kWsSlices = 0, kWsStoi = 1 };      // STOI keeps a buffer of its own: it never moves the one SDR / the mix captured
 std::map<void*, Workspace> g_ws[2][kMaxDevices];
 std::mutex g_mu;
-
-int check_device(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-    return rced_fail(RCED_ERR_HIP, "no HIP device visible (this library has no CPU fallback)");
-  if (device < 0 || device >= n || device >= kMaxDevices) return rced_fail(RCED_ERR_ARG, "device %d out of range", device);
-  return RCED_OK;
-}
 
 int workspace(int device, void* stream, size_t bytes, double** out, int which = kWsSlices) {
   std::lock_guard<std::mutex> lk(g_mu);
@@ -59,16 +42,6 @@ int workspace(int device, void* stream, size_t bytes, double** out, int which = 
   *out = w.p;
   return RCED_OK;
 }
-
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) { prev = -1; return; }
-    ok = (prev == dev) || (hipSetDevice(dev) == hipSuccess);
-  }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
 // ---- STOI tables: built on the host once per process, uploaded once per device ---------------------------------------------------
 struct StoiTables {
@@ -110,19 +83,6 @@ std::vector<double> stoi_taps() {
   return h;
 }
 
-unsigned short bf16_rne(float f) {
-  unsigned u;
-  std::memcpy(&u, &f, 4);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-float bf16_f(unsigned short b) {
-  const unsigned u = (unsigned)b << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
 // row 4 q + {0, 1, 2, 3} = re, im of the first bin of pair slot q, re, im of its second (kernels_stoi.h); k = sample 0 .. 255
 double stoi_coef(int row, int k) {
   const int q = row >> 2, second = (row >> 1) & 1, im = row & 1;
@@ -149,25 +109,17 @@ int stoi_tables(int device, StoiTables** out) {
       for (int c = 0; c < stoi::kChunks; ++c)
         for (int lane = 0; lane < 64; ++lane)
           for (int e = 0; e < 8; ++e) {
-            const float v = (float)stoi_coef(16 * mt + (lane & 15), 32 * c + 8 * (lane >> 4) + e);
             const size_t at = (size_t)mt * stoi::kPackPerMT + ((size_t)(c * 3) * 64 + lane) * 8 + e;
-            pack[at] = bf16_rne(v);
-            const float r1 = v - bf16_f(pack[at]);
-            pack[at + 512] = bf16_rne(r1);
-            pack[at + 1024] = bf16_rne(r1 - bf16_f(pack[at + 512]));
+            put3(pack.data(), at, (float)stoi_coef(16 * mt + (lane & 15), 32 * c + 8 * (lane >> 4) + e));
           }
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(stoi::band_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 stoi::kBandLdsBytes));
     double* dt = nullptr;
     unsigned short* dp = nullptr;
-    HIP_TRY(hipMalloc(&dt, tab.size() * sizeof(double)));
-    hipError_t e = hipMalloc(&dp, pack.size() * sizeof(unsigned short));
-    if (e == hipSuccess) e = hipMemcpy(dt, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dp, pack.data(), pack.size() * sizeof(unsigned short), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
+    if (int rc = upload(&dt, tab, "STOI tables")) return rc;
+    if (int rc = upload(&dp, pack, "STOI tables")) {
       (void)hipFree(dt);
-      if (dp) (void)hipFree(dp);
-      return rced_fail(e == hipErrorOutOfMemory ? RCED_ERR_ALLOC : RCED_ERR_HIP, "STOI tables: %s", hipGetErrorString(e));
+      return rc;
     }
     t.apack = dp;
     t.tab = dt;
@@ -191,7 +143,7 @@ int rced_stoi(const float* ref_dev, int ref_stride, const float* est_dev, int es
   const int cap = ref_stride < est_stride ? ref_stride : est_stride;
   if (cap > stoi::kMaxLen) return rced_fail(RCED_ERR_ARG, "rows longer than 2^28 samples");
   if (N == 0) return RCED_OK;
-  if (int rc = check_device(device)) return rc;
+  if (int rc = check_device(device, kMaxDevices)) return rc;
   DeviceGuard g(device);
   if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
   StoiTables* t = nullptr;
@@ -246,7 +198,7 @@ int rced_sdr(const float* ref_dev, int ref_stride, const float* est_dev, int est
   const int cap = ref_stride < est_stride ? ref_stride : est_stride;
   if (cap > eval::kMaxLen) return rced_fail(RCED_ERR_ARG, "rows longer than 2^30 samples");
   if (N == 0) return RCED_OK;
-  if (int rc = check_device(device)) return rc;
+  if (int rc = check_device(device, kMaxDevices)) return rc;
   DeviceGuard g(device);
   if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
   const int slices = eval::num_slices(cap) > 0 ? eval::num_slices(cap) : 1;
@@ -272,7 +224,7 @@ int rced_mix_snr(const float* speech_dev, const int* speech_len_dev, int N, int 
   if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
   if (Ls > eval::kMaxLen || Ln > eval::kMaxLen) return rced_fail(RCED_ERR_ARG, "rows longer than 2^30 samples");
   if (N == 0 || Ls == 0) return RCED_OK;
-  if (int rc = check_device(device)) return rc;
+  if (int rc = check_device(device, kMaxDevices)) return rc;
   DeviceGuard g(device);
   if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
   const int slices = eval::num_slices(Ls);

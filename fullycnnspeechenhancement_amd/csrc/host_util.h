@@ -1,0 +1,84 @@
+// Host-side helpers every translation unit of the library shares: error return, device selection, vector upload, and the bf16
+// roundings behind every packed three-part A-fragment stream.  Host only: no device code, no kernel header.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cstddef>
+#include <cstring>
+#include <vector>
+
+#include "../../include/rced.h"
+
+int rced_fail(int code, const char* fmt, ...);   // rced_api.hip: sets the thread's error text, returns `code`
+
+#define HIP_TRY(expr)                                                                          \
+  do {                                                                                         \
+    hipError_t e_ = (expr);                                                                    \
+    if (e_ != hipSuccess)                                                                      \
+      return rced_fail(e_ == hipErrorOutOfMemory ? RCED_ERR_ALLOC : RCED_ERR_HIP, "%s: %s", #expr, \
+                       hipGetErrorString(e_));                                                 \
+  } while (0)
+
+struct DeviceGuard {  // run on the given device, restore the caller's current device after
+  int prev = -1;
+  bool ok = false;
+  explicit DeviceGuard(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) { prev = -1; return; }
+    ok = (prev == dev) || (hipSetDevice(dev) == hipSuccess);
+  }
+  ~DeviceGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+// Is there a device, is the index one of them; `limit`: the length of a per-device table the caller indexes with it
+inline int check_device(int device, int limit = INT_MAX) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
+    return rced_fail(RCED_ERR_HIP, "no HIP device visible (this library has no CPU fallback)");
+  if (n > limit) n = limit;
+  if (device < 0 || device >= n) return rced_fail(RCED_ERR_ARG, "device %d out of range [0,%d)", device, n);
+  return RCED_OK;
+}
+
+// A host vector as a fresh device allocation.  *dev is written only after the copy succeeded (a caller may test it for "built");
+// on failure the allocation is freed.
+template <class T>
+int upload(T** dev, const std::vector<T>& host, const char* what) {
+  T* p = nullptr;
+  HIP_TRY(hipMalloc(&p, host.size() * sizeof(T)));
+  const hipError_t e = hipMemcpy(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(p);
+    return rced_fail(RCED_ERR_HIP, "hipMemcpy(%s): %s", what, hipGetErrorString(e));
+  }
+  *dev = p;
+  return RCED_OK;
+}
+
+inline unsigned short bf16_rne(float f) {   // round to nearest even
+  unsigned u;
+  memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;   // NaN
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (unsigned short)(u >> 16);
+}
+inline float bf16_to_float(unsigned short b) {
+  const unsigned u = (unsigned)b << 16;
+  float f;
+  memcpy(&f, &u, 4);
+  return f;
+}
+
+// three bf16 parts of a value (round to nearest at every step): v = h + m + l to 2^-24
+inline void split3(float v, unsigned short* h, unsigned short* mm, unsigned short* l) {
+  *h = bf16_rne(v);
+  const float r1 = v - bf16_to_float(*h);
+  *mm = bf16_rne(r1);
+  *l = bf16_rne(r1 - bf16_to_float(*mm));
+}
+// ... stored into a [part][lane][8] bf16 tile: slot `at` of the parts h, m, l
+inline void put3(unsigned short* d, size_t at, float v, size_t part_stride = 512) {
+  split3(v, &d[at], &d[at + part_stride], &d[at + 2 * part_stride]);
+}

@@ -16,14 +16,6 @@
 
 using namespace rced;
 
-inline unsigned short bf16_rne(float f) {
-  unsigned u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;   // NaN
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-
 inline int env_default(const char* name, int dflt) {   // an environment variable as the DEFAULT of a per-handle option
   const char* e = getenv(name);
   return e ? atoi(e) : dflt;
@@ -31,11 +23,9 @@ inline int env_default(const char* name, int dflt) {   // an environment variabl
 struct rced_fused {
   float* scratch = nullptr;   // V1/V2: skip fragments, per workgroup
   size_t scratch_bytes = 0;
-  float* wpack = nullptr;     // packed A-fragment stream (CR-CED: of the F32 form, built when that form is first selected)
-  float* wpack_x6 = nullptr;  // CR-CED, X6 form (v3::kGTotal floats; built when that form is first selected)
-  float* wpack_t = nullptr;   // CR-CED, fused form (v3::kTTotal floats)
-  float* wpack_a = nullptr;   // CR-CED, all-x6 form (v3::kATotal floats)
-  float* fin_tab = nullptr;   // ... its decode_final tap table (v3::kFinTFloats)
+  float* wpack = nullptr;     // R-CED V1 / V2: packed A-fragment stream
+  float* wpack_v3[4] = {};    // CR-CED: the stream of form "v3_l2x6" (kV3Forms), built when that form is first selected
+  float* fin_tab = nullptr;   // ... the all-x6 form's decode_final tap table (v3::kFinTFloats)
   // Per-handle options of the R-CED output layer's kernel; the environment variables of the same meaning only supply the
   // defaults, read when the handle is created (rced_create), never afterwards.
   int final_x6 = 1;           // option "final_x6" (default: RCED_FINAL_X6): 1 = x6::final_gemm_x6_kernel (three-part bf16 products), 0 = fp32 MFMA
@@ -61,35 +51,31 @@ struct rced_fused {
   unsigned* err_dev = nullptr;    // kernel reaches through its device alias, so the host reads it without a device sync
 };
 
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess)                                                                      \
-      return rced_fail(e_ == hipErrorOutOfMemory ? RCED_ERR_ALLOC : RCED_ERR_HIP, "%s: %s", #expr, \
-                       hipGetErrorString(e_));                                                 \
-  } while (0)
-
 namespace {
+
+constexpr const char* kWhat = "weights";   // what an upload's error text says it was copying
 
 // BN-folded weight of layer L: [kh,kw,cin,cout4] host copy
 inline float wq(const rced_layer_dev& d, int tap, int ci, int co, int cin) {
   return d.host_w[((size_t)tap * cin + ci) * d.cout4 + co];
 }
 
-// three bf16 parts of a weight (round to nearest at every step): v = h + m + l to 2^-24
-inline void split3(float v, unsigned short* h, unsigned short* mm, unsigned short* l) {
-  auto b2f = [](unsigned short b) { const unsigned u = (unsigned)b << 16; float f; memcpy(&f, &u, 4); return f; };
-  *h = bf16_rne(v);
-  const float r1 = v - b2f(*h);
-  *mm = bf16_rne(r1);
-  *l = bf16_rne(r1 - b2f(*mm));
-}
+// The forms of the CR-CED kernel (kernels_fused_v3.h), by the value of option "v3_l2x6": 3 (the product) and 0 (the bit-exact
+// fp32-MFMA comparator); 1 and 2 in legacy builds only.  A row without functions: a form this build does not hold.
+struct V3Form {
+  int stream_floats;   // of its weight stream (pack_v3)
+  int lds_bytes;       // dynamic LDS of a launch
+  int (*set_lds)();    // allows the kernel that much
+  void (*launch)(int grid, hipStream_t st, const v3::Params& P);
+};
+extern const V3Form kV3Forms[4];   // defined at the end of this file, see there
+inline bool v3_form_built(int form) { return form >= 0 && form < 4 && kV3Forms[form].launch; }
 
 // CR-CED weight streams (kernels_fused_v3.h, "packed weight streams").  x6 = false: one LDS packet per layer (F32 form);
 // x6 = true: layer 1 / layer 2 as register images for 16-byte-per-lane global loads, layer 3's packet unchanged.
 void pack_v3(const rced_model* m, int form, std::vector<float>* wpack) {
   const bool x6 = form != 0, fusedf = form >= 2, allx6 = form == 3;
-  wpack->assign(allx6 ? v3::kATotal : fusedf ? v3::kTTotal : x6 ? v3::kGTotal : v3::kWTotal, 0.f);
+  wpack->assign(kV3Forms[form].stream_floats, 0.f);
   auto put_shift = [&](float* at, int layer) {  // the packet's last 32 floats: shift[co]
     const int cout = m->net->layer[layer].cout;
     for (int c = 0; c < cout; ++c) at[c] = m->layers[layer].host_shift[c];
@@ -131,7 +117,7 @@ void pack_v3(const rced_model* m, int form, std::vector<float>* wpack) {
           for (int c = 0; c < (allx6 ? 2 : 3); ++c) {
             const int tap = 4 * c + kq;
             const size_t base = (size_t)(c * 3) * 512 + lane * 8 + e;
-            split3(tap < 9 ? w1x(tap, e, i) : 0.f, &d16[base], &d16[base + 512], &d16[base + 1024]);
+            put3(d16, base, tap < 9 ? w1x(tap, e, i) : 0.f);
           }
           if (allx6) {
             // tap 8 folded: pieces 6, 7 = the fragments F1, F2 whose k-quad selects a three-part PRODUCT (layer1_x6l): the part of
@@ -147,7 +133,7 @@ void pack_v3(const rced_model* m, int form, std::vector<float>* wpack) {
           for (int c = 0; c < 4; ++c) {
             const int r = i >> 1, co = 16 + (i & 1), tap = 4 * c + kq - r;
             const size_t base = (size_t)(rem0 + c * 3) * 512 + lane * 8 + e;
-            split3((tap >= 0 && tap < 9) ? w1x(tap, e, co) : 0.f, &d16[base], &d16[base + 512], &d16[base + 1024]);
+            put3(d16, base, (tap >= 0 && tap < 9) ? w1x(tap, e, co) : 0.f);
           }
         }
       put_shift(dst + (allx6 ? v3::kG1AMain : v3::kG1XMain) + v3::kG1XRem, 3 * blk + 0);
@@ -200,7 +186,7 @@ void pack_v3(const rced_model* m, int form, std::vector<float>* wpack) {
           for (int lane = 0; lane < 64; ++lane)
             for (int e = 0; e < 8; ++e) {
               const size_t base = ((size_t)(c * 2 + mt) * 3) * 512 + lane * 8 + e;
-              split3(w2x(lane & 15, mt, c, lane >> 4, e), &d16[base], &d16[base + 512], &d16[base + 1024]);
+              put3(d16, base, w2x(lane & 15, mt, c, lane >> 4, e));
             }
       put_shift(dst + v3::kG2Data, 3 * blk + 1);
       dst += v3::kG2;
@@ -232,7 +218,7 @@ void pack_v3(const rced_model* m, int form, std::vector<float>* wpack) {
             const int ci = e < 4 ? 4 * kq + e : 16 + 4 * kq + (e - 4);
             const float w = (tap < 9 && ci < 30) ? wq(l3, tap, ci, co, 30) : 0.f;
             const size_t base = ((size_t)j * 3) * 512 + lane * 8 + e;
-            split3(w, &d16[base], &d16[base + 512], &d16[base + 1024]);
+            put3(d16, base, w);
           }
       put_shift(dst + v3::kW3TData, 3 * blk + 2);
       dst += v3::kW3T;
@@ -281,13 +267,8 @@ void pack_v3_fintab(const rced_model* m, std::vector<float>* tab) {
   unsigned short* d16 = reinterpret_cast<unsigned short*>(tab->data());
   constexpr int kPart16 = v3::kFinTPart / 2;
   for (int t = 0; t < 129; ++t)
-    for (int c = 0; c < 8; ++c) {
-      const size_t at = (size_t)(t + 15) * 8 + c;
-      split3(wq(lf, t, c, 0, 8), &d16[at], &d16[at + kPart16], &d16[at + 2 * kPart16]);
-    }
+    for (int c = 0; c < 8; ++c) put3(d16, (size_t)(t + 15) * 8 + c, wq(lf, t, c, 0, 8), kPart16);
 }
-
-int upload(float** dev, const std::vector<float>& host);
 
 // ---- R-CED V1 / V2 (kernels_fused_chain.h) ---------------------------------------------------
 template <class N>
@@ -358,6 +339,21 @@ void pack_chain(const rced_model* m, std::vector<float>* wpack, std::vector<floa
   *fin_bias = lf.host_shift[0];
 }
 
+// the output layer's A[f, k] once more, every value as three bf16 parts in K-32 fragment order (kernels_final_x6.h)
+template <int CH>
+void pack_final_x6(const rced_layer_dev& lf, std::vector<unsigned short>* p) {
+  using X = x6::FinalX6<CH>;
+  p->assign(X::kPackShorts, 0);
+  for (int S = 0; S < X::kSteps; ++S)
+    for (int mt = 0; mt < X::kMT; ++mt)
+      for (int lane = 0; lane < 64; ++lane)
+        for (int e = 0; e < 8; ++e) {
+          const int k = 32 * S + 8 * (lane >> 4) + e, fo = 16 * mt + (lane & 15), fp = k / CH, ci = k % CH, tap = fp - fo + 64;
+          const float v = (k < X::kK && fo < 129 && tap >= 0 && tap < 129) ? wq(lf, tap, ci, 0, CH) : 0.f;
+          put3(p->data(), ((size_t)(S * X::kMT + mt) * 3) * 512 + lane * 8 + e, v);
+        }
+}
+
 template <int CH>
 void chain_final_layer(const rced_fused* f, float* y, int frames, hipStream_t st) {
   const dim3 grid((frames + chain::kFinFrames - 1) / chain::kFinFrames);
@@ -417,34 +413,13 @@ template <class N>
 int chain_create(rced_model* m, rced_fused* f) {
   using G = chain::Geo<N>;
   std::vector<float> wpack, fin;
+  std::vector<unsigned short> fin_x6;
   pack_chain<N>(m, &wpack, &fin, &f->fin_bias);
-  int rc = upload(&f->wpack, wpack);
-  if (!rc) rc = upload(&f->fin_apack, fin);
+  pack_final_x6<N::kFinalCh>(m->layers[N::kLayers], &fin_x6);
+  int rc = upload(&f->wpack, wpack, kWhat);
+  if (!rc) rc = upload(&f->fin_apack, fin, kWhat);
+  if (!rc) rc = upload(&f->fin_apack_x6, fin_x6, kWhat);
   if (rc) return rc;
-  {  // the output layer's A[f, k] once more, every value as three bf16 parts in K-32 fragment order (kernels_final_x6.h)
-    constexpr int CH = N::kFinalCh;
-    using X = x6::FinalX6<CH>;
-    const rced_layer_dev& lf = m->layers[N::kLayers];
-    std::vector<unsigned short> p(X::kPackShorts, 0);
-    auto b2f = [](unsigned short b) { const unsigned u = (unsigned)b << 16; float v; memcpy(&v, &u, 4); return v; };
-    for (int S = 0; S < X::kSteps; ++S)
-      for (int mt = 0; mt < X::kMT; ++mt)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int e = 0; e < 8; ++e) {
-            const int k = 32 * S + 8 * (lane >> 4) + e, fo = 16 * mt + (lane & 15), fp = k / CH, ci = k % CH, tap = fp - fo + 64;
-            const float v = (k < X::kK && fo < 129 && tap >= 0 && tap < 129) ? wq(lf, tap, ci, 0, CH) : 0.f;
-            const unsigned short h = bf16_rne(v);
-            const float r1 = v - b2f(h);
-            const unsigned short mm = bf16_rne(r1);
-            const unsigned short l = bf16_rne(r1 - b2f(mm));
-            const size_t base = ((size_t)(S * X::kMT + mt) * 3) * 512 + lane * 8 + e;
-            p[base] = h;
-            p[base + 512] = mm;
-            p[base + 1024] = l;
-          }
-    HIP_TRY(hipMalloc(&f->fin_apack_x6, p.size() * sizeof(unsigned short)));
-    HIP_TRY(hipMemcpy(f->fin_apack_x6, p.data(), p.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-  }
   f->scratch_bytes = (size_t)m->num_cus * G::kScratchFloatsPerWg * sizeof(float);
   HIP_TRY(hipMalloc(&f->scratch, f->scratch_bytes));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(chain::fused_chain_kernel<N>),
@@ -518,11 +493,7 @@ int frame16_enable(rced_model* m, rced_fused* f) {
   std::vector<unsigned> wpack;
   pack_frame16<N>(m, &wpack);
   unsigned* wdev = nullptr;
-  HIP_TRY(hipMalloc(&wdev, wpack.size() * sizeof(unsigned)));
-  if (hipMemcpy(wdev, wpack.data(), wpack.size() * sizeof(unsigned), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(wdev);
-    return rced_fail(RCED_ERR_HIP, "hipMemcpy(bf16 packets)");
-  }
+  if (int rc = upload(&wdev, wpack, "bf16 packets")) return rc;
   if (int rc = frame16_prepare<N, 4>(m, &f->bf16_wgs_per_cu)) { (void)hipFree(wdev); return rc; }
   int one = 1;
   if (int rc = frame16_prepare<N, 8>(m, &one)) { (void)hipFree(wdev); return rc; }
@@ -572,63 +543,29 @@ int frame16_forward(rced_model* m, rced_fused* f, const float* x, float* y, int 
   return w == 8 ? frame16_launch<N, 8>(m, f, x, y, Nb, T, st) : frame16_launch<N, 4>(m, f, x, y, Nb, T, st);
 }
 
-int upload(float** dev, const std::vector<float>& host) {   // *dev is set only when the copy succeeded
-  float* p = nullptr;
-  HIP_TRY(hipMalloc(&p, host.size() * sizeof(float)));
-  const hipError_t e = hipMemcpy(p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(p);
-    return rced_fail(RCED_ERR_HIP, "hipMemcpy(weights): %s", hipGetErrorString(e));
-  }
-  *dev = p;
-  return RCED_OK;
-}
-
 }  // namespace
 
-// tools/summarize_prof.py prints these next to a profile (the kernel-trace CSV reports 0 for dynamic LDS)
-static_assert(v3::MapA::kLdsBytes == 159424 && v3::MapF32::kLdsBytes == 163024, "update DYNAMIC_LDS in tools/summarize_prof.py");
-#if RCED_V3_LEGACY_FORMS
-static_assert(v3::MapT::kLdsBytes == 163792 && v3::MapX6::kLdsBytes == 162976, "update DYNAMIC_LDS in tools/summarize_prof.py");
-#endif
-// forms of the CR-CED kernel this build holds: 3 (the product) and 0 (the bit-exact fp32-MFMA comparator); 1 and 2 in legacy builds only
-inline bool v3_form_built(int form) { return form == 0 || form == 3 || (RCED_V3_LEGACY_FORMS && (form == 1 || form == 2)); }
-template <class M>
-int v3_set_lds() {
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(v3::fused_v3_kernel<M>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, M::kLdsBytes);
-  if (e != hipSuccess) return rced_fail(RCED_ERR_HIP, "hipFuncSetAttribute(LDS %d): %s", M::kLdsBytes, hipGetErrorString(e));
-  return RCED_OK;
-}
 // option "v3_l2x6": a form's weight stream is built when it is first selected
 // (a form counts as built only when its upload AND its LDS attribute succeeded -- the device pointer is published last)
 int v3_enable_form(rced_model* m, rced_fused* f, int form) {
   if (!v3_form_built(form)) return rced_fail(RCED_ERR_ARG, "v3_l2x6 takes 3 (the product: every layer at fp32 quality on the bf16 matrix pipe) or 0 (every "
                                                          "layer on the fp32 MFMA, the bit-exact comparator), got %d", form);
-  float** dev = form == 0 ? &f->wpack : form == 1 ? &f->wpack_x6 : form == 2 ? &f->wpack_t : &f->wpack_a;
-  if (*dev) return RCED_OK;
+  if (f->wpack_v3[form]) return RCED_OK;
   std::vector<float> wpack;
   pack_v3(m, form, &wpack);
   float* fresh = nullptr;
-  int rc = upload(&fresh, wpack);
+  int rc = upload(&fresh, wpack, kWhat);
   if (!rc && form == 3 && !f->fin_tab) {
     std::vector<float> tab;
     pack_v3_fintab(m, &tab);
-    rc = upload(&f->fin_tab, tab);
-    if (rc && f->fin_tab) {
-      (void)hipFree(f->fin_tab);
-      f->fin_tab = nullptr;
-    }
+    rc = upload(&f->fin_tab, tab, kWhat);
   }
-#if RCED_V3_LEGACY_FORMS
-  if (!rc && (form == 1 || form == 2)) rc = form == 1 ? v3_set_lds<v3::MapX6>() : v3_set_lds<v3::MapT>();
-#endif
-  if (!rc && (form == 0 || form == 3)) rc = form == 0 ? v3_set_lds<v3::MapF32>() : v3_set_lds<v3::MapA>();
+  if (!rc) rc = kV3Forms[form].set_lds();
   if (rc) {
     if (fresh) (void)hipFree(fresh);
     return rc;
   }
-  *dev = fresh;
+  f->wpack_v3[form] = fresh;
   return RCED_OK;
 }
 
@@ -645,7 +582,7 @@ int fused_create(rced_model* m) {
   }
   std::vector<float> fin;
   pack_v3_final(m, &fin, &f->fin_bias);
-  int rc = upload(&f->fin_apack, fin);
+  int rc = upload(&f->fin_apack, fin, kWhat);
   if (!rc) {   // the environment only supplies the DEFAULT of the per-handle option
     const int form = env_default("RCED_V3_L2X6", 3);
     f->v3_l2x6 = v3_form_built(form) ? form : 3;
@@ -674,9 +611,8 @@ void fused_destroy(rced_model* m) {
   rced_fused* f = m->fused;
   if (!f) return;
   if (f->wpack) (void)hipFree(f->wpack);
-  if (f->wpack_x6) (void)hipFree(f->wpack_x6);
-  if (f->wpack_t) (void)hipFree(f->wpack_t);
-  if (f->wpack_a) (void)hipFree(f->wpack_a);
+  for (float* p : f->wpack_v3)
+    if (p) (void)hipFree(p);
   if (f->fin_tab) (void)hipFree(f->fin_tab);
   if (f->wpack16) (void)hipFree(f->wpack16);
   if (f->fin_apack_x6) (void)hipFree(f->fin_apack_x6);
@@ -733,7 +669,7 @@ int fused_forward(rced_model* m, const float* x, float* y, int N, int T, hipStre
   P.err = f->err_dev;
   P.x = x;
   P.y = y;
-  P.wpack = f->v3_l2x6 == 3 ? f->wpack_a : f->v3_l2x6 == 2 ? f->wpack_t : f->v3_l2x6 ? f->wpack_x6 : f->wpack;
+  P.wpack = f->wpack_v3[f->v3_l2x6];
   P.fin = f->v3_l2x6 == 3 ? f->fin_tab : f->fin_apack;
   P.fin_bias = f->fin_bias;
   P.N = N;
@@ -744,12 +680,7 @@ int fused_forward(rced_model* m, const float* x, float* y, int N, int T, hipStre
   const int cus = f->grid_limit > 0 ? f->grid_limit : m->num_cus;
   const int grid = std::min(P.total_tiles, cus);
   m->prof_begin(RCED_K_FUSED, st);   // all 16 layers: decode_final is the kernel's last phase
-  if (f->v3_l2x6 == 3) hipLaunchKernelGGL(v3::fused_v3_kernel<v3::MapA>, dim3(grid), dim3(v3::kThreads), v3::MapA::kLdsBytes, st, P);
-#if RCED_V3_LEGACY_FORMS
-  else if (f->v3_l2x6 == 2) hipLaunchKernelGGL(v3::fused_v3_kernel<v3::MapT>, dim3(grid), dim3(v3::kThreads), v3::MapT::kLdsBytes, st, P);
-  else if (f->v3_l2x6 == 1) hipLaunchKernelGGL(v3::fused_v3_kernel<v3::MapX6>, dim3(grid), dim3(v3::kThreads), v3::MapX6::kLdsBytes, st, P);
-#endif
-  else hipLaunchKernelGGL(v3::fused_v3_kernel<v3::MapF32>, dim3(grid), dim3(v3::kThreads), v3::MapF32::kLdsBytes, st, P);
+  kV3Forms[f->v3_l2x6].launch(grid, st, P);
   m->prof_end(RCED_K_FUSED, st);
   HIP_TRY(hipGetLastError());
   return RCED_OK;
@@ -873,3 +804,38 @@ int fused_get_option(rced_model* m, const char* key, int* value) {
   }
   return RCED_ERR_ARG;
 }
+
+// ---- the table of CR-CED kernel forms (struct V3Form) ----------------------------------------------
+namespace {
+template <class M>
+struct V3FormOf {
+  static int set_lds() {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(v3::fused_v3_kernel<M>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, M::kLdsBytes);
+    if (e != hipSuccess) return rced_fail(RCED_ERR_HIP, "hipFuncSetAttribute(LDS %d): %s", M::kLdsBytes, hipGetErrorString(e));
+    return RCED_OK;
+  }
+  static void launch(int grid, hipStream_t st, const v3::Params& P) {
+    hipLaunchKernelGGL(v3::fused_v3_kernel<M>, dim3(grid), dim3(v3::kThreads), M::kLdsBytes, st, P);
+  }
+  static constexpr V3Form row(int stream_floats) { return {stream_floats, M::kLdsBytes, set_lds, launch}; }
+};
+// The compiler lays the kernels out in the code object in the order their first users are instantiated.  Defined here, behind every
+// other use of a kernel in this file, and with the product's row named first, the table puts the CR-CED kernels last, Map<3> before Map<0>.
+constexpr V3Form kV3Product = V3FormOf<v3::MapA>::row(v3::kATotal);
+constexpr V3Form kV3Forms[4] = {
+    V3FormOf<v3::MapF32>::row(v3::kWTotal),
+#if RCED_V3_LEGACY_FORMS
+    V3FormOf<v3::MapX6>::row(v3::kGTotal),
+    V3FormOf<v3::MapT>::row(v3::kTTotal),
+#else
+    {},
+    {},
+#endif
+    kV3Product,
+};
+}  // namespace
+// tools/summarize_prof.py prints these next to a profile (the kernel-trace CSV reports 0 for dynamic LDS)
+static_assert(kV3Forms[3].lds_bytes == 159424 && kV3Forms[0].lds_bytes == 163024, "update DYNAMIC_LDS in tools/summarize_prof.py");
+static_assert(!kV3Forms[2].launch || (kV3Forms[2].lds_bytes == 163792 && kV3Forms[1].lds_bytes == 162976),
+              "update DYNAMIC_LDS in tools/summarize_prof.py");

@@ -28,7 +28,6 @@ namespace {
 
 thread_local std::string g_err;
 
-#define fail rced_fail
 }  // namespace
 
 int rced_fail(int code, const char* fmt, ...) {
@@ -43,49 +42,19 @@ int rced_fail(int code, const char* fmt, ...) {
 
 namespace {
 
-#define HIP_TRY(expr)                                                                       \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess)                                                                   \
-      return fail(e_ == hipErrorOutOfMemory ? RCED_ERR_ALLOC : RCED_ERR_HIP, "%s: %s", #expr, \
-                  hipGetErrorString(e_));                                                   \
-  } while (0)
-
-struct DeviceGuard {  // run on the model's device, restore the caller's current device after
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) { prev = -1; return; }
-    ok = (prev == dev) || (hipSetDevice(dev) == hipSuccess);
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
-int check_device(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-    return fail(RCED_ERR_HIP, "no HIP device visible (this library has no CPU fallback)");
-  if (device < 0 || device >= n) return fail(RCED_ERR_ARG, "device %d out of range [0,%d)", device, n);
-  return RCED_OK;
-}
-
 // Fold inference BatchNorm into the conv (module.py:27-29): w' = w*s, shift = (b-mean)*s+beta,
-// s = gamma / sqrt(var + eps).  Done in double, rounded once to fp32.
-void fold_layer(const NetSpec& net, int i, const float* p, std::vector<float>* w4, std::vector<float>* shift4,
-                int* cout4_out) {
-  const LayerSpec& l = net.layer[i];
-  const int cin = layer_cin(net, i), cout = l.cout, cout4 = (cout + 3) & ~3;
-  const size_t kelems = (size_t)l.kh * l.kw * cin;
-  const float* kernel = p;
-  const float* bias = p + kelems * cout;
-  const float* bn = l.use_norm ? bias + cout : nullptr;
+// s = gamma / sqrt(var + eps).  Done in double, rounded once to fp32.  kernel [kelems][cout], bn = gamma, beta, moving mean,
+// moving variance ([cout] each) or null; w4 [kelems][cout4], shift4 [cout4], cout4 = cout rounded up to 4.
+// Returns -1, or the first channel whose variance does not make sqrt(var + eps) real.
+int fold_bn(const float* kernel, const float* bias, const float* bn, size_t kelems, int cout, std::vector<float>* w4,
+            std::vector<float>* shift4) {
+  const int cout4 = (cout + 3) & ~3;
   w4->assign(kelems * cout4, 0.f);
   shift4->assign(cout4, 0.f);
   for (int c = 0; c < cout; ++c) {
     double s = 1.0, sh = bias[c];
     if (bn) {
+      if (bn[3 * cout + c] + kBnEps <= 0.f) return c;
       const double g = bn[c], be = bn[cout + c], mu = bn[2 * cout + c], var = bn[3 * cout + c];
       s = g / std::sqrt(var + (double)kBnEps);
       sh = ((double)bias[c] - mu) * s + be;
@@ -93,14 +62,14 @@ void fold_layer(const NetSpec& net, int i, const float* p, std::vector<float>* w
     (*shift4)[c] = (float)sh;
     for (size_t k = 0; k < kelems; ++k) (*w4)[k * cout4 + c] = (float)((double)kernel[k * cout + c] * s);
   }
-  *cout4_out = cout4;
+  return -1;
 }
 
 int launch_generic(const float* x, float* y, const float* w, const float* shift, const float* skip_pre,
                    const float* skip_post, int frames, int T, int F, int cin, int cout, int cout4, int kh,
                    int kw, int use_act, hipStream_t st) {
   const size_t row = (size_t)kh * (F + kw - 1) * cin * sizeof(float);
-  if (row > 64 * 1024) return fail(RCED_ERR_ARG, "generic layer needs %zu B of LDS (> 64 KiB)", row);
+  if (row > 64 * 1024) return rced_fail(RCED_ERR_ARG, "generic layer needs %zu B of LDS (> 64 KiB)", row);
   if (frames <= 0) return RCED_OK;
   const int fpw = generic_frames_per_wg(F, cout4, kh, row);
   hipLaunchKernelGGL(conv_layer_generic, dim3((frames + fpw - 1) / fpw), dim3(kGenericThreads), row * fpw, st, x, y, w,
@@ -257,7 +226,7 @@ size_t rced_num_trainable(int variant) {
 }
 int rced_layer_desc(int variant, int layer, int out[9]) {
   const NetSpec* n = net_spec(variant);
-  if (!n || !out || layer < 0 || layer >= n->n_layers) return fail(RCED_ERR_ARG, "bad variant/layer");
+  if (!n || !out || layer < 0 || layer >= n->n_layers) return rced_fail(RCED_ERR_ARG, "bad variant/layer");
   const LayerSpec& l = n->layer[layer];
   const int v[9] = {l.cout, l.kh, l.kw, l.use_norm, l.use_act, l.src, l.skip_pre, l.skip_post, layer_cin(*n, layer)};
   memcpy(out, v, sizeof(v));
@@ -270,25 +239,25 @@ const char* rced_layer_scope(int variant, int layer) {
 }
 
 int rced_create(int variant, const float* blob, size_t n_floats, int device, rced_model** out) {
-  if (!out) return fail(RCED_ERR_ARG, "out is NULL");
+  if (!out) return rced_fail(RCED_ERR_ARG, "out is NULL");
   *out = nullptr;
   const NetSpec* net = net_spec(variant);
-  if (!net) return fail(RCED_ERR_ARG, "unknown variant %d (use RCED_V1/V2/V3)", variant);
-  if (!blob) return fail(RCED_ERR_ARG, "blob is NULL");
+  if (!net) return rced_fail(RCED_ERR_ARG, "unknown variant %d (use RCED_V1/V2/V3)", variant);
+  if (!blob) return rced_fail(RCED_ERR_ARG, "blob is NULL");
   if (n_floats != net_num_weights(*net))
-    return fail(RCED_ERR_ARG, "blob has %zu floats, variant %d needs %zu", n_floats, variant, net_num_weights(*net));
+    return rced_fail(RCED_ERR_ARG, "blob has %zu floats, variant %d needs %zu", n_floats, variant, net_num_weights(*net));
   for (size_t i = 0; i < n_floats; ++i)
-    if (!std::isfinite(blob[i])) return fail(RCED_ERR_ARG, "blob[%zu] is not finite", i);
+    if (!std::isfinite(blob[i])) return rced_fail(RCED_ERR_ARG, "blob[%zu] is not finite", i);
   if (int rc = check_device(device)) return rc;
   DeviceGuard g(device);
-  if (!g.ok) return fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, device));
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(RCED_ERR_HIP, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
+    return rced_fail(RCED_ERR_HIP, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
 
   rced_model* m = new (std::nothrow) rced_model();
-  if (!m) return fail(RCED_ERR_ALLOC, "host allocation failed");
+  if (!m) return rced_fail(RCED_ERR_ALLOC, "host allocation failed");
   m->variant = variant;
   m->device = device;
   m->net = net;
@@ -298,21 +267,17 @@ int rced_create(int variant, const float* blob, size_t n_floats, int device, rce
   const float* p = blob;
   for (int i = 0; i < net->n_layers; ++i) {
     std::vector<float> w4, sh4;
-    int cout4 = 0;
-    // variance must make sqrt(var+eps) real
     const LayerSpec& l = net->layer[i];
-    if (l.use_norm) {
-      const float* var = p + (size_t)l.kh * l.kw * layer_cin(*net, i) * l.cout + 4 * (size_t)l.cout;
-      for (int c = 0; c < l.cout; ++c)
-        if (var[c] + kBnEps <= 0.f) {
-          delete m;
-          return fail(RCED_ERR_ARG, "%s/batch_norm/moving_variance[%d] = %g is not > -eps", l.scope, c, var[c]);
-        }
+    const size_t kelems = (size_t)l.kh * l.kw * layer_cin(*net, i);
+    const float* bias = p + kelems * l.cout;                      // the layer's parameters: kernel, bias, then the four BatchNorm vectors
+    const float* bn = l.use_norm ? bias + l.cout : nullptr;
+    if (const int c = fold_bn(p, bias, bn, kelems, l.cout, &w4, &sh4); c >= 0) {
+      delete m;
+      return rced_fail(RCED_ERR_ARG, "%s/batch_norm/moving_variance[%d] = %g is not > -eps", l.scope, c, bn[3 * l.cout + c]);
     }
-    fold_layer(*net, i, p, &w4, &sh4, &cout4);
     rced_layer_dev& d = m->layers[i];
     d.cin = layer_cin(*net, i);
-    d.cout4 = cout4;
+    d.cout4 = (int)sh4.size();
     d.host_w = w4;
     d.host_shift = sh4;
     hipError_t e = hipMalloc(&d.w, w4.size() * sizeof(float));
@@ -321,7 +286,7 @@ int rced_create(int variant, const float* blob, size_t n_floats, int device, rce
     if (e == hipSuccess) e = hipMemcpy(d.shift, sh4.data(), sh4.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
       delete m;
-      return fail(RCED_ERR_HIP, "weight upload failed: %s", hipGetErrorString(e));
+      return rced_fail(RCED_ERR_HIP, "weight upload failed: %s", hipGetErrorString(e));
     }
     p += layer_num_weights(*net, i);
   }
@@ -337,10 +302,10 @@ int rced_create(int variant, const float* blob, size_t n_floats, int device, rce
 void rced_destroy(rced_model* m) { delete m; }
 
 int rced_set_option(rced_model* m, const char* key, int value) {
-  if (!m || !key) return fail(RCED_ERR_ARG, "null argument");
+  if (!m || !key) return rced_fail(RCED_ERR_ARG, "null argument");
   if (!strcmp(key, "path")) {
-    if (value < RCED_PATH_AUTO || value > RCED_PATH_FUSED) return fail(RCED_ERR_ARG, "bad path %d", value);
-    if (value == RCED_PATH_FUSED && !m->fused) return fail(RCED_ERR_ARG, "no fused path for variant %d", m->variant);
+    if (value < RCED_PATH_AUTO || value > RCED_PATH_FUSED) return rced_fail(RCED_ERR_ARG, "bad path %d", value);
+    if (value == RCED_PATH_FUSED && !m->fused) return rced_fail(RCED_ERR_ARG, "no fused path for variant %d", m->variant);
     m->path = value;
     return RCED_OK;
   }
@@ -351,7 +316,7 @@ int rced_set_option(rced_model* m, const char* key, int value) {
     return RCED_OK;
   }
   if (!strcmp(key, "host_chunks")) {  // rced_forward_host pipeline depth: 0 = default (8), 1 = no overlap
-    if (value < 0 || value > 64) return fail(RCED_ERR_ARG, "host_chunks must be 0..64");
+    if (value < 0 || value > 64) return rced_fail(RCED_ERR_ARG, "host_chunks must be 0..64");
     m->host_chunks = value;
     return RCED_OK;
   }
@@ -360,18 +325,18 @@ int rced_set_option(rced_model* m, const char* key, int value) {
     const int rc = fused_set_option(m, key, value);
     if (rc != RCED_OPT_UNKNOWN) return rc;   // RCED_OK, or a failure whose (specific) message the fused runtime has set
   }
-  return fail(RCED_ERR_ARG, "unknown option '%s' (or a value it does not take: %d)", key, value);
+  return rced_fail(RCED_ERR_ARG, "unknown option '%s' (or a value it does not take: %d)", key, value);
 }
 
 int rced_get_option(rced_model* m, const char* key, int* value) {
-  if (!m || !key || !value) return fail(RCED_ERR_ARG, "null argument");
+  if (!m || !key || !value) return rced_fail(RCED_ERR_ARG, "null argument");
   if (!strcmp(key, "path")) { *value = m->path; return RCED_OK; }
   if (!strcmp(key, "profile")) { *value = m->profile; return RCED_OK; }
   if (!strcmp(key, "has_fused")) { *value = m->fused != nullptr; return RCED_OK; }
   if (!strcmp(key, "num_cus")) { *value = m->num_cus; return RCED_OK; }
   if (!strcmp(key, "host_chunks")) { *value = m->host_chunks; return RCED_OK; }
   if (fused_get_option(m, key, value) == RCED_OK) return RCED_OK;
-  return fail(RCED_ERR_ARG, "unknown option '%s'", key);
+  return rced_fail(RCED_ERR_ARG, "unknown option '%s'", key);
 }
 
 static int use_fused(const rced_model* m) {
@@ -379,10 +344,10 @@ static int use_fused(const rced_model* m) {
 }
 
 int rced_reserve(rced_model* m, int N, int T) {
-  if (!m) return fail(RCED_ERR_ARG, "model is NULL");
-  if (N < 0 || T < 0) return fail(RCED_ERR_ARG, "negative shape");
+  if (!m) return rced_fail(RCED_ERR_ARG, "model is NULL");
+  if (N < 0 || T < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
   DeviceGuard g(m->device);
-  if (!g.ok) return fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", m->device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", m->device);
   if (N == 0 || T == 0) return RCED_OK;
   if (use_fused(m)) return fused_reserve(m, N, T);
   const int chunk = layerwise_chunk(m, N, T);
@@ -390,25 +355,25 @@ int rced_reserve(rced_model* m, int N, int T) {
 }
 
 int rced_forward(rced_model* m, const float* x_dev, float* y_dev, int N, int T, void* stream) {
-  if (!m) return fail(RCED_ERR_ARG, "model is NULL");
-  if (N < 0 || T < 0) return fail(RCED_ERR_ARG, "negative shape N=%d T=%d", N, T);
+  if (!m) return rced_fail(RCED_ERR_ARG, "model is NULL");
+  if (N < 0 || T < 0) return rced_fail(RCED_ERR_ARG, "negative shape N=%d T=%d", N, T);
   if (N == 0 || T == 0) return RCED_OK;  // empty batch: nothing to do (TF returns an empty array)
-  if (!x_dev || !y_dev) return fail(RCED_ERR_ARG, "x/y is NULL");
-  if ((size_t)N * T > ((size_t)1 << 31) / kFeatureDim * 4) return fail(RCED_ERR_ARG, "N*T too large");
+  if (!x_dev || !y_dev) return rced_fail(RCED_ERR_ARG, "x/y is NULL");
+  if ((size_t)N * T > ((size_t)1 << 31) / kFeatureDim * 4) return rced_fail(RCED_ERR_ARG, "N*T too large");
   DeviceGuard g(m->device);
-  if (!g.ok) return fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", m->device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", m->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (use_fused(m)) return fused_forward(m, x_dev, y_dev, N, T, st);
   return forward_layerwise(m, x_dev, y_dev, N, T, st);
 }
 
 int rced_forward_host(rced_model* m, const float* x_host, float* y_host, int N, int T) {
-  if (!m) return fail(RCED_ERR_ARG, "model is NULL");
-  if (N < 0 || T < 0) return fail(RCED_ERR_ARG, "negative shape N=%d T=%d", N, T);
+  if (!m) return rced_fail(RCED_ERR_ARG, "model is NULL");
+  if (N < 0 || T < 0) return rced_fail(RCED_ERR_ARG, "negative shape N=%d T=%d", N, T);
   if (N == 0 || T == 0) return RCED_OK;
-  if (!x_host || !y_host) return fail(RCED_ERR_ARG, "x/y is NULL");
+  if (!x_host || !y_host) return rced_fail(RCED_ERR_ARG, "x/y is NULL");
   DeviceGuard g(m->device);
-  if (!g.ok) return fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", m->device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", m->device);
   const size_t bytes = (size_t)N * T * kFeatureDim * sizeof(float);
   if (bytes > m->stage_bytes) {
     if (m->stage_x) (void)hipFree(m->stage_x);
@@ -419,7 +384,7 @@ int rced_forward_host(rced_model* m, const float* x_host, float* y_host, int N, 
     if (hipError_t e = hipMalloc(&m->stage_y, bytes); e != hipSuccess) {
       (void)hipFree(m->stage_x);
       m->stage_x = nullptr;
-      return fail(RCED_ERR_ALLOC, "hipMalloc(stage_y, %zu): %s", bytes, hipGetErrorString(e));
+      return rced_fail(RCED_ERR_ALLOC, "hipMalloc(stage_y, %zu): %s", bytes, hipGetErrorString(e));
     }
     m->stage_bytes = bytes;
   }
@@ -449,7 +414,7 @@ int rced_forward_host(rced_model* m, const float* x_host, float* y_host, int N, 
       const hipError_t e = hipEventCreateWithFlags(&m->host_events[i], hipEventDisableTiming);
       if (e != hipSuccess) {
         m->host_events.resize(i);   // keep what exists (freed with the model)
-        return fail(RCED_ERR_HIP, "hipEventCreate: %s", hipGetErrorString(e));
+        return rced_fail(RCED_ERR_HIP, "hipEventCreate: %s", hipGetErrorString(e));
       }
     }
   }
@@ -490,8 +455,8 @@ int rced_forward_host(rced_model* m, const float* x_host, float* y_host, int N, 
   downloader.join();
   (void)hipStreamSynchronize(s_run);
   if (rc != RCED_OK) return rc;
-  if (in_err != hipSuccess) return fail(RCED_ERR_HIP, "host path upload: %s", hipGetErrorString(in_err));
-  if (out_err != hipSuccess) return fail(RCED_ERR_HIP, "host path download: %s", hipGetErrorString(out_err));
+  if (in_err != hipSuccess) return rced_fail(RCED_ERR_HIP, "host path upload: %s", hipGetErrorString(in_err));
+  if (out_err != hipSuccess) return rced_fail(RCED_ERR_HIP, "host path download: %s", hipGetErrorString(out_err));
   return fused_check(m);
 }
 
@@ -499,12 +464,12 @@ int rced_conv_bn_relu(const float* x, float* y, const float* kernel, const float
                       const float* skip_input, int use_act, int N, int T, int F, int cin, int cout, int kh,
                       int kw, int device, void* stream) {
   if (N < 0 || T < 0 || F <= 0 || cin <= 0 || cout <= 0 || kh <= 0 || kw <= 0)
-    return fail(RCED_ERR_ARG, "bad shape");
+    return rced_fail(RCED_ERR_ARG, "bad shape");
   if (N == 0 || T == 0) return RCED_OK;
-  if (!x || !y || !kernel || !bias) return fail(RCED_ERR_ARG, "null pointer");
+  if (!x || !y || !kernel || !bias) return rced_fail(RCED_ERR_ARG, "null pointer");
   if (int rc = check_device(device)) return rc;
   DeviceGuard g(device);
-  if (!g.ok) return fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
   hipStream_t st = static_cast<hipStream_t>(stream);
   // fold on the host: pull the (small) parameters back, fold in double, push the folded copy
   const size_t kelems = (size_t)kh * kw * cin;
@@ -513,25 +478,17 @@ int rced_conv_bn_relu(const float* x, float* y, const float* kernel, const float
   HIP_TRY(hipMemcpyAsync(hb.data(), bias, hb.size() * sizeof(float), hipMemcpyDeviceToHost, st));
   if (bn) HIP_TRY(hipMemcpyAsync(hbn.data(), bn, hbn.size() * sizeof(float), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
-  const int cout4 = (cout + 3) & ~3;
-  std::vector<float> w4(kelems * cout4, 0.f), sh4(cout4, 0.f);
-  for (int c = 0; c < cout; ++c) {
-    double s = 1.0, sh = hb[c];
-    if (bn) {
-      if (hbn[3 * cout + c] + kBnEps <= 0.f) return fail(RCED_ERR_ARG, "moving_variance[%d] not > -eps", c);
-      s = (double)hbn[c] / std::sqrt((double)hbn[3 * cout + c] + (double)kBnEps);
-      sh = ((double)hb[c] - hbn[2 * cout + c]) * s + hbn[cout + c];
-    }
-    sh4[c] = (float)sh;
-    for (size_t k = 0; k < kelems; ++k) w4[k * cout4 + c] = (float)((double)hk[k * cout + c] * s);
-  }
+  std::vector<float> w4, sh4;
+  if (const int c = fold_bn(hk.data(), hb.data(), bn ? hbn.data() : nullptr, kelems, cout, &w4, &sh4); c >= 0)
+    return rced_fail(RCED_ERR_ARG, "moving_variance[%d] not > -eps", c);
+  const int cout4 = (int)sh4.size();
   float *dw = nullptr, *dsh = nullptr;
   HIP_TRY(hipMalloc(&dw, w4.size() * sizeof(float)));
   hipError_t e = hipMalloc(&dsh, sh4.size() * sizeof(float));
   if (e == hipSuccess) e = hipMemcpyAsync(dw, w4.data(), w4.size() * sizeof(float), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(dsh, sh4.data(), sh4.size() * sizeof(float), hipMemcpyHostToDevice, st);
   int rc = RCED_OK;
-  if (e != hipSuccess) rc = fail(RCED_ERR_HIP, "parameter upload failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) rc = rced_fail(RCED_ERR_HIP, "parameter upload failed: %s", hipGetErrorString(e));
   if (rc == RCED_OK)
     rc = launch_generic(x, y, dw, dsh, skip_input, nullptr, N * T, T, F, cin, cout, cout4, kh, kw, use_act, st);
   (void)hipStreamSynchronize(st);
@@ -541,7 +498,7 @@ int rced_conv_bn_relu(const float* x, float* y, const float* kernel, const float
 }
 
 int rced_check(rced_model* m) {
-  if (!m) return fail(RCED_ERR_ARG, "model is NULL");
+  if (!m) return rced_fail(RCED_ERR_ARG, "model is NULL");
   return fused_check(m);   // reads pinned host memory: no device call, no synchronisation
 }
 
@@ -551,7 +508,7 @@ float rced_last_kernel_ms(rced_model* m) {
 }
 
 int rced_profile_query(rced_model* m, int kind, float* total_ms, int* launches) {
-  if (!m || !total_ms || !launches) return fail(RCED_ERR_ARG, "null argument");
+  if (!m || !total_ms || !launches) return rced_fail(RCED_ERR_ARG, "null argument");
   DeviceGuard g(m->device);
   if (int rc = fused_check(m)) return rc;
   float tot = 0.f;

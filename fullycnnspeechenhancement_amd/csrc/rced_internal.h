@@ -5,6 +5,7 @@
 #include <cstddef>
 #include <vector>
 
+#include "host_util.h"
 #include "rced_spec.h"
 
 // kernel kinds for the built-in HIP-event profiler ("profile" option)
@@ -63,4 +64,3 @@ int fused_check(rced_model* m);   // RCED_ERR_STATE if an earlier launch recorde
 #define RCED_OPT_UNKNOWN (-1)   // fused_set_option: "not a key of mine" (internal; never crosses the C ABI)
 int fused_set_option(rced_model* m, const char* key, int value);
 int fused_get_option(rced_model* m, const char* key, int* value);
-int rced_fail(int code, const char* fmt, ...);

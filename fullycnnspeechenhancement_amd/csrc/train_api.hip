@@ -21,24 +21,7 @@
 
 using namespace rced;
 
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess)                                                                      \
-      return rced_fail(e_ == hipErrorOutOfMemory ? RCED_ERR_ALLOC : RCED_ERR_HIP, "%s: %s", #expr, \
-                       hipGetErrorString(e_));                                                 \
-  } while (0)
-
 namespace {
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) { prev = -1; return; }
-    ok = (prev == dev) || (hipSetDevice(dev) == hipSuccess);
-  }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 constexpr int kReduceGrid = 512;
 using rced::tmd::kPairGrid;
 using rced::tmd::allow_lds;
@@ -510,10 +493,7 @@ int rced_train_create(int variant, const float* blob, size_t n_floats, int batch
   if (!net) return rced_fail(RCED_ERR_ARG, "unknown variant %d", variant);
   if (!blob || n_floats != net_num_weights(*net)) return rced_fail(RCED_ERR_ARG, "blob must hold %zu floats", net_num_weights(*net));
   if (batch_size <= 0) return rced_fail(RCED_ERR_ARG, "batch_size must be positive");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return rced_fail(RCED_ERR_HIP, "no HIP device visible (this library has no CPU fallback)");
-  if (device < 0 || device >= ndev) return rced_fail(RCED_ERR_ARG, "device %d out of range", device);
+  if (int rc = check_device(device)) return rc;
   DeviceGuard g(device);
   if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
   rced_trainer* t = new rced_trainer();
@@ -1207,10 +1187,7 @@ int rced_conv_bn_relu_train(const float* x, float* y, const float* kernel, const
     return rced_fail(RCED_ERR_ARG, "bad shape");
   if (N == 0 || T == 0) return RCED_OK;
   if (!x || !y || !kernel || !bias || !gamma_beta) return rced_fail(RCED_ERR_ARG, "null pointer");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return rced_fail(RCED_ERR_HIP, "no HIP device visible (this library has no CPU fallback)");
-  if (device < 0 || device >= ndev) return rced_fail(RCED_ERR_ARG, "device %d out of range", device);
+  if (int rc = check_device(device)) return rc;
   DeviceGuard g(device);
   if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
   hipStream_t st = static_cast<hipStream_t>(stream);
