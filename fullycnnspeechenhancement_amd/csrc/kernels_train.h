@@ -59,7 +59,7 @@ __global__ __launch_bounds__(kThreads) void chan_reduce(const float* __restrict_
 
 // sums[c][2] = sum over partials.  One workgroup per output (launch with 2*C workgroups).
 // only_if: a device flag; the launch is a no-op when it is given and zero (the conditional exact recomputation behind
-// sums_fix_x, train_api.hip).
+// bn_finish, mode kFinX, train_api.hip).
 __global__ __launch_bounds__(kThreads) void reduce_finish(const double* __restrict__ part, int nparts, int C,
                                                            double* __restrict__ sums, const int* __restrict__ only_if = nullptr) {
   if (only_if && *only_if == 0) return;

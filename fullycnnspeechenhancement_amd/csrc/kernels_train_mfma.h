@@ -526,7 +526,7 @@ __device__ __forceinline__ float row_sum16(float v) {
 // whole batch before anything else can run.  bwd_route2 got them from one more pass over g and z (HBM-bound, 8 ms of a
 // CR-CED step); here the dgrad forms them in its epilogue, where g is still in the accumulators: the tile of z arrives
 // by LDS-DMA (no VGPRs, in flight during the whole MFMA pass), and the kernel leaves per-workgroup records
-// (sum d_u, sum d_u * z) per channel in `part`; sums_fix turns the second into S2 = rstd * (sum d_u z - mu * S1).
+// (sum d_u, sum d_u * z) per channel in `part`; bn_finish (kFinZ) turns the second into S2 = rstd * (sum d_u z - mu * S1).
 struct SumArgs {
   const float* z;                          // pre-BatchNorm output of the producer, [frames][129][COUT]
   const float *mu, *rstd, *gamma, *beta;   // its batch statistics and affine parameters
@@ -534,7 +534,7 @@ struct SumArgs {
 
 // SUMX (with SUMS, the fused backward kernel): the masked sums are formed from the TRANSFORMED tile x = relu(a z + b) the
 // same workgroup has staged for its wgrad half (zt = that tile, pixel p at row kG + p): x > 0 is the mask and the second
-// sum is sum d_u * x (sums_fix_x turns it into S2); no z tile, no extra barrier.
+// sum is sum d_u * x (bn_finish, kFinX, turns it into S2); no z tile, no extra barrier.
 // A lane's fp32 shares of the per-channel sums (STATS: sum z, sum z^2; SUMS: sum d_u, sum d_u z), carried over a few tiles
 // in registers and only then reduced over the lanes and added to the wave's record of doubles: the reduction (64 DPP adds,
 // 16 conversions, 16 double adds per wave and two-M-tile tile) was a fifth of the forward convolutions' non-MFMA

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "../../include/rced.h"
@@ -18,6 +19,7 @@
 #include "train_mfma_dispatch.h"
 #include "rced_internal.h"
 #include "rced_spec.h"
+#include "train_plan.h"
 
 using namespace rced;
 
@@ -26,6 +28,10 @@ constexpr int kReduceGrid = 512;
 using rced::tmd::kPairGrid;
 using rced::tmd::allow_lds;
 using rced::tmd::tm_packet_floats;
+using rced::tmd::WgDet;
+using rced::tms::tm_has;
+using rced::tms::first_has;
+using rced::tms::is_output_layer;
 constexpr float kAdamB1 = 0.9f, kAdamB2 = 0.999f, kAdamEps = 1e-8f;   // tf.train.AdamOptimizer defaults
 constexpr float kBnMomentum = 0.99f;                                  // tf.layers.batch_normalization default
 
@@ -51,23 +57,22 @@ struct rced_trainer {
   unsigned char* trainable = nullptr;
   std::vector<float*> wf, wt, bias4, mu, rstd;   // per layer
   std::vector<float*> pk_fwd, pk_bwd;            // per layer: MFMA A-fragment packets (1xk layers with an MFMA kernel)
-  int use_mfma = 1;
-  bool fuse_dz = true;         // RCED_TRAIN_FUSE_DZ=0: always materialise dz with bn_bwd_apply
-  bool fuse_bwd = true;        // RCED_TRAIN_FUSE_BWD=0: separate wgrad and dgrad kernels everywhere
-  bool fuse_sums = true;       // RCED_TRAIN_FUSE_SUMS=0: BatchNorm-backward sums of plain layers from bwd_route2, not from the dgrad
+  // RCED_TRAIN_MFMA / FUSE_ACT / FUSE_DZ / FUSE_SUMS / FUSE_BWD / X6 (=0: direct-conv kernels only / materialise activations / dz by
+  // bn_bwd_apply / sums of plain layers from bwd_route2 / separate wgrad and dgrad / every convolution on the fp32 MFMA), and what
+  // they make of this net: which launcher runs where (train_plan.h).  Fixed at create.
+  plan::TrainSwitches sw{true, true, true, true, true, true};
+  plan::TrainPlan plan{};
   bool det = true;             // RCED_TRAIN_DET=0: weight gradients by fp32 atomics (the round-1 behaviour; not reproducible bit for bit)
   float* wpart = nullptr;      // per-wave slices of the wgrad kernels' partial sums (deterministic mode; tmd::WgDet)
   size_t wpart_floats = 0;
   int wg_error = 0;            // tmd::wg_launch could not grow wpart: the step fails instead of using atomics
-  std::vector<char> virt;      // virt[id]: tensor id (= relu(bn(z[id-1]))) is never materialised; its consumer rebuilds it
   float* pk_first = nullptr;   // A fragments of the 8xk first layer (rebuilt every step)
   std::vector<float*> pk_fwd_x6;   // the forward packets of the layers that run in the three-part bf16 form (tmm::conv_x6_fwd)
   std::vector<float*> pk_bwd_x6;   // the dgrad packets of the fused backward kernels whose dgrad half runs in that form (tmm::bwd_x6)
-  bool use_x6 = true;          // RCED_TRAIN_X6=0: every convolution on the fp32 MFMA (forward 18 -> 30 layers, the output layer's forward and dgrad)
   float* pk_fin = nullptr, *pk_fin_bwd = nullptr;     // Toeplitz A fragments of the 1x129 output layer (rebuilt every step)
   float* zero32 = nullptr;
   double *part = nullptr, *sums = nullptr;
-  int* redo = nullptr;         // device flag behind `sums` (same allocation): sums_fix_x asks for the exact recomputation
+  int* redo = nullptr;         // device flag behind `sums` (same allocation), written by bn_finish's kFinX mode
   int* tiny_host = nullptr;    // [layers] pinned, host-mapped: 1 = some |gamma| of the layer is below kTinyGamma (written by
   int* tiny_dev = nullptr;     // tiny_gamma_scan behind every Adam step, read by the host at the start of the next step)
   // activations for P pixels
@@ -75,31 +80,27 @@ struct rced_trainer {
   std::vector<float*> out, z, G;   // out/G indexed by tensor id (0 unused), z by layer
   float* D = nullptr;
   long long global_step = 0;
-  ~rced_trainer() {
-    DeviceGuard g(device);
-    auto fr = [](void* p) { if (p) (void)hipFree(p); };
-    fr(params); fr(grads); fr(m); fr(v); fr(trainable); fr(zero32); fr(part); fr(sums); fr(D); fr(wpart);
-    if (tiny_host) (void)hipHostFree(tiny_host);
-    for (auto* p : wf) fr(p);
-    for (auto* p : wt) fr(p);
-    for (auto* p : bias4) fr(p);
-    for (auto* p : mu) fr(p);
-    for (auto* p : rstd) fr(p);
-    for (auto* p : pk_fwd) fr(p);
-    for (auto* p : pk_bwd) fr(p);
-    for (auto* p : pk_fwd_x6) fr(p);
-    for (auto* p : pk_bwd_x6) fr(p);
-    fr(pk_fin);
-    fr(pk_fin_bwd);
-    fr(pk_first);
-    free_acts();
+  std::vector<void*> owned;       // every device allocation made by rced_train_create
+  std::vector<void*> act_bases;   // the allocations behind out / z / G / D, made for a pixel count (ensure_acts)
+  template <class T>
+  hipError_t alloc(T** p, size_t bytes) {
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(p), bytes);
+    if (e == hipSuccess) owned.push_back(*p);
+    return e;
   }
-  std::vector<void*> act_bases;   // the allocations behind out / z / G (those pointers may sit at a skew inside them)
   void free_acts() {
     for (void* p : act_bases) (void)hipFree(p);
     act_bases.clear();
     out.clear(); z.clear(); G.clear();
+    D = nullptr;
     cap_px = 0;
+  }
+  ~rced_trainer() {
+    DeviceGuard g(device);
+    for (void* p : owned) (void)hipFree(p);
+    if (wpart) (void)hipFree(wpart);   // (made by the first step, regrown by tmd::wg_launch)
+    if (tiny_host) (void)hipHostFree(tiny_host);
+    free_acts();
   }
 };
 
@@ -109,7 +110,6 @@ int ensure_acts(rced_trainer* t, size_t P) {
   if (P <= t->cap_px) return RCED_OK;
   HIP_TRY(hipDeviceSynchronize());
   t->free_acts();
-  if (t->D) { (void)hipFree(t->D); t->D = nullptr; }
   const NetSpec& net = *t->net;
   const int L = net.n_layers;
   t->out.assign(L + 1, nullptr);
@@ -129,15 +129,13 @@ int ensure_acts(rced_trainer* t, size_t P) {
     const int c = net.layer[l].cout;
     maxc = std::max(maxc, c);
     if (int rc = alloc(&t->z[l], P * c * sizeof(float))) return rc;
-    if (!t->virt.empty() && t->virt[l + 1])
-      t->out[l + 1] = nullptr;   // rebuilt from z by its consumer (BnReluXform)
-    else if (net.layer[l].use_norm || net.layer[l].use_act || net.layer[l].skip_pre >= 0 || net.layer[l].skip_post >= 0) {
+    if (t->plan.layer[l].out == plan::Out::Stored) {
       if (int rc = alloc(&t->out[l + 1], P * c * sizeof(float))) return rc;
-    } else
-      t->out[l + 1] = t->z[l];   // plain conv layer (decode_final): its output IS z
+    } else   // virtual: rebuilt from z by its consumer (BnReluXform); a plain conv layer (decode_final): its output IS z
+      t->out[l + 1] = t->plan.layer[l].out == plan::Out::Virtual ? nullptr : t->z[l];
     if (int rc = alloc(&t->G[l + 1], P * c * sizeof(float))) return rc;
   }
-  HIP_TRY(hipMalloc(&t->D, P * maxc * sizeof(float)));
+  if (int rc = alloc(&t->D, P * maxc * sizeof(float))) return rc;
   t->cap_px = P;
   return RCED_OK;
 }
@@ -162,66 +160,49 @@ int reduce_channels(rced_trainer* t, const float* a, const float* b, const float
 }
 
 // ---- MFMA paths for the 1xk layers (kernels_train_mfma.h, launchers in train_mfma_dispatch.h) ----
-// forward shapes (cin, taps, cout) of the 1xk layers and the shapes of their dgrad convolutions (cout, taps, cin):
-// CR-CED V3, then R-CED V1.  R-CED V2 (even-padded internal layout) lives in train_mfma_v2.hip.
-#define RCED_TM_FWD(X)                        \
-  X(8, 9, 18) X(18, 5, 30) X(30, 9, 8)        \
-  X(12, 11, 16) X(16, 9, 20) X(20, 7, 24) X(24, 7, 32) X(32, 7, 24) X(24, 9, 20) X(20, 11, 16) X(16, 13, 12)
-#define RCED_TM_BWD(X)                                   \
-  X(18, 9, 8) X(30, 5, 18) X(8, 9, 30) X(1, 129, 8)      \
-  X(16, 11, 12) X(20, 9, 16) X(24, 7, 20) X(32, 7, 24) X(24, 7, 32) X(20, 9, 24) X(16, 11, 20) X(12, 13, 16)
+// the shapes of CR-CED V3 and R-CED V1 (RCED_TM_FWD / RCED_TM_BWD, train_shapes.h); R-CED V2 lives in train_mfma_v2.hip
 RCED_TM_DEFINE_DISPATCH(_main, RCED_TM_FWD, RCED_TM_BWD)
 }  // namespace
 // train_mfma_v2.hip
 int rced_tm_conv_v2(bool fwd, int cin, int taps, int cout, bool accum, bool stats, const float* in, const float* packet,
                     float* out, int frames, int cus, double* part, const rced::tmm::XformArgs* xa,
                     const rced::tmm::BnBwdArgs* ba, hipStream_t st, const rced::tmm::SumArgs* sa, const float* acc_from);
-bool rced_tm_has_v2(bool fwd, int cin, int taps, int cout);
-int rced_tm_wgrad_v2(int cin, int taps, int cout, const float* x, const float* dz, float* dW, float* dbias, int frames, int cus,
+int rced_tm_wgrad_v2(const rced::tmd::WgDet& wd, int cin, int taps, int cout, const float* x, const float* dz, float* dW, float* dbias, int frames, int cus,
                      const rced::tmm::XformArgs* xa, const rced::tmm::BnBwdArgs* ba, hipStream_t st);
 namespace {
 // Returns the grid size (= number of partial-sum records when stats), 0 if no kernel was built for the request.
 int tm_conv(bool fwd, int cin, int taps, int cout, bool accum, bool stats, const float* in, const float* packet, float* out,
             int frames, int cus, double* part, const tmm::XformArgs* xa, const tmm::BnBwdArgs* ba, hipStream_t st,
             const tmm::SumArgs* sa = nullptr, const float* acc_from = nullptr) {
-  if (tm_has_main(fwd, cin, taps, cout))
+  if (rced::tms::tm_has_main(fwd, cin, taps, cout))
     return tm_conv_main(fwd, cin, taps, cout, accum, stats, in, packet, out, frames, cus, part, xa, ba, st, sa, acc_from);
   return rced_tm_conv_v2(fwd, cin, taps, cout, accum, stats, in, packet, out, frames, cus, part, xa, ba, st, sa, acc_from);
 }
-bool tm_has(bool fwd, int cin, int taps, int cout) { return tm_has_main(fwd, cin, taps, cout) || rced_tm_has_v2(fwd, cin, taps, cout); }
-int tm_wgrad(int cin, int taps, int cout, const float* x, const float* dz, float* dW, float* dbias, int frames, int cus,
+int tm_wgrad(const WgDet& wd, int cin, int taps, int cout, const float* x, const float* dz, float* dW, float* dbias, int frames, int cus,
              const tmm::XformArgs* xa, const tmm::BnBwdArgs* ba, hipStream_t st) {
-  if (tm_has_main(true, cin, taps, cout)) return tm_wgrad_main(cin, taps, cout, x, dz, dW, dbias, frames, cus, xa, ba, st);
-  return rced_tm_wgrad_v2(cin, taps, cout, x, dz, dW, dbias, frames, cus, xa, ba, st);
+  if (rced::tms::tm_has_main(true, cin, taps, cout)) return tm_wgrad_main(wd, cin, taps, cout, x, dz, dW, dbias, frames, cus, xa, ba, st);
+  return rced_tm_wgrad_v2(wd, cin, taps, cout, x, dz, dW, dbias, frames, cus, xa, ba, st);
 }
 
-// ---- wgrad + dgrad of a layer in one kernel (tmm::bwd_fused_mfma): the CR-CED shapes whose input tensor has one consumer ----
-#define RCED_TM_FUSED(X) X(18, 5, 30) X(30, 9, 8)
+// ---- wgrad + dgrad of a layer in one kernel (tmm::bwd_fused_mfma): RCED_TM_FUSED ----
 // (x virtual, sums) must be (1, 1) or (0, 0).  Returns the grid size, 0 if no kernel was built for the request.
-int tm_bwd_fused(int cin, int taps, int cout, bool xf_sums, const float* x, const float* du, const float* packet, float* dx,
+int tm_bwd_fused(const WgDet& wd, int cin, int taps, int cout, bool xf_sums, const float* x, const float* du, const float* packet, float* dx,
                  float* dW, float* dbias, int frames, int cus, double* part, const tmm::XformArgs* xa, const tmm::BnBwdArgs* ba,
                  hipStream_t st) {
   const tmm::XformArgs nx{nullptr, nullptr, nullptr, nullptr};
   if (!ba || (xf_sums && !xa)) return 0;
 #define X(CI, TP, CO)                                                                                                          \
   if (cin == CI && taps == TP && cout == CO)                                                                                   \
-    return xf_sums ? rced::tmd::tm_bwd_fused_launch<CI, TP, CO, true, true>(x, du, packet, dx, dW, dbias, frames, cus, part, *xa, *ba, st) \
-                   : rced::tmd::tm_bwd_fused_launch<CI, TP, CO, false, false>(x, du, packet, dx, dW, dbias, frames, cus, part, nx, *ba, st);
+    return xf_sums ? rced::tmd::tm_bwd_fused_launch<CI, TP, CO, true, true>(wd, x, du, packet, dx, dW, dbias, frames, cus, part, *xa, *ba, st) \
+                   : rced::tmd::tm_bwd_fused_launch<CI, TP, CO, false, false>(wd, x, du, packet, dx, dW, dbias, frames, cus, part, nx, *ba, st);
   RCED_TM_FUSED(X)
 #undef X
   return 0;
 }
 
-// ---- first layer (8 x kw on the 1-channel input): MFMA wgrad (kernels_train_mfma.h) ----
-#define RCED_FIRST(X) X(9, 18) X(13, 12) X(11, 10)
-bool first_has(const LayerSpec& s, int cin) {
-#define X(KW, CO) if (s.kh == 8 && cin == 1 && s.src == 0 && s.kw == KW && s.cout == CO) return true;
-  RCED_FIRST(X)
-#undef X
-  return false;
-}
+// ---- first layer (8 x kw on the 1-channel input, RCED_FIRST): MFMA forward and wgrad (kernels_train_mfma.h) ----
 template <int KW, int COUT>
-int first_wgrad_launch(const float* x, const float* dz, float* dW, float* dbias, int frames, int T, int cus,
+int first_wgrad_launch(const WgDet& wd, const float* x, const float* dz, float* dW, float* dbias, int frames, int T, int cus,
                        const tmm::BnBwdArgs* ba, hipStream_t st) {
   constexpr int RS = 129 + KW - 1;
   const size_t lds = (((size_t)(tmm::kTF * 8 * RS + 32 + 3) / 4) * 4 + (size_t)(tmm::kTF * tmm::first_wgrad_fs(KW, COUT) + 4) * 32 + 4 * COUT) * sizeof(float);
@@ -234,15 +215,15 @@ int first_wgrad_launch(const float* x, const float* dz, float* dW, float* dbias,
   // persistent grid = what is resident (it was cus * 3 with two workgroups per CU resident: half of the second round idle)
   const dim3 grid(std::min(ntiles, ba ? rced::tmd::resident_grid(reinterpret_cast<const void*>(tmm::first_wgrad<KW, COUT, true>), lds, cus, occ_t)
                                       : rced::tmd::resident_grid(reinterpret_cast<const void*>(tmm::first_wgrad<KW, COUT, false>), lds, cus, occ_f)));
-  rced::tmd::wg_launch([&](float* dw, float* db, unsigned ps) {
+  rced::tmd::wg_launch(wd, [&](float* dw, float* db, unsigned ps) {
     if (ba) hipLaunchKernelGGL((tmm::first_wgrad<KW, COUT, true>), grid, dim3(tmm::kThreads), lds, st, x, dz, dw, db, frames, T, *ba, ps);
     else hipLaunchKernelGGL((tmm::first_wgrad<KW, COUT, false>), grid, dim3(tmm::kThreads), lds, st, x, dz, dw, db, frames, T, nb, ps);
   }, (int)grid.x * tmm::kWaves, 8 * KW * COUT, COUT, dW, dbias, st);
   return 1;
 }
-int first_wgrad(const LayerSpec& s, const float* x, const float* dz, float* dW, float* dbias, int frames, int T, int cus,
+int first_wgrad(const WgDet& wd, const LayerSpec& s, const float* x, const float* dz, float* dW, float* dbias, int frames, int T, int cus,
                 const tmm::BnBwdArgs* ba, hipStream_t st) {
-#define X(KW, CO) if (s.kw == KW && s.cout == CO) return first_wgrad_launch<KW, CO>(x, dz, dW, dbias, frames, T, cus, ba, st);
+#define X(KW, CO) if (s.kw == KW && s.cout == CO) return first_wgrad_launch<KW, CO>(wd, x, dz, dW, dbias, frames, T, cus, ba, st);
   RCED_FIRST(X)
 #undef X
   return 0;
@@ -275,17 +256,12 @@ size_t first_packet_floats(const LayerSpec& s) {   // pack_first: main section, 
   return (size_t)2 * s.kw * (tmm::tm_rem(s.cout) ? 1 : (s.cout + 15) / 16) * 64 + (tmm::tm_rem(s.cout) ? 32 * 64 : 0) + 32;
 }
 
-// ---- output layer (1x129, CH -> 1): Toeplitz forward + MFMA wgrad (kernels_train_mfma.h) ----
-#define RCED_FIN_CH(X) X(8) X(10) X(12)
+// ---- output layer (1x129, CH -> 1, RCED_FIN_CH): Toeplitz forward + MFMA wgrad (kernels_train_mfma.h) ----
 size_t fin_pack_floats(int ch) {
 #define X(CH) if (ch == CH) return tmm::FinGeo<CH>::kPack;
   RCED_FIN_CH(X)
 #undef X
   return 0;
-}
-bool is_output_layer(const LayerSpec& s, int cin) {
-  return s.kh == 1 && s.kw == kFeatureDim && s.cout == 1 && !s.use_norm && !s.use_act && s.skip_pre < 0 && s.skip_post < 0 &&
-         fin_pack_floats(cin) > 0;
 }
 // floats of the buffer that holds the output layer's packed A: the fp32 form, or the three-part bf16 form (kernels_final_x6.h)
 size_t fin_pack_alloc_floats(int ch) {
@@ -346,11 +322,11 @@ int fin_dgrad(int ch, const float* dz, const float* w, float* pack, float* dx, i
 #undef X
   return 1;
 }
-int fin_wgrad(int ch, const float* x, const float* dz, float* dW, float* dbias, int frames, int cus, hipStream_t st) {
+int fin_wgrad(const WgDet& wd, int ch, const float* x, const float* dz, float* dW, float* dbias, int frames, int cus, hipStream_t st) {
   const dim3 grid(std::min((frames + tmm::kWaves - 1) / tmm::kWaves, cus * 2));
 #define X(CH)                                                                                                              \
   if (ch == CH)                                                                                                            \
-    rced::tmd::wg_launch([&](float* dw, float* db, unsigned ps) {                                                          \
+    rced::tmd::wg_launch(wd, [&](float* dw, float* db, unsigned ps) {                                                      \
       hipLaunchKernelGGL((tmm::final_wgrad<CH>), grid, dim3(tmm::kThreads), 0, st, x, dz, dw, db, frames, ps);             \
     }, (int)grid.x, 129 * CH, 1, dW, dbias, st);
   RCED_FIN_CH(X)
@@ -358,46 +334,25 @@ int fin_wgrad(int ch, const float* x, const float* dz, float* dW, float* dbias, 
   return 1;
 }
 
-// (sum d_u, sum d_u * z) from a SUMS dgrad -> (S1, S2 = sum d_u * zhat), zhat = (z - mu) * rstd
-__global__ void sums_fix(double* __restrict__ sums, const float* __restrict__ mu, const float* __restrict__ rstd, int C) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c < C) sums[2 * c + 1] = (double)rstd[c] * (sums[2 * c + 1] - (double)mu[c] * sums[2 * c]);
-}
-
-// (sum d_u, sum d_u * x), x = relu(a z + b), from the fused backward kernel -> (S1, S2): where d_u != 0, z = (x - b) / a.
+// kFinX below: the fused backward kernel leaves (sum d_u, sum d_u * x), x = relu(a z + b); where d_u != 0, z = (x - b) / a.
 // That division is exact enough only while |gamma| is not tiny (x was rounded to fp32: zhat comes back with an error of
 // eps |x| / |gamma|), and meaningless for gamma = 0 -- where S2 is still needed: it is gamma's own gradient, and TF's
-// d gamma = sum dy * zhat does not vanish with gamma.  So the kernel also raises *redo when any channel of the layer has
-// |gamma| < kTinyGamma, and the step then recomputes the layer's sums exactly from (g, z) with bwd_route2 -- launched
-// every step with this flag as its only_if, i.e. as a no-op in every step a real training run ever takes.
+// d gamma = sum dy * zhat does not vanish with gamma.  So that mode also raises *redo when any channel of the layer has
+// |gamma| < kTinyGamma, and the step recomputes such a layer's sums exactly from (g, z) with bwd_route2 (tiny_gamma_scan).
 constexpr float kTinyGamma = 1e-3f;
-__global__ void sums_fix_x(double* __restrict__ sums, const float* __restrict__ mu, const float* __restrict__ rstd,
-                           const float* __restrict__ gamma, const float* __restrict__ beta, int C, int* __restrict__ redo) {
-  const int c = threadIdx.x;     // one workgroup of >= C threads
-  bool tiny = false;
-  if (c < C) {
-    const float a = gamma[c] * rstd[c];                 // the folded forward, exactly as xform_table_fill forms it
-    const float b = beta[c] - a * mu[c];
-    const double s1 = sums[2 * c], sx = sums[2 * c + 1];
-    tiny = !(fabsf(gamma[c]) >= kTinyGamma);
-    sums[2 * c + 1] = a != 0.f ? (double)rstd[c] * ((sx - (double)b * s1) / (double)a - (double)mu[c] * s1) : 0.0;
-  }
-  const int any = __syncthreads_or(tiny);
-  if (threadIdx.x == 0) *redo = any;
-}
 
 __global__ void sums_to_float(const double* __restrict__ sums, int C, int which, float* __restrict__ dst) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c < C) dst[c] = (float)sums[2 * c + which];
 }
 
-// ONE launch for what used to be three to five (reduce_finish over 2 C workgroups, then sums_fix / sums_fix_x or
+// ONE launch for what used to be three to five (reduce_finish over 2 C workgroups, then a fix-up of S2 or
 // bn_stats_finish, then two sums_to_float): a CR-CED step issued ~150 of these 5-us kernels, all on the critical path.
 // One workgroup of 1024 threads: thread (i, p) adds records p, p + 16, ... of value i < 2 C, the 16 partial sums are added
 // in order (the same bits every run), then threads c < C finish the layer:
 //   kFinPlain  sums = (S1, S2) as they are                      (bwd_route2's records)
-//   kFinZ      S2 = rstd (sum d_u z - mu S1)                    (a SUMS dgrad's records: sums_fix)
-//   kFinX      S2 from sum d_u x, *redo on tiny gamma           (the fused backward kernel's records: sums_fix_x)
+//   kFinZ      S2 = rstd (sum d_u z - mu S1)                    (a SUMS dgrad's records)
+//   kFinX      S2 from sum d_u x, *redo on tiny gamma           (the fused backward kernel's records)
 //   kFinStats  (sum z, sum z^2) -> mu, rstd, moving statistics  (forward: bn_stats_finish)
 // kFinPlain / Z / X also write d beta = S1 and d gamma = S2 (g_beta / g_gamma).  only_if: a device flag, no-op when zero.
 enum { kFinPlain = 0, kFinZ = 1, kFinX = 2, kFinStats = 3 };
@@ -472,7 +427,7 @@ __global__ __launch_bounds__(1024) void bn_finish(const double* __restrict__ par
 }
 
 // One workgroup per layer: does any channel of the layer have |gamma| < kTinyGamma?  (the fused backward kernel's sums
-// cannot be trusted there: see sums_fix_x.)  Launched behind every Adam step into host-mapped memory, so that the NEXT
+// cannot be trusted there: see kTinyGamma.)  Launched behind every Adam step into host-mapped memory, so that the NEXT
 // step knows on the host which layers need the exact recomputation -- instead of launching a conditional bwd_route2 +
 // finish pair for every plain layer in every step (20 no-op launches per CR-CED step).
 struct TinyScanArgs { int gamma_off[kMaxLayers]; int cout[kMaxLayers]; };
@@ -496,7 +451,8 @@ int rced_train_create(int variant, const float* blob, size_t n_floats, int batch
   if (int rc = check_device(device)) return rc;
   DeviceGuard g(device);
   if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
-  rced_trainer* t = new rced_trainer();
+  std::unique_ptr<rced_trainer> owner(new rced_trainer());   // deleted on every early return below
+  rced_trainer* t = owner.get();
   t->variant = variant;
   t->device = device;
   t->batch_size = batch_size;
@@ -504,17 +460,19 @@ int rced_train_create(int variant, const float* blob, size_t n_floats, int batch
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) t->num_cus = prop.multiProcessorCount;
-    if (const char* e = getenv("RCED_TRAIN_MFMA")) t->use_mfma = atoi(e);
-    if (const char* e = getenv("RCED_TRAIN_FUSE_DZ")) t->fuse_dz = atoi(e) != 0;
-    if (const char* e = getenv("RCED_TRAIN_FUSE_SUMS")) t->fuse_sums = atoi(e) != 0;
-    if (const char* e = getenv("RCED_TRAIN_DET")) t->det = atoi(e) != 0;
-    if (const char* e = getenv("RCED_TRAIN_FUSE_BWD")) t->fuse_bwd = atoi(e) != 0;
-    if (const char* e = getenv("RCED_TRAIN_X6")) t->use_x6 = atoi(e) != 0;
+    auto env = [](const char* name, bool* v) { if (const char* e = getenv(name)) *v = atoi(e) != 0; };
+    env("RCED_TRAIN_MFMA", &t->sw.mfma);
+    env("RCED_TRAIN_FUSE_ACT", &t->sw.fuse_act);
+    env("RCED_TRAIN_FUSE_DZ", &t->sw.fuse_dz);
+    env("RCED_TRAIN_FUSE_SUMS", &t->sw.fuse_sums);
+    env("RCED_TRAIN_FUSE_BWD", &t->sw.fuse_bwd);
+    env("RCED_TRAIN_X6", &t->sw.x6);
+    env("RCED_TRAIN_DET", &t->det);
   }
   const NetSpec* xnet = net;     // the reference's layout (what crosses the ABI)
   t->inet = *xnet;
   const int L = xnet->n_layers;
-  if (t->use_mfma)
+  if (t->sw.mfma)
     for (int l = 0; l < L; ++l)
       if (xnet->layer[l].use_norm) t->inet.layer[l].cout = (xnet->layer[l].cout + 1) & ~1;
   t->net = net = &t->inet;
@@ -565,34 +523,41 @@ int rced_train_create(int variant, const float* blob, size_t n_floats, int batch
       for (int co = 0; co < f.cout; ++co) start[f.mvar + co] = 1.f;
     }
   }
-  if (t->x2i.size() != n_floats) { delete t; return rced_fail(RCED_ERR_ARG, "blob layout: %zu floats mapped, %zu given", t->x2i.size(), n_floats); }
+  if (t->x2i.size() != n_floats) return rced_fail(RCED_ERR_ARG, "blob layout: %zu floats mapped, %zu given", t->x2i.size(), n_floats);
   for (size_t e = 0; e < n_floats; ++e) start[t->x2i[e]] = blob[e];
   n_floats = t->nvars;   // from here on: the internal blob
   blob = start.data();
-  auto fail_free = [&](int rc) { delete t; return rc; };
-#define TRY_OR_FREE(expr)                                                      \
-  do {                                                                         \
-    hipError_t e_ = (expr);                                                    \
-    if (e_ != hipSuccess) return fail_free(rced_fail(RCED_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_))); \
-  } while (0)
+  // which launcher runs where: decided here, once; a net the kernels that were built cannot train is refused now
+  plan::LayerAvail avail[kMaxLayers];
+  for (int l = 0; l < L; ++l) {
+    const LayerSpec& s = net->layer[l];
+    const LayerOff& f = t->off[l];
+    const size_t wgrad_lds = ((size_t)s.kh * (kFeatureDim + s.kw - 1) * f.cin + (size_t)kFeatureDim * s.cout) * sizeof(float);
+    avail[l] = plan::layer_avail(*net, l, f.K * s.cout <= train::kWgradMaxOut * train::kThreads && wgrad_lds <= 64 * 1024);
+  }
+  static_assert(plan::kPlanOk == RCED_OK && plan::kPlanErrArg == RCED_ERR_ARG && plan::kPlanErrState == RCED_ERR_STATE, "the planner's codes are the ABI's");
+  {
+    char why[160];
+    if (int rc = plan::plan_train(*net, t->sw, avail, &t->plan, why, sizeof why)) return rced_fail(rc, "%s", why);
+  }
   const size_t bytes = n_floats * sizeof(float);
-  TRY_OR_FREE(hipMalloc(&t->params, bytes));
-  TRY_OR_FREE(hipMalloc(&t->grads, bytes));
-  TRY_OR_FREE(hipMalloc(&t->m, bytes));
-  TRY_OR_FREE(hipMalloc(&t->v, bytes));
-  TRY_OR_FREE(hipMalloc(&t->trainable, n_floats));
-  TRY_OR_FREE(hipMemcpy(t->params, blob, bytes, hipMemcpyHostToDevice));
-  TRY_OR_FREE(hipMemset(t->m, 0, bytes));
-  TRY_OR_FREE(hipMemset(t->v, 0, bytes));
-  TRY_OR_FREE(hipMemcpy(t->trainable, mask.data(), n_floats, hipMemcpyHostToDevice));
-  TRY_OR_FREE(hipMalloc(&t->zero32, 64 * sizeof(float)));
-  TRY_OR_FREE(hipMemset(t->zero32, 0, 64 * sizeof(float)));
-  TRY_OR_FREE(hipMalloc(&t->part, (size_t)std::max(kReduceGrid, kPairGrid) * train::kMaxC * 2 * sizeof(double)));
-  TRY_OR_FREE(hipMalloc(&t->sums, (train::kMaxC * 2 + 2) * sizeof(double)));
+  HIP_TRY(t->alloc(&t->params, bytes));
+  HIP_TRY(t->alloc(&t->grads, bytes));
+  HIP_TRY(t->alloc(&t->m, bytes));
+  HIP_TRY(t->alloc(&t->v, bytes));
+  HIP_TRY(t->alloc(&t->trainable, n_floats));
+  HIP_TRY(hipMemcpy(t->params, blob, bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(t->m, 0, bytes));
+  HIP_TRY(hipMemset(t->v, 0, bytes));
+  HIP_TRY(hipMemcpy(t->trainable, mask.data(), n_floats, hipMemcpyHostToDevice));
+  HIP_TRY(t->alloc(&t->zero32, 64 * sizeof(float)));
+  HIP_TRY(hipMemset(t->zero32, 0, 64 * sizeof(float)));
+  HIP_TRY(t->alloc(&t->part, (size_t)std::max(kReduceGrid, kPairGrid) * train::kMaxC * 2 * sizeof(double)));
+  HIP_TRY(t->alloc(&t->sums, (train::kMaxC * 2 + 2) * sizeof(double)));
   t->redo = reinterpret_cast<int*>(t->sums + train::kMaxC * 2);
-  TRY_OR_FREE(hipMemset(t->redo, 0, 2 * sizeof(double)));
-  TRY_OR_FREE(hipHostMalloc(reinterpret_cast<void**>(&t->tiny_host), kMaxLayers * sizeof(int), hipHostMallocMapped));
-  TRY_OR_FREE(hipHostGetDevicePointer(reinterpret_cast<void**>(&t->tiny_dev), t->tiny_host, 0));
+  HIP_TRY(hipMemset(t->redo, 0, 2 * sizeof(double)));
+  HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&t->tiny_host), kMaxLayers * sizeof(int), hipHostMallocMapped));
+  HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&t->tiny_dev), t->tiny_host, 0));
   for (int l = 0; l < kMaxLayers; ++l) {
     t->tiny_host[l] = 0;
     if (l < L && net->layer[l].use_norm)
@@ -605,47 +570,22 @@ int rced_train_create(int variant, const float* blob, size_t n_floats, int batch
   for (int l = 0; l < L; ++l) {
     const LayerSpec& s = net->layer[l];
     const LayerOff& f = t->off[l];
-    TRY_OR_FREE(hipMalloc(&t->wf[l], (size_t)f.K * f.cout4 * sizeof(float)));
-    TRY_OR_FREE(hipMalloc(&t->wt[l], (size_t)s.kh * s.kw * s.cout * f.cin4 * sizeof(float)));
-    TRY_OR_FREE(hipMalloc(&t->bias4[l], 64 * sizeof(float)));
-    TRY_OR_FREE(hipMalloc(&t->mu[l], 64 * sizeof(float)));
-    TRY_OR_FREE(hipMalloc(&t->rstd[l], 64 * sizeof(float)));
-    if (first_has(s, f.cin) && !t->pk_first) TRY_OR_FREE(hipMalloc(&t->pk_first, first_packet_floats(s) * sizeof(float)));
-    if (is_output_layer(s, f.cin) && !t->pk_fin_bwd) TRY_OR_FREE(hipMalloc(&t->pk_fin_bwd, fin_dgrad_pack_floats(f.cin) * sizeof(float)));
-    if (is_output_layer(s, f.cin) && !t->pk_fin) TRY_OR_FREE(hipMalloc(&t->pk_fin, fin_pack_alloc_floats(f.cin) * sizeof(float)));
-    if (s.kh == 1 && tm_has(true, f.cin, s.kw, s.cout)) TRY_OR_FREE(hipMalloc(&t->pk_fwd[l], tm_packet_floats(f.cin, s.kw, s.cout) * sizeof(float)));
-    if (t->use_x6 && s.kh == 1 && t->pk_fwd[l] && rced::tmd::tm_x6_has(f.cin, s.kw, s.cout))
-      TRY_OR_FREE(hipMalloc(&t->pk_fwd_x6[l], rced::tmd::tm_packet_x6_floats(f.cin, s.kw, s.cout) * sizeof(float)));
-    if (s.kh == 1 && tm_has(false, s.cout, s.kw, f.cin)) TRY_OR_FREE(hipMalloc(&t->pk_bwd[l], tm_packet_floats(s.cout, s.kw, f.cin) * sizeof(float)));
+    HIP_TRY(t->alloc(&t->wf[l], (size_t)f.K * f.cout4 * sizeof(float)));
+    HIP_TRY(t->alloc(&t->wt[l], (size_t)s.kh * s.kw * s.cout * f.cin4 * sizeof(float)));
+    HIP_TRY(t->alloc(&t->bias4[l], 64 * sizeof(float)));
+    HIP_TRY(t->alloc(&t->mu[l], 64 * sizeof(float)));
+    HIP_TRY(t->alloc(&t->rstd[l], 64 * sizeof(float)));
+    if (avail[l].first && !t->pk_first) HIP_TRY(t->alloc(&t->pk_first, first_packet_floats(s) * sizeof(float)));
+    if (avail[l].output && !t->pk_fin_bwd) HIP_TRY(t->alloc(&t->pk_fin_bwd, fin_dgrad_pack_floats(f.cin) * sizeof(float)));
+    if (avail[l].output && !t->pk_fin) HIP_TRY(t->alloc(&t->pk_fin, fin_pack_alloc_floats(f.cin) * sizeof(float)));
+    if (avail[l].fwd) HIP_TRY(t->alloc(&t->pk_fwd[l], tm_packet_floats(f.cin, s.kw, s.cout) * sizeof(float)));
+    if (t->sw.x6 && avail[l].fwd && avail[l].x6)
+      HIP_TRY(t->alloc(&t->pk_fwd_x6[l], rced::tmd::tm_packet_x6_floats(f.cin, s.kw, s.cout) * sizeof(float)));
+    if (avail[l].dgrad) HIP_TRY(t->alloc(&t->pk_bwd[l], tm_packet_floats(s.cout, s.kw, f.cin) * sizeof(float)));
     if (t->pk_bwd[l] && tmm::bwd_x6(f.cin, s.kw, s.cout))   // (compiled into the fused kernel of this shape: not a per-trainer switch)
-      TRY_OR_FREE(hipMalloc(&t->pk_bwd_x6[l], rced::tmd::tm_packet_x6_floats(s.cout, s.kw, f.cin) * sizeof(float)));
+      HIP_TRY(t->alloc(&t->pk_bwd_x6[l], rced::tmd::tm_packet_x6_floats(s.cout, s.kw, f.cin) * sizeof(float)));
   }
-  // Tensors that need not exist in HBM: output of a plain conv+BN+ReLU layer (no skip in or out) whose only
-  // consumer is a 1xk layer with MFMA forward and wgrad kernels.  RCED_TRAIN_FUSE_ACT=0 turns this off.
-  t->virt.assign(L + 1, 0);
-  {
-    const char* e = getenv("RCED_TRAIN_FUSE_ACT");
-    const bool fuse = t->use_mfma && !(e && atoi(e) == 0);
-    std::vector<int> uses(L + 1, 0), conv_user(L + 1, -1), post_uses(L + 1, 0);
-    for (int l = 0; l < L; ++l) {
-      const LayerSpec& s = t->net->layer[l];
-      if (s.src > 0) { ++uses[s.src]; conv_user[s.src] = l; }
-      if (s.skip_pre > 0) uses[s.skip_pre] += 2;     // a skip added before the ReLU disqualifies (its backward reads the tensor)
-      // a skip added AFTER a ReLU (CR-CED's block skips) is read once, by bn_act_fwd2, which rebuilds it from the
-      // producer's z just as well (same bytes, same arithmetic); its backward needs no values
-      if (s.skip_post > 0) { if (s.cout % 2 == 0 && s.skip_pre < 0) ++post_uses[s.skip_post]; else uses[s.skip_post] += 2; }
-    }
-    for (int id = 1; fuse && id < L; ++id) {
-      const LayerSpec& p = t->net->layer[id - 1];
-      const int c = conv_user[id];
-      if (uses[id] != 1 || c < 0 || post_uses[id] > 1) continue;
-      const LayerSpec& q = t->net->layer[c];
-      t->virt[id] = p.use_norm && p.use_act && p.skip_pre < 0 && p.skip_post < 0 && p.cout % 2 == 0 && q.kh == 1 &&
-                    q.cout % 2 == 0 && t->pk_fwd[c] != nullptr && tm_has(true, p.cout, q.kw, q.cout);
-    }
-  }
-#undef TRY_OR_FREE
-  *out = t;
+  *out = owner.release();
   return RCED_OK;
 }
 
@@ -718,14 +658,7 @@ int train_run(rced_trainer* t, const float* x_dev, const float* y_dev, float* pr
   const int L = net.n_layers, F = kFeatureDim, frames = N * T;
   const size_t P = (size_t)frames * F;
   if (int rc = ensure_acts(t, P)) return rc;
-  // deterministic weight gradients: the wgrad launchers of this thread write slices into t->wpart (tmd::WgDet)
-  struct WgScope {
-    explicit WgScope(rced_trainer* tr) {
-      tr->wg_error = 0;
-      rced::tmd::g_wgdet = tr->det ? rced::tmd::WgDet{&tr->wpart, &tr->wpart_floats, &tr->wg_error} : rced::tmd::WgDet{};
-    }
-    ~WgScope() { rced::tmd::g_wgdet = rced::tmd::WgDet{}; }
-  };
+  const plan::TrainPlan& plan = t->plan;   // which launcher runs where, and who stores / accumulates / zeroes what: train_plan.h
   if (t->det && !forward_only && !t->wpart) {
     // Sized BEFORE the forward for the most any wgrad launcher can ask for: slices = workgroups (CUs x at most 4 resident per
     // CU) x 8 waves x 2 pixel parities, slice stride = the net's largest kernel + bias.  A failure to allocate is therefore
@@ -740,7 +673,9 @@ int train_run(rced_trainer* t, const float* x_dev, const float* y_dev, float* pr
     t->wpart_floats = (size_t)t->num_cus * 4 * 8 * 2 * maxps;
     HIP_TRY(hipMalloc(&t->wpart, t->wpart_floats * sizeof(float)));
   }
-  const WgScope wg_scope(t);
+  // deterministic weight gradients: the wgrad launchers write slices into t->wpart; otherwise fp32 atomics
+  t->wg_error = 0;
+  const WgDet wd = t->det ? WgDet{&t->wpart, &t->wpart_floats, &t->wg_error} : WgDet{};
   auto blocks = [](size_t n) { return dim3((unsigned)std::min<size_t>((n + train::kThreads - 1) / train::kThreads, 65535)); };
   auto pair_grid = [&](int C) {   // channel-aligned kernels: rows = 256 / (C/2) pixels per workgroup pass
     const size_t rows = train::kThreads / (C / 2);
@@ -748,125 +683,116 @@ int train_run(rced_trainer* t, const float* x_dev, const float* y_dev, float* pr
   };
   // a virtual tensor is read as its producer's z plus that layer's BatchNorm parameters (BnReluXform)
   tmm::XformArgs xa_tmp{nullptr, nullptr, nullptr, nullptr};
-  auto conv_in = [&](int id) -> const float* { return id == 0 ? x_dev : (t->virt[id] ? t->z[id - 1] : t->out[id]); };
+  auto conv_in = [&](int id) -> const float* { return id == 0 ? x_dev : (plan.virt(id) ? t->z[id - 1] : t->out[id]); };
   auto xform_of = [&](int id, tmm::XformArgs* xa) -> const tmm::XformArgs* {
-    if (id <= 0 || !t->virt[id]) return nullptr;
+    if (id <= 0 || !plan.virt(id)) return nullptr;
     const LayerOff& pf = t->off[id - 1];
     *xa = tmm::XformArgs{t->mu[id - 1], t->rstd[id - 1], t->params + pf.gamma, t->params + pf.beta};
     return xa;
   };
   auto tensor = [&](int id) -> const float* { return id < 0 ? nullptr : (id == 0 ? x_dev : t->out[id]); };
+  auto no_kernel = [](int l, const char* what) { return rced_fail(RCED_ERR_STATE, "layer %d: the planned %s kernel was not built", l, what); };
+  auto zero_grad = [&](int id) { return hipMemsetAsync(t->G[id], 0, P * net.layer[id - 1].cout * sizeof(float), st); };
 
-  // consumers[id]: how many layers read tensor id (as conv input or as a skip)
-  std::vector<int> consumers(L + 1, 0);
-  for (int l = 0; l < L; ++l) {
-    if (net.layer[l].src > 0) ++consumers[net.layer[l].src];
-    if (net.layer[l].skip_pre > 0) ++consumers[net.layer[l].skip_pre];
-    if (net.layer[l].skip_post > 0) ++consumers[net.layer[l].skip_post];
-  }
-  // ---- weights in the layouts the direct-convolution kernels want (only for layers that fall back to them)
+  // ---- weights in the layouts the direct-convolution kernels want, and the MFMA kernels' packets
   for (int l = 0; l < L; ++l) {
     const LayerSpec& s = net.layer[l];
     const LayerOff& f = t->off[l];
-    const bool mfma_fwd = t->use_mfma && (t->pk_fwd[l] || (t->pk_first && first_has(s, f.cin)) || (t->pk_fin && is_output_layer(s, f.cin)));
-    const bool mfma_bwd = t->use_mfma && (s.src == 0 || t->pk_bwd[l] ||
-                                          (t->pk_fin_bwd && is_output_layer(s, f.cin) && consumers[s.src] == 1));
-    if (!mfma_fwd) {
+    if (plan.layer[l].repack_fwd) {
       hipLaunchKernelGGL(train::repack_fwd, dim3((f.K * f.cout4 + 255) / 256), dim3(256), 0, st, t->params + f.kernel, f.K,
                          s.cout, f.cout4, t->wf[l]);
       hipLaunchKernelGGL(train::repack_fwd, dim3(1), dim3(64), 0, st, t->params + f.bias, 1, s.cout, f.cout4, t->bias4[l]);
     }
-    if (!mfma_bwd) {
+    if (plan.layer[l].repack_dgrad) {
       const int nt = s.kh * s.kw * s.cout * f.cin4;
       hipLaunchKernelGGL(train::repack_dgrad, dim3((nt + 255) / 256), dim3(256), 0, st, t->params + f.kernel, s.kh, s.kw,
                          f.cin, s.cout, f.cin4, t->wt[l]);
     }
   }
-  if (t->use_mfma)
-    for (int l = 0; l < L; ++l) {
-      const LayerSpec& s = net.layer[l];
-      const LayerOff& f = t->off[l];
-      if (t->pk_fwd_x6[l]) {
-        const int n = rced::tmd::tm_packet_x6_threads(f.cin, s.kw, s.cout);
-        hipLaunchKernelGGL(tmm::pack_packet_x6, dim3((n + 255) / 256), dim3(256), 0, st, (const float*)(t->params + f.kernel),
-                           (const float*)(t->params + f.bias), s.kw, f.cin, s.cout, rced::tmd::tm_packet_parities(s.cout), t->pk_fwd_x6[l]);
-      } else if (t->pk_fwd[l]) {
-        const int n = (int)tm_packet_floats(f.cin, s.kw, s.cout);
-        hipLaunchKernelGGL(tmm::pack_packet, dim3((n + 255) / 256), dim3(256), 0, st, (const float*)(t->params + f.kernel),
-                           (const float*)(t->params + f.bias), s.kw, f.cin, s.cout, 0, rced::tmd::tm_packet_parities(s.cout),
-                           t->pk_fwd[l]);
-      }
-      if (t->pk_bwd_x6[l]) {
-        // the fused backward kernel of this shape runs its dgrad half in the three-part bf16 form: its packet in that form too
-        // (the fp32 packet below stays: the separate dgrad kernel takes it when the fused one is not used)
-        const int n = rced::tmd::tm_packet_x6_threads(s.cout, s.kw, f.cin);
-        hipLaunchKernelGGL(tmm::pack_packet_x6, dim3((n + 255) / 256), dim3(256), 0, st, (const float*)(t->params + f.kernel),
-                           (const float*)nullptr, s.kw, s.cout, f.cin, rced::tmd::tm_packet_parities(f.cin), t->pk_bwd_x6[l], 1);
-      }
-      if (t->pk_bwd[l]) {
-        const int n = (int)tm_packet_floats(s.cout, s.kw, f.cin);
-        hipLaunchKernelGGL(tmm::pack_packet, dim3((n + 255) / 256), dim3(256), 0, st, (const float*)(t->params + f.kernel),
-                           (const float*)nullptr, s.kw, s.cout, f.cin, 1, rced::tmd::tm_packet_parities(f.cin), t->pk_bwd[l]);
-      }
+  for (int l = 0; l < L; ++l) {
+    const LayerSpec& s = net.layer[l];
+    const LayerOff& f = t->off[l];
+    if (plan.layer[l].fwd == plan::Fwd::X6) {
+      const int n = rced::tmd::tm_packet_x6_threads(f.cin, s.kw, s.cout);
+      hipLaunchKernelGGL(tmm::pack_packet_x6, dim3((n + 255) / 256), dim3(256), 0, st, (const float*)(t->params + f.kernel),
+                         (const float*)(t->params + f.bias), s.kw, f.cin, s.cout, rced::tmd::tm_packet_parities(s.cout), t->pk_fwd_x6[l]);
+    } else if (plan.layer[l].fwd == plan::Fwd::Mfma) {
+      const int n = (int)tm_packet_floats(f.cin, s.kw, s.cout);
+      hipLaunchKernelGGL(tmm::pack_packet, dim3((n + 255) / 256), dim3(256), 0, st, (const float*)(t->params + f.kernel),
+                         (const float*)(t->params + f.bias), s.kw, f.cin, s.cout, 0, rced::tmd::tm_packet_parities(s.cout),
+                         t->pk_fwd[l]);
     }
+    if (plan.layer[l].pack_dgrad && t->pk_bwd_x6[l]) {
+      // the fused backward kernel of this shape runs its dgrad half in the three-part bf16 form: its packet in that form too
+      // (the fp32 packet below stays: the separate dgrad kernel takes it when the fused one is not used)
+      const int n = rced::tmd::tm_packet_x6_threads(s.cout, s.kw, f.cin);
+      hipLaunchKernelGGL(tmm::pack_packet_x6, dim3((n + 255) / 256), dim3(256), 0, st, (const float*)(t->params + f.kernel),
+                         (const float*)nullptr, s.kw, s.cout, f.cin, rced::tmd::tm_packet_parities(f.cin), t->pk_bwd_x6[l], 1);
+    }
+    if (plan.layer[l].pack_dgrad) {
+      const int n = (int)tm_packet_floats(s.cout, s.kw, f.cin);
+      hipLaunchKernelGGL(tmm::pack_packet, dim3((n + 255) / 256), dim3(256), 0, st, (const float*)(t->params + f.kernel),
+                         (const float*)nullptr, s.kw, s.cout, f.cin, 1, rced::tmd::tm_packet_parities(f.cin), t->pk_bwd[l]);
+    }
+  }
   // ---- forward (is_training=True)
   for (int l = 0; l < L; ++l) {
     const LayerSpec& s = net.layer[l];
     const LayerOff& f = t->off[l];
-    int stat_parts = 0;   // > 0: the conv kernel already left that many (sum z, sum z^2) records in t->part
-    if (t->use_mfma && t->pk_fwd_x6[l] &&
-        (stat_parts = rced::tmd::tm_conv_x6(f.cin, s.kw, s.cout, s.use_norm != 0, conv_in(s.src), t->pk_fwd_x6[l], t->z[l], frames,
-                                            t->num_cus, t->part, xform_of(s.src, &xa_tmp), st)) > 0) {
-      if (!s.use_norm) stat_parts = 0;
-    } else if (t->use_mfma && t->pk_fwd[l] &&
-        (stat_parts = tm_conv(true, f.cin, s.kw, s.cout, false, s.use_norm != 0, conv_in(s.src), t->pk_fwd[l], t->z[l],
-                              frames, t->num_cus, t->part, xform_of(s.src, &xa_tmp), nullptr, st)) > 0) {
-      if (!s.use_norm) stat_parts = 0;
-    } else if (t->use_mfma && t->pk_first && first_has(s, f.cin) &&
-               (stat_parts = first_fwd(s, x_dev, t->params + f.kernel, t->params + f.bias, t->pk_first, t->z[l], frames, T,
-                                       t->num_cus, s.use_norm != 0, t->part, st)) > 0) {
-      if (!s.use_norm) stat_parts = 0;
-    } else if (t->use_mfma && t->pk_fin && is_output_layer(s, f.cin)) {
-      fin_forward(f.cin, tensor(s.src), t->params + f.kernel, t->params + f.bias, t->pk_fin, t->z[l], frames, st, t->use_x6);
-    } else if (s.src > 0 && t->virt[s.src]) {
-      // a virtual input exists only inside the MFMA kernels' staging: never hand its (null) pointer to the direct kernel
-      return rced_fail(RCED_ERR_STATE, "layer %d: no MFMA forward kernel for a layer whose input is not materialised", l);
-    } else if (int rc = launch_conv(tensor(s.src), t->z[l], t->wf[l], t->bias4[l], nullptr, frames, T, F, f.cin, s.cout,
-                                    f.cout4, s.kh, s.kw, (s.kh - 1) / 2, (s.kw - 1) / 2, st)) {
-      return rc;
+    const plan::LayerPlan& pl = plan.layer[l];
+    const bool stats = s.use_norm != 0;
+    int stat_parts = 0;   // the (sum z, sum z^2) records the conv kernel left in t->part (Stats::Conv)
+    switch (pl.fwd) {
+      case plan::Fwd::X6:
+        stat_parts = rced::tmd::tm_conv_x6(f.cin, s.kw, s.cout, stats, conv_in(s.src), t->pk_fwd_x6[l], t->z[l], frames, t->num_cus,
+                                           t->part, xform_of(s.src, &xa_tmp), st);
+        break;
+      case plan::Fwd::Mfma:
+        stat_parts = tm_conv(true, f.cin, s.kw, s.cout, false, stats, conv_in(s.src), t->pk_fwd[l], t->z[l], frames, t->num_cus, t->part,
+                             xform_of(s.src, &xa_tmp), nullptr, st);
+        break;
+      case plan::Fwd::First:
+        stat_parts = first_fwd(s, x_dev, t->params + f.kernel, t->params + f.bias, t->pk_first, t->z[l], frames, T, t->num_cus, stats,
+                               t->part, st);
+        break;
+      case plan::Fwd::Output:
+        stat_parts = fin_forward(f.cin, tensor(s.src), t->params + f.kernel, t->params + f.bias, t->pk_fin, t->z[l], frames, st, t->sw.x6);
+        break;
+      case plan::Fwd::Generic:
+        if (int rc = launch_conv(tensor(s.src), t->z[l], t->wf[l], t->bias4[l], nullptr, frames, T, F, f.cin, s.cout, f.cout4, s.kh,
+                                 s.kw, (s.kh - 1) / 2, (s.kw - 1) / 2, st))
+          return rc;
+        stat_parts = 1;
+        break;
     }
+    if (stat_parts <= 0) return no_kernel(l, "forward");
     const size_t n = P * s.cout;
-    if (s.use_norm) {
-      if (stat_parts > 0) {
-        FinishArgs fa{};
-        fa.P = (double)P; fa.eps = kBnEps; fa.momentum = forward_only ? 1.f : kBnMomentum;   // momentum 1: the moving statistics stay as they are
-        fa.mu_out = t->mu[l]; fa.rstd_out = t->rstd[l]; fa.moving_mean = t->params + f.mmean; fa.moving_var = t->params + f.mvar;
-        hipLaunchKernelGGL(bn_finish, dim3(1), dim3(1024), 0, st, (const double*)t->part, stat_parts, s.cout, t->sums, (int)kFinStats, fa,
-                           (const int*)nullptr);
-      } else {
-        if (int rc = reduce_channels(t, t->z[l], t->z[l], nullptr, nullptr, P, s.cout, st)) return rc;
-        hipLaunchKernelGGL(train::bn_stats_finish, dim3(1), dim3(64), 0, st, (const double*)t->sums, (double)P, s.cout,
-                           kBnEps, forward_only ? 1.f : kBnMomentum, t->mu[l], t->rstd[l], t->params + f.mmean,
-                           t->params + f.mvar);
-      }
+    if (pl.stats == plan::Stats::Conv) {
+      FinishArgs fa{};
+      fa.P = (double)P; fa.eps = kBnEps; fa.momentum = forward_only ? 1.f : kBnMomentum;   // momentum 1: the moving statistics stay as they are
+      fa.mu_out = t->mu[l]; fa.rstd_out = t->rstd[l]; fa.moving_mean = t->params + f.mmean; fa.moving_var = t->params + f.mvar;
+      hipLaunchKernelGGL(bn_finish, dim3(1), dim3(1024), 0, st, (const double*)t->part, stat_parts, s.cout, t->sums, (int)kFinStats, fa,
+                         (const int*)nullptr);
+    } else if (pl.stats == plan::Stats::Reduce) {
+      if (int rc = reduce_channels(t, t->z[l], t->z[l], nullptr, nullptr, P, s.cout, st)) return rc;
+      hipLaunchKernelGGL(train::bn_stats_finish, dim3(1), dim3(64), 0, st, (const double*)t->sums, (double)P, s.cout,
+                         kBnEps, forward_only ? 1.f : kBnMomentum, t->mu[l], t->rstd[l], t->params + f.mmean,
+                         t->params + f.mvar);
     }
-    if (t->out[l + 1] != t->z[l] && !t->virt[l + 1]) {
+    if (pl.bn_act == plan::BnAct::Pair) {
       // a virtual post-ReLU skip source: rebuilt from its producer's z inside bn_act_fwd2
-      const bool vskip = s.skip_post > 0 && t->virt[s.skip_post] != 0;
       tmm::XformArgs vs{nullptr, nullptr, nullptr, nullptr};
-      if (vskip) xform_of(s.skip_post, &vs);
-      if (vskip && s.cout % 2 != 0) return rced_fail(RCED_ERR_STATE, "layer %d: a virtual skip source needs the pair kernel", l);
-      if (s.cout % 2 == 0)
-        hipLaunchKernelGGL(train::bn_act_fwd2, pair_grid(s.cout), dim3(train::kThreads), 0, st, (const float2*)t->z[l],
-                           s.use_norm ? (const float*)t->mu[l] : nullptr, (const float*)t->rstd[l],
-                           (const float*)(t->params + f.gamma), (const float*)(t->params + f.beta),
-                           (const float2*)tensor(s.skip_pre), (const float2*)(vskip ? t->z[s.skip_post - 1] : tensor(s.skip_post)),
-                           s.use_act, P, s.cout, (float2*)t->out[l + 1], vskip ? vs.mu : nullptr, vs.rstd, vs.gamma, vs.beta);
-      else
-        hipLaunchKernelGGL(train::bn_act_fwd, blocks(n), dim3(train::kThreads), 0, st, (const float*)t->z[l],
-                           s.use_norm ? (const float*)t->mu[l] : nullptr, (const float*)t->rstd[l],
-                           (const float*)(t->params + f.gamma), (const float*)(t->params + f.beta), tensor(s.skip_pre),
-                           tensor(s.skip_post), s.use_act, n, s.cout, t->out[l + 1]);
+      if (pl.vskip) xform_of(s.skip_post, &vs);
+      hipLaunchKernelGGL(train::bn_act_fwd2, pair_grid(s.cout), dim3(train::kThreads), 0, st, (const float2*)t->z[l],
+                         s.use_norm ? (const float*)t->mu[l] : nullptr, (const float*)t->rstd[l],
+                         (const float*)(t->params + f.gamma), (const float*)(t->params + f.beta),
+                         (const float2*)tensor(s.skip_pre), (const float2*)(pl.vskip ? t->z[s.skip_post - 1] : tensor(s.skip_post)),
+                         s.use_act, P, s.cout, (float2*)t->out[l + 1], pl.vskip ? vs.mu : nullptr, vs.rstd, vs.gamma, vs.beta);
+    } else if (pl.bn_act == plan::BnAct::Scalar) {
+      hipLaunchKernelGGL(train::bn_act_fwd, blocks(n), dim3(train::kThreads), 0, st, (const float*)t->z[l],
+                         s.use_norm ? (const float*)t->mu[l] : nullptr, (const float*)t->rstd[l],
+                         (const float*)(t->params + f.gamma), (const float*)(t->params + f.beta), tensor(s.skip_pre),
+                         tensor(s.skip_post), s.use_act, n, s.cout, t->out[l + 1]);
     }
   }
   HIP_TRY(hipGetLastError());
@@ -880,124 +806,57 @@ int train_run(rced_trainer* t, const float* x_dev, const float* y_dev, float* pr
                      P, 1.f / (float)t->batch_size, t->G[L], t->part);
   std::vector<double> hp(kReduceGrid);
   HIP_TRY(hipMemcpyAsync(hp.data(), t->part, kReduceGrid * sizeof(double), hipMemcpyDeviceToHost, st));
-  // ---- backward
+  // ---- backward.  G[id] collects d loss / d tensor id from every consumer (the conv reading it, skip adds); the plan says
+  // which writer stores, which add, and which tensors are zeroed first.
   HIP_TRY(hipMemsetAsync(t->grads, 0, t->nvars * sizeof(float), st));
-  // G[id] collects d loss / d tensor id from every consumer (the conv reading it, skip adds).  A tensor with one
-  // consumer is written (=) by that consumer's dgrad; the others are zeroed here and accumulated into (+=).
-  auto overwrite = [&](int l) {   // layer l's dgrad may overwrite G[src] (MFMA path only; the generic kernel always +=)
-    const LayerSpec& s = net.layer[l];
-    const bool mfma_dgrad = t->pk_bwd[l] != nullptr || (t->pk_fin_bwd != nullptr && is_output_layer(s, t->off[l].cin));
-    return t->use_mfma && mfma_dgrad && s.src > 0 && consumers[s.src] == 1;
-  };
-  std::vector<char> lazy_zero(L + 1, 0), written(L + 1, 0);
-  {
-    std::vector<char> plain(L + 1, 0);
-    for (int l = 0; l < L; ++l) if (overwrite(l)) plain[net.layer[l].src] = 1;
-    // A tensor that some layer adds as a skip gets its first gradient contribution from that layer's bwd_route2 (the skip
-    // consumer comes later in the net than the convolution that reads the tensor, so earlier in this loop), which can
-    // STORE it: no memset, no read-modify-write there.  written[id] tracks it; whoever must add to a tensor nobody has
-    // written yet zeroes it first (ensure_zero: not reached in the three nets).
-    for (int l = 0; l < L; ++l) {
-      const LayerSpec& s = net.layer[l];
-      if (t->use_mfma && s.cout % 2 == 0) {
-        if (s.skip_pre > 0) lazy_zero[s.skip_pre] = 1;
-        if (s.skip_post > 0) lazy_zero[s.skip_post] = 1;
-      }
-    }
-    for (int id = 1; id < L; ++id) {
-      if (plain[id] || !lazy_zero[id]) written[id] = 1;
-      if (!plain[id] && !lazy_zero[id]) HIP_TRY(hipMemsetAsync(t->G[id], 0, P * net.layer[id - 1].cout * sizeof(float), st));
-    }
-  }
-  auto ensure_zero = [&](int id) -> int {
-    if (id > 0 && !written[id]) {
-      HIP_TRY(hipMemsetAsync(t->G[id], 0, P * net.layer[id - 1].cout * sizeof(float), st));
-      written[id] = 1;
-    }
-    return RCED_OK;
-  };
-  // fused_sums[l] > 0: the dgrad that wrote G[l + 1] (layer l's only consumer) has left that many (sum d_u, sum d_u z)
-  // records of layer l's BatchNorm backward in t->part (tmm::SumArgs): no bwd_route2 pass for layer l.
+  for (int id = 1; id < L; ++id)
+    if (plan.zero_first[id]) HIP_TRY(zero_grad(id));
   int tiny[kMaxLayers];
   for (int l = 0; l < kMaxLayers; ++l) tiny[l] = t->tiny_host[l];     // as of the end of the previous step (it synchronised)
-  std::vector<int> fused_sums(L, 0);
-  std::vector<char> sums_from_x(L, 0);   // those records hold (sum d_u, sum d_u * x) (fused backward kernel) rather than (.., sum d_u * z)
-  const bool fuse_sums_on = t->fuse_sums;
-  auto fuse_dz_of = [&](int l) {
-    const LayerSpec& s = net.layer[l];
-    const LayerOff& f = t->off[l];
-    return t->fuse_dz && t->use_mfma && s.use_norm && s.cout % 2 == 0 &&
-           ((t->use_mfma && first_has(s, f.cin)) || (s.kh == 1 && f.cin % 2 == 0 && tm_has(true, f.cin, s.kw, s.cout) &&
-                                                    (s.src == 0 || t->pk_bwd[l] != nullptr)));
-  };
-  auto lazy_mask_of = [&](int l) {
-    const LayerSpec& s = net.layer[l];
-    // (a skip added AFTER the ReLU -- CR-CED's block outputs, model.py:75-76 -- does not enter the mask: d_u = g [bn(z) > 0]
-    // there too, so those layers' d_u need not be written either; bwd_route2 still routes g to the skip's source)
-    return fuse_dz_of(l) && s.use_act && s.skip_pre < 0;
-  };
-  // alias_src[id]: G[id]'s first contribution would be a plain copy of another gradient tensor (layer ls adds tensor id
-  // AFTER its ReLU: d tensor id += G[ls + 1] unchanged).  The copy is not made: the one dgrad that completes G[id] reads
-  // its accumulate operand from G[ls + 1] instead (out = acc_from + conv).  G[ls + 1] is final by then -- its writers are
-  // the consumers of tensor ls + 1, all later layers -- and every G tensor is its own allocation.
-  std::vector<const float*> alias_src(L + 1, nullptr);
-  auto conv_consumer_of = [&](int id) {   // the layer reading tensor id as its convolution input, when there is exactly one
-    int lc = -1;
-    for (int k = 0; k < L; ++k)
-      if (net.layer[k].src == id) lc = lc < 0 ? k : -2;
-    return lc;
-  };
-  auto alias_ok = [&](int l) {
-    const LayerSpec& s = net.layer[l];
-    if (!t->use_mfma || !t->fuse_dz || s.skip_post <= 0 || s.skip_pre > 0 || written[s.skip_post] || consumers[s.skip_post] != 2) return false;
-    const int lc = conv_consumer_of(s.skip_post);
-    if (lc < 0 || lc >= l || !t->pk_bwd[lc]) return false;
-    const LayerSpec& c = net.layer[lc];
-    return c.kh == 1 && c.cout % 2 == 0 && tm_has(false, c.cout, c.kw, t->off[lc].cin);
-  };
-  // a producer whose BatchNorm-backward sums may come out of its consumer's dgrad: masked lazily, and nothing left to
-  // route -- no skip, or a post-ReLU skip whose gradient is not copied (alias_ok; evaluated here, at the consumer, and again at
-  // the producer itself, with nothing writing the skip's gradient tensor in between)
-  auto sums_in_dgrad_ok = [&](int pl) { return lazy_mask_of(pl) && (net.layer[pl].skip_post < 0 || alias_ok(pl)); };
+  // src_parts[l]: the records of layer l's BatchNorm-backward sums that its consumer's dgrad left in t->part (Sums::DgradZ / FusedX)
+  std::vector<int> src_parts(L, 0);
   for (int l = L - 1; l >= 0; --l) {
     const LayerSpec& s = net.layer[l];
     const LayerOff& f = t->off[l];
+    const plan::LayerPlan& pl = plan.layer[l];
     const size_t n = P * s.cout;
     const float* mu = s.use_norm ? t->mu[l] : nullptr;
-    const bool pairs = s.cout % 2 == 0;
-    // BatchNorm backward: either applied in place on D (bn_bwd_apply*), or -- when both consumers of dz are MFMA
-    // kernels -- folded into their staging, which reads (d_u, z) and never materialises dz (tile_commit_bnbwd).
-    // For a plain conv+BN+ReLU layer (no skip in or out) d_u is not materialised either: the consumers read the
-    // incoming gradient g and apply the ReLU mask themselves; bwd_route2 then only produces the two sums.
-    const bool first_mfma = t->use_mfma && first_has(s, f.cin);
-    const bool fuse_dz = fuse_dz_of(l);
-    const bool lazy_mask = lazy_mask_of(l);
-    // a linear layer without BatchNorm or skips (decode_final): d_u IS the incoming gradient -- no routing pass, no copy
-    const bool passthrough = t->use_mfma && !s.use_act && !s.use_norm && s.skip_pre < 0 && s.skip_post < 0 && is_output_layer(s, f.cin) && t->pk_fin &&
-                             t->pk_fin_bwd && s.src > 0 && consumers[s.src] == 1;   // (both of its consumers below take dsrc)
-    const float* dsrc = lazy_mask || passthrough ? t->G[l + 1] : t->D;      // what wgrad / dgrad read as their "dz" input
-    bool grads_out = false;      // d beta / d gamma already written by bn_finish
+    // BatchNorm backward: either applied in place on D (bn_bwd_apply*), or (fuse_dz) folded into the staging of the wgrad and
+    // dgrad kernels, which read (d_u, z) and never materialise dz (tile_commit_bnbwd).  With lazy_mask d_u is not materialised
+    // either: the consumers read the incoming gradient g and apply the ReLU mask themselves.  passthrough: d_u IS g.
+    const float* dsrc = pl.lazy_mask || pl.passthrough ? t->G[l + 1] : t->D;      // what wgrad / dgrad read as their "dz" input
     FinishArgs fb{};
     fb.mu = mu; fb.rstd = t->rstd[l]; fb.gamma = t->params + f.gamma; fb.beta = t->params + f.beta;
     fb.g_beta = t->grads + f.beta; fb.g_gamma = t->grads + f.gamma; fb.redo = t->redo;
-    // a post-ReLU skip whose gradient is not copied (alias_src above): recorded before the branches -- the layer's sums may
-    // already be there (fused_sums), in which case nothing of this layer is routed at all
-    const bool alias = alias_ok(l);
-    if (alias) {
-      alias_src[s.skip_post] = t->G[l + 1];
-      written[s.skip_post] = 1;
-    }
-    if (passthrough) {
-      // nothing to route
-    } else if (lazy_mask && fused_sums[l] > 0) {
-      if (s.skip_post > 0 && !alias)
-        return rced_fail(RCED_ERR_STATE, "layer %d: sums came out of the dgrad but its skip gradient still needs routing", l);
-      hipLaunchKernelGGL(bn_finish, dim3(1), dim3(1024), 0, st, (const double*)t->part, fused_sums[l], s.cout, t->sums,
-                         (int)(sums_from_x[l] ? kFinX : kFinZ), fb, (const int*)nullptr);
-      grads_out = true;
-      if (sums_from_x[l] && tiny[l]) {
+    float* const g_pre = s.skip_pre > 0 ? t->G[s.skip_pre] : nullptr;
+    float* const g_post = s.skip_post > 0 && !pl.skip_alias ? t->G[s.skip_post] : nullptr;
+    if (pl.zero_before_skip) HIP_TRY(zero_grad(plan::skip_of(s)));
+    if (pl.route == plan::Route::Pair) {
+      const dim3 grid = pair_grid(s.cout);
+      hipLaunchKernelGGL(train::bwd_route2, grid, dim3(train::kThreads), 0, st, (const float2*)t->G[l + 1],
+                         (const float2*)t->z[l], mu, (const float*)t->rstd[l], (const float*)(t->params + f.gamma),
+                         (const float*)(t->params + f.beta), (const float2*)tensor(s.skip_pre), s.use_act, P, s.cout,
+                         (float2*)g_pre, (float2*)g_post, (float2*)(pl.lazy_mask ? nullptr : t->D),
+                         s.use_norm ? t->part : (double*)nullptr, (const int*)nullptr, pl.skip_first ? 1 : 0);
+      if (pl.sums == plan::Sums::Route2)
+        hipLaunchKernelGGL(bn_finish, dim3(1), dim3(1024), 0, st, (const double*)t->part, (int)grid.x, s.cout, t->sums,
+                           (int)kFinPlain, fb, (const int*)nullptr);
+    } else if (pl.route == plan::Route::Scalar) {
+      hipLaunchKernelGGL(train::bwd_route, blocks(n), dim3(train::kThreads), 0, st, (const float*)t->G[l + 1],
+                         (const float*)t->z[l], mu, (const float*)t->rstd[l], (const float*)(t->params + f.gamma),
+                         (const float*)(t->params + f.beta), tensor(s.skip_pre), s.use_act, n, s.cout, g_pre, g_post, t->D);
+      if (pl.sums == plan::Sums::RouteReduce) {
+        if (int rc = reduce_channels(t, t->D, t->z[l], mu, t->rstd[l], P, s.cout, st)) return rc;
+        hipLaunchKernelGGL(sums_to_float, dim3(1), dim3(64), 0, st, (const double*)t->sums, s.cout, 0, t->grads + f.beta);
+        hipLaunchKernelGGL(sums_to_float, dim3(1), dim3(64), 0, st, (const double*)t->sums, s.cout, 1, t->grads + f.gamma);
+      }
+    } else if (pl.sums == plan::Sums::DgradZ || pl.sums == plan::Sums::FusedX) {
+      const bool from_x = pl.sums == plan::Sums::FusedX;   // (sum d_u, sum d_u * x) rather than (.., sum d_u * z)
+      hipLaunchKernelGGL(bn_finish, dim3(1), dim3(1024), 0, st, (const double*)t->part, src_parts[l], s.cout, t->sums,
+                         (int)(from_x ? kFinX : kFinZ), fb, (const int*)nullptr);
+      if (from_x && tiny[l]) {
         // |gamma| tiny somewhere in this layer (known on the host since the previous step's tiny_gamma_scan): the sums
-        // again, exactly, from (g, z); see sums_fix_x.  Never taken in a real training run.
+        // again, exactly, from (g, z); see kTinyGamma.  Never taken in a real training run.
         const dim3 grid = pair_grid(s.cout);
         hipLaunchKernelGGL(train::bwd_route2, grid, dim3(train::kThreads), 0, st, (const float2*)t->G[l + 1],
                            (const float2*)t->z[l], mu, (const float*)t->rstd[l], (const float*)(t->params + f.gamma),
@@ -1006,44 +865,12 @@ int train_run(rced_trainer* t, const float* x_dev, const float* y_dev, float* pr
         hipLaunchKernelGGL(bn_finish, dim3(1), dim3(1024), 0, st, (const double*)t->part, (int)grid.x, s.cout, t->sums,
                            (int)kFinPlain, fb, (const int*)nullptr);
       }
-    } else if (pairs) {
-      const dim3 grid = pair_grid(s.cout);
-      // (a layer has at most one skip; first writer of its gradient tensor: store, see `written`)
-      const int skip_id = s.skip_pre > 0 ? s.skip_pre : s.skip_post;
-      const int skip_first = skip_id > 0 && !written[skip_id] ? 1 : 0;
-      if (skip_id > 0) written[skip_id] = 1;
-      hipLaunchKernelGGL(train::bwd_route2, grid, dim3(train::kThreads), 0, st, (const float2*)t->G[l + 1],
-                         (const float2*)t->z[l], mu, (const float*)t->rstd[l], (const float*)(t->params + f.gamma),
-                         (const float*)(t->params + f.beta), (const float2*)tensor(s.skip_pre), s.use_act, P, s.cout,
-                         (float2*)(s.skip_pre > 0 ? t->G[s.skip_pre] : nullptr),
-                         (float2*)(s.skip_post > 0 && !alias ? t->G[s.skip_post] : nullptr), (float2*)(lazy_mask ? nullptr : t->D),
-                         s.use_norm ? t->part : (double*)nullptr, (const int*)nullptr, skip_first);
-      if (s.use_norm) {
-        hipLaunchKernelGGL(bn_finish, dim3(1), dim3(1024), 0, st, (const double*)t->part, (int)grid.x, s.cout, t->sums,
-                           (int)kFinPlain, fb, (const int*)nullptr);
-        grads_out = true;
-      }
-    } else {
-      if (int rc = ensure_zero(s.skip_pre)) return rc;
-      if (int rc = ensure_zero(s.skip_post)) return rc;
-      hipLaunchKernelGGL(train::bwd_route, blocks(n), dim3(train::kThreads), 0, st, (const float*)t->G[l + 1],
-                         (const float*)t->z[l], mu, (const float*)t->rstd[l], (const float*)(t->params + f.gamma),
-                         (const float*)(t->params + f.beta), tensor(s.skip_pre), s.use_act, n, s.cout,
-                         s.skip_pre > 0 ? t->G[s.skip_pre] : nullptr, s.skip_post > 0 ? t->G[s.skip_post] : nullptr, t->D);
-      if (s.use_norm)
-        if (int rc = reduce_channels(t, t->D, t->z[l], mu, t->rstd[l], P, s.cout, st)) return rc;
     }
     const tmm::BnBwdArgs ba_l{t->z[l], mu, t->rstd[l], t->params + f.gamma, t->sums, (double)P,
-                              lazy_mask ? t->params + f.beta : nullptr};
-    const tmm::BnBwdArgs* ba = fuse_dz ? &ba_l : nullptr;
-    if (s.use_norm) {
-      if (!grads_out) {
-        hipLaunchKernelGGL(sums_to_float, dim3(1), dim3(64), 0, st, (const double*)t->sums, s.cout, 0, t->grads + f.beta);
-        hipLaunchKernelGGL(sums_to_float, dim3(1), dim3(64), 0, st, (const double*)t->sums, s.cout, 1, t->grads + f.gamma);
-      }
-      if (fuse_dz) {
-        // nothing: wgrad and dgrad below rebuild dz from D = d_u and z
-      } else if (pairs)
+                              pl.lazy_mask ? t->params + f.beta : nullptr};
+    const tmm::BnBwdArgs* ba = pl.fuse_dz ? &ba_l : nullptr;
+    if (s.use_norm && !pl.fuse_dz) {
+      if (s.cout % 2 == 0)
         hipLaunchKernelGGL(train::bn_bwd_apply2, pair_grid(s.cout), dim3(train::kThreads), 0, st, (float2*)t->D,
                            (const float2*)t->z[l], mu, (const float*)t->rstd[l], (const float*)(t->params + f.gamma),
                            (const double*)t->sums, (double)P, P, s.cout);
@@ -1052,82 +879,66 @@ int train_run(rced_trainer* t, const float* x_dev, const float* y_dev, float* pr
                            (const float*)t->rstd[l], (const float*)(t->params + f.gamma), (const double*)t->sums, (double)P, n,
                            s.cout);
     }
-    // wgrad and dgrad in one kernel where the layer's input tensor has this layer as its only consumer
-    bool fused_done = false;
-    if (t->fuse_bwd && t->use_mfma && s.kh == 1 && s.src > 0 && fuse_dz && t->pk_bwd[l] && overwrite(l)) {
-      const int pl = s.src - 1;
-      const bool xvirt = t->virt[s.src] != 0, want_sums = fuse_sums_on && sums_in_dgrad_ok(pl);
-      if (xvirt == want_sums) {
-        const int g = tm_bwd_fused(f.cin, s.kw, s.cout, xvirt, conv_in(s.src), dsrc, t->pk_bwd_x6[l] ? t->pk_bwd_x6[l] : t->pk_bwd[l], t->G[s.src], t->grads + f.kernel,
-                                   t->grads + f.bias, frames, t->num_cus, t->part, xform_of(s.src, &xa_tmp), ba, st);
-        if (g > 0) {
-          fused_done = true;
-          if (want_sums) { fused_sums[pl] = g; sums_from_x[pl] = 1; }
-        }
+    // dW and dbias = sum dz (the MFMA wgrad kernels produce both)
+    int launched = 1;
+    switch (pl.wgrad) {
+      case plan::Wgrad::Fused:   // with the dgrad, below
+        break;
+      case plan::Wgrad::Mfma:
+        launched = tm_wgrad(wd, f.cin, s.kw, s.cout, conv_in(s.src), dsrc, t->grads + f.kernel, t->grads + f.bias, frames, t->num_cus,
+                            xform_of(s.src, &xa_tmp), ba, st);
+        break;
+      case plan::Wgrad::First:
+        launched = first_wgrad(wd, s, x_dev, dsrc, t->grads + f.kernel, t->grads + f.bias, frames, T, t->num_cus, ba, st);
+        break;
+      case plan::Wgrad::Output:
+        launched = fin_wgrad(wd, f.cin, tensor(s.src), dsrc, t->grads + f.kernel, t->grads + f.bias, frames, t->num_cus, st);
+        break;
+      case plan::Wgrad::Generic: {
+        if (int rc = reduce_channels(t, t->D, t->D, nullptr, nullptr, P, s.cout, st)) return rc;
+        hipLaunchKernelGGL(sums_to_float, dim3(1), dim3(64), 0, st, (const double*)t->sums, s.cout, 0, t->grads + f.bias);
+        const int fpw = 16;
+        const size_t lds = ((size_t)s.kh * (F + s.kw - 1) * f.cin + (size_t)F * s.cout) * sizeof(float);
+        hipLaunchKernelGGL(train::conv_wgrad, dim3((frames + fpw - 1) / fpw), dim3(train::kThreads), lds, st, tensor(s.src),
+                           (const float*)t->D, T, F, f.cin, s.cout, s.kh, s.kw, frames, fpw, t->grads + f.kernel);
+        break;
       }
     }
-    // dW and dbias = sum dz (the MFMA wgrad kernel produces both)
-    if (fused_done) {
-      // both gradients are out
-    } else if (t->use_mfma && s.kh == 1 && tm_wgrad(f.cin, s.kw, s.cout, conv_in(s.src), dsrc, t->grads + f.kernel,
-                                             t->grads + f.bias, frames, t->num_cus, xform_of(s.src, &xa_tmp), ba, st)) {
-      // MFMA path
-    } else if (first_mfma && first_wgrad(s, x_dev, dsrc, t->grads + f.kernel, t->grads + f.bias, frames, T, t->num_cus, ba, st)) {
-      // MFMA path, first layer
-    } else if (t->use_mfma && t->pk_fin && is_output_layer(s, f.cin)) {
-      fin_wgrad(f.cin, tensor(s.src), dsrc, t->grads + f.kernel, t->grads + f.bias, frames, t->num_cus, st);
-    } else {
-      if ((s.src > 0 && t->virt[s.src]) || fuse_dz)   // the direct kernel needs the activation and dz in HBM
-        return rced_fail(RCED_ERR_STATE, "layer %d: no MFMA wgrad kernel for a layer with fused activation / dz", l);
-      if (int rc = reduce_channels(t, t->D, t->D, nullptr, nullptr, P, s.cout, st)) return rc;
-      hipLaunchKernelGGL(sums_to_float, dim3(1), dim3(64), 0, st, (const double*)t->sums, s.cout, 0, t->grads + f.bias);
-      const int fpw = 16;
-      const size_t lds = ((size_t)s.kh * (F + s.kw - 1) * f.cin + (size_t)F * s.cout) * sizeof(float);
-      if (f.K * s.cout > train::kWgradMaxOut * train::kThreads || lds > 64 * 1024)
-        return rced_fail(RCED_ERR_ARG, "layer %d too large for conv_wgrad", l);
-      hipLaunchKernelGGL(train::conv_wgrad, dim3((frames + fpw - 1) / fpw), dim3(train::kThreads), lds, st, tensor(s.src),
-                         (const float*)t->D, T, F, f.cin, s.cout, s.kh, s.kw, frames, fpw, t->grads + f.kernel);
+    if (launched == 0) return no_kernel(l, "wgrad");
+    // dx into G[src], as a forward conv of dz with the flipped / transposed kernel and the other SAME half
+    if (pl.zero_before_dgrad) HIP_TRY(zero_grad(s.src));
+    const int pv = s.src - 1;      // the layer that produced this dgrad's output tensor
+    const tmm::SumArgs sa_p = pl.src_sums ? tmm::SumArgs{t->z[pv], t->mu[pv], t->rstd[pv], t->params + t->off[pv].gamma, t->params + t->off[pv].beta}
+                                          : rced::tmd::kNoSums;
+    const float* acc_from = pl.acc_from > 0 ? t->G[pl.acc_from] : nullptr;
+    int grid = 1;                  // the launcher's grid (= the records of layer pv's sums when src_sums), 0: no such kernel
+    switch (pl.dgrad) {
+      case plan::Dgrad::None:
+        break;
+      case plan::Dgrad::Fused:
+        grid = tm_bwd_fused(wd, f.cin, s.kw, s.cout, pl.src_sums, conv_in(s.src), dsrc, t->pk_bwd_x6[l] ? t->pk_bwd_x6[l] : t->pk_bwd[l],
+                            t->G[s.src], t->grads + f.kernel, t->grads + f.bias, frames, t->num_cus, t->part, xform_of(s.src, &xa_tmp), ba, st);
+        break;
+      case plan::Dgrad::Output:
+        grid = fin_dgrad(f.cin, dsrc, t->params + f.kernel, t->pk_fin_bwd, t->G[s.src], frames, st, t->sw.x6);
+        break;
+      case plan::Dgrad::MfmaSums:
+      case plan::Dgrad::MfmaAccSums:
+        grid = tm_conv(false, s.cout, s.kw, f.cin, pl.accumulate, false, dsrc, t->pk_bwd[l], t->G[s.src], frames, t->num_cus, t->part,
+                       nullptr, ba, st, &sa_p, acc_from);
+        break;
+      case plan::Dgrad::Mfma:
+        grid = tm_conv(false, s.cout, s.kw, f.cin, pl.accumulate, false, dsrc, t->pk_bwd[l], t->G[s.src], frames, t->num_cus, nullptr,
+                       nullptr, ba, st, nullptr, acc_from);
+        break;
+      case plan::Dgrad::Generic:
+        if (int rc = launch_conv(t->D, t->G[s.src], t->wt[l], t->zero32, t->G[s.src], frames, T, F, s.cout, f.cin, f.cin4, s.kh, s.kw,
+                                 (s.kh - 1) - (s.kh - 1) / 2, (s.kw - 1) - (s.kw - 1) / 2, st))
+          return rc;
+        break;
     }
-    // dx into G[src] (+=), as a forward conv of dz with the flipped / transposed kernel and the other SAME half
-    if (s.src > 0 && !fused_done) {
-      if (t->use_mfma && t->pk_fin_bwd && is_output_layer(s, f.cin) && consumers[s.src] == 1) {
-        fin_dgrad(f.cin, dsrc, t->params + f.kernel, t->pk_fin_bwd, t->G[s.src], frames, st, t->use_x6);   // overwrites G[src]
-      } else if (const int pl = s.src - 1;   // the layer that produced this dgrad's output tensor
-                 fuse_sums_on && t->use_mfma && t->pk_bwd[l] && overwrite(l) && sums_in_dgrad_ok(pl) && [&] {
-                   const LayerOff& pf = t->off[pl];
-                   const tmm::SumArgs sa{t->z[pl], t->mu[pl], t->rstd[pl], t->params + pf.gamma, t->params + pf.beta};
-                   fused_sums[pl] = tm_conv(false, s.cout, s.kw, f.cin, false, false, dsrc, t->pk_bwd[l], t->G[s.src], frames,
-                                            t->num_cus, t->part, nullptr, ba, st, &sa);
-                   return fused_sums[pl] > 0;
-                 }()) {
-        // MFMA path; layer pl's BatchNorm-backward sums come out of the same kernel
-      } else if (const int pl = s.src - 1;   // an accumulating dgrad that adds the LAST contribution to G[src] -- the conv
-                 // consumer of a tensor comes before its skip consumers in the net, so after them here -- sees the complete
-                 // gradient in its epilogue: layer pl's sums come out of it as well (8-channel tensors: CR-CED's skip sources)
-                 fuse_sums_on && t->use_mfma && t->pk_bwd[l] && !overwrite(l) && ba && written[s.src] &&
-                 conv_consumer_of(s.src) == l && sums_in_dgrad_ok(pl) && [&] {
-                   const LayerOff& pf = t->off[pl];
-                   const tmm::SumArgs sa{t->z[pl], t->mu[pl], t->rstd[pl], t->params + pf.gamma, t->params + pf.beta};
-                   fused_sums[pl] = tm_conv(false, s.cout, s.kw, f.cin, true, false, dsrc, t->pk_bwd[l], t->G[s.src], frames,
-                                            t->num_cus, t->part, nullptr, ba, st, &sa, alias_src[s.src]);
-                   return fused_sums[pl] > 0;
-                 }()) {
-        // MFMA path; sums of layer pl included
-      } else if (t->use_mfma && t->pk_bwd[l] && (overwrite(l) || ensure_zero(s.src) == RCED_OK) &&
-          tm_conv(false, s.cout, s.kw, f.cin, !overwrite(l), false, dsrc, t->pk_bwd[l], t->G[s.src], frames, t->num_cus,
-                  nullptr, nullptr, ba, st, nullptr, overwrite(l) ? nullptr : alias_src[s.src])) {
-        // MFMA path
-      } else if (alias_src[s.src]) {
-        return rced_fail(RCED_ERR_STATE, "layer %d: no accumulating MFMA dgrad kernel for an aliased skip gradient", l);
-      } else if (fuse_dz) {
-        return rced_fail(RCED_ERR_STATE, "layer %d: no MFMA dgrad kernel for a layer with fused dz", l);
-      } else if (int rc0 = ensure_zero(s.src)) {
-        return rc0;
-      } else if (int rc = launch_conv(t->D, t->G[s.src], t->wt[l], t->zero32, t->G[s.src], frames, T, F, s.cout, f.cin,
-                                      f.cin4, s.kh, s.kw, (s.kh - 1) - (s.kh - 1) / 2, (s.kw - 1) - (s.kw - 1) / 2, st)) {
-        return rc;
-      }
-    }
+    if (grid <= 0) return no_kernel(l, "dgrad");
+    if (pl.src_sums) src_parts[pv] = grid;
   }
   if (t->wg_error) {   // (cannot happen with the up-front size above unless the runtime reports > 4 workgroups per CU)
     (void)hipStreamSynchronize(st);   // nothing of this step is left in flight behind the error

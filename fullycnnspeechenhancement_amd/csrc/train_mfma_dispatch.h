@@ -9,6 +9,7 @@
 #include <mutex>
 
 #include "kernels_train_mfma.h"
+#include "train_shapes.h"
 
 namespace rced {
 namespace tmd {
@@ -16,20 +17,18 @@ namespace tmd {
 constexpr int kPairGrid = 2048;     // workgroups of the channel-aligned elementwise kernels (and their partial sums)
 
 // Deterministic weight gradients (default): the wgrad kernels write per-wave slices into this buffer instead of adding to
-// dW with fp32 atomics, and tmm::wg_reduce sums the slices in a fixed order.  The training step points it at the
-// trainer's buffer for the duration of its backward pass (one caller thread per trainer); part == nullptr selects atomics.
+// dW with fp32 atomics, and tmm::wg_reduce sums the slices in a fixed order.  The training step hands every wgrad launcher
+// its trainer's buffer; part == nullptr selects atomics.
 struct WgDet {
   float** part = nullptr;         // the trainer's slice buffer, grown on demand; nullptr selects atomics (RCED_TRAIN_DET=0)
   size_t* cap_floats = nullptr;
   int* error = nullptr;           // raised when the buffer cannot be grown: the step then fails (RCED_ERR_ALLOC) -- a
                                   // deterministic trainer never falls back to atomics silently
 };
-inline thread_local WgDet g_wgdet;
 // Launch helper: `launch(dW_arg, dbias_arg, pstride)` launches the wgrad kernel; slices = partial-sum slices it writes
 // (grid x waves x parities: the grid comes from the runtime's occupancy answer, so the size is only known here).
 template <class F>
-inline int wg_launch(F&& launch, int slices, int nW, int nB, float* dW, float* dbias, hipStream_t st) {
-  const WgDet& d = g_wgdet;
+inline int wg_launch(const WgDet& d, F&& launch, int slices, int nW, int nB, float* dW, float* dbias, hipStream_t st) {
   const unsigned pstride = (unsigned)((nW + nB + 3) & ~3);
   if (!d.part) {
     launch(dW, dbias, 0u);          // atomics (not reproducible bit for bit): asked for with RCED_TRAIN_DET=0
@@ -120,24 +119,8 @@ int tm_conv_x6_launch1(const float* in, const float* packet, float* out, int fra
                      frames, part, xa);
   return grid;
 }
-// forward shapes built in this form: CR-CED's 18 -> 30 layers (no remainder pass; the 30 -> 8 layers' three planes + packet do not
-// leave room for two workgroups per CU: tmm::GeoX6::kFits).  Returns the grid, 0 if not built.
-#ifndef RCED_TM_X6_FWD_818
-#define RCED_TM_X6_FWD_818 0   // 1: the 8 -> 18 forward convolutions (main pass + remainder pass) in the three-part bf16 form too.  Measured (round 6,
-                               // A/B in one call, parity tests green): the step 40.30 -> 40.60 ms -- these layers (K = 72, 1.8 GB per call) wait for
-                               // their tiles, not for the fp32 matrix pipe; not adopted
-#endif
-#if RCED_TM_X6_FWD_818
-#define RCED_TM_X6_FWD(X) X(18, 5, 30) X(8, 9, 18)
-#else
-#define RCED_TM_X6_FWD(X) X(18, 5, 30)
-#endif
-inline bool tm_x6_has(int cin, int taps, int cout) {
-#define X(CI, TP, CO) if (cin == CI && taps == TP && cout == CO) return true;
-  RCED_TM_X6_FWD(X)
-#undef X
-  return false;
-}
+// the forward shapes built in this form: RCED_TM_X6_FWD (train_shapes.h).  Returns the grid, 0 if not built.
+using tms::tm_x6_has;
 inline int tm_conv_x6(int cin, int taps, int cout, bool stats, const float* in, const float* packet, float* out, int frames, int cus,
                       double* part, const tmm::XformArgs* xa, hipStream_t st) {
   const tmm::XformArgs nx{nullptr, nullptr, nullptr, nullptr};
@@ -232,7 +215,7 @@ int tm_conv_launch(bool accum, bool stats, const float* in, const float* packet,
 
 
 template <int CIN, int TAPS, int COUT, bool XF, bool DZF>
-int tm_wgrad_launch1(const float* x, const float* dz, float* dW, float* dbias, int frames, int cus, tmm::XformArgs xa,
+int tm_wgrad_launch1(const WgDet& wd, const float* x, const float* dz, float* dW, float* dbias, int frames, int cus, tmm::XformArgs xa,
                      tmm::BnBwdArgs ba, hipStream_t st) {
   using G = tmm::Geo<CIN, TAPS, COUT>;
   const int ntiles = (frames + tmm::kTF - 1) / tmm::kTF;
@@ -243,7 +226,7 @@ int tm_wgrad_launch1(const float* x, const float* dz, float* dW, float* dbias, i
   const void* kfn = reinterpret_cast<const void*>(tmm::wgrad1xk_mfma<CIN, TAPS, COUT, XF, DZF, PH>);
   allow_lds(kfn, lds, attr);
   const int grid = std::min(ntiles, resident_grid(kfn, lds, cus, occ));
-  wg_launch([&](float* dw, float* db, unsigned ps) {
+  wg_launch(wd, [&](float* dw, float* db, unsigned ps) {
     hipLaunchKernelGGL((tmm::wgrad1xk_mfma<CIN, TAPS, COUT, XF, DZF, PH>), dim3(grid), dim3(tmm::kThreads), lds, st, x, dz, dw, db,
                        frames, xa, ba, ps);
   }, grid * tmm::kWaves * PH, TAPS * CIN * COUT, COUT, dW, dbias, st);
@@ -251,19 +234,19 @@ int tm_wgrad_launch1(const float* x, const float* dz, float* dW, float* dbias, i
 }
 // xa: x is the producer's z (see tm_conv); ba: dz is d_u, rebuilt through BatchNorm backward from (d_u, z)
 template <int CIN, int TAPS, int COUT>
-int tm_wgrad_launch(const float* x, const float* dz, float* dW, float* dbias, int frames, int cus, const tmm::XformArgs* xa,
+int tm_wgrad_launch(const WgDet& wd, const float* x, const float* dz, float* dW, float* dbias, int frames, int cus, const tmm::XformArgs* xa,
                     const tmm::BnBwdArgs* ba, hipStream_t st) {
   const tmm::XformArgs nx{nullptr, nullptr, nullptr, nullptr};
   const tmm::BnBwdArgs nb{nullptr, nullptr, nullptr, nullptr, nullptr, 1.0, nullptr};
-  if (xa && ba) return tm_wgrad_launch1<CIN, TAPS, COUT, true, true>(x, dz, dW, dbias, frames, cus, *xa, *ba, st);
-  if (xa) return tm_wgrad_launch1<CIN, TAPS, COUT, true, false>(x, dz, dW, dbias, frames, cus, *xa, nb, st);
-  if (ba) return tm_wgrad_launch1<CIN, TAPS, COUT, false, true>(x, dz, dW, dbias, frames, cus, nx, *ba, st);
-  return tm_wgrad_launch1<CIN, TAPS, COUT, false, false>(x, dz, dW, dbias, frames, cus, nx, nb, st);
+  if (xa && ba) return tm_wgrad_launch1<CIN, TAPS, COUT, true, true>(wd, x, dz, dW, dbias, frames, cus, *xa, *ba, st);
+  if (xa) return tm_wgrad_launch1<CIN, TAPS, COUT, true, false>(wd, x, dz, dW, dbias, frames, cus, *xa, nb, st);
+  if (ba) return tm_wgrad_launch1<CIN, TAPS, COUT, false, true>(wd, x, dz, dW, dbias, frames, cus, nx, *ba, st);
+  return tm_wgrad_launch1<CIN, TAPS, COUT, false, false>(wd, x, dz, dW, dbias, frames, cus, nx, nb, st);
 }
 
 // wgrad + dgrad of one layer in one kernel (tmm::bwd_fused_mfma).  Returns the grid size (= partial-sum records when sums).
 template <int CIN, int TAPS, int COUT, bool XF, bool SUMS>
-int tm_bwd_fused_launch(const float* x, const float* du, const float* packet, float* dx, float* dW, float* dbias, int frames,
+int tm_bwd_fused_launch(const WgDet& wd, const float* x, const float* du, const float* packet, float* dx, float* dW, float* dbias, int frames,
                         int cus, double* part, tmm::XformArgs xa, tmm::BnBwdArgs ba, hipStream_t st) {
   using B = tmm::BwdGeo<CIN, TAPS, COUT>;
   const int ntiles = (frames + tmm::kTF - 1) / tmm::kTF;
@@ -274,14 +257,14 @@ int tm_bwd_fused_launch(const float* x, const float* du, const float* packet, fl
   allow_lds(kfn, lds, attr);
   const int grid = std::min(ntiles, std::min(resident_grid(kfn, lds, cus, occ, tmm::kBwdThreads), kPairGrid));
   constexpr int PH = COUT == 8 ? 2 : 1;
-  wg_launch([&](float* dw, float* db, unsigned ps) {
+  wg_launch(wd, [&](float* dw, float* db, unsigned ps) {
     hipLaunchKernelGGL((tmm::bwd_fused_mfma<CIN, TAPS, COUT, XF, SUMS>), dim3(grid), dim3(tmm::kBwdThreads), lds, st, x, du, packet,
                        dx, dw, db, frames, part, xa, ba, ps);
   }, grid * 4 * PH, TAPS * CIN * COUT, COUT, dW, dbias, st);
   return grid;
 }
 
-// One list-driven dispatcher set per translation unit: TM_FWD / TM_BWD are X-macro lists of (cin, taps, cout).
+// One list-driven dispatcher set per translation unit: TM_FWD / TM_BWD are X-macro lists of (cin, taps, cout) from train_shapes.h.
 #define RCED_TM_DEFINE_DISPATCH(SUFFIX, TM_FWD, TM_BWD)                                                                   \
   int tm_conv##SUFFIX(bool fwd, int cin, int taps, int cout, bool accum, bool stats, const float* in, const float* packet, \
                       float* out, int frames, int cus, double* part, const tmm::XformArgs* xa, const tmm::BnBwdArgs* ba,    \
@@ -290,13 +273,9 @@ int tm_bwd_fused_launch(const float* x, const float* du, const float* packet, fl
     TM_BWD(RCED_TM_CONV_BWD_CASE)                                                                                           \
     return 0;                                                                                                               \
   }                                                                                                                         \
-  bool tm_has##SUFFIX(bool fwd, int cin, int taps, int cout) {                                                              \
-    if (fwd) { TM_FWD(RCED_TM_HAS_CASE) } else { TM_BWD(RCED_TM_HAS_CASE) }                                                 \
-    return false;                                                                                                           \
-  }                                                                                                                         \
-  int tm_wgrad##SUFFIX(int cin, int taps, int cout, const float* x, const float* dz, float* dW, float* dbias, int frames,   \
+  int tm_wgrad##SUFFIX(const rced::tmd::WgDet& wd, int cin, int taps, int cout, const float* x, const float* dz, float* dW, float* dbias, int frames,   \
                        int cus, const tmm::XformArgs* xa, const tmm::BnBwdArgs* ba, hipStream_t st) {                       \
-    TM_FWD(RCED_TM_WGRAD_CASE) /* the list tm_has(true, ...) answers from: fuse_dz / virt rely on the two agreeing */       \
+    TM_FWD(RCED_TM_WGRAD_CASE) /* the forward list: tms::tm_has(true, ...) answers from the same one */                     \
     return 0;                                                                                                               \
   }
 #define RCED_TM_CONV_FWD_CASE(CI, TP, CO)                \
@@ -305,11 +284,9 @@ int tm_bwd_fused_launch(const float* x, const float* du, const float* packet, fl
 #define RCED_TM_CONV_BWD_CASE(CI, TP, CO)                \
   if (!fwd && cin == CI && taps == TP && cout == CO)     \
     return rced::tmd::tm_conv_launch<CI, TP, CO, false>(accum, stats, in, packet, out, frames, cus, part, xa, ba, st, sa, acc_from);
-#define RCED_TM_HAS_CASE(CI, TP, CO) \
-  if (cin == CI && taps == TP && cout == CO) return true;
 #define RCED_TM_WGRAD_CASE(CI, TP, CO)              \
   if (cin == CI && taps == TP && cout == CO)        \
-    return rced::tmd::tm_wgrad_launch<CI, TP, CO>(x, dz, dW, dbias, frames, cus, xa, ba, st);
+    return rced::tmd::tm_wgrad_launch<CI, TP, CO>(wd, x, dz, dW, dbias, frames, cus, xa, ba, st);
 
 }  // namespace tmd
 }  // namespace rced

@@ -218,7 +218,11 @@ int rced_stoi(const float* ref_dev, int ref_stride, const float* est_dev, int es
 typedef struct rced_trainer rced_trainer;
 
 /* blob: the same TF-variable blob rced_create takes (initial values, incl. BN moving statistics);
- * batch_size: the CONFIGURED batch size the loss divides by (trainer.py:146-147), not the dynamic N. */
+ * batch_size: the CONFIGURED batch size the loss divides by (trainer.py:146-147), not the dynamic N.
+ * Which kernel every layer gets under the RCED_TRAIN_* switches is planned here, once; a combination of net, switches and
+ * built kernels that cannot be planned is refused with RCED_ERR_STATE (RCED_ERR_ARG: a layer too large for the direct
+ * kernels) instead of failing inside a step.  The three nets plan under every switch combination.  A device allocation
+ * that fails here returns RCED_ERR_ALLOC, as everywhere else in the library. */
 int rced_train_create(int variant, const float* blob, size_t n_floats, int batch_size, int device,
                       rced_trainer** out);
 void rced_train_destroy(rced_trainer* t);

@@ -204,7 +204,7 @@ def test_sums_from_the_dgrad_agree_with_the_separate_pass(switch, built, monkeyp
     """RCED_TRAIN_FUSE_BWD: wgrad + dgrad of the 18->30 and 30->8 layers in one kernel (tmm::bwd_fused_mfma, sums from the
     transformed x tile) against the separate wgrad / dgrad kernels (sums from the dgrad's z tile).  RCED_TRAIN_FUSE_SUMS:
     CR-CED's plain layers (18 and 30 channels) get their BatchNorm-backward sums S1, S2 from the epilogue of the dgrad
-    that writes their gradient (tmm::SumArgs: z tile by LDS-DMA, masked sums, sums_fix); RCED_TRAIN_FUSE_SUMS=0 is the
+    that writes their gradient (tmm::SumArgs: z tile by LDS-DMA, masked sums, bn_finish mode kFinZ); RCED_TRAIN_FUSE_SUMS=0 is the
     bwd_route2 pass over g and z they replace.  Same ragged multi-tile batch as above: the partial last tile takes the
     ordinary-load path of ztile_fetch.  The two differ only in summation order (fp32 per-tile partials vs fp64 per element)."""
     from fullycnnspeechenhancement_amd import FullyCNNTrainer
@@ -293,6 +293,40 @@ def test_fused_staging_switches_agree_with_the_materialised_tensors(switch, buil
         assert cosine(out["1"][1][name], g0) > 1 - 1e-8, name
     print("\n[%s = 0 vs 1] loss %.3e apart, forward %.2e, worst gradient %.2e of its tensor's max"
           % (switch, abs(out["0"][0] - out["1"][0]) / abs(out["0"][0]), fwd, worst))
+
+
+@pytest.mark.parametrize("switch", ["RCED_TRAIN_FUSE_ACT", "RCED_TRAIN_FUSE_DZ", "RCED_TRAIN_FUSE_BWD", "RCED_TRAIN_FUSE_SUMS"])
+@pytest.mark.parametrize("net_work", ["FullyCNN", "FullyCNNV2"])
+def test_fusion_switches_agree_on_the_r_ced_nets(net_work, switch, built, monkeypatch):
+    """The four fusion switches, each set to 0 on its own against the default, on R-CED V1 (skips added before the ReLU)
+    and V2 (phantom channels of the even-padded layout); the tests above exercise them on CR-CED only.  Ragged
+    5 x 7 = 35 frames: the smallest batch that ends on a half-empty tile.  One trainer and one step per side.  Bounds as in
+    test_fused_staging_switches_agree_with_the_materialised_tensors: the loss to 1e-6, every gradient to 1e-4 of its
+    tensor's largest entry (the two sides differ by summation order only); biases in front of BatchNorm are skipped.
+    Measured on the library from before the launch plan existed, V1 / V2: the loss identical in all eight cases; worst
+    gradient difference, of its tensor's largest entry: FUSE_ACT 0 / 0, FUSE_DZ 8.4e-7 / 1.1e-6, FUSE_BWD 0 / 0 (no fused
+    backward kernel is built for an R-CED shape), FUSE_SUMS 3.9e-7 / 7.6e-7, each on encode_1/kernel.  Inside the bounds, so
+    they are kept; every case prints its own figures before it asserts."""
+    from fullycnnspeechenhancement_amd import FullyCNNTrainer
+    w = rced_np.make_weights(net_work, seed=17)
+    x = rced_np.make_input(5, 7, seed=31)
+    y = rced_np.make_input(5, 7, seed=32)
+    out = {}
+    for mode in ("0", "1"):
+        monkeypatch.setenv(switch, mode)
+        tr = FullyCNNTrainer(net_work, batch_size=5, lr=1e-3, weights=w)
+        loss, _, _ = tr.train_step(x, y)
+        out[mode] = (loss, tr.gradients())
+        tr.close()
+    dloss = abs(out["0"][0] - out["1"][0]) / abs(out["1"][0])
+    last, worst = net_layers_last(net_work), (0.0, "")
+    for name, g1 in out["1"][1].items():
+        if "moving_" in name or (name.endswith("/bias") and not name.startswith(last)):
+            continue
+        worst = max(worst, (rel(out["0"][1][name], g1), name))
+    print("\n[%s %s = 0 vs default] loss %.3e apart, worst gradient %.3e of its tensor's max (%s)" % ((net_work, switch, dloss) + worst))
+    assert dloss <= 1e-6
+    assert worst[0] < 1e-4, worst
 
 
 def test_padded_layout_round_trips_variables_and_adam_state(built):
