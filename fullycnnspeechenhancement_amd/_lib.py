@@ -44,6 +44,12 @@ SYMBOLS = {
     "rced_stoi": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp]),
     "rced_mix_snr": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int,
                                     ctypes.c_double, _vp, ctypes.c_int, _vp]),
+    "rced_stream_delay": (ctypes.c_int, []),
+    "rced_stream_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
+    "rced_stream_destroy": (None, [_vp]),
+    "rced_stream_push": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _vp]),
+    "rced_stream_finish": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "rced_stream_reset": (ctypes.c_int, [_vp, ctypes.c_int]),
     "rced_train_create": (ctypes.c_int, [ctypes.c_int, _c_float_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
                                          ctypes.POINTER(_vp)]),
     "rced_train_destroy": (None, [_vp]),

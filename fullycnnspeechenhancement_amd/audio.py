@@ -246,6 +246,104 @@ def denoise_and_score(forward, mix, clean, lengths, nfft=512, kernels="x6", stoi
     return out, sdr_batch(clean, out, lengths)
 
 
+STREAM_DELAY, STREAM_FINISH_MAX, STREAM_MAX_HOPS = 640, 768, 64     # rced.h: RCED_STREAM_DELAY, RCED_STREAM_FINISH_MAX, the max_hops bound
+
+
+class StreamingDenoiser(object):
+    """PCM in, PCM out, a hop (128 samples, 16 ms) at a time, for `lanes` independent streams at once (rced_stream_*,
+    DESIGN.md 3.4d).  A lane's output is InferenceEngine.denoise_pcm of everything pushed before `finish`, delayed by
+    STREAM_DELAY = 640 samples: zeros first, and `finish` hands out what is still owed.  All state lives on the device; a
+    push is three launches on the current stream.
+
+    model_or_engine: a model of this package (is_training=False) or an engine holding one as `.model`; the stream runs the
+    forward form that model has selected.  max_hops: the most hops one push may carry (1..64); nfft: 512 (the reference's
+    rebuild as shipped) or 256."""
+
+    def __init__(self, model_or_engine, lanes, max_hops=8, nfft=512):
+        import ctypes
+        self._h = None
+        self.model = getattr(model_or_engine, "model", model_or_engine)
+        if getattr(self.model, "_handle", None) is None:
+            raise ValueError("StreamingDenoiser needs an inference model (Model(is_training=False)) or an engine that holds one")
+        self.lanes, self.max_hops, self.nfft, self.device = int(lanes), int(max_hops), int(nfft), self.model.device
+        h = ctypes.c_void_p()
+        _lib.check(_lib.load().rced_stream_create(self.model._handle, self.lanes, self.max_hops, self.nfft, ctypes.byref(h)))
+        self._h = h
+
+    def _tensor(self, x, dtype, shape, what):
+        import torch
+        dev = "cuda:%d" % self.device
+        if hasattr(x, "is_cuda"):
+            if not x.is_cuda or x.device.index != self.device:
+                raise ValueError("%s must live on cuda:%d (or be a numpy array)" % (what, self.device))
+            t = x.to(dtype).contiguous()
+        else:
+            t = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32 if dtype == torch.float32 else np.int32), device=dev)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError("%s must have shape %s, got %s" % (what, tuple(shape), tuple(t.shape)))
+        return t
+
+    def push(self, pcm, active=None):
+        """pcm [lanes, K*128] (1 <= K <= max_hops): the next K hops of every lane -> [lanes, K*128], the lanes' output streams.
+        active: None, or `lanes` flags; a lane flagged 0 is idle (state untouched, zeros out).  A CUDA tensor gives a CUDA
+        tensor (no synchronisation), an ndarray an ndarray."""
+        import torch
+        as_torch = hasattr(pcm, "is_cuda")
+        cols = int(pcm.shape[1]) if len(pcm.shape) == 2 else -1
+        if len(pcm.shape) != 2 or int(pcm.shape[0]) != self.lanes or cols < STEP or cols % STEP:
+            raise ValueError("pcm must be [lanes = %d, K * 128] with K >= 1, got %s" % (self.lanes, tuple(pcm.shape)))
+        x = self._tensor(pcm, torch.float32, (self.lanes, cols), "pcm")
+        act = self._tensor(active, torch.int32, (self.lanes,), "active") if active is not None else None
+        out = torch.empty_like(x)
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        _lib.check(_lib.load().rced_stream_push(self._h, x.data_ptr(), act.data_ptr() if act is not None else None, cols // STEP,
+                                                out.data_ptr(), st))
+        for t in (x, act):          # the last launch reads the inputs again: keep a temporary's memory until the stream has passed
+            if t is not None:
+                t.record_stream(torch.cuda.current_stream(x.device))
+        return out if as_torch else out.cpu().numpy()
+
+    def finish(self, lanes, tails):
+        """Ends the utterance of every lane listed: tails[i] holds the last 0..127 samples of lane lanes[i].  Returns a list of
+        float32 arrays, the samples each lane still owed (L - max(0, 128 H - 640) of them); the lanes are reset for a new
+        utterance, the others left alone.  Synchronises (the counts come back)."""
+        import torch
+        lanes = [int(v) for v in lanes]
+        if len(lanes) != len(tails) or len(set(lanes)) != len(lanes) or any(v < 0 or v >= self.lanes for v in lanes):
+            raise ValueError("lanes must be distinct indices in [0, %d), one tail each" % self.lanes)
+        tail = np.zeros((self.lanes, STEP), np.float32)
+        counts = np.full((self.lanes,), -1, np.int32)
+        for lane, t in zip(lanes, tails):
+            t = (t.detach().cpu().numpy() if hasattr(t, "is_cuda") else np.asarray(t, np.float32)).reshape(-1)
+            if t.size >= STEP:
+                raise ValueError("a tail holds fewer than %d samples (push whole hops first), got %d" % (STEP, t.size))
+            tail[lane, :t.size] = t
+            counts[lane] = t.size
+        dev = "cuda:%d" % self.device
+        tdev, cdev = torch.as_tensor(tail, device=dev), torch.as_tensor(counts, device=dev)
+        out = torch.empty((self.lanes, STREAM_FINISH_MAX), dtype=torch.float32, device=dev)
+        owed = torch.empty((self.lanes,), dtype=torch.int32, device=dev)
+        st = torch.cuda.current_stream(out.device).cuda_stream
+        _lib.check(_lib.load().rced_stream_finish(self._h, tdev.data_ptr(), cdev.data_ptr(), out.data_ptr(), owed.data_ptr(), st))
+        out, owed = out.cpu().numpy(), owed.cpu().numpy()
+        return [out[lane, :owed[lane]].copy() for lane in lanes]
+
+    def reset(self, lane=-1):
+        """Back to the start of an utterance, without output: one lane, or (-1) all of them."""
+        _lib.check(_lib.load().rced_stream_reset(self._h, int(lane)))
+
+    def close(self):
+        if self._h is not None:
+            try:
+                _lib.load().rced_stream_destroy(self._h)
+            except Exception:
+                pass
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
 class AudioFeature(object):
     """data_utils/audio_feature.py:12-115 on the GPU (numpy in, numpy out, like the reference)."""
 

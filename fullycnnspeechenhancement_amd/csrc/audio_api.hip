@@ -162,6 +162,19 @@ int tables(int device, AudioTables** out) {
 
 }  // namespace
 
+int rced_audio_x6_tables_get(int device, int nfft, rced_audio_x6_tables* out) {
+  DeviceGuard g(device);
+  AudioTables* t = nullptr;
+  if (int rc = tables(device, &t)) return rc;
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  const int v = nfft == 512;
+  out->stft = t->stft_x6;
+  out->istft = t->istft_x6[v];
+  out->cim = t->cim[v];
+  out->chead = t->chead[v];
+  return RCED_OK;
+}
+
 extern "C" {
 
 int rced_stft_num_frames(int length) { return length > 0 ? audio::num_frames(length) : 0; }

@@ -299,7 +299,10 @@ int rced_create(int variant, const float* blob, size_t n_floats, int device, rce
   return RCED_OK;
 }
 
-void rced_destroy(rced_model* m) { delete m; }
+void rced_destroy(rced_model* m) {
+  if (m) rced_streams_detach(m);
+  delete m;
+}
 
 int rced_set_option(rced_model* m, const char* key, int value) {
   if (!m || !key) return rced_fail(RCED_ERR_ARG, "null argument");

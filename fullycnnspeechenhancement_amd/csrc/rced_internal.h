@@ -64,3 +64,15 @@ int fused_check(rced_model* m);   // RCED_ERR_STATE if an earlier launch recorde
 #define RCED_OPT_UNKNOWN (-1)   // fused_set_option: "not a key of mine" (internal; never crosses the C ABI)
 int fused_set_option(rced_model* m, const char* key, int value);
 int fused_get_option(rced_model* m, const char* key, int* value);
+
+// the device's three-part bf16 STFT / ISTFT tables (audio_api.hip builds them once per device), for the streaming kernels
+struct rced_audio_x6_tables {
+  const unsigned short* stft = nullptr;    // audio::x6::kStftPackX
+  const unsigned short* istft = nullptr;   // audio::x6::kIstftPackX, of the nfft asked for
+  const float* cim = nullptr;              // [128]
+  const float* chead = nullptr;            // [258][128]
+};
+int rced_audio_x6_tables_get(int device, int nfft, rced_audio_x6_tables* out);
+
+// stream_api.hip: streams created on `m` answer RCED_ERR_STATE from now on (rced_destroy calls this before the model goes)
+void rced_streams_detach(rced_model* m);

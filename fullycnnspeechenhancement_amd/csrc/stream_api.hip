@@ -1,0 +1,168 @@
+// C ABI of the streaming denoiser (include/rced.h, "streaming" section): host side.  Three launches per push on the caller's stream --
+// the stateful STFT, rced_forward on the lanes' windows, the stateful ISTFT (kernels_stream.h) --, no allocation, no synchronisation.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <mutex>
+#include <new>
+#include <vector>
+
+#include "../../include/rced.h"
+#include "rced_internal.h"
+
+// kernels_audio.h / kernels_audio_x6.h define their kernels with external linkage and audio_api.hip is their translation unit: this
+// one takes the headers into an unnamed namespace, so that its copies (it launches only its own two kernels) are local to it.
+namespace {
+#include "kernels_stream.h"
+namespace audio = rced::audio;
+namespace as = rced::audio::stream;
+}  // namespace
+
+struct rced_stream {
+  rced_model* model = nullptr;   // null once the model was destroyed under the stream
+  int device = 0, lanes = 0, max_hops = 0, nfft = 0;
+  float* state = nullptr;        // [S, kStFloats]
+  float* win = nullptr;          // [S, 7 + K, 129] magnitudes: the CNN's input
+  float* phw = nullptr;          // [S, 7 + K, 129, 2]
+  float* masks = nullptr;        // [S, 7 + K, 129]: the CNN's output
+  hipStream_t last = nullptr;    // the stream of the latest push / finish: rced_stream_reset is ordered on it
+  rced_audio_x6_tables tab;
+};
+
+namespace {
+
+std::mutex g_mu;
+std::vector<rced_stream*> g_streams;   // the live ones: rced_destroy of a model detaches its streams
+
+int window_hops(const rced_stream* s) { return std::max(s->max_hops, as::kFinishSlots); }
+
+void release(rced_stream* s) {
+  for (void* p : {(void*)s->state, (void*)s->win, (void*)s->phw, (void*)s->masks}) (void)hipFree(p);
+  delete s;
+}
+
+// the three launches; K slots per lane (push: K hops, finish: kFinishSlots)
+int run(rced_stream* s, const float* in, const int* flags, int finish, int K, float* out, int* out_counts, hipStream_t st) {
+  const int S = s->lanes;
+  hipLaunchKernelGGL(as::stream_stft_kernel, dim3((S * K + audio::kFramesPerWg - 1) / audio::kFramesPerWg, 2), dim3(audio::x6::kThreadsX),
+                     as::kStreamStftLds, st, in, flags, finish, s->tab.stft, (const float*)s->state, S, K, s->win, s->phw);
+  HIP_TRY(hipGetLastError());
+  if (int rc = rced_forward(s->model, s->win, s->masks, S, as::kKeep + K, st)) return rc;
+  const int lpw = audio::kFramesPerWg / K;
+  hipLaunchKernelGGL(as::stream_istft_kernel, dim3((S + lpw - 1) / lpw), dim3(audio::x6::kThreadsX), as::kStreamIstftLds, st,
+                     (const float*)s->masks, (const float*)s->win, (const float*)s->phw, in, flags, finish, s->tab.istft, s->tab.cim,
+                     s->tab.chead, s->state, S, K, out, out_counts);
+  HIP_TRY(hipGetLastError());
+  s->last = st;
+  return RCED_OK;
+}
+
+int usable(rced_stream* s) {
+  if (!s) return rced_fail(RCED_ERR_ARG, "stream is NULL");
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!s->model) return rced_fail(RCED_ERR_STATE, "the stream's model has been destroyed");
+  return RCED_OK;
+}
+
+}  // namespace
+
+void rced_streams_detach(rced_model* m) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  for (rced_stream* s : g_streams)
+    if (s->model == m) s->model = nullptr;
+}
+
+extern "C" {
+
+int rced_stream_delay(void) { return RCED_STREAM_DELAY; }
+
+int rced_stream_create(rced_model* m, int lanes, int max_hops, int nfft, rced_stream** out) {
+  static_assert(RCED_STREAM_DELAY == as::kDelayHops * audio::kStep && RCED_STREAM_FINISH_MAX == as::kFinishOut, "rced.h and kernels_stream.h");
+  if (!out) return rced_fail(RCED_ERR_ARG, "out is NULL");
+  *out = nullptr;
+  if (lanes < 1 || lanes > 65536) return rced_fail(RCED_ERR_ARG, "lanes must be 1..65536, got %d", lanes);
+  if (max_hops < 1 || max_hops > as::kMaxHops) return rced_fail(RCED_ERR_ARG, "max_hops must be 1..%d, got %d", as::kMaxHops, max_hops);
+  if (nfft != 512 && nfft != 256) return rced_fail(RCED_ERR_ARG, "nfft must be 512 (reference default) or 256");
+  if (!m) return rced_fail(RCED_ERR_ARG, "model is NULL");
+  DeviceGuard g(m->device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", m->device);
+  rced_stream* s = new (std::nothrow) rced_stream();
+  if (!s) return rced_fail(RCED_ERR_ALLOC, "host allocation failed");
+  s->model = m;
+  s->device = m->device;
+  s->lanes = lanes;
+  s->max_hops = max_hops;
+  s->nfft = nfft;
+  int rc = rced_audio_x6_tables_get(m->device, nfft, &s->tab);
+  const size_t rows = (size_t)lanes * (as::kKeep + window_hops(s)) * audio::kBins;
+  auto alloc = [&](float** p, size_t floats) {
+    if (rc) return;
+    const hipError_t e = hipMalloc(p, floats * sizeof(float));
+    if (e != hipSuccess) rc = rced_fail(e == hipErrorOutOfMemory ? RCED_ERR_ALLOC : RCED_ERR_HIP, "hipMalloc(stream): %s", hipGetErrorString(e));
+  };
+  alloc(&s->state, (size_t)lanes * as::kStFloats);
+  alloc(&s->win, rows);
+  alloc(&s->phw, 2 * rows);
+  alloc(&s->masks, rows);
+  if (!rc && hipMemset(s->state, 0, (size_t)lanes * as::kStFloats * sizeof(float)) != hipSuccess) rc = rced_fail(RCED_ERR_HIP, "hipMemset(stream state)");
+  if (!rc) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(as::stream_stft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, as::kStreamStftLds);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(as::stream_istft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, as::kStreamIstftLds);
+    if (e != hipSuccess) rc = rced_fail(RCED_ERR_HIP, "hipFuncSetAttribute(stream LDS): %s", hipGetErrorString(e));
+  }
+  if (!rc) rc = rced_reserve(m, lanes, as::kKeep + window_hops(s));   // the forward of a push allocates nothing
+  if (rc) {
+    release(s);
+    return rc;
+  }
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_streams.push_back(s);
+  }
+  *out = s;
+  return RCED_OK;
+}
+
+void rced_stream_destroy(rced_stream* s) {
+  if (!s) return;
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_streams.erase(std::remove(g_streams.begin(), g_streams.end(), s), g_streams.end());
+  }
+  DeviceGuard g(s->device);
+  (void)hipDeviceSynchronize();   // launches that still read the buffers
+  release(s);
+}
+
+int rced_stream_push(rced_stream* s, const float* pcm_dev, const int* active_dev, int K, float* out_dev, void* stream) {
+  if (!s) return rced_fail(RCED_ERR_ARG, "stream is NULL");
+  if (K < 1 || K > s->max_hops) return rced_fail(RCED_ERR_ARG, "K must be 1..max_hops = %d, got %d", s->max_hops, K);
+  if (!pcm_dev || !out_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
+  if (int rc = usable(s)) return rc;
+  DeviceGuard g(s->device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", s->device);
+  return run(s, pcm_dev, active_dev, 0, K, out_dev, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int rced_stream_finish(rced_stream* s, const float* tail_dev, const int* tail_counts_dev, float* out_dev, int* out_counts_dev, void* stream) {
+  if (!s) return rced_fail(RCED_ERR_ARG, "stream is NULL");
+  if (!tail_dev || !tail_counts_dev || !out_dev || !out_counts_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
+  if (int rc = usable(s)) return rc;
+  DeviceGuard g(s->device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", s->device);
+  return run(s, tail_dev, tail_counts_dev, 1, as::kFinishSlots, out_dev, out_counts_dev, static_cast<hipStream_t>(stream));
+}
+
+int rced_stream_reset(rced_stream* s, int lane) {
+  if (!s) return rced_fail(RCED_ERR_ARG, "stream is NULL");
+  if (lane < -1 || lane >= s->lanes) return rced_fail(RCED_ERR_ARG, "lane must be -1 (all) or 0..%d, got %d", s->lanes - 1, lane);
+  DeviceGuard g(s->device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", s->device);
+  const size_t one = as::kStFloats * sizeof(float);
+  if (lane < 0) HIP_TRY(hipMemsetAsync(s->state, 0, one * s->lanes, s->last));
+  else HIP_TRY(hipMemsetAsync(s->state + (size_t)lane * as::kStFloats, 0, one, s->last));
+  return RCED_OK;
+}
+
+}  // extern "C"

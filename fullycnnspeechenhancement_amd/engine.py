@@ -161,6 +161,26 @@ class InferenceEngine(FullyCNNTester):
         out = audio.istft_batch(pred, phase, nfft)
         return out[0, :len(sig)].cpu().numpy()
 
+    def denoise_stream(self, chunks, hops=8, nfft=512):
+        """denoise_pcm for audio that arrives in pieces: a generator over an iterable of 1-D PCM pieces of any size.  The
+        pieces are re-blocked to whole hops (128 samples) and pushed, at most `hops` hops at a time, through a one-lane
+        audio.StreamingDenoiser; every push's output is yielded as it comes (numpy float32, the result delayed by 640
+        samples, zeros first), then what the stream still owed.  All pieces joined, with the leading zeros dropped, equal
+        denoise_pcm of the joined input."""
+        from . import audio
+        stream = audio.StreamingDenoiser(self.model, 1, max_hops=int(hops), nfft=nfft)
+        try:
+            held = np.zeros(0, np.float32)
+            for piece in chunks:
+                held = np.concatenate([held, np.asarray(piece, np.float32).reshape(-1)])
+                while held.size >= audio.STEP:
+                    k = min(held.size // audio.STEP, stream.max_hops)
+                    yield stream.push(held[None, :k * audio.STEP])[0]
+                    held = held[k * audio.STEP:]
+            yield stream.finish([0], [held])[0]
+        finally:
+            stream.close()
+
     def denoise_magnitude(self, mag):
         mag = np.asarray(mag, dtype=np.float32)
         if mag.ndim == 2:  # [T, 129] -> [1, T, 129, 1]  (a transpose-correct version of infer.py:59)

@@ -213,6 +213,42 @@ int rced_mix_snr(const float* speech_dev, const int* speech_len_dev, int N, int 
 int rced_stoi(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride,
               const int* lengths_dev, int N, int fs_sig, double* stoi_dev, int* detail_dev, int device, void* stream);
 
+/* ---- streaming denoiser: PCM in, PCM out, 128 samples (one hop, 16 ms) at a time, for many independent streams ("lanes") at once,
+ * at a fixed delay.  Only the first layer of the three networks looks across time (3 past, 4 future frames) and the rebuild uses no
+ * overlap-add, so the chunked run reproduces the whole-utterance chain rced_stft -> rced_forward -> rced_istft.
+ * For one lane let s[0..L) be everything pushed before rced_stream_finish (the tail included), H the hops pushed and `off` the
+ * whole-utterance result of length L.  The lane's output stream is `off` delayed by RCED_STREAM_DELAY samples: a push of K hops
+ * returns K*128 samples per lane, zeros until 640 samples have left, then off[i - 640].  Frames are the reference's own set
+ * (rced_stft_num_frames(L), zero padding applied after pre-emphasis): pushing zeros is not finishing.  All state lives on the device;
+ * after rced_stream_create a push is three launches on the caller's stream, allocates nothing and does not synchronise.  The input
+ * buffers must stay valid until that work has run (the last launch reads them again).  A stream object is not thread-safe. ---- */
+#define RCED_STREAM_DELAY 640       /* samples: 5 hops */
+#define RCED_STREAM_FINISH_MAX 768  /* floats per lane of rced_stream_finish's out_dev (at most 767 are owed) */
+typedef struct rced_stream rced_stream;
+int rced_stream_delay(void);
+
+/* lanes >= 1 streams, pushes of at most max_hops (1..64) hops, nfft 512 (the reference as shipped) or 256 for the rebuild; anything
+ * else is RCED_ERR_ARG.  Runs the forward form the model handle has selected at each push, on the model's device.  The model must
+ * outlive the stream: after rced_destroy(m) the stream's entry points return RCED_ERR_STATE (rced_stream_destroy stays valid). */
+int rced_stream_create(rced_model* m, int lanes, int max_hops, int nfft, rced_stream** out);
+void rced_stream_destroy(rced_stream* s);
+
+/* pcm_dev [lanes, K*128] float32: the next K hops of every lane; out_dev [lanes, K*128].  active_dev: NULL (every lane) or [lanes]
+ * int32 flags; a lane flagged 0 is idle: its state does not change, its input row is not read and zeros are written to its output
+ * row.  K < 1 or K > max_hops: RCED_ERR_ARG.  Asynchronous. */
+int rced_stream_push(rced_stream* s, const float* pcm_dev, const int* active_dev, int K, float* out_dev, void* stream);
+
+/* Ends the utterance of every lane whose tail_counts_dev entry is 0..127: tail_dev [lanes, 128] holds that many last samples (fewer
+ * than a hop).  out_dev [lanes, RCED_STREAM_FINISH_MAX] receives from column 0 the L - max(0, 128*H - 640) samples still owed --
+ * off[max(0, 128*H - 640) .. L); for H < 5 that is the whole of `off`, the zeros pushes have returned so far being all there are --,
+ * zeros behind them; out_counts_dev [lanes] int32 that count.  The lane is then reset for a new utterance.  Entry -1: the lane is
+ * left alone (count 0).  Asynchronous. */
+int rced_stream_finish(rced_stream* s, const float* tail_dev, const int* tail_counts_dev, float* out_dev, int* out_counts_dev,
+                       void* stream);
+
+/* Back to the start of an utterance without output: lane, or -1 for every lane.  Ordered on the stream of the latest push / finish. */
+int rced_stream_reset(rced_stream* s, int lane);
+
 /* ---- training step: FullyCNNTrainer.creat_graph + train_step,
  * model_utils/trainer.py:156-192, over Model(is_training=True).  Layer-by-layer, correctness first. ---- */
 typedef struct rced_trainer rced_trainer;

@@ -1,0 +1,51 @@
+#!/usr/bin/env python3
+"""Times the streaming denoiser (audio.StreamingDenoiser, CR-CED) for 256 lanes at K = 1, 8 and 32 hops per push, device-resident,
+with torch.cuda events: ms per push and frames/s, beside the offline PCM-to-PCM chain (stft_batch -> model -> istft_batch) at the
+same total frame count (256 utterances of K frames) and at BASELINE config-3 scale (256 x 512 frames).  One JSON line per row.
+A push recomputes 7 frames per lane for the CNN: `recompute` is (K + 7) / K."""
+import json, os, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch
+from fullycnnspeechenhancement_amd import audio, build_model
+from fullycnnspeechenhancement_amd import weights as _weights
+
+LANES = 256
+model = build_model("FullyCNNV3", False, weights=_weights.synthetic_weights(3, seed=42))
+
+
+def timed(fn, reps):
+    for _ in range(10):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def offline(n, t):
+    pcm = torch.randn((n, (t - 1) * 128 + 256), device="cuda") * 0.1
+
+    def chain():
+        mag, ph = audio.stft_batch(pcm)
+        return audio.istft_batch(model(mag), ph)
+    return chain
+
+
+for k in (1, 8, 32):
+    stream = audio.StreamingDenoiser(model, LANES, max_hops=k)
+    pcm = torch.randn((LANES, k * 128), device="cuda") * 0.1
+    reps = 2000 // k + 50                      # a second or so of pushes: every lane is far into its utterance
+    ms = timed(lambda: stream.push(pcm), reps)
+    off_ms = timed(offline(LANES, k), reps)
+    stream.close()
+    frames = LANES * k
+    print(json.dumps({"lanes": LANES, "hops_per_push": k, "push_ms": ms, "stream_frames_per_s": frames / (ms * 1e-3),
+                      "recompute": (k + 7) / k, "offline_same_frames_ms": off_ms, "offline_same_frames_per_s": frames / (off_ms * 1e-3),
+                      "realtime_lanes_per_device": 16.0 * k / ms * LANES}))     # a hop is 16 ms of audio
+ms = timed(offline(256, 512), 20)
+print(json.dumps({"offline_utterances": 256, "offline_frames_each": 512, "offline_ms": ms, "offline_frames_per_s": 256 * 512 / (ms * 1e-3)}))
