@@ -14,6 +14,7 @@ SO_PATH = os.environ.get("RCED_LIB") or os.path.join(_HERE, "librced_hip.so")
 RCED_OK, RCED_ERR_ARG, RCED_ERR_HIP, RCED_ERR_ALLOC, RCED_ERR_STATE = 0, 1, 2, 3, 4
 PATH_AUTO, PATH_LAYERWISE, PATH_FUSED = 0, 1, 2
 K_GENERIC, K_FUSED, K_FINAL = 0, 1, 2
+PCM_S16, PCM_F32 = 0, 1
 
 # every symbol include/rced.h declares: (restype, argtypes)
 _c_float_p = ctypes.POINTER(ctypes.c_float)
@@ -44,7 +45,9 @@ SYMBOLS = {
     "rced_stoi": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp]),
     "rced_mix_snr": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int,
                                     ctypes.c_double, _vp, ctypes.c_int, _vp]),
-    "rced_stream_delay": (ctypes.c_int, []),
+    "rced_gather_pcm": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_longlong, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
+                                       ctypes.c_int, _vp]),
+    "rced_stream_delay":(ctypes.c_int, []),
     "rced_stream_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
     "rced_stream_destroy": (None, [_vp]),
     "rced_stream_push": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _vp]),

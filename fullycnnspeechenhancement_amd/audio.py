@@ -175,12 +175,53 @@ def gains_needed(len_speech, len_noise):
     return int((len_speech - 1) // len_noise).bit_length()
 
 
-def mix_snr_batch(speech, noise, snr, speech_lengths=None, noise_lengths=None, starts=None, gains=None):
+def gather_pcm(arena, begins, counts, L=None, out=None):
+    """Rows of a zero-padded batch cut out of a device-resident corpus (rced_gather_pcm).
+    arena: torch.cuda int16 or float32 [S], contiguous; begins [N]: absolute sample indices; counts [N]: samples per row.
+    Row n = arena[begins[n] : begins[n] + counts[n]] as float32 (int16 / 32768, exact), zeros up to column L.
+    L: the row width (None = the largest count, rounded up to a multiple of 4 so that every row starts 16-byte aligned);
+    out: a float32 [N, >= L] device matrix with contiguous rows to write into (columns past L are left alone) -- a view of a
+    wider or taller buffer is fine, nothing is copied.  Every range must lie inside the arena and every count in [0, L]:
+    ValueError otherwise (the library would clamp).  Returns the [N, L] rows (a view of `out` when given), current stream."""
+    import torch
+    if not (hasattr(arena, "is_cuda") and arena.is_cuda and arena.dim() == 1 and arena.is_contiguous()
+            and arena.dtype in (torch.int16, torch.float32)):
+        raise ValueError("arena must be a contiguous 1-D CUDA/HIP tensor of int16 or float32")
+    dev, S = arena.device, int(arena.shape[0])
+    b = [int(v) for v in (begins.tolist() if hasattr(begins, "tolist") else begins)]
+    c = _host_ints(counts, len(b), "counts")
+    n = len(b)
+    if L is None:
+        L = out.shape[1] if out is not None else (max(c + [0]) + 3) // 4 * 4
+    L = int(L)
+    for i in range(n):
+        if c[i] < 0 or c[i] > L:
+            raise ValueError("counts[%d] = %d outside [0, L = %d]" % (i, c[i], L))
+        if b[i] < 0 or b[i] + c[i] > S:
+            raise ValueError("row %d: samples [%d, %d) leave the arena [0, %d)" % (i, b[i], b[i] + c[i], S))
+    if out is None:
+        out = torch.empty((n, L), dtype=torch.float32, device=dev)
+    elif not (hasattr(out, "is_cuda") and out.is_cuda and out.device == dev and out.dtype == torch.float32 and out.dim() == 2
+              and int(out.shape[0]) == n and int(out.shape[1]) >= L
+              and (out.shape[1] <= 1 or out.stride(1) == 1) and (n <= 1 or out.stride(0) >= out.shape[1])):
+        raise ValueError("out must be a float32 [N = %d, >= %d] matrix on the arena's device with contiguous rows" % (n, L))
+    if n and L:
+        bdev = torch.tensor(b, dtype=torch.int64, device=dev)
+        cdev = torch.tensor(c, dtype=torch.int32, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.load().rced_gather_pcm(arena.data_ptr(), _lib.PCM_S16 if arena.dtype == torch.int16 else _lib.PCM_F32, S,
+                                               bdev.data_ptr(), cdev.data_ptr(), n, L, out.data_ptr(), _row_stride(out), dev.index,
+                                               st))
+    return out[:, :L]
+
+
+def mix_snr_batch(speech, noise, snr, speech_lengths=None, noise_lengths=None, starts=None, gains=None, out=None):
     """AudioParser.add_noise (data_utils/data_loader.py:35-52) for a batch on the device, in closed form.
     speech [N, Ls], noise [N, Ln] torch.cuda float32 with per-utterance lengths (lists / tensors, or None = the full row);
     starts [N]: the crop offsets (used where the noise is longer than the speech; None = 0);
     gains [N, n_gains] float64 (array, or a list of per-utterance sequences, padded with 1): the uniform(0, 2) draws
     u_0.. (used where the speech is at least as long as the noise) -- loader.plan_noise makes both as the reference would.
+    out: None, or a contiguous float32 [N, Ls] device tensor to write into (e.g. the lower half of a [2N, Ls] buffer).
     Returns mix [N, Ls] float32 on the device (0 past each speech length), current stream."""
     import torch
     speech, noise = _rows(speech, "speech").contiguous(), _rows(noise, "noise").contiguous()
@@ -219,7 +260,13 @@ def mix_snr_batch(speech, noise, snr, speech_lengths=None, noise_lengths=None, s
             raise _lib.RcedError(_lib.RCED_ERR_ARG, "utterance %d (speech %d, noise %d samples) needs %d gains, got %d"
                                  % (i, ls_of[i], ln_of[i], gains_needed(ls_of[i], ln_of[i]), have[i]))
     n_gains = int(gdev.shape[1]) if gdev is not None else 0
-    mix = torch.empty((n, Ls), dtype=torch.float32, device=dev)
+    if out is None:
+        mix = torch.empty((n, Ls), dtype=torch.float32, device=dev)
+    elif (hasattr(out, "is_cuda") and out.is_cuda and out.device == dev and out.dtype == torch.float32
+          and tuple(out.shape) == (n, Ls) and out.is_contiguous()):
+        mix = out
+    else:
+        raise ValueError("out must be a contiguous float32 [%d, %d] tensor on the speech's device" % (n, Ls))
     if n and Ls:
         sdev = torch.tensor(sl, dtype=torch.int32, device=dev) if sl is not None else None
         ndev = torch.tensor(nl, dtype=torch.int32, device=dev) if nl is not None else None

@@ -241,4 +241,31 @@ int rced_mix_snr(const float* speech_dev, const int* speech_len_dev, int N, int 
   return RCED_OK;
 }
 
+int rced_gather_pcm(const void* arena_dev, int arena_dtype, long long arena_samples, const long long* begin_dev, const int* count_dev,
+                    int N, int L, float* rows_dev, int row_stride, int device, void* stream) {
+  if (N < 0 || L < 0 || arena_samples < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
+  if (arena_dtype != RCED_PCM_S16 && arena_dtype != RCED_PCM_F32)
+    return rced_fail(RCED_ERR_ARG, "arena_dtype must be RCED_PCM_S16 or RCED_PCM_F32, got %d", arena_dtype);
+  if (row_stride < L) return rced_fail(RCED_ERR_ARG, "row_stride %d < L %d", row_stride, L);
+  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
+  if (L > eval::kMaxLen) return rced_fail(RCED_ERR_ARG, "rows longer than 2^30 samples");
+  if (N == 0 || L == 0) return RCED_OK;
+  if (!begin_dev || !count_dev || !rows_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
+  if (!arena_dev && arena_samples > 0) return rced_fail(RCED_ERR_ARG, "null arena of %lld samples", arena_samples);
+  if (int rc = check_device(device, kMaxDevices)) return rc;
+  DeviceGuard g(device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid(eval::num_slices(L), N), block(eval::kThreads);
+  static_assert(eval::kSlice == eval::kThreads * eval::kGatherPerLane, "a column block of the gather is one slice");
+  if (arena_dtype == RCED_PCM_F32)
+    hipLaunchKernelGGL(eval::gather_pcm_kernel<true>, grid, block, 0, st, arena_dev, arena_samples, begin_dev, count_dev, L, rows_dev,
+                       row_stride);
+  else
+    hipLaunchKernelGGL(eval::gather_pcm_kernel<false>, grid, block, 0, st, arena_dev, arena_samples, begin_dev, count_dev, L, rows_dev,
+                       row_stride);
+  HIP_TRY(hipGetLastError());
+  return RCED_OK;
+}
+
 }  // extern "C"

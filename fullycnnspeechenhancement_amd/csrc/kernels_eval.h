@@ -294,5 +294,110 @@ __global__ __launch_bounds__(kThreads) void mix_apply_kernel(const float* __rest
   }
 }
 
+// ---- ragged crop-gather from a PCM arena (the loader's other half) -------------------------------------------------------------
+//
+// grid (column blocks of kSlice, N): lane t of block x owns the 8 output columns 8 (x kThreads + t) .. + 7 of row n, two
+// 16-byte stores.  A row's source starts at any sample of the arena, so its 16-byte phase (begin mod 8 for int16, mod 4 for
+// float32) is whatever the corpus index says -- but it is ONE phase for the whole row, uniform over the workgroup: the lanes
+// load the aligned 16-byte groups that cover their columns and pick their samples out of them at compile-time positions
+// (a switch over the phase, no indexed registers).  Only the last lanes of a row, and a row whose covering groups would
+// leave the arena, read sample by sample.  A copy with an exact conversion: nothing is summed, every output element has one
+// source element, so the result cannot depend on the batch around it.
+
+constexpr int kGatherPerLane = 8;
+
+// v[k] = sample P + k of the 16 int16 held in lo | hi, as float: value / 32768 (a power of two: exact)
+template <int P>
+__device__ inline void unpack_s16(const uint4& lo, const uint4& hi, float v[kGatherPerLane]) {
+  const unsigned w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+  for (int k = 0; k < kGatherPerLane; ++k) {
+    const unsigned d = w[(P + k) >> 1];
+    const short s = (short)(((P + k) & 1) ? (d >> 16) : (d & 0xffffu));
+    v[k] = (float)s * (1.f / 32768.f);
+  }
+}
+
+// v[k] = sample P + k of the 12 floats held in a | b | c
+template <int P>
+__device__ inline void pick_f32(const float4& a, const float4& b, const float4& c, float v[kGatherPerLane]) {
+  const float w[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
+#pragma unroll
+  for (int k = 0; k < kGatherPerLane; ++k) v[k] = w[P + k];
+}
+
+template <bool F32>
+__global__ __launch_bounds__(kThreads) void gather_pcm_kernel(const void* __restrict__ arena, long long arena_samples,
+                                                              const long long* __restrict__ begin, const int* __restrict__ count,
+                                                              int L, float* __restrict__ rows, int row_stride) {
+  const int n = blockIdx.y;
+  const int j = (blockIdx.x * kThreads + threadIdx.x) * kGatherPerLane;
+  if (j >= L) return;
+  // the row's range, clamped into the arena: nothing below reads outside [b, b + c)
+  long long b = begin[n];
+  b = b < 0 ? 0 : (b > arena_samples ? arena_samples : b);
+  int c = count[n];
+  c = c < 0 ? 0 : (c > L ? L : c);
+  if ((long long)c > arena_samples - b) c = (int)(arena_samples - b);
+  float v[kGatherPerLane] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (j < c) {
+    const long long s = b + j;                     // first source sample of this lane
+    const bool full = j + kGatherPerLane <= c;     // all 8 columns inside the row's count
+    const bool avec = aligned16(arena);
+    if (!F32) {
+      const short* src = static_cast<const short*>(arena);
+      const int p = (int)(s & 7);                  // = b & 7: j is a multiple of 8
+      const long long a = s - p;                   // a >= 0, and a + 8 <= s + 8 <= b + c <= arena_samples when full
+      if (avec && full && (p == 0 || a + 16 <= arena_samples)) {
+        const uint4 lo = *reinterpret_cast<const uint4*>(src + a);
+        const uint4 hi = p ? *reinterpret_cast<const uint4*>(src + a + 8) : lo;
+        switch (p) {
+          case 0: unpack_s16<0>(lo, hi, v); break;
+          case 1: unpack_s16<1>(lo, hi, v); break;
+          case 2: unpack_s16<2>(lo, hi, v); break;
+          case 3: unpack_s16<3>(lo, hi, v); break;
+          case 4: unpack_s16<4>(lo, hi, v); break;
+          case 5: unpack_s16<5>(lo, hi, v); break;
+          case 6: unpack_s16<6>(lo, hi, v); break;
+          default: unpack_s16<7>(lo, hi, v); break;
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < kGatherPerLane; ++k)
+          if (j + k < c) v[k] = (float)src[s + k] * (1.f / 32768.f);
+      }
+    } else {
+      const float* src = static_cast<const float*>(arena);
+      const int p = (int)(s & 3);
+      const long long a = s - p;                   // a + 8 <= arena_samples when full, as above
+      if (avec && full && (p == 0 || a + 12 <= arena_samples)) {
+        const float4 f0 = *reinterpret_cast<const float4*>(src + a);
+        const float4 f1 = *reinterpret_cast<const float4*>(src + a + 4);
+        const float4 f2 = p ? *reinterpret_cast<const float4*>(src + a + 8) : f1;
+        switch (p) {
+          case 0: pick_f32<0>(f0, f1, f2, v); break;
+          case 1: pick_f32<1>(f0, f1, f2, v); break;
+          case 2: pick_f32<2>(f0, f1, f2, v); break;
+          default: pick_f32<3>(f0, f1, f2, v); break;
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < kGatherPerLane; ++k)
+          if (j + k < c) v[k] = src[s + k];
+      }
+    }
+  }
+  // columns [c, L) are zeros; columns [L, row_stride) belong to the caller
+  float* orow = rows + (size_t)n * row_stride;
+  if (aligned16(orow) && j + kGatherPerLane <= L) {
+    *reinterpret_cast<float4*>(orow + j) = make_float4(v[0], v[1], v[2], v[3]);
+    *reinterpret_cast<float4*>(orow + j + 4) = make_float4(v[4], v[5], v[6], v[7]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < kGatherPerLane; ++k)
+      if (j + k < L) orow[j + k] = v[k];
+  }
+}
+
 }  // namespace eval
 }  // namespace rced

@@ -4,7 +4,7 @@ Reference: BaseTester / FullyCNNTester (model_utils/tester.py:18-90) and Inferen
 (infer.py:19-52): read cfg -> creat_graph() -> _init_session() -> _load_checkpoint() ->
 test_step(ndarray[N,T,129,1]) -> ndarray[N,T,129,1], and the evaluation loop over it (tester.py:92-167):
 `evaluate_pcm` / `test` take ragged PCM through STFT -> net -> ISTFT rebuild -> SDR (and STOI, on request) on the device.
-PESQ scoring, wav files and the manifest-driven DataLoader are not mirrored.
+PESQ scoring and wav files are not mirrored; the manifest-driven DataLoader is loader.DataLoader (batches built on the device).
 """
 
 import numpy as np
@@ -115,13 +115,21 @@ def evaluate_pcm(forward, mix_sig, clean_sig, nfft=512, device=0, lengths=None, 
     with its own forward (device [N, T, 129, 1] -> same): one upload, STFT with the lengths -> forward -> ISTFT rebuild
     (AudioReBuild(nfft), 512 as the reference ships it) -> SDR against the clean rows; the audio and N scores come back.
     mix_sig, clean_sig: lists of 1-D float arrays of ragged lengths (utterance i is scored over len(clean_sig[i]), the
-    reference's sig_length_list), or two zero-padded device tensors [N, L] with `lengths`.  kernels: the STFT / ISTFT
+    reference's sig_length_list), or two zero-padded device tensors [N, L] with `lengths`, or two loader.PcmRows (padded
+    device rows that carry their lengths: the device loader's batches, scored where they lie).  kernels: the STFT / ISTFT
     kernel family, as in audio.stft_batch.
     Returns (denoise: list of numpy float32, row i trimmed to its length; sdr: numpy float64 [N]); with stoi=True a third
     element, STOI per utterance (numpy float64 [N], audio.stoi_batch of the rebuilt audio against the clean rows)."""
     import torch
     from . import audio
-    if hasattr(mix_sig, "is_cuda"):
+    if hasattr(mix_sig, "rows") and hasattr(clean_sig, "rows"):      # loader.PcmRows: what the device loader yields
+        if len(mix_sig) != len(clean_sig) or list(mix_sig.lengths) != list(clean_sig.lengths):
+            raise ValueError("mix_sig and clean_sig must pair up, utterance by utterance and sample by sample")
+        lens = [int(v) for v in clean_sig.lengths]
+        if not lens:
+            return ([], np.zeros(0, np.float64), np.zeros(0, np.float64)) if stoi else ([], np.zeros(0, np.float64))
+        mix, clean = mix_sig.rows, clean_sig.rows
+    elif hasattr(mix_sig, "is_cuda"):
         if lengths is None:
             raise ValueError("padded device tensors need lengths")
         lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]

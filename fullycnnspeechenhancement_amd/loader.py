@@ -1,9 +1,21 @@
-"""Host-side mirror of the reference's AudioParser and batch padding (data_utils/data_loader.py:16-61, 198-209).
+"""Host-side mirror of the reference's data loader (data_utils/data_loader.py), with the batches built on the device.
 
-`add_noise` mixes on the device (rced_mix_snr) from the random draws `plan_noise` makes on the host exactly as the
-reference consumes np.random, so that after np.random.seed(s) both give the same mixture.  `load_audio` (librosa),
-manifests, Sampler and the joblib DataLoader are not built.
+One utterance at a time, numpy in and numpy out (data_loader.py:16-61, 198-209): `AudioParser.add_noise` mixes on the
+device (rced_mix_snr) from the random draws `plan_noise` makes on the host exactly as the reference consumes np.random, so
+that after np.random.seed(s) both give the same mixture; `padding_batch` pads as the reference does.
+
+Training from audio (data_loader.py:64-262): a `Corpus` is uploaded once -- one int16 (or float32) arena
+on the device plus a host index --, `DataSet` / `Sampler` / `DataLoader` keep the reference's order of items and of
+np.random draws (as its loader runs with num_works=1), and every batch is cut out of the arenas (rced_gather_pcm), mixed
+(rced_mix_snr) and transformed (one rced_stft over the clean and the mixed rows) on the device; per batch the host sends
+the plan only: which items, which crop offsets, which gains.  Manifests are the reference's json lines; wav files are read
+with the standard library (PCM16, mono, at the corpus rate).  Not built: librosa's `load_audio` (resampling, other
+formats), drop_last=True, worker processes, prefetch.
 """
+
+import codecs
+import json
+import wave
 
 import numpy as np
 
@@ -60,3 +72,319 @@ class AudioParser(object):
     def parse_audio(self, sig):
         return self.extractor.compute_spectrogram(sig, self.sample_rate, window_s=self.window_s, stride_s=self.stride_s,
                                                   nfft=256, use_complex=self.complex)
+
+
+# ---- the corpus: a host index, wav / manifest reading (no GPU needed), and the arena on the device ------------------
+
+def read_manifest(manifest_path, min_duration=0.4, max_duration=float("inf")):
+    """DataSet.read_manifest (data_loader.py:93-107): the json lines whose "duration" lies in [min, max]."""
+    manifest = []
+    for json_line in codecs.open(manifest_path, "r", "utf-8"):
+        try:
+            json_data = json.loads(json_line)
+        except Exception as e:
+            raise IOError("Error reading manifest: %s" % str(e))
+        if max_duration >= json_data["duration"] >= min_duration:
+            manifest.append(json_data)
+    return manifest
+
+
+def _open_wav(path, sample_rate):
+    try:
+        w = wave.open(path, "rb")
+    except (wave.Error, EOFError) as e:
+        raise ValueError("%s: not a PCM wav file (%s)" % (path, e))
+    if w.getnchannels() != 1 or w.getsampwidth() != 2 or w.getcomptype() != "NONE" or w.getframerate() != int(sample_rate):
+        got = (w.getnchannels(), 8 * w.getsampwidth(), w.getframerate())
+        w.close()
+        raise ValueError("%s: %d channel(s), %d bit, %d Hz; only mono PCM16 at %d Hz is read (resampling is not built)"
+                         % ((path,) + got + (int(sample_rate),)))
+    return w
+
+
+def wav_length(path, sample_rate):
+    """Samples in a wav file, from its header; ValueError unless it is mono PCM16 at sample_rate."""
+    w = _open_wav(path, sample_rate)
+    try:
+        return int(w.getnframes())
+    finally:
+        w.close()
+
+
+def read_wav(path, sample_rate):
+    """The samples of a mono PCM16 wav file at sample_rate, int16 [n]."""
+    w = _open_wav(path, sample_rate)
+    try:
+        return np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").astype(np.int16)
+    finally:
+        w.close()
+
+
+class CorpusIndex(object):
+    """Where every item lies in the arena: offsets[i] (first sample, absolute) and lengths[i], items packed back to back in
+    the order given.  Host only."""
+
+    def __init__(self, lengths, paths=None):
+        self.lengths = np.asarray(list(lengths), np.int64).reshape(-1)
+        if (self.lengths < 1).any():
+            raise ValueError("empty item %d" % int(np.argmax(self.lengths < 1)))
+        self.offsets = np.concatenate([[0], np.cumsum(self.lengths)[:-1]]).astype(np.int64) if self.lengths.size else \
+            np.zeros(0, np.int64)
+        self.total = int(self.lengths.sum())
+        self.paths = list(paths) if paths is not None else None
+
+    def __len__(self):
+        return int(self.lengths.size)
+
+    @classmethod
+    def from_manifest(cls, path, sample_rate, min_duration=0.4, max_duration=float("inf"), key="audio_filepath"):
+        """The index of a manifest's wav files, from their headers alone (nothing but the headers is read)."""
+        paths = [item[key] for item in read_manifest(path, min_duration, max_duration)]
+        return cls([wav_length(p, sample_rate) for p in paths], paths)
+
+
+class Corpus(object):
+    """Every utterance of a corpus in one device tensor (`arena`, int16 or float32 [total]) plus the host `index`
+    (CorpusIndex).  AISHELL-1 at 8 kHz int16 is about 10 GB: it is uploaded once and stays."""
+
+    def __init__(self, index, arena):
+        if int(arena.shape[0]) != index.total:
+            raise ValueError("the arena holds %d samples, the index %d" % (int(arena.shape[0]), index.total))
+        self.index, self.arena = index, arena
+        self.device = arena.device.index
+
+    def __len__(self):
+        return len(self.index)
+
+    @property
+    def lengths(self):
+        return self.index.lengths
+
+    @property
+    def offsets(self):
+        return self.index.offsets
+
+    @staticmethod
+    def _dtype(arrays):
+        """int16 in -> int16 arena; float in -> float32 arena."""
+        kinds = set("i" if a.dtype == np.int16 else ("f" if a.dtype.kind == "f" else "?") for a in arrays)
+        if kinds == {"i"}:
+            return np.int16
+        if kinds == {"f"}:
+            return np.float32
+        raise ValueError("items must all be int16 or all be float arrays")
+
+    @classmethod
+    def from_arrays(cls, arrays, device=0):
+        import torch
+        arrays = [np.asarray(a) for a in arrays]
+        if any(a.ndim != 1 for a in arrays):
+            raise ValueError("items must be 1-D arrays")
+        index = CorpusIndex([a.size for a in arrays])
+        dtype = cls._dtype(arrays) if arrays else np.int16
+        host = np.concatenate([a.astype(dtype, copy=False) for a in arrays]) if arrays else np.zeros(0, dtype)
+        return cls(index, torch.as_tensor(host, device="cuda:%d" % device))
+
+    @classmethod
+    def from_manifest(cls, path, sample_rate, min_duration=0.4, max_duration=float("inf"), key="audio_filepath", device=0):
+        """The wav files a reference manifest names (json lines, filtered by duration as data_loader.py:93-107 does; `key`
+        picks the field: "audio_filepath", or "clean_audio_filepath" / "mix_audio_filepath" of a paired manifest).  The
+        arena is sized from the headers, then filled file by file: host memory holds one file at a time."""
+        import torch
+        index = CorpusIndex.from_manifest(path, sample_rate, min_duration, max_duration, key)
+        arena = torch.empty((index.total,), dtype=torch.int16, device="cuda:%d" % device)
+        for p, off, n in zip(index.paths, index.offsets, index.lengths):
+            sig = read_wav(p, sample_rate)
+            if sig.size != n:
+                raise ValueError("%s: header says %d samples, the data holds %d" % (p, n, sig.size))
+            arena[int(off):int(off) + int(n)].copy_(torch.from_numpy(sig))
+        return cls(index, arena)
+
+    def gather(self, items, starts=None, counts=None, L=None, out=None):
+        """Rows cut from the arena: row n = item items[n] from its sample starts[n] (None = 0) over counts[n] samples (None =
+        to its end); audio.gather_pcm with the absolute positions."""
+        items = [int(i) for i in items]
+        starts = [0] * len(items) if starts is None else [int(s) for s in starts]
+        lens = [int(self.index.lengths[i]) for i in items]
+        counts = [n - s for n, s in zip(lens, starts)] if counts is None else [int(c) for c in counts]
+        for i, s, c, n in zip(items, starts, counts, lens):
+            if s < 0 or c < 0 or s + c > n:
+                raise ValueError("item %d has %d samples: [%d, %d) leaves it" % (i, n, s, s + c))
+        return audio.gather_pcm(self.arena, [int(self.index.offsets[i]) + s for i, s in zip(items, starts)], counts, L, out)
+
+
+class PcmRows(object):
+    """The `mix_sig` / `clean_sig` slot of a batch: zero-padded device rows [N, L] and their lengths.  len() and indexing
+    give what the reference's lists give, as trimmed device views; engine.evaluate_pcm takes the object as it is."""
+
+    def __init__(self, rows, lengths):
+        self.rows, self.lengths = rows, [int(v) for v in lengths]
+
+    def __len__(self):
+        return len(self.lengths)
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[k] for k in range(*i.indices(len(self)))]
+        i = int(i)
+        if not -len(self) <= i < len(self):
+            raise IndexError(i)
+        return self.rows[i, :self.lengths[i]]
+
+
+# ---- data_loader.py:64-262 -------------------------------------------------------------------------------------------
+
+class DataSet(object):
+    """data_loader.py:64-134 over corpora instead of manifests.  clean, noise, mix: Corpus objects (a CorpusIndex does
+    for everything but building batches).  `item_list` holds item ids of `clean`; with `noise`, `noise_list` holds its
+    ids, replicated ceil(len(items) / len(noise)) times where it is shorter (data_loader.py:87-91), and item k of a
+    batch is mixed with noise_list[k] at `snr` dB.  `mix=` is the paired mode (the reference's clean_audio_filepath /
+    mix_audio_filepath manifests): item i of `mix` is the mixture of item i of `clean`, nothing is mixed.
+    use_complex=True (the validation set of train.py): the reference then yields complex spectrograms that test() /
+    valid() never read (they recompute them from the PCM, engine.py); here the two spectrogram slots are None."""
+
+    def __init__(self, clean, noise=None, mix=None, snr=0, use_complex=False):
+        if (noise is None) == (mix is None):
+            raise ValueError("give either noise= (mixed at snr on the device) or mix= (a paired corpus)")
+        if mix is not None and len(mix) != len(clean):
+            raise ValueError("a paired corpus holds one mixture per clean item: %d != %d" % (len(mix), len(clean)))
+        self.clean, self.noise, self.mix = clean, noise, mix
+        self.snr, self.complex = snr, bool(use_complex)
+        self.item_list = list(range(len(clean)))
+        if noise is not None:
+            if len(noise) < 1:
+                raise ValueError("empty noise corpus")
+            self.noise_list = list(range(len(noise)))
+            if len(self.noise_list) < len(self.item_list):
+                self.noise_list = self.noise_list * int(np.ceil(len(self.item_list) / len(self.noise_list)))
+            assert len(self.noise_list) >= len(self.item_list)
+
+    def plan(self, index):
+        """The host half of DataSet.__getitem__ (data_loader.py:109-125): (clean id, noise id, start, gains) with the draws
+        add_noise makes -- or (clean id, None, 0, no gains) in the paired mode.  IndexError where the reference raises it."""
+        if self.noise is not None:
+            cid, nid = self.item_list[index], self.noise_list[index]
+            start, gains = plan_noise(self.clean.lengths[cid], self.noise.lengths[nid])
+            return cid, nid, start, gains
+        return self.item_list[index], None, 0, np.zeros(0, np.float64)
+
+    def __len__(self):
+        return len(self.item_list)
+
+    def __call__(self, *args, **kwargs):
+        return self
+
+    def shuffle(self):
+        np.random.shuffle(self.item_list)
+
+
+class Sampler(object):
+    """data_loader.py:137-168 as train.py uses it (drop_last=False), quirks included: the item list is extended by its own
+    tail to the next multiple of batch_size -- by a whole batch when it already is one --, and the bins are shuffled in
+    place, so they stay shuffled across epochs."""
+
+    def __init__(self, dataset, batch_size, start_index=0, drop_last=False):
+        if drop_last:
+            raise NotImplementedError("drop_last=True is not built (train.py does not use it)")
+        self.dataset = dataset
+        self.batch_size = batch_size
+        self.start_index = start_index
+        last_size = (int(len(self.dataset) / batch_size) + 1) * batch_size - len(self.dataset)
+        self.dataset.item_list.extend(self.dataset.item_list[-last_size:])
+        ids = list(range(len(self.dataset)))
+        self.bins = [ids[i:i + self.batch_size] for i in range(0, len(ids), self.batch_size)]
+        self.indices = (np.random.permutation(len(self.bins) - self.start_index) + self.start_index).tolist()
+
+    def __iter__(self):
+        for x in self.indices:
+            batch_ids = self.bins[x]
+            np.random.shuffle(batch_ids)
+            yield batch_ids
+
+    def __len__(self):
+        return len(self.bins) - self.start_index
+
+    def reset_start_index(self, start_index):
+        self.start_index = start_index
+
+    def __call__(self, *args, **kwargs):
+        return self
+
+    def iter_num(self):
+        return len(self.indices)
+
+
+class DataLoader(object):
+    """data_loader.py:171-262 with the batch built on the device.  Iterating yields the reference's 4-tuple
+    (batch_mix, batch_clean, mix_sig, clean_sig): two [N, T, 129, 1] float32 device tensors, zero past each utterance's
+    frames as padding_batch leaves them (None with use_complex=True, see DataSet), and two PcmRows.  np.random is
+    consumed in the order of the reference's loader with num_works=1: the sampler's shuffle of a bin, then add_noise's
+    draws item by item (with more workers the reference draws in forked processes and repeats nothing)."""
+
+    def __init__(self, dataset, batch_size, sampler=None):
+        self.dataset = dataset
+        self.batch_size = batch_size
+        self.sampler = sampler
+        if self.sampler is None:
+            self.bins = []
+            for i in range(0, len(self.dataset), self.batch_size):
+                self.bins.append(list(range(i, min(i + self.batch_size, len(self.dataset)))))
+
+    def plans(self):
+        """The host half of an epoch: per batch the list of DataSet.plan tuples, drawn lazily, batch by batch."""
+        if self.sampler is not None:
+            if self.sampler.batch_size != self.batch_size:
+                self.batch_size = self.sampler.batch_size
+                print("Warrning: sampler.batch_size != batch_size. batch_size changed!")
+            source = self.sampler
+        else:
+            source = self.bins
+        for index_list in source:
+            yield [self.dataset.plan(index) for index in index_list]
+
+    def build(self, plan):
+        """One batch on the device from its plan: gather the speech into rows 0..N of a [2N, Ls] buffer, the noise -- only the
+        ls samples add_noise keeps where it is longer than the speech, whole where it is shorter -- into [N, <= Ls], mix
+        into rows N..2N, one STFT over the 2N rows.  Paired mode: both halves are gathered."""
+        import torch
+        ds = self.dataset
+        n = len(plan)
+        cids = [p[0] for p in plan]
+        ls = [int(ds.clean.lengths[c]) for c in cids]
+        if ds.mix is not None:
+            lm = [int(ds.mix.lengths[c]) for c in cids]
+            width = (max(ls + lm) + 3) // 4 * 4
+            both = torch.empty((2 * n, width), dtype=torch.float32, device=ds.clean.arena.device)
+            ds.clean.gather(cids, L=width, out=both[:n])
+            ds.mix.gather(cids, L=width, out=both[n:])
+        else:
+            lm = ls
+            width = (max(ls) + 3) // 4 * 4           # every row starts 16-byte aligned
+            both = torch.empty((2 * n, width), dtype=torch.float32, device=ds.clean.arena.device)
+            ds.clean.gather(cids, L=width, out=both[:n])
+            nids, starts, counts, gains = [], [], [], []
+            for (_, nid, start, g), s in zip(plan, ls):
+                ln = int(ds.noise.lengths[nid])
+                nids.append(nid)
+                starts.append(start if ln > s else 0)
+                counts.append(s if ln > s else ln)         # cropped to the speech: it mixes as ln == ls, start 0, no gains
+                gains.append(g)
+            noise = ds.noise.gather(nids, starts, counts)
+            audio.mix_snr_batch(both[:n], noise, ds.snr, speech_lengths=ls, noise_lengths=counts, gains=gains, out=both[n:])
+        clean_sig, mix_sig = PcmRows(both[:n], ls), PcmRows(both[n:], lm)
+        if ds.complex:
+            return None, None, mix_sig, clean_sig
+        mag, _ = audio.stft_batch(both, ls + lm, with_phase=False)
+        return mag[n:], mag[:n], mix_sig, clean_sig
+
+    def __iter__(self):
+        for plan in self.plans():
+            yield self.build(plan)
+
+    def __len__(self):
+        if self.sampler is not None:
+            return len(self.sampler)
+        return len(self.bins)
+
+    def shuffle(self):
+        self.dataset.shuffle()

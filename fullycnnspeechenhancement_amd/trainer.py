@@ -4,15 +4,30 @@ Reference: FullyCNNTrainer (model_utils/trainer.py:121-192) -- creat_graph build
 `pred = Model(is_training=True)(input_x)`, `loss = sum((target - pred)^2) / batch_size`, Adam under the
 BatchNorm UPDATE_OPS; train_step runs `[loss, summaries, global_step, train_op]`; the training loop feeds the
 learning rate: `init_lr` for the first step, then the Noam schedule of the returned global step
-(trainer.py:27,68-76,215).  Loops, checkpoints and TF summaries are host orchestration and not mirrored.
+(trainer.py:27,68-76,215).  `train` is the epoch loop (trainer.py:194-243) over a loader that yields the reference's 4-tuple
+-- loader.DataLoader builds the batches on the device --, with a checkpoint per epoch under the reference's name.  TF
+summaries are not built.
 """
 
 import ctypes
+import os
+import time
 
 import numpy as np
 
 from . import _lib, model as _model, spec, weights as _weights
 from .metrics import AverageMeter
+
+
+def checkpoint_path(checkpoints_path, net_arch, net_work, epoch, global_step):
+    """trainer.py:232-238: {checkpoints_path}/{arch}_{net}/{arch}_{net}_{epoch}_{global_step-1}.ckpt."""
+    return os.path.join(checkpoints_path + "/{}_{}".format(net_arch, net_work),
+                        "{}_{}_{}_{}.ckpt".format(net_arch, net_work, epoch, global_step - 1))
+
+
+def start_epoch(continue_from):
+    """trainer.py:198-201: the epoch after the one a checkpoint's name carries; 0 without a checkpoint."""
+    return int(continue_from.split("_")[-2]) + 1 if continue_from is not None else 0
 
 
 class FullyCNNTrainer(object):
@@ -29,6 +44,10 @@ class FullyCNNTrainer(object):
         self.device = int(device)
         self.sdr_score = AverageMeter()            # trainer.py:34; valid() adds to it and never resets it, as there
         self.stoi_score = AverageMeter()           # trainer.py:33; filled by valid(..., stoi=True)
+        self.train_loss = AverageMeter()           # trainer.py:29-31; train() updates the three
+        self.data_time = AverageMeter()
+        self.batch_time = AverageMeter()
+        self.continue_from = None                  # trainer.py:24; from_checkpoint records the path, train() resumes after its epoch
         w = weights if weights is not None else _weights.initial_weights(self.variant, seed)
         self._blob_n = spec.num_weights(self.variant)
         # creat_graph (trainer.py:165-172): self.model = Model(is_training=True); self.pred = self.model(self.input_x).
@@ -103,6 +122,41 @@ class FullyCNNTrainer(object):
         out = self.train_step(input_x, target_y)
         self.lr = self.noam_scheme(out[2], self.warmup_steps)
         return out
+
+    def train(self, train_loader, valid_loader, epochs, logger=None, checkpoints_path=None, net_arch="FullyCNN",
+              num_iter_print=100):
+        """trainer.py:194-243: per epoch shuffle, one fit_step per batch of train_loader (anything that yields the reference's
+        4-tuple and has shuffle(), batch_size and len(): loader.DataLoader), the reference's progress line every
+        num_iter_print batches, a checkpoint (save_checkpoint) under the reference's name when checkpoints_path is given,
+        valid(valid_loader, epoch, logger) after every fifth epoch.  A trainer made by from_checkpoint starts at the epoch
+        after the one its checkpoint's name carries.  Returns the last global step.  TF summaries are not built."""
+        global_step = 0
+        for epoch in range(start_epoch(self.continue_from), epochs):
+            train_batch_id = 0
+            train_loader.shuffle()
+            start_time = time.time()
+            for batch_mix, batch_clean, _, _ in train_loader:
+                train_batch_id += 1
+                self.data_time.update(time.time() - start_time)
+                start_time = time.time()
+                batch_loss, _, global_step = self.fit_step(batch_mix, batch_clean)
+                self.train_loss.update(batch_loss, n=1)
+                self.batch_time.update(time.time() - start_time)
+                if train_batch_id % num_iter_print == 0:
+                    print("epoch: {}, batch: {}/{}, "
+                          "TrainLoss: {train_loss.val:.4f}({train_loss.avg:.4f}), "
+                          "DataTime: {data_time.val:.3f}({data_time.avg:.3f}), "
+                          "BatchTime: {batch_time.val:.3f}({batch_time.avg:.3f})".format(
+                              epoch, train_batch_id, len(train_loader), train_loss=self.train_loss,
+                              data_time=self.data_time, batch_time=self.batch_time))
+                start_time = time.time()
+            if checkpoints_path is not None:
+                path = checkpoint_path(checkpoints_path, net_arch, self.net_work, epoch, global_step)
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+                self.save_checkpoint(path)
+            if (epoch + 1) % 5 == 0:
+                self.valid(valid_loader, epoch, logger)
+        return global_step
 
     @property
     def global_step(self):
@@ -192,6 +246,7 @@ class FullyCNNTrainer(object):
         weights, adam_m, adam_v, step = tf_checkpoint.load_training_state(path, variant)
         tr = cls(net_work, weights=weights, **kw)
         tr.load_optimizer_state(adam_m, adam_v, step)
+        tr.continue_from = path
         return tr
 
     def restore(self, weights, keep_optimizer=True):

@@ -200,6 +200,21 @@ int rced_mix_snr(const float* speech_dev, const int* speech_len_dev, int N, int 
                  const int* start_dev, const double* gains_dev, int n_gains,
                  double snr_db, float* mix_dev, int device, void* stream);
 
+#define RCED_PCM_S16 0
+#define RCED_PCM_F32 1
+/* Rows of a zero-padded batch, cut out of a device-resident corpus (the training loader):
+ *   rows_dev[n, 0 .. count[n])  = arena[begin[n] .. begin[n] + count[n])  as float32
+ *                                 (int16: value / 32768, exact -- what librosa / soundfile give for PCM16; float32: copied)
+ *   rows_dev[n, count[n] .. L)  = 0;   columns L .. row_stride are not touched.
+ * arena_dev: int16 or float32 [arena_samples]; begin_dev [N] int64 (absolute sample index); count_dev [N] int32.
+ * A row whose range leaves [0, arena_samples) or whose count leaves [0, L] is clamped into them (begin into
+ * [0, arena_samples], count into [0, min(L, arena_samples - begin)]: never read outside the arena), as the other entries
+ * clamp lengths; the Python side validates and raises.  The same item may fill several rows.  One launch, grid over
+ * (column blocks, N); asynchronous, allocates nothing, stream-capturable, bit-reproducible. */
+int rced_gather_pcm(const void* arena_dev, int arena_dtype, long long arena_samples,
+                    const long long* begin_dev, const int* count_dev, int N, int L,
+                    float* rows_dev, int row_stride, int device, void* stream);
+
 /* STOI (Taal, Hendriks, Heusdens, Jensen 2011; the reference takes it from pystoi, tester.py:92-167) per utterance over
  * its own length: stoi(x = ref row, y = est row, fs_sig), exactly as DESIGN.md "STOI" specifies it -- polyphase resampling
  * to 10 kHz (fs_sig = 8000; fs_sig = 10000 skips it; any other rate is RCED_ERR_ARG), removal of the frames more than
