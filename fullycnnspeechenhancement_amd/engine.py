@@ -4,7 +4,7 @@ Reference: BaseTester / FullyCNNTester (model_utils/tester.py:18-90) and Inferen
 (infer.py:19-52): read cfg -> creat_graph() -> _init_session() -> _load_checkpoint() ->
 test_step(ndarray[N,T,129,1]) -> ndarray[N,T,129,1], and the evaluation loop over it (tester.py:92-167):
 `evaluate_pcm` / `test` take ragged PCM through STFT -> net -> ISTFT rebuild -> SDR (and STOI, on request) on the device.
-PESQ scoring and wav files are not mirrored; the manifest-driven DataLoader is loader.DataLoader (batches built on the device).
+PESQ scoring and the evaluation loop's wav files are not mirrored; the manifest-driven DataLoader is loader.DataLoader (batches built on the device).
 """
 
 import numpy as np
@@ -155,19 +155,52 @@ class InferenceEngine(FullyCNNTester):
     """infer.py:19-52, the forward slice: `denoise_magnitude` is infer.py:62-65 without the
     STFT/ISTFT around it."""
 
-    def denoise_pcm(self, sig, nfft=512):
+    def denoise_pcm(self, sig, nfft=512, sample_rate=8000):
         """infer.py:54-71 end to end on the device: STFT (audio_feature.py) -> model -> rebuild (utils.py:171-183).
         The magnitude is laid out [1, T, 129, 1] by TRANSPOSE, as the batch loader does
         (data_loader.py:206-208); infer.py:59 itself reshapes without transposing.
-        sig: 1-D float PCM at 8 kHz.  Returns the denoised signal, same length, numpy float32."""
+        sig: 1-D float PCM at 8 kHz.  Returns the denoised signal, same length, numpy float32.
+        sample_rate other than 8000: sig is at that rate and is resampled to 8 kHz on the device first (audio.resample_batch:
+        what infer.py's librosa.load(sr=8000) does to a file); the result is at 8 kHz, audio.resample_length samples."""
         import torch
         from . import audio
         dev = "cuda:%d" % self.device
-        pcm = torch.as_tensor(np.asarray(sig, dtype=np.float32), device=dev)[None]
+        if int(sample_rate) != audio.SAMPLE_RATE:
+            rows, lens = audio.resample_batch(np.asarray(sig, dtype=np.float32).reshape(1, -1), sample_rate, audio.SAMPLE_RATE,
+                                              device=self.device)
+            pcm, n = rows[:, :lens[0]], lens[0]
+        else:
+            pcm, n = torch.as_tensor(np.asarray(sig, dtype=np.float32), device=dev)[None], len(sig)
         mag, phase = audio.stft_batch(pcm)
         pred = self.model(mag)
         out = audio.istft_batch(pred, phase, nfft)
-        return out[0, :len(sig)].cpu().numpy()
+        return out[0, :n].cpu().numpy()
+
+    def denoise_file(self, path, save_dir=None, nfft=512):
+        """infer.py:54-76 for one wav file: PCM16 of any rate and channel count is downmixed and resampled to 8 kHz on the
+        device (loader.read_wav_frames + audio.resample_batch, in place of librosa.load(sr=8000)), denoised as denoise_pcm
+        does, and -- with save_dir -- written as PCM16 at 8 kHz to save_dir/<basename with .wav -> _de.wav> (infer.py:72-76's
+        name; int16 by clip(rint(y * 32768))).  Returns the denoised float32 signal."""
+        import os
+        import wave
+        from . import audio, loader
+        frames, rate = loader.read_wav_frames(path)
+        rows, lens = audio.resample_batch(frames[None], rate, audio.SAMPLE_RATE, device=self.device)
+        n = lens[0]
+        mag, phase = audio.stft_batch(rows[:, :n])
+        out = audio.istft_batch(self.model(mag), phase, nfft)[0, :n].cpu().numpy()
+        if save_dir is not None:
+            os.makedirs(save_dir, exist_ok=True)
+            pcm16 = np.clip(np.rint(out.astype(np.float64) * 32768.0), -32768, 32767).astype("<i2")
+            w = wave.open(os.path.join(save_dir, os.path.basename(path).replace(".wav", "_de.wav")), "wb")
+            try:
+                w.setnchannels(1)
+                w.setsampwidth(2)
+                w.setframerate(audio.SAMPLE_RATE)
+                w.writeframes(pcm16.tobytes())
+            finally:
+                w.close()
+        return out
 
     def denoise_stream(self, chunks, hops=8, nfft=512):
         """denoise_pcm for audio that arrives in pieces: a generator over an iterable of 1-D PCM pieces of any size.  The

@@ -9,8 +9,10 @@ on the device plus a host index --, `DataSet` / `Sampler` / `DataLoader` keep th
 np.random draws (as its loader runs with num_works=1), and every batch is cut out of the arenas (rced_gather_pcm), mixed
 (rced_mix_snr) and transformed (one rced_stft over the clean and the mixed rows) on the device; per batch the host sends
 the plan only: which items, which crop offsets, which gains.  Manifests are the reference's json lines; wav files are read
-with the standard library (PCM16, mono, at the corpus rate).  Not built: librosa's `load_audio` (resampling, other
-formats), drop_last=True, worker processes, prefetch.
+with the standard library: PCM16, mono, at the corpus rate -- or, with resample=True, PCM16 of any rate and channel count,
+downmixed and resampled on the device while the corpus is uploaded (rced_resample, DESIGN.md 3.4f: what librosa's
+`load_audio` does on the host).  Not built: other sample formats (8 / 24 / 32 bit, flac), drop_last=True, worker
+processes, prefetch.
 """
 
 import codecs
@@ -89,21 +91,48 @@ def read_manifest(manifest_path, min_duration=0.4, max_duration=float("inf")):
     return manifest
 
 
-def _open_wav(path, sample_rate):
+def _open_wav(path, sample_rate, resample=False):
     try:
         w = wave.open(path, "rb")
     except (wave.Error, EOFError) as e:
         raise ValueError("%s: not a PCM wav file (%s)" % (path, e))
-    if w.getnchannels() != 1 or w.getsampwidth() != 2 or w.getcomptype() != "NONE" or w.getframerate() != int(sample_rate):
-        got = (w.getnchannels(), 8 * w.getsampwidth(), w.getframerate())
+    got = (w.getnchannels(), 8 * w.getsampwidth(), w.getframerate())
+    if resample:
+        if w.getsampwidth() != 2 or w.getcomptype() != "NONE" or got[0] < 1 or got[2] < 1:
+            w.close()
+            raise ValueError("%s: %d channel(s), %d bit, %d Hz; only PCM16 is read" % ((path,) + got))
+    elif got[0] != 1 or w.getsampwidth() != 2 or w.getcomptype() != "NONE" or got[2] != int(sample_rate):
         w.close()
-        raise ValueError("%s: %d channel(s), %d bit, %d Hz; only mono PCM16 at %d Hz is read (resampling is not built)"
-                         % ((path,) + got + (int(sample_rate),)))
+        raise ValueError("%s: %d channel(s), %d bit, %d Hz; only mono PCM16 at %d Hz is read (resample=True converts PCM16 of "
+                         "any rate and channel count on the device)" % ((path,) + got + (int(sample_rate),)))
     return w
 
 
-def wav_length(path, sample_rate):
-    """Samples in a wav file, from its header; ValueError unless it is mono PCM16 at sample_rate."""
+def wav_info(path):
+    """(rate, channels, frames) of a PCM16 wav file, from its header."""
+    w = _open_wav(path, None, resample=True)
+    try:
+        return int(w.getframerate()), int(w.getnchannels()), int(w.getnframes())
+    finally:
+        w.close()
+
+
+def read_wav_frames(path):
+    """A PCM16 wav file as it is stored: (int16 [frames, channels], rate)."""
+    w = _open_wav(path, None, resample=True)
+    try:
+        sig = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").astype(np.int16)
+        return sig.reshape(-1, w.getnchannels()), int(w.getframerate())
+    finally:
+        w.close()
+
+
+def wav_length(path, sample_rate, resample=False):
+    """Samples in a wav file at sample_rate, from its header; ValueError unless it is mono PCM16 at sample_rate.  With
+    resample=True any PCM16 file: the samples it has once resampled (audio.resample_length)."""
+    if resample:
+        rate, _, frames = wav_info(path)
+        return audio.resample_length(frames, rate, sample_rate)
     w = _open_wav(path, sample_rate)
     try:
         return int(w.getnframes())
@@ -111,13 +140,53 @@ def wav_length(path, sample_rate):
         w.close()
 
 
-def read_wav(path, sample_rate):
-    """The samples of a mono PCM16 wav file at sample_rate, int16 [n]."""
+def read_wav(path, sample_rate, resample=False, device=0):
+    """The samples of a mono PCM16 wav file at sample_rate, int16 [n].  With resample=True any PCM16 file, downmixed and
+    resampled to sample_rate on the device (needs a GPU), int16 [n] by the rule of rced_resample."""
+    if resample:
+        frames, rate = read_wav_frames(path)
+        rows, lens = audio.resample_batch(frames[None], rate, sample_rate, dtype="int16", device=device)
+        return rows[0, :lens[0]].cpu().numpy()
     w = _open_wav(path, sample_rate)
     try:
         return np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").astype(np.int16)
     finally:
         w.close()
+
+
+STAGING_BYTES = 256 << 20      # raw PCM16 per upload of Corpus.from_manifest(resample=True)
+
+
+def staged_uploads(paths, device):
+    """PCM16 wav files of any rate and channel count, uploaded as they are stored, at most STAGING_BYTES at a time (a larger
+    file goes alone).  Yields (raw, groups) per upload: raw, an int16 device tensor, and groups[(rate, channels)] = [(i, first
+    frame, frames)] -- where file i lies in raw, in frames of its own channel count.  Host memory holds one staging buffer."""
+    import torch
+    infos = [wav_info(p) for p in paths]
+    sizes = [frames * channels for _, channels, frames in infos]
+    chans = [channels for _, channels, _ in infos]
+    stage = np.empty((min(max([STAGING_BYTES // 2] + sizes), sum(sizes) + sum(chans)),), np.int16)
+    first = 0
+    while first < len(paths):
+        # the files of one upload: each starts on a whole frame of its own channel count; always at least one file
+        last, used, starts = first, 0, []
+        while last < len(paths):
+            at = -(-used // chans[last]) * chans[last]
+            if last > first and at + sizes[last] > stage.size:
+                break
+            starts.append(at)
+            used = at + sizes[last]
+            last += 1
+        groups = {}
+        for i, at in zip(range(first, last), starts):
+            rate, channels, frames = infos[i]
+            sig, _ = read_wav_frames(paths[i])
+            if sig.shape[0] != frames:
+                raise ValueError("%s: header says %d frames, the data holds %d" % (paths[i], frames, sig.shape[0]))
+            stage[at:at + sizes[i]] = sig.reshape(-1)
+            groups.setdefault((rate, channels), []).append((i, at // channels, frames))
+        yield torch.from_numpy(stage[:used]).to(device), groups
+        first = last
 
 
 class CorpusIndex(object):
@@ -137,10 +206,11 @@ class CorpusIndex(object):
         return int(self.lengths.size)
 
     @classmethod
-    def from_manifest(cls, path, sample_rate, min_duration=0.4, max_duration=float("inf"), key="audio_filepath"):
-        """The index of a manifest's wav files, from their headers alone (nothing but the headers is read)."""
+    def from_manifest(cls, path, sample_rate, min_duration=0.4, max_duration=float("inf"), key="audio_filepath", resample=False):
+        """The index of a manifest's wav files, from their headers alone (nothing but the headers is read).  resample=True:
+        PCM16 files of any rate and channel count; the lengths are those they have at sample_rate."""
         paths = [item[key] for item in read_manifest(path, min_duration, max_duration)]
-        return cls([wav_length(p, sample_rate) for p in paths], paths)
+        return cls([wav_length(p, sample_rate, resample) for p in paths], paths)
 
 
 class Corpus(object):
@@ -186,18 +256,37 @@ class Corpus(object):
         return cls(index, torch.as_tensor(host, device="cuda:%d" % device))
 
     @classmethod
-    def from_manifest(cls, path, sample_rate, min_duration=0.4, max_duration=float("inf"), key="audio_filepath", device=0):
+    def from_manifest(cls, path, sample_rate, min_duration=0.4, max_duration=float("inf"), key="audio_filepath", device=0,
+                      resample=False, arena_dtype=None):
         """The wav files a reference manifest names (json lines, filtered by duration as data_loader.py:93-107 does; `key`
         picks the field: "audio_filepath", or "clean_audio_filepath" / "mix_audio_filepath" of a paired manifest).  The
-        arena is sized from the headers, then filled file by file: host memory holds one file at a time."""
+        arena is sized from the headers, then filled file by file: host memory holds one file at a time.
+        resample=True: PCM16 files of any rate and channel count.  They are uploaded as stored, at most STAGING_BYTES at a
+        time, and downmixed and resampled to sample_rate on the device straight into the arena (audio.resample_arena in
+        packed mode, one call per (rate, channels) of an upload); the arena is float32, or int16 with arena_dtype="int16".
+        Host memory holds one staging buffer, never the corpus."""
         import torch
-        index = CorpusIndex.from_manifest(path, sample_rate, min_duration, max_duration, key)
-        arena = torch.empty((index.total,), dtype=torch.int16, device="cuda:%d" % device)
-        for p, off, n in zip(index.paths, index.offsets, index.lengths):
-            sig = read_wav(p, sample_rate)
-            if sig.size != n:
-                raise ValueError("%s: header says %d samples, the data holds %d" % (p, n, sig.size))
-            arena[int(off):int(off) + int(n)].copy_(torch.from_numpy(sig))
+        if not resample:
+            if arena_dtype not in (None, "int16"):
+                raise ValueError("without resample=True the arena holds the files' int16 samples")
+            index = CorpusIndex.from_manifest(path, sample_rate, min_duration, max_duration, key)
+            arena = torch.empty((index.total,), dtype=torch.int16, device="cuda:%d" % device)
+            for p, off, n in zip(index.paths, index.offsets, index.lengths):
+                sig = read_wav(p, sample_rate)
+                if sig.size != n:
+                    raise ValueError("%s: header says %d samples, the data holds %d" % (p, n, sig.size))
+                arena[int(off):int(off) + int(n)].copy_(torch.from_numpy(sig))
+            return cls(index, arena)
+        arena_dtype = arena_dtype or "float32"
+        if arena_dtype not in audio.PCM_DTYPES:
+            raise ValueError("arena_dtype must be 'float32' or 'int16', got %r" % (arena_dtype,))
+        index = CorpusIndex.from_manifest(path, sample_rate, min_duration, max_duration, key, resample=True)
+        arena = torch.empty((index.total,), dtype=torch.float32 if arena_dtype == "float32" else torch.int16,
+                            device="cuda:%d" % device)
+        for raw, groups in staged_uploads(index.paths, arena.device):
+            for (rate, channels), rows in groups.items():
+                audio.resample_arena(raw, [a for _, a, _ in rows], [f for _, _, f in rows], channels, rate, sample_rate,
+                                     out=arena, out_begins=[int(index.offsets[i]) for i, _, _ in rows], dtype=arena_dtype)
         return cls(index, arena)
 
     def gather(self, items, starts=None, counts=None, L=None, out=None):

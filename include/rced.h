@@ -215,6 +215,40 @@ int rced_gather_pcm(const void* arena_dev, int arena_dtype, long long arena_samp
                     const long long* begin_dev, const int* count_dev, int N, int L,
                     float* rows_dev, int row_stride, int device, void* stream);
 
+/* ---- resample: audio at any rate ---------------------------------------------------------------------
+ * A band-limited (Kaiser-windowed sinc) interpolator with the parameters of resampy's kaiser_best, evaluated exactly:
+ *   ratio = (double)sr_new / sr_orig, s = min(1, ratio), p / q = sr_new / sr_orig in lowest terms,
+ *   y[m] = sum_j x[j] s h(s ((j - n0) - r / p)),  (n0, r) = divmod(m q, p),  m < (long long)(n * ratio),  x = 0 outside the row,
+ *   h(t) = rho sinc(rho t) I0(beta sqrt(1 - (t / 64)^2)) / I0(beta) for |t| < 64, else 0,
+ * everything in float64 from the stored samples.  sr_orig == sr_new is the (downmixing) copy. */
+
+/* Output samples of n input frames: (long long)((double)n * ((double)sr_new / sr_orig)); -1 on bad arguments (n < 0, a rate <= 0). */
+long long rced_resample_length(long long n, int sr_orig, int sr_new);
+
+/* The phase table of a ratio, host only (works without a GPU): table[r][c] = s h(s ((c - left) - r / p)), r < p, c < width: the
+ * `width` columns any phase reaches, `left` of them before n0.  Writes p, q, left, width (each may be NULL) and, when
+ * table_host is not NULL, the p * width doubles (n_doubles: the buffer's size; too small is RCED_ERR_ARG).  Built once per
+ * ratio and process.  A ratio whose table would exceed 1 MiB (8001 -> 8000, say), or one output of which reaches more frames
+ * than a workgroup stages (rates more than 47 : 1 apart going down), is refused: RCED_ERR_ARG, the message names the ratio. */
+int rced_resample_taps(int sr_orig, int sr_new, int* p, int* q, int* left, int* width,
+                       double* table_host, size_t n_doubles);
+
+/* Row n = frames [begin[n], begin[n] + count[n]) of src_dev, resampled.  src_dev: int16 or float32 (RCED_PCM_*),
+ * [src_frames][channels] interleaved; a sample is value / 32768 (int16) or the value, the channels are averaged in float64.
+ * begin_dev [N] int64 and count_dev [N] int32 are in frames and clamped into the source as rced_gather_pcm clamps (never
+ * read outside it; the Python side validates and raises).  Row n has rced_resample_length(count[n]) outputs, at most L.
+ *   out_begin_dev == NULL: they go to out + n * row_stride, zeros from there up to column L; columns L .. row_stride are not touched.
+ *   out_begin_dev [N] int64: they go to out + out_begin[n], packed, nothing else is written (a corpus arena, say); L bounds them.
+ * out_dtype RCED_PCM_F32: the float64 sum rounded once; RCED_PCM_S16: clip(rint(y * 32768), -32768, 32767), ties to even.
+ * One launch, grid over (output tiles, N).  The first call of a ratio on a device uploads its table (allocates, synchronises);
+ * every later one allocates nothing, is asynchronous and stream-capturable.  Finite inputs give bit-identical results from
+ * run to run, independent of N, the row, begin's alignment, the output mode and the neighbouring rows. */
+int rced_resample(const void* src_dev, int src_dtype, int channels, long long src_frames,
+                  const long long* begin_dev, const int* count_dev, int N,
+                  int sr_orig, int sr_new,
+                  void* out_dev, int out_dtype, const long long* out_begin_dev,
+                  int row_stride, int L, int device, void* stream);
+
 /* STOI (Taal, Hendriks, Heusdens, Jensen 2011; the reference takes it from pystoi, tester.py:92-167) per utterance over
  * its own length: stoi(x = ref row, y = est row, fs_sig), exactly as DESIGN.md "STOI" specifies it -- polyphase resampling
  * to 10 kHz (fs_sig = 8000; fs_sig = 10000 skips it; any other rate is RCED_ERR_ARG), removal of the frames more than
