@@ -58,6 +58,14 @@ SYMBOLS = {
     "rced_stream_push": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _vp]),
     "rced_stream_finish": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "rced_stream_reset": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "rced_rstream_create": (ctypes.c_int, [ctypes.c_int] * 10 + [ctypes.POINTER(_vp)]),
+    "rced_rstream_create_ex": (ctypes.c_int, [ctypes.c_int] * 11 + [ctypes.POINTER(_vp)]),
+    "rced_rstream_destroy": (None, [_vp]),
+    "rced_rstream_started": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "rced_rstream_delay": (ctypes.c_int, [_vp]),
+    "rced_rstream_push": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _vp]),
+    "rced_rstream_finish": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "rced_rstream_reset": (ctypes.c_int, [_vp, ctypes.c_int]),
     "rced_train_create": (ctypes.c_int, [ctypes.c_int, _c_float_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
                                          ctypes.POINTER(_vp)]),
     "rced_train_destroy": (None, [_vp]),

@@ -417,18 +417,40 @@ class StreamingDenoiser(object):
 
     model_or_engine: a model of this package (is_training=False) or an engine holding one as `.model`; the stream runs the
     forward form that model has selected.  max_hops: the most hops one push may carry (1..64); nfft: 512 (the reference's
-    rebuild as shipped) or 256."""
+    rebuild as shipped) or 256.
 
-    def __init__(self, model_or_engine, lanes, max_hops=8, nfft=512):
+    sample_rate, channels, dtype ("float32" or "int16"), output_rate: the capture and playback device's format.  With the
+    defaults this is the 8 kHz object above.  Otherwise a push takes [lanes, K * hop_in (* channels)] at sample_rate, hop_in =
+    128 * sample_rate / 8000, through resampler lanes (StreamingResampler) down to 8 kHz, the denoiser, and --
+    with output_rate, normally sample_rate -- resampler lanes up again, without synchronisation; the output is float32 mono,
+    InferenceEngine.denoise_pcm(x, sample_rate=...) (resampled to output_rate) delayed by `.delay` = stream_delay(...)
+    samples.  A rate at which the hop is not a whole number of frames (44.1 kHz: 128 * 441 / 80) is a ValueError naming the
+    rate: denoise_pcm serves those rates offline."""
+
+    def __init__(self, model_or_engine, lanes, max_hops=8, nfft=512, sample_rate=8000, channels=1, dtype="float32", output_rate=None):
         import ctypes
-        self._h = None
+        self._h = self._down = self._up = None
         self.model = getattr(model_or_engine, "model", model_or_engine)
         if getattr(self.model, "_handle", None) is None:
             raise ValueError("StreamingDenoiser needs an inference model (Model(is_training=False)) or an engine that holds one")
         self.lanes, self.max_hops, self.nfft, self.device = int(lanes), int(max_hops), int(nfft), self.model.device
         h = ctypes.c_void_p()
+        self.sample_rate, self.channels, self.dtype = int(sample_rate), int(channels), dtype
+        self.output_rate = int(output_rate) if output_rate is not None else None
+        for rate in (self.sample_rate, self.output_rate):
+            if rate is not None and (rate < 1 or STEP * rate % SAMPLE_RATE):
+                raise ValueError("a hop of %d samples at 8 kHz is not a whole number of frames at %r Hz: streaming serves rates that are a "
+                                 "multiple of 62.5 Hz, InferenceEngine.denoise_pcm(sample_rate=...) every rate" % (STEP, rate))
         _lib.check(_lib.load().rced_stream_create(self.model._handle, self.lanes, self.max_hops, self.nfft, ctypes.byref(h)))
         self._h = h
+        self.hop_in = STEP * self.sample_rate // SAMPLE_RATE
+        self.delay = stream_delay(self.sample_rate, self.output_rate, self.channels, dtype)
+        if self.sample_rate != SAMPLE_RATE or self.channels != 1 or dtype != "float32":
+            self._down = StreamingResampler(self.sample_rate, SAMPLE_RATE, self.lanes, unit_out=STEP, channels=self.channels, dtype=dtype,
+                                            max_units=self.max_hops, device=self.device, delay=STEP)
+        if self.output_rate is not None and self.output_rate != SAMPLE_RATE:
+            self._up = StreamingResampler(SAMPLE_RATE, self.output_rate, self.lanes, unit_in=STEP, max_units=self.max_hops,
+                                          device=self.device)
 
     def _tensor(self, x, dtype, shape, what):
         import torch
@@ -446,7 +468,15 @@ class StreamingDenoiser(object):
     def push(self, pcm, active=None):
         """pcm [lanes, K*128] (1 <= K <= max_hops): the next K hops of every lane -> [lanes, K*128], the lanes' output streams.
         active: None, or `lanes` flags; a lane flagged 0 is idle (state untouched, zeros out).  A CUDA tensor gives a CUDA
-        tensor (no synchronisation), an ndarray an ndarray."""
+        tensor (no synchronisation), an ndarray an ndarray.
+        At the device's rate: pcm [lanes, K * hop_in (* channels)] of `dtype` -> [lanes, K*128] at 8 kHz, or with output_rate
+        [lanes, K * 128 * output_rate / 8000], float32."""
+        import torch
+        if self._down is not None or self._up is not None:
+            return self._push_rate(pcm, active)
+        return self._push8(pcm, active)
+
+    def _push8(self, pcm, active=None):
         import torch
         as_torch = hasattr(pcm, "is_cuda")
         cols = int(pcm.shape[1]) if len(pcm.shape) == 2 else -1
@@ -463,10 +493,66 @@ class StreamingDenoiser(object):
                 t.record_stream(torch.cuda.current_stream(x.device))
         return out if as_torch else out.cpu().numpy()
 
+    def _push_rate(self, pcm, active):
+        """down lanes -> the three launches of the 8 kHz push -> up lanes, nothing waits.  The down lanes run a whole hop behind
+        (delay 128), so what they hand on is whole hops of the 8 kHz signal -- except the first hop of a lane's first push, which
+        is the delay's zeros and not signal: the denoiser takes that hop apart from the others, for the lanes that have started
+        only (StreamingResampler.started), and returns zeros for the rest."""
+        import torch
+        as_torch = hasattr(pcm, "is_cuda")
+        dev = "cuda:%d" % self.device
+        x = pcm
+        if not as_torch:
+            a = np.asarray(pcm)
+            x = torch.as_tensor(np.ascontiguousarray(a, dtype=np.int16 if self.dtype == "int16" else np.float32), device=dev)
+        if self._down is not None:
+            act = self._down._active(active)
+            started = self._down.started(act)
+            z = self._down.push(x, act)                              # [lanes, K * 128] at 8 kHz, one hop late
+            y = self._push8(z[:, :STEP], started)
+            if z.shape[1] > STEP:
+                y = torch.cat([y, self._push8(z[:, STEP:], act)], dim=1)
+        else:
+            act = active
+            y = self._push8(x, act)
+        if self._up is not None:
+            y = self._up.push(y, act)
+        return y if as_torch else y.cpu().numpy()
+
+    def _drain(self, stage, unit, lanes, seqs):
+        """Whole units of seqs[i] through lane lanes[i] of `stage`, one unit a push, the other lanes idle; then its finish with
+        what is left.  Returns every lane's output, joined."""
+        seqs = [np.asarray(s, np.float32) for s in seqs]
+        got = [[] for _ in lanes]
+        at = 0
+        while any(len(s) - at >= unit for s in seqs):
+            pcm, active = np.zeros((self.lanes, unit), np.float32), [0] * self.lanes
+            for lane, s in zip(lanes, seqs):
+                if len(s) - at >= unit:
+                    pcm[lane], active[lane] = s[at:at + unit], 1
+            out = stage.push(pcm, active) if stage is not self else self._push8(pcm, active)
+            for i, (lane, s) in enumerate(zip(lanes, seqs)):
+                if len(s) - at >= unit:
+                    got[i].append(np.asarray(out[lane]))
+            at += unit
+        tails = [s[len(s) // unit * unit:] for s in seqs]
+        rest = stage.finish(lanes, tails) if stage is not self else self._finish8(lanes, tails)
+        return [np.concatenate(g + [np.asarray(r)]) for g, r in zip(got, rest)]
+
     def finish(self, lanes, tails):
         """Ends the utterance of every lane listed: tails[i] holds the last 0..127 samples of lane lanes[i].  Returns a list of
         float32 arrays, the samples each lane still owed (L - max(0, 128 H - 640) of them); the lanes are reset for a new
-        utterance, the others left alone.  Synchronises (the counts come back)."""
+        utterance, the others left alone.  Synchronises (the counts come back).
+        At the device's rate: tails[i] holds fewer than hop_in frames; the stages are drained in order -- what the down lanes
+        owe goes hop by hop through the denoiser and its finish, all of that through the up lanes and their finish."""
+        if self._down is None and self._up is None:
+            return self._finish8(lanes, tails)
+        lanes = [int(v) for v in lanes]
+        seqs = self._down.finish(lanes, tails) if self._down is not None else None
+        out = self._drain(self, STEP, lanes, seqs) if seqs is not None else self._finish8(lanes, tails)
+        return self._drain(self._up, STEP, lanes, out) if self._up is not None else out
+
+    def _finish8(self, lanes, tails):
         import torch
         lanes = [int(v) for v in lanes]
         if len(lanes) != len(tails) or len(set(lanes)) != len(lanes) or any(v < 0 or v >= self.lanes for v in lanes):
@@ -491,11 +577,196 @@ class StreamingDenoiser(object):
     def reset(self, lane=-1):
         """Back to the start of an utterance, without output: one lane, or (-1) all of them."""
         _lib.check(_lib.load().rced_stream_reset(self._h, int(lane)))
+        for stage in (self._down, self._up):
+            if stage is not None:
+                stage.reset(lane)
+
+    def close(self):
+        for stage in (getattr(self, "_down", None), getattr(self, "_up", None)):
+            if stage is not None:
+                stage.close()
+        self._down = self._up = None
+        if self._h is not None:
+            try:
+                _lib.load().rced_stream_destroy(self._h)
+            except Exception:
+                pass
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+def resampler_delay(sr_in, sr_out):
+    """The delay D of a resampler lane (StreamingResampler.delay) in output samples, from the phase table alone
+    (needs no GPU): the smallest D at which a push reaches only frames already pushed, floor(right * p / q)."""
+    p, q, left, table = resample_taps(sr_in, sr_out)
+    return (table.shape[1] - 1 - left) * p // q
+
+
+def stream_delay(sample_rate=8000, output_rate=None, channels=1, dtype="float32"):
+    """StreamingDenoiser(..., sample_rate, channels, dtype, output_rate).delay, in samples at the output's rate (needs no GPU):
+    STREAM_DELAY = 640 at 8 kHz; with down lanes (any input but mono float32 at 8 kHz) one hop more, 128 -- the down lanes hand on
+    whole hops, which costs resampler_delay's 63 rounded up to a hop --; with up lanes all of that carried to output_rate, and
+    their own resampler_delay(8000, output_rate).  48 kHz in and out: (128 + 640) * 6 + 384 = 4,992."""
+    d = STREAM_DELAY + (STEP if int(sample_rate) != SAMPLE_RATE or int(channels) != 1 or dtype != "float32" else 0)
+    if output_rate is not None and int(output_rate) != SAMPLE_RATE:
+        d = d * int(output_rate) // SAMPLE_RATE + resampler_delay(SAMPLE_RATE, output_rate)
+    return d
+
+
+class StreamingResampler(object):
+    """resample_batch for audio that arrives unit by unit, for `lanes` independent streams at once (rced_rstream_*, DESIGN.md
+    3.4g).  A push of K units hands every active lane K * unit_in source frames at sr_in and returns K * unit_out samples at
+    sr_out; a lane's output is resample_batch of everything pushed before `finish`, delayed by `.delay` samples, bit for
+    bit: zeros first, and `finish` hands out what is still owed.  All state lives on the device; a push is one launch on
+    the current stream.
+
+    unit_out / unit_in: give one (the other follows from the ratio; a unit that gives no whole number on the other side is a
+    ValueError), both (they must stand in the ratio), or neither (the smallest pair: q frames in, p samples out).
+    channels: interleaved channels per frame, averaged; dtype / out_dtype: "float32" or "int16", as in resample_arena;
+    max_units: the most units one push may carry; delay: None (the smallest, resampler_delay(sr_in, sr_out)) or a longer one."""
+
+    def __init__(self, sr_in, sr_out, lanes, unit_out=None, unit_in=None, channels=1, dtype="float32", out_dtype="float32",
+                 max_units=8, device=0, delay=None):
+        import ctypes
+        from math import gcd
+        self._h = None
+        sr_in, sr_out = int(sr_in), int(sr_out)
+        if sr_in < 1 or sr_out < 1:
+            raise ValueError("both rates must be positive, got %d -> %d" % (sr_in, sr_out))
+        if dtype not in PCM_DTYPES or out_dtype not in PCM_DTYPES:
+            raise ValueError("dtype and out_dtype must be 'float32' or 'int16', got %r, %r" % (dtype, out_dtype))
+        p, q = sr_out // gcd(sr_in, sr_out), sr_in // gcd(sr_in, sr_out)
+        if unit_out is None and unit_in is None:
+            unit_in, unit_out = q, p
+        elif unit_in is None:
+            if int(unit_out) * q % p:
+                raise ValueError("%d samples at %d Hz are not a whole number of frames at %d Hz (%d * %d / %d)"
+                                 % (unit_out, sr_out, sr_in, unit_out, q, p))
+            unit_in = int(unit_out) * q // p
+        elif unit_out is None:
+            if int(unit_in) * p % q:
+                raise ValueError("%d frames at %d Hz are not a whole number of samples at %d Hz (%d * %d / %d)"
+                                 % (unit_in, sr_in, sr_out, unit_in, p, q))
+            unit_out = int(unit_in) * p // q
+        unit_in, unit_out = int(unit_in), int(unit_out)
+        if unit_in < 1 or unit_out < 1 or unit_in * p != unit_out * q:
+            raise ValueError("units of %d frames in and %d samples out do not stand in the ratio %d Hz -> %d Hz (%d / %d)"
+                             % (unit_in, unit_out, sr_in, sr_out, p, q))
+        self.sr_in, self.sr_out, self.lanes, self.channels, self.device = sr_in, sr_out, int(lanes), int(channels), int(device)
+        self.unit_in, self.unit_out, self.max_units, self.dtype, self.out_dtype = unit_in, unit_out, int(max_units), dtype, out_dtype
+        if self.channels < 1:
+            raise ValueError("channels must be >= 1, got %d" % self.channels)
+        h = ctypes.c_void_p()
+        code = lambda d: _lib.PCM_F32 if d == "float32" else _lib.PCM_S16      # noqa: E731
+        _lib.check(_lib.load().rced_rstream_create_ex(sr_in, sr_out, self.channels, code(dtype), code(out_dtype), unit_in, unit_out,
+                                                      self.lanes, self.max_units, -1 if delay is None else int(delay), self.device,
+                                                      ctypes.byref(h)))
+        self._h = h
+        self.delay = int(_lib.load().rced_rstream_delay(h))
+        self.finish_max = unit_out + self.delay
+
+    def _torch_dtype(self, name):
+        import torch
+        return torch.float32 if name == "float32" else torch.int16
+
+    def _frames(self, x, frames, what):
+        """[lanes, frames] (mono), [lanes, frames * channels] or [lanes, frames, channels] -> contiguous, on the device, of `dtype`"""
+        import torch
+        shapes = [(self.lanes, frames, self.channels), (self.lanes, frames * self.channels)]
+        if tuple(x.shape) not in shapes:
+            raise ValueError("%s must have shape %s or %s, got %s" % (what, shapes[0], shapes[1], tuple(x.shape)))
+        if hasattr(x, "is_cuda"):
+            if not x.is_cuda or x.device.index != self.device:
+                raise ValueError("%s must live on cuda:%d (or be a numpy array)" % (what, self.device))
+            return x.to(self._torch_dtype(self.dtype)).contiguous()
+        a = np.ascontiguousarray(x, dtype=np.float32 if self.dtype == "float32" else np.int16)
+        return torch.as_tensor(a, device="cuda:%d" % self.device)
+
+    def _active(self, active):
+        import torch
+        if active is None:
+            return None
+        dev = "cuda:%d" % self.device
+        act = (active.to(torch.int32).contiguous() if hasattr(active, "is_cuda")
+               else torch.as_tensor(np.ascontiguousarray(active, dtype=np.int32), device=dev))
+        if tuple(act.shape) != (self.lanes,) or not act.is_cuda or act.device.index != self.device:
+            raise ValueError("active must hold lanes = %d flags on the stream's device" % self.lanes)
+        return act
+
+    def started(self, active=None):
+        """[lanes] int32 on the device: 1 where the lane is active and has taken a unit since the start of its utterance
+        (rced_rstream_started).  No synchronisation."""
+        import torch
+        act = self._active(active)
+        out = torch.empty((self.lanes,), dtype=torch.int32, device="cuda:%d" % self.device)
+        st = torch.cuda.current_stream(out.device).cuda_stream
+        _lib.check(_lib.load().rced_rstream_started(self._h, act.data_ptr() if act is not None else None, out.data_ptr(), st))
+        if act is not None:
+            act.record_stream(torch.cuda.current_stream(out.device))
+        return out
+
+    def push(self, pcm, active=None):
+        """pcm [lanes, K * unit_in] (interleaved: [lanes, K * unit_in * channels] or [lanes, K * unit_in, channels]), 1 <= K <=
+        max_units: the next K units of every lane -> [lanes, K * unit_out] of out_dtype.  active: None, or `lanes` flags; a lane
+        flagged 0 is idle (state untouched, zeros out).  A CUDA tensor gives a CUDA tensor (no synchronisation), an ndarray an
+        ndarray."""
+        import torch
+        as_torch = hasattr(pcm, "is_cuda")
+        per = self.unit_in * (self.channels if len(pcm.shape) == 2 else 1)
+        cols = int(pcm.shape[1]) if len(pcm.shape) in (2, 3) else 0
+        if cols < per or cols % per:
+            raise ValueError("pcm must be [lanes = %d, K * %d frames] with K >= 1, got %s" % (self.lanes, self.unit_in, tuple(pcm.shape)))
+        k = cols // per
+        x = self._frames(pcm, k * self.unit_in, "pcm")
+        act = self._active(active)
+        out = torch.empty((self.lanes, k * self.unit_out), dtype=self._torch_dtype(self.out_dtype), device=x.device)
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        _lib.check(_lib.load().rced_rstream_push(self._h, x.data_ptr(), act.data_ptr() if act is not None else None, k, out.data_ptr(), st))
+        for t in (x, act):          # a temporary's memory stays until the stream has passed
+            if t is not None:
+                t.record_stream(torch.cuda.current_stream(x.device))
+        return out if as_torch else out.cpu().numpy()
+
+    def finish(self, lanes, tails):
+        """Ends the utterance of every lane listed: tails[i] holds the last 0 .. unit_in - 1 frames of lane lanes[i] ([frames] or
+        [frames, channels]).  Returns a list of arrays of out_dtype, the samples each lane still owed
+        (resample_length(L) - max(0, H * unit_out - delay) of them); the lanes are reset for a new utterance, the others left
+        alone.  Synchronises (the counts come back)."""
+        import torch
+        lanes = [int(v) for v in lanes]
+        if len(lanes) != len(tails) or len(set(lanes)) != len(lanes) or any(v < 0 or v >= self.lanes for v in lanes):
+            raise ValueError("lanes must be distinct indices in [0, %d), one tail each" % self.lanes)
+        np_dtype = np.float32 if self.dtype == "float32" else np.int16
+        tail = np.zeros((self.lanes, self.unit_in, self.channels), np_dtype)
+        counts = np.full((self.lanes,), -1, np.int32)
+        for lane, t in zip(lanes, tails):
+            t = (t.detach().cpu().numpy() if hasattr(t, "is_cuda") else np.asarray(t)).astype(np_dtype, copy=False)
+            if t.size % self.channels:
+                raise ValueError("a tail holds whole frames of %d channels, got %d values" % (self.channels, t.size))
+            t = t.reshape(-1, self.channels)
+            if t.shape[0] >= self.unit_in:
+                raise ValueError("a tail holds fewer than %d frames (push whole units first), got %d" % (self.unit_in, t.shape[0]))
+            tail[lane, :t.shape[0]] = t
+            counts[lane] = t.shape[0]
+        dev = "cuda:%d" % self.device
+        tdev, cdev = torch.as_tensor(tail, device=dev), torch.as_tensor(counts, device=dev)
+        out = torch.empty((self.lanes, self.finish_max), dtype=self._torch_dtype(self.out_dtype), device=dev)
+        owed = torch.empty((self.lanes,), dtype=torch.int32, device=dev)
+        st = torch.cuda.current_stream(out.device).cuda_stream
+        _lib.check(_lib.load().rced_rstream_finish(self._h, tdev.data_ptr(), cdev.data_ptr(), out.data_ptr(), owed.data_ptr(), st))
+        out, owed = out.cpu().numpy(), owed.cpu().numpy()
+        return [out[lane, :owed[lane]].copy() for lane in lanes]
+
+    def reset(self, lane=-1):
+        """Back to the start of an utterance, without output: one lane, or (-1) all of them."""
+        _lib.check(_lib.load().rced_rstream_reset(self._h, int(lane)))
 
     def close(self):
         if self._h is not None:
             try:
-                _lib.load().rced_stream_destroy(self._h)
+                _lib.load().rced_rstream_destroy(self._h)
             except Exception:
                 pass
             self._h = None

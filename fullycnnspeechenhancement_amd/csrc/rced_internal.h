@@ -76,3 +76,7 @@ int rced_audio_x6_tables_get(int device, int nfft, rced_audio_x6_tables* out);
 
 // stream_api.hip: streams created on `m` answer RCED_ERR_STATE from now on (rced_destroy calls this before the model goes)
 void rced_streams_detach(rced_model* m);
+
+// resample_api.hip: the phase table of sr_new / sr_orig (found or built, as rced_resample_taps refuses) and, with table_dev, its
+// copy on `device` (uploaded once; the caller has checked the device and made it current), for the resampler lanes
+int rced_resample_table(int sr_orig, int sr_new, int* p, int* q, int* left, int* width, int device, const double** table_dev);

@@ -12,6 +12,7 @@
 #include "../../include/rced.h"
 #include "host_util.h"
 #include "kernels_resample.h"
+#include "rced_internal.h"
 
 using namespace rced;
 
@@ -128,6 +129,16 @@ int tile_for(const Ratio& R) {
 }
 
 }  // namespace
+
+int rced_resample_table(int sr_orig, int sr_new, int* p, int* q, int* left, int* width, int device, const double** table_dev) {
+  Ratio* R = nullptr;
+  if (int rc = ratio_for(sr_orig, sr_new, &R)) return rc;
+  *p = R->p;
+  *q = R->q;
+  *left = R->left;
+  *width = R->width;
+  return table_dev ? device_table(R, device, table_dev) : RCED_OK;
+}
 
 extern "C" {
 

@@ -202,22 +202,25 @@ class InferenceEngine(FullyCNNTester):
                 w.close()
         return out
 
-    def denoise_stream(self, chunks, hops=8, nfft=512):
+    def denoise_stream(self, chunks, hops=8, nfft=512, sample_rate=8000, output_rate=None):
         """denoise_pcm for audio that arrives in pieces: a generator over an iterable of 1-D PCM pieces of any size.  The
         pieces are re-blocked to whole hops (128 samples) and pushed, at most `hops` hops at a time, through a one-lane
         audio.StreamingDenoiser; every push's output is yielded as it comes (numpy float32, the result delayed by 640
         samples, zeros first), then what the stream still owed.  All pieces joined, with the leading zeros dropped, equal
-        denoise_pcm of the joined input."""
+        denoise_pcm of the joined input.
+        sample_rate / output_rate: the pieces are mono float at sample_rate and re-blocked to that rate's hop; the lane is
+        StreamingDenoiser(sample_rate=..., output_rate=...), which see for the delay and the rates it refuses."""
         from . import audio
-        stream = audio.StreamingDenoiser(self.model, 1, max_hops=int(hops), nfft=nfft)
+        stream = audio.StreamingDenoiser(self.model, 1, max_hops=int(hops), nfft=nfft, sample_rate=sample_rate, output_rate=output_rate)
+        hop = stream.hop_in
         try:
             held = np.zeros(0, np.float32)
             for piece in chunks:
                 held = np.concatenate([held, np.asarray(piece, np.float32).reshape(-1)])
-                while held.size >= audio.STEP:
-                    k = min(held.size // audio.STEP, stream.max_hops)
-                    yield stream.push(held[None, :k * audio.STEP])[0]
-                    held = held[k * audio.STEP:]
+                while held.size >= hop:
+                    k = min(held.size // hop, stream.max_hops)
+                    yield stream.push(held[None, :k * hop])[0]
+                    held = held[k * hop:]
             yield stream.finish([0], [held])[0]
         finally:
             stream.close()

@@ -298,6 +298,51 @@ int rced_stream_finish(rced_stream* s, const float* tail_dev, const int* tail_co
 /* Back to the start of an utterance without output: lane, or -1 for every lane.  Ordered on the stream of the latest push / finish. */
 int rced_stream_reset(rced_stream* s, int lane);
 
+/* ---- streaming resampler: the conversion of the "resample" section for audio that arrives piece by piece, for many independent
+ * streams ("lanes") at once, at a fixed delay.  A lane stream is created for a unit pair: every push of K units
+ * hands each active lane K * unit_in source frames and returns K * unit_out samples; unit_in * p must equal unit_out * q (p / q =
+ * sr_out / sr_in in lowest terms).  For one lane let x[0..L) be everything pushed before rced_rstream_finish (the tail included),
+ * H the units pushed and y = rced_resample(x), M = rced_resample_length(L) samples, x = 0 outside [0, L).  The lane's output stream
+ * is y delayed by D = rced_rstream_delay() samples -- zeros first, then y[i - D] --, bit for bit: every sample is the chain of
+ * fused multiply-adds rced_resample runs.  D is the smallest delay at which a push reaches only frames already pushed:
+ * floor(right * p / q) with right = width - 1 - left of rced_resample_taps (63 for 16 k -> 8 k and 48 k -> 8 k, 128 for 8 k -> 16 k,
+ * 384 for 8 k -> 48 k).  Source and output formats, downmix and scaling as in rced_resample.  All state lives on the device (per
+ * lane the units pushed and the last ceil(D q / p) + left frames in float64); after rced_rstream_create a push is one launch on the
+ * caller's stream, allocates nothing, does not synchronise and can be captured.  A stream object is not thread-safe. ---- */
+typedef struct rced_rstream rced_rstream;
+
+/* lanes 1..65536, pushes of at most max_units units.  RCED_ERR_ARG, before a device is looked for: units that do not stand in the
+ * ratio, and what rced_resample_taps refuses (the message names the ratio).  The first stream of a ratio on a device uploads its table. */
+int rced_rstream_create(int sr_in, int sr_out, int channels, int src_dtype, int out_dtype, int unit_in, int unit_out,
+                        int lanes, int max_units, int device, rced_rstream** out);
+/* The same with a delay of the caller's, D <= delay (less is RCED_ERR_ARG); delay < 0: D.  The history grows with it.  The streaming
+ * denoiser's down lanes run at 128, a whole hop, so that every hop they hand on is a whole hop of the 8 kHz signal. */
+int rced_rstream_create_ex(int sr_in, int sr_out, int channels, int src_dtype, int out_dtype, int unit_in, int unit_out,
+                           int lanes, int max_units, int delay, int device, rced_rstream** out);
+void rced_rstream_destroy(rced_rstream* h);
+/* D, in output samples; -1 for NULL. */
+int rced_rstream_delay(const rced_rstream* h);
+
+/* pcm_dev [lanes, K * unit_in, channels] of src_dtype: the next K units of every lane; out_dev [lanes, K * unit_out] of out_dtype.
+ * active_dev: NULL (every lane) or [lanes] int32 flags; a lane flagged 0 is idle: its state does not change, its input row is not
+ * read and zeros are written to its output row.  K < 1 or K > max_units: RCED_ERR_ARG.  Asynchronous. */
+int rced_rstream_push(rced_rstream* h, const void* pcm_dev, const int* active_dev, int K, void* out_dev, void* stream);
+
+/* Ends the utterance of every lane whose tail_counts_dev entry is 0 .. unit_in - 1: tail_dev [lanes, unit_in, channels] holds that
+ * many last frames.  out_dev [lanes, unit_out + D] receives from column 0 the M - max(0, H * unit_out - D) samples still owed,
+ * computed with zeros past L, zeros behind them; out_counts_dev [lanes] int32 that count.  The lane is then reset for a new
+ * utterance.  Entry -1 (or any other value): the lane is left alone (count 0).  Asynchronous. */
+int rced_rstream_finish(rced_rstream* h, const void* tail_dev, const int* tail_counts_dev, void* out_dev, int* out_counts_dev,
+                        void* stream);
+
+/* started_dev [lanes] int32 = 1 where the lane is active (active_dev as in rced_rstream_push) and has taken at least one unit since
+ * the start of its utterance, else 0: what the next push's first unit_out samples of a lane at a delay >= unit_out are -- signal, or
+ * the zeros of the delay.  One small launch, asynchronous. */
+int rced_rstream_started(rced_rstream* h, const int* active_dev, int* started_dev, void* stream);
+
+/* Back to the start of an utterance without output: lane, or -1 for every lane.  Ordered on the stream of the latest push / finish. */
+int rced_rstream_reset(rced_rstream* h, int lane);
+
 /* ---- training step: FullyCNNTrainer.creat_graph + train_step,
  * model_utils/trainer.py:156-192, over Model(is_training=True).  Layer-by-layer, correctness first. ---- */
 typedef struct rced_trainer rced_trainer;
