@@ -121,7 +121,7 @@ def evaluate_pcm(forward, mix_sig, clean_sig, nfft=512, device=0, lengths=None, 
     Returns (denoise: list of numpy float32, row i trimmed to its length; sdr: numpy float64 [N]); with stoi=True a third
     element, STOI per utterance (numpy float64 [N], audio.stoi_batch of the rebuilt audio against the clean rows)."""
     import torch
-    from . import audio
+    from . import _args, audio
     if hasattr(mix_sig, "rows") and hasattr(clean_sig, "rows"):      # loader.PcmRows: what the device loader yields
         if len(mix_sig) != len(clean_sig) or list(mix_sig.lengths) != list(clean_sig.lengths):
             raise ValueError("mix_sig and clean_sig must pair up, utterance by utterance and sample by sample")
@@ -132,7 +132,7 @@ def evaluate_pcm(forward, mix_sig, clean_sig, nfft=512, device=0, lengths=None, 
     elif hasattr(mix_sig, "is_cuda"):
         if lengths is None:
             raise ValueError("padded device tensors need lengths")
-        lens = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        lens = _args.host_ints(lengths)
         mix, clean = mix_sig, clean_sig
     else:
         lens = [len(c) for c in clean_sig]

@@ -1,0 +1,123 @@
+"""The evaluation loop's entry points on the device, over the C ABI: SDR and STOI per utterance,
+add_noise's SNR mixing in closed form, and the core of the loop, STFT -> forward -> ISTFT -> scores.  audio.py re-exports
+every public name here."""
+
+import numpy as np
+
+from . import _args, _lib
+from ._args import SAMPLE_RATE
+
+
+def sdr_batch(clean, estimate, lengths=None):
+    """SDR.sdr (model_utils/utils.py:68-86) per utterance on the device: clean [N, Lc], estimate [N, Le] torch.cuda float32,
+    row n holding utterance n from column 0 (the estimate may be istft_batch's [N, (T+1)*128] buffer as it is: the length
+    trims, nothing is copied); lengths: per-utterance sample counts in [0, min(Lc, Le)] or None (= min(Lc, Le) each).
+    Returns torch.float64 [N] (dB) on the device, current stream."""
+    import torch
+    clean, estimate, n, dev, sc, se, ldev = _args.scoring_args(clean, estimate, lengths)
+    out = torch.empty((n,), dtype=torch.float64, device=dev)
+    if n:
+        _lib.check(_lib.load().rced_sdr(clean.data_ptr(), sc, estimate.data_ptr(), se, ldev.data_ptr() if ldev is not None else None,
+                                        n, out.data_ptr(), None, dev.index, _args.current_stream(dev)))
+    return out
+
+
+STOI_RATES = (8000, 10000)
+
+
+def stoi_batch(clean, estimate, lengths=None, sample_rate=8000, detail=False):
+    """STOI (Taal et al. 2011; the reference's pystoi.stoi(clean, denoise, sr, extended=False), tester.py:92-167) per utterance
+    on the device, as DESIGN.md "STOI" specifies it.  clean [N, Lc], estimate [N, Le], lengths: as in sdr_batch (the estimate
+    may be istft_batch's buffer as it is).  sample_rate: 8000 (resampled to 10 kHz on the device) or 10000.
+    Returns torch.float64 [N] on the device, current stream; with detail=True also torch.int32 [N, 3]: frames at 10 kHz,
+    frames kept by the 40 dB silent-frame removal, 30-frame segments (0 segments: the score is 1e-5)."""
+    import torch
+    if int(sample_rate) not in STOI_RATES:
+        raise ValueError("sample_rate must be 8000 or 10000, got %r" % (sample_rate,))
+    clean, estimate, n, dev, sc, se, ldev = _args.scoring_args(clean, estimate, lengths)
+    out = torch.empty((n,), dtype=torch.float64, device=dev)
+    det = torch.empty((n, 3), dtype=torch.int32, device=dev) if detail else None
+    if n:
+        _lib.check(_lib.load().rced_stoi(clean.data_ptr(), sc, estimate.data_ptr(), se, ldev.data_ptr() if ldev is not None else None,
+                                         n, int(sample_rate), out.data_ptr(), det.data_ptr() if det is not None else None, dev.index,
+                                         _args.current_stream(dev)))
+    return (out, det) if detail else out
+
+
+def gains_needed(len_speech, len_noise):
+    """How many of add_noise's uniform(0, 2) draws can reach the first len_speech samples: bit_length((ls - 1) // ln)."""
+    if len_speech < len_noise or len_speech < 1:
+        return 0
+    return int((len_speech - 1) // len_noise).bit_length()
+
+
+def mix_snr_batch(speech, noise, snr, speech_lengths=None, noise_lengths=None, starts=None, gains=None, out=None):
+    """AudioParser.add_noise (data_utils/data_loader.py:35-52) for a batch on the device, in closed form.
+    speech [N, Ls], noise [N, Ln] torch.cuda float32 with per-utterance lengths (lists / tensors, or None = the full row);
+    starts [N]: the crop offsets (used where the noise is longer than the speech; None = 0);
+    gains [N, n_gains] float64 (array, or a list of per-utterance sequences, padded with 1): the uniform(0, 2) draws
+    u_0.. (used where the speech is at least as long as the noise) -- loader.plan_noise makes both as the reference would.
+    out: None, or a contiguous float32 [N, Ls] device tensor to write into (e.g. the lower half of a [2N, Ls] buffer).
+    Returns mix [N, Ls] float32 on the device (0 past each speech length), current stream."""
+    import torch
+    speech, noise = _args.rows(speech, "speech").contiguous(), _args.rows(noise, "noise").contiguous()
+    n, Ls, Ln = int(speech.shape[0]), int(speech.shape[1]), int(noise.shape[1])
+    if int(noise.shape[0]) != n or noise.device != speech.device:
+        raise ValueError("speech and noise must hold the same number of utterances on one device")
+    dev = speech.device
+    sl, nl = _args.host_ints(speech_lengths, n, "speech_lengths"), _args.host_ints(noise_lengths, n, "noise_lengths")
+    if sl is not None and any(v < 0 or v > Ls for v in sl):
+        raise ValueError("speech_lengths must lie in [0, %d]" % Ls)
+    if nl is not None and any(v < 1 or v > Ln for v in nl):
+        raise ValueError("noise_lengths must lie in [1, %d]" % Ln)
+    if n and Ls and Ln < 1:
+        raise ValueError("empty noise")
+    ls_of = sl if sl is not None else [Ls] * n
+    ln_of = nl if nl is not None else [Ln] * n
+    st_host = _args.host_ints(starts, n, "starts")
+    if st_host is not None:
+        for i in range(n):
+            if ls_of[i] < ln_of[i] and not 0 <= st_host[i] <= ln_of[i] - ls_of[i]:
+                raise ValueError("starts[%d] = %d outside [0, %d]" % (i, st_host[i], ln_of[i] - ls_of[i]))
+    if gains is not None and hasattr(gains, "is_cuda"):      # already on the device: [N, n_gains], every row complete
+        gdev = gains.to(device=dev, dtype=torch.float64).reshape(n, -1).contiguous()
+        have = [int(gdev.shape[1])] * n
+    else:
+        rows = [np.asarray(r, np.float64).reshape(-1) for r in gains] if gains is not None else [np.zeros(0)] * n
+        if len(rows) != n:
+            raise ValueError("gains must hold N = %d rows" % n)
+        have = [r.size for r in rows]
+        g = np.ones((n, max(have + [0])), np.float64)
+        for i, r in enumerate(rows):
+            g[i, :r.size] = r
+        gdev = torch.from_numpy(g).to(dev) if g.shape[1] else None
+    for i in range(n):       # the library cannot see the lengths; this side can
+        if gains_needed(ls_of[i], ln_of[i]) > have[i]:
+            raise _lib.RcedError(_lib.RCED_ERR_ARG, "utterance %d (speech %d, noise %d samples) needs %d gains, got %d"
+                                 % (i, ls_of[i], ln_of[i], gains_needed(ls_of[i], ln_of[i]), have[i]))
+    n_gains = int(gdev.shape[1]) if gdev is not None else 0
+    mix = torch.empty((n, Ls), dtype=torch.float32, device=dev) if out is None else _args.check_out(out, n, Ls, dev, torch.float32, exact=True)
+    if n and Ls:
+        sdev = torch.tensor(sl, dtype=torch.int32, device=dev) if sl is not None else None
+        ndev = torch.tensor(nl, dtype=torch.int32, device=dev) if nl is not None else None
+        tdev = torch.tensor(st_host, dtype=torch.int32, device=dev) if st_host is not None else None
+        ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+        _lib.check(_lib.load().rced_mix_snr(speech.data_ptr(), ptr(sdev), n, Ls, noise.data_ptr(), ptr(ndev), Ln, ptr(tdev),
+                                            ptr(gdev), n_gains, float(snr), mix.data_ptr(), dev.index, _args.current_stream(dev)))
+    return mix
+
+
+def denoise_and_score(forward, mix, clean, lengths, nfft=512, kernels="x6", stoi=False):
+    """The device core of the evaluation loop (tester.py:100-146 / trainer.py:260-307 without PESQ / wav files):
+    STFT of the mixtures -> forward (device [N, T, 129, 1] -> same) -> ISTFT rebuild -> SDR (and, with stoi=True, STOI) of
+    every rebuilt row against its clean row over its own length.  mix, clean: torch.cuda float32 [N, L] zero-padded;
+    lengths: N sample counts.
+    Returns (audio [N, (T+1)*128] on the device -- the caller trims row n to lengths[n] --, sdr torch.float64 [N]), with
+    stoi=True (audio, sdr, stoi torch.float64 [N])."""
+    from . import audio
+    mag, phase = audio.stft_batch(mix, lengths, kernels=kernels)
+    pred = forward(mag)
+    out = audio.istft_batch(pred, phase, nfft, kernels=kernels)
+    if stoi:
+        return out, sdr_batch(clean, out, lengths), stoi_batch(clean, out, lengths, SAMPLE_RATE)
+    return out, sdr_batch(clean, out, lengths)

@@ -276,6 +276,59 @@ def test_composite_in_longer_pushes_equals_the_stages_by_hand_in_the_same_pushes
         assert not portions                                          # every 8 kHz push of the lane is accounted for
 
 
+def plain8(net, x8, hop_counts):
+    """The whole output stream of a plain 8 kHz StreamingDenoiser for the 8 kHz signal x8: pushes of hop_counts hops (consumed
+    from the front), then its finish."""
+    from fullycnnspeechenhancement_amd import StreamingDenoiser
+    plain = StreamingDenoiser(engine(net), 1, max_hops=8)
+    z8, at = [], 0
+    while len(x8) - at >= 128:
+        k = hop_counts.pop(0)
+        z8.append(plain.push(x8[None, at:at + 128 * k])[0])
+        at += 128 * k
+    z8.append(plain.finish([0], [x8[at:]])[0])
+    plain.close()
+    return np.concatenate(z8)
+
+
+@pytest.mark.parametrize("sample_rate,output_rate", [(16000, None), (8000, 16000)], ids=["down_lanes_only", "up_lanes_only"])
+def test_half_chain_equals_its_stages_by_hand_bit_for_bit(built, sample_rate, output_rate):
+    """A chain of two stages.  Down lanes only (16 kHz in, 8 kHz out): the plain 8 kHz denoiser fed resample_batch(x -> 8 kHz)
+    hop by hop, then its finish, behind the hop of zeros the down lanes' delay puts in front.  Up lanes only (8 kHz in, 16 kHz
+    out): the plain denoiser's whole output stream through resample_batch(8 kHz -> 16 kHz), behind the up lanes' delay.  Two
+    lanes pushed a hop at a time (as in test_composite_equals_the_three_stages_by_hand_bit_for_bit) that finish at different
+    pushes: one signal of 6 hops and 11 frames; one of 2 hops and hop - 1 frames, then on the same lane one of exactly 3 hops,
+    whose tail is empty."""
+    from fullycnnspeechenhancement_amd import StreamingDenoiser, audio
+    hop = 128 * sample_rate // 8000
+    jobs = [[signal(6 * hop + 11, 1, "float32", 90)], [signal(2 * hop + hop - 1, 1, "float32", 91), signal(3 * hop, 1, "float32", 92)]]
+    stream = StreamingDenoiser(engine("FullyCNN"), 2, max_hops=4, sample_rate=sample_rate, output_rate=output_rate)
+    stream.unit_in = stream.hop_in                                  # the driver's name for it
+    done = S.run_lanes(stream, jobs, [1])
+    delay = stream.delay
+    stream.close()
+    assert delay == audio.stream_delay(sample_rate, output_rate) == (768 if output_rate is None else 1280 + audio.resampler_delay(8000, 16000))
+    for lane in range(2):
+        assert len(done[lane]) == len(jobs[lane])
+        for x, (out, hops) in zip(jobs[lane], done[lane]):
+            if output_rate is None:
+                x8 = offline(x, sample_rate, 8000, "float32")
+                want = np.concatenate([np.zeros(128, np.float32), plain8("FullyCNN", x8, [1] * 100)])
+            else:
+                x8 = x
+                up = np.zeros(audio.resampler_delay(8000, output_rate), np.float32)
+                want = np.concatenate([up, offline(plain8("FullyCNN", x, [1] * 100), 8000, output_rate, "float32")])
+            # `.delay` zeros, then the result; less the zeros of its 640 that a denoiser lane of under 5 hops never handed out
+            short = max(0, 640 - len(x8) // 128 * 128)
+            length = (delay + len(x8) - short if output_rate is None
+                      else delay + audio.resample_length(len(x8), 8000, output_rate) - short * output_rate // 8000)
+            assert hops == len(x) // hop and out.dtype == np.float32 and len(out) == length and out.shape == want.shape, (out.shape, want.shape)
+            diff = out != want
+            print("[half chain %d -> %s Hz] lane %d, %d frames: %d of %d samples differ" % (sample_rate, output_rate or 8000, lane, len(x),
+                                                                                          int(diff.sum()), out.size))
+            assert not diff.any() and out.any()
+
+
 @pytest.mark.parametrize("rate", [48000, 16000])
 def test_composite_against_the_offline_chain(built, rate):
     """The reference is resample_batch(denoise_pcm(x, sample_rate=rate), 8 kHz -> rate) delayed by `.delay`.  The up lanes are
