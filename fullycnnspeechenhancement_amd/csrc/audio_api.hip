@@ -18,7 +18,6 @@ using namespace rced;
 
 namespace {
 
-constexpr int kMaxDevices = 16;
 struct AudioTables {   // per device, built once
   float* stft = nullptr;
   float* istft512 = nullptr;
@@ -72,20 +71,7 @@ std::vector<float> pack_istft(int nfft) {   // [st][mt][lane][e]; row = sample n
   return p;
 }
 
-// [mt][chunk][part][lane][8] bf16 from a coefficient function coef(row, k), k = 32 chunk + 8 (lane >> 4) + e
-template <class F>
-std::vector<unsigned short> pack_x6(int mtiles, F coef) {
-  std::vector<unsigned short> p((size_t)mtiles * audio::x6::kPackPerMT, 0);
-  for (int mt = 0; mt < mtiles; ++mt)
-    for (int c = 0; c < audio::x6::kChunks; ++c)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int e = 0; e < 8; ++e) {
-          const int row = 16 * mt + (lane & 15), k = 32 * c + 8 * (lane >> 4) + e;
-          const size_t at = (size_t)mt * audio::x6::kPackPerMT + ((size_t)(c * 3) * 64 + lane) * 8 + e;
-          put3(p.data(), at, (float)coef(row, k));
-        }
-  return p;
-}
+using x6dft::pack_x6;
 // STFT rows (kernels_audio_x6.h): 0 = re(0), 1 = re(128), 2b / 2b + 1 = re / im of bin b
 double stft_coef(int row, int k) {
   const int b = row == 1 ? 128 : row >> 1;

@@ -15,7 +15,6 @@ using namespace rced;
 
 namespace {
 
-constexpr int kMaxDevices = 16;
 // Slice partials [N, slices, 2] double, one buffer per (device, stream): launches on one stream are ordered, so the buffer
 // of a stream is never shared by two calls in flight.  It only grows; a call whose shape fits allocates nothing, so the
 // entries can be stream-captured after one warm-up call of the shape.
@@ -103,15 +102,7 @@ int stoi_tables(int device, StoiTables** out) {
     const std::vector<double> taps = stoi_taps();
     std::copy(taps.begin(), taps.end(), tab.begin());
     for (int k = 0; k < stoi::kFrame; ++k) tab[stoi::kTabWin + k] = stoi_window(k);
-    // [mt][chunk][part][lane][8] bf16, k = 32 chunk + 8 (lane >> 4) + e, row = 16 mt + (lane & 15)
-    std::vector<unsigned short> pack((size_t)stoi::kPack, 0);
-    for (int mt = 0; mt < stoi::kMTiles; ++mt)
-      for (int c = 0; c < stoi::kChunks; ++c)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int e = 0; e < 8; ++e) {
-            const size_t at = (size_t)mt * stoi::kPackPerMT + ((size_t)(c * 3) * 64 + lane) * 8 + e;
-            put3(pack.data(), at, (float)stoi_coef(16 * mt + (lane & 15), 32 * c + 8 * (lane >> 4) + e));
-          }
+    const std::vector<unsigned short> pack = x6dft::pack_x6(stoi::kMTiles, stoi_coef);
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(stoi::band_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 stoi::kBandLdsBytes));
     double* dt = nullptr;

@@ -5,7 +5,7 @@
 //   3. mask_kernel      per utterance: max energy, the 40 dB mask, its exclusive scan -> the list of kept frames; (F, K, M)
 //   4. band_kernel      the 512-point DFT of the re-windowed overlap-added kept frames, bins 7..218 only, as a GEMM with K = 256 (the
 //                       second window is folded into the matrix, the zero-padded half drops out): three-part bf16 operands, six products,
-//                       fp32 accumulators -- the form of kernels_audio_x6.h.  The epilogue squares the accumulators in fp64 and sums them
+//                       fp32 accumulators -- x6_dft.h, the GEMM of kernels_audio_x6.h.  The epilogue squares the accumulators in fp64 and sums them
 //                       per one-third-octave band: spectra never reach memory, only sqrt(band power) [frame][15] does.
 //   5. segment_kernel   one thread per (segment of 30 frames, band): normalise, clip, centre, correlate -- fp64
 //   6. final_kernel     the mean over segments and bands; 1e-5 where fewer than 30 spectral frames exist
@@ -22,6 +22,7 @@
 #include <cstdint>
 
 #include "kernels_eval.h"
+#include "x6_dft.h"
 
 namespace rced {
 namespace stoi {
@@ -139,17 +140,11 @@ __global__ __launch_bounds__(64) void mask_kernel(const double* __restrict__ e, 
 }
 
 // ---- 4. DFT + one-third-octave bands ---------------------------------------------------------------------------------------------
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using namespace x6dft;   // the GEMM: put_pair, AFrag, load_a, gemm_block (x6_dft.h); STOI's frame is its depth
+static_assert(kFrame == kK, "a frame is the GEMM's depth");
 
 constexpr int kWaves = 8, kThreads = kWaves * 64;
 constexpr int kBlockFrames = 64;                              // spectral frames per workgroup
-constexpr int kChunks = kFrame / 32;                          // K = 256 in eight K = 32 chunks
-constexpr int kPackPerMT = kChunks * 3 * 64 * 8;              // bf16 per M-tile: [chunk][part][lane][8]
-constexpr int kPack = kMTiles * kPackPerMT;
 constexpr int kRowB = 2 * kHop + 16;                          // bytes per 128 samples of one part (+ pad): 272
 constexpr int kPartB = (kBlockFrames + 1) * kRowB;            // 65 rows: 17,680
 constexpr int kPairs = (kBlockFrames + 1) * (kHop / 2);       // 4,160 sample pairs
@@ -157,45 +152,7 @@ constexpr int kPowB = kMTiles * 4 * kBlockFrames * 8;         // [slot][frame] f
 constexpr int kBandLdsBytes = 3 * kPartB + kPowB + kFrame * 8 + (kBlockFrames + 2) * 4 + 8;
 static_assert((3 * kPartB) % 16 == 0 && kBandLdsBytes <= 160 * 1024, "LDS layout");
 
-__device__ __forceinline__ f32x4 mfma32(s16x8 a, s16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-struct Parts {
-  s16x8 h, m, l;
-};
-// the six products of one chunk for two independent chains, smallest first
-__device__ __forceinline__ void mma2(const s16x8 (&a)[3], const Parts& b0, f32x4& c0, const Parts& b1, f32x4& c1) {
-  c0 = mfma32(a[1], b0.m, c0);
-  c1 = mfma32(a[1], b1.m, c1);
-  c0 = mfma32(a[2], b0.h, c0);
-  c1 = mfma32(a[2], b1.h, c1);
-  c0 = mfma32(a[0], b0.l, c0);
-  c1 = mfma32(a[0], b1.l, c1);
-  c0 = mfma32(a[1], b0.h, c0);
-  c1 = mfma32(a[1], b1.h, c1);
-  c0 = mfma32(a[0], b0.m, c0);
-  c1 = mfma32(a[0], b1.m, c1);
-  c0 = mfma32(a[0], b0.h, c0);
-  c1 = mfma32(a[0], b1.h, c1);
-}
-// two fp32 values -> three packed bf16 pairs, x = h + m + l to 2^-24
-struct P3 {
-  unsigned h, m, l;
-};
-__device__ __forceinline__ P3 split2(float x0, float x1) {
-  P3 p;
-  const bf16x2 bh = {(__bf16)x0, (__bf16)x1};
-  p.h = __builtin_bit_cast(unsigned, bh);
-  const float r0 = x0 - __builtin_bit_cast(float, p.h << 16), r1 = x1 - __builtin_bit_cast(float, p.h & 0xffff0000u);
-  const bf16x2 bm = {(__bf16)r0, (__bf16)r1};
-  p.m = __builtin_bit_cast(unsigned, bm);
-  const float s0 = r0 - __builtin_bit_cast(float, p.m << 16), s1 = r1 - __builtin_bit_cast(float, p.m & 0xffff0000u);
-  const bf16x2 bl = {(__bf16)s0, (__bf16)s1};
-  p.l = __builtin_bit_cast(unsigned, bl);
-  return p;
-}
-
-// grid (ceil((fcap - 1) / 64), 2 signals, N), 8 waves; wave w takes M-tiles w, w + 8, ...  apack: kPack bf16.
+// grid (ceil((fcap - 1) / 64), 2 signals, N), 8 waves; wave w takes M-tiles w, w + 8, ...  apack: kMTiles * kPackPerMT bf16.
 // tob: [N][2][fcap][16] fp64, sqrt(band power) of spectral frame m in [.. m][band]
 __global__ __launch_bounds__(kThreads) void band_kernel(const double* __restrict__ r, int rstride, const int* __restrict__ kept,
                                                         const int* __restrict__ cnt, int fcap, const unsigned short* __restrict__ apack,
@@ -235,38 +192,17 @@ __global__ __launch_bounds__(kThreads) void band_kernel(const double* __restrict
       v0 += win[j] * s[0];
       v1 += win[j + 1] * s[1];
     }
-    const P3 q = split2((float)v0, (float)v1);
-    char* d = img + row * kRowB + (p & 63) * 4;
-    *reinterpret_cast<unsigned*>(d) = q.h;
-    *reinterpret_cast<unsigned*>(d + kPartB) = q.m;
-    *reinterpret_cast<unsigned*>(d + 2 * kPartB) = q.l;
+    put_pair(img, kPartB, row * kRowB + (p & 63) * 4, (float)v0, (float)v1);
   }
   __syncthreads();
-  // sample k = 32 c + 8 kq + e of frame 16 t + fn: row (16 t + fn) + (c >> 2), byte 64 (c & 3) + 16 kq
-  const char* base = img + fn * kRowB + 16 * kq;
   for (int mt = wave; mt < kMTiles; mt += kWaves) {
-    s16x8 A[kChunks][3];
-    const u32x4* src = reinterpret_cast<const u32x4*>(apack + (size_t)mt * kPackPerMT) + lane;
-#pragma unroll
-    for (int c = 0; c < kChunks; ++c)
-#pragma unroll
-      for (int q = 0; q < 3; ++q) A[c][q] = __builtin_bit_cast(s16x8, src[(c * 3 + q) * 64]);
+    AFrag A;
+    load_a(A, apack, mt, lane);
     f32x4 acc[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < kChunks; ++c) {
-      Parts b[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const char* p = base + t * 16 * kRowB + (c >> 2) * kRowB + 64 * (c & 3);
-        b[t].h = *reinterpret_cast<const s16x8*>(p);
-        b[t].m = *reinterpret_cast<const s16x8*>(p + kPartB);
-        b[t].l = *reinterpret_cast<const s16x8*>(p + 2 * kPartB);
-      }
-      mma2(A[c], b[0], acc[0], b[1], acc[1]);
-      mma2(A[c], b[2], acc[2], b[3], acc[3]);
-    }
+    // sample k = 32 c + 8 kq + e of frame 16 t + fn: row (16 t + fn) + (c >> 2), byte 64 (c & 3) + 16 kq (the rows of stft_x6_kernel)
+    gemm_block(A, img, kPartB, fn * kRowB + 16 * kq, 16 * kRowB, [](int c) { return (c >> 2) * kRowB + 64 * (c & 3); }, acc);
     // rows 4 kq .. 4 kq + 3 of the tile = pair slot 4 mt + kq: |A|^2 + |B|^2 in fp64, fixed order
 #pragma unroll
     for (int t = 0; t < 4; ++t) {

@@ -1,7 +1,9 @@
 // Streaming denoiser: the stateful STFT front end and ISTFT back end around the unchanged CNN forward.
 // A lane is one audio stream; audio arrives in hops of 128 samples and leaves 5 hops (640 samples) later.  Same reference rows as
-// kernels_audio_x6.h, whose device functions (three-part bf16 operands, six products per term) carry both GEMMs here: a frame's
-// spectrum comes out of the same instruction sequence as in stft_x6_kernel, whatever was pushed with it.
+// kernels_audio_x6.h.  Both GEMMs are x6_dft.h's (three-part bf16 operands, six products per term), and everything around them that
+// the offline kernels do as well is the device function they call: stft_store, slot_pair, rank1_add, head_spectrum / head_sample /
+// head_deemph, deemph_scan (kernels_audio_x6.h).  So a frame's spectrum comes out of the same code as in stft_x6_kernel, whatever was
+// pushed with it.  What is stateful is here: frame_sample, the lanes' bookkeeping, sample_at, the state update.
 //
 // One push of K hops to a lane that has seen H hops (frame t = hops t, t + 1; hop g completes frame g - 1):
 //   stream_stft_kernel   frames H - 1 .. H + K - 2 -> rows 7 .. 6 + K of the lane's window [7 + K, 129]; rows 0 .. 6 = the 7 kept frames,
@@ -72,9 +74,12 @@ __device__ __forceinline__ float frame_sample(const float* __restrict__ in, cons
 
 // in: pcm [S, K * 128] (push) or the tails [S, 128] (finish, K = 6 slots); flags: push: active [S] or null, finish: tail counts [S]
 // (-1 = not finishing).  win [S, 7 + K, 129], phw [S, 7 + K, 129, 2].  grid (ceil(S K / 64), 2 M-groups), dynamic LDS kStreamStftLds.
+// phw nonnull (stream_api.hip allocates it with win): stft_store serves "magnitude only" too, and without the attribute the compiler
+// unswitches on the pointer and keeps both forms of the epilogue here, 1,915 instructions against 1,506 (1,512 before it was shared).
 __global__ __launch_bounds__(kThreadsX) void stream_stft_kernel(const float* __restrict__ in, const int* __restrict__ flags, int finish,
                                                                  const unsigned short* __restrict__ apack, const float* __restrict__ state,
-                                                                 int S, int K, float* __restrict__ win, float* __restrict__ phw) {
+                                                                 int S, int K, float* __restrict__ win,
+                                                                 float* __restrict__ phw __attribute__((nonnull))) {
   extern __shared__ __attribute__((aligned(16))) char xs[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -118,42 +123,21 @@ __global__ __launch_bounds__(kThreadsX) void stream_stft_kernel(const float* __r
         e1 = frame_sample(src, st, finish, r, H, h, k + 1);
       }
     }
-    const P3 q = split2(e0, e1);
-    char* d = xs + fr * kXRowB + (i & 127) * 4;
-    *reinterpret_cast<unsigned*>(d) = q.h;
-    *reinterpret_cast<unsigned*>(d + kXPartB) = q.m;
-    *reinterpret_cast<unsigned*>(d + 2 * kXPartB) = q.l;
+    put_pair(xs, kXPartB, fr * kXRowB + (i & 127) * 4, e0, e1);
   }
   __syncthreads();
   f32x4 acc[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
   gemm_block(A, xs, kXPartB, n * kXRowB + 16 * kq, 16 * kXRowB, [](int c) { return 64 * c; }, acc);
-  // epilogue of stft_x6_kernel: rows 4kq + {0,1} / {2,3} = (re, im) of bins 8 mt + 2kq + {0, 1}; M-tile 0, kq 0: re of bin 0, re of bin 128.
-  // A frame staged as zeros leaves as zero magnitude, phase 1 + 0j.
+  // the offline epilogue, every frame live (one staged as zeros leaves as zero magnitude, phase 1 + 0j), but for the two roundings
+  // this kernel has always had in re^2 + im^2
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const int j = j0 + 16 * t + n;
     if (j >= total) continue;
     const int s = j / K, h = j - s * K;
-    const size_t row = ((size_t)s * rows + kKeep + h) * kBins;
-    const f32x4 v = acc[t];
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
-      float re = hh ? v.z : v.x, im = hh ? v.w : v.y;
-      const int b = 8 * mt + 2 * kq + hh;
-      if (b == 0) {
-        const float re128 = im;
-        const float m128 = fabsf(re128);
-        win[row + kBins - 1] = m128;
-        *reinterpret_cast<f32x2*>(phw + 2 * (row + kBins - 1)) = m128 > 0.f ? f32x2{re128 / m128, 0.f} : f32x2{1.f, 0.f};
-        im = 0.f;
-      }
-      const float m = sqrtf(re * re + im * im);
-      win[row + b] = m;
-      const float inv = m > 0.f ? 1.f / m : 0.f;
-      *reinterpret_cast<f32x2*>(phw + 2 * (row + b)) = m > 0.f ? f32x2{re * inv, im * inv} : f32x2{1.f, 0.f};
-    }
+    stft_store(acc[t], true, false, mt, kq, ((size_t)s * rows + kKeep + h) * kBins, win, phw);
   }
 }
 
@@ -183,10 +167,6 @@ __global__ __launch_bounds__(kThreadsX) void stream_istft_kernel(const float* __
   AFrag A;
   load_a(A, cpack, wave, lane);
   const f32x4 ci = *reinterpret_cast<const f32x4*>(cim + 16 * wave + 4 * kq);
-  float pw[kDeBlock + 1];
-  pw[0] = 1.f;
-#pragma unroll
-  for (int j = 1; j <= kDeBlock; ++j) pw[j] = pw[j - 1] * kPre;
 
   // the lanes of this workgroup: hops so far, flag (0 = leave the lane alone), the slot that holds frame 0 (or -1), the two carries
   if (tid < kFramesPerWg) {
@@ -215,71 +195,30 @@ __global__ __launch_bounds__(kThreadsX) void stream_istft_kernel(const float* __
   for (int q = 0; q < lpw; ++q) {
     const int p0 = sP0[q];
     if (p0 < 0) continue;   // (uniform over the workgroup)
-    for (int b = tid; b < kBins; b += kThreadsX) {
-      const size_t o = ((size_t)(s0w + q) * rows + p0 + 3) * kBins + b;
-      const float m = y[o];
-      const f32x2 p = *reinterpret_cast<const f32x2*>(phw + 2 * o);
-      xk[2 * b] = m * p.x;
-      xk[2 * b + 1] = m * p.y;
-    }
+    head_spectrum(xk, y, phw, ((size_t)(s0w + q) * rows + p0 + 3) * kBins, tid, kThreadsX);
     __syncthreads();
-    if (tid < kStep) {
-      float s = 0.f;
-#pragma unroll 6
-      for (int k = 0; k < 2 * kBins; ++k) s = fmaf(chead[k * kStep + tid], xk[k], s);
-      hbuf[q * kHRow + tid] = s;
-    }
+    if (tid < kStep) hbuf[q * kHRow + tid] = head_sample(chead, xk, tid);
     __syncthreads();
   }
-  if (tid < lpw && sP0[tid] >= 0) {   // their de-emphasis, y[0] = x[0]: serial, the lanes side by side
-    float run = 0.f;
-    for (int j = 0; j < kStep; ++j) {
-      run = fmaf(kPre, run, hbuf[tid * kHRow + j]);
-      hbuf[tid * kHRow + j] = run;
-    }
-    sHeadLast[tid] = run;
-  }
+  // their de-emphasis: serial, the lanes side by side
+  if (tid < lpw && sP0[tid] >= 0) sHeadLast[tid] = head_deemph(hbuf + tid * kHRow);
 
-  // stage X[slot][2b + c] = mask * (re, im) of bin b as three bf16 parts; slot 1 = re of bin 128, im of bin 128 to xim; zeros where the
-  // slot has no frame (no lane, an idle lane, a frame index below 0)
+  // stage X[slot][2b + c] of the masked spectrum as three bf16 parts, im of bin 128 to xim; zeros where the slot has no frame (no lane,
+  // an idle lane, a frame index below 0)
   for (int i = tid; i < kFramesPerWg * 128; i += kThreadsX) {
     const int fr = i >> 7, b = i & 127;
     const int q = fr / K, p = fr - q * K;
     float v0 = 0.f, v1 = 0.f, vi = 0.f;
-    if (sFlag[q] && sH[q] - kDelayHops + p >= 0) {
-      const size_t o = ((size_t)(s0w + q) * rows + p + 3) * kBins + b;
-      const float m = y[o];
-      const f32x2 ph = *reinterpret_cast<const f32x2*>(phw + 2 * o);
-      v0 = m * ph.x;
-      v1 = m * ph.y;
-      if (b == 0) {
-        const size_t o8 = o + kBins - 1;
-        const float m8 = y[o8];
-        const f32x2 p8 = *reinterpret_cast<const f32x2*>(phw + 2 * o8);
-        v1 = m8 * p8.x;
-        vi = m8 * p8.y;
-      }
-    }
+    if (sFlag[q] && sH[q] - kDelayHops + p >= 0) slot_pair(y, phw, ((size_t)(s0w + q) * rows + p + 3) * kBins + b, b, v0, v1, vi);
     if (b == 0) xim[fr] = vi;
-    const P3 q3 = split2(v0, v1);
-    char* d = xs + fr * kXRowB + b * 4;
-    *reinterpret_cast<unsigned*>(d) = q3.h;
-    *reinterpret_cast<unsigned*>(d + kXPartB) = q3.m;
-    *reinterpret_cast<unsigned*>(d + 2 * kXPartB) = q3.l;
+    put_pair(xs, kXPartB, fr * kXRowB + b * 4, v0, v1);
   }
   __syncthreads();
   f32x4 acc[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
   gemm_block(A, xs, kXPartB, n * kXRowB + 16 * kq, 16 * kXRowB, [](int c) { return 64 * c; }, acc);
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {   // + the rank-1 term of im(bin 128); rows = samples 128 + 16 wave + 4kq + j of slot 16 t + n
-    const float xi = xim[16 * t + n];
-    acc[t].x = fmaf(ci.x, xi, acc[t].x);
-    acc[t].y = fmaf(ci.y, xi, acc[t].y);
-    acc[t].z = fmaf(ci.z, xi, acc[t].z);
-    acc[t].w = fmaf(ci.w, xi, acc[t].w);
-  }
+  rank1_add(acc, ci, xim, n);
   __syncthreads();   // every wave has read its last fragment: the images are dead
 #pragma unroll
   for (int t = 0; t < 4; ++t) *reinterpret_cast<f32x4*>(obuf + (16 * t + n) * kORow + 16 * wave + 4 * kq) = acc[t];
@@ -288,50 +227,14 @@ __global__ __launch_bounds__(kThreadsX) void stream_istft_kernel(const float* __
   // de-emphasis: a blocked affine scan over the 8,192 samples in slot order (thread i: samples 16 (i & 7) .. of slot i >> 3), cut into one
   // segment per lane; a lane whose frame 0 is in this push starts at that slot from its head's last sample (the slots before it are zeros)
   {
-    const int fl = tid >> 3, c0 = kDeBlock * (tid & 7);
+    const int fl = tid >> 3;
     const int q = fl / K, p = fl - q * K;
     const bool after_head = sP0[q] >= 0 && p >= sP0[q];
     const int seg0 = (q * K + (after_head ? sP0[q] : 0)) * 8;
-    const float carry = after_head ? sHeadLast[q] : sCarry[q];
-    float yv[kDeBlock];
-    float run = 0.f;
+    f32x4 yv[kDeBlock / 4];
+    deemph_scan(obuf, sa, sb, tid, true, seg0, after_head ? sHeadLast[q] : sCarry[q], yv);
 #pragma unroll
-    for (int j4 = 0; j4 < kDeBlock / 4; ++j4) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(obuf + fl * kORow + c0 + 4 * j4);
-      run = fmaf(kPre, run, v.x);
-      yv[4 * j4] = run;
-      run = fmaf(kPre, run, v.y);
-      yv[4 * j4 + 1] = run;
-      run = fmaf(kPre, run, v.z);
-      yv[4 * j4 + 2] = run;
-      run = fmaf(kPre, run, v.w);
-      yv[4 * j4 + 3] = run;
-    }
-    float Am = pw[kDeBlock], Bm = run;   // this thread's map: y_out = Am * y_in + Bm
-    sa[tid] = Am;
-    sb[tid] = Bm;
-    __syncthreads();
-    for (int d = 1; d < kThreadsX; d <<= 1) {
-      const bool take = tid - d >= seg0;
-      float a2 = 1.f, b2 = 0.f;
-      if (take) {
-        a2 = sa[tid - d];
-        b2 = sb[tid - d];
-      }
-      __syncthreads();
-      if (take) {   // compose: (earlier map) then (mine)
-        Bm = fmaf(Am, b2, Bm);
-        Am = Am * a2;
-        sa[tid] = Am;
-        sb[tid] = Bm;
-      }
-      __syncthreads();
-    }
-    const float yin = tid == seg0 ? carry : fmaf(sa[tid - 1], carry, sb[tid - 1]);
-#pragma unroll
-    for (int j4 = 0; j4 < kDeBlock / 4; ++j4)
-      *reinterpret_cast<f32x4*>(obuf + fl * kORow + c0 + 4 * j4) = f32x4{fmaf(pw[4 * j4 + 1], yin, yv[4 * j4]), fmaf(pw[4 * j4 + 2], yin, yv[4 * j4 + 1]),
-                                                                         fmaf(pw[4 * j4 + 3], yin, yv[4 * j4 + 2]), fmaf(pw[4 * j4 + 4], yin, yv[4 * j4 + 3])};
+    for (int j4 = 0; j4 < kDeBlock / 4; ++j4) *reinterpret_cast<f32x4*>(obuf + fl * kORow + kDeBlock * (tid & 7) + 4 * j4) = yv[j4];
   }
   __syncthreads();
 

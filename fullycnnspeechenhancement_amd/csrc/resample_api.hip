@@ -18,7 +18,6 @@ using namespace rced;
 
 namespace {
 
-constexpr int kMaxDevices = 16;
 constexpr double kZero = 64.0;                     // zero crossings on either side
 constexpr double kRolloff = 0.9475937167399596;
 constexpr double kBeta = 14.769656459379492;

@@ -20,8 +20,6 @@ struct rced_rstream {
 
 namespace {
 
-constexpr int kMaxDevices = 16;   // resample_api.hip's per-device tables
-
 int launch(rced_rstream* h, const void* in, int in_frames, const int* flags, int finish, int K, void* out, int out_cols, int* out_counts,
            hipStream_t st) {
   const rstream::Plan& L = h->plan;

@@ -12,6 +12,7 @@
 
 // kernels_audio.h / kernels_audio_x6.h define their kernels with external linkage and audio_api.hip is their translation unit: this
 // one takes the headers into an unnamed namespace, so that its copies (it launches only its own two kernels) are local to it.
+// (x6_dft.h comes in with them; what it includes -- <vector>, host_util.h through rced_internal.h -- is already in, at file scope.)
 namespace {
 #include "kernels_stream.h"
 namespace audio = rced::audio;
