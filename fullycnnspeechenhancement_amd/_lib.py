@@ -15,6 +15,7 @@ RCED_OK, RCED_ERR_ARG, RCED_ERR_HIP, RCED_ERR_ALLOC, RCED_ERR_STATE = 0, 1, 2, 3
 PATH_AUTO, PATH_LAYERWISE, PATH_FUSED = 0, 1, 2
 K_GENERIC, K_FUSED, K_FINAL = 0, 1, 2
 PCM_S16, PCM_F32 = 0, 1
+STOI_CLASSIC, STOI_EXTENDED = 1, 2
 
 # every symbol include/rced.h declares: (restype, argtypes)
 _c_float_p = ctypes.POINTER(ctypes.c_float)
@@ -43,6 +44,10 @@ SYMBOLS = {
     "rced_istft_ex": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int]),
     "rced_sdr": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp]),
     "rced_stoi": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp]),
+    "rced_stoi_ex": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp,
+                                    ctypes.c_int, _vp]),
+    "rced_si_sdr": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp]),
+    "rced_seg_snr": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp]),
     "rced_mix_snr": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int,
                                     ctypes.c_double, _vp, ctypes.c_int, _vp]),
     "rced_gather_pcm": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_longlong, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,

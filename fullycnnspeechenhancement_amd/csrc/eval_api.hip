@@ -22,8 +22,9 @@ struct Workspace {
   double* p = nullptr;
   size_t bytes = 0;
 };
-enum { kWsSlices = 0, kWsStoi = 1 };      // STOI keeps a buffer of its own: it never moves the one SDR / the mix captured
-std::map<void*, Workspace> g_ws[2][kMaxDevices];
+// STOI, SI-SDR and the segmental SNR keep buffers of their own: none ever moves the one another entry's captured graph reads
+enum { kWsSlices = 0, kWsStoi = 1, kWsSiSdr = 2, kWsSegSnr = 3, kWsKinds = 4 };
+std::map<void*, Workspace> g_ws[kWsKinds][kMaxDevices];
 std::mutex g_mu;
 
 int workspace(int device, void* stream, size_t bytes, double** out, int which = kWsSlices) {
@@ -125,10 +126,13 @@ size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 extern "C" {
 
-int rced_stoi(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N, int fs_sig,
-              double* stoi_dev, int* detail_dev, int device, void* stream) {
+int rced_stoi_ex(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N, int fs_sig,
+                 int which, double* stoi_dev, double* estoi_dev, int* detail_dev, int device, void* stream) {
   if (N < 0 || ref_stride < 0 || est_stride < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
-  if (!ref_dev || !est_dev || !stoi_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
+  if (which <= 0 || (which & ~(RCED_STOI_CLASSIC | RCED_STOI_EXTENDED)))
+    return rced_fail(RCED_ERR_ARG, "which must be RCED_STOI_CLASSIC, RCED_STOI_EXTENDED or both, got %d", which);
+  const bool classic = which & RCED_STOI_CLASSIC, extended = which & RCED_STOI_EXTENDED;
+  if (!ref_dev || !est_dev || (classic && !stoi_dev) || (extended && !estoi_dev)) return rced_fail(RCED_ERR_ARG, "null pointer");
   if (fs_sig != 8000 && fs_sig != stoi::kFs) return rced_fail(RCED_ERR_ARG, "fs_sig must be 8000 or 10000, got %d", fs_sig);
   if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
   const int cap = ref_stride < est_stride ? ref_stride : est_stride;
@@ -139,13 +143,14 @@ int rced_stoi(const float* ref_dev, int ref_stride, const float* est_dev, int es
   if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
   StoiTables* t = nullptr;
   if (int rc = stoi_tables(device, &t)) return rc;
-  // workspace: r [N][2][rstride] f64 | e [N][fcap] f64 | tob [N][2][fcap][16] f64 | dseg [N][mcap] f64 | kept [N][fcap] i32 | cnt [N][4] i32
+  // workspace: r [N][2][rstride] f64 | e [N][fcap] f64 | tob [N][2][fcap][16] f64 | dseg [2][N][mcap] f64 (classic, extended) |
+  // kept [N][fcap] i32 | cnt [N][4] i32 -- one layout whatever `which` asks for: a shape's size never depends on it
   const int l10 = stoi::len10k(cap, fs_sig);
   const int fcap = stoi::num_frames(l10) > 0 ? stoi::num_frames(l10) : 1;
   const int mcap = fcap > stoi::kSeg ? fcap - stoi::kSeg : 1;
   const int rstride = (l10 + 1) & ~1;
   const size_t o_r = 0, o_e = o_r + align256((size_t)N * 2 * rstride * 8), o_tob = o_e + align256((size_t)N * fcap * 8),
-               o_d = o_tob + align256((size_t)N * 2 * fcap * 16 * 8), o_kept = o_d + align256((size_t)N * mcap * 8),
+               o_d = o_tob + align256((size_t)N * 2 * fcap * 16 * 8), o_kept = o_d + 2 * align256((size_t)N * mcap * 8),
                o_cnt = o_kept + align256((size_t)N * fcap * 4), total = o_cnt + align256((size_t)N * 4 * 4);
   double* ws = nullptr;
   if (int rc = workspace(device, stream, total, &ws, kWsStoi)) return rc;
@@ -154,6 +159,7 @@ int rced_stoi(const float* ref_dev, int ref_stride, const float* est_dev, int es
   double* e = reinterpret_cast<double*>(base + o_e);
   double* tob = reinterpret_cast<double*>(base + o_tob);
   double* dseg = reinterpret_cast<double*>(base + o_d);
+  double* dseg_ext = reinterpret_cast<double*>(base + o_d + align256((size_t)N * mcap * 8));
   int* kept = reinterpret_cast<int*>(base + o_kept);
   int* cnt = reinterpret_cast<int*>(base + o_cnt);
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -172,11 +178,89 @@ int rced_stoi(const float* ref_dev, int ref_stride, const float* est_dev, int es
                        stoi::kBandLdsBytes, st, (const double*)r, rstride, (const int*)kept, (const int*)cnt, fcap,
                        (const unsigned short*)t->apack, (const double*)t->tab, tob);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(stoi::segment_kernel, dim3((mcap + 15) / 16, N), dim3(256), 0, st, (const double*)tob, (const int*)cnt, fcap,
-                       mcap, 1.0 + std::pow(10.0, 15.0 / 20.0), dseg);
+    if (classic) {
+      hipLaunchKernelGGL(stoi::segment_kernel, dim3((mcap + 15) / 16, N), dim3(256), 0, st, (const double*)tob, (const int*)cnt, fcap,
+                         mcap, 1.0 + std::pow(10.0, 15.0 / 20.0), dseg);
+      HIP_TRY(hipGetLastError());
+    }
+    if (extended) {
+      hipLaunchKernelGGL(stoi::segment_ext_kernel, dim3((mcap + 15) / 16, N), dim3(256), 0, st, (const double*)tob, (const int*)cnt,
+                         fcap, mcap, dseg_ext);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  if (classic) {
+    hipLaunchKernelGGL(stoi::final_kernel, dim3(N), dim3(256), 0, st, (const double*)dseg, (const int*)cnt, mcap, (double)stoi::kBands,
+                       stoi_dev, detail_dev);
     HIP_TRY(hipGetLastError());
   }
-  hipLaunchKernelGGL(stoi::final_kernel, dim3(N), dim3(256), 0, st, (const double*)dseg, (const int*)cnt, mcap, stoi_dev, detail_dev);
+  if (extended) {
+    hipLaunchKernelGGL(stoi::final_kernel, dim3(N), dim3(256), 0, st, (const double*)dseg_ext, (const int*)cnt, mcap, (double)stoi::kSeg,
+                       estoi_dev, classic ? nullptr : detail_dev);
+    HIP_TRY(hipGetLastError());
+  }
+  return RCED_OK;
+}
+
+int rced_stoi(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N, int fs_sig,
+              double* stoi_dev, int* detail_dev, int device, void* stream) {
+  return rced_stoi_ex(ref_dev, ref_stride, est_dev, est_stride, lengths_dev, N, fs_sig, RCED_STOI_CLASSIC, stoi_dev, nullptr, detail_dev,
+                      device, stream);
+}
+
+int rced_si_sdr(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N,
+                double* out_dev, double* parts_dev, int device, void* stream) {
+  if (N < 0 || ref_stride < 0 || est_stride < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
+  if (!ref_dev || !est_dev || !out_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
+  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
+  const int cap = ref_stride < est_stride ? ref_stride : est_stride;
+  if (cap > eval::kMaxLen) return rced_fail(RCED_ERR_ARG, "rows longer than 2^30 samples");
+  if (N == 0) return RCED_OK;
+  if (int rc = check_device(device, kMaxDevices)) return rc;
+  DeviceGuard g(device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  const int slices = eval::num_slices(cap) > 0 ? eval::num_slices(cap) : 1;
+  const size_t pass = (size_t)N * slices * 2;            // doubles per pass: [N, slices, 2]
+  double* ws1 = nullptr;
+  if (int rc = workspace(device, stream, 2 * pass * sizeof(double), &ws1, kWsSiSdr)) return rc;
+  double* ws2 = ws1 + pass;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(eval::si_sdr_dot_kernel, dim3(slices, N), dim3(eval::kThreads), 0, st, ref_dev, ref_stride, est_dev, est_stride,
+                     lengths_dev, cap, ws1, slices);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(eval::si_sdr_energy_kernel, dim3(slices, N), dim3(eval::kThreads), 0, st, ref_dev, ref_stride, est_dev,
+                     est_stride, lengths_dev, cap, (const double*)ws1, ws2, slices);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(eval::si_sdr_final_kernel, dim3(N), dim3(eval::kThreads), 0, st, (const double*)ws1, (const double*)ws2,
+                     lengths_dev, cap, slices, out_dev, parts_dev);
+  HIP_TRY(hipGetLastError());
+  return RCED_OK;
+}
+
+int rced_seg_snr(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N, int fs,
+                 double* out_dev, int* frames_dev, int device, void* stream) {
+  if (N < 0 || ref_stride < 0 || est_stride < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
+  if (!ref_dev || !est_dev || !out_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
+  const int W = fs > 0 ? eval::seg_window(fs) : 0;
+  if (W < eval::kSegMinW || W > eval::kSegMaxW)
+    return rced_fail(RCED_ERR_ARG, "fs = %d gives frames of %d samples: outside [%d, %d]", fs, W, eval::kSegMinW, eval::kSegMaxW);
+  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
+  const int cap = ref_stride < est_stride ? ref_stride : est_stride;
+  if (cap > eval::kMaxLen) return rced_fail(RCED_ERR_ARG, "rows longer than 2^30 samples");
+  if (N == 0) return RCED_OK;
+  if (int rc = check_device(device, kMaxDevices)) return rc;
+  DeviceGuard g(device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  const int nfcap = eval::seg_frames(cap, W) > 0 ? eval::seg_frames(cap, W) : 1;
+  const int blocks = (nfcap + eval::kSegFramesPerBlock - 1) / eval::kSegFramesPerBlock;
+  double* snr = nullptr;
+  if (int rc = workspace(device, stream, (size_t)N * nfcap * sizeof(double), &snr, kWsSegSnr)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(eval::seg_snr_frame_kernel, dim3(blocks, N), dim3(eval::kThreads), 0, st, ref_dev, ref_stride, est_dev,
+                     est_stride, lengths_dev, cap, W, snr, nfcap);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(eval::seg_snr_mean_kernel, dim3(N), dim3(eval::kThreads), 0, st, (const double*)snr, lengths_dev, cap, W, nfcap,
+                     out_dev, frames_dev);
   HIP_TRY(hipGetLastError());
   return RCED_OK;
 }

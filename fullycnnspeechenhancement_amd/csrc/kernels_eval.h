@@ -1,5 +1,5 @@
 // Evaluation-loop kernels (include/rced.h, "evaluation" section): AudioParser.add_noise for a ragged batch in closed form,
-// and the per-utterance SDR.  Both are streaming reductions over ragged rows.
+// and the per-utterance SDR, SI-SDR and segmental SNR.  All are streaming reductions over ragged rows.
 //
 // One mapping for every kernel here: an utterance is cut into slices of kSlice samples; inside a slice, lane t of the
 // workgroup owns the 16-byte groups t and t + kThreads (samples 4g .. 4g+3 of the slice).  Which lane and slice an element
@@ -132,6 +132,167 @@ __global__ __launch_bounds__(64) void sdr_final_kernel(const double* __restrict_
   if (threadIdx.x == 0) {
     sdr[n] = 10.0 * log10(sy / (se + 1.1920928955078125e-07));   // np.finfo(np.float32).eps = 2^-23
     if (energies) *reinterpret_cast<double2*>(energies + (size_t)n * 2) = make_double2(sy, se);
+  }
+}
+
+// ---- SI-SDR ------------------------------------------------------------------------------------------------------
+// alpha = sum(y x) / sum(x x), then 10 log10(sum((alpha x)^2) / sum((y - alpha x)^2)), x = ref, y = est: two partial passes
+// over the SDR's slices and a final.  The one-pass form (Sxy^2 / Sxx against Syy - Sxy^2 / Sxx) cancels for good estimates
+// and is not used.  Both sums of pass 1 run in one order, so y = 2^k x gives alpha = 2^k and a residual of exactly zero.
+
+// grid (slices, N): ws1[n][s] = (sum y x, sum x x) over slice s of utterance n
+__global__ __launch_bounds__(kThreads) void si_sdr_dot_kernel(const float* __restrict__ ref, int ref_stride,
+                                                              const float* __restrict__ est, int est_stride,
+                                                              const int* __restrict__ lengths, int cap,
+                                                              double* __restrict__ ws1, int slices) {
+  __shared__ double red[kWaves][2];
+  const int n = blockIdx.y, s = blockIdx.x;
+  const int len = clamp_len(lengths, n, cap);
+  const int base = s * kSlice;
+  if (base >= len) return;
+  const float* r = ref + (size_t)n * ref_stride;
+  const float* e = est + (size_t)n * est_stride;
+  const bool rvec = aligned16(r), evec = aligned16(e);
+  double sxy = 0.0, sxx = 0.0;
+#pragma unroll
+  for (int j = 0; j < kGroupsPerLane; ++j) {
+    const int p = base + (j * kThreads + threadIdx.x) * 4;
+    if (p < len) {
+      float a[4], b[4];
+      load4(r, p, len, rvec, a);
+      load4(e, p, len, evec, b);
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (p + k < len) {
+          const double x = a[k], y = b[k];
+          sxy += y * x;
+          sxx += x * x;
+        }
+    }
+  }
+  block_sum2<kWaves>(sxy, sxx, red);
+  if (threadIdx.x == 0) *reinterpret_cast<double2*>(ws1 + ((size_t)n * slices + s) * 2) = make_double2(sxy, sxx);
+}
+
+// grid (slices, N): every workgroup sums its utterance's pass-1 partials itself (in slice order: the same alpha in every
+// workgroup and in the final), then ws2[n][s] = (sum (alpha x)^2, sum (y - alpha x)^2) over its slice.  alpha x is rounded
+// before the subtraction, as numpy rounds it (no fused multiply-subtract).
+__global__ __launch_bounds__(kThreads) void si_sdr_energy_kernel(const float* __restrict__ ref, int ref_stride,
+                                                                 const float* __restrict__ est, int est_stride,
+                                                                 const int* __restrict__ lengths, int cap,
+                                                                 const double* __restrict__ ws1, double* __restrict__ ws2,
+                                                                 int slices) {
+  __shared__ double red[kWaves][2];
+  const int n = blockIdx.y, s = blockIdx.x;
+  const int len = clamp_len(lengths, n, cap);
+  const int base = s * kSlice;
+  if (base >= len) return;
+  double sxy, sxx;
+  sum_partials<kWaves>(ws1, n, slices, num_slices(len), sxy, sxx, red);
+  const double alpha = sxy / sxx;
+  const float* r = ref + (size_t)n * ref_stride;
+  const float* e = est + (size_t)n * est_stride;
+  const bool rvec = aligned16(r), evec = aligned16(e);
+  double st = 0.0, sn = 0.0;
+#pragma unroll
+  for (int j = 0; j < kGroupsPerLane; ++j) {
+    const int p = base + (j * kThreads + threadIdx.x) * 4;
+    if (p < len) {
+      float a[4], b[4];
+      load4(r, p, len, rvec, a);
+      load4(e, p, len, evec, b);
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (p + k < len) {
+          const double t = __dmul_rn(alpha, (double)a[k]), d = (double)b[k] - t;
+          st += t * t;
+          sn += d * d;
+        }
+    }
+  }
+  block_sum2<kWaves>(st, sn, red);
+  if (threadIdx.x == 0) *reinterpret_cast<double2*>(ws2 + ((size_t)n * slices + s) * 2) = make_double2(st, sn);
+}
+
+// grid (N), kThreads: both sets of partials in the order the energy pass summed the first.  x = 0, y = 0 or a length of 0
+// give nan (0 / 0), a zero residual gives +inf, as numpy does.  parts: NULL or [N][3] = alpha, sum (alpha x)^2, sum (y - alpha x)^2
+__global__ __launch_bounds__(kThreads) void si_sdr_final_kernel(const double* __restrict__ ws1, const double* __restrict__ ws2,
+                                                                const int* __restrict__ lengths, int cap, int slices,
+                                                                double* __restrict__ out, double* __restrict__ parts) {
+  __shared__ double red[kWaves][2];
+  const int n = blockIdx.x;
+  const int nsl = num_slices(clamp_len(lengths, n, cap));
+  double sxy, sxx, st, sn;
+  sum_partials<kWaves>(ws1, n, slices, nsl, sxy, sxx, red);
+  sum_partials<kWaves>(ws2, n, slices, nsl, st, sn, red);
+  if (threadIdx.x == 0) {
+    out[n] = 10.0 * log10(st / sn);
+    if (parts) {
+      parts[(size_t)n * 3] = sxy / sxx;
+      parts[(size_t)n * 3 + 1] = st;
+      parts[(size_t)n * 3 + 2] = sn;
+    }
+  }
+}
+
+// ---- segmental SNR -----------------------------------------------------------------------------------------------
+// Frames of W = (3 fs + 50) / 100 samples at hop W / 4 under w[j] = 0.5 (1 - cos(2 pi (j + 1) / (W + 1))); per frame
+// 10 log10(sum (w x)^2 / (sum (w (x - y))^2 + eps) + eps) clamped to [-10, 35]; the mean over the frames.
+
+constexpr int kSegMinW = 4, kSegMaxW = 1440;
+constexpr int kSegFramesPerBlock = 16;                  // four per wave
+constexpr double kEps64 = 2.220446049250313e-16;        // np.finfo(float).eps
+
+__host__ __device__ inline int seg_window(int fs) { return (int)((3ll * fs + 50) / 100); }
+__host__ __device__ inline int seg_frames(int len, int W) { return len >= W ? (len - W) / (W / 4) + 1 : 0; }
+
+// grid (ceil(nfcap / 16), N), 4 waves: wave w takes frames 16 bx + w, + 4, + 8, + 12.  Lane l of the wave owns samples l, l + 64, ...
+// of the frame, summed in index order, then the xor butterfly.  Every load is a scalar load.  snr: [N][nfcap], clamped
+__global__ __launch_bounds__(kThreads) void seg_snr_frame_kernel(const float* __restrict__ ref, int ref_stride,
+                                                                 const float* __restrict__ est, int est_stride,
+                                                                 const int* __restrict__ lengths, int cap, int W,
+                                                                 double* __restrict__ snr, int nfcap) {
+  __shared__ double win[kSegMaxW];
+  const int n = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int H = W / 4;
+  const int nf = seg_frames(clamp_len(lengths, n, cap), W);
+  const int f0 = blockIdx.x * kSegFramesPerBlock;
+  if (f0 >= nf) return;                                  // uniform over the workgroup
+  for (int j = threadIdx.x; j < W; j += kThreads) win[j] = 0.5 * (1.0 - cos(2.0 * M_PI * (double)(j + 1) / (double)(W + 1)));
+  __syncthreads();
+  const float* r = ref + (size_t)n * ref_stride;
+  const float* e = est + (size_t)n * est_stride;
+  for (int f = f0 + wave; f < f0 + kSegFramesPerBlock && f < nf; f += kWaves) {   // uniform over the wave
+    const float* x = r + (size_t)f * H;                  // f H + W <= (nf - 1) H + W <= len
+    const float* y = e + (size_t)f * H;
+    double ss = 0.0, sn = 0.0;
+    for (int j = lane; j < W; j += 64) {
+      const double a = x[j], wx = win[j] * a, wd = win[j] * (a - (double)y[j]);
+      ss += wx * wx;
+      sn += wd * wd;
+    }
+    ss = wave_sum(ss);
+    sn = wave_sum(sn);
+    if (lane == 0) {
+      const double s = 10.0 * log10(ss / (sn + kEps64) + kEps64);
+      snr[(size_t)n * nfcap + f] = s < -10.0 ? -10.0 : (s > 35.0 ? 35.0 : s);
+    }
+  }
+}
+
+// grid (N), kThreads: lane t takes frames t, t + kThreads, ..., then block_sum2; no frame gives nan.  frames: NULL or [N] = nf
+__global__ __launch_bounds__(kThreads) void seg_snr_mean_kernel(const double* __restrict__ snr, const int* __restrict__ lengths,
+                                                                int cap, int W, int nfcap, double* __restrict__ out,
+                                                                int* __restrict__ frames) {
+  __shared__ double red[kWaves][2];
+  const int n = blockIdx.x;
+  const int nf = seg_frames(clamp_len(lengths, n, cap), W);
+  double s = 0.0, z = 0.0;
+  for (int f = threadIdx.x; f < nf; f += kThreads) s += snr[(size_t)n * nfcap + f];
+  block_sum2<kWaves>(s, z, red);
+  if (threadIdx.x == 0) {
+    out[n] = nf > 0 ? s / (double)nf : __longlong_as_double(0x7ff8000000000000ll);
+    if (frames) frames[n] = nf;
   }
 }
 

@@ -1,5 +1,6 @@
-// STOI (Taal, Hendriks, Heusdens, Jensen 2011) per utterance for a ragged batch, on the device (include/rced.h, "evaluation" section;
-// the specification, stage by stage, is in DESIGN.md).  Six launches on one stream:
+// STOI (Taal, Hendriks, Heusdens, Jensen 2011) and ESTOI (Jensen, Taal 2016) per utterance for a ragged batch, on the device
+// (include/rced.h, "evaluation" section; the specification, stage by stage, is in DESIGN.md).  Six launches on one stream for either
+// score, eight for both (stages 1-4 run once):
 //   1. resample_kernel  8 kHz -> 10 kHz polyphase (5/4, 365 fp64 taps from the host), both signals, fp64 out        [or a widening copy]
 //   2. energy_kernel    20 log10(|| hann * frame || + eps) of every clean frame (256 samples, hop 128), one wave per frame
 //   3. mask_kernel      per utterance: max energy, the 40 dB mask, its exclusive scan -> the list of kept frames; (F, K, M)
@@ -8,7 +9,8 @@
 //                       fp32 accumulators -- x6_dft.h, the GEMM of kernels_audio_x6.h.  The epilogue squares the accumulators in fp64 and sums them
 //                       per one-third-octave band: spectra never reach memory, only sqrt(band power) [frame][15] does.
 //   5. segment_kernel   one thread per (segment of 30 frames, band): normalise, clip, centre, correlate -- fp64
-//   6. final_kernel     the mean over segments and bands; 1e-5 where fewer than 30 spectral frames exist
+//      segment_ext_kernel  the extended form on the same thread map: rows normalised in registers, columns across 16 lanes -- fp64
+//   6. final_kernel     the mean over segments and bands (or frames); 1e-5 where fewer than 30 spectral frames exist
 // Everything but the DFT products is fp64 from the fp32 inputs.  The invariants of kernels_eval.h hold: no atomics; every sum in one
 // fixed order that depends on positions inside the utterance only (never on N, the row, the neighbours or the strides: every load of
 // the inputs is a scalar load); samples past a length are never read; all scratch lives in a caller-provided workspace.
@@ -278,9 +280,78 @@ __global__ __launch_bounds__(256) void segment_kernel(const double* __restrict__
   }
 }
 
+// ---- 5x. segments, extended (ESTOI: Jensen & Taal 2016) ---------------------------------------------------------------------------
+// The same grid and thread map as segment_kernel: thread (segment = tid >> 4, band = tid & 15), the 16 band-threads of a segment in
+// 16 consecutive lanes; lane 15 (no band) and the lanes of segments past M hold zeros and take part in every shuffle.  No clipping,
+// no scaling.  Summation order, all fp64:
+//   rows     (band over the 30 frames): mean and squared norm in the thread's registers, frames 0 .. 29 in order;
+//   columns  (frame over the 15 bands): a butterfly over the 16 lanes of the segment, one DPP row, in four steps -- lane ^ 1, lane ^ 2
+//            (quad permutes), then the mirror of its 8 lanes, then the mirror of the 16: pairs, quads, halves, the row (each fp64
+//            travels as its two 32-bit halves; a + b and b + a are the same sum, so all 16 lanes end with the same bits), lane 15
+//            adding zero;
+//   segment  sum of xn * yn: per thread over frames 0 .. 29 in order, then the same butterfly over the bands.
+// dseg: [N][mcap], the sum over the 30 frames and 15 bands.
+template <int kCtrl>
+__device__ inline double dpp_add(double v) {   // v + the v of the lane kCtrl names; every lane of the row is active
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), kCtrl, 0xf, 0xf, true);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), kCtrl, 0xf, 0xf, true);
+  return v + __hiloint2double(hi, lo);
+}
+__device__ inline double band_sum16(double v) {
+  v = dpp_add<0xB1>(v);      // quad_perm [1, 0, 3, 2]
+  v = dpp_add<0x4E>(v);      // quad_perm [2, 3, 0, 1]
+  v = dpp_add<0x141>(v);     // row_half_mirror
+  return dpp_add<0x140>(v);  // row_mirror
+}
+
+__global__ __launch_bounds__(256) void segment_ext_kernel(const double* __restrict__ tob, const int* __restrict__ cnt, int fcap, int mcap,
+                                                          double* __restrict__ dseg) {
+  const int n = blockIdx.y, band = threadIdx.x & 15, sl = threadIdx.x >> 4;
+  const int seg = blockIdx.x * 16 + sl;
+  const int M = cnt[(size_t)n * 4 + 2];
+  if (blockIdx.x * 16 >= M) return;                                             // uniform
+  const bool live = seg < M && band < kBands;
+  const double* px = tob + ((size_t)n * 2) * fcap * 16 + (size_t)(live ? seg : 0) * 16 + (live ? band : 0);
+  const double* py = px + (size_t)fcap * 16;
+  double xs[kSeg], ys[kSeg];
+  double mx = 0.0, my = 0.0;
+#pragma unroll
+  for (int t = 0; t < kSeg; ++t) {
+    xs[t] = live ? px[t * 16] : 0.0;
+    ys[t] = live ? py[t * 16] : 0.0;
+    mx += xs[t];
+    my += ys[t];
+  }
+  mx /= kSeg;
+  my /= kSeg;
+  double nx = 0.0, ny = 0.0;
+#pragma unroll
+  for (int t = 0; t < kSeg; ++t) {
+    xs[t] -= mx;
+    ys[t] -= my;
+    nx += xs[t] * xs[t];
+    ny += ys[t] * ys[t];
+  }
+  nx = sqrt(nx) + kEps;
+  ny = sqrt(ny) + kEps;
+  double d = 0.0;
+#pragma unroll
+  for (int t = 0; t < kSeg; ++t) {
+    double x = xs[t] / nx, y = ys[t] / ny;                                      // 0 in the lanes that are not live
+    const double cx = band_sum16(x) / kBands, cy = band_sum16(y) / kBands;
+    x = live ? x - cx : 0.0;
+    y = live ? y - cy : 0.0;
+    const double qx = sqrt(band_sum16(x * x)) + kEps, qy = sqrt(band_sum16(y * y)) + kEps;
+    d += (x / qx) * (y / qy);
+  }
+  d = band_sum16(d);
+  if (band == 0 && seg < M) dseg[(size_t)n * mcap + seg] = d;
+}
+
 // ---- 6. the mean ----------------------------------------------------------------------------------------------------------------
-// grid (N), 256 threads: lane t takes segments t, t + 256, ..., then the block sum of kernels_eval.h
-__global__ __launch_bounds__(256) void final_kernel(const double* __restrict__ dseg, const int* __restrict__ cnt, int mcap,
+// grid (N), 256 threads: lane t takes segments t, t + 256, ..., then the block sum of kernels_eval.h.  per: what one segment's sum is
+// a sum of per unit of score -- the 15 bands (classic) or the 30 frames (extended).
+__global__ __launch_bounds__(256) void final_kernel(const double* __restrict__ dseg, const int* __restrict__ cnt, int mcap, double per,
                                                     double* __restrict__ out, int* __restrict__ detail) {
   __shared__ double red[4][2];
   const int n = blockIdx.x;
@@ -289,7 +360,7 @@ __global__ __launch_bounds__(256) void final_kernel(const double* __restrict__ d
   for (int m = threadIdx.x; m < M; m += 256) s += dseg[(size_t)n * mcap + m];
   eval::block_sum2<4>(s, z, red);
   if (threadIdx.x == 0) {
-    out[n] = M > 0 ? s / ((double)kBands * (double)M) : 1e-5;
+    out[n] = M > 0 ? s / (per * (double)M) : 1e-5;
     if (detail) {
       detail[(size_t)n * 3] = cnt[(size_t)n * 4];
       detail[(size_t)n * 3 + 1] = cnt[(size_t)n * 4 + 1];

@@ -3,13 +3,14 @@
 Reference: BaseTester / FullyCNNTester (model_utils/tester.py:18-90) and InferenceEngine
 (infer.py:19-52): read cfg -> creat_graph() -> _init_session() -> _load_checkpoint() ->
 test_step(ndarray[N,T,129,1]) -> ndarray[N,T,129,1], and the evaluation loop over it (tester.py:92-167):
-`evaluate_pcm` / `test` take ragged PCM through STFT -> net -> ISTFT rebuild -> SDR (and STOI, on request) on the device.
+`evaluate_pcm` / `test` take ragged PCM through STFT -> net -> ISTFT rebuild -> SDR (and STOI, ESTOI, SI-SDR, segmental SNR on request) on the device.
 PESQ scoring and the evaluation loop's wav files are not mirrored; the manifest-driven DataLoader is loader.DataLoader (batches built on the device).
 """
 
 import numpy as np
 
 from . import model as _model, spec, weights as _weights
+from .evaluation import EXTRA_METRICS, check_extra
 from .metrics import AverageMeter
 
 
@@ -44,6 +45,7 @@ class FullyCNNTester(object):
         self._weights = weights
         self.sdr_score = AverageMeter()     # tester.py:63; test() adds to it and never resets it, as there
         self.stoi_score = AverageMeter()    # tester.py:62; filled by test(..., stoi=True)
+        self.extra_scores = {name: AverageMeter() for name in EXTRA_METRICS}    # filled by test(..., extra=(names))
         self.creat_graph()
         self._load_checkpoint()
 
@@ -82,35 +84,48 @@ class FullyCNNTester(object):
             pool[2] ^= 1
         return self.model(input_x, out=out) if out is not None else self.model(input_x)
 
-    def evaluate_pcm(self, mix_sig, clean_sig, nfft=512, model=None, lengths=None, kernels="x6", stoi=False):
+    def evaluate_pcm(self, mix_sig, clean_sig, nfft=512, model=None, lengths=None, kernels="x6", stoi=False, extra=()):
         """One batch of the evaluation loop (tester.py:100-146) from PCM, on the device: the module's evaluate_pcm with
         this engine's network, or with `model` (a callable, device [N, T, 129, 1] -> same) in its place."""
         return evaluate_pcm(model if model is not None else self.model, mix_sig, clean_sig, nfft, self.device, lengths, kernels,
-                            stoi=stoi)
+                            stoi=stoi, extra=extra)
 
-    def test(self, valid_loader, stoi=False):
+    def test(self, valid_loader, stoi=False, extra=()):
         """tester.py:92-167 over anything that yields the reference's 4-tuple (batch_mix, batch_clean, mix_sig,
         clean_sig): every batch goes through evaluate_pcm(mix_sig, clean_sig), every utterance's SDR into
         self.sdr_score (an AverageMeter); prints the reference's summary line with its SDR field and returns the
         average.  The spectrogram is recomputed on the device from mix_sig (equal to batch_mix within the STFT's
         pinned 2e-6 of the scale), so batch_mix / batch_clean are not read.  With stoi=True every utterance's STOI goes
         into self.stoi_score as well and the line gains the reference's st_score field, in the reference's order.
+        extra: names from evaluation.EXTRA_METRICS ("estoi", "si_sdr", "seg_snr"); every utterance's score goes into
+        self.extra_scores[name], and one further line with their averages follows the reference's.
         PESQ and the wav files the reference writes next to the scores are not built."""
+        extra = check_extra(extra)
         for _batch_mix, _batch_clean, mix_sig, clean_sig in valid_loader:
-            scores = self.evaluate_pcm(mix_sig, clean_sig, stoi=stoi)
+            scores = self.evaluate_pcm(mix_sig, clean_sig, stoi=stoi, extra=extra)
             for score in scores[1]:
                 self.sdr_score.update(float(score))
             if stoi:
                 for score in scores[2]:
                     self.stoi_score.update(float(score))
+            for name in extra:
+                for score in scores[-1][name]:
+                    self.extra_scores[name].update(float(score))
         if stoi:
             print("Average st_score: {:.4f}; Average sd_score: {:.4f}.\n".format(self.stoi_score.avg, self.sdr_score.avg))
         else:
             print("Average sd_score: {:.4f}.\n".format(self.sdr_score.avg))
+        if extra:
+            print(extra_line(extra, self.extra_scores))
         return self.sdr_score.avg
 
 
-def evaluate_pcm(forward, mix_sig, clean_sig, nfft=512, device=0, lengths=None, kernels="x6", stoi=False):
+def extra_line(extra, meters):
+    """The line test() and valid() add under the reference's when extra scores were asked for."""
+    return "; ".join("Average {}: {:.4f}".format(name, meters[name].avg) for name in extra) + ".\n"
+
+
+def evaluate_pcm(forward, mix_sig, clean_sig, nfft=512, device=0, lengths=None, kernels="x6", stoi=False, extra=()):
     """What FullyCNNTester.test and FullyCNNTrainer.valid do with one batch (tester.py:104-146, trainer.py:264-307), each
     with its own forward (device [N, T, 129, 1] -> same): one upload, STFT with the lengths -> forward -> ISTFT rebuild
     (AudioReBuild(nfft), 512 as the reference ships it) -> SDR against the clean rows; the audio and N scores come back.
@@ -119,15 +134,22 @@ def evaluate_pcm(forward, mix_sig, clean_sig, nfft=512, device=0, lengths=None, 
     device rows that carry their lengths: the device loader's batches, scored where they lie).  kernels: the STFT / ISTFT
     kernel family, as in audio.stft_batch.
     Returns (denoise: list of numpy float32, row i trimmed to its length; sdr: numpy float64 [N]); with stoi=True a third
-    element, STOI per utterance (numpy float64 [N], audio.stoi_batch of the rebuilt audio against the clean rows)."""
+    element, STOI per utterance (numpy float64 [N], audio.stoi_batch of the rebuilt audio against the clean rows).
+    extra: names from evaluation.EXTRA_METRICS ("estoi", "si_sdr", "seg_snr"; anything else is a ValueError before any
+    device work).  With extra non-empty the tuple gains one last element, a dict name -> numpy float64 [N]
+    (audio.stoi_batch(extended=True), audio.si_sdr_batch, audio.seg_snr_batch of the same pairs)."""
+    extra = check_extra(extra)
     import torch
     from . import _args, audio
+    empty = ([], np.zeros(0, np.float64)) + ((np.zeros(0, np.float64),) if stoi else ())
+    if extra:
+        empty += ({name: np.zeros(0, np.float64) for name in extra},)
     if hasattr(mix_sig, "rows") and hasattr(clean_sig, "rows"):      # loader.PcmRows: what the device loader yields
         if len(mix_sig) != len(clean_sig) or list(mix_sig.lengths) != list(clean_sig.lengths):
             raise ValueError("mix_sig and clean_sig must pair up, utterance by utterance and sample by sample")
         lens = [int(v) for v in clean_sig.lengths]
         if not lens:
-            return ([], np.zeros(0, np.float64), np.zeros(0, np.float64)) if stoi else ([], np.zeros(0, np.float64))
+            return empty
         mix, clean = mix_sig.rows, clean_sig.rows
     elif hasattr(mix_sig, "is_cuda"):
         if lengths is None:
@@ -139,16 +161,17 @@ def evaluate_pcm(forward, mix_sig, clean_sig, nfft=512, device=0, lengths=None, 
         if len(mix_sig) != len(lens) or any(len(m) != n for m, n in zip(mix_sig, lens)):
             raise ValueError("mix_sig and clean_sig must pair up, utterance by utterance and sample by sample")
         if not lens:
-            return ([], np.zeros(0, np.float64), np.zeros(0, np.float64)) if stoi else ([], np.zeros(0, np.float64))
+            return empty
         both = np.zeros((2, len(lens), max(lens)), np.float32)
         for i, n in enumerate(lens):
             both[0, i, :n] = mix_sig[i]
             both[1, i, :n] = clean_sig[i]
         both = torch.as_tensor(both, device="cuda:%d" % device)
         mix, clean = both[0], both[1]
-    scored = audio.denoise_and_score(forward, mix, clean, lens, nfft, kernels, stoi=stoi)
+    scored = audio.denoise_and_score(forward, mix, clean, lens, nfft, kernels, stoi=stoi, extra=extra)
     audio_host = scored[0].cpu().numpy()
-    return ([audio_host[i, :lens[i]].copy() for i in range(len(lens))],) + tuple(s.cpu().numpy() for s in scored[1:])
+    host = lambda s: {k: v.cpu().numpy() for k, v in s.items()} if isinstance(s, dict) else s.cpu().numpy()      # noqa: E731
+    return ([audio_host[i, :lens[i]].copy() for i in range(len(lens))],) + tuple(host(s) for s in scored[1:])
 
 
 class InferenceEngine(FullyCNNTester):

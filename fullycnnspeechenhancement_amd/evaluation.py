@@ -1,5 +1,5 @@
-"""The evaluation loop's entry points on the device, over the C ABI: SDR and STOI per utterance,
-add_noise's SNR mixing in closed form, and the core of the loop, STFT -> forward -> ISTFT -> scores.  audio.py re-exports
+"""The evaluation loop's entry points on the device, over the C ABI: SDR, STOI, ESTOI, SI-SDR and
+segmental SNR per utterance, add_noise's SNR mixing in closed form, and the core of the loop, STFT -> forward -> ISTFT -> scores.  audio.py re-exports
 every public name here."""
 
 import numpy as np
@@ -25,23 +25,97 @@ def sdr_batch(clean, estimate, lengths=None):
 STOI_RATES = (8000, 10000)
 
 
-def stoi_batch(clean, estimate, lengths=None, sample_rate=8000, detail=False):
+def stoi_batch(clean, estimate, lengths=None, sample_rate=8000, detail=False, extended=False):
     """STOI (Taal et al. 2011; the reference's pystoi.stoi(clean, denoise, sr, extended=False), tester.py:92-167) per utterance
     on the device, as DESIGN.md "STOI" specifies it.  clean [N, Lc], estimate [N, Le], lengths: as in sdr_batch (the estimate
     may be istft_batch's buffer as it is).  sample_rate: 8000 (resampled to 10 kHz on the device) or 10000.
-    Returns torch.float64 [N] on the device, current stream; with detail=True also torch.int32 [N, 3]: frames at 10 kHz,
-    frames kept by the 40 dB silent-frame removal, 30-frame segments (0 segments: the score is 1e-5)."""
+    extended: False = STOI; True = ESTOI (Jensen, Taal 2016, DESIGN.md "ESTOI") in its place; "both" = (stoi, estoi) from one
+    call that resamples, removes silent frames and takes the band spectra once.
+    Returns torch.float64 [N] on the device, current stream (two of them for "both"); with detail=True also, last,
+    torch.int32 [N, 3]: frames at 10 kHz, frames kept by the 40 dB silent-frame removal, 30-frame segments (0 segments: the
+    score is 1e-5)."""
     import torch
     if int(sample_rate) not in STOI_RATES:
         raise ValueError("sample_rate must be 8000 or 10000, got %r" % (sample_rate,))
+    if not (extended is False or extended is True or extended == "both"):
+        raise ValueError("extended must be False, True or 'both', got %r" % (extended,))
+    clean, estimate, n, dev, sc, se, ldev = _args.scoring_args(clean, estimate, lengths)
+    det = torch.empty((n, 3), dtype=torch.int32, device=dev) if detail else None
+    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+    if extended is False:
+        out = torch.empty((n,), dtype=torch.float64, device=dev)
+        if n:
+            _lib.check(_lib.load().rced_stoi(clean.data_ptr(), sc, estimate.data_ptr(), se, ptr(ldev), n, int(sample_rate),
+                                             out.data_ptr(), ptr(det), dev.index, _args.current_stream(dev)))
+        return (out, det) if detail else out
+    classic = torch.empty((n,), dtype=torch.float64, device=dev) if extended == "both" else None
+    ext = torch.empty((n,), dtype=torch.float64, device=dev)
+    if n:
+        which = _lib.STOI_EXTENDED | (_lib.STOI_CLASSIC if classic is not None else 0)
+        _lib.check(_lib.load().rced_stoi_ex(clean.data_ptr(), sc, estimate.data_ptr(), se, ptr(ldev), n, int(sample_rate), which,
+                                            ptr(classic), ext.data_ptr(), ptr(det), dev.index, _args.current_stream(dev)))
+    scores = (classic, ext) if classic is not None else (ext,)
+    if detail:
+        return scores + (det,)
+    return scores if classic is not None else ext
+
+
+def si_sdr_batch(clean, estimate, lengths=None):
+    """SI-SDR per utterance on the device (DESIGN.md "SI-SDR": alpha = sum(y x) / sum(x x), 10 log10(sum((alpha x)^2) /
+    sum((y - alpha x)^2)), two passes, no mean removal).  Arguments as in sdr_batch.  Returns torch.float64 [N] (dB) on the
+    device, current stream; +inf where the estimate is a power-of-two multiple of the clean row, nan for an all-zero row or
+    a length of 0."""
+    import torch
     clean, estimate, n, dev, sc, se, ldev = _args.scoring_args(clean, estimate, lengths)
     out = torch.empty((n,), dtype=torch.float64, device=dev)
-    det = torch.empty((n, 3), dtype=torch.int32, device=dev) if detail else None
     if n:
-        _lib.check(_lib.load().rced_stoi(clean.data_ptr(), sc, estimate.data_ptr(), se, ldev.data_ptr() if ldev is not None else None,
-                                         n, int(sample_rate), out.data_ptr(), det.data_ptr() if det is not None else None, dev.index,
-                                         _args.current_stream(dev)))
-    return (out, det) if detail else out
+        _lib.check(_lib.load().rced_si_sdr(clean.data_ptr(), sc, estimate.data_ptr(), se, ldev.data_ptr() if ldev is not None else None,
+                                           n, out.data_ptr(), None, dev.index, _args.current_stream(dev)))
+    return out
+
+
+SEG_SNR_WINDOW = (4, 1440)
+
+
+def seg_snr_window(sample_rate):
+    """Samples per frame of the segmental SNR at a rate, (3 sr + 50) // 100 (30 ms); ValueError where the library refuses it."""
+    sr = int(sample_rate)
+    w = (3 * sr + 50) // 100 if sr > 0 else 0
+    if sr != sample_rate or not SEG_SNR_WINDOW[0] <= w <= SEG_SNR_WINDOW[1]:
+        raise ValueError("sample_rate %r gives frames of %d samples: outside [%d, %d]" % ((sample_rate, w) + SEG_SNR_WINDOW))
+    return w
+
+
+def seg_snr_batch(clean, estimate, lengths=None, sample_rate=8000, detail=False):
+    """Segmental SNR per utterance on the device (DESIGN.md "Segmental SNR": 30 ms Hann-windowed frames at a quarter-frame
+    hop, each frame's SNR clamped to [-10, 35] dB, the mean over the frames).  Arguments as in sdr_batch; sample_rate: any
+    rate whose frame has 4 .. 1440 samples.  Returns torch.float64 [N] (dB) on the device, current stream -- nan for an
+    utterance shorter than one frame; with detail=True also torch.int32 [N], the frames of each utterance."""
+    import torch
+    seg_snr_window(sample_rate)
+    clean, estimate, n, dev, sc, se, ldev = _args.scoring_args(clean, estimate, lengths)
+    out = torch.empty((n,), dtype=torch.float64, device=dev)
+    frames = torch.empty((n,), dtype=torch.int32, device=dev) if detail else None
+    if n:
+        _lib.check(_lib.load().rced_seg_snr(clean.data_ptr(), sc, estimate.data_ptr(), se, ldev.data_ptr() if ldev is not None else None,
+                                            n, int(sample_rate), out.data_ptr(), frames.data_ptr() if detail else None, dev.index,
+                                            _args.current_stream(dev)))
+    return (out, frames) if detail else out
+
+
+EXTRA_METRICS = ("estoi", "si_sdr", "seg_snr")
+
+
+def check_extra(extra):
+    """The evaluation loop's `extra` argument as a tuple of names from EXTRA_METRICS, in the caller's order; ValueError for
+    anything else.  Touches no device."""
+    names = (extra,) if isinstance(extra, str) else tuple(extra)
+    for name in names:
+        if name not in EXTRA_METRICS:
+            raise ValueError("extra names must come from %r, got %r" % (EXTRA_METRICS, name))
+    if len(set(names)) != len(names):
+        raise ValueError("extra names must be distinct, got %r" % (names,))
+    return names
 
 
 def gains_needed(len_speech, len_noise):
@@ -107,17 +181,30 @@ def mix_snr_batch(speech, noise, snr, speech_lengths=None, noise_lengths=None, s
     return mix
 
 
-def denoise_and_score(forward, mix, clean, lengths, nfft=512, kernels="x6", stoi=False):
+def denoise_and_score(forward, mix, clean, lengths, nfft=512, kernels="x6", stoi=False, extra=()):
     """The device core of the evaluation loop (tester.py:100-146 / trainer.py:260-307 without PESQ / wav files):
     STFT of the mixtures -> forward (device [N, T, 129, 1] -> same) -> ISTFT rebuild -> SDR (and, with stoi=True, STOI) of
     every rebuilt row against its clean row over its own length.  mix, clean: torch.cuda float32 [N, L] zero-padded;
-    lengths: N sample counts.
+    lengths: N sample counts.  extra: names from EXTRA_METRICS, further scores of the same pairs.
     Returns (audio [N, (T+1)*128] on the device -- the caller trims row n to lengths[n] --, sdr torch.float64 [N]), with
-    stoi=True (audio, sdr, stoi torch.float64 [N])."""
+    stoi=True (audio, sdr, stoi torch.float64 [N]); with extra, one more element last: a dict name -> torch.float64 [N]
+    (STOI and ESTOI, asked for together, come from one rced_stoi_ex call)."""
     from . import audio
+    extra = check_extra(extra)
     mag, phase = audio.stft_batch(mix, lengths, kernels=kernels)
     pred = forward(mag)
     out = audio.istft_batch(pred, phase, nfft, kernels=kernels)
-    if stoi:
-        return out, sdr_batch(clean, out, lengths), stoi_batch(clean, out, lengths, SAMPLE_RATE)
-    return out, sdr_batch(clean, out, lengths)
+    scored = (out, sdr_batch(clean, out, lengths))
+    more = {}
+    if stoi and "estoi" in extra:
+        st, more["estoi"] = stoi_batch(clean, out, lengths, SAMPLE_RATE, extended="both")
+        scored += (st,)
+    elif stoi:
+        scored += (stoi_batch(clean, out, lengths, SAMPLE_RATE),)
+    elif "estoi" in extra:
+        more["estoi"] = stoi_batch(clean, out, lengths, SAMPLE_RATE, extended=True)
+    if "si_sdr" in extra:
+        more["si_sdr"] = si_sdr_batch(clean, out, lengths)
+    if "seg_snr" in extra:
+        more["seg_snr"] = seg_snr_batch(clean, out, lengths, SAMPLE_RATE)
+    return scored + ({name: more[name] for name in extra},) if extra else scored

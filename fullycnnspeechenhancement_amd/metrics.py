@@ -4,6 +4,9 @@ AverageMeter is plain Python.  SDR keeps the reference's call surface -- `SDR()(
 out -- and computes on the device (rced_sdr); a batch is scored without leaving the device by `audio.sdr_batch`.
 STOI does the same over rced_stoi / `audio.stoi_batch`; the reference takes it from pystoi, which this project cannot
 reach: parity is pinned to the restatement of the published algorithm in tests/stoi_np.py (DESIGN.md "STOI").
+ESTOI (pystoi's extended=True), SISDR (the optimal-scaling form the reference carries, commented out, inside SDR.sdr,
+utils.py:80-85) and SegSNR have the same call surface over rced_stoi_ex / rced_si_sdr / rced_seg_snr; each is pinned to the
+float64 restatement of its definition in tests/ (DESIGN.md "ESTOI", "SI-SDR", "Segmental SNR"), not to pystoi or pysepm.
 PESQ is not built (the reference takes it from pypesq).
 """
 
@@ -77,3 +80,78 @@ class STOI(object):
 
     def __call__(self, x, y):
         return self.stoi(x, y)
+
+
+def _pair(x, y):
+    """Two 1-D signals of one length, as STOI takes them, stacked [2, L] float32."""
+    x, y = np.asarray(x), np.asarray(y)
+    if len(x.shape) != 1 or len(y.shape) != 1:
+        raise ValueError("x and y must be 1-D signals, got shapes %s and %s" % (x.shape, y.shape))
+    if len(x) != len(y):
+        raise ValueError("x and y must have the same length, got %d and %d" % (len(x), len(y)))
+    return np.stack([x.astype(np.float32), y.astype(np.float32)])
+
+
+def _score_pair(batch_fn, pair, device, **kw):
+    import torch
+    both = torch.as_tensor(pair, device="cuda:%d" % device)
+    return float(batch_fn(both[0:1], both[1:2], **kw)[0])
+
+
+class ESTOI(object):
+    """Extended STOI (Jensen, Taal 2016; pystoi's `stoi(clean, denoise, sr, extended=True)`) with STOI's call surface:
+    `ESTOI(sr)(clean, processed)`, numpy 1-D in, Python float out, computed on the device (rced_stoi_ex)."""
+
+    def __init__(self, sr=8000, device=0):
+        from . import audio
+        if sr not in audio.STOI_RATES:
+            raise ValueError("sr must be 8000 or 10000, got %r" % (sr,))
+        self.sr, self.device = int(sr), device
+
+    def estoi(self, x, y):
+        from . import audio
+        pair = _pair(x, y)
+        if not pair.shape[1]:
+            return 1e-5
+        return _score_pair(audio.stoi_batch, pair, self.device, sample_rate=self.sr, extended=True)
+
+    def __call__(self, x, y):
+        return self.estoi(x, y)
+
+
+class SISDR(object):
+    """Scale-invariant SDR, `SISDR()(y, y_pred)` as `SDR()(y, y_pred)`: numpy 1-D in, Python float (dB) out, computed on the
+    device (rced_si_sdr).  Two empty signals give nan, as the definition does."""
+
+    def __init__(self, device=0):
+        self.device = device
+
+    def si_sdr(self, y, y_pred):
+        from . import audio
+        pair = _pair(y, y_pred)
+        if not pair.shape[1]:
+            return float("nan")
+        return _score_pair(audio.si_sdr_batch, pair, self.device)
+
+    def __call__(self, x, y):
+        return self.si_sdr(x, y)
+
+
+class SegSNR(object):
+    """Segmental SNR, `SegSNR(sr)(clean, processed)`: numpy 1-D in, Python float (dB) out, computed on the device
+    (rced_seg_snr).  Signals shorter than one frame give nan."""
+
+    def __init__(self, sr=8000, device=0):
+        from . import audio
+        self.window = audio.seg_snr_window(sr)           # ValueError for a rate the library refuses
+        self.sr, self.device = int(sr), device
+
+    def seg_snr(self, x, y):
+        from . import audio
+        pair = _pair(x, y)
+        if not pair.shape[1]:
+            return float("nan")
+        return _score_pair(audio.seg_snr_batch, pair, self.device, sample_rate=self.sr)
+
+    def __call__(self, x, y):
+        return self.seg_snr(x, y)

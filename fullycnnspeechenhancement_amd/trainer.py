@@ -16,6 +16,7 @@ import time
 import numpy as np
 
 from . import _lib, model as _model, spec, weights as _weights
+from .evaluation import EXTRA_METRICS, check_extra
 from .metrics import AverageMeter
 
 
@@ -44,6 +45,7 @@ class FullyCNNTrainer(object):
         self.device = int(device)
         self.sdr_score = AverageMeter()            # trainer.py:34; valid() adds to it and never resets it, as there
         self.stoi_score = AverageMeter()           # trainer.py:33; filled by valid(..., stoi=True)
+        self.extra_scores = {name: AverageMeter() for name in EXTRA_METRICS}    # filled by valid(..., extra=(names))
         self.train_loss = AverageMeter()           # trainer.py:29-31; train() updates the three
         self.data_time = AverageMeter()
         self.batch_time = AverageMeter()
@@ -93,20 +95,26 @@ class FullyCNNTrainer(object):
         statistics, is `build_model(net_work, False, weights=trainer.variables())`.)"""
         return self.model(input_x)
 
-    def valid(self, valid_loader, epoch, logger=None, nfft=512, stoi=False):
+    def valid(self, valid_loader, epoch, logger=None, nfft=512, stoi=False, extra=()):
         """trainer.py:252-338 over anything that yields the reference's 4-tuple (batch_mix, batch_clean, mix_sig,
         clean_sig): engine.evaluate_pcm with valid_step as the forward (BatchNorm with each batch's own statistics),
         every utterance's SDR into self.sdr_score; prints -- and logs, given a logger -- the reference's line with its
         SDR field and returns the average.  With stoi=True every utterance's STOI goes into self.stoi_score as well and
-        the line gains the reference's st_score field, in the reference's order.  PESQ and the wav files are not built."""
-        from .engine import evaluate_pcm
+        the line gains the reference's st_score field, in the reference's order.  extra: names from
+        evaluation.EXTRA_METRICS; every utterance's score goes into self.extra_scores[name], and one further line with their
+        averages is printed and logged after the reference's.  PESQ and the wav files are not built."""
+        from .engine import evaluate_pcm, extra_line
+        extra = check_extra(extra)
         for _batch_mix, _batch_clean, mix_sig, clean_sig in valid_loader:
-            scores = evaluate_pcm(self.valid_step, mix_sig, clean_sig, nfft, self.device, stoi=stoi)
+            scores = evaluate_pcm(self.valid_step, mix_sig, clean_sig, nfft, self.device, stoi=stoi, extra=extra)
             for score in scores[1]:
                 self.sdr_score.update(float(score))
             if stoi:
                 for score in scores[2]:
                     self.stoi_score.update(float(score))
+            for name in extra:
+                for score in scores[-1][name]:
+                    self.extra_scores[name].update(float(score))
         if stoi:
             line = "Epoch: {}, Average st_score: {:.4f}; Average sd_score: {:.4f}.\n".format(epoch, self.stoi_score.avg,
                                                                                              self.sdr_score.avg)
@@ -115,6 +123,11 @@ class FullyCNNTrainer(object):
         print(line)
         if logger is not None:
             logger.info(line)
+        if extra:
+            more = "Epoch: {}, ".format(epoch) + extra_line(extra, self.extra_scores)
+            print(more)
+            if logger is not None:
+                logger.info(more)
         return self.sdr_score.avg
 
     def fit_step(self, input_x, target_y):

@@ -262,6 +262,43 @@ int rced_resample(const void* src_dev, int src_dtype, int channels, long long sr
 int rced_stoi(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride,
               const int* lengths_dev, int N, int fs_sig, double* stoi_dev, int* detail_dev, int device, void* stream);
 
+/* STOI and / or ESTOI (Jensen, Taal 2016: the `extended` mode of the package the reference takes STOI from) in one call.
+ * which: RCED_STOI_CLASSIC, RCED_STOI_EXTENDED or both; with both, the resampling, the silent-frame removal and the band
+ * spectra run once.  stoi_dev [N] double is written with CLASSIC, estoi_dev [N] double with EXTENDED; an output that is asked
+ * for and NULL, or any other `which`, is RCED_ERR_ARG; one that is not asked for is not touched and may be NULL.  detail_dev
+ * and everything else as in rced_stoi, whose results are the bits of which = RCED_STOI_CLASSIC and of the classic half of both.
+ * ESTOI as DESIGN.md "ESTOI" specifies it: the same M = K - 30 segments of 30 frames x 15 bands, of x and of y, no clipping
+ * and no scaling; each segment's band rows lose their mean over the 30 frames and are divided by (their 2-norm + eps), then
+ * its frame columns lose their mean over the 15 bands and are divided by (their 2-norm + eps); sum(xn yn) / (30 M).  M = 0
+ * gives 1e-5, an all-zero row gives 0.  fp64; the same invariants; the workspace is rced_stoi's. */
+#define RCED_STOI_CLASSIC 1
+#define RCED_STOI_EXTENDED 2
+int rced_stoi_ex(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride,
+                 const int* lengths_dev, int N, int fs_sig, int which, double* stoi_dev, double* estoi_dev,
+                 int* detail_dev, int device, void* stream);
+
+/* SI-SDR per utterance over its own length, x = ref row, y = est row, no mean removal:
+ *   alpha = sum(y x) / sum(x x);   10 * log10( sum((alpha x)^2) / sum((y - alpha x)^2) ),
+ * in two passes (alpha first, then the two energies with alpha in hand: the one-pass closed form cancels for good
+ * estimates), fp64 from the fp32 inputs.  Pointers, strides, lengths_dev and their clamping as in rced_sdr.  out_dev [N]
+ * double (dB); parts_dev: NULL or [N, 3] double receiving alpha, sum((alpha x)^2), sum((y - alpha x)^2).  IEEE results stand
+ * as numpy gives them: y = 2^k x gives +inf (both sums of the first pass run in one order: alpha is exact, the residual
+ * zero), x = 0, y = 0 or a length of 0 give nan.  Three launches; a workspace of its own per (device, stream), growing
+ * only.  The invariants stated above hold.  Asynchronous. */
+int rced_si_sdr(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride,
+                const int* lengths_dev, int N, double* out_dev, double* parts_dev, int device, void* stream);
+
+/* Segmental SNR per utterance over its own length L: frames of W = (3 fs + 50) / 100 samples (240 at 8 kHz) at hop
+ * H = W / 4 (integer divisions), frame i starting at i H, nf = (L - W) / H + 1 frames for L >= W, else 0; window
+ * w[j] = 0.5 (1 - cos(2 pi (j + 1) / (W + 1))), j = 0 .. W - 1; per frame
+ *   s = 10 * log10( sum((w x)^2) / (sum((w (x - y))^2) + eps) + eps ),  eps = np.finfo(float).eps,
+ * clamped to [-10, 35]; the score is the mean over the frames, nan for nf = 0.  fs with W outside [4, 1440] is
+ * RCED_ERR_ARG.  Pointers, strides, lengths_dev and their clamping as in rced_sdr; samples past a length are never read.
+ * out_dev [N] double (dB); frames_dev: NULL or [N] int32 receiving nf.  fp64 from the fp32 inputs.  Two launches; a
+ * workspace of its own per (device, stream), growing only.  The invariants stated above hold.  Asynchronous. */
+int rced_seg_snr(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride,
+                 const int* lengths_dev, int N, int fs, double* out_dev, int* frames_dev, int device, void* stream);
+
 /* ---- streaming denoiser: PCM in, PCM out, 128 samples (one hop, 16 ms) at a time, for many independent streams ("lanes") at once,
  * at a fixed delay.  Only the first layer of the three networks looks across time (3 past, 4 future frames) and the rebuild uses no
  * overlap-add, so the chunked run reproduces the whole-utterance chain rced_stft -> rced_forward -> rced_istft.

@@ -5,6 +5,9 @@ of per-run times), beside the HBM floor their byte counts imply; and FullyCNNTes
 the same chain without the score (stft_batch -> model -> istft_batch): the difference is what scoring costs.
 STOI (rced_stoi) is timed at the same shape, beside the wall time of its float64 numpy / scipy restatement
 (tests/stoi_np.py) for the same batch on 16 host processes.  `python tools/time_eval.py stoi` times STOI alone.
+The further scores -- legs `estoi`, `stoi+estoi` (one rced_stoi_ex call for both), `si_sdr`, `seg_snr` -- run at the same shape
+beside their restatements (tests/estoi_np.py, tests/td_metrics_np.py) on the same 16 processes, with the ratio of `stoi+estoi`
+to rced_stoi alone in this process; `python tools/time_eval.py ext` times those alone.
 Prints one JSON line."""
 import json
 import os
@@ -50,15 +53,44 @@ def _host_stoi(seed):
     return stoi_np.stoi(x, x + 0.05 * rng.standard_normal(L), 8000)
 
 
-def host_stoi_seconds():
-    """Wall time of the restatement over N utterances of L samples on HOST_PROCS processes (forked before the GPU is touched)."""
+def _host_pair(seed):
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    x = 0.1 * rng.standard_normal(L)
+    return x, x + 0.05 * rng.standard_normal(L)
+
+
+def _host_estoi(seed):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import estoi_np
+    return estoi_np.estoi(*_host_pair(seed), 8000)
+
+
+def _host_si_sdr(seed):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import td_metrics_np
+    return td_metrics_np.si_sdr(*_host_pair(seed))
+
+
+def _host_seg_snr(seed):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import td_metrics_np
+    return td_metrics_np.seg_snr(*_host_pair(seed), 8000)
+
+
+def host_seconds(fn):
+    """Wall time of a restatement over N utterances of L samples on HOST_PROCS processes (forked before the GPU is touched)."""
     import multiprocessing
     import time
     with multiprocessing.get_context("fork").Pool(HOST_PROCS) as pool:
-        pool.map(_host_stoi, range(HOST_PROCS))              # imports and first-call costs
+        pool.map(fn, range(HOST_PROCS))                      # imports and first-call costs
         t0 = time.perf_counter()
-        pool.map(_host_stoi, range(N), chunksize=1)
+        pool.map(fn, range(N), chunksize=1)
         return time.perf_counter() - t0
+
+
+def host_stoi_seconds():
+    return host_seconds(_host_stoi)
 
 
 def stoi_timings(speech, mix):
@@ -67,9 +99,26 @@ def stoi_timings(speech, mix):
     return r, one
 
 
+def ext_timings(speech, mix, host_ext):
+    """The four further legs, each beside its restatement's wall time, and stoi+estoi over rced_stoi alone (same process)."""
+    out = {"estoi": timed_us(lambda: audio.stoi_batch(speech, mix, extended=True)),
+           "stoi+estoi": timed_us(lambda: audio.stoi_batch(speech, mix, extended="both")),
+           "si_sdr": timed_us(lambda: audio.si_sdr_batch(speech, mix)),
+           "seg_snr": timed_us(lambda: audio.seg_snr_batch(speech, mix))}
+    alone = timed_us(lambda: audio.stoi_batch(speech, mix))
+    out["stoi_alone_same_process"] = alone
+    out["stoi+estoi_over_stoi"] = out["stoi+estoi"]["median_us"] / alone["median_us"]
+    for leg, seconds in host_ext.items():
+        out[leg + "_host_restatement_s"] = {"seconds": seconds, "processes": HOST_PROCS}
+    return out
+
+
 def main():
     only_stoi = sys.argv[1:] == ["stoi"]
-    host_s = host_stoi_seconds()                                 # first: it forks
+    only_ext = sys.argv[1:] == ["ext"]
+    host_s = host_stoi_seconds() if not only_ext else None       # first: these fork
+    host_ext = {} if only_stoi else {"estoi": host_seconds(_host_estoi), "si_sdr": host_seconds(_host_si_sdr),
+                                     "seg_snr": host_seconds(_host_seg_snr)}
     g = torch.Generator(device="cuda").manual_seed(1)
     speech = torch.randn((N, L), device="cuda", generator=g) * 0.1
     noise = torch.randn((N, L), device="cuda", generator=g) * 0.05
@@ -78,6 +127,10 @@ def main():
         mix = audio.mix_snr_batch(speech, noise, 5.0)
         out["stoi"], out["stoi_single_utterance"] = stoi_timings(speech, mix)
         out["stoi_host_restatement_s"] = {"seconds": host_s, "processes": HOST_PROCS}
+        print(json.dumps(out))
+        return
+    if only_ext:
+        out.update(ext_timings(speech, audio.mix_snr_batch(speech, noise, 5.0), host_ext))
         print(json.dumps(out))
         return
 
@@ -105,6 +158,7 @@ def main():
 
     out["stoi"], out["stoi_single_utterance"] = stoi_timings(speech, mix)
     out["stoi_host_restatement_s"] = {"seconds": host_s, "processes": HOST_PROCS}
+    out.update(ext_timings(speech, mix, host_ext))
 
     model = build_model("FullyCNNV3", False, weights=_weights.synthetic_weights(3, seed=42))
     lens = [L] * N
