@@ -20,6 +20,19 @@ def pcm_format(name, what="dtype"):
     return getattr(torch, name), np.dtype(name), _PCM_CODES[name]
 
 
+REBUILDS = ("reference", "ola")     # AudioReBuild.rebuild_audio as shipped (rced_istft) / weighted overlap-add (rced_istft_ola)
+
+
+def check_rebuild(rebuild, kernels="x6"):
+    """The `rebuild` keyword of everything that turns spectra into audio, checked before any device work.  Returns it."""
+    if rebuild not in REBUILDS:
+        raise ValueError("rebuild must be 'reference' (AudioReBuild as the reference ships it) or 'ola' (weighted overlap-add), got %r"
+                         % (rebuild,))
+    if rebuild == "ola" and kernels == "f32":
+        raise ValueError("rebuild='ola' has no kernels='f32' form (the fp32-MFMA comparators cover the reference rebuild only)")
+    return rebuild
+
+
 def pcm_name(dtype):
     """The name of a torch or numpy dtype if it is a sample format, else None."""
     name = str(dtype).rsplit(".", 1)[-1]

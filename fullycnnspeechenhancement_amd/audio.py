@@ -69,9 +69,16 @@ def stft_batch(pcm, lengths=None, frames=None, with_phase=True, kernels="x6"):
     return mag, (torch.view_as_complex(ph) if ph is not None else None)
 
 
-def istft_batch(mag, phase, nfft=512, kernels="x6"):
-    """mag [N, T, 129(,1)] float32, phase [N, T, 129] complex64 (torch.cuda) -> audio [N, (T+1)*128]."""
+def istft_batch(mag, phase, nfft=512, kernels="x6", rebuild="reference", frames=None):
+    """mag [N, T, 129(,1)] float32, phase [N, T, 129] complex64 (torch.cuda) -> audio [N, (T+1)*128].
+    rebuild: "reference" (AudioReBuild.rebuild_audio as shipped: divide by the window, keep half of every frame; nfft as there)
+    or "ola" (least-squares weighted overlap-add, rced_istft_ola: both halves of every frame, nfft plays no part).
+    frames (rebuild="ola" only): per-utterance frame counts (list / tensor, clamped into [0, T]) or None (= T each); frames at or
+    past an utterance's count are never read, and its columns from 128 (frames + 1) on are zero."""
     import torch
+    _args.check_rebuild(rebuild, kernels)
+    if frames is not None and rebuild != "ola":
+        raise ValueError("frames belongs to rebuild='ola' (the reference rebuild keeps every frame apart: the caller trims)")
     if mag.dim() == 4:
         mag = mag.squeeze(-1)
     mag = mag.float().contiguous()
@@ -80,6 +87,20 @@ def istft_batch(mag, phase, nfft=512, kernels="x6"):
     if tuple(mag.shape) != (n, t, BINS) or tuple(ph.shape) != (n, t, BINS, 2):
         raise ValueError("mag must be [N, T, 129], phase [N, T, 129] complex")
     out = torch.empty((n, (t + 1) * STEP), dtype=torch.float32, device=mag.device)
+    if rebuild == "ola":
+        fdev = None
+        if frames is not None:
+            if hasattr(frames, "is_cuda") and frames.is_cuda:
+                fdev = frames.to(device=mag.device, dtype=torch.int32).reshape(-1).contiguous()
+                if int(fdev.shape[0]) != n:
+                    raise ValueError("frames must hold N = %d values, got %d" % (n, int(fdev.shape[0])))
+            else:
+                fdev = torch.tensor(_args.host_ints(frames, n, "frames"), dtype=torch.int32, device=mag.device)
+        if n:
+            _lib.check(_lib.load().rced_istft_ola(mag.data_ptr() if t else None, ph.data_ptr() if t else None,
+                                                  fdev.data_ptr() if fdev is not None else None, n, t, out.data_ptr(), mag.device.index,
+                                                  _args.current_stream(mag.device)))
+        return out
     if n and t:
         _lib.check(_lib.load().rced_istft_ex(mag.data_ptr(), ph.data_ptr(), n, t, int(nfft), out.data_ptr(), mag.device.index,
                                              _args.current_stream(mag.device), _kernels(kernels)))
@@ -118,13 +139,14 @@ class AudioFeature(object):
 class AudioReBuild(object):
     """model_utils/utils.py:93-183 on the GPU.  nfft defaults to 512 exactly as the reference's does."""
 
-    def __init__(self, windows_name=None, nfft=512, device=0, kernels="x6"):
+    def __init__(self, windows_name=None, nfft=512, device=0, kernels="x6", rebuild="reference"):
         if windows_name not in (None, "hamming"):
             raise ValueError("only the hamming window is built")
         if nfft not in (256, 512):
             raise ValueError("nfft must be 512 (reference default) or 256")
         self.nfft, self.device, self.kernels = nfft, device, kernels
         _kernels(kernels)
+        self.rebuild = _args.check_rebuild(rebuild, kernels)      # "ola": weighted overlap-add over num_frames(length) frames each
 
     def rebuild_audio(self, sig_length_list, spec, phase, sample_rate, windows_ms, stride_ms):
         import torch
@@ -132,5 +154,6 @@ class AudioReBuild(object):
         dev = "cuda:%d" % self.device
         mag = torch.as_tensor(np.asarray(spec, dtype=np.float32), device=dev)
         ph = torch.as_tensor(np.asarray(phase).astype(np.complex64), device=dev)
-        audio = istft_batch(mag, ph, self.nfft, kernels=self.kernels).cpu().numpy()
+        frames = [num_frames(v) for v in sig_length_list] if self.rebuild == "ola" else None
+        audio = istft_batch(mag, ph, self.nfft, kernels=self.kernels, rebuild=self.rebuild, frames=frames).cpu().numpy()
         return [audio[i][:sig_length_list[i]] for i in range(len(audio))]

@@ -12,6 +12,7 @@
 
 #include "kernels_audio.h"
 #include "kernels_audio_x6.h"
+#include "kernels_ola_x6.h"
 #include "rced_internal.h"
 
 using namespace rced;
@@ -27,8 +28,11 @@ struct AudioTables {   // per device, built once
   unsigned short* istft_x6[2] = {nullptr, nullptr};   // [nfft == 512]
   float* cim[2] = {nullptr, nullptr};
   float* chead[2] = {nullptr, nullptr};
+  // overlap-add (kernels_ola_x6.h): 16 M-tiles of A fragments, the single-frame factors of hops 0 and F
+  unsigned short* ola_x6 = nullptr;
+  float* ola_fix = nullptr;
   void release() {   // of a build that failed half way
-    for (void* p : {(void*)stft, (void*)istft512, (void*)istft256, (void*)stft_x6}) (void)hipFree(p);
+    for (void* p : {(void*)stft, (void*)istft512, (void*)istft256, (void*)stft_x6, (void*)ola_x6, (void*)ola_fix}) (void)hipFree(p);
     for (int v = 0; v < 2; ++v)
       for (void* p : {(void*)istft_x6[v], (void*)cim[v], (void*)chead[v]}) (void)hipFree(p);
   }
@@ -104,8 +108,24 @@ int build_x6(AudioTables& t) {
     if (int rc = upload(&t.cim[v], cim, kWhat)) return rc;
     if (int rc = upload(&t.chead[v], head, kWhat)) return rc;
   }
+  {   // overlap-add: rows = samples 0..255 of a frame, the synthesis window over the interior denominator folded in
+    auto den = [](int s) { return hamming(s) * hamming(s) + hamming(s + 128) * hamming(s + 128); };
+    auto coef = [&](int row, int k) {
+      return (k == 1 ? istft_coef(256, row, 128, 0) : istft_coef(256, row, k >> 1, k & 1)) * hamming(row) * hamming(row) / den(row & 127);
+    };
+    if (int rc = upload(&t.ola_x6, pack_x6(audio::x6::kOlaMTx, coef), kWhat)) return rc;
+    std::vector<float> fix(2 * 128);
+    for (int s = 0; s < 128; ++s) {
+      fix[s] = (float)(den(s) / (hamming(s) * hamming(s)));
+      fix[128 + s] = (float)(den(s) / (hamming(s + 128) * hamming(s + 128)));
+    }
+    if (int rc = upload(&t.ola_fix, fix, kWhat)) return rc;
+  }
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(audio::x6::istft_x6_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      audio::x6::kIstftLdsBytes);
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(audio::x6::istft_ola_x6_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            audio::x6::kOlaLdsBytes);
   if (e == hipSuccess)
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(audio::x6::istft_x6_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             audio::x6::kIstftLdsBytes);
@@ -232,6 +252,23 @@ int rced_istft_ex(const float* mag_dev, const float* phase_dev, int N, int T, in
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(audio::deemphasis_kernel, dim3(N), dim3(audio::kThreads), 0, st, audio_dev,
                      (T + 1) * audio::kStep);
+  HIP_TRY(hipGetLastError());
+  return RCED_OK;
+}
+
+int rced_istft_ola(const float* mag_dev, const float* phase_dev, const int* frames_dev, int N, int T, float* audio_dev, int device,
+                   void* stream) {
+  if (N < 0 || T < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
+  if (N == 0) return RCED_OK;
+  if (!audio_dev || (T > 0 && (!mag_dev || !phase_dev))) return rced_fail(RCED_ERR_ARG, "null pointer");
+  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
+  DeviceGuard g(device);
+  AudioTables* t = nullptr;
+  if (int rc = tables(device, &t)) return rc;
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  // one workgroup per utterance walks its blocks: the add across frames, the seam, the de-emphasis and the zero tail in one launch
+  hipLaunchKernelGGL(audio::x6::istft_ola_x6_kernel, dim3(N), dim3(audio::x6::kThreadsX), audio::x6::kOlaLdsBytes, static_cast<hipStream_t>(stream),
+                     mag_dev, phase_dev, frames_dev, (const unsigned short*)t->ola_x6, (const float*)t->ola_fix, T, audio_dev);
   HIP_TRY(hipGetLastError());
   return RCED_OK;
 }

@@ -95,18 +95,20 @@ class FullyCNNTrainer(object):
         statistics, is `build_model(net_work, False, weights=trainer.variables())`.)"""
         return self.model(input_x)
 
-    def valid(self, valid_loader, epoch, logger=None, nfft=512, stoi=False, extra=()):
+    def valid(self, valid_loader, epoch, logger=None, nfft=512, stoi=False, extra=(), rebuild="reference"):
         """trainer.py:252-338 over anything that yields the reference's 4-tuple (batch_mix, batch_clean, mix_sig,
         clean_sig): engine.evaluate_pcm with valid_step as the forward (BatchNorm with each batch's own statistics),
         every utterance's SDR into self.sdr_score; prints -- and logs, given a logger -- the reference's line with its
         SDR field and returns the average.  With stoi=True every utterance's STOI goes into self.stoi_score as well and
         the line gains the reference's st_score field, in the reference's order.  extra: names from
         evaluation.EXTRA_METRICS; every utterance's score goes into self.extra_scores[name], and one further line with their
-        averages is printed and logged after the reference's.  PESQ and the wav files are not built."""
-        from .engine import evaluate_pcm, extra_line
+        averages is printed and logged after the reference's.  rebuild: "reference" or "ola" (engine.evaluate_pcm).
+        PESQ and the wav files are not built."""
+        from .engine import check_rebuild, evaluate_pcm, extra_line
         extra = check_extra(extra)
+        check_rebuild(rebuild)
         for _batch_mix, _batch_clean, mix_sig, clean_sig in valid_loader:
-            scores = evaluate_pcm(self.valid_step, mix_sig, clean_sig, nfft, self.device, stoi=stoi, extra=extra)
+            scores = evaluate_pcm(self.valid_step, mix_sig, clean_sig, nfft, self.device, stoi=stoi, extra=extra, rebuild=rebuild)
             for score in scores[1]:
                 self.sdr_score.update(float(score))
             if stoi:

@@ -167,6 +167,20 @@ int rced_stft_ex(const float* pcm_dev, const int* lengths_dev, int N, int L, int
 int rced_istft_ex(const float* mag_dev, const float* phase_dev, int N, int T, int nfft, float* audio_dev,
                   int device, void* stream, int kernels);
 
+/* The opt-in rebuild: least-squares weighted overlap-add (Griffin-Lim synthesis) in place of AudioReBuild's divide-by-window-and-
+ * keep-half.  For utterance n with F = frames_dev[n] frames, w = hamming(256):
+ *   x_t  = irfft(mag[n,t] * phase[n,t], 256), t < F (the imaginary parts of bins 0 and 128 are ignored, as irfft ignores them);
+ *   e[i] = sum_{t<F} w[i - 128t] x_t[i - 128t] / sum_{t<F} w[i - 128t]^2,  i < 128 (F + 1), the sums over the frames that cover i
+ *          (hops 0 and F are covered by one frame: their denominator is that frame's w^2 alone);
+ *   y[0] = e[0], y[i] = e[i] + 0.97 y[i-1] (the reference's de-emphasis); columns 128 (F + 1) .. (T + 1) * 128 are written as 0.
+ * frames_dev [N] int32 (device) or NULL (= T each); a value outside [0, T] is clamped into it.  Frames t >= F are never read (after
+ * the net a padded frame is not zero and would bleed into hop F), so utterance n's result does not depend on T, N, its row or its
+ * neighbours, and is bit-identical run to run (no atomics).  audio_dev [N, (T+1)*128] float32, every column written; there is no
+ * nfft (the nfft = 512 quirk has no overlap-add counterpart) and no RCED_AUDIO_F32 form.  One launch; after the first call's table
+ * upload it is asynchronous and allocates nothing. */
+int rced_istft_ola(const float* mag_dev, const float* phase_dev, const int* frames_dev, int N, int T, float* audio_dev,
+                   int device, void* stream);
+
 /* ---- evaluation loop (tester.py:92-167, trainer.py:252-338): the two numpy pieces around the rebuilt audio, for a
  * ragged batch.  Streaming reductions without atomics: results are bit-identical run to run, and utterance n's result
  * does not depend on N, on its neighbours, on its row index or on the row strides (kernels_eval.h).  Both keep a slice

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Times the STFT front-end, the CNN and the ISTFT rebuild at BASELINE config-3 scale
-(256 utterances x 512 frames = 65,664 samples each), device-resident, with torch.cuda events."""
+(256 utterances x 512 frames = 65,664 samples each), device-resident, with torch.cuda events.  A second line times the
+overlap-add rebuild (rebuild="ola") next to the reference rebuild, same spectra, same run."""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -38,3 +39,13 @@ print(json.dumps({"frames": frames, "stft_ms": t_stft, "cnn_ms": t_cnn, "istft_m
                   "stft_gbps_algorithmic": (N * L * 4 + frames * 129 * 12) / t_stft / 1e6,
                   "istft_gbps_algorithmic": (frames * 129 * 12 + N * (T + 1) * 128 * 4) / t_istft / 1e6,
                   "pipeline_frames_per_s": frames / ((t_stft + t_cnn + t_istft) * 1e-3)}))
+# the two rebuilds on the same spectra, alternating, 100 calls a window (a 10-call window is 2 ms: the clock as much as the kernel)
+ola, ref = [], []
+for _ in range(5):
+    ola.append(timed(lambda: audio.istft_batch(pred, ph, rebuild="ola"), reps=100)[0])
+    ref.append(timed(lambda: audio.istft_batch(pred, ph), reps=100)[0])
+t_ola, t_ref = sorted(ola)[2], sorted(ref)[2]
+print(json.dumps({"frames": frames, "istft_reference_ms": t_ref, "istft_ola_ms": t_ola, "ola_over_reference": t_ola / t_ref,
+                  "istft_reference_ms_windows": ref, "istft_ola_ms_windows": ola,
+                  "ola_tflops": frames * 2 * 256 * 256 / t_ola / 1e9,
+                  "ola_gbps_algorithmic": (frames * 129 * 12 + N * (T + 1) * 128 * 4) / t_ola / 1e6}))
