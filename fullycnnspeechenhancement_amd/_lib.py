@@ -60,6 +60,7 @@ SYMBOLS = {
                                      ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
     "rced_stream_delay":(ctypes.c_int, []),
     "rced_stream_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
+    "rced_stream_create_ex": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
     "rced_stream_destroy": (None, [_vp]),
     "rced_stream_push": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _vp]),
     "rced_stream_finish": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),

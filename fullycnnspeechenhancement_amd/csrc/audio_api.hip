@@ -178,6 +178,8 @@ int rced_audio_x6_tables_get(int device, int nfft, rced_audio_x6_tables* out) {
   out->istft = t->istft_x6[v];
   out->cim = t->cim[v];
   out->chead = t->chead[v];
+  out->ola = t->ola_x6;
+  out->ola_fix = t->ola_fix;
   return RCED_OK;
 }
 

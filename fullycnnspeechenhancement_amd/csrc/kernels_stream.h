@@ -34,8 +34,10 @@ constexpr int kFinishOut = 6 * kStep;    // floats per lane of rced_stream_finis
 // per-lane state, floats; all zero = the start of an utterance
 constexpr int kStHops = 0;                                  // int: hops pushed
 constexpr int kStSample = 1;                                // the last input sample (pre-emphasis carry)
+constexpr int kStCarry = 2;                                 // overlap-add streams only: the de-emphasis carry (word 3 is unused)
 constexpr int kStPrevE = 4;                                 // the previous hop, pre-emphasised
 constexpr int kStPend = kStPrevE + kStep;                   // the pending output hop, de-emphasised; its last sample is the carry
+                                                            // (overlap-add streams: the newest frame's second-half addend, kernels_stream_ola.h)
 constexpr int kStPhase = kStPend + kStep;                   // phase of the 7 kept frames [7, 129, 2]
 constexpr int kStMag = kStPhase + kKeep * kBins * 2;        // magnitude of the 7 kept frames [7, 129]
 constexpr int kStFloats = (kStMag + kKeep * kBins + 3) & ~3;
@@ -70,6 +72,21 @@ __device__ __forceinline__ float frame_sample(const float* __restrict__ in, cons
     return pre_emph(in, (h - 1) * kStep + k, before, H == 0);
   }
   return pre_emph(in, h * kStep + k - kStep, before, H == 0);
+}
+
+// A lane's state after a push of K hops, but for what the rebuild keeps (the pending hop, a carry): the 7 newest frames of its window
+// (o0 = the index of bin 0 of window row K), the last hop pre-emphasised, the last sample, the hop count.  By the whole workgroup.
+__device__ __forceinline__ void advance_lane(float* __restrict__ st, const float* __restrict__ src, const float* __restrict__ win,
+                                             const float* __restrict__ phw, size_t o0, int K, int H, float sample, int tid) {
+  for (int i = tid; i < kKeep * kBins; i += kThreadsX) {
+    st[kStMag + i] = win[o0 + i];
+    *reinterpret_cast<f32x2*>(st + kStPhase + 2 * i) = *reinterpret_cast<const f32x2*>(phw + 2 * (o0 + i));
+  }
+  if (tid < kStep) st[kStPrevE + tid] = pre_emph(src, (K - 1) * kStep + tid, sample, H == 0);
+  if (tid == 0) {
+    reinterpret_cast<int*>(st)[kStHops] = H + K;
+    st[kStSample] = src[K * kStep - 1];
+  }
 }
 
 // in: pcm [S, K * 128] (push) or the tails [S, 128] (finish, K = 6 slots); flags: push: active [S] or null, finish: tail counts [S]
@@ -273,20 +290,8 @@ __global__ __launch_bounds__(kThreadsX) void stream_istft_kernel(const float* __
       for (int i = tid; i < kStFloats; i += kThreadsX) st[i] = 0.f;
       continue;
     }
-    const float* src = in + (size_t)s * in_stride;
-    for (int i = tid; i < kKeep * kBins; i += kThreadsX) {
-      const size_t o = ((size_t)s * rows + K) * kBins + i;
-      st[kStMag + i] = win[o];
-      *reinterpret_cast<f32x2*>(st + kStPhase + 2 * i) = *reinterpret_cast<const f32x2*>(phw + 2 * o);
-    }
-    if (tid < kStep) {
-      st[kStPend + tid] = obuf[(q * K + K - 1) * kORow + tid];
-      st[kStPrevE + tid] = pre_emph(src, (K - 1) * kStep + tid, sSample[q], sH[q] == 0);
-    }
-    if (tid == 0) {
-      reinterpret_cast<int*>(st)[kStHops] = sH[q] + K;
-      st[kStSample] = src[K * kStep - 1];
-    }
+    if (tid < kStep) st[kStPend + tid] = obuf[(q * K + K - 1) * kORow + tid];
+    advance_lane(st, in + (size_t)s * in_stride, win, phw, ((size_t)s * rows + K) * kBins, K, sH[q], sSample[q], tid);
   }
 }
 

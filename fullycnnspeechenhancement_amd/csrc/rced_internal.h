@@ -73,6 +73,8 @@ struct rced_audio_x6_tables {
   const unsigned short* istft = nullptr;   // audio::x6::kIstftPackX, of the nfft asked for
   const float* cim = nullptr;              // [128]
   const float* chead = nullptr;            // [258][128]
+  const unsigned short* ola = nullptr;     // audio::x6::kOlaPackX: the overlap-add rebuild's 16 M-tiles (no nfft)
+  const float* ola_fix = nullptr;          // [2][128]: its single-frame factors
 };
 int rced_audio_x6_tables_get(int device, int nfft, rced_audio_x6_tables* out);
 

@@ -1,5 +1,6 @@
 // C ABI of the streaming denoiser (include/rced.h, "streaming" section): host side.  Three launches per push on the caller's stream --
-// the stateful STFT, rced_forward on the lanes' windows, the stateful ISTFT (kernels_stream.h) --, no allocation, no synchronisation.
+// the stateful STFT, rced_forward on the lanes' windows, the stateful ISTFT (kernels_stream.h; for a stream created with
+// RCED_STREAM_REBUILD_OLA the overlap-add one, kernels_stream_ola.h) --, no allocation, no synchronisation.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,17 +12,18 @@
 #include "rced_internal.h"
 
 // kernels_audio.h / kernels_audio_x6.h define their kernels with external linkage and audio_api.hip is their translation unit: this
-// one takes the headers into an unnamed namespace, so that its copies (it launches only its own two kernels) are local to it.
+// one takes the headers into an unnamed namespace, so that its copies (it launches only its own three kernels) are local to it.
 // (x6_dft.h comes in with them; what it includes -- <vector>, host_util.h through rced_internal.h -- is already in, at file scope.)
 namespace {
 #include "kernels_stream.h"
+#include "kernels_stream_ola.h"
 namespace audio = rced::audio;
 namespace as = rced::audio::stream;
 }  // namespace
 
 struct rced_stream {
   rced_model* model = nullptr;   // null once the model was destroyed under the stream
-  int device = 0, lanes = 0, max_hops = 0, nfft = 0;
+  int device = 0, lanes = 0, max_hops = 0, nfft = 0, rebuild = RCED_STREAM_REBUILD_REFERENCE;
   float* state = nullptr;        // [S, kStFloats]
   float* win = nullptr;          // [S, 7 + K, 129] magnitudes: the CNN's input
   float* phw = nullptr;          // [S, 7 + K, 129, 2]
@@ -50,9 +52,14 @@ int run(rced_stream* s, const float* in, const int* flags, int finish, int K, fl
   HIP_TRY(hipGetLastError());
   if (int rc = rced_forward(s->model, s->win, s->masks, S, as::kKeep + K, st)) return rc;
   const int lpw = audio::kFramesPerWg / K;
-  hipLaunchKernelGGL(as::stream_istft_kernel, dim3((S + lpw - 1) / lpw), dim3(audio::x6::kThreadsX), as::kStreamIstftLds, st,
-                     (const float*)s->masks, (const float*)s->win, (const float*)s->phw, in, flags, finish, s->tab.istft, s->tab.cim,
-                     s->tab.chead, s->state, S, K, out, out_counts);
+  if (s->rebuild == RCED_STREAM_REBUILD_OLA)
+    hipLaunchKernelGGL(as::stream_istft_ola_kernel, dim3((S + lpw - 1) / lpw), dim3(audio::x6::kThreadsX), as::kStreamOlaLds, st,
+                       (const float*)s->masks, (const float*)s->win, (const float*)s->phw, in, flags, finish, s->tab.ola, s->tab.ola_fix,
+                       s->state, S, K, out, out_counts);
+  else
+    hipLaunchKernelGGL(as::stream_istft_kernel, dim3((S + lpw - 1) / lpw), dim3(audio::x6::kThreadsX), as::kStreamIstftLds, st,
+                       (const float*)s->masks, (const float*)s->win, (const float*)s->phw, in, flags, finish, s->tab.istft, s->tab.cim,
+                       s->tab.chead, s->state, S, K, out, out_counts);
   HIP_TRY(hipGetLastError());
   s->last = st;
   return RCED_OK;
@@ -78,12 +85,18 @@ extern "C" {
 int rced_stream_delay(void) { return RCED_STREAM_DELAY; }
 
 int rced_stream_create(rced_model* m, int lanes, int max_hops, int nfft, rced_stream** out) {
+  return rced_stream_create_ex(m, lanes, max_hops, nfft, RCED_STREAM_REBUILD_REFERENCE, out);
+}
+
+int rced_stream_create_ex(rced_model* m, int lanes, int max_hops, int nfft, int rebuild, rced_stream** out) {
   static_assert(RCED_STREAM_DELAY == as::kDelayHops * audio::kStep && RCED_STREAM_FINISH_MAX == as::kFinishOut, "rced.h and kernels_stream.h");
   if (!out) return rced_fail(RCED_ERR_ARG, "out is NULL");
   *out = nullptr;
   if (lanes < 1 || lanes > 65536) return rced_fail(RCED_ERR_ARG, "lanes must be 1..65536, got %d", lanes);
   if (max_hops < 1 || max_hops > as::kMaxHops) return rced_fail(RCED_ERR_ARG, "max_hops must be 1..%d, got %d", as::kMaxHops, max_hops);
   if (nfft != 512 && nfft != 256) return rced_fail(RCED_ERR_ARG, "nfft must be 512 (reference default) or 256");
+  if (rebuild != RCED_STREAM_REBUILD_REFERENCE && rebuild != RCED_STREAM_REBUILD_OLA)
+    return rced_fail(RCED_ERR_ARG, "rebuild must be RCED_STREAM_REBUILD_REFERENCE (0) or RCED_STREAM_REBUILD_OLA (1), got %d", rebuild);
   if (!m) return rced_fail(RCED_ERR_ARG, "model is NULL");
   DeviceGuard g(m->device);
   if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", m->device);
@@ -94,6 +107,7 @@ int rced_stream_create(rced_model* m, int lanes, int max_hops, int nfft, rced_st
   s->lanes = lanes;
   s->max_hops = max_hops;
   s->nfft = nfft;
+  s->rebuild = rebuild;
   int rc = rced_audio_x6_tables_get(m->device, nfft, &s->tab);
   const size_t rows = (size_t)lanes * (as::kKeep + window_hops(s)) * audio::kBins;
   auto alloc = [&](float** p, size_t floats) {
@@ -110,6 +124,8 @@ int rced_stream_create(rced_model* m, int lanes, int max_hops, int nfft, rced_st
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(as::stream_stft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, as::kStreamStftLds);
     if (e == hipSuccess)
       e = hipFuncSetAttribute(reinterpret_cast<const void*>(as::stream_istft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, as::kStreamIstftLds);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(as::stream_istft_ola_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, as::kStreamOlaLds);
     if (e != hipSuccess) rc = rced_fail(RCED_ERR_HIP, "hipFuncSetAttribute(stream LDS): %s", hipGetErrorString(e));
   }
   if (!rc) rc = rced_reserve(m, lanes, as::kKeep + window_hops(s));   // the forward of a push allocates nothing

@@ -235,16 +235,19 @@ class InferenceEngine(FullyCNNTester):
                 w.close()
         return out
 
-    def denoise_stream(self, chunks, hops=8, nfft=512, sample_rate=8000, output_rate=None):
+    def denoise_stream(self, chunks, hops=8, nfft=512, sample_rate=8000, output_rate=None, rebuild="reference"):
         """denoise_pcm for audio that arrives in pieces: a generator over an iterable of 1-D PCM pieces of any size.  The
         pieces are re-blocked to whole hops (128 samples) and pushed, at most `hops` hops at a time, through a one-lane
         audio.StreamingDenoiser; every push's output is yielded as it comes (numpy float32, the result delayed by 640
         samples, zeros first), then what the stream still owed.  All pieces joined, with the leading zeros dropped, equal
         denoise_pcm of the joined input.
         sample_rate / output_rate: the pieces are mono float at sample_rate and re-blocked to that rate's hop; the lane is
-        StreamingDenoiser(sample_rate=..., output_rate=...), which see for the delay and the rates it refuses."""
+        StreamingDenoiser(sample_rate=..., output_rate=...), which see for the delay and the rates it refuses.
+        rebuild: "reference" or "ola", as in denoise_pcm; the delay is the same."""
         from . import audio
-        stream = audio.StreamingDenoiser(self.model, 1, max_hops=int(hops), nfft=nfft, sample_rate=sample_rate, output_rate=output_rate)
+        check_rebuild(rebuild)
+        stream = audio.StreamingDenoiser(self.model, 1, max_hops=int(hops), nfft=nfft, sample_rate=sample_rate, output_rate=output_rate,
+                                         rebuild=rebuild)
         hop = stream.hop_in
         try:
             held = np.zeros(0, np.float32)

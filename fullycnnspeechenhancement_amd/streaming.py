@@ -164,10 +164,11 @@ class _DenoiserLanes(_Lanes):
 
     _family = "rced_stream"
 
-    def __init__(self, model, lanes, max_hops, nfft):
+    def __init__(self, model, lanes, max_hops, nfft, rebuild="reference"):
         import ctypes
         h = ctypes.c_void_p()
-        _lib.check(_lib.load().rced_stream_create(model._handle, int(lanes), int(max_hops), int(nfft), ctypes.byref(h)))
+        _lib.check(_lib.load().rced_stream_create_ex(model._handle, int(lanes), int(max_hops), int(nfft), _args.REBUILDS.index(rebuild),
+                                                     ctypes.byref(h)))      # RCED_STREAM_REBUILD_REFERENCE = 0, _OLA = 1
         self._open(h, lanes, model.device, STEP, STEP, 1, "float32", "float32", STREAM_FINISH_MAX)
 
 
@@ -190,7 +191,9 @@ class StreamingDenoiser(object):
 
     model_or_engine: a model of this package (is_training=False) or an engine holding one as `.model`; the stream runs the
     forward form that model has selected.  max_hops: the most hops one push may carry (1..64); nfft: 512 (the reference's
-    rebuild as shipped) or 256.
+    rebuild as shipped) or 256.  rebuild: "reference", or "ola" -- the lane's output is then denoise_pcm(..., rebuild="ola"), weighted
+    overlap-add, at the same delay (hop h needs frames h and h - 1, and both are there when the reference rebuild hands out hop h);
+    nfft is checked and plays no part.
 
     sample_rate, channels, dtype ("float32" or "int16"), output_rate: the capture and playback device's format.  With the
     defaults this is the 8 kHz object above.  Otherwise a push takes [lanes, K * hop_in (* channels)] at sample_rate, hop_in =
@@ -200,8 +203,10 @@ class StreamingDenoiser(object):
     samples.  A rate at which the hop is not a whole number of frames (44.1 kHz: 128 * 441 / 80) is a ValueError naming the
     rate: denoise_pcm serves those rates offline."""
 
-    def __init__(self, model_or_engine, lanes, max_hops=8, nfft=512, sample_rate=8000, channels=1, dtype="float32", output_rate=None):
+    def __init__(self, model_or_engine, lanes, max_hops=8, nfft=512, sample_rate=8000, channels=1, dtype="float32", output_rate=None,
+                 rebuild="reference"):
         self._down = self._denoiser = self._up = None
+        self.rebuild = _args.check_rebuild(rebuild)
         self.model = getattr(model_or_engine, "model", model_or_engine)
         if getattr(self.model, "_handle", None) is None:
             raise ValueError("StreamingDenoiser needs an inference model (Model(is_training=False)) or an engine that holds one")
@@ -212,7 +217,7 @@ class StreamingDenoiser(object):
             if rate is not None and (rate < 1 or STEP * rate % SAMPLE_RATE):
                 raise ValueError("a hop of %d samples at 8 kHz is not a whole number of frames at %r Hz: streaming serves rates that are a "
                                  "multiple of 62.5 Hz, InferenceEngine.denoise_pcm(sample_rate=...) every rate" % (STEP, rate))
-        self._denoiser = _DenoiserLanes(self.model, self.lanes, self.max_hops, self.nfft)
+        self._denoiser = _DenoiserLanes(self.model, self.lanes, self.max_hops, self.nfft, self.rebuild)
         self._push8 = self._denoiser.push        # the one name every 8 kHz push goes through, finish's drain included
         self.hop_in = STEP * self.sample_rate // SAMPLE_RATE
         self.delay = stream_delay(self.sample_rate, self.output_rate, self.channels, dtype)

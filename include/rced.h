@@ -321,7 +321,18 @@ int rced_seg_snr(const float* ref_dev, int ref_stride, const float* est_dev, int
  * returns K*128 samples per lane, zeros until 640 samples have left, then off[i - 640].  Frames are the reference's own set
  * (rced_stft_num_frames(L), zero padding applied after pre-emphasis): pushing zeros is not finishing.  All state lives on the device;
  * after rced_stream_create a push is three launches on the caller's stream, allocates nothing and does not synchronise.  The input
- * buffers must stay valid until that work has run (the last launch reads them again).  A stream object is not thread-safe. ---- */
+ * buffers must stay valid until that work has run (the last launch reads them again).  A stream object is not thread-safe.
+ *
+ * A stream created with RCED_STREAM_REBUILD_OLA (rced_stream_create_ex) rebuilds by weighted overlap-add instead: `off` is the chain
+ * rced_stft -> rced_forward -> rced_istft_ola over the utterance's T = rced_stft_num_frames(L) frames, and everything else above holds
+ * as it stands -- the delay too: a push that brings a lane to H' hops has the masks of frames <= H' - 6 and emits hops <= H' - 6, and
+ * hop h needs frames h and h - 1.  With w = hamming(256), D[s] = w[s]^2 + w[s+128]^2 and x_t = irfft(mask_t * phase_t, 256), output
+ * position p of a push to a lane at H hops is hop t = H - 5 + p:
+ *   t < 0: exactly zero;   t = 0: e = w[s] x_0[s] / w[s]^2;   t >= 1: e = (w[s] x_t[s] + w[s+128] x_{t-1}[s+128]) / D[s];
+ * a hop a push emits is never the utterance's last.  y = e + 0.97 * (the sample before), through the hops in time order, y[0] = e[0].
+ * rced_stream_finish (L = 128*H + r): frames at or past T are not rebuilt, hop T has frame T - 1 alone (denominator w[s+128]^2), hops
+ * past T are not owed; a frame t < T counts in numerator and denominator even where the signal gave it only zeros (L < 256).
+ * A lane keeps the second half of its newest rebuilt frame and the last sample handed out; the state's size does not change. ---- */
 #define RCED_STREAM_DELAY 640       /* samples: 5 hops */
 #define RCED_STREAM_FINISH_MAX 768  /* floats per lane of rced_stream_finish's out_dev (at most 767 are owed) */
 typedef struct rced_stream rced_stream;
@@ -331,6 +342,12 @@ int rced_stream_delay(void);
  * else is RCED_ERR_ARG.  Runs the forward form the model handle has selected at each push, on the model's device.  The model must
  * outlive the stream: after rced_destroy(m) the stream's entry points return RCED_ERR_STATE (rced_stream_destroy stays valid). */
 int rced_stream_create(rced_model* m, int lanes, int max_hops, int nfft, rced_stream** out);
+/* The same with the rebuild named: RCED_STREAM_REBUILD_REFERENCE (what rced_stream_create makes, bit for bit) or
+ * RCED_STREAM_REBUILD_OLA (weighted overlap-add, above); any other value is RCED_ERR_ARG.  With overlap-add nfft is checked as above
+ * and plays no part, as in rced_istft_ola.  Push, finish, reset and destroy do not differ. */
+#define RCED_STREAM_REBUILD_REFERENCE 0
+#define RCED_STREAM_REBUILD_OLA 1
+int rced_stream_create_ex(rced_model* m, int lanes, int max_hops, int nfft, int rebuild, rced_stream** out);
 void rced_stream_destroy(rced_stream* s);
 
 /* pcm_dev [lanes, K*128] float32: the next K hops of every lane; out_dev [lanes, K*128].  active_dev: NULL (every lane) or [lanes]

@@ -2,13 +2,22 @@
 """Times the streaming denoiser (audio.StreamingDenoiser, CR-CED) for 256 lanes at K = 1, 8 and 32 hops per push, device-resident,
 with torch.cuda events: ms per push and frames/s, beside the offline PCM-to-PCM chain (stft_batch -> model -> istft_batch) at the
 same total frame count (256 utterances of K frames) and at BASELINE config-3 scale (256 x 512 frames).  One JSON line per row.
-A push recomputes 7 frames per lane for the CNN: `recompute` is (K + 7) / K."""
-import json, os, sys
+A push recomputes 7 frames per lane for the CNN: `recompute` is (K + 7) / K.
+--rebuild both (the default) times a reference-rebuild stream and an overlap-add stream (rebuild="ola") in the same run, in alternating
+rounds, and reports each one's median round and their ratio; --rebuild reference / ola times one of them."""
+import argparse, json, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 from fullycnnspeechenhancement_amd import audio, build_model
 from fullycnnspeechenhancement_amd import weights as _weights
+
+parser = argparse.ArgumentParser(description=__doc__)
+parser.add_argument("--rebuild", choices=("both", "reference", "ola"), default="both",
+                    help="the streams' rebuild; both (default): one stream of each, timed in alternating rounds of the same run")
+parser.add_argument("--rounds", type=int, default=5, help="timed rounds per stream; the median is reported")
+args = parser.parse_args()
+REBUILDS = ("reference", "ola") if args.rebuild == "both" else (args.rebuild,)
 
 LANES = 256
 model = build_model("FullyCNNV3", False, weights=_weights.synthetic_weights(3, seed=42))
@@ -37,15 +46,25 @@ def offline(n, t):
 
 
 for k in (1, 8, 32):
-    stream = audio.StreamingDenoiser(model, LANES, max_hops=k)
+    streams = {r: audio.StreamingDenoiser(model, LANES, max_hops=k, rebuild=r) for r in REBUILDS}
     pcm = torch.randn((LANES, k * 128), device="cuda") * 0.1
     reps = 2000 // k + 50                      # a second or so of pushes: every lane is far into its utterance
-    ms = timed(lambda: stream.push(pcm), reps)
+    rounds = {r: [] for r in REBUILDS}
+    for _ in range(args.rounds):               # reference, ola, reference, ola, ..: what else the machine does falls on both alike
+        for r in REBUILDS:
+            rounds[r].append(timed(lambda: streams[r].push(pcm), reps))
     off_ms = timed(offline(LANES, k), reps)
-    stream.close()
+    for s in streams.values():
+        s.close()
     frames = LANES * k
-    print(json.dumps({"lanes": LANES, "hops_per_push": k, "push_ms": ms, "stream_frames_per_s": frames / (ms * 1e-3),
-                      "recompute": (k + 7) / k, "offline_same_frames_ms": off_ms, "offline_same_frames_per_s": frames / (off_ms * 1e-3),
-                      "realtime_lanes_per_device": 16.0 * k / ms * LANES}))     # a hop is 16 ms of audio
+    push = {r: statistics.median(v) for r, v in rounds.items()}
+    row = {"lanes": LANES, "hops_per_push": k, "recompute": (k + 7) / k, "offline_same_frames_ms": off_ms,
+           "offline_same_frames_per_s": frames / (off_ms * 1e-3)}
+    for r, ms in push.items():
+        row[r] = {"push_ms": ms, "push_ms_rounds": [round(v, 5) for v in rounds[r]], "stream_frames_per_s": frames / (ms * 1e-3),
+                  "realtime_lanes_per_device": 16.0 * k / ms * LANES}     # a hop is 16 ms of audio
+    if len(push) == 2:
+        row["ola_over_reference"] = push["ola"] / push["reference"]
+    print(json.dumps(row), flush=True)
 ms = timed(offline(256, 512), 20)
 print(json.dumps({"offline_utterances": 256, "offline_frames_each": 512, "offline_ms": ms, "offline_frames_per_s": 256 * 512 / (ms * 1e-3)}))
