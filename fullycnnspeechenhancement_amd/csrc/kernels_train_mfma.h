@@ -82,30 +82,19 @@ __device__ unsigned long long g_tm[4][4];   // [wave][gemm, barrier 2, epilogue,
 #if RCED_TM_EXP != 0 && !defined(RCED_TIMING_ONLY)
 #error "RCED_TM_EXP builds compute wrong results: timing experiments only (tools/mkexp.sh ... -DRCED_TIMING_ONLY -DRCED_TM_EXP=...)"
 #endif
-#ifndef RCED_TM_OPQ_MIN
-#define RCED_TM_OPQ_MIN 1000   // prefetch size (VGPRs) from which the conv kernels' epilogue re-derives its lane coordinates
-                               // (64 paid while the largest dgrad spilled; with the loop-invariant staging channels nothing
-                               // spills and the recomputation only costs: 56.0 vs 56.9 ms per CR-CED step)
-#endif
-#ifndef RCED_TM_FIXCH
-#define RCED_TM_FIXCH 1   // staging stride chosen so that a thread's pieces share their channels (Stage<C>::kStride)
-#endif
 #ifndef RCED_TM_OCC
 #define RCED_TM_OCC 2   // workgroups per CU the register allocator must leave room for (conv / wgrad kernels): several
                         // of them sat at 260-300 VGPRs+AGPRs = ONE workgroup per CU; 2 costs a few spilled dwords in the
                         // largest, 3 spills hundreds of bytes and is slower (64.8 / 60.9 / 77.8 ms per CR-CED step)
 #endif
 
-// Remainder pass (RCED_TM_REM): a conv with 18 output channels fills two 16-row M-tiles 56 %.  As in the inference kernels
+// Remainder pass: a conv with 18 output channels fills two 16-row M-tiles 56 %.  As in the inference kernels
 // (kernels_fused_v3.h's ->18 layers, kernels_fused_chain.h's 17..24-channel layers) channels 0..15 run as ONE M-tile (the
 // main pass) and channels 16, 17 in a remainder pass whose 16 rows are (pixel phase p < 8, channel 16 + c): a column is a
 // group of 8 adjacent pixels, K = (TAPS + 7) * cin (row (p, c) holds the kernel shifted by p taps), a remainder tile = 128
 // pixels.  Per two-frame tile: 17 x K/4 + 3 x (K + 7 cin)/4 MFMAs instead of 34 x K/4 (-29 % for the 30 -> 18 dgrad, -36 %
 // for the 8 -> 18 forward).  tm_rem(cout) = channels of the remainder pass (0: none); only the 18-channel form is built.
-#ifndef RCED_TM_REM
-#define RCED_TM_REM 1
-#endif
-__host__ __device__ constexpr int tm_rem(int cout) { return (RCED_TM_REM && cout == 18) ? 2 : 0; }
+__host__ __device__ constexpr int tm_rem(int cout) { return cout == 18 ? 2 : 0; }
 // Pixel phases per remainder column.  16 / R = 8 rows pairs fill the M-tile, but a column stride of 8 pixels puts the 16 columns of an
 // operand read on the same banks whenever 8 * cin floats is a multiple of 256 bytes (cin = 8: 16-way conflicts -- 71 % of the LDS
 // cycles of the 8 -> 18 forward convolution were conflict cycles, profiles/r04_rocprof_train_step.txt; cin = 30: 4-way).  SEVEN phases
@@ -114,10 +103,7 @@ __host__ __device__ constexpr int tm_rem(int cout) { return (RCED_TM_REM && cout
 // pixels of a two-frame tile (round 5; the inference kernel's layer 1 does the same, kernels_fused_v3.h).  NOT for cin = 30 (the
 // 30 -> 18 dgrad inside bwd_fused_mfma<18,5,30>: 4-way at 8 phases, conflict-free at 7 -- and 12 % SLOWER, 2.24 -> 2.51 ms: that
 // kernel's waves are balanced to the MFMA counts of the 8-phase form).
-#ifndef RCED_TM_REM_P
-#define RCED_TM_REM_P 7
-#endif
-__host__ __device__ constexpr int tm_rem_p(int r, int cinp) { return r == 2 && cinp % 8 == 0 ? RCED_TM_REM_P : (r ? 16 / r : 0); }
+__host__ __device__ constexpr int tm_rem_p(int r, int cinp) { return r == 2 && cinp % 8 == 0 ? 7 : (r ? 16 / r : 0); }
 
 template <int CIN, int TAPS, int COUT>
 struct Geo {
@@ -231,10 +217,10 @@ template <int C, int NTHR = kThreads>
 struct Stage {
   static constexpr int kFrame = kF * C, kElems = kTF * kFrame, kVec = kElems / 4;
   static constexpr int kMod = C % 4 == 0 ? C / 4 : C / 2;              // pieces per channel period
-  static constexpr int kStride = RCED_TM_FIXCH ? NTHR - NTHR % kMod : NTHR;
+  static constexpr int kStride = NTHR - NTHR % kMod;
   static constexpr int kPer = (kVec + kStride - 1) / kStride;
   static_assert(C % 2 == 0 && kElems % 4 == 0, "wide staging needs an even channel count");
-  static_assert(!RCED_TM_FIXCH || (4 * kStride) % C == 0, "a thread's pieces all start at the same channel");
+  static_assert((4 * kStride) % C == 0, "a thread's pieces all start at the same channel");
 };
 template <int C, int NTHR = kThreads>
 __device__ __forceinline__ void tile_fetch(const float* __restrict__ base, int frame0, int frames, int tid,
@@ -243,17 +229,13 @@ __device__ __forceinline__ void tile_fetch(const float* __restrict__ base, int f
   const float* src = base + (size_t)frame0 * St::kFrame;
   const int left = frames - frame0;
   if (left >= kTF) {   // whole tile (wave-uniform): straight-line 16-byte loads, no per-piece bounds logic
+    // (plain loads: the nontemporal form was a switch defined below this function, so no built kernel ever had it -- DESIGN 3.5)
     const f32x4* s4 = reinterpret_cast<const f32x4*>(src) + tid;
     const bool active = St::kStride == NTHR || tid < St::kStride;
-#if RCED_TM_NT
-#define RCED_TM_LD(p) __builtin_nontemporal_load(p)
-#else
-#define RCED_TM_LD(p) (*(p))
-#endif
 #pragma unroll
     for (int i = 0; i < St::kPer; ++i) {
-      if ((i + 1) * St::kStride <= St::kVec) pre[i] = active ? RCED_TM_LD(s4 + i * St::kStride) : f32x4{0.f, 0.f, 0.f, 0.f};
-      else pre[i] = (active && tid + i * St::kStride < St::kVec) ? RCED_TM_LD(s4 + i * St::kStride) : f32x4{0.f, 0.f, 0.f, 0.f};
+      if ((i + 1) * St::kStride <= St::kVec) pre[i] = active ? s4[i * St::kStride] : f32x4{0.f, 0.f, 0.f, 0.f};
+      else pre[i] = (active && tid + i * St::kStride < St::kVec) ? s4[i * St::kStride] : f32x4{0.f, 0.f, 0.f, 0.f};
     }
     return;
   }
@@ -275,10 +257,10 @@ __device__ __forceinline__ void tile_fetch(const float* __restrict__ base, int f
   }
 }
 // One 16-byte piece of a WHOLE tile (wave-uniform precondition: frames - frame0 >= kTF): what tile_fetch's full-tile branch
-// does for piece I.  The kernels issue the next tile's pieces one at a time between the MFMAs of the current tile
-// (gemm_pass's `each`, the wgrad loops): issued in one burst right behind the barrier they took 3-4 k cycles per tile in
-// which nothing else ran (s_memtime stamps of bwd_fused_mfma: the memory pipeline's queues fill and vector-memory issue
-// blocks), 14 % of the fused backward kernel.
+// does for piece I.  Left over from the retired piece-by-piece ("spread") issue of the next tile's loads: no
+// kernel executes it, but bwd_fused_mfma's `each` still names it in an arm that is never taken -- without that arm hipcc
+// compiles the kernel to other code (same opcode counts, another schedule; one instantiation loses its 12 bytes of scratch),
+// and this header's kernels are kept instruction for instruction.  To go, with the arm, behind a timing comparison.
 template <int C, int NTHR, int I>
 __device__ __forceinline__ void tile_fetch_piece(const float* __restrict__ base, int frame0, int tid,
                                                  f32x4 (&pre)[Stage<C, NTHR>::kPer]) {
@@ -292,44 +274,6 @@ __device__ __forceinline__ void tile_fetch_piece(const float* __restrict__ base,
                       ((I + 1) * St::kStride <= St::kVec || tid + I * St::kStride < St::kVec);
   if (active) pre[I] = *reinterpret_cast<const f32x4*>(sb + voff);   // idle lanes: the commit never looks at theirs
 }
-// The same piece by LDS-DMA into a raw copy of the tile in LDS (`stg`, float4 q of the tile at stg + 4 q): no VGPR holds
-// the next tile while the current one is computed.  A wave's 64 lanes are 64 consecutive float4, i.e. one contiguous
-// 1-KiB transfer (global_load_lds_dwordx4: lane i writes M0 + 16 i); wave-uniform source base + one lane offset.
-// `tid` is the thread of the NTHR-thread mapping whose piece this is, not necessarily the issuing thread: the transfer
-// touches no register, so any wave can issue any wave's share (bwd_fused_mfma: the wgrad half issues the whole tile).
-template <int C, int NTHR, int I>
-__device__ __forceinline__ void tile_dma_piece(const float* __restrict__ base, int frame0, int tid, float* stg) {
-  using St = Stage<C, NTHR>;
-  static_assert(I < St::kPer, "piece index");
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const bool active = (St::kStride == NTHR || tid < St::kStride) &&
-                      ((I + 1) * St::kStride <= St::kVec || tid + I * St::kStride < St::kVec);
-  // (the source base is wave-uniform by construction; taken through readfirstlane because hipcc otherwise hands the "s"
-  // operand of the inline asm a VGPR pair in some instantiations -- an assembler error, not a silent one)
-  const unsigned long long a = reinterpret_cast<unsigned long long>(base + (size_t)frame0 * St::kFrame + (size_t)(I * St::kStride + 64 * wave) * 4);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-  const float* src = reinterpret_cast<const float*>(((unsigned long long)hi << 32) | lo);
-  if (active) lds_dma16s(src, (unsigned)(tid & 63) * 16u, stg + (I * St::kStride + 64 * wave) * 4);
-}
-// staging copy -> the registers tile_commit* take (transient: only while a tile is committed)
-template <int C, int NTHR>
-__device__ __forceinline__ void stage_load(const float* stg, int tid, f32x4 (&pre)[Stage<C, NTHR>::kPer]) {
-  using St = Stage<C, NTHR>;
-  const f32x4* s4 = reinterpret_cast<const f32x4*>(stg) + tid;
-#pragma unroll
-  for (int i = 0; i < St::kPer; ++i)
-    if ((St::kStride == NTHR || tid < St::kStride) && ((i + 1) * St::kStride <= St::kVec || tid + i * St::kStride < St::kVec))
-      pre[i] = s4[i * St::kStride];
-}
-// a tile cut short by the end of the batch: tile_fetch's bounds-checked loads, then into the staging copy
-template <int C, int NTHR>
-__device__ __forceinline__ void stage_store(float* stg, int tid, const f32x4 (&pre)[Stage<C, NTHR>::kPer]) {
-  using St = Stage<C, NTHR>;
-  f32x4* s4 = reinterpret_cast<f32x4*>(stg) + tid;
-#pragma unroll
-  for (int i = 0; i < St::kPer; ++i)
-    if ((St::kStride == NTHR || tid < St::kStride) && tid + i * St::kStride < St::kVec) s4[i * St::kStride] = pre[i];
-}
 template <int I, int N, class F>
 __device__ __forceinline__ void tm_static_for(F&& f) {
   if constexpr (I < N) {
@@ -337,28 +281,6 @@ __device__ __forceinline__ void tm_static_for(F&& f) {
     tm_static_for<I + 1, N>(f);
   }
 }
-#ifndef RCED_TM_BWD_DMA
-#define RCED_TM_BWD_DMA 0     // 1: bwd_fused_mfma stages the next tile by LDS-DMA into a raw LDS copy, issued by the wgrad half
-                              // (no VGPR holds the next tile: no scratch).  Measured slower than VGPR staging in every form
-                              // (all waves in a burst 2.99 / 2.05 ms, spread over the MFMA phase 3.29 / 2.13, wgrad half alone
-                              // 2.99 / 2.24, against 2.86 / 1.94 ms for the two CR-CED shapes): kept as a switch for the record
-#endif
-#ifndef RCED_TM_NT
-#define RCED_TM_NT 1          // the tile fetches are nontemporal loads (every staged byte is used once): -0.6 ... -1 % per kernel (A/B, round 3)
-#endif
-#ifndef RCED_TM_BWD_STAGGER
-#define RCED_TM_BWD_STAGGER 1 // VGPR staging: the wgrad half issues its share of the next tile's loads at the start of the MFMA
-                              // phase, the dgrad half its share BEHIND its MFMA pass (in front of its epilogue): two half-size
-                              // bursts, each beside the other half's MFMAs, instead of one that stalls all eight waves
-#endif
-#ifndef RCED_TM_BWD_DEPTH
-#define RCED_TM_BWD_DEPTH (RCED_TM_BWD_DMA ? 2 : 1)   // operand prefetch depth of the fused backward kernel's dgrad pass
-#endif
-#ifndef RCED_TM_SPREAD
-#define RCED_TM_SPREAD 0   // 1: the next tile's loads are issued piece by piece inside the MFMA phase; 0: in one burst.
-                           // Measured (round 3, CR-CED step): spread 55.1 ms, burst 51.5 ms -- a load that finds the memory
-                           // pipeline's queues full blocks its wave, and with it that wave's MFMAs, piece after piece
-#endif
 // dst index of element (frame fr, offset r inside the frame) = base_row(fr) * ROWSTRIDE-style mapping given by MAP
 // Input transform applied while committing a tile: the producer layer's BatchNorm + ReLU (module.py:28-33),
 //   act = relu(a * z + b),   a = gamma * rstd,  b = beta - a * mu   (per channel; bn_act_fwd2 / bwd_route2 use the
@@ -398,10 +320,9 @@ __device__ __forceinline__ void tile_commit_bnrelu(float* lds, int tid, const f3
                                                    const float* table, int frame0, int frames) {
   using St = Stage<C, NTHR>;
   static_assert(St::kFrame % C == 0 && C % 2 == 0, "frames start at channel 0; float2 pieces stay inside a pixel");
-  constexpr int kStep = (4 * St::kStride) % C;   // 0 with RCED_TM_FIXCH
   int c = (4 * tid) % C;
   f32x2 ta[2], tb[2];
-  auto load_tables = [&]() {
+  auto load_tables = [&]() {      // (a lambda, here and in tile_commit_bnbwd: written in line, the same reads compile to other code)
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       int ch = c + 2 * h;
@@ -410,11 +331,10 @@ __device__ __forceinline__ void tile_commit_bnrelu(float* lds, int tid, const f3
       tb[h] = *reinterpret_cast<const f32x2*>(table + C + ch);
     }
   };
-  if (kStep == 0) load_tables();
+  load_tables();
 #pragma unroll
   for (int i = 0; i < St::kPer; ++i) {
     const int q = tid + i * St::kStride;
-    if (kStep != 0) load_tables();
     if (q < St::kVec && tid < St::kStride) {
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -426,8 +346,6 @@ __device__ __forceinline__ void tile_commit_bnrelu(float* lds, int tid, const f3
         *reinterpret_cast<f32x2*>(lds + map(fr, r)) = v;
       }
     }
-    c += kStep;
-    if (c >= C) c -= C;
   }
 }
 
@@ -466,7 +384,6 @@ __device__ __forceinline__ void tile_commit_bnbwd(float* lds, int tid, const f32
                                                   int frame0, int frames, bool mask, EXTRA extra = EXTRA()) {
   using St = Stage<C, NTHR>;
   static_assert(St::kFrame % C == 0 && C % 2 == 0, "frames start at channel 0; float2 pieces stay inside a pixel");
-  constexpr int kStep = (4 * St::kStride) % C;   // 0 with RCED_TM_FIXCH: the tables are read once per commit
   int c = (4 * tid) % C;
   f32x2 tA[2], tB[2], tK[2], tF[2];
   auto load_tables = [&]() {
@@ -480,11 +397,10 @@ __device__ __forceinline__ void tile_commit_bnbwd(float* lds, int tid, const f32
       tF[h] = *reinterpret_cast<const f32x2*>(table + 3 * C + ch);
     }
   };
-  if (kStep == 0) load_tables();
+  load_tables();      // once per commit: every piece of the thread starts at channel c (Stage::kStride)
 #pragma unroll
   for (int i = 0; i < St::kPer; ++i) {
     const int q = tid + i * St::kStride;
-    if (kStep != 0) load_tables();
     if (q < St::kVec && tid < St::kStride) {
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -503,8 +419,6 @@ __device__ __forceinline__ void tile_commit_bnbwd(float* lds, int tid, const f32
         extra(fr, r, v);
       }
     }
-    c += kStep;
-    if (c >= C) c -= C;
   }
 }
 
@@ -539,14 +453,8 @@ struct SumArgs {
 // in registers and only then reduced over the lanes and added to the wave's record of doubles: the reduction (64 DPP adds,
 // 16 conversions, 16 double adds per wave and two-M-tile tile) was a fifth of the forward convolutions' non-MFMA
 // instructions when done per tile.  kSumFlush tiles x <= 5 values per lane stay far inside fp32 (the round-2 form summed 5).
-#ifndef RCED_TM_SUMFLUSH
-#define RCED_TM_SUMFLUSH 4
-#endif
-constexpr int kSumFlush = RCED_TM_SUMFLUSH;
-#ifndef RCED_TM_BWD_CARRY
-#define RCED_TM_BWD_CARRY 0     // 1: the fused backward kernel carries its masked sums too -- it sits at 256 VGPRs (10-12 dwords of
-                                // scratch with them) and gains nothing (2.407 / 1.895 vs 2.405 / 1.889 ms): off
-#endif
+// The forward and dgrad convolutions carry them; the fused backward kernel, which sits at 256 VGPRs, flushes every tile.
+constexpr int kSumFlush = 4;
 template <int MT>
 struct SumState {
   float p1[MT][4], p2[MT][4], pr1[2], pr2[2];
@@ -560,28 +468,22 @@ struct SumState {
 };
 // ---------------------------------------------------------------------------------------------
 // fp32 quality on the bf16 matrix pipe for the forward convolutions (kernels_final_x6.h): the input tile lives
-// in LDS as THREE bf16 planes [pixel][channel] (x = h + m + l, exact to 2^-24; channel stride rounded to 4 so that a lane's
-// eight consecutive k of a pixel's im2col window start 8-byte aligned), the packet holds the weights the same way
+// in LDS as THREE bf16 planes [pixel][channel] (x = h + m + l, exact to 2^-24; channel stride = the even-padded channel count,
+// so a lane's eight consecutive k of a pixel's im2col window start 4-byte aligned), the packet holds the weights the same way
 // ([step][M-tile][part][lane] x 8 bf16, k = 32 S + 8 kq + e), and a product is six v_mfma_f32_16x16x32_bf16 (m m, l h, h l,
 // m h, h m, h h) into the fp32 accumulator: 6 x 16 cycles per K = 32 where the fp32 pipe takes 8 x 32.  The epilogue
 // (conv_tile) does not change: same accumulator layout.  Built for the shapes without a remainder pass.
 // ---------------------------------------------------------------------------------------------
 typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-// channel stride of a plane (bf16 elements): the even-padded channel count rounded to 4 (8-byte aligned windows), plus 4 where a
-// column's stride (ph pixels) would be a multiple of 128 bytes -- all 16 columns of a B fragment on the same banks
-// (30 -> 32 channels with pixel-pair columns: measured 1.50 ms against 0.85 ms for the fp32 kernel)
-#ifndef RCED_X6_ALIGN
-#define RCED_X6_ALIGN 2      // channel stride granularity of the planes: 4 (8-byte aligned windows, two ds_read_b64 per fragment) or
-                             // 2 (the even-padded channel count itself: no K padding per tap, four ds_read_b32 per fragment).
-                             // Measured on the 18 -> 30 forward: K 100 -> 90 (four steps -> three): 0.85 -> 0.78 ms
-#endif
+// channel stride of a plane (bf16 elements): the even-padded channel count itself (no K padding per tap; a fragment is four
+// ds_read_b32), plus 2 where a column's stride (ph pixels) would be a multiple of 128 bytes -- all 16 columns of a B fragment
+// on the same banks
 __host__ __device__ constexpr int x6_cs(int cin, int ph) {
-  const int cs = ((((cin + 1) & ~1) + RCED_X6_ALIGN - 1) / RCED_X6_ALIGN) * RCED_X6_ALIGN;
-  return (ph * cs * 2) % 128 == 0 ? cs + RCED_X6_ALIGN : cs;
+  const int cs = ((((cin + 1) & ~1) + 1) / 2) * 2;   // = (cin + 1) & ~1; spelled as pack_packet_x6's code object has it (run time there)
+  return (ph * cs * 2) % 128 == 0 ? cs + 2 : cs;
 }
 template <int CIN, int TAPS, int COUT>
 struct GeoX6 {
@@ -591,10 +493,8 @@ struct GeoX6 {
   static constexpr int kSteps = (kKX + 31) / 32;
   static constexpr int kPlane = ((G::kInRows * kCS + 32 + 7) / 8) * 8;   // bf16 per part; + 32: the last step reads past its window
   static constexpr int kInFloats = ((3 * kPlane / 2 + 3) / 4) * 4;       // the three parts, counted in floats
-  // remainder pass (G::kR channels past the first M-tile; Geo): rows (pixel phase, channel) over K = (TAPS + P - 1) * kCS
-  static constexpr int kKXR = G::kR ? (TAPS + G::kP - 1) * kCS : 0, kStepsR = (kKXR + 31) / 32;
-  static constexpr int kDataMainFloats = kSteps * G::kMTm * 3 * 64 * 4;  // A fragments: 16 bytes per (step, M-tile, part, lane)
-  static constexpr int kDataFloats = kDataMainFloats + kStepsR * 3 * 64 * 4;
+  static_assert(G::kR == 0, "the three-part bf16 form has no remainder pass");
+  static constexpr int kDataFloats = kSteps * G::kMT * 3 * 64 * 4;       // A fragments: 16 bytes per (step, M-tile, part, lane)
   static constexpr int kPacket = kDataFloats + 32;                       // + shift[32]
   static constexpr int kShiftOff = kDataFloats;
   static constexpr int kLdsFloats = kInFloats + kPacket;
@@ -632,12 +532,10 @@ __device__ __forceinline__ X6Parts x6_split8(const f32x2 (&q)[4]) {
   r.l = s16x8{pl[0].x, pl[0].y, pl[1].x, pl[1].y, pl[2].x, pl[2].y, pl[3].x, pl[3].y};
   return r;
 }
-#ifndef RCED_TM_WG_X6_B
-#define RCED_TM_WG_X6_B 1    // bwd_fused_mfma<18,5,30>: whole runs of eight pixel groups of the wgrad half in the three-part bf16 form:
-                             // 2.38 -> 2.28 ms.  (The 30 -> 8 kernel's wgrad has ONE N-tile: its 19 A fragments per 32 pixel pairs would each be
-                             // split for six MFMAs -- 36 VALU for 96 cycles of MFMA: no gain, not built.)
-#endif
-__host__ __device__ constexpr bool bwd_wg_x6(int cin, int taps, int cout) { return RCED_TM_WG_X6_B && cin == 18 && taps == 5 && cout == 30; }
+// bwd_fused_mfma<18,5,30>: whole runs of eight pixel groups of the wgrad half in the three-part bf16 form: 2.38 -> 2.28 ms.
+// (The 30 -> 8 kernel's wgrad has ONE N-tile: its 19 A fragments per 32 pixel pairs would each be split for six MFMAs --
+// 36 VALU for 96 cycles of MFMA: no gain, not built.)
+__host__ __device__ constexpr bool bwd_wg_x6(int cin, int taps, int cout) { return cin == 18 && taps == 5 && cout == 30; }
 // in: part 0 of the tile at pixel 0 (bf16), the other parts PLANE elements further; off0 / offx: this lane's window start of
 // its first regular / its extra column tile; TSTRIDE: elements between a wave's consecutive column tiles
 template <int NR, int NX, int MT, int STEPS, int TSTRIDE, int PLANE>
@@ -656,14 +554,9 @@ __device__ __forceinline__ void gemm_pass_x6(const unsigned short* in, int off0,
 #pragma unroll
       for (int p = 0; p < 3; ++p) {
         const unsigned short* q = in + (t < NR ? off0 + t * TSTRIDE : offx) + 32 * s + p * PLANE;
-        if constexpr (RCED_X6_ALIGN == 4) {
-          const s16x4 lo = *reinterpret_cast<const s16x4*>(q), hi = *reinterpret_cast<const s16x4*>(q + 4);   // 8-byte aligned
-          b[t][p] = s16x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-        } else {
-          const s16x2 q0 = *reinterpret_cast<const s16x2*>(q), q1 = *reinterpret_cast<const s16x2*>(q + 2),
-                      q2 = *reinterpret_cast<const s16x2*>(q + 4), q3 = *reinterpret_cast<const s16x2*>(q + 6);   // 4-byte aligned
-          b[t][p] = s16x8{q0.x, q0.y, q1.x, q1.y, q2.x, q2.y, q3.x, q3.y};
-        }
+        const s16x2 q0 = *reinterpret_cast<const s16x2*>(q), q1 = *reinterpret_cast<const s16x2*>(q + 2),
+                    q2 = *reinterpret_cast<const s16x2*>(q + 4), q3 = *reinterpret_cast<const s16x2*>(q + 6);   // 4-byte aligned
+        b[t][p] = s16x8{q0.x, q0.y, q1.x, q1.y, q2.x, q2.y, q3.x, q3.y};
       }
 #pragma unroll
     for (int t = 0; t < NT; ++t)
@@ -726,6 +619,8 @@ __device__ __forceinline__ void tile_commit_x6(unsigned short* planes, int tid, 
 // transpose = 1: the dgrad's packet (pack_packet's convention: cin / cout are those of the conv being packed).
 static __global__ void pack_packet_x6(const float* __restrict__ w, const float* __restrict__ shift, int taps, int cin, int cout,
                                       int ph, float* __restrict__ packet, int transpose = 0) {
+  // (The remainder rows below are never reached: no shape packed here has 18 output channels.  They stay because this kernel's
+  // code object is kept instruction for instruction.)
   const int R = ph == 1 ? tm_rem(cout) : 0, P = tm_rem_p(R, (cin + 1) & ~1);   // (as Geo::kP)
   const int cs = x6_cs(cin, ph), K = (taps + ph - 1) * cs, steps = (K + 31) / 32, MT = R ? 1 : (cout + 15) / 16;
   const int KR = R ? (taps + P - 1) * cs : 0, stepsR = (KR + 31) / 32;
@@ -781,19 +676,20 @@ constexpr int conv_shift_off() {      // floats in front of the packet's shift[3
   if constexpr (X6) return GeoX6<CIN, TAPS, COUT>::kShiftOff;
   else return Geo<CIN, TAPS, COUT>::kData;
 }
-template <int CIN, int TAPS, int COUT, bool ACCUM, bool STATS, int NX, bool SUMS = false, bool OPQ = false, bool SUMX = false,
-          class Each = chain::NoEach, bool EXTACC = false, int DEPTH = 2, bool KS = false, int XMT = -1, bool X6 = false>
+template <int CIN, int TAPS, int COUT, bool ACCUM, bool STATS, int NX, bool SUMS = false, bool SUMX = false,
+          class Each = chain::NoEach, bool EXTACC = false, int DEPTH = 2, bool KS = false, bool X6 = false>
 __device__ __forceinline__ void conv_tile(const float* lds_in, const float* lds_w, float* __restrict__ out, int frame0,
                                           int frames, int wave, int lane,
                                           double* red_wave, const float* zt = nullptr, const float* stab = nullptr,
                                           Each each = Each(), f32x4* acc_store = nullptr, const f32x4* ks_own = nullptr,
                                           const float* ks_lds = nullptr) {
   SumState<Geo<CIN, TAPS, COUT>::kMTm> local_sums;
-  conv_tile<CIN, TAPS, COUT, ACCUM, STATS, NX, SUMS, OPQ, SUMX, Each, EXTACC, DEPTH, KS, XMT, X6>(
+  conv_tile<CIN, TAPS, COUT, ACCUM, STATS, NX, SUMS, SUMX, Each, EXTACC, DEPTH, KS, X6>(
       lds_in, lds_w, out, frame0, frames, wave, lane, red_wave, zt, stab, each, acc_store, ks_own, ks_lds, local_sums, false, true);
 }
-template <int CIN, int TAPS, int COUT, bool ACCUM, bool STATS, int NX, bool SUMS = false, bool OPQ = false, bool SUMX = false,
-          class Each = chain::NoEach, bool EXTACC = false, int DEPTH = 2, bool KS = false, int XMT = -1, bool X6 = false>
+// DEPTH: operand prefetch depth of the fp32 pass (2; the fused backward kernel's dgrad half, short of registers, runs 1)
+template <int CIN, int TAPS, int COUT, bool ACCUM, bool STATS, int NX, bool SUMS = false, bool SUMX = false,
+          class Each = chain::NoEach, bool EXTACC = false, int DEPTH = 2, bool KS = false, bool X6 = false>
 __device__ __forceinline__ void conv_tile(const float* lds_in, const float* lds_w, float* __restrict__ out, int frame0,
                                           int frames, int wave, int lane, double* red_wave, const float* zt, const float* stab,
                                           Each each, f32x4* acc_store, const f32x4* ks_own, const float* ks_lds,
@@ -808,13 +704,10 @@ __device__ __forceinline__ void conv_tile(const float* lds_in, const float* lds_
   static_assert(!(SUMS && (STATS || (COUT & 1))), "SUMS: dgrads with an even cout");
   static_assert(!(SUMS && SUMX && (ACCUM || G::kPH != 1)), "SUMX: the fused backward kernel's overwriting, unpaired dgrad");
   constexpr int NR = G::kRegular, NT = NR + NX, MT = G::kMTm, PH = G::kPH;   // MT: M-tiles of the MAIN pass
-  static_assert(!X6 || (!KS && XMT < 0 && (!SUMS || SUMX) && !ACCUM), "the three-part bf16 form: overwriting, no K split");
+  static_assert(!X6 || (!KS && (!SUMS || SUMX) && !ACCUM), "the three-part bf16 form: overwriting, no K split");
   constexpr int kShiftOff = conv_shift_off<X6, CIN, TAPS, COUT>();
   const float* in = lds_in + G::kG * G::kCinP;
-  // XMT >= 0 (two-M-tile shapes, RCED_TM_MSPLIT): the odd column tile is cut by M-tile -- this wave's extra slot computes
-  // and stores only M-tile XMT of column tile 4 NR; another wave has the other half
-  const int xwave = XMT >= 0 ? 0 : wave;
-  const int xtile = NR * kWaves + xwave;
+  const int xtile = NR * kWaves + wave;
   // acc_store: the caller's registers for the tile's accumulators (bwd_fused_mfma shares them with its wgrad half's
   // kernel-lifetime accumulators: a wave has one role, but two arrays are both live in every wave for the allocator)
   f32x4 acc_local[EXTACC ? 1 : NT][EXTACC ? 1 : MT];
@@ -860,21 +753,12 @@ __device__ __forceinline__ void conv_tile(const float* lds_in, const float* lds_
       }
     } else {
     if (!(RCED_TM_EXP & 4))
-      chain::gemm_pass<NR, NX, MT, G::kKP, PH * 64 * G::kCinP, DEPTH, XMT, chain::NoPre, Each>(
+      chain::gemm_pass<NR, NX, MT, G::kKP, PH * 64 * G::kCinP, DEPTH, -1, chain::NoPre, Each>(
           in, (PH * px0 - G::kG) * G::kCinP + 2 * kq, (PH * pxx - G::kG) * G::kCinP + 2 * kq, lds_w, lane, acc, chain::NoPre(), each);
     }
     each(-1);   // behind the pass, in front of the epilogue (bwd_fused_mfma's dgrad half issues its loads here)
   }
-  // The epilogue's lane coordinates are re-derived behind an opaque barrier: left visible, hipcc hoists every per-lane
-  // address of the epilogue (pixel -> frame / bin splits, LDS offsets of the z tile, 64-bit row offsets) out of the tile
-  // loop, keeps them live across the MFMA pass and spills them; each reload in the epilogue is a scratch load +
-  // s_waitcnt vmcnt(0), which also waits for the global stores issued just before it -- a full HBM write round trip per
-  // reload, 15.8 k cycles of epilogue per tile against 10.5 k of MFMA pass (s_memtime stamps, RCED_TM_STAMPS).
-  // Only where the prefetched next tile is large enough for that to happen (OPQ): the kernels that have the registers
-  // lose 5-10 % to the recomputation.
-  int le = lane;
-  if constexpr (OPQ) asm volatile("" : "+v"(le));
-  const int n = le & 15, kq = le >> 4;
+  const int n = lane & 15, kq = lane >> 4;
   const int px0 = 16 * wave + n, pxx = 16 * xtile + n;
   // the lane's shares of sum z, sum z^2 (SUMS: sum d_u, sum d_u z), fp32: the caller's (carried over kSumFlush tiles) or local
   // S: the caller's (carried over kSumFlush tiles) or the wrapper's local one -- by reference, never through a pointer select
@@ -923,17 +807,13 @@ __device__ __forceinline__ void conv_tile(const float* lds_in, const float* lds_
   // same for every slot) plus wave-uniform terms -- no per-lane pixel -> (frame, bin) split, no validity masks, no 64-bit
   // lane arithmetic (what used to be hoisted out of the tile loop for every slot and spilled).  The two mixed tiles keep
   // the per-lane path below.
-#ifndef RCED_TM_CLEAN
-#define RCED_TM_CLEAN 1
-#endif
-  constexpr bool kCleanPath = RCED_TM_CLEAN && (COUT % 2 == 0) && !(SUMS && !SUMX) && !(RCED_TM_EXP & 2);
+  constexpr bool kCleanPath = (COUT % 2 == 0) && !(SUMS && !SUMX) && !(RCED_TM_EXP & 2);
   const int px_lane0 = PH == 2 ? 2 * px0 + (kq >> 1) : px0;                      // this lane's pixel in slot 0
   const unsigned lane_b = (unsigned)(px_lane0 * COUT + (PH == 2 ? 4 * (kq & 1) : 4 * kq)) * 4u;   // bytes
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     if constexpr (kCleanPath) {
-      const bool xslot = XMT >= 0 && t == NR;                        // the M-split odd tile: column tile 4 NR for every wave
-      const int k = (xslot ? 0 : wave) + kWaves * t, pbeg = 16 * PH * k, pend = pbeg + 16 * PH - 1;
+      const int k = wave + kWaves * t, pbeg = 16 * PH * k, pend = pbeg + 16 * PH - 1;
       const bool in0 = pend < kF, in1 = pbeg >= G::kS && pend < G::kS + kF;
       if (in0 || in1) {
         const int fr = in1 ? 1 : 0;
@@ -943,18 +823,15 @@ __device__ __forceinline__ void conv_tile(const float* lds_in, const float* lds_
           for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-              if (XMT >= 0 && t == NR && mt != XMT) continue;
               const float v = acc[t][mt][j];
               p1[mt][j] += v;
               p2[mt][j] = fmaf(v, v, p2[mt][j]);
             }
         }
-        static_assert(XMT < 0 || !SUMS, "M-split odd tiles: forward shapes only");
         if constexpr (SUMS && SUMX) {
           const char* zb = reinterpret_cast<const char*>(zt) + lane_b;
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) {
-            constexpr int dummy = 0; (void)dummy;
             const int imm = ((G::kG + 64 * t) * COUT + 16 * mt) * 4;
             const int co0 = 16 * mt + 4 * kq;
             f32x4 xv = {0.f, 0.f, 0.f, 0.f};
@@ -971,10 +848,9 @@ __device__ __forceinline__ void conv_tile(const float* lds_in, const float* lds_
         }
         // wave-uniform base of this slot (scalar registers) + the lane offset: the saddr form of the global accesses
         char* ob = reinterpret_cast<char*>(out + (size_t)(frame0 + fr) * (kF * COUT)) +
-                   ((64 * PH * t - (xslot ? 16 * PH * wave : 0)) * COUT - (in1 ? G::kS * COUT : 0)) * 4;
+                   (64 * PH * t * COUT - (in1 ? G::kS * COUT : 0)) * 4;
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-          if (XMT >= 0 && t == NR && mt != XMT) continue;
           const f32x4 v = acc[t][mt];
           char* p = ob + 16 * mt * 4 + lane_b;
           if (PH == 2 || 16 * mt + 16 <= COUT) {
@@ -1007,7 +883,6 @@ __device__ __forceinline__ void conv_tile(const float* lds_in, const float* lds_
       for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          if (XMT >= 0 && t == NR && mt != XMT) continue;
           const float v = acc[t][mt][j];
           p1[mt][j] += v;
           p2[mt][j] = fmaf(v, v, p2[mt][j]);
@@ -1061,7 +936,6 @@ __device__ __forceinline__ void conv_tile(const float* lds_in, const float* lds_
     if ((RCED_TM_EXP & 2) && acc[t][0][0] != 12345.678f) continue;
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
-      if (XMT >= 0 && t == NR && mt != XMT) continue;
       const int co0 = PH == 2 ? 4 * (kq & 1) : 16 * mt + 4 * kq;
       f32x4 v = acc[t][mt];
       if (co0 + 1 < COUT || (co0 < COUT && (COUT & 1))) {
@@ -1094,7 +968,7 @@ __device__ __forceinline__ void conv_tile(const float* lds_in, const float* lds_
   // 3 - rt % 4 (wave 0 carries the odd main tile).  Lane (column n, kq) ends up with rows 4 kq + j = (phase 2 kq + j / 2,
   // channel 16 + j % 2): two pixels x two channels.  Three tiles per two-frame tile, so everything here is per lane.
   if constexpr (G::kR > 0) {
-    static_assert(G::kR == 2 && (COUT & 1) == 0 && !KS, "the 18-channel form");
+    static_assert(G::kR == 2 && (COUT & 1) == 0 && !KS && !X6, "the 18-channel form, fp32 pipe only");
     constexpr int P = G::kP, KR = G::kKR;
     const float* wr = lds_w + G::kDataMain;
     const f32x4 rsh = *reinterpret_cast<const f32x4*>(lds_w + kShiftOff + 16 + 4 * kq);
@@ -1102,12 +976,6 @@ __device__ __forceinline__ void conv_tile(const float* lds_in, const float* lds_
     for (int rt = 3 - wave; rt < G::kNRT; rt += kWaves) {
       const int pb = P * (16 * rt + n);                    // first pixel of this lane's column
       f32x4 racc[1][1] = {{rsh}};
-      if constexpr (X6) {
-        using GX = GeoX6<CIN, TAPS, COUT>;
-        const unsigned short* inx = reinterpret_cast<const unsigned short*>(lds_in) + G::kG * GX::kCS;
-        gemm_pass_x6<1, 0, 1, GX::kStepsR, 0, GX::kPlane>(inx, (pb - G::kG) * GX::kCS + 8 * kq, 0,
-                                                          reinterpret_cast<const s16x8*>(lds_w) + GX::kSteps * MT * 3 * 64, lane, racc);
-      } else
       chain::gemm_pass<1, 0, 1, KR, 0, 1>(in, (pb - G::kG) * G::kCinP + 2 * kq, 0, wr, lane, racc);
       const float vv[4] = {racc[0][0].x, racc[0][0].y, racc[0][0].z, racc[0][0].w};
 #pragma unroll
@@ -1236,7 +1104,7 @@ constexpr int conv_red_off() {   // even float offset: the records are doubles
   return conv_sums_off<CIN, TAPS, COUT, XF>() + (SUMS ? kTF * kF * COUT + ((2 * COUT + 3) & ~3) : 0);
 }
 constexpr int kConvRedFloats = kWaves * 64 * 2;
-// K-split of the odd column tile (RCED_TM_KSPLIT).  A tile of two frames is 17 column tiles (9 with pixel-pair columns)
+// K-split of the odd column tile.  A tile of two frames is 17 column tiles (9 with pixel-pair columns)
 // for four waves: 5 / 4 / 4 / 4 (3 / 2 / 2 / 2), and with two workgroups per CU both heavy waves sit on SIMD 0 -- the
 // end-of-tile barrier waited for 25 % (50 %) more MFMAs than the mean.  Now every wave runs a QUARTER of the odd tile's K
 // steps FIRST (its own small pass; wave 0 starts from the shift, wave 3 also takes the b32 tail), waves 1..3 park their
@@ -1245,17 +1113,10 @@ constexpr int kConvRedFloats = kWaves * 64 * 2;
 // Measured (round 3, CR-CED step, A/B on one box): the 9-tile kernels' forward (30 -> 8: 3 / 2 / 2 / 2) 1.012 -> 0.898 ms; the
 // 17-tile shapes do not gain (18 -> 30 forward 1.049 -> 1.111 ms: 25 more VGPRs and the odd tile's A fragments read four
 // times cost more than 5 / 4 / 4 / 4 does), so the split is used where a wave would otherwise carry >= 1.5 x the mean.
-#ifndef RCED_TM_KSPLIT
-#define RCED_TM_KSPLIT 1
-#endif
-#ifndef RCED_TM_MSPLIT
-#define RCED_TM_MSPLIT 0     // 1: two-M-tile shapes cut the odd column tile by M-tile over two waves (see conv1xk_mfma).  Measured:
-                             // 18 -> 30 forward 1.077 -> 1.10 ms -- the kernel is not bound by its fullest SIMD; off
-#endif
 template <int CIN, int TAPS, int COUT>
 constexpr bool conv_ks_on() {
   using G = Geo<CIN, TAPS, COUT>;
-  return RCED_TM_KSPLIT && G::kExtra == 1 && G::kRegular <= 2 && CIN % 2 == 0;
+  return G::kExtra == 1 && G::kRegular <= 2 && CIN % 2 == 0;
 }
 template <int CIN, int TAPS, int COUT, int XF, bool STATS, bool SUMS>
 constexpr int conv_ks_off() {
@@ -1352,51 +1213,29 @@ __global__ __launch_bounds__(kThreads, RCED_TM_OCC) void conv1xk_mfma(const floa
       TM_ST(2);   // barrier 1
       if constexpr (SUMS)
         if (!(RCED_TM_EXP & 1) || tile == (int)blockIdx.x) ztile_fetch<COUT>(sa.z, zt, frame0, frames, tid);   // the previous tile's epilogue is behind a barrier
-      // The next tile's loads: piece by piece between this tile's MFMAs (RCED_TM_SPREAD; not where the epilogue waits on
-      // vmcnt(0) for its z tile (SUMS), which would wait for them too), or all at once here -- a tile cut short by the
-      // end of the batch always takes the latter, with tile_fetch's per-element bounds.
-      constexpr bool kSpread = RCED_TM_SPREAD && !SUMS;
+      // The next tile's loads, all at once (a tile cut short by the end of the batch: with tile_fetch's per-element bounds)
       const int nframe0 = (tile + (int)gridDim.x) * kTF;
       const bool more = tile + (int)gridDim.x < ntiles && !(RCED_TM_EXP & 1);
-      const bool spread = kSpread && more && frames - nframe0 >= kTF;
-      if (more && !spread) {
+      if (more) {
         tile_fetch<CIN>(in, nframe0, frames, tid, pre);
         if constexpr (XF == kXfBnBwd) tile_fetch<CIN>(ba.z, nframe0, frames, tid, pre2);
       }
       pin();
       TM_ST(3);   // fetch issue
-      constexpr int kP1 = Stage<CIN>::kPer, kNP = (XF == kXfBnBwd ? 2 : 1) * kP1, kNS = G::kKP / 8;
-      auto each = [&](int s) {
-        if constexpr (kSpread) {
-          if (spread)
-            tm_static_for<0, kNP>([&](auto ic) {
-              constexpr int i = decltype(ic)::value;
-              if (s == i * kNS / kNP) {
-                if constexpr (i < kP1) tile_fetch_piece<CIN, kThreads, i>(in, nframe0, tid, pre);
-                else if constexpr (XF == kXfBnBwd) tile_fetch_piece<CIN, kThreads, i - kP1>(ba.z, nframe0, tid, pre2);
-              }
-            });
-        }
-      };
-      constexpr bool kOpq = (XF == kXfBnBwd ? 2 : 1) * Stage<CIN>::kPer * 4 >= RCED_TM_OPQ_MIN;   // VGPRs holding the next tile
+      // nothing is issued between the MFMAs.  (An empty lambda, not chain::NoEach: with the latter the SUMS kernels come out
+      // of hipcc as other code, and this header's kernels are kept instruction for instruction.)
+      auto each = [&](int) {};
+      using Each = decltype(each);
       constexpr bool kKs = conv_ks_on<CIN, TAPS, COUT>() && !SUMS;
       if constexpr (kKs) {
         float* ks = lds + conv_ks_off<CIN, TAPS, COUT, XF, STATS, SUMS>();
         f32x4 xacc[G::kMT];
         conv_ks_partial<CIN, TAPS, COUT>(lin, lw, ks, wave, lane, xacc);
-        if (wave == 0) conv_tile<CIN, TAPS, COUT, ACCUM, STATS, 1, SUMS, kOpq, false, decltype(each), false, 2, true>(lin, lw, out, frame0, frames, wave, lane, red_wave, zt, stab, each, nullptr, xacc, ks, sums, carried, flush, acc_delta);
-        else conv_tile<CIN, TAPS, COUT, ACCUM, STATS, 0, SUMS, kOpq, false, decltype(each), false, 2, true>(lin, lw, out, frame0, frames, wave, lane, red_wave, zt, stab, each, nullptr, xacc, ks, sums, carried, flush, acc_delta);
-      } else if constexpr (RCED_TM_MSPLIT && G::kExtra == 1 && G::kMTm == 2 && !SUMS && !ACCUM) {
-        // The odd column tile by M-tile: two waves carry half of it each (4.5 / 4.5 / 4 / 4 tiles of MFMAs instead of
-        // 5 / 4 / 4 / 4), and the second half of the grid -- with a resident grid of two workgroups per CU the likely partner
-        // on the same CU -- gives its halves to waves 2, 3: 8.5 on every SIMD.
-        const int xw = (int)blockIdx.x >= ((int)gridDim.x + 1) / 2 ? 2 : 0;
-        if (wave == xw) conv_tile<CIN, TAPS, COUT, ACCUM, STATS, 1, SUMS, kOpq, false, decltype(each), false, 2, false, 0>(lin, lw, out, frame0, frames, wave, lane, red_wave, zt, stab, each, nullptr, nullptr, nullptr, sums, carried, flush, acc_delta);
-        else if (wave == xw + 1) conv_tile<CIN, TAPS, COUT, ACCUM, STATS, 1, SUMS, kOpq, false, decltype(each), false, 2, false, 1>(lin, lw, out, frame0, frames, wave, lane, red_wave, zt, stab, each, nullptr, nullptr, nullptr, sums, carried, flush, acc_delta);
-        else conv_tile<CIN, TAPS, COUT, ACCUM, STATS, 0, SUMS, kOpq, false>(lin, lw, out, frame0, frames, wave, lane, red_wave, zt, stab, each, nullptr, nullptr, nullptr, sums, carried, flush, acc_delta);
+        if (wave == 0) conv_tile<CIN, TAPS, COUT, ACCUM, STATS, 1, SUMS, false, Each, false, 2, true>(lin, lw, out, frame0, frames, wave, lane, red_wave, zt, stab, each, nullptr, xacc, ks, sums, carried, flush, acc_delta);
+        else conv_tile<CIN, TAPS, COUT, ACCUM, STATS, 0, SUMS, false, Each, false, 2, true>(lin, lw, out, frame0, frames, wave, lane, red_wave, zt, stab, each, nullptr, xacc, ks, sums, carried, flush, acc_delta);
       } else {
-      if (wave < G::kExtra) conv_tile<CIN, TAPS, COUT, ACCUM, STATS, 1, SUMS, kOpq, false>(lin, lw, out, frame0, frames, wave, lane, red_wave, zt, stab, each, nullptr, nullptr, nullptr, sums, carried, flush, acc_delta);
-      else conv_tile<CIN, TAPS, COUT, ACCUM, STATS, 0, SUMS, kOpq, false>(lin, lw, out, frame0, frames, wave, lane, red_wave, zt, stab, each, nullptr, nullptr, nullptr, sums, carried, flush, acc_delta);
+      if (wave < G::kExtra) conv_tile<CIN, TAPS, COUT, ACCUM, STATS, 1, SUMS>(lin, lw, out, frame0, frames, wave, lane, red_wave, zt, stab, each, nullptr, nullptr, nullptr, sums, carried, flush, acc_delta);
+      else conv_tile<CIN, TAPS, COUT, ACCUM, STATS, 0, SUMS>(lin, lw, out, frame0, frames, wave, lane, red_wave, zt, stab, each, nullptr, nullptr, nullptr, sums, carried, flush, acc_delta);
       }
       TM_ST(4);   // conv_tile
       __syncthreads();
@@ -1480,12 +1319,11 @@ __global__ __launch_bounds__(kThreads, RCED_TM_OCC) void conv_x6_fwd(const float
     const int nframe0 = (tile + (int)gridDim.x) * kTF;
     if (tile + (int)gridDim.x < ntiles) tile_fetch<CIN>(in, nframe0, frames, tid, pre);
     pin();
-    constexpr bool kOpq = Stage<CIN>::kPer * 4 >= RCED_TM_OPQ_MIN;
     if (wave < G::kExtra)
-      conv_tile<CIN, TAPS, COUT, false, STATS, 1, false, kOpq, false, chain::NoEach, false, 2, false, -1, true>(
+      conv_tile<CIN, TAPS, COUT, false, STATS, 1, false, false, chain::NoEach, false, 2, false, true>(
           lds, lw, out, frame0, frames, wave, lane, red_wave, nullptr, nullptr, chain::NoEach(), nullptr, nullptr, nullptr, sums, carried, flush);
     else
-      conv_tile<CIN, TAPS, COUT, false, STATS, 0, false, kOpq, false, chain::NoEach, false, 2, false, -1, true>(
+      conv_tile<CIN, TAPS, COUT, false, STATS, 0, false, false, chain::NoEach, false, 2, false, true>(
           lds, lw, out, frame0, frames, wave, lane, red_wave, nullptr, nullptr, chain::NoEach(), nullptr, nullptr, nullptr, sums, carried, flush);
     __syncthreads();
   }
@@ -1584,27 +1422,13 @@ __global__ __launch_bounds__(kThreads, RCED_TM_OCC) void wgrad1xk_mfma(const flo
     else tile_commit<COUT>(ldz, tid, prez, where_dz);
     __syncthreads();
     const int nframe0 = (tile + (int)gridDim.x) * kTF;
-    const bool more = tile + (int)gridDim.x < ntiles;
-    const bool spread = RCED_TM_SPREAD && more && frames - nframe0 >= kTF;
-    if (more && !spread) {
+    if (tile + (int)gridDim.x < ntiles) {
       tile_fetch<CIN>(x, nframe0, frames, tid, prex);
       tile_fetch<COUT>(dz, nframe0, frames, tid, prez);
       if constexpr (DZF) tile_fetch<COUT>(ba.z, nframe0, frames, tid, prez2);
     }
     pin();
-    constexpr int kPX = Stage<CIN>::kPer, kPZ = Stage<COUT>::kPer, kNP = kPX + (DZF ? 2 : 1) * kPZ;
-    constexpr int kIters = kGroups / kWaves;     // iterations every wave runs: the pieces are spread over them
-    int it = 0;
-    for (int g = wave; g < kGroups; g += kWaves, ++it) {
-      if (spread)
-        tm_static_for<0, kNP>([&](auto ic) {
-          constexpr int i = decltype(ic)::value;
-          if (it == i * kIters / kNP) {
-            if constexpr (i < kPX) tile_fetch_piece<CIN, kThreads, i>(x, nframe0, tid, prex);
-            else if constexpr (i < kPX + kPZ) tile_fetch_piece<COUT, kThreads, i - kPX>(dz, nframe0, tid, prez);
-            else if constexpr (DZF) tile_fetch_piece<COUT, kThreads, i - kPX - kPZ>(ba.z, nframe0, tid, prez2);
-          }
-        });
+    for (int g = wave; g < kGroups; g += kWaves) {
       const int px0 = 4 * PH * g;
       float a[KT], b[NTo];
 #pragma unroll
@@ -1695,19 +1519,9 @@ __global__ __launch_bounds__(kThreads, RCED_TM_OCC) void wgrad1xk_mfma(const flo
 // CIN / COUT are the LAYER's (x has CIN channels, dz COUT); the packet is the dgrad packet (pack_packet transpose = 1).
 // ---------------------------------------------------------------------------------------------
 constexpr int kBwdThreads = 512;
-#ifndef RCED_TM_BWD_X6_C
-#define RCED_TM_BWD_X6_C 1   // bwd_fused_mfma<30,9,8>: its dgrad half (8 -> 30, no remainder pass) in the three-part bf16 form (GeoX6)
-#endif
-// fused backward shapes whose dgrad half runs on the bf16 pipe: the host packs their dgrad packet with pack_packet_x6
-#ifndef RCED_TM_BWD_X6_B
-#define RCED_TM_BWD_X6_B 0   // bwd_fused_mfma<18,5,30>: its dgrad half (30 -> 18: main pass + remainder pass) likewise.  Measured
-                             // 3.2 ms against 2.35 ms: with ONE M-tile a B fragment (48 bytes per lane for the three parts) feeds only six
-                             // MFMAs (96 cycles) -- four dgrad waves saturate the LDS port (24 cycles per fragment each); the
-                             // two-M-tile shapes (8 -> 30 dgrad, 18 -> 30 forward) reuse every fragment twice and gain.  Off.
-#endif
-__host__ __device__ constexpr bool bwd_x6(int cin, int taps, int cout) {
-  return (RCED_TM_BWD_X6_C && cin == 30 && taps == 9 && cout == 8) || (RCED_TM_BWD_X6_B && cin == 18 && taps == 5 && cout == 30);
-}
+// fused backward shapes whose dgrad half runs on the bf16 pipe (the host packs their dgrad packet with pack_packet_x6):
+// bwd_fused_mfma<30,9,8>, whose dgrad (8 -> 30) has two M-tiles and no remainder pass
+__host__ __device__ constexpr bool bwd_x6(int cin, int taps, int cout) { return cin == 30 && taps == 9 && cout == 8; }
 template <int CIN, int TAPS, int COUT, bool X6D>
 struct BwdX6Sizes {      // floats the dgrad's packet region and its planes take
   static constexpr int kPacket = Geo<COUT, TAPS, CIN>::kPacket, kPlanes = 0;
@@ -1730,11 +1544,7 @@ struct BwdGeo {
   static constexpr int kXOff = r4(kPkOff + XS::kPacket);             // [GW::kInRows][CIN] (+ slack)
   static constexpr int kTabOff = r4(kXOff + GW::kInFloats + 64);     // [2][CIN] BatchNorm + ReLU of x, then [4][COUT] BatchNorm backward
   static constexpr int kRedOff = r4(kTabOff + 2 * CIN + 4 * COUT);   // [4 waves][32][2] doubles
-  // raw copies of the NEXT tile (LDS-DMA targets, RCED_TM_BWD_DMA): x [2][129][CIN], d_u / g [2][129][COUT], z [2][129][COUT]
-  static constexpr int kStgX = r4(kRedOff + kConvRedFloats);
-  static constexpr int kStgD = kStgX + r4(kTF * kF * CIN);
-  static constexpr int kStgZ = kStgD + r4(kTF * kF * COUT);
-  static constexpr int kPlOff = r4(RCED_TM_BWD_DMA ? kStgZ + r4(kTF * kF * COUT) : kRedOff + kConvRedFloats);   // dz as three bf16 planes (kX6D)
+  static constexpr int kPlOff = r4(kRedOff + kConvRedFloats);        // dz as three bf16 planes (kX6D)
   static constexpr int kLdsFloats = kPlOff + XS::kPlanes;
   static_assert(kLdsFloats * 4 <= 160 * 1024, "LDS budget");
   static_assert(GD::kG == GW::kG && GD::kS == GW::kS, "one pixel space");
@@ -1779,25 +1589,13 @@ struct BwdBalance {
   __device__ __forceinline__ static int begin(int w) {      // w wave-uniform, 0..4
     return w == 0 ? 0 : w == 1 ? begin_c(1) : w == 2 ? begin_c(2) : w == 3 ? begin_c(3) : kGroups;
   }
-  static constexpr int kMinIters = count(0) < count(1) ? (count(0) < count(2) ? (count(0) < count(3) ? count(0) : count(3))
-                                                                               : (count(2) < count(3) ? count(2) : count(3)))
-                                                        : (count(1) < count(2) ? (count(1) < count(3) ? count(1) : count(3))
-                                                                               : (count(2) < count(3) ? count(2) : count(3)));
   static_assert(begin_c(4) == kGroups && count(0) > 0 && count(1) > 0 && count(2) > 0 && count(3) > 0, "every group has one owner");
 };
 
-#ifndef RCED_TM_OWN_B
-#define RCED_TM_OWN_B 1     // bwd_fused_mfma<18,5,30>: tensors staged by the dgrad half alone (bit 0: x, bit 1: (d_u, z))
-#endif
-#ifndef RCED_TM_OWN_C
-#define RCED_TM_OWN_C 0     // bwd_fused_mfma<30,9,8>
-#endif
-#ifndef RCED_TM_OWN_OTHER
-#define RCED_TM_OWN_OTHER 0 // the R-CED shapes
-#endif
+// tensors of a tile staged by the dgrad half alone (bit 0: x, bit 1: (d_u, z)): x for bwd_fused_mfma<18,5,30>, none elsewhere
 template <int CIN, int TAPS, int COUT>
 constexpr int bwd_own() {
-  return (CIN == 18 && TAPS == 5 && COUT == 30) ? RCED_TM_OWN_B : (CIN == 30 && TAPS == 9 && COUT == 8) ? RCED_TM_OWN_C : RCED_TM_OWN_OTHER;
+  return (CIN == 18 && TAPS == 5 && COUT == 30) ? 1 : 0;
 }
 // Measured alternatives: tile i+1 committed into a second pair of LDS buffers by the wgrad half alone while
 // tile i is computed (one barrier per tile), with the staging behind or in front of that half's MFMAs, with s_setprio on
@@ -1849,35 +1647,15 @@ __global__ __launch_bounds__(kBwdThreads) void bwd_fused_mfma(const float* __res
 #pragma unroll
   for (int a = 0; a < kAccN; ++a) accs[a] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int ntiles = (frames + kTF - 1) / kTF;
-  constexpr bool DMA = RCED_TM_BWD_DMA != 0;
   // OWN: which of the tile's tensors are fetched and committed by the DGRAD half alone (bit 0: x, bit 1: (d_u, z)) instead
   // of by all 512 threads.  The wgrad half is the tile's critical path (stamps: commit, then ~7.5 k cycles blocked in the
   // issue of its share of the next tile's loads, then its MFMAs), the dgrad half waits 3-6 k cycles at the tile's end:
   // bytes moved from one half's burst to the other's shorten the first by what the second has to spare.
   constexpr int OWN = bwd_own<CIN, TAPS, COUT>();
-  static_assert(OWN == 0 || (!DMA && !RCED_TM_SPREAD && RCED_TM_BWD_STAGGER), "ownership is built for the staggered VGPR staging");
   constexpr int XN = (OWN & 1) ? NTH / 2 : NTH, ZN = (OWN & 2) ? NTH / 2 : NTH;
   constexpr int kPX = Stage<CIN, XN>::kPer, kPZ = Stage<COUT, ZN>::kPer, kNP = kPX + 2 * kPZ;
-  float* sx = lds + B::kStgX;
-  float* sd = lds + B::kStgD;
-  float* sz = lds + B::kStgZ;
-  f32x4 prex[kPX], pred[kPZ], prez[kPZ];     // DMA: transient (stage_load -> commit); else the next tile for a whole tile time
-  // the next tile into the staging copies: by LDS-DMA piece i (whole tiles), or all of a ragged last tile with bounds checks
-  auto dma_piece = [&](auto ic, int f0, int vt) {     // vt: the thread of the piece map whose share is issued
-    constexpr int i = decltype(ic)::value;
-    if constexpr (i < kPX) tile_dma_piece<CIN, XN, i>(x, f0, vt, sx);
-    else if constexpr (i < kPX + kPZ) tile_dma_piece<COUT, ZN, i - kPX>(du, f0, vt, sd);
-    else tile_dma_piece<COUT, ZN, i - kPX - kPZ>(ba.z, f0, vt, sz);
-  };
-  auto stage_ragged = [&](int f0) {
-    tile_fetch<CIN, XN>(x, f0, frames, tid, prex);
-    tile_fetch<COUT, ZN>(du, f0, frames, tid, pred);
-    tile_fetch<COUT, ZN>(ba.z, f0, frames, tid, prez);
-    stage_store<CIN, XN>(sx, tid, prex);
-    stage_store<COUT, ZN>(sd, tid, pred);
-    stage_store<COUT, ZN>(sz, tid, prez);
-  };
-  // this thread's pieces of the tile at frame f0 (VGPR staging): the tensors its half owns, or shares
+  f32x4 prex[kPX], pred[kPZ], prez[kPZ];     // the next tile, for a whole tile time
+  // this thread's pieces of the tile at frame f0: the tensors its half owns, or shares
   auto fetch_mine = [&](int f0) {
     if (!(OWN & 1) || role == 0) tile_fetch<CIN, XN>(x, f0, frames, tid, prex);
     if (!(OWN & 2) || role == 0) {
@@ -1886,15 +1664,7 @@ __global__ __launch_bounds__(kBwdThreads) void bwd_fused_mfma(const float* __res
     }
   };
   __syncthreads();                            // the LDS image is zeroed / the packet is in place before anything lands in it
-  if ((int)blockIdx.x < ntiles) {
-    const int f0 = blockIdx.x * kTF;
-    if constexpr (DMA) {
-      if (frames - f0 >= kTF) tm_static_for<0, kNP>([&](auto ic) { dma_piece(ic, f0, tid); });
-      else stage_ragged(f0);
-    } else {
-      fetch_mine(f0);
-    }
-  }
+  if ((int)blockIdx.x < ntiles) fetch_mine(blockIdx.x * kTF);
   __syncthreads();
   const float* ain = lx + PH * kq * GW::kCinP + i;
   const float* ldzp = ldz + GD::kG * COUT;
@@ -1904,38 +1674,19 @@ __global__ __launch_bounds__(kBwdThreads) void bwd_fused_mfma(const float* __res
   unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = stamps_on ? tm_stamp() : 0;
   if (stamps_on && lane == 0 && role == 0) for (int q = 0; q < 4; ++q) g_tm[wave][q] = g_tm2[wave][q] = 0;
 #endif
-  SumState<GD::kMTm> sums;        // the dgrad half's masked sums, carried over kSumFlush tiles (conv_tile)
-  sums.zero();
-  int tile_no = 0;
+  SumState<GD::kMTm> sums;        // the dgrad half's masked sums: not carried here -- the kernel sits at 256 VGPRs -- so they
+  sums.zero();                    // leave with every tile (conv_tile)
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int frame0 = tile * kTF;
-    const bool flush = (++tile_no % kSumFlush) == 0 || tile + (int)gridDim.x >= ntiles;
-    constexpr bool carried = SUMS && kSumFlush > 1 && RCED_TM_BWD_CARRY;
     auto where_x = [](int fr, int r) { return (GW::kG + fr * GW::kS) * CIN + r; };
     auto where_dz = [](int fr, int r) { return (GD::kG + fr * GD::kS) * COUT + r; };
-    if constexpr (DMA) {
-      // this wave's transfers of the tile have landed ... and everybody's (this is also the barrier behind the previous
-      // tile's MFMA reads of the operand tiles the commit below overwrites)
-      // (the dgrad half issued none -- except in the prologue -- and must not wait here: vmcnt(0) would also wait for
-      // its epilogue's global stores, which are free to stay in flight across the barrier)
-      if (role == 1 || tile == (int)blockIdx.x) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      TM_ST(0);   // wait for the staged tile
-      __syncthreads();
-      stage_load<CIN, XN>(sx, tid, prex);
-    } else {
 #if RCED_TM_STAMPS
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      TM_ST(0);   // wait for the prefetched tile
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    TM_ST(0);   // wait for the prefetched tile
 #endif
-    }
     if (!(OWN & 1) || role == 0) {
       if constexpr (XF) tile_commit_bnrelu<CIN, XN>(lx, tid, prex, where_x, xt, frame0, frames);
       else tile_commit<CIN, XN>(lx, tid, prex, where_x);
-    }
-    if constexpr (DMA) {      // the x pieces are dead before the (d_u, z) pieces are read: 12-16 fewer registers at the peak
-      pin();
-      stage_load<COUT, ZN>(sd, tid, pred);
-      stage_load<COUT, ZN>(sz, tid, prez);
     }
     if (!(OWN & 2) || role == 0) {
       if constexpr (X6D) {
@@ -1960,32 +1711,18 @@ __global__ __launch_bounds__(kBwdThreads) void bwd_fused_mfma(const float* __res
     TM_ST(2);   // barrier 1
     const int nframe0 = (tile + (int)gridDim.x) * kTF;
     const bool more = tile + (int)gridDim.x < ntiles;
-    const bool spread = RCED_TM_SPREAD && !DMA && more && frames - nframe0 >= kTF;
-    if (more && !spread) {
-      if constexpr (DMA) {
-        // Issued by the WGRAD half alone, each of its threads for two threads of the 512-thread piece map: the burst
-        // finds the memory pipeline's queues full and blocks the issuing waves for 3-4 k cycles (stamps) -- now only the
-        // wgrad wave of every SIMD, while its dgrad wave runs the MFMA pass; the wgrad wave's own MFMAs then run beside
-        // the dgrad wave's epilogue.  (All eight waves issuing their own pieces stalled the whole CU: 14 % of the kernel.)
-        if (frames - nframe0 >= kTF) {
-          if (role == 1)
-            tm_static_for<0, kNP>([&](auto ic) {
-              dma_piece(ic, nframe0, tid - 256);
-              dma_piece(ic, nframe0, tid);
-            });
-        } else {
-          stage_ragged(nframe0);
-        }
-      } else if (!RCED_TM_BWD_STAGGER || role == 1) {
-        fetch_mine(nframe0);
-      }
-    }
+    // The next tile's loads in two half-size bursts, each beside the other half's MFMAs, instead of one that stalls all
+    // eight waves: the wgrad half issues its share here, at the start of the MFMA phase, the dgrad half its share BEHIND its
+    // MFMA pass, in front of its epilogue (conv_tile's each(-1))
+    if (more && role == 1) fetch_mine(nframe0);
     pin();
     TM_ST(3);   // fetch issue
+    // (`spread` and `piece`: the retired piece-by-piece issue, never taken; kept for the code hipcc makes of `each` -- see
+    // tile_fetch_piece)
+    const bool spread = false && more && frames - nframe0 >= kTF;
     auto piece = [&](auto ic) {
       constexpr int i = decltype(ic)::value;
-      if constexpr (DMA) dma_piece(ic, nframe0, tid);
-      else if constexpr (i < kPX) tile_fetch_piece<CIN, XN, i>(x, nframe0, tid, prex);
+      if constexpr (i < kPX) tile_fetch_piece<CIN, XN, i>(x, nframe0, tid, prex);
       else if constexpr (i < kPX + kPZ) tile_fetch_piece<COUT, ZN, i - kPX>(du, nframe0, tid, pred);
       else tile_fetch_piece<COUT, ZN, i - kPX - kPZ>(ba.z, nframe0, tid, prez);
     };
@@ -1994,21 +1731,19 @@ __global__ __launch_bounds__(kBwdThreads) void bwd_fused_mfma(const float* __res
       auto each = [&](int s) {
         if (spread)
           tm_static_for<0, kNP>([&](auto ic) { if (s == decltype(ic)::value * kNS / kNP) piece(ic); });
-        if (RCED_TM_BWD_STAGGER && !DMA && s == -1 && more && !spread) {
+        if (s == -1 && more && !spread) {
           fetch_mine(nframe0);
           pin();
         }
       };
       const float* dgin = X6D ? lds + B::kPlOff : ldz;      // the dgrad's input tile: bf16 planes, or the fp32 dz tile
-      if (wave < GD::kExtra) conv_tile<COUT, TAPS, CIN, false, false, 1, SUMS, false, true, decltype(each), true, RCED_TM_BWD_DEPTH, false, -1, X6D>(dgin, lw, dx, frame0, frames, wave, lane, red + wave * 64, lx, nullptr, each, accs, nullptr, nullptr, sums, carried, flush);
-      else conv_tile<COUT, TAPS, CIN, false, false, 0, SUMS, false, true, decltype(each), true, RCED_TM_BWD_DEPTH, false, -1, X6D>(dgin, lw, dx, frame0, frames, wave, lane, red + wave * 64, lx, nullptr, each, accs, nullptr, nullptr, sums, carried, flush);
+      if (wave < GD::kExtra) conv_tile<COUT, TAPS, CIN, false, false, 1, SUMS, true, decltype(each), true, 1, false, X6D>(dgin, lw, dx, frame0, frames, wave, lane, red + wave * 64, lx, nullptr, each, accs, nullptr, nullptr, sums, false, true);
+      else conv_tile<COUT, TAPS, CIN, false, false, 0, SUMS, true, decltype(each), true, 1, false, X6D>(dgin, lw, dx, frame0, frames, wave, lane, red + wave * 64, lx, nullptr, each, accs, nullptr, nullptr, sums, false, true);
     } else {
       // Groups of this wgrad wave: a contiguous range sized so that every SIMD (dgrad wave w + wgrad wave w) issues the
       // same number of MFMAs per tile -- the dgrad wave that carries the odd column tile gets fewer groups beside it
       // (the barrier that ends a tile waits for the fullest SIMD: 573 / 498 / 498 / 498 MFMAs before, for the 18 -> 30 layer).
       const int gbeg = BwdBalance<CIN, TAPS, COUT>::begin(wave), gend = BwdBalance<CIN, TAPS, COUT>::begin(wave + 1);
-      constexpr int kIters = BwdBalance<CIN, TAPS, COUT>::kMinIters;
-      int it = 0;
       int g = gbeg;
       if constexpr (bwd_wg_x6(CIN, TAPS, COUT) && PH == 1) {
         // Whole runs of eight groups (32 pixels) in the three-part bf16 form: the operands run along PIXELS here, so a lane's
@@ -2017,7 +1752,7 @@ __global__ __launch_bounds__(kBwdThreads) void bwd_fused_mfma(const float* __res
         // pixels where the fp32 form issues KT * NTo * 8 of 32.  The groups left over (< 8) take the fp32 loop below.
         const float* ain8 = lx + 8 * kq * GW::kCinP + i;
         const float* bin8 = ldzp + 8 * kq * COUT + i;
-        for (; g + 8 <= gend; g += 8, it += 8) {
+        for (; g + 8 <= gend; g += 8) {
           const int pxc = 4 * g;
           X6Parts bp[NTo];
 #pragma unroll
@@ -2051,9 +1786,7 @@ __global__ __launch_bounds__(kBwdThreads) void bwd_fused_mfma(const float* __res
           }
         }
       }
-      for (; g < gend; ++g, ++it) {
-        if (spread)
-          tm_static_for<0, kNP>([&](auto ic) { if (it == decltype(ic)::value * kIters / kNP) piece(ic); });
+      for (; g < gend; ++g) {
         const int px0 = 4 * PH * g;
         float a[KT], b[NTo];
 #pragma unroll
@@ -2068,10 +1801,9 @@ __global__ __launch_bounds__(kBwdThreads) void bwd_fused_mfma(const float* __res
       }
     }
     TM_ST(4);   // role work
-    if constexpr (!DMA) __syncthreads();   // (DMA: the barrier at the top of the next tile, behind its vmcnt wait)
+    __syncthreads();
     TM_ST(5);   // barrier 2
   }
-  if constexpr (DMA) __syncthreads();      // the dgrad half's LDS records are complete before they are summed below
 #if RCED_TM_STAMPS
   if (stamps_on && lane == 0)
     printf("BWST<%d,%d,%d> wave8 %d: loadwait %llu commit %llu bar1 %llu fetch %llu work %llu bar2 %llu | gemm %llu epi %llu (coords %llu sums %llu stores %llu)\n",

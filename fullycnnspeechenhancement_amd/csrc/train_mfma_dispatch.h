@@ -92,8 +92,7 @@ constexpr size_t tm_packet_floats(int cin, int taps, int cout) {     // Geo::kPa
 // ---- the forward convolutions in the three-part bf16 form (tmm::conv_x6_fwd) ----
 constexpr size_t tm_packet_x6_floats(int cin, int taps, int cout) {   // tmm::GeoX6::kPacket (static_assert below)
   const int ph = tm_packet_parities(cout), cs = tmm::x6_cs(cin, ph), K = (taps + ph - 1) * cs;
-  const int R = ph == 1 ? tmm::tm_rem(cout) : 0, P = tmm::tm_rem_p(R, (cin + 1) & ~1), KR = R ? (taps + P - 1) * cs : 0;   // as GeoX6 / pack_packet_x6
-  return (size_t)(((K + 31) / 32) * (R ? 1 : (cout + 15) / 16) + (KR + 31) / 32) * 3 * 64 * 4 + 32;
+  return (size_t)(((K + 31) / 32) * ((cout + 15) / 16)) * 3 * 64 * 4 + 32;
 }
 // the host-side sizes are the kernels' own for every shape the three nets' training steps launch
 static_assert(tm_packet_floats(8, 9, 18) == (size_t)tmm::Geo<8, 9, 18>::kPacket && tm_packet_floats(18, 5, 30) == (size_t)tmm::Geo<18, 5, 30>::kPacket &&

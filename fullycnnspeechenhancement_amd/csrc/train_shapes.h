@@ -22,17 +22,9 @@
 // wgrad + dgrad of a layer in one kernel (tmm::bwd_fused_mfma): the CR-CED shapes whose input tensor has one consumer
 #define RCED_TM_FUSED(X) X(18, 5, 30) X(30, 9, 8)
 // forward shapes built in the three-part bf16 form (tmm::conv_x6_fwd): CR-CED's 18 -> 30 layers (no remainder pass; the
-// 30 -> 8 layers' three planes + packet do not leave room for two workgroups per CU: tmm::GeoX6::kFits)
-#ifndef RCED_TM_X6_FWD_818
-#define RCED_TM_X6_FWD_818 0   // 1: the 8 -> 18 forward convolutions (main pass + remainder pass) in the three-part bf16 form too.  Measured (round 6,
-                               // A/B in one call, parity tests green): the step 40.30 -> 40.60 ms -- these layers (K = 72, 1.8 GB per call) wait for
-                               // their tiles, not for the fp32 matrix pipe; not adopted
-#endif
-#if RCED_TM_X6_FWD_818
-#define RCED_TM_X6_FWD(X) X(18, 5, 30) X(8, 9, 18)
-#else
+// 30 -> 8 layers' three planes + packet do not leave room for two workgroups per CU: tmm::GeoX6::kFits; the 8 -> 18 layers
+// wait for their tiles, not for the fp32 matrix pipe: DESIGN 3.5, "tried and retired")
 #define RCED_TM_X6_FWD(X) X(18, 5, 30)
-#endif
 #define RCED_FIRST(X) X(9, 18) X(13, 12) X(11, 10)   // first layer (8 x kw on the 1-channel input): (kw, cout)
 #define RCED_FIN_CH(X) X(8) X(10) X(12)              // output layer (1x129, CH -> 1): CH
 
