@@ -11,7 +11,7 @@ from .model import (FullyCNNSEModel, FullyCNNSEModelV2, FullyCNNSEModelV3, build
 from .engine import FullyCNNTester, InferenceEngine  # noqa: F401
 from .trainer import FullyCNNTrainer  # noqa: F401
 from . import audio, loader, metrics, spec, weights  # noqa: F401
-from .audio import StreamingDenoiser, StreamingResampler  # noqa: F401
+from .audio import BlockDenoiser, FreeResampler, StreamingDenoiser, StreamingResampler  # noqa: F401
 
 __all__ = ["FullyCNNSEModel", "FullyCNNSEModelV2", "FullyCNNSEModelV3", "build_model", "conv_bn_relu",
-           "FullyCNNTester", "InferenceEngine", "FullyCNNTrainer", "StreamingDenoiser", "StreamingResampler", "audio", "loader", "metrics", "spec", "weights"]
+           "FullyCNNTester", "InferenceEngine", "FullyCNNTrainer", "StreamingDenoiser", "StreamingResampler", "BlockDenoiser", "FreeResampler", "audio", "loader", "metrics", "spec", "weights"]

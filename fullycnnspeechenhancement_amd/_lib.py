@@ -73,6 +73,13 @@ SYMBOLS = {
     "rced_rstream_push": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _vp]),
     "rced_rstream_finish": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "rced_rstream_reset": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "rced_rfree_available": (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int, ctypes.c_longlong]),
+    "rced_rfree_plan": (ctypes.c_int, [ctypes.c_int] * 7 + [_c_int_p] * 4),
+    "rced_rfree_create": (ctypes.c_int, [ctypes.c_int] * 10 + [ctypes.POINTER(_vp)]),
+    "rced_rfree_destroy": (None, [_vp]),
+    "rced_rfree_push": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp]),
+    "rced_rfree_finish": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "rced_rfree_reset": (ctypes.c_int, [_vp, ctypes.c_int]),
     "rced_train_create": (ctypes.c_int, [ctypes.c_int, _c_float_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
                                          ctypes.POINTER(_vp)]),
     "rced_train_destroy": (None, [_vp]),

@@ -1,10 +1,13 @@
 // C ABI of the resampler lanes (include/rced.h, "streaming resampler" section): host side.  One launch per push on the
 // caller's stream (kernels_rstream.h), no allocation, no synchronisation; the arithmetic of a lane stream is rstream_plan.h's.
+// Below them the free-running lanes ("free-running resampler" section), in the same shape: kernels_rfree.h, which
+// stages frames with kernels_rstream.h's frame<>, and rfree_plan.h.
 #include <hip/hip_runtime.h>
 
 #include <new>
 
 #include "../../include/rced.h"
+#include "kernels_rfree.h"
 #include "kernels_rstream.h"
 #include "rced_internal.h"
 
@@ -158,6 +161,187 @@ int rced_rstream_started(rced_rstream* h, const int* active_dev, int* started_de
 
 int rced_rstream_reset(rced_rstream* h, int lane) {
   if (!h) return rced_fail(RCED_ERR_ARG, "stream is NULL");
+  if (lane < -1 || lane >= h->lanes) return rced_fail(RCED_ERR_ARG, "lane must be -1 (all) or 0..%d, got %d", h->lanes - 1, lane);
+  DeviceGuard g(h->device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", h->device);
+  const size_t one = (size_t)h->plan.words * sizeof(long long);
+  if (lane < 0) HIP_TRY(hipMemsetAsync(h->state, 0, one * h->lanes, h->last));
+  else HIP_TRY(hipMemsetAsync(h->state + (size_t)lane * h->plan.words, 0, one, h->last));
+  return RCED_OK;
+}
+
+}  // extern "C"
+
+// ---- free-running lanes ----
+
+struct rced_rfree {
+  rfree::Plan plan;
+  int sr_in = 0, sr_out = 0, channels = 1, src_dtype = 0, out_dtype = 0, lanes = 0, device = 0;
+  const double* table = nullptr;   // the ratio's, on the device: resample_api.hip owns it
+  long long* state = nullptr;      // [lanes][plan.words]
+  hipStream_t last = nullptr;      // the stream of the latest push / finish: rced_rfree_reset is ordered on it
+};
+
+namespace {
+
+// the checks and the plan that need no device
+int plan_for(int sr_in, int sr_out, int channels, int src_dtype, int out_dtype, int lanes, int max_frames, int max_take, int prefill,
+             rfree::Plan* plan) {
+  if (sr_in <= 0 || sr_out <= 0) return rced_fail(RCED_ERR_ARG, "sample rates must be positive, got %d -> %d", sr_in, sr_out);
+  if (channels < 1) return rced_fail(RCED_ERR_ARG, "channels must be >= 1, got %d", channels);
+  if (src_dtype != RCED_PCM_S16 && src_dtype != RCED_PCM_F32)
+    return rced_fail(RCED_ERR_ARG, "src_dtype must be RCED_PCM_S16 or RCED_PCM_F32, got %d", src_dtype);
+  if (out_dtype != RCED_PCM_S16 && out_dtype != RCED_PCM_F32)
+    return rced_fail(RCED_ERR_ARG, "out_dtype must be RCED_PCM_S16 or RCED_PCM_F32, got %d", out_dtype);
+  int p, q, left, width;
+  if (int rc = rced_resample_table(sr_in, sr_out, &p, &q, &left, &width, 0, nullptr)) return rc;
+  char err[256] = "";
+  if (rfree::plan(p, q, left, width, max_frames, max_take, prefill, out_dtype == RCED_PCM_F32 ? 4 : 2, lanes, plan, err, sizeof err) !=
+      rfree::kPlanOk)
+    return rced_fail(RCED_ERR_ARG, "free-running lanes %d Hz -> %d Hz: %s", sr_in, sr_out, err);
+  return RCED_OK;
+}
+
+int launch(rced_rfree* h, const void* in, int in_cols, const int* counts, const int* take, int finish, void* out, int out_cols, int* out_counts,
+           hipStream_t st) {
+  const rfree::Plan& L = h->plan;
+  rfree::Params P;
+  P.in = in;
+  P.in_cols = in_cols;
+  P.channels = h->channels;
+  P.counts = counts;
+  P.take = take;
+  P.finish = finish;
+  P.state = h->state;
+  P.words = L.words;
+  P.hist = L.hist;
+  P.cap = L.cap;
+  P.prefill = L.prefill;
+  P.table = h->table;
+  P.p = L.p;
+  P.q = L.q;
+  P.left = L.left;
+  P.width = L.width;
+  P.right = L.right;
+  P.ratio = (double)h->sr_out / (double)h->sr_in;
+  P.tile = L.tile;
+  P.out = out;
+  P.out_cols = out_cols;
+  P.out_counts = out_counts;
+  const dim3 grid(h->lanes), block(rfree::kThreads);
+  const bool sf = h->src_dtype == RCED_PCM_F32, of = h->out_dtype == RCED_PCM_F32;
+  if (sf && of)
+    hipLaunchKernelGGL((rfree::rfree_kernel<true, true>), grid, block, 0, st, P);
+  else if (sf)
+    hipLaunchKernelGGL((rfree::rfree_kernel<true, false>), grid, block, 0, st, P);
+  else if (of)
+    hipLaunchKernelGGL((rfree::rfree_kernel<false, true>), grid, block, 0, st, P);
+  else
+    hipLaunchKernelGGL((rfree::rfree_kernel<false, false>), grid, block, 0, st, P);
+  HIP_TRY(hipGetLastError());
+  h->last = st;
+  return RCED_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+long long rced_rfree_available(int sr_in, int sr_out, long long frames) {
+  if (sr_in <= 0 || sr_out <= 0 || frames < 0) {
+    rced_fail(RCED_ERR_ARG, "rates must be positive and frames >= 0, got %d -> %d, %lld frames", sr_in, sr_out, frames);
+    return -1;
+  }
+  int p, q, left, width;
+  if (rced_resample_table(sr_in, sr_out, &p, &q, &left, &width, 0, nullptr)) return -1;
+  if (frames > ((long long)1 << 62) / p) {
+    rced_fail(RCED_ERR_ARG, "%lld frames at %d / %d: the count does not fit 64 bits", frames, p, q);
+    return -1;
+  }
+  return rfree::emitted(frames, p, q, width - 1 - left);
+}
+
+int rced_rfree_plan(int sr_in, int sr_out, int out_dtype, int lanes, int max_frames, int max_take, int prefill, int* history, int* tile,
+                    int* capacity, int* finish_max) {
+  rfree::Plan plan;
+  if (int rc = plan_for(sr_in, sr_out, 1, RCED_PCM_F32, out_dtype, lanes, max_frames, max_take, prefill, &plan)) return rc;
+  if (history) *history = plan.hist;
+  if (tile) *tile = plan.tile;
+  if (capacity) *capacity = plan.cap;
+  if (finish_max) *finish_max = plan.finish_max;
+  return RCED_OK;
+}
+
+int rced_rfree_create(int sr_in, int sr_out, int channels, int src_dtype, int out_dtype, int lanes, int max_frames, int max_take, int prefill,
+                      int device, rced_rfree** out) {
+  if (!out) return rced_fail(RCED_ERR_ARG, "out is NULL");
+  *out = nullptr;
+  // the ratio and the plan need no device: a refusal comes before one is looked for
+  rfree::Plan plan;
+  if (int rc = plan_for(sr_in, sr_out, channels, src_dtype, out_dtype, lanes, max_frames, max_take, prefill, &plan)) return rc;
+  if (int rc = check_device(device, kMaxDevices)) return rc;
+  DeviceGuard g(device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  rced_rfree* h = new (std::nothrow) rced_rfree();
+  if (!h) return rced_fail(RCED_ERR_ALLOC, "host allocation failed");
+  h->plan = plan;
+  h->sr_in = sr_in;
+  h->sr_out = sr_out;
+  h->channels = channels;
+  h->src_dtype = src_dtype;
+  h->out_dtype = out_dtype;
+  h->lanes = lanes;
+  h->device = device;
+  int p, q, left, width;
+  int rc = rced_resample_table(sr_in, sr_out, &p, &q, &left, &width, device, &h->table);
+  const size_t bytes = (size_t)lanes * plan.words * sizeof(long long);
+  if (!rc) {
+    const hipError_t e = hipMalloc(&h->state, bytes);
+    if (e != hipSuccess)
+      rc = rced_fail(e == hipErrorOutOfMemory ? RCED_ERR_ALLOC : RCED_ERR_HIP, "hipMalloc(free-running lanes): %s", hipGetErrorString(e));
+  }
+  if (!rc && hipMemset(h->state, 0, bytes) != hipSuccess) rc = rced_fail(RCED_ERR_HIP, "hipMemset(free-running lane state)");
+  if (rc) {
+    (void)hipFree(h->state);
+    delete h;
+    return rc;
+  }
+  *out = h;
+  return RCED_OK;
+}
+
+void rced_rfree_destroy(rced_rfree* h) {
+  if (!h) return;
+  DeviceGuard g(h->device);
+  (void)hipDeviceSynchronize();   // launches that still use the state
+  (void)hipFree(h->state);
+  delete h;
+}
+
+int rced_rfree_push(rced_rfree* h, const void* pcm_dev, int in_cols, const int* counts_dev, void* out_dev, int out_cols, const int* take_dev,
+                    void* stream) {
+  if (!h) return rced_fail(RCED_ERR_ARG, "lanes are NULL");
+  if (in_cols < 0 || in_cols > h->plan.max_in) return rced_fail(RCED_ERR_ARG, "in_cols must be 0..max_frames = %d, got %d", h->plan.max_in, in_cols);
+  if (out_cols < 0 || out_cols > h->plan.max_take)
+    return rced_fail(RCED_ERR_ARG, "out_cols must be 0..max_take = %d, got %d", h->plan.max_take, out_cols);
+  if ((in_cols && !pcm_dev) || (out_cols && !out_dev)) return rced_fail(RCED_ERR_ARG, "null pointer");
+  DeviceGuard g(h->device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", h->device);
+  return launch(h, pcm_dev, in_cols, counts_dev, take_dev, 0, out_dev, out_cols, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int rced_rfree_finish(rced_rfree* h, const void* tail_dev, int in_cols, const int* tail_counts_dev, void* out_dev, int* out_counts_dev,
+                      void* stream) {
+  if (!h) return rced_fail(RCED_ERR_ARG, "lanes are NULL");
+  if (in_cols < 0 || in_cols > h->plan.max_in) return rced_fail(RCED_ERR_ARG, "in_cols must be 0..max_frames = %d, got %d", h->plan.max_in, in_cols);
+  if ((in_cols && !tail_dev) || !tail_counts_dev || !out_dev || !out_counts_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
+  DeviceGuard g(h->device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", h->device);
+  return launch(h, tail_dev, in_cols, tail_counts_dev, nullptr, 1, out_dev, h->plan.finish_max, out_counts_dev, static_cast<hipStream_t>(stream));
+}
+
+int rced_rfree_reset(rced_rfree* h, int lane) {
+  if (!h) return rced_fail(RCED_ERR_ARG, "lanes are NULL");
   if (lane < -1 || lane >= h->lanes) return rced_fail(RCED_ERR_ARG, "lane must be -1 (all) or 0..%d, got %d", h->lanes - 1, lane);
   DeviceGuard g(h->device);
   if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", h->device);

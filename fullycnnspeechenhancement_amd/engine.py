@@ -235,7 +235,7 @@ class InferenceEngine(FullyCNNTester):
                 w.close()
         return out
 
-    def denoise_stream(self, chunks, hops=8, nfft=512, sample_rate=8000, output_rate=None, rebuild="reference"):
+    def denoise_stream(self, chunks, hops=8, nfft=512, sample_rate=8000, output_rate=None, rebuild="reference", block=None):
         """denoise_pcm for audio that arrives in pieces: a generator over an iterable of 1-D PCM pieces of any size.  The
         pieces are re-blocked to whole hops (128 samples) and pushed, at most `hops` hops at a time, through a one-lane
         audio.StreamingDenoiser; every push's output is yielded as it comes (numpy float32, the result delayed by 640
@@ -243,9 +243,26 @@ class InferenceEngine(FullyCNNTester):
         denoise_pcm of the joined input.
         sample_rate / output_rate: the pieces are mono float at sample_rate and re-blocked to that rate's hop; the lane is
         StreamingDenoiser(sample_rate=..., output_rate=...), which see for the delay and the rates it refuses.
-        rebuild: "reference" or "ola", as in denoise_pcm; the delay is the same."""
+        rebuild: "reference" or "ola", as in denoise_pcm; the delay is the same.
+        block: None, or a number of frames: the pieces are cut to blocks of that size and go through a one-lane
+        audio.BlockDenoiser(block=..., sample_rate=..., output_rate=...), which serves every rate (44.1 kHz too) and yields block *
+        output_rate / sample_rate samples a block, the result delayed by audio.block_delay(block, sample_rate, output_rate);
+        `hops` plays no part."""
         from . import audio
         check_rebuild(rebuild)
+        if block is not None:
+            lane = audio.BlockDenoiser(self.model, 1, int(block), sample_rate=sample_rate, output_rate=output_rate, nfft=nfft, rebuild=rebuild)
+            try:
+                held = np.zeros(0, np.float32)
+                for piece in chunks:
+                    held = np.concatenate([held, np.asarray(piece, np.float32).reshape(-1)])
+                    while held.size >= lane.block:
+                        yield lane.process(held[None, :lane.block])[0]
+                        held = held[lane.block:]
+                yield lane.finish([0], [held])[0]
+            finally:
+                lane.close()
+            return
         stream = audio.StreamingDenoiser(self.model, 1, max_hops=int(hops), nfft=nfft, sample_rate=sample_rate, output_rate=output_rate,
                                          rebuild=rebuild)
         hop = stream.hop_in

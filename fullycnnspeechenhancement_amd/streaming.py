@@ -183,6 +183,27 @@ def stream_delay(sample_rate=8000, output_rate=None, channels=1, dtype="float32"
     return d
 
 
+def drain_hops(n_lanes, push, finish, lanes, seqs):
+    """Whole hops of seqs[i] through lane lanes[i] of a stage of n_lanes lanes that takes the 8 kHz signal, given as its push and
+    finish, one hop a push, the other lanes idle; then its finish with what is left.  Returns every lane's output, joined."""
+    unit = STEP
+    seqs = [np.asarray(s, np.float32) for s in seqs]
+    got = [[] for _ in lanes]
+    at = 0
+    while any(len(s) - at >= unit for s in seqs):
+        pcm, active = np.zeros((n_lanes, unit), np.float32), [0] * n_lanes
+        for lane, s in zip(lanes, seqs):
+            if len(s) - at >= unit:
+                pcm[lane], active[lane] = s[at:at + unit], 1
+        out = push(pcm, active)
+        for i, (lane, s) in enumerate(zip(lanes, seqs)):
+            if len(s) - at >= unit:
+                got[i].append(np.asarray(out[lane]))
+        at += unit
+    rest = finish(lanes, [s[len(s) // unit * unit:] for s in seqs])
+    return [np.concatenate(g + [np.asarray(r)]) for g, r in zip(got, rest)]
+
+
 class StreamingDenoiser(object):
     """PCM in, PCM out, a hop (128 samples, 16 ms) at a time, for `lanes` independent streams at once (rced_stream_*,
     DESIGN.md 3.4d).  A lane's output is InferenceEngine.denoise_pcm of everything pushed before `finish`, delayed by
@@ -265,24 +286,7 @@ class StreamingDenoiser(object):
         return y if as_torch else y.cpu().numpy()
 
     def _drain(self, push, finish, lanes, seqs):
-        """Whole hops of seqs[i] through lane lanes[i] of a stage that takes the 8 kHz signal, given as its push and finish, one
-        hop a push, the other lanes idle; then its finish with what is left.  Returns every lane's output, joined."""
-        unit = STEP
-        seqs = [np.asarray(s, np.float32) for s in seqs]
-        got = [[] for _ in lanes]
-        at = 0
-        while any(len(s) - at >= unit for s in seqs):
-            pcm, active = np.zeros((self.lanes, unit), np.float32), [0] * self.lanes
-            for lane, s in zip(lanes, seqs):
-                if len(s) - at >= unit:
-                    pcm[lane], active[lane] = s[at:at + unit], 1
-            out = push(pcm, active)
-            for i, (lane, s) in enumerate(zip(lanes, seqs)):
-                if len(s) - at >= unit:
-                    got[i].append(np.asarray(out[lane]))
-            at += unit
-        rest = finish(lanes, [s[len(s) // unit * unit:] for s in seqs])
-        return [np.concatenate(g + [np.asarray(r)]) for g, r in zip(got, rest)]
+        return drain_hops(self.lanes, push, finish, lanes, seqs)
 
     def finish(self, lanes, tails):
         """Ends the utterance of every lane listed: tails[i] holds the last 0..127 samples of lane lanes[i].  Returns a list of

@@ -411,6 +411,55 @@ int rced_rstream_started(rced_rstream* h, const int* active_dev, int* started_de
 /* Back to the start of an utterance without output: lane, or -1 for every lane.  Ordered on the stream of the latest push / finish. */
 int rced_rstream_reset(rced_rstream* h, int lane);
 
+/* ---- free-running resampler: the same conversion for audio that arrives in pieces of any size, without a delay.  A
+ * lane counts in frames.  With right = width - 1 - left of rced_resample_taps, output m of y = rced_resample(x) reads frames up to
+ * floor(m q / p) + right, so after F frames exactly A(F) = ceil((F - right) p / q) outputs (0 for F <= right) are final; a push
+ * computes the new ones, [A(F), A(F + count)), each by the chain of fused multiply-adds rced_resample runs, into a ring on the device
+ * and hands out of the ring as many samples as the caller takes.  The ring starts an utterance holding `prefill` zeros.  What a lane
+ * hands out, from the start of an utterance to the end of its rced_rfree_finish, is `prefill` zeros and then y, M =
+ * rced_resample_length(L) samples, bit for bit.  The ring holds prefill + A(F) - (samples taken) samples, a function of numbers the
+ * caller knows: the caller keeps count, takes no more than is there and leaves no more than the capacity (rced_rfree_plan) less what
+ * the next push adds -- at most ceil(max_frames p / q).  A take beyond what is there hands out zeros for the rest and does not move
+ * past the ring's end; no call reads or writes outside the ring.  sr_in == sr_out passes samples through exactly (a re-blocker).
+ * Source and output formats, downmix and scaling as in rced_resample.  All state lives on the device (per lane the frames taken, the
+ * samples handed out, the last width - 1 frames in float64 and the ring); after rced_rfree_create a push is one launch on the
+ * caller's stream, allocates nothing, does not synchronise and can be captured.  An object is not thread-safe. ---- */
+typedef struct rced_rfree rced_rfree;
+
+/* A(frames) for the ratio: host arithmetic, no device.  -1 (and rced_last_error) for what rced_resample_taps refuses or frames < 0. */
+long long rced_rfree_available(int sr_in, int sr_out, long long frames);
+
+/* The sizes rced_rfree_create would give lanes of these arguments, without a device; any pointer may be NULL.  history: frames a lane
+ * keeps (width - 1); tile: outputs per staging pass; capacity: the ring's, prefill + ceil(max_frames p / q) + max_take samples;
+ * finish_max: samples per lane of rced_rfree_finish's out_dev.  Refuses what rced_rfree_create refuses. */
+int rced_rfree_plan(int sr_in, int sr_out, int out_dtype, int lanes, int max_frames, int max_take, int prefill, int* history, int* tile,
+                    int* capacity, int* finish_max);
+
+/* lanes 1..65536; a push brings at most max_frames >= 1 frames and takes at most max_take >= 1 samples per lane; prefill >= 0.
+ * RCED_ERR_ARG, before a device is looked for: bad formats and sizes, and what rced_resample_taps refuses (the message names the
+ * ratio).  The first object of a ratio on a device uploads its table. */
+int rced_rfree_create(int sr_in, int sr_out, int channels, int src_dtype, int out_dtype, int lanes, int max_frames, int max_take,
+                      int prefill, int device, rced_rfree** out);
+void rced_rfree_destroy(rced_rfree* h);
+
+/* pcm_dev [lanes, in_cols, channels] of src_dtype, 0 <= in_cols <= max_frames; counts_dev: NULL (in_cols frames each) or [lanes] int32,
+ * the frames lane s brings, 0 .. in_cols (more counts as in_cols); a negative count is an idle lane: its state does not change, its
+ * input row is not read and zeros are written to its output row.  out_dev [lanes, out_cols] of out_dtype, 0 <= out_cols <= max_take;
+ * take_dev: NULL (out_cols each) or [lanes] int32, the samples lane s hands out into out_dev[s, :take], zeros behind them.  A pointer
+ * may be NULL where its column count is 0.  Asynchronous. */
+int rced_rfree_push(rced_rfree* h, const void* pcm_dev, int in_cols, const int* counts_dev, void* out_dev, int out_cols,
+                    const int* take_dev, void* stream);
+
+/* Ends the utterance of every lane whose tail_counts_dev entry is 0 .. in_cols: tail_dev [lanes, in_cols, channels] holds that many
+ * last frames (in_cols <= max_frames).  out_dev [lanes, finish_max] receives from column 0 what is in the ring and behind it the
+ * outputs up to M, computed with zeros past L, zeros behind them; out_counts_dev [lanes] int32 that count, prefill + M - (samples
+ * taken).  The lane is then at the start of an utterance.  Any other entry: the lane is left alone (count 0).  Asynchronous. */
+int rced_rfree_finish(rced_rfree* h, const void* tail_dev, int in_cols, const int* tail_counts_dev, void* out_dev, int* out_counts_dev,
+                      void* stream);
+
+/* Back to the start of an utterance without output: lane, or -1 for every lane.  Ordered on the stream of the latest push / finish. */
+int rced_rfree_reset(rced_rfree* h, int lane);
+
 /* ---- training step: FullyCNNTrainer.creat_graph + train_step,
  * model_utils/trainer.py:156-192, over Model(is_training=True).  Layer-by-layer, correctness first. ---- */
 typedef struct rced_trainer rced_trainer;

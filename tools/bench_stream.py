@@ -4,7 +4,10 @@ with torch.cuda events: ms per push and frames/s, beside the offline PCM-to-PCM 
 same total frame count (256 utterances of K frames) and at BASELINE config-3 scale (256 x 512 frames).  One JSON line per row.
 A push recomputes 7 frames per lane for the CNN: `recompute` is (K + 7) / K.
 --rebuild both (the default) times a reference-rebuild stream and an overlap-add stream (rebuild="ola") in the same run, in alternating
-rounds, and reports each one's median round and their ratio; --rebuild reference / ola times one of them."""
+rounds, and reports each one's median round and their ratio; --rebuild reference / ola times one of them.
+The last line times audio.BlockDenoiser (--blocks: that line alone): ms per process() for 256 lanes at 48 kHz in blocks of 480
+and of 768 frames and at 44.1 kHz in blocks of 441, beside StreamingDenoiser(48000, 48000)'s push of one hop (768 frames), all four in
+alternating rounds of the same run; one JSON line."""
 import argparse, json, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -16,6 +19,7 @@ parser = argparse.ArgumentParser(description=__doc__)
 parser.add_argument("--rebuild", choices=("both", "reference", "ola"), default="both",
                     help="the streams' rebuild; both (default): one stream of each, timed in alternating rounds of the same run")
 parser.add_argument("--rounds", type=int, default=5, help="timed rounds per stream; the median is reported")
+parser.add_argument("--blocks", action="store_true", help="time BlockDenoiser.process at 48 and 44.1 kHz beside the one-hop push at 48 kHz")
 args = parser.parse_args()
 REBUILDS = ("reference", "ola") if args.rebuild == "both" else (args.rebuild,)
 
@@ -45,6 +49,32 @@ def offline(n, t):
     return chain
 
 
+def block_rows():
+    cases = {"block_480_at_48000": (48000, 480), "block_768_at_48000": (48000, 768), "block_441_at_44100": (44100, 441)}
+    objs = {name: audio.BlockDenoiser(model, LANES, block, sample_rate=rate, output_rate=rate) for name, (rate, block) in cases.items()}
+    pcm = {name: torch.randn((LANES, block), device="cuda") * 0.1 for name, (rate, block) in cases.items()}
+    calls = {name: (lambda name=name: objs[name].process(pcm[name])) for name in cases}
+    hop = audio.StreamingDenoiser(model, LANES, max_hops=1, sample_rate=48000, output_rate=48000)
+    hop_pcm = torch.randn((LANES, 768), device="cuda") * 0.1
+    calls["hop_push_768_at_48000"] = lambda: hop.push(hop_pcm)
+    rounds = {name: [] for name in calls}
+    for _ in range(args.rounds):               # a period of the 44.1 kHz pattern is 128 calls: 1,280 calls cover ten
+        for name, fn in calls.items():
+            rounds[name].append(timed(fn, 1280))
+    row = {"lanes": LANES, "rounds": args.rounds}
+    for name, v in rounds.items():
+        row[name] = {"ms": statistics.median(v), "ms_rounds": [round(x, 5) for x in v]}
+        if name in objs:
+            row[name].update(delay=objs[name].delay, hops_per_call=objs[name].hops_per_call)
+    print(json.dumps(row), flush=True)
+    for o in list(objs.values()) + [hop]:
+        o.close()
+
+
+if args.blocks:
+    block_rows()
+    sys.exit(0)
+
 for k in (1, 8, 32):
     streams = {r: audio.StreamingDenoiser(model, LANES, max_hops=k, rebuild=r) for r in REBUILDS}
     pcm = torch.randn((LANES, k * 128), device="cuda") * 0.1
@@ -68,3 +98,4 @@ for k in (1, 8, 32):
     print(json.dumps(row), flush=True)
 ms = timed(offline(256, 512), 20)
 print(json.dumps({"offline_utterances": 256, "offline_frames_each": 512, "offline_ms": ms, "offline_frames_per_s": 256 * 512 / (ms * 1e-3)}))
+block_rows()
