@@ -43,6 +43,12 @@ SYMBOLS = {
     "rced_stft_ex": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int]),
     "rced_istft_ex": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int]),
     "rced_istft_ola": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp]),
+    "rced_framing_check": (ctypes.c_int, [ctypes.c_int] * 3),
+    "rced_stft_num_frames_fr": (ctypes.c_int, [ctypes.c_int] * 3),
+    "rced_stft_fr": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 6 + [_vp, _vp, ctypes.c_int, _vp]),
+    "rced_istft_fr": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 5 + [_vp, ctypes.c_int, _vp]),
+    "rced_istft_fr_check": (ctypes.c_int, [ctypes.c_int] * 3),
+    "rced_istft_ola_fr": (ctypes.c_int, [_vp, _vp, _vp] + [ctypes.c_int] * 5 + [_vp, ctypes.c_int, _vp]),
     "rced_sdr": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp]),
     "rced_stoi": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp]),
     "rced_stoi_ex": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp,

@@ -3,6 +3,7 @@
 
 #include <atomic>
 #include <cmath>
+#include <map>
 #include <mutex>
 #include <vector>
 
@@ -13,6 +14,7 @@
 #include "kernels_audio.h"
 #include "kernels_audio_x6.h"
 #include "kernels_ola_x6.h"
+#include "kernels_framing.h"
 #include "rced_internal.h"
 
 using namespace rced;
@@ -166,6 +168,164 @@ int tables(int device, AudioTables** out) {
   return RCED_OK;
 }
 
+
+// ---- any framing (kernels_framing.h) ----------------------------------------------------------------------------------------------
+// numpy's hamming / hanning / blackman / bartlett at length W >= 2, as numpy evaluates them (over n = 1 - W + 2k), in double
+double window_at(int name, int W, int k) {
+  const double n = 1.0 - W + 2.0 * k, a = M_PI * n / (W - 1);
+  switch (name) {
+    case RCED_WINDOW_HAMMING: return 0.54 + 0.46 * std::cos(a);
+    case RCED_WINDOW_HANNING: return 0.5 + 0.5 * std::cos(a);
+    case RCED_WINDOW_BLACKMAN: return 0.42 + 0.5 * std::cos(a) + 0.08 * std::cos(2.0 * a);
+    default: return n <= 0 ? 1.0 + n / (W - 1) : 1.0 - n / (W - 1);   // bartlett
+  }
+}
+
+const char* const kWindowNames[4] = {"hamming", "hanning", "blackman", "bartlett"};
+
+int framing_check(int W, int S, int name) {
+  if (W < 2 || W > audio::fr::kMaxWindow)
+    return rced_fail(RCED_ERR_ARG, "window must lie in [2, 256] samples (rfft(256) would crop a longer frame), got %d", W);
+  if (S < 1 || S > W) return rced_fail(RCED_ERR_ARG, "stride must lie in [1, window = %d] samples, got %d", W, S);
+  if (name < 0 || name > 3) return rced_fail(RCED_ERR_ARG, "window name must be RCED_WINDOW_HAMMING .. RCED_WINDOW_BARTLETT (0..3), got %d", name);
+  return RCED_OK;
+}
+
+int reference_rebuild_check(int name) {
+  if (name != RCED_WINDOW_HAMMING)
+    return rced_fail(RCED_ERR_ARG,
+                     "the reference rebuild divides every frame by its window, and the ends of a %s window are zero: the result is not "
+                     "finite (or off by 1e17); it is built for hamming only -- use the overlap-add rebuild",
+                     name >= 0 && name <= 3 ? kWindowNames[name] : "?");
+  return RCED_OK;
+}
+
+// One pack per (kind, window length, window name) and device, with the fp32 table that goes with it; the stride enters no pack.
+enum { kFrStft = 0, kFrOla = 1, kFrRef256 = 2, kFrRef512 = 3 };
+struct FrPack {
+  unsigned short* pack = nullptr;
+  float* aux = nullptr;   // rebuilds: [2][256], the coefficients of im(bin 128) (row scale folded in), then w^2; kFrStft: none
+};
+std::map<int, FrPack> g_fr[kMaxDevices];
+bool g_fr_attr[kMaxDevices] = {};
+// Held by an _fr entry from its look-up to its last launch: a pack or a frame buffer is never freed (below) between the moment a call
+// has its pointer and the moment its kernels are queued.
+std::mutex g_fr_mu;
+constexpr size_t kFrMaxPacks = 64;   // 25 MB; past it every pack of the device is dropped (after the device has gone idle) and rebuilt on demand
+
+double irfft_coef(int nfft, int n, int b, int c) {   // istft_coef without a window
+  const bool edge = b == 0 || 2 * b == nfft;
+  if (edge && c) return 0.0;
+  const double th = 2.0 * M_PI * ((long long)b * n % nfft) / nfft;
+  return (edge ? 1.0 : 2.0) / nfft * (c ? -std::sin(th) : std::cos(th));
+}
+
+int build_fr(FrPack& e, int kind, int W, int name) {
+  std::vector<double> w(audio::kFrame, 0.0);
+  for (int k = 0; k < W; ++k) w[k] = window_at(name, W, k);
+  if (kind == kFrStft) {
+    auto coef = [&](int row, int k) {
+      const int b = row == 1 ? 128 : row >> 1;
+      const bool im = row >= 2 && (row & 1);
+      const double th = 2.0 * M_PI * ((b * k) % audio::kFrame) / audio::kFrame;
+      return w[k] * (im ? -std::sin(th) : std::cos(th));
+    };
+    return upload(&e.pack, pack_x6(audio::fr::kFrMT, coef), kWhat);
+  }
+  const int nfft = kind == kFrRef512 ? 512 : 256;
+  auto scale = [&](int r) { return r >= W ? 0.0 : kind == kFrOla ? w[r] : 1.0 / w[r]; };
+  auto coef = [&](int row, int k) { return scale(row) * (k == 1 ? irfft_coef(nfft, row, 128, 0) : irfft_coef(nfft, row, k >> 1, k & 1)); };
+  if (int rc = upload(&e.pack, pack_x6(audio::fr::kFrMT, coef), kWhat)) return rc;
+  std::vector<float> aux(2 * audio::kFrame);
+  for (int r = 0; r < audio::kFrame; ++r) {
+    aux[r] = (float)(scale(r) * irfft_coef(nfft, r, 128, 1));    // zero at nfft = 256: irfft ignores im of the Nyquist bin
+    aux[audio::kFrame + r] = (float)(w[r] * w[r]);
+  }
+  return upload(&e.aux, aux, kWhat);
+}
+
+int fr_pack(int device, int kind, int W, int name, FrPack* out) {   // g_fr_mu held
+  if (int rc = check_device(device, kMaxDevices)) return rc;
+  if (!g_fr_attr[device]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(audio::fr::stft_fr_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       audio::fr::kStftFrLdsBytes);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(audio::fr::frames_fr_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              audio::fr::kFramesFrLdsBytes);
+    if (e != hipSuccess) return rced_fail(RCED_ERR_HIP, "hipFuncSetAttribute(framing LDS): %s", hipGetErrorString(e));
+    g_fr_attr[device] = true;
+  }
+  std::map<int, FrPack>& m = g_fr[device];
+  const int key = (kind * 4 + name) * 512 + W;
+  auto it = m.find(key);
+  if (it == m.end()) {
+    if (m.size() >= kFrMaxPacks) {
+      HIP_TRY(hipDeviceSynchronize());   // a kernel in flight may still read one
+      for (auto& kv : m) {
+        (void)hipFree(kv.second.pack);
+        (void)hipFree(kv.second.aux);
+      }
+      m.clear();
+    }
+    FrPack e;
+    if (int rc = build_fr(e, kind, W, name)) {
+      (void)hipFree(e.pack);
+      return rc;
+    }
+    it = m.emplace(key, e).first;
+  }
+  *out = it->second;
+  return RCED_OK;
+}
+
+// The frames between the two steps of a rebuild, [N, T, 256] fp32: one buffer per (device, stream) that only grows, as eval_api.hip
+// keeps its slice partials -- launches on one stream are ordered, and a call whose shape fits allocates nothing.
+struct FrScratch {
+  float* p = nullptr;
+  size_t bytes = 0;
+};
+std::map<void*, FrScratch> g_fr_scratch[kMaxDevices];
+
+int fr_scratch(int device, void* stream, size_t bytes, float** out) {   // g_fr_mu held
+  FrScratch& w = g_fr_scratch[device][stream];
+  if (w.bytes < bytes) {
+    if (w.p) {
+      HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));   // an earlier call may still read it
+      (void)hipFree(w.p);
+      w = FrScratch();
+    }
+    HIP_TRY(hipMalloc(&w.p, bytes));
+    w.bytes = bytes;
+  }
+  *out = w.p;
+  return RCED_OK;
+}
+
+// frames_fr_kernel, then rebuild_fr_kernel<OLA>
+template <bool OLA>
+int rebuild_fr(const float* mag_dev, const float* phase_dev, const int* frames_dev, int N, int T, int kind, int W, int S, int name,
+               float* audio_dev, int device, void* stream) {
+  DeviceGuard g(device);
+  std::lock_guard<std::mutex> lk(g_fr_mu);
+  FrPack p;
+  if (int rc = fr_pack(device, kind, W, name, &p)) return rc;
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  float* Y = nullptr;
+  if (T > 0) {
+    if (int rc = fr_scratch(device, stream, (size_t)N * T * audio::kFrame * sizeof(float), &Y)) return rc;
+    const int nblk = (T + audio::kFramesPerWg - 1) / audio::kFramesPerWg;
+    if (nblk > 65535) return rced_fail(RCED_ERR_ARG, "T > 65535 * 64 frames per call");
+    hipLaunchKernelGGL(audio::fr::frames_fr_kernel, dim3(N, 2, nblk), dim3(audio::x6::kThreadsX), audio::fr::kFramesFrLdsBytes, st, mag_dev, phase_dev,
+                       frames_dev, (const unsigned short*)p.pack, (const float*)p.aux, T, W, Y);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(audio::fr::rebuild_fr_kernel<OLA>, dim3(N), dim3(audio::x6::kThreadsX), 0, st, (const float*)Y, frames_dev, (const float*)p.aux + audio::kFrame, T, W, S,
+                     audio_dev);
+  HIP_TRY(hipGetLastError());
+  return RCED_OK;
+}
+
 }  // namespace
 
 int rced_audio_x6_tables_get(int device, int nfft, rced_audio_x6_tables* out) {
@@ -273,6 +433,59 @@ int rced_istft_ola(const float* mag_dev, const float* phase_dev, const int* fram
                      mag_dev, phase_dev, frames_dev, (const unsigned short*)t->ola_x6, (const float*)t->ola_fix, T, audio_dev);
   HIP_TRY(hipGetLastError());
   return RCED_OK;
+}
+
+int rced_framing_check(int window, int stride, int window_name) { return framing_check(window, stride, window_name); }
+
+int rced_istft_fr_check(int window, int stride, int window_name) {
+  if (int rc = framing_check(window, stride, window_name)) return rc;
+  return reference_rebuild_check(window_name);
+}
+
+int rced_stft_num_frames_fr(int length, int window, int stride) {
+  if (framing_check(window, stride, RCED_WINDOW_HAMMING)) return -1;
+  return length > 0 ? audio::fr::num_frames(length, window, stride) : 0;
+}
+
+int rced_stft_fr(const float* pcm_dev, const int* lengths_dev, int N, int L, int T, int window, int stride, int window_name, float* mag_dev,
+                 float* phase_dev, int device, void* stream) {
+  if (int rc = framing_check(window, stride, window_name)) return rc;
+  if (N < 0 || L < 0 || T < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
+  if (N == 0 || T == 0) return RCED_OK;
+  if (L == 0) return rced_fail(RCED_ERR_ARG, "empty signals (L = 0) with T > 0");
+  if (!pcm_dev || !mag_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
+  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
+  DeviceGuard g(device);
+  std::lock_guard<std::mutex> lk(g_fr_mu);
+  FrPack p;
+  if (int rc = fr_pack(device, kFrStft, window, window_name, &p)) return rc;
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  hipLaunchKernelGGL(audio::fr::stft_fr_kernel, dim3(N, 2, range_split(N, T)), dim3(audio::x6::kThreadsX), audio::fr::kStftFrLdsBytes,
+                     static_cast<hipStream_t>(stream), pcm_dev, lengths_dev, (const unsigned short*)p.pack, L, T, window, stride, mag_dev, phase_dev);
+  HIP_TRY(hipGetLastError());
+  return RCED_OK;
+}
+
+int rced_istft_fr(const float* mag_dev, const float* phase_dev, int N, int T, int nfft, int window, int stride, float* audio_dev, int device,
+                  void* stream) {
+  if (int rc = framing_check(window, stride, RCED_WINDOW_HAMMING)) return rc;
+  if (N < 0 || T < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
+  if (nfft != 512 && nfft != 256) return rced_fail(RCED_ERR_ARG, "nfft must be 512 (reference default) or 256");
+  if (N == 0 || T == 0) return RCED_OK;
+  if (!mag_dev || !phase_dev || !audio_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
+  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
+  return rebuild_fr<false>(mag_dev, phase_dev, nullptr, N, T, nfft == 512 ? kFrRef512 : kFrRef256, window, stride, RCED_WINDOW_HAMMING, audio_dev,
+                           device, stream);
+}
+
+int rced_istft_ola_fr(const float* mag_dev, const float* phase_dev, const int* frames_dev, int N, int T, int window, int stride, int window_name,
+                      float* audio_dev, int device, void* stream) {
+  if (int rc = framing_check(window, stride, window_name)) return rc;
+  if (N < 0 || T < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
+  if (N == 0) return RCED_OK;
+  if (!audio_dev || (T > 0 && (!mag_dev || !phase_dev))) return rced_fail(RCED_ERR_ARG, "null pointer");
+  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
+  return rebuild_fr<true>(mag_dev, phase_dev, frames_dev, N, T, kFrOla, window, stride, window_name, audio_dev, device, stream);
 }
 
 }  // extern "C"

@@ -85,11 +85,12 @@ class FullyCNNTester(object):
             pool[2] ^= 1
         return self.model(input_x, out=out) if out is not None else self.model(input_x)
 
-    def evaluate_pcm(self, mix_sig, clean_sig, nfft=512, model=None, lengths=None, kernels="x6", stoi=False, extra=(), rebuild="reference"):
+    def evaluate_pcm(self, mix_sig, clean_sig, nfft=512, model=None, lengths=None, kernels="x6", stoi=False, extra=(), rebuild="reference",
+                     framing=None):
         """One batch of the evaluation loop (tester.py:100-146) from PCM, on the device: the module's evaluate_pcm with
         this engine's network, or with `model` (a callable, device [N, T, 129, 1] -> same) in its place."""
         return evaluate_pcm(model if model is not None else self.model, mix_sig, clean_sig, nfft, self.device, lengths, kernels,
-                            stoi=stoi, extra=extra, rebuild=rebuild)
+                            stoi=stoi, extra=extra, rebuild=rebuild, framing=framing)
 
     def test(self, valid_loader, stoi=False, extra=(), rebuild="reference"):
         """tester.py:92-167 over anything that yields the reference's 4-tuple (batch_mix, batch_clean, mix_sig,
@@ -101,11 +102,14 @@ class FullyCNNTester(object):
         extra: names from evaluation.EXTRA_METRICS ("estoi", "si_sdr", "seg_snr"); every utterance's score goes into
         self.extra_scores[name], and one further line with their averages follows the reference's.
         rebuild: "reference" (the rebuild the reference's scores are made with) or "ola" (weighted overlap-add: evaluate_pcm).
+        The framing is valid_loader.dataset.framing where the loader has one (loader.DataSet(framing=...)), as the reference
+        reads window_s from the dataset; else the default.
         PESQ and the wav files the reference writes next to the scores are not built."""
         extra = check_extra(extra)
         check_rebuild(rebuild)
+        framing = loader_framing(valid_loader)
         for _batch_mix, _batch_clean, mix_sig, clean_sig in valid_loader:
-            scores = self.evaluate_pcm(mix_sig, clean_sig, stoi=stoi, extra=extra, rebuild=rebuild)
+            scores = self.evaluate_pcm(mix_sig, clean_sig, stoi=stoi, extra=extra, rebuild=rebuild, framing=framing)
             for score in scores[1]:
                 self.sdr_score.update(float(score))
             if stoi:
@@ -128,7 +132,13 @@ def extra_line(extra, meters):
     return "; ".join("Average {}: {:.4f}".format(name, meters[name].avg) for name in extra) + ".\n"
 
 
-def evaluate_pcm(forward, mix_sig, clean_sig, nfft=512, device=0, lengths=None, kernels="x6", stoi=False, extra=(), rebuild="reference"):
+def loader_framing(loader):
+    """The framing a loader's batches were cut with: loader.dataset.framing, or None (the default) where there is none."""
+    return getattr(getattr(loader, "dataset", None), "framing", None)
+
+
+def evaluate_pcm(forward, mix_sig, clean_sig, nfft=512, device=0, lengths=None, kernels="x6", stoi=False, extra=(), rebuild="reference",
+                 framing=None):
     """What FullyCNNTester.test and FullyCNNTrainer.valid do with one batch (tester.py:104-146, trainer.py:264-307), each
     with its own forward (device [N, T, 129, 1] -> same): one upload, STFT with the lengths -> forward -> ISTFT rebuild
     (AudioReBuild(nfft), 512 as the reference ships it) -> SDR against the clean rows; the audio and N scores come back.
@@ -143,11 +153,15 @@ def evaluate_pcm(forward, mix_sig, clean_sig, nfft=512, device=0, lengths=None, 
     (audio.stoi_batch(extended=True), audio.si_sdr_batch, audio.seg_snr_batch of the same pairs).
     rebuild: "reference" (AudioReBuild as shipped, the default) or "ola" (weighted overlap-add, audio.istft_batch: utterance i is
     rebuilt from its own num_frames(length) frames, nfft plays no part); anything else, or "ola" with kernels="f32", is a
-    ValueError before any device work."""
+    ValueError before any device work.
+    framing: an audio.Framing (STFT and rebuild are cut by it; the reference rebuild exists for hamming windows only), or None
+    for the default, 256 / 128 / hamming."""
     extra = check_extra(extra)
     check_rebuild(rebuild, kernels)
     import torch
     from . import _args, audio
+    if rebuild == "reference":
+        audio.check_reference_rebuild(framing)
     empty = ([], np.zeros(0, np.float64)) + ((np.zeros(0, np.float64),) if stoi else ())
     if extra:
         empty += ({name: np.zeros(0, np.float64) for name in extra},)
@@ -175,7 +189,7 @@ def evaluate_pcm(forward, mix_sig, clean_sig, nfft=512, device=0, lengths=None, 
             both[1, i, :n] = clean_sig[i]
         both = torch.as_tensor(both, device="cuda:%d" % device)
         mix, clean = both[0], both[1]
-    scored = audio.denoise_and_score(forward, mix, clean, lens, nfft, kernels, stoi=stoi, extra=extra, rebuild=rebuild)
+    scored = audio.denoise_and_score(forward, mix, clean, lens, nfft, kernels, stoi=stoi, extra=extra, rebuild=rebuild, framing=framing)
     audio_host = scored[0].cpu().numpy()
     host = lambda s: {k: v.cpu().numpy() for k, v in s.items()} if isinstance(s, dict) else s.cpu().numpy()      # noqa: E731
     return ([audio_host[i, :lens[i]].copy() for i in range(len(lens))],) + tuple(host(s) for s in scored[1:])
@@ -185,17 +199,21 @@ class InferenceEngine(FullyCNNTester):
     """infer.py:19-52, the forward slice: `denoise_magnitude` is infer.py:62-65 without the
     STFT/ISTFT around it."""
 
-    def denoise_pcm(self, sig, nfft=512, sample_rate=8000, rebuild="reference"):
+    def denoise_pcm(self, sig, nfft=512, sample_rate=8000, rebuild="reference", framing=None):
         """infer.py:54-71 end to end on the device: STFT (audio_feature.py) -> model -> rebuild (utils.py:171-183).
         The magnitude is laid out [1, T, 129, 1] by TRANSPOSE, as the batch loader does
         (data_loader.py:206-208); infer.py:59 itself reshapes without transposing.
         sig: 1-D float PCM at 8 kHz.  Returns the denoised signal, same length, numpy float32.
         sample_rate other than 8000: sig is at that rate and is resampled to 8 kHz on the device first (audio.resample_batch:
         what infer.py's librosa.load(sr=8000) does to a file); the result is at 8 kHz, audio.resample_length samples.
-        rebuild: "reference" (utils.py:171-183 as shipped) or "ola" (weighted overlap-add, audio.istft_batch; nfft plays no part)."""
+        rebuild: "reference" (utils.py:171-183 as shipped) or "ola" (weighted overlap-add, audio.istft_batch; nfft plays no part).
+        framing: an audio.Framing, the framing the network was trained with, or None for the default (the cfg key `windows` is
+        not read, as in the reference: a checkpoint is never fed another window silently)."""
         import torch
         from . import audio
         check_rebuild(rebuild)
+        if rebuild == "reference":
+            audio.check_reference_rebuild(framing)
         dev = "cuda:%d" % self.device
         if int(sample_rate) != audio.SAMPLE_RATE:
             rows, lens = audio.resample_batch(np.asarray(sig, dtype=np.float32).reshape(1, -1), sample_rate, audio.SAMPLE_RATE,
@@ -203,25 +221,27 @@ class InferenceEngine(FullyCNNTester):
             pcm, n = rows[:, :lens[0]], lens[0]
         else:
             pcm, n = torch.as_tensor(np.asarray(sig, dtype=np.float32), device=dev)[None], len(sig)
-        mag, phase = audio.stft_batch(pcm)
+        mag, phase = audio.stft_batch(pcm, framing=framing)
         pred = self.model(mag)
-        out = audio.istft_batch(pred, phase, nfft, rebuild=rebuild)
+        out = audio.istft_batch(pred, phase, nfft, rebuild=rebuild, framing=framing)
         return out[0, :n].cpu().numpy()
 
-    def denoise_file(self, path, save_dir=None, nfft=512, rebuild="reference"):
+    def denoise_file(self, path, save_dir=None, nfft=512, rebuild="reference", framing=None):
         """infer.py:54-76 for one wav file: PCM16 of any rate and channel count is downmixed and resampled to 8 kHz on the
         device (loader.read_wav_frames + audio.resample_batch, in place of librosa.load(sr=8000)), denoised as denoise_pcm
         does, and -- with save_dir -- written as PCM16 at 8 kHz to save_dir/<basename with .wav -> _de.wav> (infer.py:72-76's
-        name; int16 by clip(rint(y * 32768))).  Returns the denoised float32 signal.  rebuild: as in denoise_pcm."""
+        name; int16 by clip(rint(y * 32768))).  Returns the denoised float32 signal.  rebuild, framing: as in denoise_pcm."""
         import os
         import wave
         from . import audio, loader
         check_rebuild(rebuild)
+        if rebuild == "reference":
+            audio.check_reference_rebuild(framing)
         frames, rate = loader.read_wav_frames(path)
         rows, lens = audio.resample_batch(frames[None], rate, audio.SAMPLE_RATE, device=self.device)
         n = lens[0]
-        mag, phase = audio.stft_batch(rows[:, :n])
-        out = audio.istft_batch(self.model(mag), phase, nfft, rebuild=rebuild)[0, :n].cpu().numpy()
+        mag, phase = audio.stft_batch(rows[:, :n], framing=framing)
+        out = audio.istft_batch(self.model(mag), phase, nfft, rebuild=rebuild, framing=framing)[0, :n].cpu().numpy()
         if save_dir is not None:
             os.makedirs(save_dir, exist_ok=True)
             pcm16 = np.clip(np.rint(out.astype(np.float64) * 32768.0), -32768, 32767).astype("<i2")

@@ -181,7 +181,7 @@ def mix_snr_batch(speech, noise, snr, speech_lengths=None, noise_lengths=None, s
     return mix
 
 
-def denoise_and_score(forward, mix, clean, lengths, nfft=512, kernels="x6", stoi=False, extra=(), rebuild="reference"):
+def denoise_and_score(forward, mix, clean, lengths, nfft=512, kernels="x6", stoi=False, extra=(), rebuild="reference", framing=None):
     """The device core of the evaluation loop (tester.py:100-146 / trainer.py:260-307 without PESQ / wav files):
     STFT of the mixtures -> forward (device [N, T, 129, 1] -> same) -> ISTFT rebuild -> SDR (and, with stoi=True, STOI) of
     every rebuilt row against its clean row over its own length.  mix, clean: torch.cuda float32 [N, L] zero-padded;
@@ -189,14 +189,17 @@ def denoise_and_score(forward, mix, clean, lengths, nfft=512, kernels="x6", stoi
     Returns (audio [N, (T+1)*128] on the device -- the caller trims row n to lengths[n] --, sdr torch.float64 [N]), with
     stoi=True (audio, sdr, stoi torch.float64 [N]); with extra, one more element last: a dict name -> torch.float64 [N]
     (STOI and ESTOI, asked for together, come from one rced_stoi_ex call).
-    rebuild: "reference" or "ola" (audio.istft_batch; "ola" rebuilds utterance n from its own num_frames(lengths[n]) frames)."""
+    rebuild: "reference" or "ola" (audio.istft_batch; "ola" rebuilds utterance n from its own num_frames(lengths[n]) frames).
+    framing: an audio.Framing for the STFT and the rebuild (the audio is then [N, (W - S) + T * S]), or None for the default."""
     from . import audio
     extra = check_extra(extra)
     _args.check_rebuild(rebuild, kernels)
-    mag, phase = audio.stft_batch(mix, lengths, kernels=kernels)
+    if rebuild == "reference":
+        audio.check_reference_rebuild(framing)       # before any device work
+    mag, phase = audio.stft_batch(mix, lengths, kernels=kernels, framing=framing)
     pred = forward(mag)
-    frames = [audio.num_frames(v) for v in _args.host_ints(lengths)] if rebuild == "ola" else None
-    out = audio.istft_batch(pred, phase, nfft, kernels=kernels, rebuild=rebuild, frames=frames)
+    frames = [audio.num_frames(v, framing) for v in _args.host_ints(lengths)] if rebuild == "ola" else None
+    out = audio.istft_batch(pred, phase, nfft, kernels=kernels, rebuild=rebuild, frames=frames, framing=framing)
     scored = (out, sdr_batch(clean, out, lengths))
     more = {}
     if stoi and "estoi" in extra:

@@ -330,9 +330,14 @@ class DataSet(object):
     batch is mixed with noise_list[k] at `snr` dB.  `mix=` is the paired mode (the reference's clean_audio_filepath /
     mix_audio_filepath manifests): item i of `mix` is the mixture of item i of `clean`, nothing is mixed.
     use_complex=True (the validation set of train.py): the reference then yields complex spectrograms that test() /
-    valid() never read (they recompute them from the PCM, engine.py); here the two spectrogram slots are None."""
+    valid() never read (they recompute them from the PCM, engine.py); here the two spectrogram slots are None.
+    framing: the audio.Framing the batches' spectrograms are cut with (None: the default); kept as `.framing`, where
+    FullyCNNTester.test and FullyCNNTrainer.valid read it, as the reference reads window_s from the dataset."""
 
-    def __init__(self, clean, noise=None, mix=None, snr=0, use_complex=False):
+    def __init__(self, clean, noise=None, mix=None, snr=0, use_complex=False, framing=None):
+        if framing is not None and not isinstance(framing, audio.Framing):
+            raise ValueError("framing must be an audio.Framing or None, got %r" % (framing,))
+        self.framing = framing
         if (noise is None) == (mix is None):
             raise ValueError("give either noise= (mixed at snr on the device) or mix= (a paired corpus)")
         if mix is not None and len(mix) != len(clean):
@@ -463,7 +468,7 @@ class DataLoader(object):
         clean_sig, mix_sig = PcmRows(both[:n], ls), PcmRows(both[n:], lm)
         if ds.complex:
             return None, None, mix_sig, clean_sig
-        mag, _ = audio.stft_batch(both, ls + lm, with_phase=False)
+        mag, _ = audio.stft_batch(both, ls + lm, with_phase=False, framing=ds.framing)
         return mag[n:], mag[:n], mix_sig, clean_sig
 
     def __iter__(self):

@@ -103,12 +103,15 @@ class FullyCNNTrainer(object):
         the line gains the reference's st_score field, in the reference's order.  extra: names from
         evaluation.EXTRA_METRICS; every utterance's score goes into self.extra_scores[name], and one further line with their
         averages is printed and logged after the reference's.  rebuild: "reference" or "ola" (engine.evaluate_pcm).
+        The framing is valid_loader.dataset.framing where there is one, else the default.
         PESQ and the wav files are not built."""
-        from .engine import check_rebuild, evaluate_pcm, extra_line
+        from .engine import check_rebuild, evaluate_pcm, extra_line, loader_framing
         extra = check_extra(extra)
         check_rebuild(rebuild)
+        framing = loader_framing(valid_loader)
         for _batch_mix, _batch_clean, mix_sig, clean_sig in valid_loader:
-            scores = evaluate_pcm(self.valid_step, mix_sig, clean_sig, nfft, self.device, stoi=stoi, extra=extra, rebuild=rebuild)
+            scores = evaluate_pcm(self.valid_step, mix_sig, clean_sig, nfft, self.device, stoi=stoi, extra=extra, rebuild=rebuild,
+                                  framing=framing)
             for score in scores[1]:
                 self.sdr_score.update(float(score))
             if stoi:

@@ -181,6 +181,45 @@ int rced_istft_ex(const float* mag_dev, const float* phase_dev, int N, int T, in
 int rced_istft_ola(const float* mag_dev, const float* phase_dev, const int* frames_dev, int N, int T, float* audio_dev,
                    int device, void* stream);
 
+/* ---- any framing: the same three transforms with the window length W, the stride S and the window's name as arguments.
+ * 2 <= W <= 256 (rfft(256) would crop a longer frame), 1 <= S <= W; the window is numpy's hamming / hanning / blackman / bartlett at
+ * length W, evaluated in double on the host.  These entries always run the general kernels (kernels_framing.h), at 256 / 128 / hamming
+ * too, where the entries above run the specialised ones.  Coefficient packs are cached per device and (W, name); the rebuilds keep a
+ * frame buffer [N, T, 256] per (device, stream) that only grows: after one call of a shape they allocate nothing. ---- */
+#define RCED_WINDOW_HAMMING 0
+#define RCED_WINDOW_HANNING 1
+#define RCED_WINDOW_BLACKMAN 2
+#define RCED_WINDOW_BARTLETT 3
+
+/* RCED_OK or RCED_ERR_ARG (the reason in rced_last_error); touches no device. */
+int rced_framing_check(int window, int stride, int window_name);
+
+/* ceil(|L - W| / S + 1) (audio_feature.py:70); 0 for length <= 0, -1 for a framing rced_framing_check refuses.  Host only. */
+int rced_stft_num_frames_fr(int length, int window, int stride);
+
+/* rced_stft at a framing: frame t holds the pre-emphasised samples t S .. t S + W - 1 (zero fill after pre-emphasis), times the window,
+ * rfft(256).  Shapes, lengths_dev, phase_dev = NULL and the padding frames (zero magnitude, phase 1+0j) as rced_stft. */
+int rced_stft_fr(const float* pcm_dev, const int* lengths_dev, int N, int L, int T, int window, int stride, int window_name,
+                 float* mag_dev, float* phase_dev, int device, void* stream);
+
+/* rced_istft at a framing, hamming window: irfft(n = nfft)[:W] / w, the first W - S samples of frame 0 and the last S samples of
+ * every frame, de-emphasis.  audio_dev [N, (W - S) + T * S].  There is no window name: the other three windows end in zero, so the
+ * reference's own division is not finite there (hanning, bartlett) or off by 1e17 (blackman); rced_istft_fr_check says so by name. */
+int rced_istft_fr(const float* mag_dev, const float* phase_dev, int N, int T, int nfft, int window, int stride, float* audio_dev,
+                  int device, void* stream);
+
+/* Whether the reference rebuild exists for a framing: RCED_OK for hamming, RCED_ERR_ARG with the reason for the other names (decided
+ * by the name, not by testing a window value against zero) and for a framing rced_framing_check refuses.  Touches no device. */
+int rced_istft_fr_check(int window, int stride, int window_name);
+
+/* rced_istft_ola at a framing.  x_t = irfft(mag_t * phase_t, 256)[:W];
+ *   e[i] = sum_t w[i - tS] x_t[i - tS] / sum_t w[i - tS]^2 over the frames t < F that cover i, and 0 where the denominator is at most
+ *   1e-10 (scipy.signal.istft's rule; never for hamming); y[i] = e[i] + 0.97 y[i-1]; columns from (F - 1) S + W on are 0.
+ * audio_dev [N, (W - S) + T * S], every column written; frames_dev and everything about frame counts as rced_istft_ola.  The addends
+ * of a sample are summed in ascending frame order: bit-identical run to run and whatever N, T or the utterance's row. */
+int rced_istft_ola_fr(const float* mag_dev, const float* phase_dev, const int* frames_dev, int N, int T, int window, int stride,
+                      int window_name, float* audio_dev, int device, void* stream);
+
 /* ---- evaluation loop (tester.py:92-167, trainer.py:252-338): the two numpy pieces around the rebuilt audio, for a
  * ragged batch.  Streaming reductions without atomics: results are bit-identical run to run, and utterance n's result
  * does not depend on N, on its neighbours, on its row index or on the row strides (kernels_eval.h).  Both keep a slice
