@@ -67,6 +67,10 @@ SYMBOLS = {
     "rced_stream_delay":(ctypes.c_int, []),
     "rced_stream_create": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
     "rced_stream_create_ex": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
+    "rced_stream_fr_check": (ctypes.c_int, [ctypes.c_int] * 4),
+    "rced_stream_delay_fr": (ctypes.c_int, [ctypes.c_int] * 2),
+    "rced_stream_finish_max_fr": (ctypes.c_int, [ctypes.c_int] * 2),
+    "rced_stream_create_fr": (ctypes.c_int, [_vp] + [ctypes.c_int] * 7 + [ctypes.POINTER(_vp)]),
     "rced_stream_destroy": (None, [_vp]),
     "rced_stream_push": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _vp]),
     "rced_stream_finish": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),

@@ -20,7 +20,7 @@ from .evaluation import (EXTRA_METRICS, STOI_RATES, denoise_and_score, gains_nee
                          seg_snr_batch, seg_snr_window, si_sdr_batch, stoi_batch)
 from .arena import PCM_DTYPES, gather_pcm, resample_arena, resample_batch, resample_length, resample_taps  # noqa: F401
 from .streaming import (STREAM_DELAY, STREAM_FINISH_MAX, STREAM_MAX_HOPS, StreamingDenoiser, StreamingResampler,  # noqa: F401
-                        resampler_delay, stream_delay)
+                        resampler_delay, stream_delay, stream_delay_fr)
 from .freerun import BlockDenoiser, FreeResampler, block_delay, free_available  # noqa: F401
 
 

@@ -205,13 +205,14 @@ enum { kFrStft = 0, kFrOla = 1, kFrRef256 = 2, kFrRef512 = 3 };
 struct FrPack {
   unsigned short* pack = nullptr;
   float* aux = nullptr;   // rebuilds: [2][256], the coefficients of im(bin 128) (row scale folded in), then w^2; kFrStft: none
+  int pins = 0;           // streams at this framing (rced_fr_tables_pin): a pinned pack is never dropped
 };
 std::map<int, FrPack> g_fr[kMaxDevices];
 bool g_fr_attr[kMaxDevices] = {};
 // Held by an _fr entry from its look-up to its last launch: a pack or a frame buffer is never freed (below) between the moment a call
 // has its pointer and the moment its kernels are queued.
 std::mutex g_fr_mu;
-constexpr size_t kFrMaxPacks = 64;   // 25 MB; past it every pack of the device is dropped (after the device has gone idle) and rebuilt on demand
+constexpr size_t kFrMaxPacks = 64;   // 25 MB; past it every pack of the device that no stream has pinned is dropped (after the device has gone idle) and rebuilt on demand
 
 double irfft_coef(int nfft, int n, int b, int c) {   // istft_coef without a window
   const bool edge = b == 0 || 2 * b == nfft;
@@ -244,6 +245,8 @@ int build_fr(FrPack& e, int kind, int W, int name) {
   return upload(&e.aux, aux, kWhat);
 }
 
+int fr_key(int kind, int W, int name) { return (kind * 4 + name) * 512 + W; }
+
 int fr_pack(int device, int kind, int W, int name, FrPack* out) {   // g_fr_mu held
   if (int rc = check_device(device, kMaxDevices)) return rc;
   if (!g_fr_attr[device]) {
@@ -256,16 +259,20 @@ int fr_pack(int device, int kind, int W, int name, FrPack* out) {   // g_fr_mu h
     g_fr_attr[device] = true;
   }
   std::map<int, FrPack>& m = g_fr[device];
-  const int key = (kind * 4 + name) * 512 + W;
+  const int key = fr_key(kind, W, name);
   auto it = m.find(key);
   if (it == m.end()) {
     if (m.size() >= kFrMaxPacks) {
       HIP_TRY(hipDeviceSynchronize());   // a kernel in flight may still read one
-      for (auto& kv : m) {
-        (void)hipFree(kv.second.pack);
-        (void)hipFree(kv.second.aux);
+      for (auto kv = m.begin(); kv != m.end();) {
+        if (kv->second.pins) {
+          ++kv;
+          continue;
+        }
+        (void)hipFree(kv->second.pack);
+        (void)hipFree(kv->second.aux);
+        kv = m.erase(kv);
       }
-      m.clear();
     }
     FrPack e;
     if (int rc = build_fr(e, kind, W, name)) {
@@ -341,6 +348,35 @@ int rced_audio_x6_tables_get(int device, int nfft, rced_audio_x6_tables* out) {
   out->ola = t->ola_x6;
   out->ola_fix = t->ola_fix;
   return RCED_OK;
+}
+
+int rced_fr_tables_pin(int device, int window, int window_name, int ola, int nfft, rced_fr_tables* out) {
+  DeviceGuard g(device);
+  std::lock_guard<std::mutex> lk(g_fr_mu);
+  const int kind = ola ? kFrOla : nfft == 512 ? kFrRef512 : kFrRef256;
+  FrPack a, c;
+  if (int rc = fr_pack(device, kFrStft, window, window_name, &a)) return rc;
+  g_fr[device][fr_key(kFrStft, window, window_name)].pins++;   // (before the second look-up, which may drop what is not pinned)
+  if (int rc = fr_pack(device, kind, window, window_name, &c)) {
+    g_fr[device][fr_key(kFrStft, window, window_name)].pins--;
+    return rc;
+  }
+  g_fr[device][fr_key(kind, window, window_name)].pins++;
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  out->stft = a.pack;
+  out->rebuild = c.pack;
+  out->cim = c.aux;
+  out->w2 = c.aux + audio::kFrame;
+  return RCED_OK;
+}
+
+void rced_fr_tables_unpin(int device, int window, int window_name, int ola, int nfft) {
+  std::lock_guard<std::mutex> lk(g_fr_mu);
+  const int kind = ola ? kFrOla : nfft == 512 ? kFrRef512 : kFrRef256;
+  for (int key : {fr_key(kFrStft, window, window_name), fr_key(kind, window, window_name)}) {
+    auto it = g_fr[device].find(key);
+    if (it != g_fr[device].end() && it->second.pins > 0) it->second.pins--;
+  }
 }
 
 extern "C" {

@@ -78,6 +78,18 @@ struct rced_audio_x6_tables {
 };
 int rced_audio_x6_tables_get(int device, int nfft, rced_audio_x6_tables* out);
 
+// the packs of a framing (audio_api.hip's per-device cache, kernels_framing.h), for the streaming kernels at a framing: the STFT pack,
+// the rebuild's (overlap-add, or the reference rebuild at nfft 256 / 512) and its two fp32 tables.  Pinned: they stay until
+// rced_fr_tables_unpin with the same arguments, whatever else the cache drops.
+struct rced_fr_tables {
+  const unsigned short* stft = nullptr;      // audio::fr::kFrPack
+  const unsigned short* rebuild = nullptr;   // audio::fr::kFrPack
+  const float* cim = nullptr;                // [256]: the coefficients of im(bin 128), row scale folded in (zeros unless nfft = 512)
+  const float* w2 = nullptr;                 // [256]: w^2, zero past the window
+};
+int rced_fr_tables_pin(int device, int window, int window_name, int ola, int nfft, rced_fr_tables* out);
+void rced_fr_tables_unpin(int device, int window, int window_name, int ola, int nfft);
+
 // stream_api.hip: streams created on `m` answer RCED_ERR_STATE from now on (rced_destroy calls this before the model goes)
 void rced_streams_detach(rced_model* m);
 

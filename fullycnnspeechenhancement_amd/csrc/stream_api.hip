@@ -1,6 +1,7 @@
 // C ABI of the streaming denoiser (include/rced.h, "streaming" section): host side.  Three launches per push on the caller's stream --
 // the stateful STFT, rced_forward on the lanes' windows, the stateful ISTFT (kernels_stream.h; for a stream created with
-// RCED_STREAM_REBUILD_OLA the overlap-add one, kernels_stream_ola.h) --, no allocation, no synchronisation.
+// RCED_STREAM_REBUILD_OLA the overlap-add one, kernels_stream_ola.h) --, no allocation, no synchronisation.  A stream created at a framing
+// (rced_stream_create_fr) runs the general kernels instead, four launches per push (kernels_stream_fr.h, planned by stream_fr_plan.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -10,6 +11,9 @@
 
 #include "../../include/rced.h"
 #include "rced_internal.h"
+#include "stream_fr_plan.h"
+
+namespace sfp = ::rced::stream_fr;   // (named before the unnamed namespace below gets an rced of its own)
 
 // kernels_audio.h / kernels_audio_x6.h define their kernels with external linkage and audio_api.hip is their translation unit: this
 // one takes the headers into an unnamed namespace, so that its copies (it launches only its own three kernels) are local to it.
@@ -17,8 +21,10 @@
 namespace {
 #include "kernels_stream.h"
 #include "kernels_stream_ola.h"
+#include "kernels_stream_fr.h"
 namespace audio = rced::audio;
 namespace as = rced::audio::stream;
+namespace af = rced::audio::stream::fr;
 }  // namespace
 
 struct rced_stream {
@@ -30,6 +36,12 @@ struct rced_stream {
   float* masks = nullptr;        // [S, 7 + K, 129]: the CNN's output
   hipStream_t last = nullptr;    // the stream of the latest push / finish: rced_stream_reset is ordered on it
   rced_audio_x6_tables tab;
+  // a stream at a framing (rced_stream_create_fr): the general kernels, their state layout, their packs (pinned in audio_api.hip's cache)
+  bool fr = false, pinned = false;
+  int window = 0, stride = 0, window_name = 0;
+  float* frames = nullptr;       // [S, window_hops, 256]: the frames between the two steps of the rebuild
+  rced_fr_tables ft;
+  int state_floats = 0;          // per lane
 };
 
 namespace {
@@ -37,15 +49,40 @@ namespace {
 std::mutex g_mu;
 std::vector<rced_stream*> g_streams;   // the live ones: rced_destroy of a model detaches its streams
 
-int window_hops(const rced_stream* s) { return std::max(s->max_hops, as::kFinishSlots); }
+int finish_slots(const rced_stream* s) { return s->fr ? sfp::finish_slots(s->window, s->stride) : as::kFinishSlots; }
+int window_hops(const rced_stream* s) { return std::max(s->max_hops, finish_slots(s)); }
 
 void release(rced_stream* s) {
-  for (void* p : {(void*)s->state, (void*)s->win, (void*)s->phw, (void*)s->masks}) (void)hipFree(p);
+  for (void* p : {(void*)s->state, (void*)s->win, (void*)s->phw, (void*)s->masks, (void*)s->frames}) (void)hipFree(p);
+  if (s->pinned) rced_fr_tables_unpin(s->device, s->window, s->window_name, s->rebuild == RCED_STREAM_REBUILD_OLA, s->nfft);
   delete s;
+}
+
+// the four launches of a stream at a framing; K slots per lane (push: K hops, finish: R + 4)
+int run_fr(rced_stream* s, const float* in, const int* flags, int finish, int K, float* out, int* out_counts, hipStream_t st) {
+  const int S = s->lanes, W = s->window, hop = s->stride;
+  const dim3 grid((S * K + audio::kFramesPerWg - 1) / audio::kFramesPerWg, 2), block(audio::x6::kThreadsX);
+  hipLaunchKernelGGL(af::stream_fr_stft_kernel, grid, block, af::kStftLds, st, in, flags, finish, s->ft.stft, (const float*)s->state, S, K, W, hop,
+                     s->win, s->phw);
+  HIP_TRY(hipGetLastError());
+  if (int rc = rced_forward(s->model, s->win, s->masks, S, as::kKeep + K, st)) return rc;
+  hipLaunchKernelGGL(af::stream_fr_frames_kernel, grid, block, af::kFramesLds, st, (const float*)s->masks, (const float*)s->phw, flags, finish,
+                     s->ft.rebuild, s->ft.cim, (const float*)s->state, S, K, window_hops(s), W, hop, s->frames);
+  HIP_TRY(hipGetLastError());
+  if (s->rebuild == RCED_STREAM_REBUILD_OLA)
+    hipLaunchKernelGGL(af::stream_fr_rebuild_kernel<true>, dim3(S), block, 0, st, (const float*)s->frames, s->ft.w2, in, flags, finish,
+                       (const float*)s->win, (const float*)s->phw, s->state, K, window_hops(s), W, hop, out, out_counts);
+  else
+    hipLaunchKernelGGL(af::stream_fr_rebuild_kernel<false>, dim3(S), block, 0, st, (const float*)s->frames, s->ft.w2, in, flags, finish,
+                       (const float*)s->win, (const float*)s->phw, s->state, K, window_hops(s), W, hop, out, out_counts);
+  HIP_TRY(hipGetLastError());
+  s->last = st;
+  return RCED_OK;
 }
 
 // the three launches; K slots per lane (push: K hops, finish: kFinishSlots)
 int run(rced_stream* s, const float* in, const int* flags, int finish, int K, float* out, int* out_counts, hipStream_t st) {
+  if (s->fr) return run_fr(s, in, flags, finish, K, out, out_counts, st);
   const int S = s->lanes;
   hipLaunchKernelGGL(as::stream_stft_kernel, dim3((S * K + audio::kFramesPerWg - 1) / audio::kFramesPerWg, 2), dim3(audio::x6::kThreadsX),
                      as::kStreamStftLds, st, in, flags, finish, s->tab.stft, (const float*)s->state, S, K, s->win, s->phw);
@@ -72,23 +109,8 @@ int usable(rced_stream* s) {
   return RCED_OK;
 }
 
-}  // namespace
-
-void rced_streams_detach(rced_model* m) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  for (rced_stream* s : g_streams)
-    if (s->model == m) s->model = nullptr;
-}
-
-extern "C" {
-
-int rced_stream_delay(void) { return RCED_STREAM_DELAY; }
-
-int rced_stream_create(rced_model* m, int lanes, int max_hops, int nfft, rced_stream** out) {
-  return rced_stream_create_ex(m, lanes, max_hops, nfft, RCED_STREAM_REBUILD_REFERENCE, out);
-}
-
-int rced_stream_create_ex(rced_model* m, int lanes, int max_hops, int nfft, int rebuild, rced_stream** out) {
+// what every create entry ends in; fr: at a framing (checked by the caller), the general kernels
+int create(rced_model* m, int lanes, int max_hops, int nfft, int rebuild, bool fr, int window, int stride, int window_name, rced_stream** out) {
   static_assert(RCED_STREAM_DELAY == as::kDelayHops * audio::kStep && RCED_STREAM_FINISH_MAX == as::kFinishOut, "rced.h and kernels_stream.h");
   if (!out) return rced_fail(RCED_ERR_ARG, "out is NULL");
   *out = nullptr;
@@ -108,19 +130,32 @@ int rced_stream_create_ex(rced_model* m, int lanes, int max_hops, int nfft, int 
   s->max_hops = max_hops;
   s->nfft = nfft;
   s->rebuild = rebuild;
-  int rc = rced_audio_x6_tables_get(m->device, nfft, &s->tab);
+  s->fr = fr;
+  s->window = window;
+  s->stride = stride;
+  s->window_name = window_name;
+  s->state_floats = fr ? sfp::kStFloats : as::kStFloats;
+  int rc = fr ? rced_fr_tables_pin(m->device, window, window_name, rebuild == RCED_STREAM_REBUILD_OLA, nfft, &s->ft)
+              : rced_audio_x6_tables_get(m->device, nfft, &s->tab);
+  s->pinned = fr && !rc;
   const size_t rows = (size_t)lanes * (as::kKeep + window_hops(s)) * audio::kBins;
   auto alloc = [&](float** p, size_t floats) {
     if (rc) return;
     const hipError_t e = hipMalloc(p, floats * sizeof(float));
     if (e != hipSuccess) rc = rced_fail(e == hipErrorOutOfMemory ? RCED_ERR_ALLOC : RCED_ERR_HIP, "hipMalloc(stream): %s", hipGetErrorString(e));
   };
-  alloc(&s->state, (size_t)lanes * as::kStFloats);
+  alloc(&s->state, (size_t)lanes * s->state_floats);
   alloc(&s->win, rows);
   alloc(&s->phw, 2 * rows);
   alloc(&s->masks, rows);
-  if (!rc && hipMemset(s->state, 0, (size_t)lanes * as::kStFloats * sizeof(float)) != hipSuccess) rc = rced_fail(RCED_ERR_HIP, "hipMemset(stream state)");
-  if (!rc) {
+  if (fr) alloc(&s->frames, (size_t)lanes * window_hops(s) * audio::kFrame);
+  if (!rc && hipMemset(s->state, 0, (size_t)lanes * s->state_floats * sizeof(float)) != hipSuccess) rc = rced_fail(RCED_ERR_HIP, "hipMemset(stream state)");
+  if (!rc && fr) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(af::stream_fr_stft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, af::kStftLds);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(af::stream_fr_frames_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, af::kFramesLds);
+    if (e != hipSuccess) rc = rced_fail(RCED_ERR_HIP, "hipFuncSetAttribute(stream LDS): %s", hipGetErrorString(e));
+  } else if (!rc) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(as::stream_stft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, as::kStreamStftLds);
     if (e == hipSuccess)
       e = hipFuncSetAttribute(reinterpret_cast<const void*>(as::stream_istft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, as::kStreamIstftLds);
@@ -139,6 +174,52 @@ int rced_stream_create_ex(rced_model* m, int lanes, int max_hops, int nfft, int 
   }
   *out = s;
   return RCED_OK;
+}
+
+}  // namespace
+
+void rced_streams_detach(rced_model* m) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  for (rced_stream* s : g_streams)
+    if (s->model == m) s->model = nullptr;
+}
+
+extern "C" {
+
+int rced_stream_delay(void) { return RCED_STREAM_DELAY; }
+
+int rced_stream_create(rced_model* m, int lanes, int max_hops, int nfft, rced_stream** out) {
+  return rced_stream_create_ex(m, lanes, max_hops, nfft, RCED_STREAM_REBUILD_REFERENCE, out);
+}
+
+int rced_stream_create_ex(rced_model* m, int lanes, int max_hops, int nfft, int rebuild, rced_stream** out) {
+  return create(m, lanes, max_hops, nfft, rebuild, false, 0, 0, 0, out);
+}
+
+int rced_stream_fr_check(int window, int stride, int window_name, int rebuild) {
+  char err[512];
+  if (sfp::check(window, stride, window_name, rebuild, err, sizeof err)) return rced_fail(RCED_ERR_ARG, "%s", err);
+  return RCED_OK;
+}
+
+int rced_stream_delay_fr(int window, int stride) {
+  char err[512];
+  if (sfp::check(window, stride, RCED_WINDOW_HAMMING, RCED_STREAM_REBUILD_OLA, err, sizeof err)) return -1;
+  return sfp::delay(window, stride);
+}
+
+int rced_stream_finish_max_fr(int window, int stride) {
+  char err[512];
+  if (sfp::check(window, stride, RCED_WINDOW_HAMMING, RCED_STREAM_REBUILD_OLA, err, sizeof err)) return -1;
+  return sfp::finish_max(window, stride);
+}
+
+int rced_stream_create_fr(rced_model* m, int lanes, int max_hops, int nfft, int rebuild, int window, int stride, int window_name,
+                          rced_stream** out) {
+  if (!out) return rced_fail(RCED_ERR_ARG, "out is NULL");
+  *out = nullptr;
+  if (int rc = rced_stream_fr_check(window, stride, window_name, rebuild)) return rc;
+  return create(m, lanes, max_hops, nfft, rebuild, true, window, stride, window_name, out);
 }
 
 void rced_stream_destroy(rced_stream* s) {
@@ -168,7 +249,7 @@ int rced_stream_finish(rced_stream* s, const float* tail_dev, const int* tail_co
   if (int rc = usable(s)) return rc;
   DeviceGuard g(s->device);
   if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", s->device);
-  return run(s, tail_dev, tail_counts_dev, 1, as::kFinishSlots, out_dev, out_counts_dev, static_cast<hipStream_t>(stream));
+  return run(s, tail_dev, tail_counts_dev, 1, finish_slots(s), out_dev, out_counts_dev, static_cast<hipStream_t>(stream));
 }
 
 int rced_stream_reset(rced_stream* s, int lane) {
@@ -176,9 +257,9 @@ int rced_stream_reset(rced_stream* s, int lane) {
   if (lane < -1 || lane >= s->lanes) return rced_fail(RCED_ERR_ARG, "lane must be -1 (all) or 0..%d, got %d", s->lanes - 1, lane);
   DeviceGuard g(s->device);
   if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", s->device);
-  const size_t one = as::kStFloats * sizeof(float);
+  const size_t one = s->state_floats * sizeof(float);
   if (lane < 0) HIP_TRY(hipMemsetAsync(s->state, 0, one * s->lanes, s->last));
-  else HIP_TRY(hipMemsetAsync(s->state + (size_t)lane * as::kStFloats, 0, one, s->last));
+  else HIP_TRY(hipMemsetAsync(s->state + (size_t)lane * s->state_floats, 0, one, s->last));
   return RCED_OK;
 }
 

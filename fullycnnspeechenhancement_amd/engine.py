@@ -255,7 +255,7 @@ class InferenceEngine(FullyCNNTester):
                 w.close()
         return out
 
-    def denoise_stream(self, chunks, hops=8, nfft=512, sample_rate=8000, output_rate=None, rebuild="reference", block=None):
+    def denoise_stream(self, chunks, hops=8, nfft=512, sample_rate=8000, output_rate=None, rebuild="reference", block=None, framing=None):
         """denoise_pcm for audio that arrives in pieces: a generator over an iterable of 1-D PCM pieces of any size.  The
         pieces are re-blocked to whole hops (128 samples) and pushed, at most `hops` hops at a time, through a one-lane
         audio.StreamingDenoiser; every push's output is yielded as it comes (numpy float32, the result delayed by 640
@@ -267,11 +267,15 @@ class InferenceEngine(FullyCNNTester):
         block: None, or a number of frames: the pieces are cut to blocks of that size and go through a one-lane
         audio.BlockDenoiser(block=..., sample_rate=..., output_rate=...), which serves every rate (44.1 kHz too) and yields block *
         output_rate / sample_rate samples a block, the result delayed by audio.block_delay(block, sample_rate, output_rate);
-        `hops` plays no part."""
+        `hops` plays no part.
+        framing: an audio.Framing (None: the default): the pieces are re-blocked to hops of its stride, through
+        StreamingDenoiser(framing=...); the result is denoise_pcm(..., framing=framing) delayed by audio.stream_delay_fr(framing).
+        8 kHz only, and without `block`: anything else with a framing is a ValueError."""
         from . import audio
         check_rebuild(rebuild)
         if block is not None:
-            lane = audio.BlockDenoiser(self.model, 1, int(block), sample_rate=sample_rate, output_rate=output_rate, nfft=nfft, rebuild=rebuild)
+            lane = audio.BlockDenoiser(self.model, 1, int(block), sample_rate=sample_rate, output_rate=output_rate, nfft=nfft, rebuild=rebuild,
+                                       framing=framing)
             try:
                 held = np.zeros(0, np.float32)
                 for piece in chunks:
@@ -284,7 +288,7 @@ class InferenceEngine(FullyCNNTester):
                 lane.close()
             return
         stream = audio.StreamingDenoiser(self.model, 1, max_hops=int(hops), nfft=nfft, sample_rate=sample_rate, output_rate=output_rate,
-                                         rebuild=rebuild)
+                                         rebuild=rebuild, framing=framing)
         hop = stream.hop_in
         try:
             held = np.zeros(0, np.float32)

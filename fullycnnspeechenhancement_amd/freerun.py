@@ -295,13 +295,17 @@ class BlockDenoiser(object):
     lane's output is what StreamingDenoiser's chain gives -- resample_batch to 8 kHz, the denoiser, resample_batch up -- delayed by
     `.delay` = block_delay(block, sample_rate, output_rate) samples.  44.1 kHz is served like any other rate.
 
-    model_or_engine, nfft, rebuild, channels, dtype: as in StreamingDenoiser.  A lane starts its utterance with a process() call
+    model_or_engine, nfft, rebuild, channels, dtype: as in StreamingDenoiser.  framing: None or Framing() only -- the blocks run
+    at 256 / 128 / hamming, and another audio.Framing is a ValueError that says so (StreamingDenoiser(framing=...) serves the
+    8 kHz signal at a framing).  A lane starts its utterance with a process() call
     and ends it with finish(); the host keeps every lane's frame count, from which all the bookkeeping follows."""
 
     def __init__(self, model_or_engine, lanes, block, sample_rate=8000, output_rate=None, channels=1, dtype="float32", nfft=512,
-                 rebuild="reference"):
+                 rebuild="reference", framing=None):
+        from .streaming import stream_framing
         self._down = self._denoiser = self._up = None
         self.rebuild = _args.check_rebuild(rebuild)
+        stream_framing(framing, self.rebuild, block=(int(block), None))      # None or Framing() only: a framing has no block form yet
         self.model = getattr(model_or_engine, "model", model_or_engine)
         if getattr(self.model, "_handle", None) is None:
             raise ValueError("BlockDenoiser needs an inference model (Model(is_training=False)) or an engine that holds one")

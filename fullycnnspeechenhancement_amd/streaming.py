@@ -160,16 +160,51 @@ class StreamingResampler(_Lanes):
 
 class _DenoiserLanes(_Lanes):
     """The 8 kHz lanes of the denoiser (rced_stream_*): hops of 128 mono float32 samples in and out, a push is
-    three launches on the current stream.  The library refuses a push once the model's handle is gone."""
+    three launches on the current stream; at a framing hops of its stride and four launches.  The library
+    refuses a push once the model's handle is gone."""
 
     _family = "rced_stream"
 
-    def __init__(self, model, lanes, max_hops, nfft, rebuild="reference"):
+    def __init__(self, model, lanes, max_hops, nfft, rebuild="reference", framing=None):
+        """framing: None (the specialised kernels), or a Framing stream_framing has let through: hops of its stride, four launches
+        a push (rced_stream_create_fr)."""
         import ctypes
         h = ctypes.c_void_p()
-        _lib.check(_lib.load().rced_stream_create_ex(model._handle, int(lanes), int(max_hops), int(nfft), _args.REBUILDS.index(rebuild),
-                                                     ctypes.byref(h)))      # RCED_STREAM_REBUILD_REFERENCE = 0, _OLA = 1
-        self._open(h, lanes, model.device, STEP, STEP, 1, "float32", "float32", STREAM_FINISH_MAX)
+        lib, code = _lib.load(), _args.REBUILDS.index(rebuild)              # RCED_STREAM_REBUILD_REFERENCE = 0, _OLA = 1
+        if framing is None:
+            _lib.check(lib.rced_stream_create_ex(model._handle, int(lanes), int(max_hops), int(nfft), code, ctypes.byref(h)))
+            self._open(h, lanes, model.device, STEP, STEP, 1, "float32", "float32", STREAM_FINISH_MAX)
+            return
+        _lib.check(lib.rced_stream_create_fr(model._handle, int(lanes), int(max_hops), int(nfft), code, framing.window, framing.stride,
+                                             framing.code, ctypes.byref(h)))
+        self._open(h, lanes, model.device, framing.stride, framing.stride, 1, "float32", "float32",
+                   int(lib.rced_stream_finish_max_fr(framing.window, framing.stride)))
+
+
+def stream_framing(framing, rebuild="ola", **others):
+    """The framing of a stream: None for None or Framing() (today's lanes, today's bits), else the Framing -- after the library's
+    refusals (rced_stream_fr_check: the reference rebuild with a window that ends in zero, more than 8 frames of overlap) as
+    ValueErrors with its message, before any device work.  others: arguments of the caller that a framing does not combine with
+    yet, as name = (value, default): a ValueError that names the combination."""
+    from . import audio
+    fr = audio._general(framing)
+    if fr is None:
+        return None
+    for name, (value, default) in sorted(others.items()):
+        if value != default:
+            raise ValueError("framing=%r together with %s=%r: the rate-aware chain and the block denoiser run at 256 / 128 / hamming "
+                             "only (their down lanes would have to run whole hops of the framing late); stream the 8 kHz mono "
+                             "float32 signal, or use InferenceEngine.denoise_pcm(framing=...)" % (fr, name, value))
+    audio._refused(_lib.load().rced_stream_fr_check(fr.window, fr.stride, fr.code, _args.REBUILDS.index(rebuild)))
+    return fr
+
+
+def stream_delay_fr(framing=None):
+    """StreamingDenoiser(..., framing=framing).delay in samples at 8 kHz (needs no GPU): (ceil(W / S) + 3) * S -- a frame is
+    complete ceil(W / S) - 1 hops after the one it starts in, its mask needs 4 more frames, and the hop that leaves needs the
+    frames back to the one that started ceil(W / S) - 1 hops before it.  640 at 256 / 128; 400 at 160 / 80."""
+    fr = stream_framing(framing)
+    return STREAM_DELAY if fr is None else int(_lib.load().rced_stream_delay_fr(fr.window, fr.stride))
 
 
 def stream_delay(sample_rate=8000, output_rate=None, channels=1, dtype="float32"):
@@ -222,15 +257,23 @@ class StreamingDenoiser(object):
     with output_rate, normally sample_rate -- resampler lanes up again, without synchronisation; the output is float32 mono,
     InferenceEngine.denoise_pcm(x, sample_rate=...) (resampled to output_rate) delayed by `.delay` = stream_delay(...)
     samples.  A rate at which the hop is not a whole number of frames (44.1 kHz: 128 * 441 / 80) is a ValueError naming the
-    rate: denoise_pcm serves those rates offline."""
+    rate: denoise_pcm serves those rates offline.
+
+    framing: None or Framing() -- all of the above --, or another audio.Framing: the hop (`.hop`) is its stride S,
+    push and finish take and give units of S samples, and a lane's output is denoise_pcm(..., rebuild=rebuild, framing=framing)
+    delayed by `.delay` = stream_delay_fr(framing) = (ceil(W / S) + 3) * S samples; a push is four launches.  8 kHz mono float32
+    only: with sample_rate, channels, dtype or output_rate it is a ValueError, and so is what the library refuses (the reference
+    rebuild with a window that ends in zero, more than 8 frames of overlap)."""
 
     def __init__(self, model_or_engine, lanes, max_hops=8, nfft=512, sample_rate=8000, channels=1, dtype="float32", output_rate=None,
-                 rebuild="reference"):
+                 rebuild="reference", framing=None):
         self._down = self._denoiser = self._up = None
         self.rebuild = _args.check_rebuild(rebuild)
         self.model = getattr(model_or_engine, "model", model_or_engine)
         if getattr(self.model, "_handle", None) is None:
             raise ValueError("StreamingDenoiser needs an inference model (Model(is_training=False)) or an engine that holds one")
+        self.framing = stream_framing(framing, self.rebuild, sample_rate=(int(sample_rate), SAMPLE_RATE), channels=(int(channels), 1),
+                                      dtype=(dtype, "float32"), output_rate=(output_rate, None))
         self.lanes, self.max_hops, self.nfft, self.device = int(lanes), int(max_hops), int(nfft), self.model.device
         self.sample_rate, self.channels, self.dtype = int(sample_rate), int(channels), dtype
         self.output_rate = int(output_rate) if output_rate is not None else None
@@ -238,10 +281,11 @@ class StreamingDenoiser(object):
             if rate is not None and (rate < 1 or STEP * rate % SAMPLE_RATE):
                 raise ValueError("a hop of %d samples at 8 kHz is not a whole number of frames at %r Hz: streaming serves rates that are a "
                                  "multiple of 62.5 Hz, InferenceEngine.denoise_pcm(sample_rate=...) every rate" % (STEP, rate))
-        self._denoiser = _DenoiserLanes(self.model, self.lanes, self.max_hops, self.nfft, self.rebuild)
+        self._denoiser = _DenoiserLanes(self.model, self.lanes, self.max_hops, self.nfft, self.rebuild, self.framing)
         self._push8 = self._denoiser.push        # the one name every 8 kHz push goes through, finish's drain included
-        self.hop_in = STEP * self.sample_rate // SAMPLE_RATE
-        self.delay = stream_delay(self.sample_rate, self.output_rate, self.channels, dtype)
+        self.hop = STEP if self.framing is None else self.framing.stride
+        self.hop_in = self.hop * self.sample_rate // SAMPLE_RATE
+        self.delay = stream_delay(self.sample_rate, self.output_rate, self.channels, dtype) if self.framing is None else stream_delay_fr(self.framing)
         if self.sample_rate != SAMPLE_RATE or self.channels != 1 or dtype != "float32":
             self._down = StreamingResampler(self.sample_rate, SAMPLE_RATE, self.lanes, unit_out=STEP, channels=self.channels, dtype=dtype,
                                             max_units=self.max_hops, device=self.device, delay=STEP)
@@ -262,7 +306,7 @@ class StreamingDenoiser(object):
         active: None, or `lanes` flags; a lane flagged 0 is idle (state untouched, zeros out).  A CUDA tensor gives a CUDA
         tensor (no synchronisation), an ndarray an ndarray.
         At the device's rate: pcm [lanes, K * hop_in (* channels)] of `dtype` -> [lanes, K*128] at 8 kHz, or with output_rate
-        [lanes, K * 128 * output_rate / 8000], float32.
+        [lanes, K * 128 * output_rate / 8000], float32.  At a framing: [lanes, K * hop] in and out, hop = the framing's stride.
 
         down lanes -> the three launches of the 8 kHz push -> up lanes, nothing waits.  The down lanes run a whole hop behind
         (delay 128), so what they hand on is whole hops of the 8 kHz signal -- except the first hop of a lane's first push, which
@@ -292,6 +336,7 @@ class StreamingDenoiser(object):
         """Ends the utterance of every lane listed: tails[i] holds the last 0..127 samples of lane lanes[i].  Returns a list of
         float32 arrays, the samples each lane still owed (L - max(0, 128 H - 640) of them); the lanes are reset for a new
         utterance, the others left alone.  Synchronises (the counts come back).
+        At a framing: the last 0 .. hop - 1 samples; L - max(0, hop * H - delay) samples are owed.
         At the device's rate: tails[i] holds fewer than hop_in frames; the stages are drained in order -- what the down lanes
         owe goes hop by hop through the denoiser and its finish, all of that through the up lanes and their finish."""
         lanes = _args.host_ints(lanes)

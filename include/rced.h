@@ -405,6 +405,31 @@ int rced_stream_finish(rced_stream* s, const float* tail_dev, const int* tail_co
 /* Back to the start of an utterance without output: lane, or -1 for every lane.  Ordered on the stream of the latest push / finish. */
 int rced_stream_reset(rced_stream* s, int lane);
 
+/* ---- streaming at a framing: a stream created for a window W, a stride S and a window name (the "any framing"
+ * section above).  The hop is S samples, R = ceil(W / S), and `off` is the offline chain at that framing cut to L samples:
+ * rced_stft_fr -> rced_forward -> rced_istft_ola_fr (RCED_STREAM_REBUILD_OLA) or rced_istft_fr (RCED_STREAM_REBUILD_REFERENCE) over
+ * the utterance's T = rced_stft_num_frames_fr(L, W, S) frames.  The lane's output is `off` delayed by D = (R + 3) * S samples: frame t
+ * covers samples tS .. tS + W - 1 and is complete with hop t + R - 1, its mask needs 4 future frames, and hop h is rebuilt from frames
+ * h - R + 1 .. h.  Everything the section above says about frame sets holds with W, S and T: the tail is zero-filled after
+ * pre-emphasis, a frame at or past T is neither input nor rebuilt, a frame below T counts in numerator and denominator, denominators
+ * count the frames that exist, a sample whose sum of w^2 is at most 1e-10 is 0, de-emphasis is carried across pushes.
+ * rced_stream_push, _finish, _reset and _destroy serve such a stream with their signatures unchanged: K*S floats per lane in and out,
+ * tail counts 0 .. S - 1 with tail_dev [lanes, S], out_dev of a finish [lanes, rced_stream_finish_max_fr(W, S)], of which the first
+ * L - max(0, S*H - D) are owed.  A push is four launches (the rebuild is two), allocates nothing and does not synchronise.  Such a
+ * stream always runs the general kernels, at 256 / 128 / hamming too (delay 640, as RCED_STREAM_DELAY). ---- */
+
+/* RCED_OK, or RCED_ERR_ARG with the reason: what rced_framing_check refuses; rebuild other than the two above; the reference rebuild
+ * with a window rced_istft_fr_check refuses; ceil(W / S) > 8 (state and delay grow with the overlap).  Touches no device. */
+int rced_stream_fr_check(int window, int stride, int window_name, int rebuild);
+/* D = (ceil(W / S) + 3) * S samples; -1 for a framing rced_stream_fr_check refuses.  Host only. */
+int rced_stream_delay_fr(int window, int stride);
+/* Floats per lane of rced_stream_finish's out_dev on such a stream: (ceil(W / S) + 4) * S = D + S; -1 as above.  Host only. */
+int rced_stream_finish_max_fr(int window, int stride);
+/* rced_stream_create_ex at a framing.  lanes, max_hops (1..64) and nfft are checked as there (nfft plays no part in overlap-add);
+ * what rced_stream_fr_check refuses is RCED_ERR_ARG. */
+int rced_stream_create_fr(rced_model* m, int lanes, int max_hops, int nfft, int rebuild, int window, int stride, int window_name,
+                          rced_stream** out);
+
 /* ---- streaming resampler: the conversion of the "resample" section for audio that arrives piece by piece, for many independent
  * streams ("lanes") at once, at a fixed delay.  A lane stream is created for a unit pair: every push of K units
  * hands each active lane K * unit_in source frames and returns K * unit_out samples; unit_in * p must equal unit_out * q (p / q =

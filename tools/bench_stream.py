@@ -7,7 +7,10 @@ A push recomputes 7 frames per lane for the CNN: `recompute` is
 rounds, and reports each one's median round and their ratio; --rebuild reference / ola times one of them.
 The last line times audio.BlockDenoiser (--blocks: that line alone): ms per process() for 256 lanes at 48 kHz in blocks of 480
 and of 768 frames and at 44.1 kHz in blocks of 441, beside StreamingDenoiser(48000, 48000)'s push of one hop (768 frames), all four in
-alternating rounds of the same run; one JSON line."""
+alternating rounds of the same run; one JSON line.
+After it (--framing: that line alone) the lanes at a framing, overlap-add, 256 lanes at K = 1, 8 and 32 hops per push:
+the general stream (rced_stream_create_fr) at 256 / 128 / hamming beside the specialised one, and at 160 / 80 / hamming and 256 / 64 /
+hanning, all four in alternating rounds of the same run; ms per push, and per framing the audio a push carries; one JSON line."""
 import argparse, json, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -19,6 +22,7 @@ parser = argparse.ArgumentParser(description=__doc__)
 parser.add_argument("--rebuild", choices=("both", "reference", "ola"), default="both",
                     help="the streams' rebuild; both (default): one stream of each, timed in alternating rounds of the same run")
 parser.add_argument("--rounds", type=int, default=5, help="timed rounds per stream; the median is reported")
+parser.add_argument("--framing", action="store_true", help="time the lanes at a framing beside the specialised stream, that line alone")
 parser.add_argument("--blocks", action="store_true", help="time BlockDenoiser.process at 48 and 44.1 kHz beside the one-hop push at 48 kHz")
 args = parser.parse_args()
 REBUILDS = ("reference", "ola") if args.rebuild == "both" else (args.rebuild,)
@@ -71,8 +75,35 @@ def block_rows():
         o.close()
 
 
+def framing_rows():
+    from fullycnnspeechenhancement_amd.streaming import _DenoiserLanes
+    cases = {"general_256_128_hamming": audio.Framing(256, 128, "hamming"), "general_160_80_hamming": audio.Framing(160, 80, "hamming"),
+             "general_256_64_hanning": audio.Framing(256, 64, "hanning")}
+    row = {"lanes": LANES, "rounds": args.rounds, "rebuild": "ola"}
+    for k in (1, 8, 32):
+        # _DenoiserLanes with a Framing always makes the general stream, at the default framing too (StreamingDenoiser would not)
+        objs = {"specialised_256_128_hamming": audio.StreamingDenoiser(model, LANES, max_hops=k, rebuild="ola")}
+        objs.update({name: _DenoiserLanes(model, LANES, k, 512, "ola", fr) for name, fr in cases.items()})
+        hop = {name: cases[name].stride if name in cases else 128 for name in objs}
+        pcm = {name: torch.randn((LANES, k * hop[name]), device="cuda") * 0.1 for name in objs}
+        reps = 2000 // k + 50
+        rounds = {name: [] for name in objs}
+        for _ in range(args.rounds):
+            for name in objs:
+                rounds[name].append(timed(lambda name=name: objs[name].push(pcm[name]), reps))
+        for o in objs.values():
+            o.close()
+        ms = {name: statistics.median(v) for name, v in rounds.items()}
+        row["hops_%d" % k] = {name: {"push_ms": ms[name], "push_ms_rounds": [round(v, 5) for v in rounds[name]], "audio_ms_per_push": k * hop[name] / 8.0,
+                                     "over_specialised": ms[name] / ms["specialised_256_128_hamming"]} for name in objs}
+    print(json.dumps(row), flush=True)
+
+
 if args.blocks:
     block_rows()
+    sys.exit(0)
+if args.framing:
+    framing_rows()
     sys.exit(0)
 
 for k in (1, 8, 32):
@@ -99,3 +130,4 @@ for k in (1, 8, 32):
 ms = timed(offline(256, 512), 20)
 print(json.dumps({"offline_utterances": 256, "offline_frames_each": 512, "offline_ms": ms, "offline_frames_per_s": 256 * 512 / (ms * 1e-3)}))
 block_rows()
+framing_rows()
