@@ -8,6 +8,7 @@
 
 #include "../../include/rced.h"
 #include "kernels_eval.h"
+#include "kernels_sepm.h"
 #include "kernels_stoi.h"
 #include "rced_internal.h"
 
@@ -22,8 +23,8 @@ struct Workspace {
   double* p = nullptr;
   size_t bytes = 0;
 };
-// STOI, SI-SDR and the segmental SNR keep buffers of their own: none ever moves the one another entry's captured graph reads
-enum { kWsSlices = 0, kWsStoi = 1, kWsSiSdr = 2, kWsSegSnr = 3, kWsKinds = 4 };
+// STOI, SI-SDR, the segmental SNR, LLR and WSS keep buffers of their own: none ever moves the one another entry's captured graph reads
+enum { kWsSlices = 0, kWsStoi = 1, kWsSiSdr = 2, kWsSegSnr = 3, kWsLlr = 4, kWsWss = 5, kWsKinds = 6 };
 std::map<void*, Workspace> g_ws[kWsKinds][kMaxDevices];
 std::mutex g_mu;
 
@@ -121,6 +122,108 @@ int stoi_tables(int device, StoiTables** out) {
 }
 
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// ---- WSS tables: built on the host in fp64 once per process and rate, uploaded once per device -----------------------------------
+struct WssTables {
+  double* coef = nullptr;            // the DFT's cos / -sin columns in MFMA fragment order (sepm::wss_coef_len)
+  double* filt = nullptr;            // [25][kBins] critical-band filters
+  int* range = nullptr;              // [25][2]: a filter's nonzero bins [lo, hi)
+};
+WssTables g_wss[kMaxDevices][2];     // [device][fs == 16000]
+std::mutex g_wss_mu;
+
+const double kWssCentre[sepm::kBands] = {50.0,    120.0,   190.0,   260.0,   330.0,   400.0,   470.0,   540.0,   617.372,
+                                         703.378, 798.717, 904.128, 1020.38, 1148.30, 1288.72, 1442.54, 1610.70, 1794.16,
+                                         1993.93, 2211.08, 2446.71, 2701.97, 2978.04, 3276.17, 3597.63};
+const double kWssWidth[sepm::kBands] = {70.0,    70.0,    70.0,    70.0,    70.0,    70.0,    70.0,    77.3724, 86.0056,
+                                        95.3398, 105.411, 116.256, 127.914, 140.423, 153.823, 168.154, 183.457, 199.776,
+                                        217.153, 235.631, 255.255, 276.072, 298.126, 321.465, 346.136};
+
+int wss_tables(int device, int fs, WssTables** out) {
+  std::lock_guard<std::mutex> lk(g_wss_mu);
+  WssTables& t = g_wss[device][fs == 16000];
+  if (!t.coef) {
+    const int W = eval::seg_window(fs), S = W / 4;
+    int nfft = 1;
+    while (nfft < 2 * W) nfft *= 2;
+    const int nb = nfft / 2;
+    const double fmax = fs / 2.0;
+    // wave w, step s, tile q, part (cos, -sin), lane: B[k = 4 s + (lane >> 4)][bin = 16 (4 w + q) + (lane & 15)]
+    std::vector<double> coef(sepm::wss_coef_len(W));
+    size_t at = 0;
+    for (int w = 0; w < sepm::kWaves; ++w)
+      for (int s = 0; s < S; ++s)
+        for (int q = 0; q < sepm::kBinTilesPerWave; ++q)
+          for (int part = 0; part < 2; ++part)
+            for (int lane = 0; lane < 64; ++lane) {
+              const int k = 4 * s + (lane >> 4), bin = 16 * (sepm::kBinTilesPerWave * w + q) + (lane & 15);
+              const double th = 2.0 * M_PI * (double)(((long long)bin * k) % nfft) / (double)nfft;
+              coef[at++] = bin < nb ? (part ? -std::sin(th) : std::cos(th)) : 0.0;
+            }
+    std::vector<double> filt((size_t)sepm::kBands * sepm::kBins, 0.0);
+    std::vector<int> range(2 * sepm::kBands, 0);
+    const double floor_g = std::exp(-30.0 / (2.0 * 2.303));
+    for (int i = 0; i < sepm::kBands; ++i) {
+      const double f0 = std::floor(kWssCentre[i] / fmax * nb), bw = kWssWidth[i] / fmax * nb;
+      int lo = nb, hi = 0;
+      for (int j = 0; j < nb; ++j) {
+        const double r = (j - f0) / bw, g = std::exp(-11.0 * (r * r) + std::log(kWssWidth[0]) - std::log(kWssWidth[i]));
+        if (!(g > floor_g)) continue;
+        if (j >= sepm::kPowLd || j >= sepm::kBins) return rced_fail(RCED_ERR_STATE, "WSS filter %d reaches bin %d", i, j);
+        filt[(size_t)i * sepm::kBins + j] = g;
+        lo = j < lo ? j : lo;
+        hi = j + 1;
+      }
+      range[2 * i] = lo < hi ? lo : 0;
+      range[2 * i + 1] = hi;
+    }
+    double *dc = nullptr, *df = nullptr;
+    int* dr = nullptr;
+    if (int rc = upload(&dc, coef, "WSS tables")) return rc;
+    if (int rc = upload(&df, filt, "WSS tables")) {
+      (void)hipFree(dc);
+      return rc;
+    }
+    if (int rc = upload(&dr, range, "WSS tables")) {
+      (void)hipFree(dc);
+      (void)hipFree(df);
+      return rc;
+    }
+    t.filt = df;
+    t.range = dr;
+    t.coef = dc;
+  }
+  *out = &t;
+  return RCED_OK;
+}
+
+// what rced_llr and rced_wss check alike; *nfcap = the frames of the longest utterance the strides allow, at least 1
+int sepm_args(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, int N, int fs, const double* out_dev,
+              const double* frames_out, int frames_stride, int* cap, int* nfcap) {
+  if (N < 0 || ref_stride < 0 || est_stride < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
+  if (!ref_dev || !est_dev || !out_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
+  if (fs != 8000 && fs != 16000) return rced_fail(RCED_ERR_ARG, "sample_rate must be 8000 or 16000, got %d", fs);
+  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
+  *cap = ref_stride < est_stride ? ref_stride : est_stride;
+  if (*cap > eval::kMaxLen) return rced_fail(RCED_ERR_ARG, "rows longer than 2^30 samples");
+  const int most = eval::seg_frames(*cap, eval::seg_window(fs));
+  if (frames_out && frames_stride < most)
+    return rced_fail(RCED_ERR_ARG, "frames_stride %d < %d, the frames of an utterance as long as the rows", frames_stride, most);
+  *nfcap = most > 0 ? most : 1;
+  return RCED_OK;
+}
+
+// rank every frame value inside its utterance, then the mean of the lowest 95 %
+int lowest_mean(const double* d, double* sorted, const int* lengths_dev, int N, int cap, int W, int nfcap, double* out_dev,
+                int* nf_out, hipStream_t st) {
+  hipLaunchKernelGGL(sepm::rank_kernel, dim3((nfcap + sepm::kThreads - 1) / sepm::kThreads, N), dim3(sepm::kThreads), 0, st, d,
+                     lengths_dev, cap, W, nfcap, sorted);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(sepm::lowest_mean_kernel, dim3(N), dim3(sepm::kThreads), 0, st, (const double*)sorted, lengths_dev, cap, W, nfcap,
+                     out_dev, nf_out);
+  HIP_TRY(hipGetLastError());
+  return RCED_OK;
+}
 
 }  // namespace
 
@@ -263,6 +366,76 @@ int rced_seg_snr(const float* ref_dev, int ref_stride, const float* est_dev, int
                      out_dev, frames_dev);
   HIP_TRY(hipGetLastError());
   return RCED_OK;
+}
+
+int rced_llr(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N, int sample_rate,
+             double limit, double* out_dev, double* frames_out, int frames_stride, int* nf_out, int device, void* stream) {
+  int cap = 0, nfcap = 0;
+  if (int rc = sepm_args(ref_dev, ref_stride, est_dev, est_stride, N, sample_rate, out_dev, frames_out, frames_stride, &cap, &nfcap))
+    return rc;
+  if (limit != limit) return rced_fail(RCED_ERR_ARG, "limit is nan");
+  if (N == 0) return RCED_OK;
+  if (int rc = check_device(device, kMaxDevices)) return rc;
+  DeviceGuard g(device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  const int W = eval::seg_window(sample_rate), P = sepm::lpc_order(sample_rate);
+  // workspace: R [N][nfcap][2][17] | d [N][nfcap] | sorted [N][nfcap]
+  const size_t o_d = align256((size_t)N * nfcap * 2 * sepm::kMaxLags * 8), o_s = o_d + align256((size_t)N * nfcap * 8),
+               total = o_s + align256((size_t)N * nfcap * 8);
+  double* ws = nullptr;
+  if (int rc = workspace(device, stream, total, &ws, kWsLlr)) return rc;
+  char* base = reinterpret_cast<char*>(ws);
+  double* d = reinterpret_cast<double*>(base + o_d);
+  double* sorted = reinterpret_cast<double*>(base + o_s);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(sepm::llr_frame_kernel, dim3((nfcap + sepm::kLlrFramesPerBlock - 1) / sepm::kLlrFramesPerBlock, N),
+                     dim3(sepm::kThreads), 0, st, ref_dev, ref_stride, est_dev, est_stride, lengths_dev, cap, W, P, ws, nfcap);
+  HIP_TRY(hipGetLastError());
+  const dim3 per_frame((nfcap + sepm::kThreads - 1) / sepm::kThreads, N);
+  if (P == 10)
+    hipLaunchKernelGGL(sepm::llr_recursion_kernel<10>, per_frame, dim3(sepm::kThreads), 0, st, (const double*)ws, lengths_dev, cap, W,
+                       nfcap, limit, d, frames_out, frames_stride);
+  else
+    hipLaunchKernelGGL(sepm::llr_recursion_kernel<16>, per_frame, dim3(sepm::kThreads), 0, st, (const double*)ws, lengths_dev, cap, W,
+                       nfcap, limit, d, frames_out, frames_stride);
+  HIP_TRY(hipGetLastError());
+  return lowest_mean(d, sorted, lengths_dev, N, cap, W, nfcap, out_dev, nf_out, st);
+}
+
+int rced_wss(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N, int sample_rate,
+             double* out_dev, double* frames_out, int frames_stride, int* nf_out, int device, void* stream) {
+  int cap = 0, nfcap = 0;
+  if (int rc = sepm_args(ref_dev, ref_stride, est_dev, est_stride, N, sample_rate, out_dev, frames_out, frames_stride, &cap, &nfcap))
+    return rc;
+  if (N == 0) return RCED_OK;
+  if (int rc = check_device(device, kMaxDevices)) return rc;
+  DeviceGuard g(device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  WssTables* t = nullptr;
+  if (int rc = wss_tables(device, sample_rate, &t)) return rc;
+  const int W = eval::seg_window(sample_rate);
+  // workspace: energy [N][2][nfcap][25] | d [N][nfcap] | sorted [N][nfcap]
+  const size_t o_d = align256((size_t)N * 2 * nfcap * sepm::kBands * 8), o_s = o_d + align256((size_t)N * nfcap * 8),
+               total = o_s + align256((size_t)N * nfcap * 8);
+  double* ws = nullptr;
+  if (int rc = workspace(device, stream, total, &ws, kWsWss)) return rc;
+  char* base = reinterpret_cast<char*>(ws);
+  double* d = reinterpret_cast<double*>(base + o_d);
+  double* sorted = reinterpret_cast<double*>(base + o_s);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (W == sepm::kMaxW)           // 16 kHz: 16 frames of 480 samples fill the LDS; 8 kHz: 32 frames of 240
+    hipLaunchKernelGGL(sepm::wss_spectrum_kernel<1>, dim3((nfcap + 15) / 16, 2, N), dim3(sepm::kThreads), sepm::wss_lds_bytes(W, 1), st,
+                       ref_dev, ref_stride, est_dev, est_stride, lengths_dev, cap, W, (const double*)t->coef, (const double*)t->filt,
+                       (const int*)t->range, ws, nfcap);
+  else
+    hipLaunchKernelGGL(sepm::wss_spectrum_kernel<2>, dim3((nfcap + 31) / 32, 2, N), dim3(sepm::kThreads), sepm::wss_lds_bytes(W, 2), st,
+                       ref_dev, ref_stride, est_dev, est_stride, lengths_dev, cap, W, (const double*)t->coef, (const double*)t->filt,
+                       (const int*)t->range, ws, nfcap);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(sepm::wss_slope_kernel, dim3((nfcap + sepm::kThreads - 1) / sepm::kThreads, N), dim3(sepm::kThreads), 0, st,
+                     (const double*)ws, lengths_dev, cap, W, nfcap, d, frames_out, frames_stride);
+  HIP_TRY(hipGetLastError());
+  return lowest_mean(d, sorted, lengths_dev, N, cap, W, nfcap, out_dev, nf_out, st);
 }
 
 int rced_sdr(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N,

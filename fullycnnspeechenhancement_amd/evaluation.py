@@ -1,5 +1,5 @@
-"""The evaluation loop's entry points on the device, over the C ABI: SDR, STOI, ESTOI, SI-SDR and
-segmental SNR per utterance, add_noise's SNR mixing in closed form, and the core of the loop, STFT -> forward -> ISTFT -> scores.  audio.py re-exports
+"""The evaluation loop's entry points on the device, over the C ABI: SDR, STOI, ESTOI, SI-SDR,
+segmental SNR, LLR and WSS per utterance, add_noise's SNR mixing in closed form, and the core of the loop, STFT -> forward -> ISTFT -> scores.  audio.py re-exports
 every public name here."""
 
 import numpy as np
@@ -103,16 +103,68 @@ def seg_snr_batch(clean, estimate, lengths=None, sample_rate=8000, detail=False)
     return (out, frames) if detail else out
 
 
+SPECTRAL_RATES = (8000, 16000)
+
+
+def _spectral_rate(sample_rate):
+    if sample_rate not in SPECTRAL_RATES:
+        raise ValueError("sample_rate must be 8000 or 16000, got %r" % (sample_rate,))
+    return int(sample_rate)
+
+
+def _spectral_batch(name, clean, estimate, lengths, sample_rate, detail, limit=None):
+    import torch
+    fs = _spectral_rate(sample_rate)
+    clean, estimate, n, dev, sc, se, ldev = _args.scoring_args(clean, estimate, lengths)
+    w = (3 * fs + 50) // 100
+    most = (min(sc, se) - w) // (w // 4) + 1 if min(sc, se) >= w else 0      # the frames of a row read to its end
+    out = torch.empty((n,), dtype=torch.float64, device=dev)
+    nf = torch.empty((n,), dtype=torch.int32, device=dev) if detail else None
+    frames = torch.zeros((n, most), dtype=torch.float64, device=dev) if detail else None
+    if n:
+        ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+        head = (clean.data_ptr(), sc, estimate.data_ptr(), se, ptr(ldev), n, fs)
+        tail = (out.data_ptr(), ptr(frames), most, ptr(nf), dev.index, _args.current_stream(dev))
+        if name == "llr":
+            _lib.check(_lib.load().rced_llr(*(head + (limit,) + tail)))
+        else:
+            _lib.check(_lib.load().rced_wss(*(head + tail)))
+    return (out, nf, frames) if detail else out
+
+
+def llr_batch(clean, estimate, lengths=None, sample_rate=8000, limit=2.0, detail=False):
+    """Log-likelihood ratio of the two signals' LPC models per utterance on the device (DESIGN.md "LLR": the segmental SNR's
+    frames of x + eps and y + eps, order 10 below 10 kHz else 16, Levinson-Durbin, ln of the ratio of the two models'
+    residual energies on the clean frame, the mean of the lowest 95 % of the frames).  Arguments as in sdr_batch;
+    sample_rate: 8000 or 16000; limit: each frame's value enters the mean as min(value, limit) -- None or inf for none, the
+    form metrics.composite takes.  Returns torch.float64 [N] on the device, current stream -- nan for an utterance shorter
+    than one frame; with detail=True also torch.int32 [N], the frames of each utterance, and torch.float64 [N, F], every
+    frame's value before the limit in frame order (0 past an utterance's frames).  Built as DESIGN.md writes it: parity
+    with pysepm is unpinned."""
+    limit = float("inf") if limit is None else float(limit)
+    if limit != limit:
+        raise ValueError("limit must be a number or None, got nan")
+    return _spectral_batch("llr", clean, estimate, lengths, sample_rate, detail, limit)
+
+
+def wss_batch(clean, estimate, lengths=None, sample_rate=8000, detail=False):
+    """Weighted spectral slope distance per utterance on the device (DESIGN.md "WSS": the segmental SNR's frames, an fp64
+    DFT, 25 critical-band energies in dB, their 24 slopes weighted by the nearest peak and the global maximum, the mean of
+    the lowest 95 % of the frames).  Arguments and returns as in llr_batch, without the limit."""
+    return _spectral_batch("wss", clean, estimate, lengths, sample_rate, detail)
+
+
 EXTRA_METRICS = ("estoi", "si_sdr", "seg_snr")
+SPECTRAL_METRICS = ("llr", "wss")       # the composite measures' two spectral terms; `extra` takes names from both tuples
 
 
 def check_extra(extra):
-    """The evaluation loop's `extra` argument as a tuple of names from EXTRA_METRICS, in the caller's order; ValueError for
-    anything else.  Touches no device."""
+    """The evaluation loop's `extra` argument as a tuple of names from EXTRA_METRICS + SPECTRAL_METRICS, in the caller's
+    order; ValueError for anything else.  Touches no device."""
     names = (extra,) if isinstance(extra, str) else tuple(extra)
     for name in names:
-        if name not in EXTRA_METRICS:
-            raise ValueError("extra names must come from %r, got %r" % (EXTRA_METRICS, name))
+        if name not in EXTRA_METRICS + SPECTRAL_METRICS:
+            raise ValueError("extra names must come from %r, got %r" % (EXTRA_METRICS + SPECTRAL_METRICS, name))
     if len(set(names)) != len(names):
         raise ValueError("extra names must be distinct, got %r" % (names,))
     return names
@@ -185,7 +237,8 @@ def denoise_and_score(forward, mix, clean, lengths, nfft=512, kernels="x6", stoi
     """The device core of the evaluation loop (tester.py:100-146 / trainer.py:260-307 without PESQ / wav files):
     STFT of the mixtures -> forward (device [N, T, 129, 1] -> same) -> ISTFT rebuild -> SDR (and, with stoi=True, STOI) of
     every rebuilt row against its clean row over its own length.  mix, clean: torch.cuda float32 [N, L] zero-padded;
-    lengths: N sample counts.  extra: names from EXTRA_METRICS, further scores of the same pairs.
+    lengths: N sample counts.  extra: names from EXTRA_METRICS + SPECTRAL_METRICS, further scores of the same pairs ("llr" is
+    the form limited at 2).
     Returns (audio [N, (T+1)*128] on the device -- the caller trims row n to lengths[n] --, sdr torch.float64 [N]), with
     stoi=True (audio, sdr, stoi torch.float64 [N]); with extra, one more element last: a dict name -> torch.float64 [N]
     (STOI and ESTOI, asked for together, come from one rced_stoi_ex call).
@@ -213,4 +266,8 @@ def denoise_and_score(forward, mix, clean, lengths, nfft=512, kernels="x6", stoi
         more["si_sdr"] = si_sdr_batch(clean, out, lengths)
     if "seg_snr" in extra:
         more["seg_snr"] = seg_snr_batch(clean, out, lengths, SAMPLE_RATE)
+    if "llr" in extra:
+        more["llr"] = llr_batch(clean, out, lengths, SAMPLE_RATE)
+    if "wss" in extra:
+        more["wss"] = wss_batch(clean, out, lengths, SAMPLE_RATE)
     return scored + ({name: more[name] for name in extra},) if extra else scored

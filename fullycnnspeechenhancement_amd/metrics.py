@@ -7,7 +7,9 @@ reach: parity is pinned to the restatement of the published algorithm in tests/s
 ESTOI (pystoi's extended=True), SISDR (the optimal-scaling form the reference carries, commented out, inside SDR.sdr,
 utils.py:80-85) and SegSNR have the same call surface over rced_stoi_ex / rced_si_sdr / rced_seg_snr; each is pinned to the
 float64 restatement of its definition in tests/ (DESIGN.md "ESTOI", "SI-SDR", "Segmental SNR"), not to pystoi or pysepm.
-PESQ is not built (the reference takes it from pypesq).
+LLR and WSS (rced_llr / rced_wss, pinned to tests/sepm_np.py in the same way) are the two spectral terms of the composite
+measures of Hu and Loizou (2008); `composite` turns them, the segmental SNR and a PESQ column into CSIG / CBAK / COVL.
+PESQ is not built (the reference takes it from pypesq); everything else the composite measures need is.
 """
 
 import numpy as np
@@ -155,3 +157,63 @@ class SegSNR(object):
 
     def __call__(self, x, y):
         return self.seg_snr(x, y)
+
+
+class LLR(object):
+    """Log-likelihood ratio of the LPC models, `LLR(sr, limit)(clean, processed)`: numpy 1-D in, Python float out, computed
+    on the device (rced_llr).  limit: the cap on a frame's value (2 as published; None for none, the form `composite`
+    takes).  Signals shorter than one frame give nan."""
+
+    def __init__(self, sr=8000, limit=2.0, device=0):
+        from . import audio
+        if sr not in audio.SPECTRAL_RATES:
+            raise ValueError("sr must be 8000 or 16000, got %r" % (sr,))
+        if limit is not None and float(limit) != float(limit):
+            raise ValueError("limit must be a number or None, got nan")
+        self.sr, self.limit, self.device = int(sr), limit, device
+
+    def llr(self, x, y):
+        from . import audio
+        pair = _pair(x, y)
+        if not pair.shape[1]:
+            return float("nan")
+        return _score_pair(audio.llr_batch, pair, self.device, sample_rate=self.sr, limit=self.limit)
+
+    def __call__(self, x, y):
+        return self.llr(x, y)
+
+
+class WSS(object):
+    """Weighted spectral slope distance, `WSS(sr)(clean, processed)`: numpy 1-D in, Python float out, computed on the device
+    (rced_wss).  Signals shorter than one frame give nan."""
+
+    def __init__(self, sr=8000, device=0):
+        from . import audio
+        if sr not in audio.SPECTRAL_RATES:
+            raise ValueError("sr must be 8000 or 16000, got %r" % (sr,))
+        self.sr, self.device = int(sr), device
+
+    def wss(self, x, y):
+        from . import audio
+        pair = _pair(x, y)
+        if not pair.shape[1]:
+            return float("nan")
+        return _score_pair(audio.wss_batch, pair, self.device, sample_rate=self.sr)
+
+    def __call__(self, x, y):
+        return self.wss(x, y)
+
+
+def composite(pesq, llr, wss, seg_snr):
+    """The composite measures of Hu and Loizou (2008), elementwise over numpy-broadcastable columns, on the host:
+        CSIG = 3.093 - 1.029 LLR + 0.603 PESQ - 0.009 WSS
+        CBAK = 1.634 + 0.478 PESQ - 0.007 WSS + 0.063 segSNR
+        COVL = 1.594 + 0.805 PESQ - 0.512 LLR - 0.007 WSS
+    each clipped to [1, 5].  llr is the unlimited form (audio.llr_batch(limit=None) / LLR(limit=None)), wss and seg_snr as
+    audio.wss_batch and audio.seg_snr_batch give them.  pesq is the caller's: this project does not compute it.
+    Returns (csig, cbak, covl), numpy float64."""
+    pesq, llr, wss, seg_snr = (np.asarray(v, np.float64) for v in (pesq, llr, wss, seg_snr))
+    csig = 3.093 - 1.029 * llr + 0.603 * pesq - 0.009 * wss
+    cbak = 1.634 + 0.478 * pesq - 0.007 * wss + 0.063 * seg_snr
+    covl = 1.594 + 0.805 * pesq - 0.512 * llr - 0.007 * wss
+    return tuple(np.clip(v, 1.0, 5.0) for v in (csig, cbak, covl))

@@ -352,6 +352,32 @@ int rced_si_sdr(const float* ref_dev, int ref_stride, const float* est_dev, int 
 int rced_seg_snr(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride,
                  const int* lengths_dev, int N, int fs, double* out_dev, int* frames_dev, int device, void* stream);
 
+/* LLR and WSS per utterance over its own length L: the log-likelihood ratio of the two signals' LPC models and the
+ * weighted spectral slope distance, the two spectral terms of the composite measures CSIG / CBAK / COVL (Hu, Loizou 2008;
+ * the other two are the segmental SNR above and PESQ, which this library does not compute).  Both are built as DESIGN.md
+ * 3.4c writes them; parity with pysepm or the MATLAB originals is unpinned.
+ *   Framing: rced_seg_snr's (W = (3 fs + 50) / 100, hop W / 4, the same window), sample_rate 8000 or 16000 only -- any
+ * other rate is RCED_ERR_ARG.  Aggregation, both scores: the mean of the k = (95 nf + 50) / 100 smallest frame values
+ * (ties by frame index, summed in one order fixed by the ranks), nan for nf = 0.
+ *   LLR: order P = 10 below 10 kHz, else 16; frames of x + eps and y + eps under the window; autocorrelation lags 0 .. P;
+ * Levinson-Durbin; d = ln((A_y T A_y') / (A_x T A_x')), T the Toeplitz matrix of the clean frame's lags; with a finite
+ * `limit` each d enters the aggregation as min(d, limit) (the usual limit is 2; +inf leaves d alone: the form the
+ * composite formulas take; nan is RCED_ERR_ARG).  IEEE results stand.
+ *   WSS: |DFT_nfft(w frame)|^2 (nfft = 512 at 8 kHz, 1024 at 16 kHz) in fp64 on the matrix pipe, 25 critical-band
+ * energies in dB, 24 slopes, nearest-peak weights, d = sum(W (s_x - s_y)^2) / sum(W).
+ *   Pointers, strides, lengths_dev and their clamping as in rced_sdr; samples past a length are never read.  out_dev [N]
+ * double.  frames_out: NULL or [N][frames_stride] double receiving every frame's value in frame order (LLR: before the
+ * limit); entries at and past an utterance's nf are left untouched.  The lengths live on the device, so frames_stride is
+ * held against the most frames a row can carry: frames_stride < frames(min(ref_stride, est_stride)) is RCED_ERR_ARG.
+ * nf_out: NULL or [N] int32 receiving nf.  Four launches each; a workspace of its own per (device, stream), growing only;
+ * the WSS tables are built once per process and rate and uploaded once per device.  The ranking compares every pair of an
+ * utterance's frames: its cost grows with nf^2.  The invariants stated above hold.  Asynchronous. */
+int rced_llr(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N,
+             int sample_rate, double limit, double* out_dev, double* frames_out, int frames_stride, int* nf_out,
+             int device, void* stream);
+int rced_wss(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N,
+             int sample_rate, double* out_dev, double* frames_out, int frames_stride, int* nf_out, int device, void* stream);
+
 /* ---- streaming denoiser: PCM in, PCM out, 128 samples (one hop, 16 ms) at a time, for many independent streams ("lanes") at once,
  * at a fixed delay.  Only the first layer of the three networks looks across time (3 past, 4 future frames) and the rebuild uses no
  * overlap-add, so the chunked run reproduces the whole-utterance chain rced_stft -> rced_forward -> rced_istft.

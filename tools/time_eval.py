@@ -8,6 +8,8 @@ STOI (rced_stoi) is timed at the same shape, beside the wall time of its float64
 The further scores -- legs `estoi`, `stoi+estoi` (one rced_stoi_ex call for both), `si_sdr`, `seg_snr` -- run at the same shape
 beside their restatements (tests/estoi_np.py, tests/td_metrics_np.py) on the same 16 processes, with the ratio of `stoi+estoi`
 to rced_stoi alone in this process; `python tools/time_eval.py ext` times those alone.
+LLR and WSS (rced_llr, rced_wss) -- legs `llr`, `wss` -- run at the same shape beside their restatement (tests/sepm_np.py) on the
+same 16 processes; `python tools/time_eval.py sepm` times those alone.
 Prints one JSON line."""
 import json
 import os
@@ -78,6 +80,18 @@ def _host_seg_snr(seed):
     return td_metrics_np.seg_snr(*_host_pair(seed), 8000)
 
 
+def _host_llr(seed):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import sepm_np
+    return sepm_np.llr(*_host_pair(seed), 8000)
+
+
+def _host_wss(seed):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import sepm_np
+    return sepm_np.wss(*_host_pair(seed), 8000)
+
+
 def host_seconds(fn):
     """Wall time of a restatement over N utterances of L samples on HOST_PROCS processes (forked before the GPU is touched)."""
     import multiprocessing
@@ -113,12 +127,22 @@ def ext_timings(speech, mix, host_ext):
     return out
 
 
+def sepm_timings(speech, mix, host_sepm):
+    """LLR and WSS, each beside its restatement's wall time."""
+    out = {"llr": timed_us(lambda: audio.llr_batch(speech, mix)), "wss": timed_us(lambda: audio.wss_batch(speech, mix))}
+    for leg, seconds in host_sepm.items():
+        out[leg + "_host_restatement_s"] = {"seconds": seconds, "processes": HOST_PROCS}
+    return out
+
+
 def main():
     only_stoi = sys.argv[1:] == ["stoi"]
     only_ext = sys.argv[1:] == ["ext"]
-    host_s = host_stoi_seconds() if not only_ext else None       # first: these fork
-    host_ext = {} if only_stoi else {"estoi": host_seconds(_host_estoi), "si_sdr": host_seconds(_host_si_sdr),
-                                     "seg_snr": host_seconds(_host_seg_snr)}
+    only_sepm = sys.argv[1:] == ["sepm"]
+    host_s = host_stoi_seconds() if not (only_ext or only_sepm) else None       # first: these fork
+    host_ext = {} if only_stoi or only_sepm else {"estoi": host_seconds(_host_estoi), "si_sdr": host_seconds(_host_si_sdr),
+                                                  "seg_snr": host_seconds(_host_seg_snr)}
+    host_sepm = {} if only_stoi or only_ext else {"llr": host_seconds(_host_llr), "wss": host_seconds(_host_wss)}
     g = torch.Generator(device="cuda").manual_seed(1)
     speech = torch.randn((N, L), device="cuda", generator=g) * 0.1
     noise = torch.randn((N, L), device="cuda", generator=g) * 0.05
@@ -131,6 +155,10 @@ def main():
         return
     if only_ext:
         out.update(ext_timings(speech, audio.mix_snr_batch(speech, noise, 5.0), host_ext))
+        print(json.dumps(out))
+        return
+    if only_sepm:
+        out.update(sepm_timings(speech, audio.mix_snr_batch(speech, noise, 5.0), host_sepm))
         print(json.dumps(out))
         return
 
@@ -159,6 +187,7 @@ def main():
     out["stoi"], out["stoi_single_utterance"] = stoi_timings(speech, mix)
     out["stoi_host_restatement_s"] = {"seconds": host_s, "processes": HOST_PROCS}
     out.update(ext_timings(speech, mix, host_ext))
+    out.update(sepm_timings(speech, mix, host_sepm))
 
     model = build_model("FullyCNNV3", False, weights=_weights.synthetic_weights(3, seed=42))
     lens = [L] * N
