@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/rced.h"
+#include "kernels_bsseval.h"
 #include "kernels_eval.h"
 #include "kernels_sepm.h"
 #include "kernels_stoi.h"
@@ -23,8 +24,8 @@ struct Workspace {
   double* p = nullptr;
   size_t bytes = 0;
 };
-// STOI, SI-SDR, the segmental SNR, LLR and WSS keep buffers of their own: none ever moves the one another entry's captured graph reads
-enum { kWsSlices = 0, kWsStoi = 1, kWsSiSdr = 2, kWsSegSnr = 3, kWsLlr = 4, kWsWss = 5, kWsKinds = 6 };
+// STOI, SI-SDR, the segmental SNR, LLR, WSS and the BSS Eval SDR keep buffers of their own: none ever moves the one another entry's captured graph reads
+enum { kWsSlices = 0, kWsStoi = 1, kWsSiSdr = 2, kWsSegSnr = 3, kWsLlr = 4, kWsWss = 5, kWsBss = 6, kWsKinds = 7 };
 std::map<void*, Workspace> g_ws[kWsKinds][kMaxDevices];
 std::mutex g_mu;
 
@@ -436,6 +437,45 @@ int rced_wss(const float* ref_dev, int ref_stride, const float* est_dev, int est
                      (const double*)ws, lengths_dev, cap, W, nfcap, d, frames_out, frames_stride);
   HIP_TRY(hipGetLastError());
   return lowest_mean(d, sorted, lengths_dev, N, cap, W, nfcap, out_dev, nf_out, st);
+}
+
+int rced_bss_sdr(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N,
+                 int filter_length, double* sdr_dev, double* filter_dev, double* energies_dev, int device, void* stream) {
+  if (N < 0 || ref_stride < 0 || est_stride < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
+  if (!ref_dev || !est_dev || !sdr_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
+  if (filter_length < 1 || filter_length > bss::kMaxTaps)
+    return rced_fail(RCED_ERR_ARG, "filter_length must lie in [1, %d], got %d", bss::kMaxTaps, filter_length);
+  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
+  const int cap = ref_stride < est_stride ? ref_stride : est_stride;
+  if (cap > eval::kMaxLen) return rced_fail(RCED_ERR_ARG, "rows longer than 2^30 samples");
+  if (N == 0) return RCED_OK;
+  if (int rc = check_device(device, kMaxDevices)) return rc;
+  DeviceGuard g(device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  const int F = filter_length;
+  const int slices = bss::corr_slices(cap) > 0 ? bss::corr_slices(cap) : 1;
+  const int pslices = bss::out_slices(cap, F) > 0 ? bss::out_slices(cap, F) : 1;
+  // workspace: part [N][2][slices][F] | c [N][F] | energies [N][pslices][2]
+  const size_t o_c = align256((size_t)N * 2 * slices * F * 8), o_p = o_c + align256((size_t)N * F * 8),
+               total = o_p + align256((size_t)N * pslices * 2 * 8);
+  double* ws = nullptr;
+  if (int rc = workspace(device, stream, total, &ws, kWsBss)) return rc;
+  char* base = reinterpret_cast<char*>(ws);
+  double* c = reinterpret_cast<double*>(base + o_c);
+  double* pws = reinterpret_cast<double*>(base + o_p);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(bss::correlate_kernel, dim3(slices, 2, N), dim3(bss::kThreads), 0, st, ref_dev, ref_stride, est_dev, est_stride,
+                     lengths_dev, cap, F, ws, slices);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(bss::solve_kernel, dim3(N), dim3(64), 0, st, (const double*)ws, lengths_dev, cap, F, slices, c, filter_dev);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(bss::project_kernel, dim3(pslices, N), dim3(bss::kThreads), 0, st, ref_dev, ref_stride, est_dev, est_stride,
+                     lengths_dev, cap, F, (const double*)c, pws, pslices);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(bss::final_kernel, dim3(N), dim3(64), 0, st, (const double*)pws, lengths_dev, cap, F, pslices, sdr_dev,
+                     energies_dev);
+  HIP_TRY(hipGetLastError());
+  return RCED_OK;
 }
 
 int rced_sdr(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N,

@@ -1,5 +1,5 @@
 """The evaluation loop's entry points on the device, over the C ABI: SDR, STOI, ESTOI, SI-SDR,
-segmental SNR, LLR and WSS per utterance, add_noise's SNR mixing in closed form, and the core of the loop, STFT -> forward -> ISTFT -> scores.  audio.py re-exports
+segmental SNR, LLR, WSS and the SDR of BSS Eval per utterance, add_noise's SNR mixing in closed form, and the core of the loop, STFT -> forward -> ISTFT -> scores.  audio.py re-exports
 every public name here."""
 
 import numpy as np
@@ -154,17 +154,53 @@ def wss_batch(clean, estimate, lengths=None, sample_rate=8000, detail=False):
     return _spectral_batch("wss", clean, estimate, lengths, sample_rate, detail)
 
 
+BSS_MAX_FILTER = 512
+
+
+def _filter_length(filter_length):
+    if isinstance(filter_length, bool) or not isinstance(filter_length, (int, np.integer)) or not 1 <= filter_length <= BSS_MAX_FILTER:
+        raise ValueError("filter_length must be an integer in [1, %d], got %r" % (BSS_MAX_FILTER, filter_length))
+    return int(filter_length)
+
+
+def bss_sdr_batch(clean, estimate, lengths=None, filter_length=512, detail=False):
+    """The SDR of BSS Eval (Vincent, Gribonval, Fevotte 2006) for a single source, per utterance on the device (DESIGN.md
+    "BSS Eval SDR"): the estimate is projected onto the span of the clean row delayed by 0 .. filter_length - 1 samples --
+    r = autocorrelation of x, d = cross-correlation of x and y at lags 0 .. F - 1, toeplitz(r) c = d, s = x * c,
+    e = [y, 0 ..] - s over L + F - 1 samples, 10 log10(sum s^2 / sum e^2) -- so a fixed linear filtering or a delay of the
+    estimate is forgiven.  All of it in fp64.  Arguments as in si_sdr_batch; filter_length: an integer in [1, 512], anything
+    else is a ValueError before any device work; 1 gives si_sdr_batch's score.
+    Returns torch.float64 [N] (dB) on the device, current stream -- nan for a length of 0, an all-zero clean row or an all-zero
+    estimate; with detail=True also torch.float64 [N, filter_length], the filters c, and torch.float64 [N, 2], sum s^2 and
+    sum e^2.  Nothing is regularised and there is no least-squares fallback: a singular toeplitz(r) (a clean row with an
+    empty band) gives whatever the recursion gives.  This is bss_eval_sources for one source; parity with mir_eval or museval
+    is unpinned, the pin is the float64 restatement in tests/bsseval_np.py."""
+    import torch
+    taps = _filter_length(filter_length)
+    clean, estimate, n, dev, sc, se, ldev = _args.scoring_args(clean, estimate, lengths)
+    out = torch.empty((n,), dtype=torch.float64, device=dev)
+    filt = torch.empty((n, taps), dtype=torch.float64, device=dev) if detail else None
+    energies = torch.empty((n, 2), dtype=torch.float64, device=dev) if detail else None
+    if n:
+        ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+        _lib.check(_lib.load().rced_bss_sdr(clean.data_ptr(), sc, estimate.data_ptr(), se, ptr(ldev), n, taps, out.data_ptr(), ptr(filt),
+                                            ptr(energies), dev.index, _args.current_stream(dev)))
+    return (out, filt, energies) if detail else out
+
+
 EXTRA_METRICS = ("estoi", "si_sdr", "seg_snr")
-SPECTRAL_METRICS = ("llr", "wss")       # the composite measures' two spectral terms; `extra` takes names from both tuples
+SPECTRAL_METRICS = ("llr", "wss")       # the composite measures' two spectral terms; `extra` takes names from all three tuples
+PROJECTION_METRICS = ("bss_sdr",)       # BSS Eval's SDR at its filter length of 512
+ALL_EXTRA = EXTRA_METRICS + SPECTRAL_METRICS + PROJECTION_METRICS
 
 
 def check_extra(extra):
-    """The evaluation loop's `extra` argument as a tuple of names from EXTRA_METRICS + SPECTRAL_METRICS, in the caller's
-    order; ValueError for anything else.  Touches no device."""
+    """The evaluation loop's `extra` argument as a tuple of names from EXTRA_METRICS + SPECTRAL_METRICS + PROJECTION_METRICS,
+    in the caller's order; ValueError for anything else.  Touches no device."""
     names = (extra,) if isinstance(extra, str) else tuple(extra)
     for name in names:
-        if name not in EXTRA_METRICS + SPECTRAL_METRICS:
-            raise ValueError("extra names must come from %r, got %r" % (EXTRA_METRICS + SPECTRAL_METRICS, name))
+        if name not in ALL_EXTRA:
+            raise ValueError("extra names must come from %r, got %r" % (ALL_EXTRA, name))
     if len(set(names)) != len(names):
         raise ValueError("extra names must be distinct, got %r" % (names,))
     return names
@@ -237,8 +273,8 @@ def denoise_and_score(forward, mix, clean, lengths, nfft=512, kernels="x6", stoi
     """The device core of the evaluation loop (tester.py:100-146 / trainer.py:260-307 without PESQ / wav files):
     STFT of the mixtures -> forward (device [N, T, 129, 1] -> same) -> ISTFT rebuild -> SDR (and, with stoi=True, STOI) of
     every rebuilt row against its clean row over its own length.  mix, clean: torch.cuda float32 [N, L] zero-padded;
-    lengths: N sample counts.  extra: names from EXTRA_METRICS + SPECTRAL_METRICS, further scores of the same pairs ("llr" is
-    the form limited at 2).
+    lengths: N sample counts.  extra: names from EXTRA_METRICS + SPECTRAL_METRICS + PROJECTION_METRICS, further scores of
+    the same pairs ("llr" is the form limited at 2, "bss_sdr" BSS Eval's SDR with 512 taps).
     Returns (audio [N, (T+1)*128] on the device -- the caller trims row n to lengths[n] --, sdr torch.float64 [N]), with
     stoi=True (audio, sdr, stoi torch.float64 [N]); with extra, one more element last: a dict name -> torch.float64 [N]
     (STOI and ESTOI, asked for together, come from one rced_stoi_ex call).
@@ -270,4 +306,6 @@ def denoise_and_score(forward, mix, clean, lengths, nfft=512, kernels="x6", stoi
         more["llr"] = llr_batch(clean, out, lengths, SAMPLE_RATE)
     if "wss" in extra:
         more["wss"] = wss_batch(clean, out, lengths, SAMPLE_RATE)
+    if "bss_sdr" in extra:
+        more["bss_sdr"] = bss_sdr_batch(clean, out, lengths)
     return scored + ({name: more[name] for name in extra},) if extra else scored

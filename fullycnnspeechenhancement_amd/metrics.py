@@ -9,6 +9,8 @@ utils.py:80-85) and SegSNR have the same call surface over rced_stoi_ex / rced_s
 float64 restatement of its definition in tests/ (DESIGN.md "ESTOI", "SI-SDR", "Segmental SNR"), not to pystoi or pysepm.
 LLR and WSS (rced_llr / rced_wss, pinned to tests/sepm_np.py in the same way) are the two spectral terms of the composite
 measures of Hu and Loizou (2008); `composite` turns them, the segmental SNR and a PESQ column into CSIG / CBAK / COVL.
+BSSSDR (rced_bss_sdr, pinned to tests/bsseval_np.py) is the SDR of BSS Eval for one source: the estimate is projected onto
+the clean signal's delayed copies first, so a fixed filtering or delay is forgiven.
 PESQ is not built (the reference takes it from pypesq); everything else the composite measures need is.
 """
 
@@ -137,6 +139,27 @@ class SISDR(object):
 
     def __call__(self, x, y):
         return self.si_sdr(x, y)
+
+
+class BSSSDR(object):
+    """The SDR of BSS Eval for one source, `BSSSDR(filter_length)(y, y_pred)` as `SISDR()(y, y_pred)`: numpy 1-D in, Python
+    float (dB) out, computed on the device (rced_bss_sdr): the estimate is scored after its projection onto the clean signal
+    delayed by 0 .. filter_length - 1 samples (512 as bss_eval_sources has it; parity with mir_eval is unpinned, the pin is
+    tests/bsseval_np.py).  Two empty signals give nan, as the definition does."""
+
+    def __init__(self, filter_length=512, device=0):
+        from . import evaluation
+        self.filter_length, self.device = evaluation._filter_length(filter_length), device      # ValueError outside 1 .. 512
+
+    def bss_sdr(self, y, y_pred):
+        from . import audio
+        pair = _pair(y, y_pred)
+        if not pair.shape[1]:
+            return float("nan")
+        return _score_pair(audio.bss_sdr_batch, pair, self.device, filter_length=self.filter_length)
+
+    def __call__(self, x, y):
+        return self.bss_sdr(x, y)
 
 
 class SegSNR(object):

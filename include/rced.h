@@ -378,6 +378,28 @@ int rced_llr(const float* ref_dev, int ref_stride, const float* est_dev, int est
 int rced_wss(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N,
              int sample_rate, double* out_dev, double* frames_out, int frames_stride, int* nf_out, int device, void* stream);
 
+/* The signal-to-distortion ratio of BSS Eval (Vincent, Gribonval, Fevotte 2006) for a single source, per utterance over
+ * its own length L: the estimate is first projected onto the span of the clean signal delayed by 0 .. F - 1 samples,
+ * F = filter_length, 1 <= F <= 512 (anything else is RCED_ERR_ARG), so a fixed linear filtering or a delay of the estimate
+ * is forgiven.  x = ref row, y = est row, float32 samples [0, L) read as float64; samples at or past L count as 0 and are
+ * never read:
+ *   r[t] = sum_n x[n] x[n + t],  d[t] = sum_n x[n] y[n + t],  t = 0 .. F - 1;
+ *   G = toeplitz(r), G c = d: the least-squares causal FIR of F taps from x to y;
+ *   s = x * c over L + F - 1 samples,  e = [y, 0 .. 0] - s over the same;   score = 10 * log10(sum s^2 / sum e^2) dB.
+ * This is bss_eval_sources for one source (its SDR equals its SAR, its SIR is infinite); parity with mir_eval or museval
+ * is unpinned: the pin is the float64 restatement in tests/bsseval_np.py.  With F = 1 the score is rced_si_sdr's.
+ * L = 0, x = 0 and y = 0 give nan; non-finite samples propagate.  Nothing is regularised and there is no least-squares
+ * fallback: a singular or numerically singular G (a reference with an empty band) gives whatever the recursion gives.
+ * Pointers, strides, lengths_dev (NULL: every row is read to the shorter stride) and their clamping as in rced_sdr.
+ * sdr_dev [N] double; filter_dev: NULL or [N, filter_length] double receiving c; energies_dev: NULL or [N, 2] double
+ * receiving sum s^2, sum e^2.  fp64 throughout: both correlations and the projection are block-Toeplitz products on the
+ * fp64 matrix pipe over slices of 4096 samples, summed in slice order; the solve is Levinson's recursion with a general
+ * right-hand side, one wave per utterance.  Four launches; a workspace of its own per (device, stream), growing only: after
+ * one call of a shape nothing is allocated and the call can be stream-captured.  The invariants stated above hold.
+ * Asynchronous. */
+int rced_bss_sdr(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N,
+                 int filter_length, double* sdr_dev, double* filter_dev, double* energies_dev, int device, void* stream);
+
 /* ---- streaming denoiser: PCM in, PCM out, 128 samples (one hop, 16 ms) at a time, for many independent streams ("lanes") at once,
  * at a fixed delay.  Only the first layer of the three networks looks across time (3 past, 4 future frames) and the rebuild uses no
  * overlap-add, so the chunked run reproduces the whole-utterance chain rced_stft -> rced_forward -> rced_istft.

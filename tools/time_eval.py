@@ -10,6 +10,8 @@ beside their restatements (tests/estoi_np.py, tests/td_metrics_np.py) on the sam
 to rced_stoi alone in this process; `python tools/time_eval.py ext` times those alone.
 LLR and WSS (rced_llr, rced_wss) -- legs `llr`, `wss` -- run at the same shape beside their restatement (tests/sepm_np.py) on the
 same 16 processes; `python tools/time_eval.py sepm` times those alone.
+The SDR of BSS Eval (rced_bss_sdr, 512 taps) -- leg `bss_sdr` -- runs at the same shape beside its restatement (tests/bsseval_np.py,
+the normal equations) on the same 16 processes; `python tools/time_eval.py bss` times it alone, with WSS and STOI from the same run.
 Prints one JSON line."""
 import json
 import os
@@ -92,6 +94,12 @@ def _host_wss(seed):
     return sepm_np.wss(*_host_pair(seed), 8000)
 
 
+def _host_bss_sdr(seed):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import bsseval_np
+    return bsseval_np.bss_sdr(*_host_pair(seed), 512)
+
+
 def host_seconds(fn):
     """Wall time of a restatement over N utterances of L samples on HOST_PROCS processes (forked before the GPU is touched)."""
     import multiprocessing
@@ -135,14 +143,25 @@ def sepm_timings(speech, mix, host_sepm):
     return out
 
 
+def bss_timings(speech, mix, host_bss):
+    """BSS Eval's SDR at 512 taps (and at one tap: what the 512 lags cost) beside its restatement's wall time."""
+    out = {"bss_sdr": timed_us(lambda: audio.bss_sdr_batch(speech, mix)),
+           "bss_sdr_one_tap": timed_us(lambda: audio.bss_sdr_batch(speech, mix, filter_length=1)),
+           "bss_sdr_single_utterance": timed_us(lambda: audio.bss_sdr_batch(speech[:1], mix[:1]))}
+    out["bss_sdr_host_restatement_s"] = {"seconds": host_bss, "processes": HOST_PROCS}
+    return out
+
+
 def main():
     only_stoi = sys.argv[1:] == ["stoi"]
     only_ext = sys.argv[1:] == ["ext"]
     only_sepm = sys.argv[1:] == ["sepm"]
-    host_s = host_stoi_seconds() if not (only_ext or only_sepm) else None       # first: these fork
-    host_ext = {} if only_stoi or only_sepm else {"estoi": host_seconds(_host_estoi), "si_sdr": host_seconds(_host_si_sdr),
+    only_bss = sys.argv[1:] == ["bss"]
+    host_s = host_stoi_seconds() if not (only_ext or only_sepm or only_bss) else None       # first: these fork
+    host_bss = None if only_stoi or only_ext or only_sepm else host_seconds(_host_bss_sdr)
+    host_ext = {} if only_stoi or only_sepm or only_bss else {"estoi": host_seconds(_host_estoi), "si_sdr": host_seconds(_host_si_sdr),
                                                   "seg_snr": host_seconds(_host_seg_snr)}
-    host_sepm = {} if only_stoi or only_ext else {"llr": host_seconds(_host_llr), "wss": host_seconds(_host_wss)}
+    host_sepm = {} if only_stoi or only_ext or only_bss else {"llr": host_seconds(_host_llr), "wss": host_seconds(_host_wss)}
     g = torch.Generator(device="cuda").manual_seed(1)
     speech = torch.randn((N, L), device="cuda", generator=g) * 0.1
     noise = torch.randn((N, L), device="cuda", generator=g) * 0.05
@@ -155,6 +174,12 @@ def main():
         return
     if only_ext:
         out.update(ext_timings(speech, audio.mix_snr_batch(speech, noise, 5.0), host_ext))
+        print(json.dumps(out))
+        return
+    if only_bss:
+        mix = audio.mix_snr_batch(speech, noise, 5.0)
+        out.update(bss_timings(speech, mix, host_bss))
+        out["wss"], out["stoi"] = timed_us(lambda: audio.wss_batch(speech, mix)), timed_us(lambda: audio.stoi_batch(speech, mix))
         print(json.dumps(out))
         return
     if only_sepm:
@@ -188,6 +213,7 @@ def main():
     out["stoi_host_restatement_s"] = {"seconds": host_s, "processes": HOST_PROCS}
     out.update(ext_timings(speech, mix, host_ext))
     out.update(sepm_timings(speech, mix, host_sepm))
+    out.update(bss_timings(speech, mix, host_bss))
 
     model = build_model("FullyCNNV3", False, weights=_weights.synthetic_weights(3, seed=42))
     lens = [L] * N
