@@ -63,6 +63,11 @@ def row_stride(x):
     return int(x.stride(0)) if x.shape[0] > 1 else int(x.shape[1])
 
 
+def ptr(t):
+    """A tensor's address as the C ABI takes it; None is the null pointer."""
+    return t.data_ptr() if t is not None else None
+
+
 def scoring_args(clean, estimate, lengths):
     """What rced_sdr and rced_stoi both take: (clean, estimate, n, device, clean's row stride, estimate's row stride, the
     lengths on the device or None), from clean [N, Lc], estimate [N, Le] and N lengths in [0, min(Lc, Le)] or None."""

@@ -1,6 +1,7 @@
 // C ABI of the evaluation loop's device pieces (include/rced.h, "evaluation" section): host side.
 #include <hip/hip_runtime.h>
 
+#include <cassert>
 #include <cmath>
 #include <map>
 #include <mutex>
@@ -25,13 +26,13 @@ struct Workspace {
   size_t bytes = 0;
 };
 // STOI, SI-SDR, the segmental SNR, LLR, WSS and the BSS Eval SDR keep buffers of their own: none ever moves the one another entry's captured graph reads
-enum { kWsSlices = 0, kWsStoi = 1, kWsSiSdr = 2, kWsSegSnr = 3, kWsLlr = 4, kWsWss = 5, kWsBss = 6, kWsKinds = 7 };
-std::map<void*, Workspace> g_ws[kWsKinds][kMaxDevices];
+enum class Ws { Slices, Stoi, SiSdr, SegSnr, Llr, Wss, Bss, Kinds };
+std::map<void*, Workspace> g_ws[(int)Ws::Kinds][kMaxDevices];
 std::mutex g_mu;
 
-int workspace(int device, void* stream, size_t bytes, double** out, int which = kWsSlices) {
+int workspace(int device, void* stream, Ws which, size_t bytes, double** out) {
   std::lock_guard<std::mutex> lk(g_mu);
-  Workspace& w = g_ws[which][device][stream];
+  Workspace& w = g_ws[(int)which][device][stream];
   if (w.bytes < bytes) {
     if (w.p) {
       HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));   // an earlier call may still read it
@@ -44,6 +45,56 @@ int workspace(int device, void* stream, size_t bytes, double** out, int which = 
   *out = w.p;
   return RCED_OK;
 }
+
+size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// An entry's workspace, carved: take() books `count` elements of T at the next 256-byte boundary, in the order of the calls;
+// bind() gets the whole from workspace() and points every booked pointer at its part.  At most 8 buffers.
+struct Carve {
+  void* slot[8];
+  size_t at[8], bytes = 0;
+  int n = 0;
+  template <class T>
+  void take(T** p, size_t count) {
+    assert(n < 8);
+    slot[n] = p;
+    at[n++] = bytes;
+    bytes += align256(count * sizeof(T));
+  }
+  int bind(int device, void* stream, Ws which) {
+    double* base = nullptr;
+    if (int rc = workspace(device, stream, which, bytes, &base)) return rc;
+    for (int i = 0; i < n; ++i) {
+      char* p = reinterpret_cast<char*>(base) + at[i];
+      memcpy(slot[i], &p, sizeof p);
+    }
+    return RCED_OK;
+  }
+};
+
+// Two padded row matrices scored pair by pair, row n of `ref` against row n of `est`: what every score's entry takes first
+struct Pairs {
+  const float* ref;
+  int ref_stride;
+  const float* est;
+  int est_stride, N;
+  int cap() const { return ref_stride < est_stride ? ref_stride : est_stride; }   // the samples every row holds in both
+};
+
+// what every pair-scoring entry refuses; `outputs`: the results it was asked for have somewhere to go
+int check_pairs(const Pairs& p, bool outputs, int max_len, const char* max_text) {
+  if (p.N < 0 || p.ref_stride < 0 || p.est_stride < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
+  if (!p.ref || !p.est || !outputs) return rced_fail(RCED_ERR_ARG, "null pointer");
+  if (p.N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
+  if (p.cap() > max_len) return rced_fail(RCED_ERR_ARG, "rows longer than %s samples", max_text);
+  return RCED_OK;
+}
+
+#define LAUNCH(kernel, grid, block, lds, st, ...)                         \
+  do {                                                                    \
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, __VA_ARGS__);        \
+    HIP_TRY(hipGetLastError());                                           \
+  } while (0)
 
 // ---- STOI tables: built on the host once per process, uploaded once per device ---------------------------------------------------
 struct StoiTables {
@@ -122,8 +173,6 @@ int stoi_tables(int device, StoiTables** out) {
   return RCED_OK;
 }
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // ---- WSS tables: built on the host in fp64 once per process and rate, uploaded once per device -----------------------------------
 struct WssTables {
   double* coef = nullptr;            // the DFT's cos / -sin columns in MFMA fragment order (sepm::wss_coef_len)
@@ -199,15 +248,10 @@ int wss_tables(int device, int fs, WssTables** out) {
 }
 
 // what rced_llr and rced_wss check alike; *nfcap = the frames of the longest utterance the strides allow, at least 1
-int sepm_args(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, int N, int fs, const double* out_dev,
-              const double* frames_out, int frames_stride, int* cap, int* nfcap) {
-  if (N < 0 || ref_stride < 0 || est_stride < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
-  if (!ref_dev || !est_dev || !out_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
+int sepm_args(const Pairs& p, int fs, const double* out_dev, const double* frames_out, int frames_stride, int* nfcap) {
   if (fs != 8000 && fs != 16000) return rced_fail(RCED_ERR_ARG, "sample_rate must be 8000 or 16000, got %d", fs);
-  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
-  *cap = ref_stride < est_stride ? ref_stride : est_stride;
-  if (*cap > eval::kMaxLen) return rced_fail(RCED_ERR_ARG, "rows longer than 2^30 samples");
-  const int most = eval::seg_frames(*cap, eval::seg_window(fs));
+  if (int rc = check_pairs(p, out_dev, eval::kMaxLen, "2^30")) return rc;
+  const int most = eval::seg_frames(p.cap(), eval::seg_window(fs));
   if (frames_out && frames_stride < most)
     return rced_fail(RCED_ERR_ARG, "frames_stride %d < %d, the frames of an utterance as long as the rows", frames_stride, most);
   *nfcap = most > 0 ? most : 1;
@@ -217,12 +261,10 @@ int sepm_args(const float* ref_dev, int ref_stride, const float* est_dev, int es
 // rank every frame value inside its utterance, then the mean of the lowest 95 %
 int lowest_mean(const double* d, double* sorted, const int* lengths_dev, int N, int cap, int W, int nfcap, double* out_dev,
                 int* nf_out, hipStream_t st) {
-  hipLaunchKernelGGL(sepm::rank_kernel, dim3((nfcap + sepm::kThreads - 1) / sepm::kThreads, N), dim3(sepm::kThreads), 0, st, d,
-                     lengths_dev, cap, W, nfcap, sorted);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(sepm::lowest_mean_kernel, dim3(N), dim3(sepm::kThreads), 0, st, (const double*)sorted, lengths_dev, cap, W, nfcap,
-                     out_dev, nf_out);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(sepm::rank_kernel, dim3((nfcap + sepm::kThreads - 1) / sepm::kThreads, N), dim3(sepm::kThreads), 0, st, d, lengths_dev, cap, W,
+         nfcap, sorted);
+  LAUNCH(sepm::lowest_mean_kernel, dim3(N), dim3(sepm::kThreads), 0, st, (const double*)sorted, lengths_dev, cap, W, nfcap, out_dev,
+         nf_out);
   return RCED_OK;
 }
 
@@ -232,77 +274,57 @@ extern "C" {
 
 int rced_stoi_ex(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N, int fs_sig,
                  int which, double* stoi_dev, double* estoi_dev, int* detail_dev, int device, void* stream) {
-  if (N < 0 || ref_stride < 0 || est_stride < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
   if (which <= 0 || (which & ~(RCED_STOI_CLASSIC | RCED_STOI_EXTENDED)))
     return rced_fail(RCED_ERR_ARG, "which must be RCED_STOI_CLASSIC, RCED_STOI_EXTENDED or both, got %d", which);
   const bool classic = which & RCED_STOI_CLASSIC, extended = which & RCED_STOI_EXTENDED;
-  if (!ref_dev || !est_dev || (classic && !stoi_dev) || (extended && !estoi_dev)) return rced_fail(RCED_ERR_ARG, "null pointer");
   if (fs_sig != 8000 && fs_sig != stoi::kFs) return rced_fail(RCED_ERR_ARG, "fs_sig must be 8000 or 10000, got %d", fs_sig);
-  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
-  const int cap = ref_stride < est_stride ? ref_stride : est_stride;
-  if (cap > stoi::kMaxLen) return rced_fail(RCED_ERR_ARG, "rows longer than 2^28 samples");
+  const Pairs p{ref_dev, ref_stride, est_dev, est_stride, N};
+  if (int rc = check_pairs(p, (!classic || stoi_dev) && (!extended || estoi_dev), stoi::kMaxLen, "2^28")) return rc;
   if (N == 0) return RCED_OK;
-  if (int rc = check_device(device, kMaxDevices)) return rc;
-  DeviceGuard g(device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  OnDevice on(device, kMaxDevices);
+  if (on.rc) return on.rc;
   StoiTables* t = nullptr;
   if (int rc = stoi_tables(device, &t)) return rc;
-  // workspace: r [N][2][rstride] f64 | e [N][fcap] f64 | tob [N][2][fcap][16] f64 | dseg [2][N][mcap] f64 (classic, extended) |
-  // kept [N][fcap] i32 | cnt [N][4] i32 -- one layout whatever `which` asks for: a shape's size never depends on it
-  const int l10 = stoi::len10k(cap, fs_sig);
+  const int cap = p.cap(), l10 = stoi::len10k(cap, fs_sig);
   const int fcap = stoi::num_frames(l10) > 0 ? stoi::num_frames(l10) : 1;
   const int mcap = fcap > stoi::kSeg ? fcap - stoi::kSeg : 1;
   const int rstride = (l10 + 1) & ~1;
-  const size_t o_r = 0, o_e = o_r + align256((size_t)N * 2 * rstride * 8), o_tob = o_e + align256((size_t)N * fcap * 8),
-               o_d = o_tob + align256((size_t)N * 2 * fcap * 16 * 8), o_kept = o_d + 2 * align256((size_t)N * mcap * 8),
-               o_cnt = o_kept + align256((size_t)N * fcap * 4), total = o_cnt + align256((size_t)N * 4 * 4);
-  double* ws = nullptr;
-  if (int rc = workspace(device, stream, total, &ws, kWsStoi)) return rc;
-  char* base = reinterpret_cast<char*>(ws);
-  double* r = reinterpret_cast<double*>(base + o_r);
-  double* e = reinterpret_cast<double*>(base + o_e);
-  double* tob = reinterpret_cast<double*>(base + o_tob);
-  double* dseg = reinterpret_cast<double*>(base + o_d);
-  double* dseg_ext = reinterpret_cast<double*>(base + o_d + align256((size_t)N * mcap * 8));
-  int* kept = reinterpret_cast<int*>(base + o_kept);
-  int* cnt = reinterpret_cast<int*>(base + o_cnt);
+  // one layout whatever `which` asks for: a shape's size never depends on it
+  double *r, *e, *tob, *dseg, *dseg_ext;
+  int *kept, *cnt;
+  Carve ws;
+  ws.take(&r, (size_t)N * 2 * rstride);
+  ws.take(&e, (size_t)N * fcap);
+  ws.take(&tob, (size_t)N * 2 * fcap * 16);
+  ws.take(&dseg, (size_t)N * mcap);          // classic
+  ws.take(&dseg_ext, (size_t)N * mcap);      // extended
+  ws.take(&kept, (size_t)N * fcap);
+  ws.take(&cnt, (size_t)N * 4);
+  if (int rc = ws.bind(device, stream, Ws::Stoi)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (l10 > 0) {
-    hipLaunchKernelGGL(stoi::resample_kernel, dim3((l10 + 255) / 256, 2, N), dim3(256), 0, st, ref_dev, ref_stride, est_dev,
-                       est_stride, lengths_dev, cap, fs_sig, (const double*)t->tab, r, rstride);
-    HIP_TRY(hipGetLastError());
-  }
-  hipLaunchKernelGGL(stoi::energy_kernel, dim3((fcap + 3) / 4, N), dim3(256), 0, st, (const double*)r, rstride, lengths_dev, cap,
-                     fs_sig, (const double*)t->tab, e, fcap);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(stoi::mask_kernel, dim3(N), dim3(64), 0, st, (const double*)e, lengths_dev, cap, fs_sig, fcap, kept, cnt);
-  HIP_TRY(hipGetLastError());
+  if (l10 > 0)
+    LAUNCH(stoi::resample_kernel, dim3((l10 + 255) / 256, 2, N), dim3(256), 0, st, ref_dev, ref_stride, est_dev, est_stride, lengths_dev,
+           cap, fs_sig, (const double*)t->tab, r, rstride);
+  LAUNCH(stoi::energy_kernel, dim3((fcap + 3) / 4, N), dim3(256), 0, st, (const double*)r, rstride, lengths_dev, cap, fs_sig,
+         (const double*)t->tab, e, fcap);
+  LAUNCH(stoi::mask_kernel, dim3(N), dim3(64), 0, st, (const double*)e, lengths_dev, cap, fs_sig, fcap, kept, cnt);
   if (fcap - 1 >= stoi::kSeg) {
-    hipLaunchKernelGGL(stoi::band_kernel, dim3((fcap - 1 + stoi::kBlockFrames - 1) / stoi::kBlockFrames, 2, N), dim3(stoi::kThreads),
-                       stoi::kBandLdsBytes, st, (const double*)r, rstride, (const int*)kept, (const int*)cnt, fcap,
-                       (const unsigned short*)t->apack, (const double*)t->tab, tob);
-    HIP_TRY(hipGetLastError());
-    if (classic) {
-      hipLaunchKernelGGL(stoi::segment_kernel, dim3((mcap + 15) / 16, N), dim3(256), 0, st, (const double*)tob, (const int*)cnt, fcap,
-                         mcap, 1.0 + std::pow(10.0, 15.0 / 20.0), dseg);
-      HIP_TRY(hipGetLastError());
-    }
-    if (extended) {
-      hipLaunchKernelGGL(stoi::segment_ext_kernel, dim3((mcap + 15) / 16, N), dim3(256), 0, st, (const double*)tob, (const int*)cnt,
-                         fcap, mcap, dseg_ext);
-      HIP_TRY(hipGetLastError());
-    }
+    LAUNCH(stoi::band_kernel, dim3((fcap - 1 + stoi::kBlockFrames - 1) / stoi::kBlockFrames, 2, N), dim3(stoi::kThreads),
+           stoi::kBandLdsBytes, st, (const double*)r, rstride, (const int*)kept, (const int*)cnt, fcap, (const unsigned short*)t->apack,
+           (const double*)t->tab, tob);
+    if (classic)
+      LAUNCH(stoi::segment_kernel, dim3((mcap + 15) / 16, N), dim3(256), 0, st, (const double*)tob, (const int*)cnt, fcap, mcap,
+             1.0 + std::pow(10.0, 15.0 / 20.0), dseg);
+    if (extended)
+      LAUNCH(stoi::segment_ext_kernel, dim3((mcap + 15) / 16, N), dim3(256), 0, st, (const double*)tob, (const int*)cnt, fcap, mcap,
+             dseg_ext);
   }
-  if (classic) {
-    hipLaunchKernelGGL(stoi::final_kernel, dim3(N), dim3(256), 0, st, (const double*)dseg, (const int*)cnt, mcap, (double)stoi::kBands,
-                       stoi_dev, detail_dev);
-    HIP_TRY(hipGetLastError());
-  }
-  if (extended) {
-    hipLaunchKernelGGL(stoi::final_kernel, dim3(N), dim3(256), 0, st, (const double*)dseg_ext, (const int*)cnt, mcap, (double)stoi::kSeg,
-                       estoi_dev, classic ? nullptr : detail_dev);
-    HIP_TRY(hipGetLastError());
-  }
+  if (classic)
+    LAUNCH(stoi::final_kernel, dim3(N), dim3(256), 0, st, (const double*)dseg, (const int*)cnt, mcap, (double)stoi::kBands, stoi_dev,
+           detail_dev);
+  if (extended)
+    LAUNCH(stoi::final_kernel, dim3(N), dim3(256), 0, st, (const double*)dseg_ext, (const int*)cnt, mcap, (double)stoi::kSeg, estoi_dev,
+           classic ? nullptr : detail_dev);
   return RCED_OK;
 }
 
@@ -314,191 +336,149 @@ int rced_stoi(const float* ref_dev, int ref_stride, const float* est_dev, int es
 
 int rced_si_sdr(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N,
                 double* out_dev, double* parts_dev, int device, void* stream) {
-  if (N < 0 || ref_stride < 0 || est_stride < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
-  if (!ref_dev || !est_dev || !out_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
-  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
-  const int cap = ref_stride < est_stride ? ref_stride : est_stride;
-  if (cap > eval::kMaxLen) return rced_fail(RCED_ERR_ARG, "rows longer than 2^30 samples");
+  const Pairs p{ref_dev, ref_stride, est_dev, est_stride, N};
+  if (int rc = check_pairs(p, out_dev, eval::kMaxLen, "2^30")) return rc;
   if (N == 0) return RCED_OK;
-  if (int rc = check_device(device, kMaxDevices)) return rc;
-  DeviceGuard g(device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
-  const int slices = eval::num_slices(cap) > 0 ? eval::num_slices(cap) : 1;
-  const size_t pass = (size_t)N * slices * 2;            // doubles per pass: [N, slices, 2]
+  OnDevice on(device, kMaxDevices);
+  if (on.rc) return on.rc;
+  const int cap = p.cap(), slices = eval::num_slices(cap) > 0 ? eval::num_slices(cap) : 1;
+  const size_t pass = (size_t)N * slices * 2;            // doubles per pass: [N, slices, 2]; the two passes lie back to back, unpadded
   double* ws1 = nullptr;
-  if (int rc = workspace(device, stream, 2 * pass * sizeof(double), &ws1, kWsSiSdr)) return rc;
+  if (int rc = workspace(device, stream, Ws::SiSdr, 2 * pass * sizeof(double), &ws1)) return rc;
   double* ws2 = ws1 + pass;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(eval::si_sdr_dot_kernel, dim3(slices, N), dim3(eval::kThreads), 0, st, ref_dev, ref_stride, est_dev, est_stride,
-                     lengths_dev, cap, ws1, slices);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(eval::si_sdr_energy_kernel, dim3(slices, N), dim3(eval::kThreads), 0, st, ref_dev, ref_stride, est_dev,
-                     est_stride, lengths_dev, cap, (const double*)ws1, ws2, slices);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(eval::si_sdr_final_kernel, dim3(N), dim3(eval::kThreads), 0, st, (const double*)ws1, (const double*)ws2,
-                     lengths_dev, cap, slices, out_dev, parts_dev);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(eval::si_sdr_dot_kernel, dim3(slices, N), dim3(eval::kThreads), 0, st, ref_dev, ref_stride, est_dev, est_stride, lengths_dev,
+         cap, ws1, slices);
+  LAUNCH(eval::si_sdr_energy_kernel, dim3(slices, N), dim3(eval::kThreads), 0, st, ref_dev, ref_stride, est_dev, est_stride,
+         lengths_dev, cap, (const double*)ws1, ws2, slices);
+  LAUNCH(eval::si_sdr_final_kernel, dim3(N), dim3(eval::kThreads), 0, st, (const double*)ws1, (const double*)ws2, lengths_dev, cap,
+         slices, out_dev, parts_dev);
   return RCED_OK;
 }
 
 int rced_seg_snr(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N, int fs,
                  double* out_dev, int* frames_dev, int device, void* stream) {
-  if (N < 0 || ref_stride < 0 || est_stride < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
-  if (!ref_dev || !est_dev || !out_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
   const int W = fs > 0 ? eval::seg_window(fs) : 0;
   if (W < eval::kSegMinW || W > eval::kSegMaxW)
     return rced_fail(RCED_ERR_ARG, "fs = %d gives frames of %d samples: outside [%d, %d]", fs, W, eval::kSegMinW, eval::kSegMaxW);
-  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
-  const int cap = ref_stride < est_stride ? ref_stride : est_stride;
-  if (cap > eval::kMaxLen) return rced_fail(RCED_ERR_ARG, "rows longer than 2^30 samples");
+  const Pairs p{ref_dev, ref_stride, est_dev, est_stride, N};
+  if (int rc = check_pairs(p, out_dev, eval::kMaxLen, "2^30")) return rc;
   if (N == 0) return RCED_OK;
-  if (int rc = check_device(device, kMaxDevices)) return rc;
-  DeviceGuard g(device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
-  const int nfcap = eval::seg_frames(cap, W) > 0 ? eval::seg_frames(cap, W) : 1;
+  OnDevice on(device, kMaxDevices);
+  if (on.rc) return on.rc;
+  const int cap = p.cap(), nfcap = eval::seg_frames(cap, W) > 0 ? eval::seg_frames(cap, W) : 1;
   const int blocks = (nfcap + eval::kSegFramesPerBlock - 1) / eval::kSegFramesPerBlock;
   double* snr = nullptr;
-  if (int rc = workspace(device, stream, (size_t)N * nfcap * sizeof(double), &snr, kWsSegSnr)) return rc;
+  if (int rc = workspace(device, stream, Ws::SegSnr, (size_t)N * nfcap * sizeof(double), &snr)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(eval::seg_snr_frame_kernel, dim3(blocks, N), dim3(eval::kThreads), 0, st, ref_dev, ref_stride, est_dev,
-                     est_stride, lengths_dev, cap, W, snr, nfcap);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(eval::seg_snr_mean_kernel, dim3(N), dim3(eval::kThreads), 0, st, (const double*)snr, lengths_dev, cap, W, nfcap,
-                     out_dev, frames_dev);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(eval::seg_snr_frame_kernel, dim3(blocks, N), dim3(eval::kThreads), 0, st, ref_dev, ref_stride, est_dev, est_stride,
+         lengths_dev, cap, W, snr, nfcap);
+  LAUNCH(eval::seg_snr_mean_kernel, dim3(N), dim3(eval::kThreads), 0, st, (const double*)snr, lengths_dev, cap, W, nfcap, out_dev,
+         frames_dev);
   return RCED_OK;
 }
 
 int rced_llr(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N, int sample_rate,
              double limit, double* out_dev, double* frames_out, int frames_stride, int* nf_out, int device, void* stream) {
-  int cap = 0, nfcap = 0;
-  if (int rc = sepm_args(ref_dev, ref_stride, est_dev, est_stride, N, sample_rate, out_dev, frames_out, frames_stride, &cap, &nfcap))
-    return rc;
+  const Pairs p{ref_dev, ref_stride, est_dev, est_stride, N};
+  int nfcap = 0;
+  if (int rc = sepm_args(p, sample_rate, out_dev, frames_out, frames_stride, &nfcap)) return rc;
   if (limit != limit) return rced_fail(RCED_ERR_ARG, "limit is nan");
   if (N == 0) return RCED_OK;
-  if (int rc = check_device(device, kMaxDevices)) return rc;
-  DeviceGuard g(device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
-  const int W = eval::seg_window(sample_rate), P = sepm::lpc_order(sample_rate);
-  // workspace: R [N][nfcap][2][17] | d [N][nfcap] | sorted [N][nfcap]
-  const size_t o_d = align256((size_t)N * nfcap * 2 * sepm::kMaxLags * 8), o_s = o_d + align256((size_t)N * nfcap * 8),
-               total = o_s + align256((size_t)N * nfcap * 8);
-  double* ws = nullptr;
-  if (int rc = workspace(device, stream, total, &ws, kWsLlr)) return rc;
-  char* base = reinterpret_cast<char*>(ws);
-  double* d = reinterpret_cast<double*>(base + o_d);
-  double* sorted = reinterpret_cast<double*>(base + o_s);
+  OnDevice on(device, kMaxDevices);
+  if (on.rc) return on.rc;
+  const int cap = p.cap(), W = eval::seg_window(sample_rate), P = sepm::lpc_order(sample_rate);
+  double *lags, *d, *sorted;
+  Carve ws;
+  ws.take(&lags, (size_t)N * nfcap * 2 * sepm::kMaxLags);
+  ws.take(&d, (size_t)N * nfcap);
+  ws.take(&sorted, (size_t)N * nfcap);
+  if (int rc = ws.bind(device, stream, Ws::Llr)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(sepm::llr_frame_kernel, dim3((nfcap + sepm::kLlrFramesPerBlock - 1) / sepm::kLlrFramesPerBlock, N),
-                     dim3(sepm::kThreads), 0, st, ref_dev, ref_stride, est_dev, est_stride, lengths_dev, cap, W, P, ws, nfcap);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(sepm::llr_frame_kernel, dim3((nfcap + sepm::kLlrFramesPerBlock - 1) / sepm::kLlrFramesPerBlock, N), dim3(sepm::kThreads), 0, st,
+         ref_dev, ref_stride, est_dev, est_stride, lengths_dev, cap, W, P, lags, nfcap);
   const dim3 per_frame((nfcap + sepm::kThreads - 1) / sepm::kThreads, N);
   if (P == 10)
-    hipLaunchKernelGGL(sepm::llr_recursion_kernel<10>, per_frame, dim3(sepm::kThreads), 0, st, (const double*)ws, lengths_dev, cap, W,
-                       nfcap, limit, d, frames_out, frames_stride);
+    LAUNCH(sepm::llr_recursion_kernel<10>, per_frame, dim3(sepm::kThreads), 0, st, (const double*)lags, lengths_dev, cap, W, nfcap, limit,
+           d, frames_out, frames_stride);
   else
-    hipLaunchKernelGGL(sepm::llr_recursion_kernel<16>, per_frame, dim3(sepm::kThreads), 0, st, (const double*)ws, lengths_dev, cap, W,
-                       nfcap, limit, d, frames_out, frames_stride);
-  HIP_TRY(hipGetLastError());
+    LAUNCH(sepm::llr_recursion_kernel<16>, per_frame, dim3(sepm::kThreads), 0, st, (const double*)lags, lengths_dev, cap, W, nfcap, limit,
+           d, frames_out, frames_stride);
   return lowest_mean(d, sorted, lengths_dev, N, cap, W, nfcap, out_dev, nf_out, st);
 }
 
 int rced_wss(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N, int sample_rate,
              double* out_dev, double* frames_out, int frames_stride, int* nf_out, int device, void* stream) {
-  int cap = 0, nfcap = 0;
-  if (int rc = sepm_args(ref_dev, ref_stride, est_dev, est_stride, N, sample_rate, out_dev, frames_out, frames_stride, &cap, &nfcap))
-    return rc;
+  const Pairs p{ref_dev, ref_stride, est_dev, est_stride, N};
+  int nfcap = 0;
+  if (int rc = sepm_args(p, sample_rate, out_dev, frames_out, frames_stride, &nfcap)) return rc;
   if (N == 0) return RCED_OK;
-  if (int rc = check_device(device, kMaxDevices)) return rc;
-  DeviceGuard g(device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  OnDevice on(device, kMaxDevices);
+  if (on.rc) return on.rc;
   WssTables* t = nullptr;
   if (int rc = wss_tables(device, sample_rate, &t)) return rc;
-  const int W = eval::seg_window(sample_rate);
-  // workspace: energy [N][2][nfcap][25] | d [N][nfcap] | sorted [N][nfcap]
-  const size_t o_d = align256((size_t)N * 2 * nfcap * sepm::kBands * 8), o_s = o_d + align256((size_t)N * nfcap * 8),
-               total = o_s + align256((size_t)N * nfcap * 8);
-  double* ws = nullptr;
-  if (int rc = workspace(device, stream, total, &ws, kWsWss)) return rc;
-  char* base = reinterpret_cast<char*>(ws);
-  double* d = reinterpret_cast<double*>(base + o_d);
-  double* sorted = reinterpret_cast<double*>(base + o_s);
+  const int cap = p.cap(), W = eval::seg_window(sample_rate);
+  double *energy, *d, *sorted;
+  Carve ws;
+  ws.take(&energy, (size_t)N * 2 * nfcap * sepm::kBands);
+  ws.take(&d, (size_t)N * nfcap);
+  ws.take(&sorted, (size_t)N * nfcap);
+  if (int rc = ws.bind(device, stream, Ws::Wss)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (W == sepm::kMaxW)           // 16 kHz: 16 frames of 480 samples fill the LDS; 8 kHz: 32 frames of 240
-    hipLaunchKernelGGL(sepm::wss_spectrum_kernel<1>, dim3((nfcap + 15) / 16, 2, N), dim3(sepm::kThreads), sepm::wss_lds_bytes(W, 1), st,
-                       ref_dev, ref_stride, est_dev, est_stride, lengths_dev, cap, W, (const double*)t->coef, (const double*)t->filt,
-                       (const int*)t->range, ws, nfcap);
+    LAUNCH(sepm::wss_spectrum_kernel<1>, dim3((nfcap + 15) / 16, 2, N), dim3(sepm::kThreads), sepm::wss_lds_bytes(W, 1), st, ref_dev,
+           ref_stride, est_dev, est_stride, lengths_dev, cap, W, (const double*)t->coef, (const double*)t->filt, (const int*)t->range,
+           energy, nfcap);
   else
-    hipLaunchKernelGGL(sepm::wss_spectrum_kernel<2>, dim3((nfcap + 31) / 32, 2, N), dim3(sepm::kThreads), sepm::wss_lds_bytes(W, 2), st,
-                       ref_dev, ref_stride, est_dev, est_stride, lengths_dev, cap, W, (const double*)t->coef, (const double*)t->filt,
-                       (const int*)t->range, ws, nfcap);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(sepm::wss_slope_kernel, dim3((nfcap + sepm::kThreads - 1) / sepm::kThreads, N), dim3(sepm::kThreads), 0, st,
-                     (const double*)ws, lengths_dev, cap, W, nfcap, d, frames_out, frames_stride);
-  HIP_TRY(hipGetLastError());
+    LAUNCH(sepm::wss_spectrum_kernel<2>, dim3((nfcap + 31) / 32, 2, N), dim3(sepm::kThreads), sepm::wss_lds_bytes(W, 2), st, ref_dev,
+           ref_stride, est_dev, est_stride, lengths_dev, cap, W, (const double*)t->coef, (const double*)t->filt, (const int*)t->range,
+           energy, nfcap);
+  LAUNCH(sepm::wss_slope_kernel, dim3((nfcap + sepm::kThreads - 1) / sepm::kThreads, N), dim3(sepm::kThreads), 0, st,
+         (const double*)energy, lengths_dev, cap, W, nfcap, d, frames_out, frames_stride);
   return lowest_mean(d, sorted, lengths_dev, N, cap, W, nfcap, out_dev, nf_out, st);
 }
 
 int rced_bss_sdr(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N,
                  int filter_length, double* sdr_dev, double* filter_dev, double* energies_dev, int device, void* stream) {
-  if (N < 0 || ref_stride < 0 || est_stride < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
-  if (!ref_dev || !est_dev || !sdr_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
-  if (filter_length < 1 || filter_length > bss::kMaxTaps)
-    return rced_fail(RCED_ERR_ARG, "filter_length must lie in [1, %d], got %d", bss::kMaxTaps, filter_length);
-  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
-  const int cap = ref_stride < est_stride ? ref_stride : est_stride;
-  if (cap > eval::kMaxLen) return rced_fail(RCED_ERR_ARG, "rows longer than 2^30 samples");
-  if (N == 0) return RCED_OK;
-  if (int rc = check_device(device, kMaxDevices)) return rc;
-  DeviceGuard g(device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
   const int F = filter_length;
-  const int slices = bss::corr_slices(cap) > 0 ? bss::corr_slices(cap) : 1;
+  if (F < 1 || F > bss::kMaxTaps) return rced_fail(RCED_ERR_ARG, "filter_length must lie in [1, %d], got %d", bss::kMaxTaps, F);
+  const Pairs p{ref_dev, ref_stride, est_dev, est_stride, N};
+  if (int rc = check_pairs(p, sdr_dev, eval::kMaxLen, "2^30")) return rc;
+  if (N == 0) return RCED_OK;
+  OnDevice on(device, kMaxDevices);
+  if (on.rc) return on.rc;
+  const int cap = p.cap(), slices = bss::corr_slices(cap) > 0 ? bss::corr_slices(cap) : 1;
   const int pslices = bss::out_slices(cap, F) > 0 ? bss::out_slices(cap, F) : 1;
-  // workspace: part [N][2][slices][F] | c [N][F] | energies [N][pslices][2]
-  const size_t o_c = align256((size_t)N * 2 * slices * F * 8), o_p = o_c + align256((size_t)N * F * 8),
-               total = o_p + align256((size_t)N * pslices * 2 * 8);
-  double* ws = nullptr;
-  if (int rc = workspace(device, stream, total, &ws, kWsBss)) return rc;
-  char* base = reinterpret_cast<char*>(ws);
-  double* c = reinterpret_cast<double*>(base + o_c);
-  double* pws = reinterpret_cast<double*>(base + o_p);
+  double *part, *c, *pws;
+  Carve ws;
+  ws.take(&part, (size_t)N * 2 * slices * F);
+  ws.take(&c, (size_t)N * F);
+  ws.take(&pws, (size_t)N * pslices * 2);
+  if (int rc = ws.bind(device, stream, Ws::Bss)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(bss::correlate_kernel, dim3(slices, 2, N), dim3(bss::kThreads), 0, st, ref_dev, ref_stride, est_dev, est_stride,
-                     lengths_dev, cap, F, ws, slices);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(bss::solve_kernel, dim3(N), dim3(64), 0, st, (const double*)ws, lengths_dev, cap, F, slices, c, filter_dev);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(bss::project_kernel, dim3(pslices, N), dim3(bss::kThreads), 0, st, ref_dev, ref_stride, est_dev, est_stride,
-                     lengths_dev, cap, F, (const double*)c, pws, pslices);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(bss::final_kernel, dim3(N), dim3(64), 0, st, (const double*)pws, lengths_dev, cap, F, pslices, sdr_dev,
-                     energies_dev);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(bss::correlate_kernel, dim3(slices, 2, N), dim3(bss::kThreads), 0, st, ref_dev, ref_stride, est_dev, est_stride, lengths_dev,
+         cap, F, part, slices);
+  LAUNCH(bss::solve_kernel, dim3(N), dim3(64), 0, st, (const double*)part, lengths_dev, cap, F, slices, c, filter_dev);
+  LAUNCH(bss::project_kernel, dim3(pslices, N), dim3(bss::kThreads), 0, st, ref_dev, ref_stride, est_dev, est_stride, lengths_dev, cap,
+         F, (const double*)c, pws, pslices);
+  LAUNCH(bss::final_kernel, dim3(N), dim3(64), 0, st, (const double*)pws, lengths_dev, cap, F, pslices, sdr_dev, energies_dev);
   return RCED_OK;
 }
 
 int rced_sdr(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N,
              double* sdr_dev, double* energies_dev, int device, void* stream) {
-  if (N < 0 || ref_stride < 0 || est_stride < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
-  if (!ref_dev || !est_dev || !sdr_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
-  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
-  const int cap = ref_stride < est_stride ? ref_stride : est_stride;
-  if (cap > eval::kMaxLen) return rced_fail(RCED_ERR_ARG, "rows longer than 2^30 samples");
+  const Pairs p{ref_dev, ref_stride, est_dev, est_stride, N};
+  if (int rc = check_pairs(p, sdr_dev, eval::kMaxLen, "2^30")) return rc;
   if (N == 0) return RCED_OK;
-  if (int rc = check_device(device, kMaxDevices)) return rc;
-  DeviceGuard g(device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
-  const int slices = eval::num_slices(cap) > 0 ? eval::num_slices(cap) : 1;
+  OnDevice on(device, kMaxDevices);
+  if (on.rc) return on.rc;
+  const int cap = p.cap(), slices = eval::num_slices(cap) > 0 ? eval::num_slices(cap) : 1;
   double* ws = nullptr;
-  if (int rc = workspace(device, stream, (size_t)N * slices * 2 * sizeof(double), &ws)) return rc;
+  if (int rc = workspace(device, stream, Ws::Slices, (size_t)N * slices * 2 * sizeof(double), &ws)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(eval::sdr_partial_kernel, dim3(slices, N), dim3(eval::kThreads), 0, st, ref_dev, ref_stride, est_dev,
-                     est_stride, lengths_dev, cap, ws, slices);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(eval::sdr_final_kernel, dim3(N), dim3(64), 0, st, (const double*)ws, lengths_dev, cap, slices, sdr_dev,
-                     energies_dev);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(eval::sdr_partial_kernel, dim3(slices, N), dim3(eval::kThreads), 0, st, ref_dev, ref_stride, est_dev, est_stride, lengths_dev,
+         cap, ws, slices);
+  LAUNCH(eval::sdr_final_kernel, dim3(N), dim3(64), 0, st, (const double*)ws, lengths_dev, cap, slices, sdr_dev, energies_dev);
   return RCED_OK;
 }
 
@@ -512,20 +492,16 @@ int rced_mix_snr(const float* speech_dev, const int* speech_len_dev, int N, int 
   if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
   if (Ls > eval::kMaxLen || Ln > eval::kMaxLen) return rced_fail(RCED_ERR_ARG, "rows longer than 2^30 samples");
   if (N == 0 || Ls == 0) return RCED_OK;
-  if (int rc = check_device(device, kMaxDevices)) return rc;
-  DeviceGuard g(device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  OnDevice on(device, kMaxDevices);
+  if (on.rc) return on.rc;
   const int slices = eval::num_slices(Ls);
   double* ws = nullptr;
-  if (int rc = workspace(device, stream, (size_t)N * slices * 2 * sizeof(double), &ws)) return rc;
+  if (int rc = workspace(device, stream, Ws::Slices, (size_t)N * slices * 2 * sizeof(double), &ws)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(eval::mix_partial_kernel, dim3(slices, N), dim3(eval::kThreads), 0, st, speech_dev, speech_len_dev, Ls,
-                     noise_dev, noise_len_dev, Ln, start_dev, gains_dev, n_gains, ws, slices);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(eval::mix_apply_kernel, dim3(slices, N), dim3(eval::kThreads), 0, st, speech_dev, speech_len_dev, Ls,
-                     noise_dev, noise_len_dev, Ln, start_dev, gains_dev, n_gains, (const double*)ws, slices,
-                     std::pow(10.0, snr_db / 10.0), mix_dev);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(eval::mix_partial_kernel, dim3(slices, N), dim3(eval::kThreads), 0, st, speech_dev, speech_len_dev, Ls, noise_dev,
+         noise_len_dev, Ln, start_dev, gains_dev, n_gains, ws, slices);
+  LAUNCH(eval::mix_apply_kernel, dim3(slices, N), dim3(eval::kThreads), 0, st, speech_dev, speech_len_dev, Ls, noise_dev, noise_len_dev,
+         Ln, start_dev, gains_dev, n_gains, (const double*)ws, slices, std::pow(10.0, snr_db / 10.0), mix_dev);
   return RCED_OK;
 }
 
@@ -540,19 +516,15 @@ int rced_gather_pcm(const void* arena_dev, int arena_dtype, long long arena_samp
   if (N == 0 || L == 0) return RCED_OK;
   if (!begin_dev || !count_dev || !rows_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
   if (!arena_dev && arena_samples > 0) return rced_fail(RCED_ERR_ARG, "null arena of %lld samples", arena_samples);
-  if (int rc = check_device(device, kMaxDevices)) return rc;
-  DeviceGuard g(device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  OnDevice on(device, kMaxDevices);
+  if (on.rc) return on.rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid(eval::num_slices(L), N), block(eval::kThreads);
   static_assert(eval::kSlice == eval::kThreads * eval::kGatherPerLane, "a column block of the gather is one slice");
   if (arena_dtype == RCED_PCM_F32)
-    hipLaunchKernelGGL(eval::gather_pcm_kernel<true>, grid, block, 0, st, arena_dev, arena_samples, begin_dev, count_dev, L, rows_dev,
-                       row_stride);
+    LAUNCH(eval::gather_pcm_kernel<true>, grid, block, 0, st, arena_dev, arena_samples, begin_dev, count_dev, L, rows_dev, row_stride);
   else
-    hipLaunchKernelGGL(eval::gather_pcm_kernel<false>, grid, block, 0, st, arena_dev, arena_samples, begin_dev, count_dev, L, rows_dev,
-                       row_stride);
-  HIP_TRY(hipGetLastError());
+    LAUNCH(eval::gather_pcm_kernel<false>, grid, block, 0, st, arena_dev, arena_samples, begin_dev, count_dev, L, rows_dev, row_stride);
   return RCED_OK;
 }
 

@@ -23,7 +23,9 @@ int rced_fail(int code, const char* fmt, ...);   // rced_api.hip: sets the threa
 struct DeviceGuard {  // run on the given device, restore the caller's current device after
   int prev = -1;
   bool ok = false;
-  explicit DeviceGuard(int dev) {
+  DeviceGuard() = default;            // idle until enter()
+  explicit DeviceGuard(int dev) { enter(dev); }
+  void enter(int dev) {
     if (hipGetDevice(&prev) != hipSuccess) { prev = -1; return; }
     ok = (prev == dev) || (hipSetDevice(dev) == hipSuccess);
   }
@@ -41,6 +43,17 @@ inline int check_device(int device, int limit = INT_MAX) {
   if (device < 0 || device >= n) return rced_fail(RCED_ERR_ARG, "device %d out of range [0,%d)", device, n);
   return RCED_OK;
 }
+
+// check_device, then a DeviceGuard for the rest of the scope: `OnDevice on(device, limit); if (on.rc) return on.rc;`
+struct OnDevice {
+  int rc;
+  DeviceGuard g;
+  explicit OnDevice(int device, int limit = INT_MAX) : rc(check_device(device, limit)) {
+    if (rc) return;
+    g.enter(device);
+    if (!g.ok) rc = rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  }
+};
 
 // A host vector as a fresh device allocation.  *dev is written only after the copy succeeded (a caller may test it for "built");
 // on failure the allocation is freed.

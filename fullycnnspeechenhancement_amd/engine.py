@@ -111,14 +111,7 @@ class FullyCNNTester(object):
         framing = loader_framing(valid_loader)
         for _batch_mix, _batch_clean, mix_sig, clean_sig in valid_loader:
             scores = self.evaluate_pcm(mix_sig, clean_sig, stoi=stoi, extra=extra, rebuild=rebuild, framing=framing)
-            for score in scores[1]:
-                self.sdr_score.update(float(score))
-            if stoi:
-                for score in scores[2]:
-                    self.stoi_score.update(float(score))
-            for name in extra:
-                for score in scores[-1][name]:
-                    self.extra_scores[name].update(float(score))
+            feed_meters(self, scores, stoi, extra)
         if stoi:
             print("Average st_score: {:.4f}; Average sd_score: {:.4f}.\n".format(self.stoi_score.avg, self.sdr_score.avg))
         else:
@@ -126,6 +119,19 @@ class FullyCNNTester(object):
         if extra:
             print(extra_line(extra, self.extra_scores))
         return self.sdr_score.avg
+
+
+def feed_meters(owner, scores, stoi, extra):
+    """One batch's scores, as evaluate_pcm returns them, into the owner's sdr_score, stoi_score and extra_scores meters, utterance by
+    utterance: what test() and valid() do alike."""
+    for score in scores[1]:
+        owner.sdr_score.update(float(score))
+    if stoi:
+        for score in scores[2]:
+            owner.stoi_score.update(float(score))
+    for name in extra:
+        for score in scores[-1][name]:
+            owner.extra_scores[name].update(float(score))
 
 
 def extra_line(extra, meters):

@@ -5,7 +5,29 @@ every public name here."""
 import numpy as np
 
 from . import _args, _lib
-from ._args import SAMPLE_RATE
+from ._args import SAMPLE_RATE, ptr
+
+
+class _Pairs(object):
+    """What every pair-scoring *_batch goes through: scoring_args, the result `out` (float64 [N]), further [N, ...] tensors
+    from new(), and call(): the entry with the shared head (both matrices and their row strides, the lengths, N), the entry's own
+    arguments and the (device, stream) tail -- skipped for an empty batch.  cap: the samples a row holds in both matrices."""
+
+    def __init__(self, clean, estimate, lengths):
+        self.head = _args.scoring_args(clean, estimate, lengths)
+        self.n, self.dev, self.cap = self.head[2], self.head[3], min(self.head[4:6])
+        self.out = self.new()
+
+    def new(self, *tail, dtype="float64", zeros=False):
+        import torch
+        return (torch.zeros if zeros else torch.empty)((self.n,) + tail, dtype=getattr(torch, dtype), device=self.dev)
+
+    def call(self, entry, *middle):
+        clean, estimate, n, dev, sc, se, ldev = self.head
+        if n:
+            _lib.check(getattr(_lib.load(), entry)(clean.data_ptr(), sc, estimate.data_ptr(), se, ptr(ldev), n, *middle, dev.index,
+                                                   _args.current_stream(dev)))
+        return self.out
 
 
 def sdr_batch(clean, estimate, lengths=None):
@@ -13,13 +35,8 @@ def sdr_batch(clean, estimate, lengths=None):
     row n holding utterance n from column 0 (the estimate may be istft_batch's [N, (T+1)*128] buffer as it is: the length
     trims, nothing is copied); lengths: per-utterance sample counts in [0, min(Lc, Le)] or None (= min(Lc, Le) each).
     Returns torch.float64 [N] (dB) on the device, current stream."""
-    import torch
-    clean, estimate, n, dev, sc, se, ldev = _args.scoring_args(clean, estimate, lengths)
-    out = torch.empty((n,), dtype=torch.float64, device=dev)
-    if n:
-        _lib.check(_lib.load().rced_sdr(clean.data_ptr(), sc, estimate.data_ptr(), se, ldev.data_ptr() if ldev is not None else None,
-                                        n, out.data_ptr(), None, dev.index, _args.current_stream(dev)))
-    return out
+    p = _Pairs(clean, estimate, lengths)
+    return p.call("rced_sdr", p.out.data_ptr(), None)
 
 
 STOI_RATES = (8000, 10000)
@@ -34,26 +51,18 @@ def stoi_batch(clean, estimate, lengths=None, sample_rate=8000, detail=False, ex
     Returns torch.float64 [N] on the device, current stream (two of them for "both"); with detail=True also, last,
     torch.int32 [N, 3]: frames at 10 kHz, frames kept by the 40 dB silent-frame removal, 30-frame segments (0 segments: the
     score is 1e-5)."""
-    import torch
     if int(sample_rate) not in STOI_RATES:
         raise ValueError("sample_rate must be 8000 or 10000, got %r" % (sample_rate,))
     if not (extended is False or extended is True or extended == "both"):
         raise ValueError("extended must be False, True or 'both', got %r" % (extended,))
-    clean, estimate, n, dev, sc, se, ldev = _args.scoring_args(clean, estimate, lengths)
-    det = torch.empty((n, 3), dtype=torch.int32, device=dev) if detail else None
-    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+    p = _Pairs(clean, estimate, lengths)
+    det = p.new(3, dtype="int32") if detail else None
     if extended is False:
-        out = torch.empty((n,), dtype=torch.float64, device=dev)
-        if n:
-            _lib.check(_lib.load().rced_stoi(clean.data_ptr(), sc, estimate.data_ptr(), se, ptr(ldev), n, int(sample_rate),
-                                             out.data_ptr(), ptr(det), dev.index, _args.current_stream(dev)))
+        out = p.call("rced_stoi", int(sample_rate), p.out.data_ptr(), ptr(det))
         return (out, det) if detail else out
-    classic = torch.empty((n,), dtype=torch.float64, device=dev) if extended == "both" else None
-    ext = torch.empty((n,), dtype=torch.float64, device=dev)
-    if n:
-        which = _lib.STOI_EXTENDED | (_lib.STOI_CLASSIC if classic is not None else 0)
-        _lib.check(_lib.load().rced_stoi_ex(clean.data_ptr(), sc, estimate.data_ptr(), se, ptr(ldev), n, int(sample_rate), which,
-                                            ptr(classic), ext.data_ptr(), ptr(det), dev.index, _args.current_stream(dev)))
+    classic = p.new() if extended == "both" else None
+    which = _lib.STOI_EXTENDED | (_lib.STOI_CLASSIC if classic is not None else 0)
+    ext = p.call("rced_stoi_ex", int(sample_rate), which, ptr(classic), p.out.data_ptr(), ptr(det))
     scores = (classic, ext) if classic is not None else (ext,)
     if detail:
         return scores + (det,)
@@ -65,13 +74,8 @@ def si_sdr_batch(clean, estimate, lengths=None):
     sum((y - alpha x)^2)), two passes, no mean removal).  Arguments as in sdr_batch.  Returns torch.float64 [N] (dB) on the
     device, current stream; +inf where the estimate is a power-of-two multiple of the clean row, nan for an all-zero row or
     a length of 0."""
-    import torch
-    clean, estimate, n, dev, sc, se, ldev = _args.scoring_args(clean, estimate, lengths)
-    out = torch.empty((n,), dtype=torch.float64, device=dev)
-    if n:
-        _lib.check(_lib.load().rced_si_sdr(clean.data_ptr(), sc, estimate.data_ptr(), se, ldev.data_ptr() if ldev is not None else None,
-                                           n, out.data_ptr(), None, dev.index, _args.current_stream(dev)))
-    return out
+    p = _Pairs(clean, estimate, lengths)
+    return p.call("rced_si_sdr", p.out.data_ptr(), None)
 
 
 SEG_SNR_WINDOW = (4, 1440)
@@ -91,15 +95,10 @@ def seg_snr_batch(clean, estimate, lengths=None, sample_rate=8000, detail=False)
     hop, each frame's SNR clamped to [-10, 35] dB, the mean over the frames).  Arguments as in sdr_batch; sample_rate: any
     rate whose frame has 4 .. 1440 samples.  Returns torch.float64 [N] (dB) on the device, current stream -- nan for an
     utterance shorter than one frame; with detail=True also torch.int32 [N], the frames of each utterance."""
-    import torch
     seg_snr_window(sample_rate)
-    clean, estimate, n, dev, sc, se, ldev = _args.scoring_args(clean, estimate, lengths)
-    out = torch.empty((n,), dtype=torch.float64, device=dev)
-    frames = torch.empty((n,), dtype=torch.int32, device=dev) if detail else None
-    if n:
-        _lib.check(_lib.load().rced_seg_snr(clean.data_ptr(), sc, estimate.data_ptr(), se, ldev.data_ptr() if ldev is not None else None,
-                                            n, int(sample_rate), out.data_ptr(), frames.data_ptr() if detail else None, dev.index,
-                                            _args.current_stream(dev)))
+    p = _Pairs(clean, estimate, lengths)
+    frames = p.new(dtype="int32") if detail else None
+    out = p.call("rced_seg_snr", int(sample_rate), p.out.data_ptr(), ptr(frames))
     return (out, frames) if detail else out
 
 
@@ -112,23 +111,14 @@ def _spectral_rate(sample_rate):
     return int(sample_rate)
 
 
-def _spectral_batch(name, clean, estimate, lengths, sample_rate, detail, limit=None):
-    import torch
+def _spectral_batch(entry, clean, estimate, lengths, sample_rate, detail, *limit):
     fs = _spectral_rate(sample_rate)
-    clean, estimate, n, dev, sc, se, ldev = _args.scoring_args(clean, estimate, lengths)
+    p = _Pairs(clean, estimate, lengths)
     w = (3 * fs + 50) // 100
-    most = (min(sc, se) - w) // (w // 4) + 1 if min(sc, se) >= w else 0      # the frames of a row read to its end
-    out = torch.empty((n,), dtype=torch.float64, device=dev)
-    nf = torch.empty((n,), dtype=torch.int32, device=dev) if detail else None
-    frames = torch.zeros((n, most), dtype=torch.float64, device=dev) if detail else None
-    if n:
-        ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
-        head = (clean.data_ptr(), sc, estimate.data_ptr(), se, ptr(ldev), n, fs)
-        tail = (out.data_ptr(), ptr(frames), most, ptr(nf), dev.index, _args.current_stream(dev))
-        if name == "llr":
-            _lib.check(_lib.load().rced_llr(*(head + (limit,) + tail)))
-        else:
-            _lib.check(_lib.load().rced_wss(*(head + tail)))
+    most = (p.cap - w) // (w // 4) + 1 if p.cap >= w else 0      # the frames of a row read to its end
+    nf = p.new(dtype="int32") if detail else None
+    frames = p.new(most, zeros=True) if detail else None
+    out = p.call(entry, fs, *limit, p.out.data_ptr(), ptr(frames), most, ptr(nf))
     return (out, nf, frames) if detail else out
 
 
@@ -144,14 +134,14 @@ def llr_batch(clean, estimate, lengths=None, sample_rate=8000, limit=2.0, detail
     limit = float("inf") if limit is None else float(limit)
     if limit != limit:
         raise ValueError("limit must be a number or None, got nan")
-    return _spectral_batch("llr", clean, estimate, lengths, sample_rate, detail, limit)
+    return _spectral_batch("rced_llr", clean, estimate, lengths, sample_rate, detail, limit)
 
 
 def wss_batch(clean, estimate, lengths=None, sample_rate=8000, detail=False):
     """Weighted spectral slope distance per utterance on the device (DESIGN.md "WSS": the segmental SNR's frames, an fp64
     DFT, 25 critical-band energies in dB, their 24 slopes weighted by the nearest peak and the global maximum, the mean of
     the lowest 95 % of the frames).  Arguments and returns as in llr_batch, without the limit."""
-    return _spectral_batch("wss", clean, estimate, lengths, sample_rate, detail)
+    return _spectral_batch("rced_wss", clean, estimate, lengths, sample_rate, detail)
 
 
 BSS_MAX_FILTER = 512
@@ -175,23 +165,26 @@ def bss_sdr_batch(clean, estimate, lengths=None, filter_length=512, detail=False
     sum e^2.  Nothing is regularised and there is no least-squares fallback: a singular toeplitz(r) (a clean row with an
     empty band) gives whatever the recursion gives.  This is bss_eval_sources for one source; parity with mir_eval or museval
     is unpinned, the pin is the float64 restatement in tests/bsseval_np.py."""
-    import torch
     taps = _filter_length(filter_length)
-    clean, estimate, n, dev, sc, se, ldev = _args.scoring_args(clean, estimate, lengths)
-    out = torch.empty((n,), dtype=torch.float64, device=dev)
-    filt = torch.empty((n, taps), dtype=torch.float64, device=dev) if detail else None
-    energies = torch.empty((n, 2), dtype=torch.float64, device=dev) if detail else None
-    if n:
-        ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
-        _lib.check(_lib.load().rced_bss_sdr(clean.data_ptr(), sc, estimate.data_ptr(), se, ptr(ldev), n, taps, out.data_ptr(), ptr(filt),
-                                            ptr(energies), dev.index, _args.current_stream(dev)))
+    p = _Pairs(clean, estimate, lengths)
+    filt = p.new(taps) if detail else None
+    energies = p.new(2) if detail else None
+    out = p.call("rced_bss_sdr", taps, p.out.data_ptr(), ptr(filt), ptr(energies))
     return (out, filt, energies) if detail else out
 
 
+# every score `extra` can name -> (its batch function, the keywords the evaluation loop calls it with)
+_EXTRA = {"estoi": (stoi_batch, {"sample_rate": SAMPLE_RATE, "extended": True}),
+          "si_sdr": (si_sdr_batch, {}),
+          "seg_snr": (seg_snr_batch, {"sample_rate": SAMPLE_RATE}),
+          "llr": (llr_batch, {"sample_rate": SAMPLE_RATE, "limit": 2.0}),
+          "wss": (wss_batch, {"sample_rate": SAMPLE_RATE}),
+          "bss_sdr": (bss_sdr_batch, {"filter_length": 512})}
 EXTRA_METRICS = ("estoi", "si_sdr", "seg_snr")
 SPECTRAL_METRICS = ("llr", "wss")       # the composite measures' two spectral terms; `extra` takes names from all three tuples
 PROJECTION_METRICS = ("bss_sdr",)       # BSS Eval's SDR at its filter length of 512
-ALL_EXTRA = EXTRA_METRICS + SPECTRAL_METRICS + PROJECTION_METRICS
+ALL_EXTRA = tuple(_EXTRA)
+assert ALL_EXTRA == EXTRA_METRICS + SPECTRAL_METRICS + PROJECTION_METRICS
 
 
 def check_extra(extra):
@@ -263,7 +256,6 @@ def mix_snr_batch(speech, noise, snr, speech_lengths=None, noise_lengths=None, s
         sdev = torch.tensor(sl, dtype=torch.int32, device=dev) if sl is not None else None
         ndev = torch.tensor(nl, dtype=torch.int32, device=dev) if nl is not None else None
         tdev = torch.tensor(st_host, dtype=torch.int32, device=dev) if st_host is not None else None
-        ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
         _lib.check(_lib.load().rced_mix_snr(speech.data_ptr(), ptr(sdev), n, Ls, noise.data_ptr(), ptr(ndev), Ln, ptr(tdev),
                                             ptr(gdev), n_gains, float(snr), mix.data_ptr(), dev.index, _args.current_stream(dev)))
     return mix
@@ -296,16 +288,7 @@ def denoise_and_score(forward, mix, clean, lengths, nfft=512, kernels="x6", stoi
         scored += (st,)
     elif stoi:
         scored += (stoi_batch(clean, out, lengths, SAMPLE_RATE),)
-    elif "estoi" in extra:
-        more["estoi"] = stoi_batch(clean, out, lengths, SAMPLE_RATE, extended=True)
-    if "si_sdr" in extra:
-        more["si_sdr"] = si_sdr_batch(clean, out, lengths)
-    if "seg_snr" in extra:
-        more["seg_snr"] = seg_snr_batch(clean, out, lengths, SAMPLE_RATE)
-    if "llr" in extra:
-        more["llr"] = llr_batch(clean, out, lengths, SAMPLE_RATE)
-    if "wss" in extra:
-        more["wss"] = wss_batch(clean, out, lengths, SAMPLE_RATE)
-    if "bss_sdr" in extra:
-        more["bss_sdr"] = bss_sdr_batch(clean, out, lengths)
+    for name, (batch, kw) in _EXTRA.items():
+        if name in extra and name not in more:
+            more[name] = batch(clean, out, lengths, **kw)
     return scored + ({name: more[name] for name in extra},) if extra else scored

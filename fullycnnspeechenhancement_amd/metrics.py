@@ -36,56 +36,6 @@ class AverageMeter(object):
         self.avg = self.sum / self.count
 
 
-class SDR(object):
-    """utils.py:64-90: 10 * log10(sum(y^2) / (sum((y_pred - y)^2) + float32 eps))."""
-
-    def __init__(self, device=0):
-        self.device = device
-
-    def sdr(self, y, y_pred):
-        import torch
-        from . import audio
-        y, y_pred = np.asarray(y), np.asarray(y_pred)
-        if len(y.shape) != 1:                                   # the reference's two asserts (utils.py:74-75)
-            raise ValueError("y must be a 1-D signal, got shape %s" % (y.shape,))
-        if len(y) != len(y_pred):
-            raise ValueError("y and y_pred must have the same length, got %d and %d" % (len(y), len(y_pred)))
-        dev = "cuda:%d" % self.device
-        both = torch.as_tensor(np.stack([y.astype(np.float32), y_pred.astype(np.float32).reshape(-1)]), device=dev)
-        return float(audio.sdr_batch(both[0:1], both[1:2])[0])
-
-    def __call__(self, x, y):
-        return self.sdr(x, y)
-
-
-class STOI(object):
-    """The reference's `stoi(clean, denoise, sr, extended=False)` (tester.py:92-167) with SDR's call surface:
-    `STOI(sr)(clean, processed)`, numpy 1-D in, Python float out, computed on the device (rced_stoi)."""
-
-    def __init__(self, sr=8000, device=0):
-        from . import audio
-        if sr not in audio.STOI_RATES:
-            raise ValueError("sr must be 8000 or 10000, got %r" % (sr,))
-        self.sr, self.device = int(sr), device
-
-    def stoi(self, x, y):
-        import torch
-        from . import audio
-        x, y = np.asarray(x), np.asarray(y)
-        if len(x.shape) != 1 or len(y.shape) != 1:
-            raise ValueError("x and y must be 1-D signals, got shapes %s and %s" % (x.shape, y.shape))
-        if len(x) != len(y):
-            raise ValueError("x and y must have the same length, got %d and %d" % (len(x), len(y)))
-        if len(x) == 0:
-            return 1e-5
-        dev = "cuda:%d" % self.device
-        both = torch.as_tensor(np.stack([x.astype(np.float32), y.astype(np.float32)]), device=dev)
-        return float(audio.stoi_batch(both[0:1], both[1:2], sample_rate=self.sr)[0])
-
-    def __call__(self, x, y):
-        return self.stoi(x, y)
-
-
 def _pair(x, y):
     """Two 1-D signals of one length, as STOI takes them, stacked [2, L] float32."""
     x, y = np.asarray(x), np.asarray(y)
@@ -102,7 +52,60 @@ def _score_pair(batch_fn, pair, device, **kw):
     return float(batch_fn(both[0:1], both[1:2], **kw)[0])
 
 
-class ESTOI(object):
+class SDR(object):
+    """utils.py:64-90: 10 * log10(sum(y^2) / (sum((y_pred - y)^2) + float32 eps))."""
+
+    def __init__(self, device=0):
+        self.device = device
+
+    def sdr(self, y, y_pred):
+        from . import audio
+        y, y_pred = np.asarray(y), np.asarray(y_pred)
+        if len(y.shape) != 1:                                   # the reference's two asserts (utils.py:74-75)
+            raise ValueError("y must be a 1-D signal, got shape %s" % (y.shape,))
+        if len(y) != len(y_pred):
+            raise ValueError("y and y_pred must have the same length, got %d and %d" % (len(y), len(y_pred)))
+        return _score_pair(audio.sdr_batch, np.stack([y.astype(np.float32), y_pred.astype(np.float32).reshape(-1)]), self.device)
+
+    def __call__(self, x, y):
+        return self.sdr(x, y)
+
+
+class _PairMetric(object):
+    """What the mirrors below share: `Metric(...)(x, y)`, two numpy 1-D signals of one length in, a Python float out, from one
+    audio.*_batch call over the single pair on cuda:`device`; `empty`: the score of two empty signals, given without a device.
+    A subclass checks its arguments, keeps them as attributes and names its method after the score."""
+
+    def __init__(self, device, method, empty, batch, **keywords):
+        self.device, self._method, self._empty, self._batch, self._keywords = device, method, empty, batch, keywords
+
+    def _score(self, x, y):
+        from . import audio
+        pair = _pair(x, y)
+        if not pair.shape[1]:
+            return self._empty
+        return _score_pair(getattr(audio, self._batch), pair, self.device, **self._keywords)
+
+    def __call__(self, x, y):
+        return getattr(self, self._method)(x, y)
+
+
+class STOI(_PairMetric):
+    """The reference's `stoi(clean, denoise, sr, extended=False)` (tester.py:92-167) with SDR's call surface:
+    `STOI(sr)(clean, processed)`, numpy 1-D in, Python float out, computed on the device (rced_stoi)."""
+
+    def __init__(self, sr=8000, device=0):
+        from . import audio
+        if sr not in audio.STOI_RATES:
+            raise ValueError("sr must be 8000 or 10000, got %r" % (sr,))
+        self.sr = int(sr)
+        _PairMetric.__init__(self, device, "stoi", 1e-5, "stoi_batch", sample_rate=self.sr)
+
+    def stoi(self, x, y):
+        return self._score(x, y)
+
+
+class ESTOI(_PairMetric):
     """Extended STOI (Jensen, Taal 2016; pystoi's `stoi(clean, denoise, sr, extended=True)`) with STOI's call surface:
     `ESTOI(sr)(clean, processed)`, numpy 1-D in, Python float out, computed on the device (rced_stoi_ex)."""
 
@@ -110,38 +113,25 @@ class ESTOI(object):
         from . import audio
         if sr not in audio.STOI_RATES:
             raise ValueError("sr must be 8000 or 10000, got %r" % (sr,))
-        self.sr, self.device = int(sr), device
+        self.sr = int(sr)
+        _PairMetric.__init__(self, device, "estoi", 1e-5, "stoi_batch", sample_rate=self.sr, extended=True)
 
     def estoi(self, x, y):
-        from . import audio
-        pair = _pair(x, y)
-        if not pair.shape[1]:
-            return 1e-5
-        return _score_pair(audio.stoi_batch, pair, self.device, sample_rate=self.sr, extended=True)
-
-    def __call__(self, x, y):
-        return self.estoi(x, y)
+        return self._score(x, y)
 
 
-class SISDR(object):
+class SISDR(_PairMetric):
     """Scale-invariant SDR, `SISDR()(y, y_pred)` as `SDR()(y, y_pred)`: numpy 1-D in, Python float (dB) out, computed on the
     device (rced_si_sdr).  Two empty signals give nan, as the definition does."""
 
     def __init__(self, device=0):
-        self.device = device
+        _PairMetric.__init__(self, device, "si_sdr", float("nan"), "si_sdr_batch")
 
     def si_sdr(self, y, y_pred):
-        from . import audio
-        pair = _pair(y, y_pred)
-        if not pair.shape[1]:
-            return float("nan")
-        return _score_pair(audio.si_sdr_batch, pair, self.device)
-
-    def __call__(self, x, y):
-        return self.si_sdr(x, y)
+        return self._score(y, y_pred)
 
 
-class BSSSDR(object):
+class BSSSDR(_PairMetric):
     """The SDR of BSS Eval for one source, `BSSSDR(filter_length)(y, y_pred)` as `SISDR()(y, y_pred)`: numpy 1-D in, Python
     float (dB) out, computed on the device (rced_bss_sdr): the estimate is scored after its projection onto the clean signal
     delayed by 0 .. filter_length - 1 samples (512 as bss_eval_sources has it; parity with mir_eval is unpinned, the pin is
@@ -149,40 +139,28 @@ class BSSSDR(object):
 
     def __init__(self, filter_length=512, device=0):
         from . import evaluation
-        self.filter_length, self.device = evaluation._filter_length(filter_length), device      # ValueError outside 1 .. 512
+        self.filter_length = evaluation._filter_length(filter_length)      # ValueError outside 1 .. 512
+        _PairMetric.__init__(self, device, "bss_sdr", float("nan"), "bss_sdr_batch", filter_length=self.filter_length)
 
     def bss_sdr(self, y, y_pred):
-        from . import audio
-        pair = _pair(y, y_pred)
-        if not pair.shape[1]:
-            return float("nan")
-        return _score_pair(audio.bss_sdr_batch, pair, self.device, filter_length=self.filter_length)
-
-    def __call__(self, x, y):
-        return self.bss_sdr(x, y)
+        return self._score(y, y_pred)
 
 
-class SegSNR(object):
+class SegSNR(_PairMetric):
     """Segmental SNR, `SegSNR(sr)(clean, processed)`: numpy 1-D in, Python float (dB) out, computed on the device
     (rced_seg_snr).  Signals shorter than one frame give nan."""
 
     def __init__(self, sr=8000, device=0):
         from . import audio
         self.window = audio.seg_snr_window(sr)           # ValueError for a rate the library refuses
-        self.sr, self.device = int(sr), device
+        self.sr = int(sr)
+        _PairMetric.__init__(self, device, "seg_snr", float("nan"), "seg_snr_batch", sample_rate=self.sr)
 
     def seg_snr(self, x, y):
-        from . import audio
-        pair = _pair(x, y)
-        if not pair.shape[1]:
-            return float("nan")
-        return _score_pair(audio.seg_snr_batch, pair, self.device, sample_rate=self.sr)
-
-    def __call__(self, x, y):
-        return self.seg_snr(x, y)
+        return self._score(x, y)
 
 
-class LLR(object):
+class LLR(_PairMetric):
     """Log-likelihood ratio of the LPC models, `LLR(sr, limit)(clean, processed)`: numpy 1-D in, Python float out, computed
     on the device (rced_llr).  limit: the cap on a frame's value (2 as published; None for none, the form `composite`
     takes).  Signals shorter than one frame give nan."""
@@ -193,20 +171,14 @@ class LLR(object):
             raise ValueError("sr must be 8000 or 16000, got %r" % (sr,))
         if limit is not None and float(limit) != float(limit):
             raise ValueError("limit must be a number or None, got nan")
-        self.sr, self.limit, self.device = int(sr), limit, device
+        self.sr, self.limit = int(sr), limit
+        _PairMetric.__init__(self, device, "llr", float("nan"), "llr_batch", sample_rate=self.sr, limit=limit)
 
     def llr(self, x, y):
-        from . import audio
-        pair = _pair(x, y)
-        if not pair.shape[1]:
-            return float("nan")
-        return _score_pair(audio.llr_batch, pair, self.device, sample_rate=self.sr, limit=self.limit)
-
-    def __call__(self, x, y):
-        return self.llr(x, y)
+        return self._score(x, y)
 
 
-class WSS(object):
+class WSS(_PairMetric):
     """Weighted spectral slope distance, `WSS(sr)(clean, processed)`: numpy 1-D in, Python float out, computed on the device
     (rced_wss).  Signals shorter than one frame give nan."""
 
@@ -214,17 +186,11 @@ class WSS(object):
         from . import audio
         if sr not in audio.SPECTRAL_RATES:
             raise ValueError("sr must be 8000 or 16000, got %r" % (sr,))
-        self.sr, self.device = int(sr), device
+        self.sr = int(sr)
+        _PairMetric.__init__(self, device, "wss", float("nan"), "wss_batch", sample_rate=self.sr)
 
     def wss(self, x, y):
-        from . import audio
-        pair = _pair(x, y)
-        if not pair.shape[1]:
-            return float("nan")
-        return _score_pair(audio.wss_batch, pair, self.device, sample_rate=self.sr)
-
-    def __call__(self, x, y):
-        return self.wss(x, y)
+        return self._score(x, y)
 
 
 def composite(pesq, llr, wss, seg_snr):

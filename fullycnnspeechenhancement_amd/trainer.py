@@ -105,21 +105,14 @@ class FullyCNNTrainer(object):
         averages is printed and logged after the reference's.  rebuild: "reference" or "ola" (engine.evaluate_pcm).
         The framing is valid_loader.dataset.framing where there is one, else the default.
         PESQ and the wav files are not built."""
-        from .engine import check_rebuild, evaluate_pcm, extra_line, loader_framing
+        from .engine import check_rebuild, evaluate_pcm, extra_line, feed_meters, loader_framing
         extra = check_extra(extra)
         check_rebuild(rebuild)
         framing = loader_framing(valid_loader)
         for _batch_mix, _batch_clean, mix_sig, clean_sig in valid_loader:
             scores = evaluate_pcm(self.valid_step, mix_sig, clean_sig, nfft, self.device, stoi=stoi, extra=extra, rebuild=rebuild,
                                   framing=framing)
-            for score in scores[1]:
-                self.sdr_score.update(float(score))
-            if stoi:
-                for score in scores[2]:
-                    self.stoi_score.update(float(score))
-            for name in extra:
-                for score in scores[-1][name]:
-                    self.extra_scores[name].update(float(score))
+            feed_meters(self, scores, stoi, extra)
         if stoi:
             line = "Epoch: {}, Average st_score: {:.4f}; Average sd_score: {:.4f}.\n".format(epoch, self.stoi_score.avg,
                                                                                              self.sdr_score.avg)

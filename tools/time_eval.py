@@ -48,80 +48,50 @@ def timed_us(fn):
 HOST_PROCS = 16
 
 
-def _host_stoi(seed):
+# leg -> (module under tests/, function, arguments after the pair): the float64 restatement a device leg is set beside
+RESTATEMENTS = {"stoi": ("stoi_np", "stoi", (8000,)), "estoi": ("estoi_np", "estoi", (8000,)), "si_sdr": ("td_metrics_np", "si_sdr", ()),
+                "seg_snr": ("td_metrics_np", "seg_snr", (8000,)), "llr": ("sepm_np", "llr", (8000,)), "wss": ("sepm_np", "wss", (8000,)),
+                "bss_sdr": ("bsseval_np", "bss_sdr", (512,))}
+# command-line leg -> the restatements it runs; no leg: all of them
+HOST_LEGS = {"stoi": ("stoi",), "bss": ("bss_sdr",), "ext": ("estoi", "si_sdr", "seg_snr"), "sepm": ("llr", "wss")}
+
+
+def _host_score(job):
+    leg, seed = job
     sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import importlib
     import numpy as np
-    import stoi_np
+    module, fn, rest = RESTATEMENTS[leg]
     rng = np.random.default_rng(seed)
     x = 0.1 * rng.standard_normal(L)
-    return stoi_np.stoi(x, x + 0.05 * rng.standard_normal(L), 8000)
+    return getattr(importlib.import_module(module), fn)(x, x + 0.05 * rng.standard_normal(L), *rest)
 
 
-def _host_pair(seed):
-    import numpy as np
-    rng = np.random.default_rng(seed)
-    x = 0.1 * rng.standard_normal(L)
-    return x, x + 0.05 * rng.standard_normal(L)
-
-
-def _host_estoi(seed):
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import estoi_np
-    return estoi_np.estoi(*_host_pair(seed), 8000)
-
-
-def _host_si_sdr(seed):
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import td_metrics_np
-    return td_metrics_np.si_sdr(*_host_pair(seed))
-
-
-def _host_seg_snr(seed):
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import td_metrics_np
-    return td_metrics_np.seg_snr(*_host_pair(seed), 8000)
-
-
-def _host_llr(seed):
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import sepm_np
-    return sepm_np.llr(*_host_pair(seed), 8000)
-
-
-def _host_wss(seed):
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import sepm_np
-    return sepm_np.wss(*_host_pair(seed), 8000)
-
-
-def _host_bss_sdr(seed):
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import bsseval_np
-    return bsseval_np.bss_sdr(*_host_pair(seed), 512)
-
-
-def host_seconds(fn):
-    """Wall time of a restatement over N utterances of L samples on HOST_PROCS processes (forked before the GPU is touched)."""
+def host_seconds(leg):
+    """Wall time of a leg's restatement over N utterances of L samples on HOST_PROCS processes (forked before the GPU is touched)."""
     import multiprocessing
     import time
     with multiprocessing.get_context("fork").Pool(HOST_PROCS) as pool:
-        pool.map(fn, range(HOST_PROCS))                      # imports and first-call costs
+        pool.map(_host_score, [(leg, seed) for seed in range(HOST_PROCS)])      # imports and first-call costs
         t0 = time.perf_counter()
-        pool.map(fn, range(N), chunksize=1)
+        pool.map(_host_score, [(leg, seed) for seed in range(N)], chunksize=1)
         return time.perf_counter() - t0
 
 
-def host_stoi_seconds():
-    return host_seconds(_host_stoi)
+def beside(out, host, legs):
+    """`out` with each leg's restatement wall time next to its device time."""
+    for leg in legs:
+        out[leg + "_host_restatement_s"] = {"seconds": host[leg], "processes": HOST_PROCS}
+    return out
 
 
-def stoi_timings(speech, mix):
-    r = timed_us(lambda: audio.stoi_batch(speech, mix))
-    one = timed_us(lambda: audio.stoi_batch(speech[:1], mix[:1]))
-    return r, one
+def stoi_timings(speech, mix, host):
+    out = {"stoi": timed_us(lambda: audio.stoi_batch(speech, mix)),
+           "stoi_single_utterance": timed_us(lambda: audio.stoi_batch(speech[:1], mix[:1]))}
+    return beside(out, host, HOST_LEGS["stoi"])
 
 
-def ext_timings(speech, mix, host_ext):
+def ext_timings(speech, mix, host):
     """The four further legs, each beside its restatement's wall time, and stoi+estoi over rced_stoi alone (same process)."""
     out = {"estoi": timed_us(lambda: audio.stoi_batch(speech, mix, extended=True)),
            "stoi+estoi": timed_us(lambda: audio.stoi_batch(speech, mix, extended="both")),
@@ -130,60 +100,38 @@ def ext_timings(speech, mix, host_ext):
     alone = timed_us(lambda: audio.stoi_batch(speech, mix))
     out["stoi_alone_same_process"] = alone
     out["stoi+estoi_over_stoi"] = out["stoi+estoi"]["median_us"] / alone["median_us"]
-    for leg, seconds in host_ext.items():
-        out[leg + "_host_restatement_s"] = {"seconds": seconds, "processes": HOST_PROCS}
-    return out
+    return beside(out, host, HOST_LEGS["ext"])
 
 
-def sepm_timings(speech, mix, host_sepm):
+def sepm_timings(speech, mix, host):
     """LLR and WSS, each beside its restatement's wall time."""
     out = {"llr": timed_us(lambda: audio.llr_batch(speech, mix)), "wss": timed_us(lambda: audio.wss_batch(speech, mix))}
-    for leg, seconds in host_sepm.items():
-        out[leg + "_host_restatement_s"] = {"seconds": seconds, "processes": HOST_PROCS}
-    return out
+    return beside(out, host, HOST_LEGS["sepm"])
 
 
-def bss_timings(speech, mix, host_bss):
+def bss_timings(speech, mix, host):
     """BSS Eval's SDR at 512 taps (and at one tap: what the 512 lags cost) beside its restatement's wall time."""
     out = {"bss_sdr": timed_us(lambda: audio.bss_sdr_batch(speech, mix)),
            "bss_sdr_one_tap": timed_us(lambda: audio.bss_sdr_batch(speech, mix, filter_length=1)),
            "bss_sdr_single_utterance": timed_us(lambda: audio.bss_sdr_batch(speech[:1], mix[:1]))}
-    out["bss_sdr_host_restatement_s"] = {"seconds": host_bss, "processes": HOST_PROCS}
-    return out
+    return beside(out, host, HOST_LEGS["bss"])
+
+
+TIMINGS = {"stoi": stoi_timings, "ext": ext_timings, "sepm": sepm_timings, "bss": bss_timings}
 
 
 def main():
-    only_stoi = sys.argv[1:] == ["stoi"]
-    only_ext = sys.argv[1:] == ["ext"]
-    only_sepm = sys.argv[1:] == ["sepm"]
-    only_bss = sys.argv[1:] == ["bss"]
-    host_s = host_stoi_seconds() if not (only_ext or only_sepm or only_bss) else None       # first: these fork
-    host_bss = None if only_stoi or only_ext or only_sepm else host_seconds(_host_bss_sdr)
-    host_ext = {} if only_stoi or only_sepm or only_bss else {"estoi": host_seconds(_host_estoi), "si_sdr": host_seconds(_host_si_sdr),
-                                                  "seg_snr": host_seconds(_host_seg_snr)}
-    host_sepm = {} if only_stoi or only_ext or only_bss else {"llr": host_seconds(_host_llr), "wss": host_seconds(_host_wss)}
+    leg = sys.argv[1] if len(sys.argv) == 2 and sys.argv[1] in TIMINGS else None
+    host = {name: host_seconds(name) for group in ([leg] if leg else HOST_LEGS) for name in HOST_LEGS[group]}     # first: these fork
     g = torch.Generator(device="cuda").manual_seed(1)
     speech = torch.randn((N, L), device="cuda", generator=g) * 0.1
     noise = torch.randn((N, L), device="cuda", generator=g) * 0.05
     out = {"N": N, "L": L}
-    if only_stoi:
+    if leg:
         mix = audio.mix_snr_batch(speech, noise, 5.0)
-        out["stoi"], out["stoi_single_utterance"] = stoi_timings(speech, mix)
-        out["stoi_host_restatement_s"] = {"seconds": host_s, "processes": HOST_PROCS}
-        print(json.dumps(out))
-        return
-    if only_ext:
-        out.update(ext_timings(speech, audio.mix_snr_batch(speech, noise, 5.0), host_ext))
-        print(json.dumps(out))
-        return
-    if only_bss:
-        mix = audio.mix_snr_batch(speech, noise, 5.0)
-        out.update(bss_timings(speech, mix, host_bss))
-        out["wss"], out["stoi"] = timed_us(lambda: audio.wss_batch(speech, mix)), timed_us(lambda: audio.stoi_batch(speech, mix))
-        print(json.dumps(out))
-        return
-    if only_sepm:
-        out.update(sepm_timings(speech, audio.mix_snr_batch(speech, noise, 5.0), host_sepm))
+        out.update(TIMINGS[leg](speech, mix, host))
+        if leg == "bss":
+            out["wss"], out["stoi"] = timed_us(lambda: audio.wss_batch(speech, mix)), timed_us(lambda: audio.stoi_batch(speech, mix))
         print(json.dumps(out))
         return
 
@@ -209,11 +157,8 @@ def main():
     one = speech[:1].contiguous()                              # N = 1: a long signal alone (33 workgroups)
     out["sdr_single_utterance"] = timed_us(lambda: audio.sdr_batch(one, mix[:1]))
 
-    out["stoi"], out["stoi_single_utterance"] = stoi_timings(speech, mix)
-    out["stoi_host_restatement_s"] = {"seconds": host_s, "processes": HOST_PROCS}
-    out.update(ext_timings(speech, mix, host_ext))
-    out.update(sepm_timings(speech, mix, host_sepm))
-    out.update(bss_timings(speech, mix, host_bss))
+    for group in ("stoi", "ext", "sepm", "bss"):
+        out.update(TIMINGS[group](speech, mix, host))
 
     model = build_model("FullyCNNV3", False, weights=_weights.synthetic_weights(3, seed=42))
     lens = [L] * N
