@@ -129,6 +129,15 @@ def keep_alive(stream, *tensors):
             t.record_stream(stream)
 
 
+def pcm_units(shape, lanes, channels, unit=1):
+    """How many units of `unit` frames a lane the PCM of `shape` holds -- [lanes, n * unit] interleaved ([lanes, n * unit * channels])
+    or [lanes, n * unit, channels] --, or -1 where it is neither."""
+    shape = tuple(shape)
+    per = unit * (channels if len(shape) == 2 else 1)
+    n = shape[1] // per if len(shape) in (2, 3) else -1
+    return n if shape in ((lanes, n * unit * channels), (lanes, n * unit, channels)) else -1
+
+
 def pack_tails(lanes_total, unit, channels, np_dtype, lanes, tails):
     """What a finish uploads: (tail [lanes_total, unit(, channels)] of np_dtype, counts int32 [lanes_total]) with tails[i], the
     last 0 .. unit - 1 frames of lane lanes[i] ([frames], [frames * channels] or [frames, channels]; arrays or tensors), in its

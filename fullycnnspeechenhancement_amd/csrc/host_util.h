@@ -6,6 +6,7 @@
 #include <climits>
 #include <cstddef>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rced.h"
@@ -54,6 +55,48 @@ struct OnDevice {
     if (!g.ok) rc = rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
   }
 };
+
+// A DeviceGuard for the rest of the scope, or its failure returned: for push / finish / reset paths, which ask for no device count
+// (OnDevice does; it is for create paths)
+#define ON_DEVICE(dev)        \
+  DeviceGuard guard_(dev);    \
+  if (!guard_.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", dev)
+
+// One lane of [lanes][per_lane] elements of per-lane state, or (-1) all of them, back to zero behind the work queued on `last`
+template <class T>
+int reset_lanes(T* state, size_t per_lane, int lanes, int lane, int device, hipStream_t last) {
+  if (lane < -1 || lane >= lanes) return rced_fail(RCED_ERR_ARG, "lane must be -1 (all) or 0..%d, got %d", lanes - 1, lane);
+  ON_DEVICE(device);
+  const size_t one = per_lane * sizeof(T);
+  if (lane < 0) HIP_TRY(hipMemsetAsync(state, 0, one * lanes, last));
+  else HIP_TRY(hipMemsetAsync(state + (size_t)lane * per_lane, 0, one, last));
+  return RCED_OK;
+}
+
+// The refusals of a PCM format, in the words every resampling entry uses
+inline int check_rates(int sr_in, int sr_out) {
+  return sr_in <= 0 || sr_out <= 0 ? rced_fail(RCED_ERR_ARG, "sample rates must be positive, got %d -> %d", sr_in, sr_out) : RCED_OK;
+}
+inline int check_channels(int channels) {
+  return channels < 1 ? rced_fail(RCED_ERR_ARG, "channels must be >= 1, got %d", channels) : RCED_OK;
+}
+inline int check_pcm_dtypes(int src_dtype, int out_dtype) {
+  if (src_dtype != RCED_PCM_S16 && src_dtype != RCED_PCM_F32)
+    return rced_fail(RCED_ERR_ARG, "src_dtype must be RCED_PCM_S16 or RCED_PCM_F32, got %d", src_dtype);
+  if (out_dtype != RCED_PCM_S16 && out_dtype != RCED_PCM_F32)
+    return rced_fail(RCED_ERR_ARG, "out_dtype must be RCED_PCM_S16 or RCED_PCM_F32, got %d", out_dtype);
+  return RCED_OK;
+}
+
+// f(SRC_F32, OUT_F32) with the two PCM types as std::true_type / std::false_type: a kernel template's <SRC_F32, OUT_F32> from dtypes
+template <class F>
+void with_pcm_types(int src_dtype, int out_dtype, F f) {
+  const bool sf = src_dtype == RCED_PCM_F32, of = out_dtype == RCED_PCM_F32;
+  if (sf && of) f(std::true_type(), std::true_type());
+  else if (sf) f(std::true_type(), std::false_type());
+  else if (of) f(std::false_type(), std::true_type());
+  else f(std::false_type(), std::false_type());
+}
 
 // A host vector as a fresh device allocation.  *dev is written only after the copy succeeded (a caller may test it for "built");
 // on failure the allocation is freed.

@@ -8,7 +8,7 @@
 // stages, and `cap` samples of the output's type.  Output m of the utterance lives in ring slot (prefill + m) mod cap, the read
 // position R in slot R mod cap: all zero is the start of an utterance with `prefill` zeros in the ring.  The workgroup walks the new
 // outputs in tiles of at most `tile`, stages the frames a tile reaches in LDS -- out of the history, out of the call's own input,
-// zero past a finished utterance's end -- and runs kernels_rstream.h's loop over them: resample::fir<> and put<>, the same chain of
+// zero past a finished utterance's end -- and runs resample_kernel's loop over them: resample::fir_tile and put<>, the same chain of
 // `width` FMAs in ascending tap order for every output.  Behind the barrier that ends the last tile it copies the samples taken out
 // of the ring, and only then writes the lane's state: nothing is read and written by different workgroups.
 // The loops that store to global memory run a trip count the whole workgroup shares, with the bound as a mask inside, as in
@@ -18,15 +18,13 @@
 
 #include <type_traits>
 
-#include "kernels_rstream.h"
+#include "kernels_resample.h"
 #include "rfree_plan.h"
 
 namespace rced {
 namespace rfree {
 
-using resample::kK;
 using resample::kThreads;
-using resample::kWaves;
 
 struct Params {
   const void* in;           // [S][in_cols][channels]
@@ -75,68 +73,17 @@ __global__ __launch_bounds__(kThreads) void rfree_kernel(const Params P) {
   // a push writes them into the ring, a finish behind the ring's samples into the lane's row
   if (P.finish && A1 - A0 > P.out_cols - have) A1 = A0 + (P.out_cols - have);   // never: finish_max bounds what a finish owes
 
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int C = P.channels;
   for (long long m0 = A0; m0 < A1; m0 += P.tile) {
     const int Tn = (int)(A1 - m0 < P.tile ? A1 - m0 : P.tile);
-    // stage frames j0 .. j0 + span: history below F0, the call's input from there, zero behind it
-    const long long n0_first = (m0 * P.q) / P.p;
-    const long long n0_last = ((m0 + Tn - 1) * P.q) / P.p;
-    const long long j0 = n0_first - P.left;
-    int span = (int)(n0_last - n0_first) + P.width;
-    if (span > kSpanMax) span = kSpanMax;   // never: the host sizes the tile (span_bound)
-    for (int e = tid; e < span; e += kThreads) {
-      const long long j = j0 + e;
-      double v = 0.0;
-      if (j < F0) {
-        const long long at = j - (F0 - P.hist);
-        if (at >= 0) v = hist[at];          // always: an output not emitted at F0 frames reaches frame F0 - 1 - right + 1 or later
-      } else if (j - F0 < cnt) {
-        v = rstream::frame<SRC_F32>(P.in, (irow + (j - F0)) * C, C);
-      }
-      lds[e] = v;
-    }
+    const resample::Reach reach = resample::reach_of(m0, Tn, P.p, P.q, P.left, P.width);
+    resample::stage_lane<SRC_F32>(lds, reach, F0, hist, P.hist, P.in, irow, cnt, C, tid);
     __syncthreads();
-    // resample_kernel's runs of same-phase outputs: class u = outputs m0 + u + v p, run g = its outputs v in [256 g, 256 g + 256)
-    const int V = (Tn + P.p - 1) / P.p;
-    const int G = (V + 64 * kK - 1) / (64 * kK);
-    const int classes = Tn < P.p ? Tn : P.p;
-    for (int w = wave; w < classes * G; w += kWaves) {
-      const int u = w / G, g = w - u * G;
-      const int Vu = (Tn - u + P.p - 1) / P.p;
-      const int v0 = g * 64 * kK;
-      if (v0 >= Vu) continue;
-      const int left_v = Vu - v0;
-      const int nk = left_v >= 64 * kK ? kK : (left_v + 63) / 64;
-      const long long a = (m0 + u) * P.q;
-      const long long n0u = a / P.p;
-      const int r = (int)(a - n0u * P.p);
-      const double* taps = P.table + (size_t)r * P.width;
-      int xo[kK];
-      double acc[kK];
-#pragma unroll
-      for (int k = 0; k < kK; ++k) {
-        int v = v0 + 64 * k + lane;
-        if (v > Vu - 1) v = Vu - 1;   // idle lanes recompute the class's last output: every read stays inside the span
-        xo[k] = (int)(n0u - n0_first) + v * P.q;
-        acc[k] = 0.0;
-      }
-      switch (nk) {
-        case 1: resample::fir<1>(lds, taps, P.width, xo, acc); break;
-        case 2: resample::fir<2>(lds, taps, P.width, xo, acc); break;
-        case 3: resample::fir<3>(lds, taps, P.width, xo, acc); break;
-        default: resample::fir<4>(lds, taps, P.width, xo, acc); break;
-      }
-#pragma unroll
-      for (int k = 0; k < kK; ++k) {
-        const int v = v0 + 64 * k + lane;
-        if (k < nk && v < Vu) {
-          const long long m = m0 + u + (long long)v * P.p;
-          if (P.finish) resample::put<OUT_F32>(P.out, orow + have + (m - A0), acc[k]);
-          else resample::put<OUT_F32>(ring, (P.prefill + m) % P.cap, acc[k]);
-        }
-      }
-    }
+    resample::fir_tile(lds, P.table, P.p, P.q, P.width, m0, Tn, reach.n0_first, tid, [&](long long t, double y) {
+      const long long m = m0 + t;
+      if (P.finish) resample::put<OUT_F32>(P.out, orow + have + (m - A0), y);
+      else resample::put<OUT_F32>(ring, (P.prefill + m) % P.cap, y);
+    });
     __syncthreads();   // the tile's reads of LDS are done; with the last tile the ring holds every new output
   }
 
@@ -162,19 +109,7 @@ __global__ __launch_bounds__(kThreads) void rfree_kernel(const Params P) {
     const int t = t0 + tid;
     if (t < P.out_cols) out[orow + t] = t < tk ? ring[(R + t) % P.cap] : (Elt)0;
   }
-  // the history moves on by the call's frames: the last `hist` of (history, input).  A pass reads its 256 values, then writes them
-  // `cnt` frames further down; what a later pass reads lies above everything written so far.
-  double* hist_w = reinterpret_cast<double*>(st + kHead);
-  for (int e0 = 0; e0 < P.hist; e0 += kThreads) {
-    const int e = e0 + tid;
-    double v = 0.0;
-    if (e < P.hist) {
-      const long long g = (long long)e + cnt;
-      v = g < P.hist ? hist[g] : rstream::frame<SRC_F32>(P.in, (irow + (g - P.hist)) * C, C);
-    }
-    __syncthreads();
-    if (e < P.hist) hist_w[e] = v;
-  }
+  resample::shift_history<SRC_F32>(reinterpret_cast<double*>(st + kHead), P.hist, P.in, irow, cnt, C, tid);
   if (tid == 0) {
     st[0] = F0 + cnt;
     st[1] = R + tk;

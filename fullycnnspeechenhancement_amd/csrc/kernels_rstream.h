@@ -8,6 +8,8 @@
 // -- and runs resample_kernel's loop over them: resample::fir<> and put<>, the same chain of `width` FMAs in ascending tap
 // order for every output, so that the stream equals the offline result bit for bit.  Only then, behind the barrier that ends
 // the last tile, does the workgroup write the lane's state: nothing is read and written by different workgroups.
+// The staging, the run loop and the history shift stand here in full, the text of kernels_resample.h's stage_lane<>, fir_tile and
+// shift_history<>: compiled over those, this kernel alone ran measurably slower ("One tile loop").
 // The loops that store to global memory run a trip count the whole workgroup shares, with the bound as a mask inside: a trip
 // count per lane compiles to "v_cmp vcc / global_store / s_or .., vcc", the sequence tools/isa_lint.py keeps out of the library.
 #pragma once
@@ -22,8 +24,6 @@ namespace rstream {
 using resample::kK;
 using resample::kThreads;
 using resample::kWaves;
-
-static_assert(kSpanMax == resample::kSpanMax && kTileMax == resample::kTileMax && kRun == 64 * kK, "rstream_plan.h and kernels_resample.h");
 
 struct Params {
   const void* in;           // [S][in_frames][channels]: a push's K unit_in frames of every lane, a finish's tail (unit_in)
@@ -40,24 +40,6 @@ struct Params {
   int out_cols;
   int* out_counts;          // finish: [S] outputs owed
 };
-
-// frame `a` of the lane's row of the call's input, as resample_kernel stages it
-template <bool SRC_F32>
-__device__ inline double frame(const void* in, long long at, int C) {
-  double v;
-  const double inv = 1.0 / 32768.0;
-  if (SRC_F32) {
-    const float* s = static_cast<const float*>(in) + at;
-    v = (double)s[0];
-    for (int ch = 1; ch < C; ++ch) v += (double)s[ch];
-  } else {
-    const short* s = static_cast<const short*>(in) + at;
-    v = (double)s[0] * inv;
-    for (int ch = 1; ch < C; ++ch) v += (double)s[ch] * inv;
-  }
-  if (C > 1) v /= (double)C;
-  return v;
-}
 
 template <bool SRC_F32, bool OUT_F32>
 __global__ __launch_bounds__(kThreads) void rstream_kernel(const Params P) {
@@ -110,7 +92,7 @@ __global__ __launch_bounds__(kThreads) void rstream_kernel(const Params P) {
         const long long at = j - (F0 - P.hist);
         if (at >= 0) v = hist[at];          // always: the delay bounds how far back a push reaches
       } else if (j - F0 < avail) {
-        v = frame<SRC_F32>(P.in, (irow + (j - F0)) * C, C);
+        v = resample::frame<SRC_F32>(P.in, (irow + (j - F0)) * C, C);
       }
       lds[e] = v;
     }
@@ -166,7 +148,7 @@ __global__ __launch_bounds__(kThreads) void rstream_kernel(const Params P) {
     double v = 0.0;
     if (e < P.hist) {
       const long long g = (long long)e + avail;
-      v = g < P.hist ? hist[g] : frame<SRC_F32>(P.in, (irow + (g - P.hist)) * C, C);
+      v = g < P.hist ? hist[g] : resample::frame<SRC_F32>(P.in, (irow + (g - P.hist)) * C, C);
     }
     __syncthreads();
     if (e < P.hist) hist[e] = v;

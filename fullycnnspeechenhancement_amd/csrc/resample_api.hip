@@ -118,15 +118,6 @@ int device_table(Ratio* R, int device, const double** out) {
   return RCED_OK;
 }
 
-// outputs per workgroup: the largest tile whose span fits, a whole number of full runs (64 kK outputs of every phase) where it holds one
-int tile_for(const Ratio& R) {
-  long long t = ((long long)(resample::kSpanMax - R.width - 1) * R.p) / R.q + 1;
-  if (t > resample::kTileMax) t = resample::kTileMax;
-  const long long run = 64LL * resample::kK * R.p;
-  if (t >= run) t -= t % run;
-  return (int)t;
-}
-
 }  // namespace
 
 int rced_resample_table(int sr_orig, int sr_new, int* p, int* q, int* left, int* width, int device, const double** table_dev) {
@@ -147,7 +138,7 @@ long long rced_resample_length(long long n, int sr_orig, int sr_new) {
 }
 
 int rced_resample_taps(int sr_orig, int sr_new, int* p, int* q, int* left, int* width, double* table_host, size_t n_doubles) {
-  if (sr_orig <= 0 || sr_new <= 0) return rced_fail(RCED_ERR_ARG, "sample rates must be positive, got %d -> %d", sr_orig, sr_new);
+  if (int rc = check_rates(sr_orig, sr_new)) return rc;
   Ratio* R = nullptr;
   if (int rc = ratio_for(sr_orig, sr_new, &R)) return rc;
   if (p) *p = R->p;
@@ -166,12 +157,9 @@ int rced_resample(const void* src_dev, int src_dtype, int channels, long long sr
                   int N, int sr_orig, int sr_new, void* out_dev, int out_dtype, const long long* out_begin_dev, int row_stride, int L,
                   int device, void* stream) {
   if (N < 0 || L < 0 || src_frames < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
-  if (channels < 1) return rced_fail(RCED_ERR_ARG, "channels must be >= 1, got %d", channels);
-  if (sr_orig <= 0 || sr_new <= 0) return rced_fail(RCED_ERR_ARG, "sample rates must be positive, got %d -> %d", sr_orig, sr_new);
-  if (src_dtype != RCED_PCM_S16 && src_dtype != RCED_PCM_F32)
-    return rced_fail(RCED_ERR_ARG, "src_dtype must be RCED_PCM_S16 or RCED_PCM_F32, got %d", src_dtype);
-  if (out_dtype != RCED_PCM_S16 && out_dtype != RCED_PCM_F32)
-    return rced_fail(RCED_ERR_ARG, "out_dtype must be RCED_PCM_S16 or RCED_PCM_F32, got %d", out_dtype);
+  if (int rc = check_channels(channels)) return rc;
+  if (int rc = check_rates(sr_orig, sr_new)) return rc;
+  if (int rc = check_pcm_dtypes(src_dtype, out_dtype)) return rc;
   if (!out_begin_dev && row_stride < L) return rced_fail(RCED_ERR_ARG, "row_stride %d < L %d", row_stride, L);
   if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
   if (L > resample::kMaxLen) return rced_fail(RCED_ERR_ARG, "rows longer than 2^30 samples");
@@ -180,9 +168,8 @@ int rced_resample(const void* src_dev, int src_dtype, int channels, long long sr
   if (N == 0 || L == 0) return RCED_OK;
   if (!begin_dev || !count_dev || !out_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
   if (!src_dev && src_frames > 0) return rced_fail(RCED_ERR_ARG, "null source of %lld frames", src_frames);
-  if (int rc = check_device(device, kMaxDevices)) return rc;
-  DeviceGuard g(device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  OnDevice on(device, kMaxDevices);
+  if (on.rc) return on.rc;
   resample::Params P;
   if (int rc = device_table(R, device, &P.table)) return rc;
   P.src = src_dev;
@@ -195,22 +182,16 @@ int rced_resample(const void* src_dev, int src_dtype, int channels, long long sr
   P.left = R->left;
   P.width = R->width;
   P.ratio = (double)sr_new / (double)sr_orig;
-  P.tile = tile_for(*R);
+  P.tile = resample::tile_for(R->p, R->q, R->width);
   P.out = out_dev;
   P.out_begin = out_begin_dev;
   P.row_stride = row_stride;
   P.L = L;
   const dim3 grid((L + P.tile - 1) / P.tile, N), block(resample::kThreads);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const bool sf = src_dtype == RCED_PCM_F32, of = out_dtype == RCED_PCM_F32;
-  if (sf && of)
-    hipLaunchKernelGGL((resample::resample_kernel<true, true>), grid, block, 0, st, P);
-  else if (sf)
-    hipLaunchKernelGGL((resample::resample_kernel<true, false>), grid, block, 0, st, P);
-  else if (of)
-    hipLaunchKernelGGL((resample::resample_kernel<false, true>), grid, block, 0, st, P);
-  else
-    hipLaunchKernelGGL((resample::resample_kernel<false, false>), grid, block, 0, st, P);
+  with_pcm_types(src_dtype, out_dtype, [&](auto sf, auto of) {
+    hipLaunchKernelGGL((resample::resample_kernel<decltype(sf)::value, decltype(of)::value>), grid, block, 0, st, P);
+  });
   HIP_TRY(hipGetLastError());
   return RCED_OK;
 }

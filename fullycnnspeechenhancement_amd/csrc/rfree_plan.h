@@ -1,22 +1,22 @@
 // The arithmetic of a free-running resampler lane (include/rced.h, "free-running resampler" section), apart from the
 // device: how many outputs a lane has emitted after F frames, the history it keeps, the tiling of a push, the ring of finished outputs
-// and the sizes of its buffers, from a ratio's table geometry.  Host only, no HIP: rfree_api.hip plans with it at create,
+// and the sizes of its buffers, from a ratio's table geometry.  Host only, no HIP: rstream_api.hip plans with it at create,
 // tests/rfree_plan_check.cpp checks it as a program of its own.
 #pragma once
 #include <cstddef>
 #include <cstdio>
 
-#include "rstream_plan.h"
+#include "resample_plan.h"
 
 namespace rced {
 namespace rfree {
 
-using rstream::kMaxPush;
-using rstream::kMaxStateBytes;
-using rstream::kRun;
-using rstream::kSpanMax;
-using rstream::kTileMax;
-using rstream::span_bound;
+using resample::kMaxPush;
+using resample::kMaxStateBytes;
+using resample::kRun;
+using resample::kSpanMax;
+using resample::kTileMax;
+using resample::span_bound;
 
 constexpr int kHead = 2;   // 8-byte words in front of a lane's history: the frames taken, the ring's read position
 
@@ -50,10 +50,7 @@ inline long long flush_bound(long long n, int p, int q, int right) { return ((n 
 // p / q in lowest terms with its table's `left` and `width`; out_bytes 2 or 4.  kPlanArg with a message in `err`.
 inline int plan(int p, int q, int left, int width, int max_in, int max_take, int prefill, int out_bytes, int lanes, Plan* out, char* err,
                 size_t err_len) {
-  if (p < 1 || q < 1 || left < 0 || width < 1 || left >= width) {
-    snprintf(err, err_len, "not a phase table: p %d q %d left %d width %d", p, q, left, width);
-    return kPlanArg;
-  }
+  if (resample::not_a_table(p, q, left, width, err, err_len)) return kPlanArg;
   if (out_bytes != 2 && out_bytes != 4) {
     snprintf(err, err_len, "an output sample has 2 or 4 bytes, got %d", out_bytes);
     return kPlanArg;
@@ -70,14 +67,7 @@ inline int plan(int p, int q, int left, int width, int max_in, int max_take, int
     snprintf(err, err_len, "prefill must be 0..%lld samples, got %d", kMaxPush, prefill);
     return kPlanArg;
   }
-  if (lanes < 1 || lanes > 65536) {
-    snprintf(err, err_len, "lanes must be 1..65536, got %d", lanes);
-    return kPlanArg;
-  }
-  if (span_bound(1, p, q, width) > kSpanMax) {
-    snprintf(err, err_len, "the ratio %d / %d: one output reaches %d frames, more than a workgroup stages (%d)", p, q, width, kSpanMax);
-    return kPlanArg;
-  }
+  if (resample::bad_lanes(lanes, err, err_len) || resample::too_wide(p, q, width, err, err_len)) return kPlanArg;
   Plan P;
   P.p = p;
   P.q = q;
@@ -97,11 +87,7 @@ inline int plan(int p, int q, int left, int width, int max_in, int max_take, int
     snprintf(err, err_len, "the ratio %d / %d needs %lld words of state per lane: too much for %d lanes", p, q, words, lanes);
     return kPlanArg;
   }
-  long long t = ((long long)(kSpanMax - width - 1) * p) / q + 1;   // the largest tile whose span fits ...
-  if (t > kTileMax) t = kTileMax;
-  const long long run = (long long)kRun * p;                        // ... a whole number of full runs where it holds one
-  if (t >= run) t -= t % run;
-  P.tile = (int)t;
+  P.tile = resample::tile_for(p, q, width);
   P.push_max = (int)push_max;
   P.flush_max = (int)flush_max;
   P.cap = (int)cap;

@@ -1,7 +1,7 @@
 // C ABI of the resampler lanes (include/rced.h, "streaming resampler" section): host side.  One launch per push on the
 // caller's stream (kernels_rstream.h), no allocation, no synchronisation; the arithmetic of a lane stream is rstream_plan.h's.
-// Below them the free-running lanes ("free-running resampler" section), in the same shape: kernels_rfree.h, which
-// stages frames with kernels_rstream.h's frame<>, and rfree_plan.h.
+// Below them the free-running lanes ("free-running resampler" section): kernels_rfree.h and rfree_plan.h.  Both
+// handles are an rced_lanes (format, device, table, state) with the family's plan; open, destroy and reset are written once, for that base.
 #include <hip/hip_runtime.h>
 
 #include <new>
@@ -13,15 +13,88 @@
 
 using namespace rced;
 
-struct rced_rstream {
-  rstream::Plan plan;
+struct rced_lanes {
   int sr_in = 0, sr_out = 0, channels = 1, src_dtype = 0, out_dtype = 0, lanes = 0, device = 0;
+  int words = 0;                   // 8-byte words of state per lane: the plan's
   const double* table = nullptr;   // the ratio's, on the device: resample_api.hip owns it
-  long long* state = nullptr;      // [lanes][plan.words]
-  hipStream_t last = nullptr;      // the stream of the latest push / finish: rced_rstream_reset is ordered on it
+  long long* state = nullptr;      // [lanes][words]
+  hipStream_t last = nullptr;      // the stream of the latest push / finish: a reset is ordered on it
+};
+
+struct rced_rstream : rced_lanes {
+  rstream::Plan plan;
+};
+struct rced_rfree : rced_lanes {
+  rfree::Plan plan;
 };
 
 namespace {
+
+// the refusals of a format that need no device, and the ratio's table geometry
+int check_format(int sr_in, int sr_out, int channels, int src_dtype, int out_dtype, int* p, int* q, int* left, int* width) {
+  if (int rc = check_rates(sr_in, sr_out)) return rc;
+  if (int rc = check_channels(channels)) return rc;
+  if (int rc = check_pcm_dtypes(src_dtype, out_dtype)) return rc;
+  return rced_resample_table(sr_in, sr_out, p, q, left, width, 0, nullptr);
+}
+
+// A handle of family H (`what` lanes) with a plan made: the device, the table on it, the state allocated and zeroed; nothing is left
+// behind on a failure.
+template <class H, class Plan>
+int open_lanes(const rced_lanes& format, const Plan& plan, const char* what, H** out) {
+  OnDevice on(format.device, kMaxDevices);
+  if (on.rc) return on.rc;
+  H* h = new (std::nothrow) H();
+  if (!h) return rced_fail(RCED_ERR_ALLOC, "host allocation failed");
+  static_cast<rced_lanes&>(*h) = format;
+  h->plan = plan;
+  h->words = plan.words;
+  int p, q, left, width;
+  int rc = rced_resample_table(h->sr_in, h->sr_out, &p, &q, &left, &width, h->device, &h->table);
+  const size_t bytes = (size_t)h->lanes * h->words * sizeof(long long);
+  if (!rc) {
+    const hipError_t e = hipMalloc(&h->state, bytes);
+    if (e != hipSuccess) rc = rced_fail(e == hipErrorOutOfMemory ? RCED_ERR_ALLOC : RCED_ERR_HIP, "hipMalloc(%s lanes): %s", what, hipGetErrorString(e));
+  }
+  if (!rc && hipMemset(h->state, 0, bytes) != hipSuccess) rc = rced_fail(RCED_ERR_HIP, "hipMemset(%s lane state)", what);
+  if (rc) {
+    (void)hipFree(h->state);
+    delete h;
+    return rc;
+  }
+  *out = h;
+  return RCED_OK;
+}
+
+template <class H>
+void destroy(H* h) {
+  if (!h) return;
+  DeviceGuard g(h->device);
+  (void)hipDeviceSynchronize();   // launches that still use the state
+  (void)hipFree(h->state);
+  delete h;
+}
+
+rced_lanes format_of(int sr_in, int sr_out, int channels, int src_dtype, int out_dtype, int lanes, int device) {
+  rced_lanes f;
+  f.sr_in = sr_in;
+  f.sr_out = sr_out;
+  f.channels = channels;
+  f.src_dtype = src_dtype;
+  f.out_dtype = out_dtype;
+  f.lanes = lanes;
+  f.device = device;
+  return f;
+}
+
+// one workgroup a lane: kernel(sf, of) launches the family's kernel for the handle's two PCM types on `st`
+template <class Kernel>
+int launch_lanes(rced_lanes* h, hipStream_t st, Kernel kernel) {
+  with_pcm_types(h->src_dtype, h->out_dtype, kernel);
+  HIP_TRY(hipGetLastError());
+  h->last = st;
+  return RCED_OK;
+}
 
 int launch(rced_rstream* h, const void* in, int in_frames, const int* flags, int finish, int K, void* out, int out_cols, int* out_counts,
            hipStream_t st) {
@@ -49,152 +122,16 @@ int launch(rced_rstream* h, const void* in, int in_frames, const int* flags, int
   P.out = out;
   P.out_cols = out_cols;
   P.out_counts = out_counts;
-  const dim3 grid(h->lanes), block(rstream::kThreads);
-  const bool sf = h->src_dtype == RCED_PCM_F32, of = h->out_dtype == RCED_PCM_F32;
-  if (sf && of)
-    hipLaunchKernelGGL((rstream::rstream_kernel<true, true>), grid, block, 0, st, P);
-  else if (sf)
-    hipLaunchKernelGGL((rstream::rstream_kernel<true, false>), grid, block, 0, st, P);
-  else if (of)
-    hipLaunchKernelGGL((rstream::rstream_kernel<false, true>), grid, block, 0, st, P);
-  else
-    hipLaunchKernelGGL((rstream::rstream_kernel<false, false>), grid, block, 0, st, P);
-  HIP_TRY(hipGetLastError());
-  h->last = st;
-  return RCED_OK;
+  return launch_lanes(h, st, [&](auto sf, auto of) {
+    hipLaunchKernelGGL((rstream::rstream_kernel<decltype(sf)::value, decltype(of)::value>), dim3(h->lanes), dim3(rstream::kThreads), 0, st, P);
+  });
 }
 
-}  // namespace
-
-extern "C" {
-
-int rced_rstream_create(int sr_in, int sr_out, int channels, int src_dtype, int out_dtype, int unit_in, int unit_out, int lanes, int max_units,
-                        int device, rced_rstream** out) {
-  return rced_rstream_create_ex(sr_in, sr_out, channels, src_dtype, out_dtype, unit_in, unit_out, lanes, max_units, -1, device, out);
-}
-
-int rced_rstream_create_ex(int sr_in, int sr_out, int channels, int src_dtype, int out_dtype, int unit_in, int unit_out, int lanes, int max_units,
-                           int delay, int device, rced_rstream** out) {
-  if (!out) return rced_fail(RCED_ERR_ARG, "out is NULL");
-  *out = nullptr;
-  if (sr_in <= 0 || sr_out <= 0) return rced_fail(RCED_ERR_ARG, "sample rates must be positive, got %d -> %d", sr_in, sr_out);
-  if (channels < 1) return rced_fail(RCED_ERR_ARG, "channels must be >= 1, got %d", channels);
-  if (src_dtype != RCED_PCM_S16 && src_dtype != RCED_PCM_F32)
-    return rced_fail(RCED_ERR_ARG, "src_dtype must be RCED_PCM_S16 or RCED_PCM_F32, got %d", src_dtype);
-  if (out_dtype != RCED_PCM_S16 && out_dtype != RCED_PCM_F32)
-    return rced_fail(RCED_ERR_ARG, "out_dtype must be RCED_PCM_S16 or RCED_PCM_F32, got %d", out_dtype);
-  // the ratio and the plan need no device: a refusal comes before one is looked for
-  int p, q, left, width;
-  if (int rc = rced_resample_table(sr_in, sr_out, &p, &q, &left, &width, 0, nullptr)) return rc;
-  rstream::Plan plan;
-  char err[256] = "";
-  if (rstream::plan(p, q, left, width, unit_in, unit_out, max_units, lanes, delay, &plan, err, sizeof err) != rstream::kPlanOk)
-    return rced_fail(RCED_ERR_ARG, "resampler lanes %d Hz -> %d Hz: %s", sr_in, sr_out, err);
-  if (int rc = check_device(device, kMaxDevices)) return rc;
-  DeviceGuard g(device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
-  rced_rstream* h = new (std::nothrow) rced_rstream();
-  if (!h) return rced_fail(RCED_ERR_ALLOC, "host allocation failed");
-  h->plan = plan;
-  h->sr_in = sr_in;
-  h->sr_out = sr_out;
-  h->channels = channels;
-  h->src_dtype = src_dtype;
-  h->out_dtype = out_dtype;
-  h->lanes = lanes;
-  h->device = device;
-  int rc = rced_resample_table(sr_in, sr_out, &p, &q, &left, &width, device, &h->table);
-  const size_t bytes = (size_t)lanes * plan.words * sizeof(long long);
-  if (!rc) {
-    const hipError_t e = hipMalloc(&h->state, bytes);
-    if (e != hipSuccess) rc = rced_fail(e == hipErrorOutOfMemory ? RCED_ERR_ALLOC : RCED_ERR_HIP, "hipMalloc(resampler lanes): %s", hipGetErrorString(e));
-  }
-  if (!rc && hipMemset(h->state, 0, bytes) != hipSuccess) rc = rced_fail(RCED_ERR_HIP, "hipMemset(resampler lane state)");
-  if (rc) {
-    (void)hipFree(h->state);
-    delete h;
-    return rc;
-  }
-  *out = h;
-  return RCED_OK;
-}
-
-void rced_rstream_destroy(rced_rstream* h) {
-  if (!h) return;
-  DeviceGuard g(h->device);
-  (void)hipDeviceSynchronize();   // launches that still use the state
-  (void)hipFree(h->state);
-  delete h;
-}
-
-int rced_rstream_delay(const rced_rstream* h) { return h ? h->plan.delay : -1; }
-
-int rced_rstream_push(rced_rstream* h, const void* pcm_dev, const int* active_dev, int K, void* out_dev, void* stream) {
-  if (!h) return rced_fail(RCED_ERR_ARG, "stream is NULL");
-  if (K < 1 || K > h->plan.max_units) return rced_fail(RCED_ERR_ARG, "K must be 1..max_units = %d, got %d", h->plan.max_units, K);
-  if (!pcm_dev || !out_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
-  DeviceGuard g(h->device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", h->device);
-  return launch(h, pcm_dev, K * h->plan.unit_in, active_dev, 0, K, out_dev, K * h->plan.unit_out, nullptr, static_cast<hipStream_t>(stream));
-}
-
-int rced_rstream_finish(rced_rstream* h, const void* tail_dev, const int* tail_counts_dev, void* out_dev, int* out_counts_dev, void* stream) {
-  if (!h) return rced_fail(RCED_ERR_ARG, "stream is NULL");
-  if (!tail_dev || !tail_counts_dev || !out_dev || !out_counts_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
-  DeviceGuard g(h->device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", h->device);
-  return launch(h, tail_dev, h->plan.unit_in, tail_counts_dev, 1, 0, out_dev, h->plan.finish_max, out_counts_dev, static_cast<hipStream_t>(stream));
-}
-
-int rced_rstream_started(rced_rstream* h, const int* active_dev, int* started_dev, void* stream) {
-  if (!h) return rced_fail(RCED_ERR_ARG, "stream is NULL");
-  if (!started_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
-  DeviceGuard g(h->device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", h->device);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(rstream::started_kernel, dim3((h->lanes + 255) / 256), dim3(256), 0, st, (const long long*)h->state, h->plan.words, active_dev,
-                     h->lanes, started_dev);
-  HIP_TRY(hipGetLastError());
-  h->last = st;
-  return RCED_OK;
-}
-
-int rced_rstream_reset(rced_rstream* h, int lane) {
-  if (!h) return rced_fail(RCED_ERR_ARG, "stream is NULL");
-  if (lane < -1 || lane >= h->lanes) return rced_fail(RCED_ERR_ARG, "lane must be -1 (all) or 0..%d, got %d", h->lanes - 1, lane);
-  DeviceGuard g(h->device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", h->device);
-  const size_t one = (size_t)h->plan.words * sizeof(long long);
-  if (lane < 0) HIP_TRY(hipMemsetAsync(h->state, 0, one * h->lanes, h->last));
-  else HIP_TRY(hipMemsetAsync(h->state + (size_t)lane * h->plan.words, 0, one, h->last));
-  return RCED_OK;
-}
-
-}  // extern "C"
-
-// ---- free-running lanes ----
-
-struct rced_rfree {
-  rfree::Plan plan;
-  int sr_in = 0, sr_out = 0, channels = 1, src_dtype = 0, out_dtype = 0, lanes = 0, device = 0;
-  const double* table = nullptr;   // the ratio's, on the device: resample_api.hip owns it
-  long long* state = nullptr;      // [lanes][plan.words]
-  hipStream_t last = nullptr;      // the stream of the latest push / finish: rced_rfree_reset is ordered on it
-};
-
-namespace {
-
-// the checks and the plan that need no device
+// the checks and the plan of free-running lanes that need no device
 int plan_for(int sr_in, int sr_out, int channels, int src_dtype, int out_dtype, int lanes, int max_frames, int max_take, int prefill,
              rfree::Plan* plan) {
-  if (sr_in <= 0 || sr_out <= 0) return rced_fail(RCED_ERR_ARG, "sample rates must be positive, got %d -> %d", sr_in, sr_out);
-  if (channels < 1) return rced_fail(RCED_ERR_ARG, "channels must be >= 1, got %d", channels);
-  if (src_dtype != RCED_PCM_S16 && src_dtype != RCED_PCM_F32)
-    return rced_fail(RCED_ERR_ARG, "src_dtype must be RCED_PCM_S16 or RCED_PCM_F32, got %d", src_dtype);
-  if (out_dtype != RCED_PCM_S16 && out_dtype != RCED_PCM_F32)
-    return rced_fail(RCED_ERR_ARG, "out_dtype must be RCED_PCM_S16 or RCED_PCM_F32, got %d", out_dtype);
   int p, q, left, width;
-  if (int rc = rced_resample_table(sr_in, sr_out, &p, &q, &left, &width, 0, nullptr)) return rc;
+  if (int rc = check_format(sr_in, sr_out, channels, src_dtype, out_dtype, &p, &q, &left, &width)) return rc;
   char err[256] = "";
   if (rfree::plan(p, q, left, width, max_frames, max_take, prefill, out_dtype == RCED_PCM_F32 ? 4 : 2, lanes, plan, err, sizeof err) !=
       rfree::kPlanOk)
@@ -228,24 +165,71 @@ int launch(rced_rfree* h, const void* in, int in_cols, const int* counts, const 
   P.out = out;
   P.out_cols = out_cols;
   P.out_counts = out_counts;
-  const dim3 grid(h->lanes), block(rfree::kThreads);
-  const bool sf = h->src_dtype == RCED_PCM_F32, of = h->out_dtype == RCED_PCM_F32;
-  if (sf && of)
-    hipLaunchKernelGGL((rfree::rfree_kernel<true, true>), grid, block, 0, st, P);
-  else if (sf)
-    hipLaunchKernelGGL((rfree::rfree_kernel<true, false>), grid, block, 0, st, P);
-  else if (of)
-    hipLaunchKernelGGL((rfree::rfree_kernel<false, true>), grid, block, 0, st, P);
-  else
-    hipLaunchKernelGGL((rfree::rfree_kernel<false, false>), grid, block, 0, st, P);
-  HIP_TRY(hipGetLastError());
-  h->last = st;
-  return RCED_OK;
+  return launch_lanes(h, st, [&](auto sf, auto of) {
+    hipLaunchKernelGGL((rfree::rfree_kernel<decltype(sf)::value, decltype(of)::value>), dim3(h->lanes), dim3(rfree::kThreads), 0, st, P);
+  });
 }
 
 }  // namespace
 
 extern "C" {
+
+int rced_rstream_create(int sr_in, int sr_out, int channels, int src_dtype, int out_dtype, int unit_in, int unit_out, int lanes, int max_units,
+                        int device, rced_rstream** out) {
+  return rced_rstream_create_ex(sr_in, sr_out, channels, src_dtype, out_dtype, unit_in, unit_out, lanes, max_units, -1, device, out);
+}
+
+int rced_rstream_create_ex(int sr_in, int sr_out, int channels, int src_dtype, int out_dtype, int unit_in, int unit_out, int lanes, int max_units,
+                           int delay, int device, rced_rstream** out) {
+  if (!out) return rced_fail(RCED_ERR_ARG, "out is NULL");
+  *out = nullptr;
+  // the ratio and the plan need no device: a refusal comes before one is looked for
+  int p, q, left, width;
+  if (int rc = check_format(sr_in, sr_out, channels, src_dtype, out_dtype, &p, &q, &left, &width)) return rc;
+  rstream::Plan plan;
+  char err[256] = "";
+  if (rstream::plan(p, q, left, width, unit_in, unit_out, max_units, lanes, delay, &plan, err, sizeof err) != rstream::kPlanOk)
+    return rced_fail(RCED_ERR_ARG, "resampler lanes %d Hz -> %d Hz: %s", sr_in, sr_out, err);
+  return open_lanes(format_of(sr_in, sr_out, channels, src_dtype, out_dtype, lanes, device), plan, "resampler", out);
+}
+
+void rced_rstream_destroy(rced_rstream* h) { destroy(h); }
+
+int rced_rstream_delay(const rced_rstream* h) { return h ? h->plan.delay : -1; }
+
+int rced_rstream_push(rced_rstream* h, const void* pcm_dev, const int* active_dev, int K, void* out_dev, void* stream) {
+  if (!h) return rced_fail(RCED_ERR_ARG, "stream is NULL");
+  if (K < 1 || K > h->plan.max_units) return rced_fail(RCED_ERR_ARG, "K must be 1..max_units = %d, got %d", h->plan.max_units, K);
+  if (!pcm_dev || !out_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
+  ON_DEVICE(h->device);
+  return launch(h, pcm_dev, K * h->plan.unit_in, active_dev, 0, K, out_dev, K * h->plan.unit_out, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int rced_rstream_finish(rced_rstream* h, const void* tail_dev, const int* tail_counts_dev, void* out_dev, int* out_counts_dev, void* stream) {
+  if (!h) return rced_fail(RCED_ERR_ARG, "stream is NULL");
+  if (!tail_dev || !tail_counts_dev || !out_dev || !out_counts_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
+  ON_DEVICE(h->device);
+  return launch(h, tail_dev, h->plan.unit_in, tail_counts_dev, 1, 0, out_dev, h->plan.finish_max, out_counts_dev, static_cast<hipStream_t>(stream));
+}
+
+int rced_rstream_started(rced_rstream* h, const int* active_dev, int* started_dev, void* stream) {
+  if (!h) return rced_fail(RCED_ERR_ARG, "stream is NULL");
+  if (!started_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
+  ON_DEVICE(h->device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(rstream::started_kernel, dim3((h->lanes + 255) / 256), dim3(256), 0, st, (const long long*)h->state, h->words, active_dev,
+                     h->lanes, started_dev);
+  HIP_TRY(hipGetLastError());
+  h->last = st;
+  return RCED_OK;
+}
+
+int rced_rstream_reset(rced_rstream* h, int lane) {
+  if (!h) return rced_fail(RCED_ERR_ARG, "stream is NULL");
+  return reset_lanes(h->state, h->words, h->lanes, lane, h->device, h->last);
+}
+
+// ---- free-running lanes ----
 
 long long rced_rfree_available(int sr_in, int sr_out, long long frames) {
   if (sr_in <= 0 || sr_out <= 0 || frames < 0) {
@@ -279,44 +263,10 @@ int rced_rfree_create(int sr_in, int sr_out, int channels, int src_dtype, int ou
   // the ratio and the plan need no device: a refusal comes before one is looked for
   rfree::Plan plan;
   if (int rc = plan_for(sr_in, sr_out, channels, src_dtype, out_dtype, lanes, max_frames, max_take, prefill, &plan)) return rc;
-  if (int rc = check_device(device, kMaxDevices)) return rc;
-  DeviceGuard g(device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
-  rced_rfree* h = new (std::nothrow) rced_rfree();
-  if (!h) return rced_fail(RCED_ERR_ALLOC, "host allocation failed");
-  h->plan = plan;
-  h->sr_in = sr_in;
-  h->sr_out = sr_out;
-  h->channels = channels;
-  h->src_dtype = src_dtype;
-  h->out_dtype = out_dtype;
-  h->lanes = lanes;
-  h->device = device;
-  int p, q, left, width;
-  int rc = rced_resample_table(sr_in, sr_out, &p, &q, &left, &width, device, &h->table);
-  const size_t bytes = (size_t)lanes * plan.words * sizeof(long long);
-  if (!rc) {
-    const hipError_t e = hipMalloc(&h->state, bytes);
-    if (e != hipSuccess)
-      rc = rced_fail(e == hipErrorOutOfMemory ? RCED_ERR_ALLOC : RCED_ERR_HIP, "hipMalloc(free-running lanes): %s", hipGetErrorString(e));
-  }
-  if (!rc && hipMemset(h->state, 0, bytes) != hipSuccess) rc = rced_fail(RCED_ERR_HIP, "hipMemset(free-running lane state)");
-  if (rc) {
-    (void)hipFree(h->state);
-    delete h;
-    return rc;
-  }
-  *out = h;
-  return RCED_OK;
+  return open_lanes(format_of(sr_in, sr_out, channels, src_dtype, out_dtype, lanes, device), plan, "free-running", out);
 }
 
-void rced_rfree_destroy(rced_rfree* h) {
-  if (!h) return;
-  DeviceGuard g(h->device);
-  (void)hipDeviceSynchronize();   // launches that still use the state
-  (void)hipFree(h->state);
-  delete h;
-}
+void rced_rfree_destroy(rced_rfree* h) { destroy(h); }
 
 int rced_rfree_push(rced_rfree* h, const void* pcm_dev, int in_cols, const int* counts_dev, void* out_dev, int out_cols, const int* take_dev,
                     void* stream) {
@@ -325,8 +275,7 @@ int rced_rfree_push(rced_rfree* h, const void* pcm_dev, int in_cols, const int* 
   if (out_cols < 0 || out_cols > h->plan.max_take)
     return rced_fail(RCED_ERR_ARG, "out_cols must be 0..max_take = %d, got %d", h->plan.max_take, out_cols);
   if ((in_cols && !pcm_dev) || (out_cols && !out_dev)) return rced_fail(RCED_ERR_ARG, "null pointer");
-  DeviceGuard g(h->device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", h->device);
+  ON_DEVICE(h->device);
   return launch(h, pcm_dev, in_cols, counts_dev, take_dev, 0, out_dev, out_cols, nullptr, static_cast<hipStream_t>(stream));
 }
 
@@ -335,20 +284,13 @@ int rced_rfree_finish(rced_rfree* h, const void* tail_dev, int in_cols, const in
   if (!h) return rced_fail(RCED_ERR_ARG, "lanes are NULL");
   if (in_cols < 0 || in_cols > h->plan.max_in) return rced_fail(RCED_ERR_ARG, "in_cols must be 0..max_frames = %d, got %d", h->plan.max_in, in_cols);
   if ((in_cols && !tail_dev) || !tail_counts_dev || !out_dev || !out_counts_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
-  DeviceGuard g(h->device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", h->device);
+  ON_DEVICE(h->device);
   return launch(h, tail_dev, in_cols, tail_counts_dev, nullptr, 1, out_dev, h->plan.finish_max, out_counts_dev, static_cast<hipStream_t>(stream));
 }
 
 int rced_rfree_reset(rced_rfree* h, int lane) {
   if (!h) return rced_fail(RCED_ERR_ARG, "lanes are NULL");
-  if (lane < -1 || lane >= h->lanes) return rced_fail(RCED_ERR_ARG, "lane must be -1 (all) or 0..%d, got %d", h->lanes - 1, lane);
-  DeviceGuard g(h->device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", h->device);
-  const size_t one = (size_t)h->plan.words * sizeof(long long);
-  if (lane < 0) HIP_TRY(hipMemsetAsync(h->state, 0, one * h->lanes, h->last));
-  else HIP_TRY(hipMemsetAsync(h->state + (size_t)lane * h->plan.words, 0, one, h->last));
-  return RCED_OK;
+  return reset_lanes(h->state, h->words, h->lanes, lane, h->device, h->last);
 }
 
 }  // extern "C"

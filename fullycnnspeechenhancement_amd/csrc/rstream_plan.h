@@ -5,14 +5,17 @@
 #include <cstddef>
 #include <cstdio>
 
+#include "resample_plan.h"
+
 namespace rced {
 namespace rstream {
 
-constexpr int kSpanMax = 6144;         // frames a workgroup stages: resample::kSpanMax (kernels_rstream.h asserts it)
-constexpr int kTileMax = 4096;         // outputs per staging pass, at most: resample::kTileMax
-constexpr int kRun = 64 * 4;           // outputs of one phase a wave takes at a time: 64 resample::kK
-constexpr long long kMaxPush = 1 << 24;   // frames or outputs of one lane and push
-constexpr size_t kMaxStateBytes = (size_t)1 << 32;
+using resample::kMaxPush;
+using resample::kMaxStateBytes;
+using resample::kRun;
+using resample::kSpanMax;
+using resample::kTileMax;
+using resample::span_bound;
 
 struct Plan {
   int p = 1, q = 1, left = 0, width = 1, right = 0;
@@ -26,9 +29,6 @@ struct Plan {
 
 enum { kPlanOk = 0, kPlanArg = 1 };
 
-// the span of `tile` consecutive outputs is at most ((tile - 1) q) / p + 1 + width frames (resample::span_bound)
-inline long long span_bound(long long tile, int p, int q, int width) { return ((tile - 1) * q) / p + 1 + width; }
-
 // The smallest D for which every output a push emits reaches only frames already pushed.  Output m of the offline result
 // reaches frame floor(m q / p) + right at most; a push that brings the lane to H units emits up to m = H unit_out - 1 - D and
 // holds H unit_in = H unit_out q / p frames: ceil((D + 1) q / p) >= right + 1, that is D = floor(right p / q).
@@ -41,10 +41,7 @@ inline long long history(int p, int q, int left, long long delay) { return (dela
 // lanes run a whole hop behind).  kPlanArg with a message in `err`.
 inline int plan(int p, int q, int left, int width, int unit_in, int unit_out, int max_units, int lanes, int delay, Plan* out, char* err,
                 size_t err_len) {
-  if (p < 1 || q < 1 || left < 0 || width < 1 || left >= width) {
-    snprintf(err, err_len, "not a phase table: p %d q %d left %d width %d", p, q, left, width);
-    return kPlanArg;
-  }
+  if (resample::not_a_table(p, q, left, width, err, err_len)) return kPlanArg;
   if (unit_in < 1 || unit_out < 1 || (long long)unit_in * p != (long long)unit_out * q) {
     snprintf(err, err_len, "units of %d frames in and %d samples out do not stand in the ratio %d / %d (unit_in * %d must equal unit_out * %d)",
              unit_in, unit_out, p, q, p, q);
@@ -55,10 +52,7 @@ inline int plan(int p, int q, int left, int width, int unit_in, int unit_out, in
              max_units, unit_in, unit_out);
     return kPlanArg;
   }
-  if (lanes < 1 || lanes > 65536) {
-    snprintf(err, err_len, "lanes must be 1..65536, got %d", lanes);
-    return kPlanArg;
-  }
+  if (resample::bad_lanes(lanes, err, err_len)) return kPlanArg;
   Plan P;
   P.p = p;
   P.q = q;
@@ -75,21 +69,14 @@ inline int plan(int p, int q, int left, int width, int unit_in, int unit_out, in
   }
   const long long d = delay < 0 ? dmin : delay;
   const long long hist = history(p, q, left, d);
-  if (span_bound(1, p, q, width) > kSpanMax) {
-    snprintf(err, err_len, "the ratio %d / %d: one output reaches %d frames, more than a workgroup stages (%d)", p, q, width, kSpanMax);
-    return kPlanArg;
-  }
+  if (resample::too_wide(p, q, width, err, err_len)) return kPlanArg;
   if (d > kMaxPush || hist > kMaxPush || (size_t)lanes * (size_t)(1 + hist) * 8 > kMaxStateBytes) {
     snprintf(err, err_len, "the ratio %d / %d needs %lld frames of history per lane: too much for %d lanes", p, q, hist, lanes);
     return kPlanArg;
   }
-  long long t = ((long long)(kSpanMax - width - 1) * p) / q + 1;   // the largest tile whose span fits ...
-  if (t > kTileMax) t = kTileMax;
-  const long long run = (long long)kRun * p;                        // ... a whole number of full runs where it holds one
-  if (t >= run) t -= t % run;
   P.delay = (int)d;
   P.hist = (int)hist;
-  P.tile = (int)t;
+  P.tile = resample::tile_for(p, q, width);
   P.finish_max = unit_out + (int)d;
   P.words = 1 + (int)hist;
   *out = P;

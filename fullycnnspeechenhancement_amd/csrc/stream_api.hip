@@ -120,8 +120,7 @@ int create(rced_model* m, int lanes, int max_hops, int nfft, int rebuild, bool f
   if (rebuild != RCED_STREAM_REBUILD_REFERENCE && rebuild != RCED_STREAM_REBUILD_OLA)
     return rced_fail(RCED_ERR_ARG, "rebuild must be RCED_STREAM_REBUILD_REFERENCE (0) or RCED_STREAM_REBUILD_OLA (1), got %d", rebuild);
   if (!m) return rced_fail(RCED_ERR_ARG, "model is NULL");
-  DeviceGuard g(m->device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", m->device);
+  ON_DEVICE(m->device);
   rced_stream* s = new (std::nothrow) rced_stream();
   if (!s) return rced_fail(RCED_ERR_ALLOC, "host allocation failed");
   s->model = m;
@@ -238,8 +237,7 @@ int rced_stream_push(rced_stream* s, const float* pcm_dev, const int* active_dev
   if (K < 1 || K > s->max_hops) return rced_fail(RCED_ERR_ARG, "K must be 1..max_hops = %d, got %d", s->max_hops, K);
   if (!pcm_dev || !out_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
   if (int rc = usable(s)) return rc;
-  DeviceGuard g(s->device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", s->device);
+  ON_DEVICE(s->device);
   return run(s, pcm_dev, active_dev, 0, K, out_dev, nullptr, static_cast<hipStream_t>(stream));
 }
 
@@ -247,20 +245,13 @@ int rced_stream_finish(rced_stream* s, const float* tail_dev, const int* tail_co
   if (!s) return rced_fail(RCED_ERR_ARG, "stream is NULL");
   if (!tail_dev || !tail_counts_dev || !out_dev || !out_counts_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
   if (int rc = usable(s)) return rc;
-  DeviceGuard g(s->device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", s->device);
+  ON_DEVICE(s->device);
   return run(s, tail_dev, tail_counts_dev, 1, finish_slots(s), out_dev, out_counts_dev, static_cast<hipStream_t>(stream));
 }
 
 int rced_stream_reset(rced_stream* s, int lane) {
   if (!s) return rced_fail(RCED_ERR_ARG, "stream is NULL");
-  if (lane < -1 || lane >= s->lanes) return rced_fail(RCED_ERR_ARG, "lane must be -1 (all) or 0..%d, got %d", s->lanes - 1, lane);
-  DeviceGuard g(s->device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", s->device);
-  const size_t one = s->state_floats * sizeof(float);
-  if (lane < 0) HIP_TRY(hipMemsetAsync(s->state, 0, one * s->lanes, s->last));
-  else HIP_TRY(hipMemsetAsync(s->state + (size_t)lane * s->state_floats, 0, one, s->last));
-  return RCED_OK;
+  return reset_lanes(s->state, (size_t)s->state_floats, s->lanes, lane, s->device, s->last);
 }
 
 }  // extern "C"

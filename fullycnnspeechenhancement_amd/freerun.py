@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _args, _lib
 from ._args import SAMPLE_RATE, STEP
-from .streaming import STREAM_DELAY, STREAM_MAX_HOPS, _DenoiserLanes, drain_hops
+from .streaming import STREAM_DELAY, STREAM_MAX_HOPS, _Chain, _DenoiserLanes, _Lanes, drain_hops
 
 
 @lru_cache(maxsize=None)
@@ -32,7 +32,7 @@ def free_available(sr_in, sr_out, frames):
     return -((-(frames - right) * p) // q) if frames > right else 0
 
 
-class FreeResampler(object):
+class FreeResampler(_Lanes):
     """resample_batch for audio that arrives in pieces of any size, for `lanes` independent streams at once, without a delay
     (rced_rfree_*).  A lane emits every output as soon as its last tap has arrived -- free_available(sr_in,
     sr_out, F) of them after F frames -- into a ring on the device that starts an utterance holding `prefill` zeros; a push hands
@@ -45,7 +45,7 @@ class FreeResampler(object):
     mirror of what every lane's ring holds, `.capacity` the ring's size: a push that would leave more than that in a ring, or take
     more than is there, is a ValueError before anything is launched."""
 
-    _h = None
+    _family = "rced_rfree"
 
     def __init__(self, sr_in, sr_out, lanes, channels=1, dtype="float32", out_dtype="float32", max_frames=4096, max_take=None, prefill=0,
                  device=0):
@@ -53,28 +53,26 @@ class FreeResampler(object):
         sr_in, sr_out = int(sr_in), int(sr_out)
         if sr_in < 1 or sr_out < 1:
             raise ValueError("both rates must be positive, got %d -> %d" % (sr_in, sr_out))
-        self._in, self._np_in, code = _args.pcm_format(dtype)
-        self._out, _, out_code = _args.pcm_format(out_dtype, "out_dtype")
+        code, out_code = _args.pcm_format(dtype)[2], _args.pcm_format(out_dtype, "out_dtype")[2]
         if int(channels) < 1:
             raise ValueError("channels must be >= 1, got %d" % channels)
         if max_take is None:
             max_take = -((-int(max_frames) * sr_out) // sr_in)
-        self.sr_in, self.sr_out, self.lanes, self.channels, self.device = sr_in, sr_out, int(lanes), int(channels), int(device)
-        self.dtype, self.out_dtype = dtype, out_dtype
+        self.sr_in, self.sr_out, self.lanes = sr_in, sr_out, int(lanes)
         self.max_frames, self.max_take, self.prefill = int(max_frames), int(max_take), int(prefill)
         lib = _lib.load()
         cap, fin = ctypes.c_int(), ctypes.c_int()
         _lib.check(lib.rced_rfree_plan(sr_in, sr_out, out_code, self.lanes, self.max_frames, self.max_take, self.prefill, None, None,
                                        ctypes.byref(cap), ctypes.byref(fin)))
-        self.capacity, self.finish_max = int(cap.value), int(fin.value)
+        self.capacity = int(cap.value)
         self._geo = _geometry(sr_in, sr_out)
         self._frames, self._taken = np.zeros(self.lanes, np.int64), np.zeros(self.lanes, np.int64)      # the host's mirror
         self.taken = [0] * self.lanes          # what the latest push took from every lane
         self._ints = {}
         h = ctypes.c_void_p()
-        _lib.check(lib.rced_rfree_create(sr_in, sr_out, self.channels, code, out_code, self.lanes, self.max_frames, self.max_take, self.prefill,
-                                         self.device, ctypes.byref(h)))
-        self._h = h
+        _lib.check(lib.rced_rfree_create(sr_in, sr_out, int(channels), code, out_code, self.lanes, self.max_frames, self.max_take, self.prefill,
+                                         int(device), ctypes.byref(h)))
+        self._open(h, lanes, device, int(channels), dtype, out_dtype, int(fin.value))
 
     def _avail(self, frames):
         """free_available for an int64 array of frame counts."""
@@ -151,9 +149,8 @@ class FreeResampler(object):
         cdev = self._dev_ints(got) if (got != n).any() else None
         tdev = self._dev_ints(take) if (take[got >= 0] != cols).any() else None
         stream = torch.cuda.current_stream(dev)
-        _lib.check(_lib.load().rced_rfree_push(self._h, x.data_ptr() if n else None, n, cdev.data_ptr() if cdev is not None else None,
-                                               out.data_ptr() if cols else None, cols, tdev.data_ptr() if tdev is not None else None,
-                                               stream.cuda_stream))
+        _lib.check(self._c["push"](self._h, x.data_ptr() if n else None, n, cdev.data_ptr() if cdev is not None else None,
+                                   out.data_ptr() if cols else None, cols, tdev.data_ptr() if tdev is not None else None, stream.cuda_stream))
         _args.keep_alive(stream, x)
         self._frames += np.maximum(got, 0)
         self._taken += take
@@ -161,11 +158,10 @@ class FreeResampler(object):
         return out
 
     def _frames_of(self, pcm):
-        shape = tuple(pcm.shape)
-        per = self.channels if len(shape) == 2 else 1
-        n = shape[1] // per if len(shape) in (2, 3) else -1
-        if n < 0 or n > self.max_frames or shape not in ((self.lanes, n * self.channels), (self.lanes, n, self.channels)):
-            raise ValueError("pcm must be [lanes = %d, 0..%d frames] of %d channels, got %s" % (self.lanes, self.max_frames, self.channels, shape))
+        n = _args.pcm_units(pcm.shape, self.lanes, self.channels)
+        if n < 0 or n > self.max_frames:
+            raise ValueError("pcm must be [lanes = %d, 0..%d frames] of %d channels, got %s"
+                             % (self.lanes, self.max_frames, self.channels, tuple(pcm.shape)))
         return n
 
     def push(self, pcm, counts=None, take=None):
@@ -215,8 +211,8 @@ class FreeResampler(object):
         tdev, cdev = torch.as_tensor(tail[:, :width].copy(), device=dev), torch.as_tensor(counts, device=dev)
         out = torch.empty((self.lanes, self.finish_max), dtype=self._out, device=dev)
         owed = torch.empty((self.lanes,), dtype=torch.int32, device=dev)
-        _lib.check(_lib.load().rced_rfree_finish(self._h, tdev.data_ptr(), width, cdev.data_ptr(), out.data_ptr(), owed.data_ptr(),
-                                                 _args.current_stream(out.device)))
+        _lib.check(self._c["finish"](self._h, tdev.data_ptr(), width, cdev.data_ptr(), out.data_ptr(), owed.data_ptr(),
+                                     _args.current_stream(out.device)))
         out, owed = out.cpu().numpy(), owed.cpu().numpy()
         for i, lane in enumerate(lanes):
             got[i].append(out[lane, :owed[lane]].copy())
@@ -224,22 +220,9 @@ class FreeResampler(object):
         self.owed = [int(owed[lane]) for lane in lanes]      # the counts the device reported for its finish launch
         return [np.concatenate(g) for g in got]
 
-    def reset(self, lane=-1):
-        """Back to the start of an utterance, without output: one lane, or (-1) all of them."""
-        _lib.check(_lib.load().rced_rfree_reset(self._h, int(lane)))
-        for s in (range(self.lanes) if int(lane) < 0 else [int(lane)]):
+    def _on_reset(self, lane):
+        for s in (range(self.lanes) if lane < 0 else [lane]):
             self._frames[s] = self._taken[s] = 0
-
-    def close(self):
-        if self._h is not None:
-            try:
-                _lib.load().rced_rfree_destroy(self._h)
-            except Exception:
-                pass
-            self._h = None
-
-    def __del__(self):
-        self.close()
 
 
 def _block_plan(block, sample_rate, output_rate):
@@ -286,7 +269,7 @@ def block_delay(block, sample_rate=8000, output_rate=None):
     return z + STREAM_DELAY * rout // SAMPLE_RATE
 
 
-class BlockDenoiser(object):
+class BlockDenoiser(_Chain):
     """PCM in, PCM out, a fixed block of any size at a time, at the capture device's rate, for `lanes` independent streams at once
     (DESIGN.md 3.4h).  process() takes [lanes, block] frames at sample_rate and returns [lanes, block * output_rate / sample_rate]
     float32 samples on every call, without synchronisation: free-running lanes (FreeResampler) down to 8 kHz -- at 8 kHz in, the
@@ -303,12 +286,9 @@ class BlockDenoiser(object):
     def __init__(self, model_or_engine, lanes, block, sample_rate=8000, output_rate=None, channels=1, dtype="float32", nfft=512,
                  rebuild="reference", framing=None):
         from .streaming import stream_framing
-        self._down = self._denoiser = self._up = None
         self.rebuild = _args.check_rebuild(rebuild)
         stream_framing(framing, self.rebuild, block=(int(block), None))      # None or Framing() only: a framing has no block form yet
-        self.model = getattr(model_or_engine, "model", model_or_engine)
-        if getattr(self.model, "_handle", None) is None:
-            raise ValueError("BlockDenoiser needs an inference model (Model(is_training=False)) or an engine that holds one")
+        self._take_model(model_or_engine, "BlockDenoiser")
         self.lanes, self.block, self.nfft, self.device = int(lanes), int(block), int(nfft), self.model.device
         self.sample_rate, self.channels, self.dtype = int(sample_rate), int(channels), dtype
         self.output_rate = SAMPLE_RATE if output_rate is None else int(output_rate)
@@ -323,9 +303,6 @@ class BlockDenoiser(object):
         self._up = FreeResampler(SAMPLE_RATE, self.output_rate, self.lanes, max_frames=STEP * self.max_hops, max_take=self.block_out,
                                  prefill=self.prefill, device=self.device)
         self._frames = np.zeros(self.lanes, np.int64)
-
-    def _stages(self):
-        return [s for s in (self._down, self._denoiser, self._up) if s is not None]
 
     def process(self, pcm, active=None):
         """pcm [lanes, block] (interleaved: [lanes, block * channels] or [lanes, block, channels]) of `dtype`: the next block of
@@ -381,17 +358,6 @@ class BlockDenoiser(object):
             self._frames[lane] = 0
         return out
 
-    def reset(self, lane=-1):
-        """Back to the start of an utterance, without output: one lane, or (-1) all of them."""
-        for stage in self._stages():
-            stage.reset(lane)
-        for s in (range(self.lanes) if int(lane) < 0 else [int(lane)]):
+    def _on_reset(self, lane):
+        for s in (range(self.lanes) if lane < 0 else [lane]):
             self._frames[s] = 0
-
-    def close(self):
-        for stage in self._stages():
-            stage.close()
-        self._down = self._denoiser = self._up = None
-
-    def __del__(self):
-        self.close()

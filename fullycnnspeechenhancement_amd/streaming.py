@@ -12,16 +12,16 @@ STREAM_DELAY, STREAM_FINISH_MAX, STREAM_MAX_HOPS = 640, 768, 64     # rced.h: RC
 
 
 class _Lanes(object):
-    """What both kinds of lanes are: a handle of the library and `lanes` streams behind it on cuda:`device`, each taking units of
-    unit_in frames of `channels` interleaved values of `dtype` and handing out units of unit_out samples of out_dtype; a
-    finish hands out at most finish_max samples a lane.  A subclass names its family of entry points (push, finish, reset,
-    destroy) and creates its handle."""
+    """What every kind of lanes is: a handle of the library and `lanes` streams behind it on cuda:`device`, each taking frames of
+    `channels` interleaved values of `dtype` and handing out samples of out_dtype; a finish hands out at most finish_max samples a
+    lane.  A subclass names its family of entry points (push, finish, reset, destroy) and creates its handle.  push and finish
+    here are those of lanes that count in units: unit_in frames in, unit_out samples out."""
 
-    _family = None      # "rced_stream" or "rced_rstream"
+    _family = None      # "rced_stream", "rced_rstream" or "rced_rfree"
     _h = None
 
-    def _open(self, h, lanes, device, unit_in, unit_out, channels, dtype, out_dtype, finish_max):
-        self.lanes, self.device, self.unit_in, self.unit_out, self.channels = int(lanes), int(device), unit_in, unit_out, channels
+    def _open(self, h, lanes, device, channels, dtype, out_dtype, finish_max):
+        self.lanes, self.device, self.channels = int(lanes), int(device), channels
         self.dtype, self.out_dtype, self.finish_max = dtype, out_dtype, finish_max
         self._in, self._np_in, _ = _args.pcm_format(dtype)
         self._out = _args.pcm_format(out_dtype)[0]
@@ -44,12 +44,10 @@ class _Lanes(object):
         idle (state untouched, zeros out).  A CUDA tensor gives a CUDA tensor (no synchronisation), an ndarray an ndarray."""
         import torch
         as_torch = hasattr(pcm, "is_cuda")
-        shape = tuple(pcm.shape)
-        per = self.unit_in * (self.channels if len(shape) == 2 else 1)
-        k = shape[1] // per if len(shape) in (2, 3) else 0
-        if k < 1 or shape not in ((self.lanes, k * self.unit_in * self.channels), (self.lanes, k * self.unit_in, self.channels)):
+        k = _args.pcm_units(pcm.shape, self.lanes, self.channels, self.unit_in)
+        if k < 1:
             raise ValueError("pcm must be [lanes = %d, K * %d frames] of %d channels with K >= 1, got %s"
-                             % (self.lanes, self.unit_in, self.channels, shape))
+                             % (self.lanes, self.unit_in, self.channels, tuple(pcm.shape)))
         x = _args.to_device(pcm, self._in, self.device, "pcm")
         act = self._active(active) if active is not None else None
         out = torch.empty((self.lanes, k * self.unit_out), dtype=self._out, device=x.device)
@@ -77,6 +75,10 @@ class _Lanes(object):
     def reset(self, lane=-1):
         """Back to the start of an utterance, without output: one lane, or (-1) all of them."""
         _lib.check(self._c["reset"](self._h, int(lane)))
+        self._on_reset(int(lane))
+
+    def _on_reset(self, lane):
+        """what the host keeps of a lane (or, -1, of all) goes back to the start with it"""
 
     def close(self):
         if self._h is not None:
@@ -144,7 +146,8 @@ class StreamingResampler(_Lanes):
         _lib.check(_lib.load().rced_rstream_create_ex(sr_in, sr_out, int(channels), code, out_code, unit_in, unit_out, int(lanes),
                                                       self.max_units, -1 if delay is None else int(delay), int(device), ctypes.byref(h)))
         self.delay = int(_lib.load().rced_rstream_delay(h))
-        self._open(h, lanes, device, unit_in, unit_out, int(channels), dtype, out_dtype, unit_out + self.delay)
+        self.unit_in, self.unit_out = unit_in, unit_out
+        self._open(h, lanes, device, int(channels), dtype, out_dtype, unit_out + self.delay)
 
     def started(self, active=None):
         """[lanes] int32 on the device: 1 where the lane is active and has taken a unit since the start of its utterance
@@ -171,14 +174,14 @@ class _DenoiserLanes(_Lanes):
         import ctypes
         h = ctypes.c_void_p()
         lib, code = _lib.load(), _args.REBUILDS.index(rebuild)              # RCED_STREAM_REBUILD_REFERENCE = 0, _OLA = 1
+        self.unit_in = self.unit_out = STEP if framing is None else framing.stride
         if framing is None:
             _lib.check(lib.rced_stream_create_ex(model._handle, int(lanes), int(max_hops), int(nfft), code, ctypes.byref(h)))
-            self._open(h, lanes, model.device, STEP, STEP, 1, "float32", "float32", STREAM_FINISH_MAX)
+            self._open(h, lanes, model.device, 1, "float32", "float32", STREAM_FINISH_MAX)
             return
         _lib.check(lib.rced_stream_create_fr(model._handle, int(lanes), int(max_hops), int(nfft), code, framing.window, framing.stride,
                                              framing.code, ctypes.byref(h)))
-        self._open(h, lanes, model.device, framing.stride, framing.stride, 1, "float32", "float32",
-                   int(lib.rced_stream_finish_max_fr(framing.window, framing.stride)))
+        self._open(h, lanes, model.device, 1, "float32", "float32", int(lib.rced_stream_finish_max_fr(framing.window, framing.stride)))
 
 
 def stream_framing(framing, rebuild="ola", **others):
@@ -239,7 +242,39 @@ def drain_hops(n_lanes, push, finish, lanes, seqs):
     return [np.concatenate(g + [np.asarray(r)]) for g, r in zip(got, rest)]
 
 
-class StreamingDenoiser(object):
+class _Chain(object):
+    """What StreamingDenoiser and BlockDenoiser (freerun.py) are: a model's denoiser lanes between optional lanes down to 8 kHz and
+    up again, reset and closed together."""
+
+    _down = _denoiser = _up = None
+
+    def _take_model(self, model_or_engine, name):
+        self.model = getattr(model_or_engine, "model", model_or_engine)
+        if getattr(self.model, "_handle", None) is None:
+            raise ValueError("%s needs an inference model (Model(is_training=False)) or an engine that holds one" % name)
+
+    def _stages(self):
+        return [s for s in (self._down, self._denoiser, self._up) if s is not None]
+
+    def reset(self, lane=-1):
+        """Back to the start of an utterance, without output: one lane, or (-1) all of them."""
+        for stage in self._stages():
+            stage.reset(lane)
+        self._on_reset(int(lane))
+
+    def _on_reset(self, lane):
+        """what the host keeps of a lane (or, -1, of all) goes back to the start with it"""
+
+    def close(self):
+        for stage in self._stages():
+            stage.close()
+        self._down = self._denoiser = self._up = None
+
+    def __del__(self):
+        self.close()
+
+
+class StreamingDenoiser(_Chain):
     """PCM in, PCM out, a hop (128 samples, 16 ms) at a time, for `lanes` independent streams at once (rced_stream_*,
     DESIGN.md 3.4d).  A lane's output is InferenceEngine.denoise_pcm of everything pushed before `finish`, delayed by
     STREAM_DELAY = 640 samples: zeros first, and `finish` hands out what is still owed.  All state lives on the device; a
@@ -267,11 +302,8 @@ class StreamingDenoiser(object):
 
     def __init__(self, model_or_engine, lanes, max_hops=8, nfft=512, sample_rate=8000, channels=1, dtype="float32", output_rate=None,
                  rebuild="reference", framing=None):
-        self._down = self._denoiser = self._up = None
         self.rebuild = _args.check_rebuild(rebuild)
-        self.model = getattr(model_or_engine, "model", model_or_engine)
-        if getattr(self.model, "_handle", None) is None:
-            raise ValueError("StreamingDenoiser needs an inference model (Model(is_training=False)) or an engine that holds one")
+        self._take_model(model_or_engine, "StreamingDenoiser")
         self.framing = stream_framing(framing, self.rebuild, sample_rate=(int(sample_rate), SAMPLE_RATE), channels=(int(channels), 1),
                                       dtype=(dtype, "float32"), output_rate=(output_rate, None))
         self.lanes, self.max_hops, self.nfft, self.device = int(lanes), int(max_hops), int(nfft), self.model.device
@@ -292,9 +324,6 @@ class StreamingDenoiser(object):
         if self.output_rate is not None and self.output_rate != SAMPLE_RATE:
             self._up = StreamingResampler(SAMPLE_RATE, self.output_rate, self.lanes, unit_in=STEP, max_units=self.max_hops,
                                           device=self.device)
-
-    def _stages(self):
-        return [s for s in (self._down, self._denoiser, self._up) if s is not None]
 
     def _chain(self):
         """(push, finish) of every stage, in order"""
@@ -345,16 +374,3 @@ class StreamingDenoiser(object):
         for push, finish in chain[1:]:
             out = self._drain(push, finish, lanes, out)
         return out
-
-    def reset(self, lane=-1):
-        """Back to the start of an utterance, without output: one lane, or (-1) all of them."""
-        for stage in self._stages():
-            stage.reset(lane)
-
-    def close(self):
-        for stage in self._stages():
-            stage.close()
-        self._down = self._denoiser = self._up = None
-
-    def __del__(self):
-        self.close()
