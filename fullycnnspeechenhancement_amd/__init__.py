@@ -14,4 +14,12 @@ from . import audio, loader, metrics, spec, weights  # noqa: F401
 from .audio import BlockDenoiser, FreeResampler, StreamingDenoiser, StreamingResampler  # noqa: F401
 
 __all__ = ["FullyCNNSEModel", "FullyCNNSEModelV2", "FullyCNNSEModelV3", "build_model", "conv_bn_relu",
-           "FullyCNNTester", "InferenceEngine", "FullyCNNTrainer", "StreamingDenoiser", "StreamingResampler", "BlockDenoiser", "FreeResampler", "audio", "loader", "metrics", "spec", "weights"]
+           "FullyCNNTester", "InferenceEngine", "FullyCNNTrainer", "DataParallelTrainer", "StreamingDenoiser", "StreamingResampler", "BlockDenoiser", "FreeResampler", "audio", "loader", "metrics", "spec", "weights"]
+
+
+def __getattr__(name):
+    """DataParallelTrainer lives in .dist, which imports torch.distributed: loaded on first use."""
+    if name == "DataParallelTrainer":
+        from .dist import DataParallelTrainer
+        return DataParallelTrainer
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -39,6 +39,11 @@ struct LayerOff {   // float offsets into the variable blob
   size_t kernel, bias, gamma, beta, mmean, mvar;
   int cin, cout, cout4, cin4, K;
 };
+// The fp64 exchange buffer of the sharded step (rced_train_grad / rced_train_apply), per BatchNorm layer in layer order:
+// (S1, S2) = (sum z, sum z^2) of the reference's channels, interleaved, then the pixel count.  soff: the layer's first
+// double, -1 without BatchNorm; xcout: the reference's channel count (cout: the even-padded one); mmean / mvar: the
+// moving statistics' float offsets in the internal blob.
+struct ShardArgs { int soff[kMaxLayers], xcout[kMaxLayers], cout[kMaxLayers], mmean[kMaxLayers], mvar[kMaxLayers]; };
 }  // namespace
 
 struct rced_trainer {
@@ -80,6 +85,12 @@ struct rced_trainer {
   std::vector<float*> out, z, G;   // out/G indexed by tensor id (0 unused), z by layer
   float* D = nullptr;
   long long global_step = 0;
+  // the sharded step: x2i on the device, every BatchNorm layer's (S1, S2) of the last rced_train_grad forward
+  // ([layers][2 * kMaxC] doubles), and where they go in the fp64 exchange buffer (xstats doubles)
+  int* x2i_dev = nullptr;
+  double* stash = nullptr;
+  ShardArgs shard{};
+  size_t xstats = 0;
   std::vector<void*> owned;       // every device allocation made by rced_train_create
   std::vector<void*> act_bases;   // the allocations behind out / z / G / D, made for a pixel count (ensure_acts)
   template <class T>
@@ -437,6 +448,51 @@ __global__ void tiny_gamma_scan(const float* __restrict__ params, TinyScanArgs a
   const int any = __syncthreads_or(tiny);
   if (c == 0) flags[l] = any;
 }
+
+// ---- the sharded step: one shard's gradient and statistics sums out into the caller's exchange buffers, and back ----
+// One element per thread with its own read-modify-write (no atomics): the sum over shards is formed in call order.
+constexpr int kShardThreads = 128;   // >= 2 * kMaxC + 1 entries of a layer
+static_assert(2 * train::kMaxC + 1 <= kShardThreads, "one thread per statistics entry of a layer");
+
+// g[e] (+)= grads[x2i[e]]: the internal (even-padded) gradient in the reference's blob order
+__global__ void shard_grad_out(const float* __restrict__ grads, const int* __restrict__ x2i, size_t n, float* __restrict__ g,
+                               int accumulate) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  const float v = grads[x2i[e]];
+  g[e] = accumulate ? g[e] + v : v;
+}
+// one workgroup per layer: s[soff + i] (+)= the layer's stashed (S1, S2) entry i < 2 xcout, the pixel count behind them
+__global__ void shard_stats_out(const double* __restrict__ stash, ShardArgs a, double P, double* __restrict__ s, int accumulate) {
+  const int l = blockIdx.x, i = threadIdx.x;
+  if (a.soff[l] < 0 || i > 2 * a.xcout[l]) return;
+  const double v = i < 2 * a.xcout[l] ? stash[(size_t)l * 2 * train::kMaxC + i] : P;
+  double* d = s + a.soff[l] + i;
+  *d = accumulate ? *d + v : v;
+}
+// grads[x2i[e]] = g[e] (phantom entries were zeroed before)
+__global__ void shard_grad_in(const float* __restrict__ g, const int* __restrict__ x2i, size_t n, float* __restrict__ grads) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n) grads[x2i[e]] = g[e];
+}
+// one workgroup per layer, one thread per channel: the moving statistics from the summed (S1, S2, P), by bn_finish's
+// kFinStats expressions.  A phantom channel has z = 0 everywhere: S1 = S2 = 0, as the unsharded step sees it.
+__global__ void shard_moving_update(const double* __restrict__ s, ShardArgs a, float momentum, float* __restrict__ params) {
+  const int l = blockIdx.x, c = threadIdx.x;
+  if (a.soff[l] < 0 || c >= a.cout[l]) return;
+  const double* sl = s + a.soff[l];
+  const bool real = c < a.xcout[l];
+  const double P = sl[2 * a.xcout[l]];
+  const double s1 = real ? sl[2 * c] : 0.0, s2 = real ? sl[2 * c + 1] : 0.0;
+  float* moving_mean = params + a.mmean[l];
+  float* moving_var = params + a.mvar[l];
+  const double m = s1 / P;
+  double var = s2 / P - m * m;
+  if (var < 0.0) var = 0.0;
+  const double unbiased = P > 1.0 ? var * P / (P - 1.0) : var;
+  moving_mean[c] = (float)((double)momentum * (double)moving_mean[c] + (1.0 - (double)momentum) * m);
+  moving_var[c] = (float)((double)momentum * (double)moving_var[c] + (1.0 - (double)momentum) * unbiased);
+}
 }  // namespace
 
 extern "C" {
@@ -556,6 +612,20 @@ int rced_train_create(int variant, const float* blob, size_t n_floats, int batch
   HIP_TRY(t->alloc(&t->sums, (train::kMaxC * 2 + 2) * sizeof(double)));
   t->redo = reinterpret_cast<int*>(t->sums + train::kMaxC * 2);
   HIP_TRY(hipMemset(t->redo, 0, 2 * sizeof(double)));
+  // the sharded step's exchange layout: the reference's blob order for the gradient, (S1, S2)[xcout] + P per BatchNorm layer
+  for (int l = 0; l < kMaxLayers; ++l) {
+    const bool bn = l < L && xnet->layer[l].use_norm;
+    t->shard.soff[l] = bn ? (int)t->xstats : -1;
+    t->shard.xcout[l] = bn ? xnet->layer[l].cout : 0;
+    t->shard.cout[l] = bn ? net->layer[l].cout : 0;
+    t->shard.mmean[l] = bn ? (int)t->off[l].mmean : 0;
+    t->shard.mvar[l] = bn ? (int)t->off[l].mvar : 0;
+    if (bn) t->xstats += 2 * (size_t)xnet->layer[l].cout + 1;
+  }
+  HIP_TRY(t->alloc(&t->x2i_dev, t->xvars * sizeof(int)));
+  HIP_TRY(hipMemcpy(t->x2i_dev, t->x2i.data(), t->xvars * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(t->alloc(&t->stash, (size_t)kMaxLayers * 2 * train::kMaxC * sizeof(double)));
+  HIP_TRY(hipMemset(t->stash, 0, (size_t)kMaxLayers * 2 * train::kMaxC * sizeof(double)));
   HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&t->tiny_host), kMaxLayers * sizeof(int), hipHostMallocMapped));
   HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&t->tiny_dev), t->tiny_host, 0));
   for (int l = 0; l < kMaxLayers; ++l) {
@@ -644,13 +714,39 @@ int rced_train_set_state(rced_trainer* t, const float* m_blob_host, const float*
 }  // extern "C"
 
 namespace {
+// Adam (TF form, trainer.py:175-179) from t->grads, global_step += 1, and the tiny-gamma scan behind it.
+// global_step: the reference fetches it in the same sess.run as train_op (trainer.py:186-191); TF1 orders a read and an
+// assign_add in one run only through control dependencies, and slim.learning.create_train_op makes train_op =
+// (increment global_step, then return the loss), so the fetched value is unordered against the increment in principle.
+// This library returns the POST-increment value, deterministically: after the first step train_step returns 1 and
+// the loop's next learning rate is noam(1) (trainer.py:215, step = global_step + 1 = 2).  See DESIGN.md 3.5.
+void adam_and_scan(rced_trainer* t, float lr, hipStream_t st) {
+  const NetSpec& net = *t->net;
+  const int L = net.n_layers;
+  t->global_step += 1;
+  const double tt = (double)t->global_step;
+  const float lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow((double)kAdamB2, tt)) / (1.0 - std::pow((double)kAdamB1, tt)));
+  hipLaunchKernelGGL(train::adam_step, dim3((unsigned)((t->nvars + train::kThreads - 1) / train::kThreads)),
+                     dim3(train::kThreads), 0, st, t->params, (const float*)t->grads, t->m, t->v,
+                     (const unsigned char*)t->trainable, t->nvars, lr_t, kAdamB1, kAdamB2, kAdamEps);
+  TinyScanArgs ta;
+  for (int l = 0; l < kMaxLayers; ++l) {
+    ta.gamma_off[l] = l < L && net.layer[l].use_norm ? (int)t->off[l].gamma : -1;
+    ta.cout[l] = l < L ? net.layer[l].cout : 0;
+  }
+  hipLaunchKernelGGL(tiny_gamma_scan, dim3(kMaxLayers), dim3(64), 0, st, (const float*)t->params, ta, t->tiny_dev);
+}
+
 // pred_dev != nullptr: forward only (rced_train_forward) -- batch-statistics BatchNorm, nothing is updated, the
-// prediction is copied to pred_dev.  Otherwise the full step.
+// prediction is copied to pred_dev.  g_out != nullptr: one shard of the sharded step (rced_train_grad) -- forward, loss and
+// backward as in the step, nothing is updated either; the gradient and every BatchNorm layer's (sum z, sum z^2, pixels) go
+// into (or, accumulate, are added to) g_out / s_out.  Otherwise the full step.
 int train_run(rced_trainer* t, const float* x_dev, const float* y_dev, float* pred_dev, int N, int T, float lr,
-              double* loss_out, void* stream) {
+              double* loss_out, void* stream, float* g_out = nullptr, double* s_out = nullptr, int accumulate = 0) {
   if (!t) return rced_fail(RCED_ERR_ARG, "trainer is NULL");
   if (N <= 0 || T <= 0 || !x_dev || (!y_dev && !pred_dev)) return rced_fail(RCED_ERR_ARG, "bad batch");
-  const bool forward_only = pred_dev != nullptr;
+  const bool forward_only = pred_dev != nullptr, shard = g_out != nullptr;
+  const float momentum = forward_only || shard ? 1.f : kBnMomentum;   // momentum 1: the moving statistics stay as they are
   DeviceGuard g(t->device);
   if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", t->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -769,15 +865,18 @@ int train_run(rced_trainer* t, const float* x_dev, const float* y_dev, float* pr
     const size_t n = P * s.cout;
     if (pl.stats == plan::Stats::Conv) {
       FinishArgs fa{};
-      fa.P = (double)P; fa.eps = kBnEps; fa.momentum = forward_only ? 1.f : kBnMomentum;   // momentum 1: the moving statistics stay as they are
+      fa.P = (double)P; fa.eps = kBnEps; fa.momentum = momentum;
       fa.mu_out = t->mu[l]; fa.rstd_out = t->rstd[l]; fa.moving_mean = t->params + f.mmean; fa.moving_var = t->params + f.mvar;
-      hipLaunchKernelGGL(bn_finish, dim3(1), dim3(1024), 0, st, (const double*)t->part, stat_parts, s.cout, t->sums, (int)kFinStats, fa,
-                         (const int*)nullptr);
+      // (a shard keeps the layer's (S1, S2) for the exchange buffer: the kernel writes them where it is told to)
+      hipLaunchKernelGGL(bn_finish, dim3(1), dim3(1024), 0, st, (const double*)t->part, stat_parts, s.cout,
+                         shard ? t->stash + (size_t)l * 2 * train::kMaxC : t->sums, (int)kFinStats, fa, (const int*)nullptr);
     } else if (pl.stats == plan::Stats::Reduce) {
       if (int rc = reduce_channels(t, t->z[l], t->z[l], nullptr, nullptr, P, s.cout, st)) return rc;
       hipLaunchKernelGGL(train::bn_stats_finish, dim3(1), dim3(64), 0, st, (const double*)t->sums, (double)P, s.cout,
-                         kBnEps, forward_only ? 1.f : kBnMomentum, t->mu[l], t->rstd[l], t->params + f.mmean,
-                         t->params + f.mvar);
+                         kBnEps, momentum, t->mu[l], t->rstd[l], t->params + f.mmean, t->params + f.mvar);
+      if (shard)
+        HIP_TRY(hipMemcpyAsync(t->stash + (size_t)l * 2 * train::kMaxC, t->sums, 2 * (size_t)s.cout * sizeof(double),
+                               hipMemcpyDeviceToDevice, st));
     }
     if (pl.bn_act == plan::BnAct::Pair) {
       // a virtual post-ReLU skip source: rebuilt from its producer's z inside bn_act_fwd2
@@ -943,27 +1042,16 @@ int train_run(rced_trainer* t, const float* x_dev, const float* y_dev, float* pr
   if (t->wg_error) {   // (cannot happen with the up-front size above unless the runtime reports > 4 workgroups per CU)
     (void)hipStreamSynchronize(st);   // nothing of this step is left in flight behind the error
     return rced_fail(RCED_ERR_ALLOC, "deterministic weight gradients: the per-wave slice buffer could not be grown; the step was "
-                                     "abandoned before the optimizer ran, but the moving statistics have advanced by this batch");
+                                     "abandoned before the optimizer ran%s",
+                     shard ? " and before the exchange buffers were written" : ", but the moving statistics have advanced by this batch");
   }
-  // ---- Adam (TF form), trainer.py:175-179
-  // global_step: the reference fetches it in the same sess.run as train_op (trainer.py:186-191); TF1 orders a read and an
-  // assign_add in one run only through control dependencies, and slim.learning.create_train_op makes train_op =
-  // (increment global_step, then return the loss), so the fetched value is unordered against the increment in principle.
-  // This library returns the POST-increment value, deterministically: after the first step train_step returns 1 and
-  // the loop's next learning rate is noam(1) (trainer.py:215, step = global_step + 1 = 2).  See DESIGN.md 3.5.
-  t->global_step += 1;
-  const double tt = (double)t->global_step;
-  const float lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow((double)kAdamB2, tt)) / (1.0 - std::pow((double)kAdamB1, tt)));
-  hipLaunchKernelGGL(train::adam_step, dim3((unsigned)((t->nvars + train::kThreads - 1) / train::kThreads)),
-                     dim3(train::kThreads), 0, st, t->params, (const float*)t->grads, t->m, t->v,
-                     (const unsigned char*)t->trainable, t->nvars, lr_t, kAdamB1, kAdamB2, kAdamEps);
-  {
-    TinyScanArgs ta;
-    for (int l = 0; l < kMaxLayers; ++l) {
-      ta.gamma_off[l] = l < L && net.layer[l].use_norm ? (int)t->off[l].gamma : -1;
-      ta.cout[l] = l < L ? net.layer[l].cout : 0;
-    }
-    hipLaunchKernelGGL(tiny_gamma_scan, dim3(kMaxLayers), dim3(64), 0, st, (const float*)t->params, ta, t->tiny_dev);
+  if (shard) {
+    hipLaunchKernelGGL(shard_grad_out, dim3((unsigned)((t->xvars + train::kThreads - 1) / train::kThreads)), dim3(train::kThreads), 0, st,
+                       (const float*)t->grads, (const int*)t->x2i_dev, t->xvars, g_out, accumulate);
+    hipLaunchKernelGGL(shard_stats_out, dim3(kMaxLayers), dim3(kShardThreads), 0, st, (const double*)t->stash, t->shard, (double)P, s_out,
+                       accumulate);
+  } else {
+    adam_and_scan(t, lr, st);
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
@@ -985,6 +1073,38 @@ int rced_train_step(rced_trainer* t, const float* x_dev, const float* y_dev, int
 int rced_train_forward(rced_trainer* t, const float* x_dev, float* pred_dev, int N, int T, void* stream) {
   if (!pred_dev) return rced_fail(RCED_ERR_ARG, "bad batch");
   return train_run(t, x_dev, nullptr, pred_dev, N, T, 0.f, nullptr, stream);
+}
+
+int rced_train_exchange_size(rced_trainer* t, size_t* n_floats, size_t* n_doubles) {
+  if (!t || !n_floats || !n_doubles) return rced_fail(RCED_ERR_ARG, "trainer or output pointer is NULL");
+  *n_floats = t->xvars;
+  *n_doubles = t->xstats;
+  return RCED_OK;
+}
+
+int rced_train_grad(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, float* g_dev, double* s_dev,
+                    int accumulate, double* loss_out, void* stream) {
+  if (!t) return rced_fail(RCED_ERR_ARG, "trainer is NULL");
+  if (N <= 0 || T <= 0) return rced_fail(RCED_ERR_ARG, "a shard must have N >= 1 and T >= 1 (got %d x %d)", N, T);
+  if (!x_dev || !y_dev) return rced_fail(RCED_ERR_ARG, "input or target is NULL");
+  if (!g_dev || !s_dev) return rced_fail(RCED_ERR_ARG, "an exchange buffer is NULL");
+  return train_run(t, x_dev, y_dev, nullptr, N, T, 0.f, loss_out, stream, g_dev, s_dev, accumulate != 0);
+}
+
+int rced_train_apply(rced_trainer* t, const float* g_dev, const double* s_dev, float lr, void* stream) {
+  if (!t) return rced_fail(RCED_ERR_ARG, "trainer is NULL");
+  if (!g_dev || !s_dev) return rced_fail(RCED_ERR_ARG, "an exchange buffer is NULL");
+  DeviceGuard g(t->device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", t->device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  HIP_TRY(hipMemsetAsync(t->grads, 0, t->nvars * sizeof(float), st));
+  hipLaunchKernelGGL(shard_grad_in, dim3((unsigned)((t->xvars + train::kThreads - 1) / train::kThreads)), dim3(train::kThreads), 0, st,
+                     g_dev, (const int*)t->x2i_dev, t->xvars, t->grads);
+  hipLaunchKernelGGL(shard_moving_update, dim3(kMaxLayers), dim3(64), 0, st, s_dev, t->shard, kBnMomentum, t->params);
+  adam_and_scan(t, lr, st);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));
+  return RCED_OK;
 }
 
 // module.py:11-34 with is_training=True, as ONE op on device pointers: z = conv(x) + bias; BatchNorm with the statistics of

@@ -48,6 +48,10 @@ usable.  `timeout_s` bounds each wait on a transfer where the backend supports i
 stream, and the process group's own timeout / watchdog applies).  A transfer TIME-OUT is different: the call still ends on
 every rank with an exception, but transfers may be left pending on the direction groups (gloo closes the pair), so the object
 is poisoned -- later forward_from_root calls raise TransferTimeout until it is closed and built again.
+
+Training.  `DataParallelTrainer` shards the same axis for the training step: the rows of a global batch on ranks, one
+all_gather of the gradients and BatchNorm sums, a sum in rank order on every rank, one optimizer step everywhere
+(DESIGN.md 3.5b).
 """
 
 import datetime
@@ -582,3 +586,101 @@ class BatchShardedForward(object):
             err = err or e
         self._finish(err)
         return None
+
+
+class PeerTrainError(RuntimeError):
+    """DataParallelTrainer: the gradient pass of another rank raised; no rank has applied the step."""
+
+
+class DataParallelTrainer(object):
+    """Data-parallel training over the ranks of `group`: one optimizer step per global batch, the rows of the batch on
+    ranks (the sharded step of DESIGN.md 3.5b with one shard per rank).  `trainer`: this rank's FullyCNNTrainer; every
+    rank builds its own from the same weights, batch_size (the one of the WHOLE batch: the loss divides by it) and
+    learning-rate settings, and the ranks then hold identical state after every step.
+
+    Every rank is handed the SAME global batch -- the loader and its random stream are the reference's on every rank -- and
+    rank r takes rows shard_bounds(N, world)[r].  One step: `grad_step` on the rank's rows; one all_gather of (status,
+    loss, statistics sums) and one of the gradient (through host memory when the group's backend is gloo, device tensors
+    otherwise); every rank adds the gathered buffers in rank order on its device; `apply_step`.  No all_reduce: its order
+    of summation is the transport's, and with an ordered sum a world of W ranks computes bit for bit what
+    `train_step_sharded` computes over the same W row ranges on one device.  BatchNorm normalises each rank's rows by
+    their own statistics (as torch DDP and tf.distribute mirrored towers do by default); the moving statistics follow the
+    whole batch.
+
+    If the gradient pass of any rank raises, every rank raises after the gather (the failing one its own exception, the
+    others PeerTrainError) and none applies; the object and the group stay usable.  A world larger than the batch is a
+    ValueError on every rank before any GPU work.  In train() only rank 0 prints, logs and writes checkpoints -- the
+    ranks' states are identical, so its files are the run's.  valid() runs over the whole loader on every rank and gives
+    identical results; sharded validation is not built."""
+
+    def __init__(self, trainer, group=None, device=None):
+        if not dist.is_initialized():
+            raise RuntimeError("torch.distributed is not initialised (one process per GPU)")
+        self.trainer = trainer
+        self.group = group
+        self.rank = dist.get_rank(group)
+        self.world = dist.get_world_size(group)
+        self.device = torch.device(device) if device is not None else torch.device("cuda:%d" % trainer.device)
+        # gloo moves host memory: the exchange buffers are staged through it; RCCL gathers the device tensors
+        self._host_stage = "nccl" not in str(dist.get_backend(group))
+
+    # the state is the wrapped trainer's (variables, checkpoints, valid_step: self.trainer)
+    lr = property(lambda self: self.trainer.lr)
+    global_step = property(lambda self: self.trainer.global_step)
+
+    def _gather(self, t):
+        """all_gather of one equally sized tensor per rank; returns the ranks' tensors on this rank's device, in rank order."""
+        src = t.cpu() if self._host_stage else t
+        out = [torch.empty_like(src) for _ in range(self.world)]
+        dist.all_gather(out, src, group=self.group)
+        return [o.to(self.device) for o in out] if self._host_stage else out
+
+    def train_step(self, input_x, target_y):
+        """One optimizer step over the global batch (input_x, target_y), the same on every rank: returns (the whole batch's
+        loss, None, global_step), identical on every rank."""
+        n = int(input_x.shape[0]) if hasattr(input_x, "shape") else len(input_x)
+        if self.world > n:
+            raise ValueError("a world of %d ranks cannot share a batch of %d rows: every rank needs at least one" % (self.world, n))
+        lo, hi = shard_bounds(n, self.world)[self.rank]
+        err, loss = None, 0.0
+        try:
+            loss = self.trainer.grad_step(input_x[lo:hi], target_y[lo:hi])
+        except Exception as e:       # the gathers below still run: the other ranks are on their way into them
+            err = e
+        g, s = self.trainer.exchange_tensors()
+        head = torch.tensor([0.0 if err is None else 1.0, loss], dtype=torch.float64, device=s.device)
+        ds = self._gather(torch.cat([head, s]))
+        gs = self._gather(g)
+        bad = [r for r in range(self.world) if float(ds[r][0].item()) != 0.0]
+        if err is not None:
+            raise err
+        if bad:
+            raise PeerTrainError("DataParallelTrainer: the gradient pass of rank %d raised; no rank has applied the step" % bad[0])
+        g.copy_(gs[0])
+        s.copy_(ds[0][2:])
+        total = float(ds[0][1].item())
+        for r in range(1, self.world):       # the ordered sum: rank order, one fp32 / fp64 addition per element and rank
+            g.add_(gs[r])
+            s.add_(ds[r][2:])
+            total += float(ds[r][1].item())
+        return total, None, self.trainer.apply_step()
+
+    def fit_step(self, input_x, target_y):
+        """train_step, then the learning rate of the next step (FullyCNNTrainer.fit_step)."""
+        out = self.train_step(input_x, target_y)
+        self.trainer.lr = self.trainer.noam_scheme(out[2], self.trainer.warmup_steps)
+        return out
+
+    def train(self, train_loader, valid_loader, epochs, logger=None, checkpoints_path=None, net_arch="FullyCNN",
+              num_iter_print=100):
+        """FullyCNNTrainer.train over the data-parallel step.  Every rank walks the same loader in the same order (seed the
+        ranks alike); rank 0 alone prints the progress lines, logs and writes the checkpoints."""
+        from .trainer import run_epochs
+        return run_epochs(self.trainer, self.fit_step, train_loader, valid_loader, epochs, logger, checkpoints_path, net_arch,
+                          num_iter_print, self.rank == 0)
+
+    def valid(self, valid_loader, epoch, logger=None, **kw):
+        """FullyCNNTrainer.valid over the WHOLE loader on every rank (identical results; only rank 0 prints and logs).
+        Sharded validation is out of scope."""
+        root = self.rank == 0
+        return self.trainer.valid(valid_loader, epoch, logger if root else None, verbose=root, **kw)

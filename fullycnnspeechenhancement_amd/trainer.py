@@ -7,6 +7,12 @@ learning rate: `init_lr` for the first step, then the Noam schedule of the retur
 (trainer.py:27,68-76,215).  `train` is the epoch loop (trainer.py:194-243) over a loader that yields the reference's 4-tuple
 -- loader.DataLoader builds the batches on the device --, with a checkpoint per epoch under the reference's name.  TF
 summaries are not built.
+
+The step in shards: `grad_step` runs forward, loss and backward of one shard into the trainer's exchange
+tensors and changes nothing else, `apply_step` updates the moving statistics and runs Adam once from them;
+`train_step_sharded` is one optimizer step over a list of shards, and `accumulate=k` makes train_step / fit_step / train
+cut every batch into k of them.  BatchNorm normalises every shard by its own statistics.  dist.DataParallelTrainer runs
+the same step with the shards on ranks.
 """
 
 import ctypes
@@ -26,16 +32,68 @@ def checkpoint_path(checkpoints_path, net_arch, net_work, epoch, global_step):
                         "{}_{}_{}_{}.ckpt".format(net_arch, net_work, epoch, global_step - 1))
 
 
+def accumulation_slices(n, k):
+    """The k contiguous row ranges `accumulate=k` cuts a batch of n rows into (dist.shard_bounds: balanced, the first
+    n % k one row longer).  k > n would leave a shard without rows: ValueError."""
+    from .dist import shard_bounds
+    n, k = int(n), int(k)
+    if k < 1:
+        raise ValueError("accumulate must be a positive integer, got %d" % k)
+    if k > n:
+        raise ValueError("cannot cut a batch of %d rows into %d shards: every shard needs at least one row" % (n, k))
+    return shard_bounds(n, k)
+
+
 def start_epoch(continue_from):
     """trainer.py:198-201: the epoch after the one a checkpoint's name carries; 0 without a checkpoint."""
     return int(continue_from.split("_")[-2]) + 1 if continue_from is not None else 0
+
+
+def run_epochs(tr, fit_step, train_loader, valid_loader, epochs, logger, checkpoints_path, net_arch, num_iter_print, root):
+    """The epoch loop of trainer.py:194-243 over `fit_step` (FullyCNNTrainer.train, dist.DataParallelTrainer.train); tr: the
+    FullyCNNTrainer whose meters, checkpoints and valid() it uses.  root=False (a data-parallel rank other than 0): the same
+    steps and validations without the progress lines, the log and the checkpoints."""
+    global_step = 0
+    for epoch in range(start_epoch(tr.continue_from), epochs):
+        train_batch_id = 0
+        train_loader.shuffle()
+        start_time = time.time()
+        for batch_mix, batch_clean, _, _ in train_loader:
+            train_batch_id += 1
+            tr.data_time.update(time.time() - start_time)
+            start_time = time.time()
+            batch_loss, _, global_step = fit_step(batch_mix, batch_clean)
+            tr.train_loss.update(batch_loss, n=1)
+            tr.batch_time.update(time.time() - start_time)
+            if root and train_batch_id % num_iter_print == 0:
+                print("epoch: {}, batch: {}/{}, "
+                      "TrainLoss: {train_loss.val:.4f}({train_loss.avg:.4f}), "
+                      "DataTime: {data_time.val:.3f}({data_time.avg:.3f}), "
+                      "BatchTime: {batch_time.val:.3f}({batch_time.avg:.3f})".format(
+                          epoch, train_batch_id, len(train_loader), train_loss=tr.train_loss,
+                          data_time=tr.data_time, batch_time=tr.batch_time))
+            start_time = time.time()
+        if root and checkpoints_path is not None:
+            path = checkpoint_path(checkpoints_path, net_arch, tr.net_work, epoch, global_step)
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            tr.save_checkpoint(path)
+        if (epoch + 1) % 5 == 0:
+            if root:
+                tr.valid(valid_loader, epoch, logger)
+            else:
+                tr.valid(valid_loader, epoch, None, verbose=False)
+    return global_step
 
 
 class FullyCNNTrainer(object):
     model = None
 
     def __init__(self, net_work="FullyCNNV3", batch_size=1, lr=1e-3, warmup_steps=4000.0, weights=None, device=0,
-                 seed=None):
+                 seed=None, accumulate=1):
+        if isinstance(accumulate, bool) or int(accumulate) != accumulate or int(accumulate) < 1:
+            raise ValueError("accumulate must be a positive integer (1: the whole batch in one piece), got %r" % (accumulate,))
+        self.accumulate = int(accumulate)          # train_step cuts its batch into this many shards (gradient accumulation)
+        self._exch = None                          # (gradient fp32, statistics sums fp64): the sharded step's exchange tensors
         self.net_work = net_work
         self.variant = spec.variant_of(net_work)
         self.batch_size = int(batch_size)          # [training] batch_size: what the loss divides by
@@ -71,8 +129,7 @@ class FullyCNNTrainer(object):
         step = global_step + 1
         return self.init_lr * w ** 0.5 * min(step * w ** -1.5, step ** -0.5)
 
-    def train_step(self, input_x, target_y):
-        """trainer.py:181-192: returns (batch_loss, summary (None here), global_step)."""
+    def _on_device(self, input_x, target_y):
         import torch
         dev = "cuda:%d" % self.device
         x = torch.as_tensor(np.asarray(input_x, dtype=np.float32) if not hasattr(input_x, "is_cuda") else input_x,
@@ -81,11 +138,67 @@ class FullyCNNTrainer(object):
                             device=dev).float().contiguous()
         if x.dim() != 4 or x.shape[2] != spec.FEATURE_DIM or x.shape[3] != 1 or x.shape != y.shape:
             raise ValueError("input and target must both be [N, T, 129, 1]")
+        return x, y
+
+    def train_step(self, input_x, target_y):
+        """trainer.py:181-192: returns (batch_loss, summary (None here), global_step).  With accumulate=k > 1 the batch is
+        cut into k contiguous row ranges (accumulation_slices) and the step is train_step_sharded over them."""
+        import torch
+        x, y = self._on_device(input_x, target_y)
+        if self.accumulate > 1:
+            return self.train_step_sharded([(x[a:b], y[a:b]) for a, b in accumulation_slices(x.shape[0], self.accumulate)])
         loss = ctypes.c_double()
         st = torch.cuda.current_stream(x.device).cuda_stream
         _lib.check(_lib.load().rced_train_step(self._h, x.data_ptr(), y.data_ptr(), int(x.shape[0]), int(x.shape[1]),
                                                ctypes.c_float(self.lr), ctypes.byref(loss), st))
         return loss.value, None, self.global_step
+
+    # -- the step in shards (DESIGN.md 3.5b) ----------------------------------------------------------
+    def exchange_tensors(self):
+        """(g, s): the trainer's exchange tensors on its device -- float32 gradient in blob order, float64 (sum z, sum z^2)
+        per BatchNorm channel and the pixel count per layer.  Adding two trainers' tensors elementwise is the sum of their
+        shards.  Their sizes depend on the net alone; they are made on first use."""
+        import torch
+        if self._exch is None:
+            nf, nd = ctypes.c_size_t(), ctypes.c_size_t()
+            _lib.check(_lib.load().rced_train_exchange_size(self._h, ctypes.byref(nf), ctypes.byref(nd)))
+            dev = "cuda:%d" % self.device
+            self._exch = (torch.zeros(nf.value, dtype=torch.float32, device=dev), torch.zeros(nd.value, dtype=torch.float64, device=dev))
+        return self._exch
+
+    def grad_step(self, input_x, target_y, accumulate=False):
+        """One shard: forward (BatchNorm with THIS shard's statistics), loss = sum((y - pred)^2) / batch_size, backward.
+        The gradient and the statistics sums overwrite the exchange tensors, or (accumulate) are added to them; variables,
+        Adam slots, moving statistics and global_step stay as they are.  Returns the shard's loss."""
+        import torch
+        x, y = self._on_device(input_x, target_y)
+        g, s = self.exchange_tensors()
+        loss = ctypes.c_double()
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        _lib.check(_lib.load().rced_train_grad(self._h, x.data_ptr(), y.data_ptr(), int(x.shape[0]), int(x.shape[1]), g.data_ptr(),
+                                               s.data_ptr(), 1 if accumulate else 0, ctypes.byref(loss), st))
+        return loss.value
+
+    def apply_step(self):
+        """The optimizer step from the exchange tensors: moving statistics from the summed statistics (they follow the union
+        of the shards), Adam once with self.lr.  Returns the global step.  gradients() then returns the summed gradient."""
+        import torch
+        g, s = self.exchange_tensors()
+        st = torch.cuda.current_stream(g.device).cuda_stream
+        _lib.check(_lib.load().rced_train_apply(self._h, g.data_ptr(), s.data_ptr(), ctypes.c_float(self.lr), st))
+        return self.global_step
+
+    def train_step_sharded(self, shards):
+        """One optimizer step over a list of (x, y) shards, each [N_s, T_s, 129, 1] (shapes may differ): the gradient is the
+        fp32 sum of the shards' gradients in list order, the reported loss the sum of their losses, BatchNorm per shard.
+        One shard is train_step, bit for bit.  Returns (loss, None, global_step).  Nothing is applied if a shard fails."""
+        shards = [self._on_device(x, y) for x, y in shards]
+        if not shards:
+            raise ValueError("train_step_sharded needs at least one shard")
+        loss = 0.0
+        for i, (x, y) in enumerate(shards):
+            loss += self.grad_step(x, y, accumulate=i > 0)
+        return loss, None, self.apply_step()
 
     def valid_step(self, input_x):
         """trainer.py:245-250: `sess.run(self.pred)` on the training graph.  That graph was built with
@@ -95,7 +208,7 @@ class FullyCNNTrainer(object):
         statistics, is `build_model(net_work, False, weights=trainer.variables())`.)"""
         return self.model(input_x)
 
-    def valid(self, valid_loader, epoch, logger=None, nfft=512, stoi=False, extra=(), rebuild="reference"):
+    def valid(self, valid_loader, epoch, logger=None, nfft=512, stoi=False, extra=(), rebuild="reference", verbose=True):
         """trainer.py:252-338 over anything that yields the reference's 4-tuple (batch_mix, batch_clean, mix_sig,
         clean_sig): engine.evaluate_pcm with valid_step as the forward (BatchNorm with each batch's own statistics),
         every utterance's SDR into self.sdr_score; prints -- and logs, given a logger -- the reference's line with its
@@ -104,6 +217,7 @@ class FullyCNNTrainer(object):
         evaluation.EXTRA_METRICS + evaluation.SPECTRAL_METRICS + evaluation.PROJECTION_METRICS; every utterance's score goes into self.extra_scores[name], and one further line with their
         averages is printed and logged after the reference's.  rebuild: "reference" or "ola" (engine.evaluate_pcm).
         The framing is valid_loader.dataset.framing where there is one, else the default.
+        verbose=False computes and returns the same without printing (the ranks of dist.DataParallelTrainer other than 0).
         PESQ and the wav files are not built."""
         from .engine import check_rebuild, evaluate_pcm, extra_line, feed_meters, loader_framing
         extra = check_extra(extra)
@@ -118,12 +232,14 @@ class FullyCNNTrainer(object):
                                                                                              self.sdr_score.avg)
         else:
             line = "Epoch: {}, Average sd_score: {:.4f}.\n".format(epoch, self.sdr_score.avg)
-        print(line)
+        if verbose:
+            print(line)
         if logger is not None:
             logger.info(line)
         if extra:
             more = "Epoch: {}, ".format(epoch) + extra_line(extra, self.extra_scores)
-            print(more)
+            if verbose:
+                print(more)
             if logger is not None:
                 logger.info(more)
         return self.sdr_score.avg
@@ -141,33 +257,8 @@ class FullyCNNTrainer(object):
         num_iter_print batches, a checkpoint (save_checkpoint) under the reference's name when checkpoints_path is given,
         valid(valid_loader, epoch, logger) after every fifth epoch.  A trainer made by from_checkpoint starts at the epoch
         after the one its checkpoint's name carries.  Returns the last global step.  TF summaries are not built."""
-        global_step = 0
-        for epoch in range(start_epoch(self.continue_from), epochs):
-            train_batch_id = 0
-            train_loader.shuffle()
-            start_time = time.time()
-            for batch_mix, batch_clean, _, _ in train_loader:
-                train_batch_id += 1
-                self.data_time.update(time.time() - start_time)
-                start_time = time.time()
-                batch_loss, _, global_step = self.fit_step(batch_mix, batch_clean)
-                self.train_loss.update(batch_loss, n=1)
-                self.batch_time.update(time.time() - start_time)
-                if train_batch_id % num_iter_print == 0:
-                    print("epoch: {}, batch: {}/{}, "
-                          "TrainLoss: {train_loss.val:.4f}({train_loss.avg:.4f}), "
-                          "DataTime: {data_time.val:.3f}({data_time.avg:.3f}), "
-                          "BatchTime: {batch_time.val:.3f}({batch_time.avg:.3f})".format(
-                              epoch, train_batch_id, len(train_loader), train_loss=self.train_loss,
-                              data_time=self.data_time, batch_time=self.batch_time))
-                start_time = time.time()
-            if checkpoints_path is not None:
-                path = checkpoint_path(checkpoints_path, net_arch, self.net_work, epoch, global_step)
-                os.makedirs(os.path.dirname(path), exist_ok=True)
-                self.save_checkpoint(path)
-            if (epoch + 1) % 5 == 0:
-                self.valid(valid_loader, epoch, logger)
-        return global_step
+        return run_epochs(self, self.fit_step, train_loader, valid_loader, epochs, logger, checkpoints_path, net_arch,
+                          num_iter_print, True)
 
     @property
     def global_step(self):

@@ -600,6 +600,32 @@ int rced_train_step(rced_trainer* t, const float* x_dev, const float* y_dev, int
  * [N, T, 129, 1] float32.  Synchronises the stream. */
 int rced_train_forward(rced_trainer* t, const float* x_dev, float* pred_dev, int N, int T, void* stream);
 
+/* ---- the step in shards (gradient accumulation on one device, data-parallel ranks): one optimizer step over a batch
+ * that arrives as shards s = 0 .. S-1 of [N_s, T_s, 129, 1].  Per shard: the forward with BatchNorm normalising by THAT
+ * shard's statistics, loss_s = sum((y_s - pred_s)^2) / batch_size, and its gradient g_s by the step's own kernels.  The
+ * step's gradient is G = ((g_0 + g_1) + g_2) + ... in fp32 in shard order; every BatchNorm channel's fp64 sums (sum z,
+ * sum z^2) and the pixel count are added over the shards in fp64 in shard order, and the moving statistics are updated
+ * once from the totals (they follow the union batch); Adam runs once from G.  With one shard all of it is rced_train_step,
+ * bit for bit.
+ *
+ * The two caller-owned exchange buffers: n_floats float32 (the gradient, in blob order) and n_doubles float64 (per
+ * BatchNorm layer in layer order: (sum z, sum z^2) per channel, interleaved, then the pixel count).  The layout depends
+ * on the variant alone; adding two buffers elementwise is the sum of the shards. */
+int rced_train_exchange_size(rced_trainer* t, size_t* n_floats, size_t* n_doubles);
+
+/* One shard: forward, loss and backward of (x_dev, y_dev), DEVICE [N, T, 129, 1] float32.  accumulate == 0: g_dev / s_dev
+ * (device) are overwritten with this shard's gradient and sums; otherwise the shard is added to them (g += g_s, s += s_s,
+ * one element per thread).  *loss_out (host) receives loss_s.  Nothing else changes: variables, Adam slots, moving
+ * statistics and global_step stay as they are.  RCED_ERR_ARG for a NULL handle or buffer, N <= 0 or T <= 0.
+ * Synchronises the stream. */
+int rced_train_grad(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, float* g_dev, double* s_dev,
+                    int accumulate, double* loss_out, void* stream);
+
+/* The moving-statistics update from s_dev (momentum 0.99, unbiased variance, by the step's expressions), then the Adam
+ * step from g_dev with the fed learning rate; global_step += 1.  Afterwards rced_train_get_gradients returns g_dev's
+ * content.  Buffers no rced_train_grad has filled are the caller's error and are not detected.  Synchronises the stream. */
+int rced_train_apply(rced_trainer* t, const float* g_dev, const double* s_dev, float lr, void* stream);
+
 long long rced_train_global_step(rced_trainer* t);
 /* Current variables / last gradients, in blob order (gradients of moving statistics are 0). */
 int rced_train_get_variables(rced_trainer* t, float* blob_host, size_t n_floats);
