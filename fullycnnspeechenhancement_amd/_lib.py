@@ -105,6 +105,13 @@ SYMBOLS = {
     "rced_train_grad": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int,
                                        ctypes.POINTER(ctypes.c_double), _vp]),
     "rced_train_apply": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_float, _vp]),
+    "rced_train_sync_points": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_size_t)]),
+    "rced_train_sync_begin": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _vp, _vp]),
+    "rced_train_sync_next": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
+    "rced_train_sync_end": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(ctypes.c_double), ctypes.c_int]),
+    "rced_train_sync_abort": (ctypes.c_int, [_vp]),
+    "rced_train_sync_reduce": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_size_t, _vp, _vp]),
+    "rced_train_copy_variables": (ctypes.c_int, [_vp, _vp, _vp]),
     "rced_train_global_step": (ctypes.c_longlong, [_vp]),
     "rced_train_get_variables": (ctypes.c_int, [_vp, _c_float_p, ctypes.c_size_t]),
     "rced_train_get_gradients": (ctypes.c_int, [_vp, _c_float_p, ctypes.c_size_t]),

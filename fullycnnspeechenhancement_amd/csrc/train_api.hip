@@ -44,6 +44,7 @@ struct LayerOff {   // float offsets into the variable blob
 // double, -1 without BatchNorm; xcout: the reference's channel count (cout: the even-padded one); mmean / mvar: the
 // moving statistics' float offsets in the internal blob.
 struct ShardArgs { int soff[kMaxLayers], xcout[kMaxLayers], cout[kMaxLayers], mmean[kMaxLayers], mvar[kMaxLayers]; };
+struct TrainPass;   // one run of the step's layer loops (below); the synchronised step keeps one open between its calls
 }  // namespace
 
 struct rced_trainer {
@@ -91,6 +92,8 @@ struct rced_trainer {
   double* stash = nullptr;
   ShardArgs shard{};
   size_t xstats = 0;
+  // the synchronised step: the pass that rced_train_sync_begin opened and rced_train_sync_end / _abort has not closed yet
+  std::shared_ptr<TrainPass> pending;
   std::vector<void*> owned;       // every device allocation made by rced_train_create
   std::vector<void*> act_bases;   // the allocations behind out / z / G / D, made for a pixel count (ensure_acts)
   template <class T>
@@ -366,6 +369,8 @@ __global__ void sums_to_float(const double* __restrict__ sums, int C, int which,
 //   kFinX      S2 from sum d_u x, *redo on tiny gamma           (the fused backward kernel's records)
 //   kFinStats  (sum z, sum z^2) -> mu, rstd, moving statistics  (forward: bn_stats_finish)
 // kFinPlain / Z / X also write d beta = S1 and d gamma = S2 (g_beta / g_gamma).  only_if: a device flag, no-op when zero.
+// Over ONE record the reduction is 0.0 + v = v: finishing a layer from an exchange buffer that holds the reduced sums gives
+// the bits of finishing it from the records (the synchronised step, TrainPass::point_finish).
 enum { kFinPlain = 0, kFinZ = 1, kFinX = 2, kFinStats = 3 };
 struct FinishArgs {
   const float *mu, *rstd, *gamma, *beta;      // kFinZ / kFinX
@@ -373,6 +378,7 @@ struct FinishArgs {
   int* redo;                                  // kFinX
   double P; float eps, momentum;              // kFinStats
   float *mu_out, *rstd_out, *moving_mean, *moving_var;
+  double* raw_out;                            // every mode (may be null): the reduced (S1, S2) as the records gave them
 };
 __global__ __launch_bounds__(1024) void bn_finish(const double* __restrict__ part, int nparts, int C, double* __restrict__ sums,
                                                   int mode, FinishArgs a, const int* __restrict__ only_if) {
@@ -407,6 +413,10 @@ __global__ __launch_bounds__(1024) void bn_finish(const double* __restrict__ par
   if (c < C) {
     const double s1 = red[0][2 * c];
     double s2 = red[0][2 * c + 1];
+    if (a.raw_out) {   // (the synchronised step's exchange buffer: what the shards add up before the layer is finished)
+      a.raw_out[2 * c] = s1;
+      a.raw_out[2 * c + 1] = s2;
+    }
     if (mode == kFinStats) {
       const double m = s1 / a.P;
       double var = s2 / a.P - m * m;
@@ -664,6 +674,13 @@ void rced_train_destroy(rced_trainer* t) { delete t; }
 long long rced_train_global_step(rced_trainer* t) { return t ? t->global_step : -1; }
 
 namespace {
+// Between rced_train_sync_begin and rced_train_sync_end / _abort the handle's buffers belong to the open pass.
+int refuse_pending(const rced_trainer* t, const char* what) {
+  if (!t->pending) return RCED_OK;
+  return rced_fail(RCED_ERR_STATE, "%s: a synchronised pass is pending on this trainer (rced_train_sync_begin without "
+                                   "rced_train_sync_end or rced_train_sync_abort)", what);
+}
+
 // internal (even-padded) device array -> the reference's layout on the host, and back (phantom entries become 0)
 int download_external(rced_trainer* t, const float* dev, float* host) {
   std::vector<float> tmp(t->nvars);
@@ -681,18 +698,21 @@ int upload_external(rced_trainer* t, const float* host, float* dev) {
 
 int rced_train_get_variables(rced_trainer* t, float* blob_host, size_t n_floats) {
   if (!t || !blob_host || n_floats != t->xvars) return rced_fail(RCED_ERR_ARG, "bad arguments");
+  if (int rc = refuse_pending(t, "rced_train_get_variables")) return rc;
   DeviceGuard g(t->device);
   return download_external(t, t->params, blob_host);
 }
 
 int rced_train_get_gradients(rced_trainer* t, float* blob_host, size_t n_floats) {
   if (!t || !blob_host || n_floats != t->xvars) return rced_fail(RCED_ERR_ARG, "bad arguments");
+  if (int rc = refuse_pending(t, "rced_train_get_gradients")) return rc;
   DeviceGuard g(t->device);
   return download_external(t, t->grads, blob_host);
 }
 
 int rced_train_get_state(rced_trainer* t, float* m_blob_host, float* v_blob_host, size_t n_floats, long long* global_step) {
   if (!t || !m_blob_host || !v_blob_host || n_floats != t->xvars) return rced_fail(RCED_ERR_ARG, "bad arguments");
+  if (int rc = refuse_pending(t, "rced_train_get_state")) return rc;
   DeviceGuard g(t->device);
   if (int rc = download_external(t, t->m, m_blob_host)) return rc;
   if (int rc = download_external(t, t->v, v_blob_host)) return rc;
@@ -704,6 +724,7 @@ int rced_train_set_state(rced_trainer* t, const float* m_blob_host, const float*
                          long long global_step) {
   if (!t || !m_blob_host || !v_blob_host || n_floats != t->xvars || global_step < 0)
     return rced_fail(RCED_ERR_ARG, "bad arguments");
+  if (int rc = refuse_pending(t, "rced_train_set_state")) return rc;
   DeviceGuard g(t->device);
   if (int rc = upload_external(t, m_blob_host, t->m)) return rc;
   if (int rc = upload_external(t, v_blob_host, t->v)) return rc;
@@ -741,102 +762,168 @@ void adam_and_scan(rced_trainer* t, float lr, hipStream_t st) {
 // prediction is copied to pred_dev.  g_out != nullptr: one shard of the sharded step (rced_train_grad) -- forward, loss and
 // backward as in the step, nothing is updated either; the gradient and every BatchNorm layer's (sum z, sum z^2, pixels) go
 // into (or, accumulate, are added to) g_out / s_out.  Otherwise the full step.
-int train_run(rced_trainer* t, const float* x_dev, const float* y_dev, float* pred_dev, int N, int T, float lr,
-              double* loss_out, void* stream, float* g_out = nullptr, double* s_out = nullptr, int accumulate = 0) {
-  if (!t) return rced_fail(RCED_ERR_ARG, "trainer is NULL");
-  if (N <= 0 || T <= 0 || !x_dev || (!y_dev && !pred_dev)) return rced_fail(RCED_ERR_ARG, "bad batch");
-  const bool forward_only = pred_dev != nullptr, shard = g_out != nullptr;
-  const float momentum = forward_only || shard ? 1.f : kBnMomentum;   // momentum 1: the moving statistics stay as they are
-  DeviceGuard g(t->device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", t->device);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const NetSpec& net = *t->net;
-  const int L = net.n_layers, F = kFeatureDim, frames = N * T;
-  const size_t P = (size_t)frames * F;
-  if (int rc = ensure_acts(t, P)) return rc;
-  const plan::TrainPlan& plan = t->plan;   // which launcher runs where, and who stores / accumulates / zeroes what: train_plan.h
-  if (t->det && !forward_only && !t->wpart) {
-    // Sized BEFORE the forward for the most any wgrad launcher can ask for: slices = workgroups (CUs x at most 4 resident per
-    // CU) x 8 waves x 2 pixel parities, slice stride = the net's largest kernel + bias.  A failure to allocate is therefore
-    // reported here, before this step has touched anything; growing inside tmd::wg_launch remains as a last resort (it
-    // synchronises, and if it fails the step returns RCED_ERR_ALLOC below with the moving statistics already advanced).
-    size_t maxps = 0;
-    for (int l = 0; l < L; ++l) {
-      const LayerSpec& s = net.layer[l];
-      const int cin = s.src == 0 ? 1 : (net.layer[s.src - 1].cout + 1) & ~1, cout = (s.cout + 1) & ~1;   // (R-CED V2: even-padded)
-      maxps = std::max(maxps, (size_t)s.kh * s.kw * cin * cout + cout + 4);
-    }
-    t->wpart_floats = (size_t)t->num_cus * 4 * 8 * 2 * maxps;
-    HIP_TRY(hipMalloc(&t->wpart, t->wpart_floats * sizeof(float)));
-  }
-  // deterministic weight gradients: the wgrad launchers write slices into t->wpart; otherwise fp32 atomics
-  t->wg_error = 0;
-  const WgDet wd = t->det ? WgDet{&t->wpart, &t->wpart_floats, &t->wg_error} : WgDet{};
-  auto blocks = [](size_t n) { return dim3((unsigned)std::min<size_t>((n + train::kThreads - 1) / train::kThreads, 65535)); };
-  auto pair_grid = [&](int C) {   // channel-aligned kernels: rows = 256 / (C/2) pixels per workgroup pass
+//
+// The pass is a TrainPass: begin() packs the weights, advance() walks the forward and the backward loop, end() hands the
+// result out.  Every bn_finish call site of the two loops is an EXCHANGE POINT, described by a FinishPoint.  The straight
+// paths (the three forms above) finish it on the spot with one launch (point_straight).  The synchronised step (xs != nullptr)
+// stops there instead: point_out reduces the records to the raw 2 C sums in xs, advance() returns, the caller replaces xs by
+// the sum over all shards, and the next advance() finishes the layer from xs with the pixel count of all shards
+// (point_finish) and goes on.  Both forms run the same per-layer pieces (fwd_conv / fwd_act, bwd_route / bwd_rest).
+struct FinishPoint {
+  int nparts = 0, C = 0, mode = kFinPlain;   // the records in t->part, the layer's channels, how bn_finish finishes them
+  FinishArgs fa{};
+  double* sums = nullptr;                    // where the finished sums go
+};
+
+struct TrainPass {
+  enum class Stage { Fwd, FwdResume, Bwd, BwdResume, Done };
+  rced_trainer* const t;
+  const float* const x_dev;
+  const float* const y_dev;
+  float* const pred_dev;
+  const int N, T;
+  const float lr;
+  const hipStream_t st;
+  const bool forward_only, shard;
+  const float momentum;        // momentum 1: the moving statistics stay as they are
+  const NetSpec& net;
+  const plan::TrainPlan& plan;   // which launcher runs where, and who stores / accumulates / zeroes what: train_plan.h
+  const int L, F, frames;
+  const size_t P;              // this pass's pixels
+  const double bnP;            // the pixels BatchNorm's statistics are over: P, or all shards' (the synchronised step)
+  double* const xs;            // the synchronised step's exchange buffer (2 * train::kMaxC doubles, the caller's), or nullptr
+  WgDet wd{};
+  tmm::XformArgs xa_tmp{nullptr, nullptr, nullptr, nullptr};
+  int tiny[kMaxLayers] = {};
+  std::vector<int> src_parts;  // [l]: the records of layer l's BatchNorm-backward sums that its consumer's dgrad left in t->part (Sums::DgradZ / FusedX)
+  std::vector<double> hp;      // the loss kernel's partial sums, on the host after end()'s synchronise
+  Stage stage = Stage::Fwd;
+  int layer = 0;
+  FinishPoint pt{};
+  bool tiny_after = false;     // straight paths: pt (kFinX) is followed by the exact recomputation of a tiny-gamma layer
+
+  TrainPass(rced_trainer* t_, const float* x, const float* y, float* pred, int N_, int T_, float lr_, void* stream, bool shard_,
+            double pixels_total, double* xs_)
+      : t(t_), x_dev(x), y_dev(y), pred_dev(pred), N(N_), T(T_), lr(lr_), st(static_cast<hipStream_t>(stream)),
+        forward_only(pred != nullptr), shard(shard_), momentum(pred != nullptr || shard_ ? 1.f : kBnMomentum), net(*t_->net),
+        plan(t_->plan), L(t_->net->n_layers), F(kFeatureDim), frames(N_ * T_), P((size_t)N_ * T_ * kFeatureDim),
+        bnP(xs_ ? pixels_total : (double)((size_t)N_ * T_ * kFeatureDim)), xs(xs_) {}
+
+  static dim3 blocks(size_t n) { return dim3((unsigned)std::min<size_t>((n + train::kThreads - 1) / train::kThreads, 65535)); }
+  dim3 pair_grid(int C) const {   // channel-aligned kernels: rows = 256 / (C/2) pixels per workgroup pass
     const size_t rows = train::kThreads / (C / 2);
     return dim3((unsigned)std::min<size_t>((P + rows - 1) / rows, kPairGrid));
-  };
+  }
   // a virtual tensor is read as its producer's z plus that layer's BatchNorm parameters (BnReluXform)
-  tmm::XformArgs xa_tmp{nullptr, nullptr, nullptr, nullptr};
-  auto conv_in = [&](int id) -> const float* { return id == 0 ? x_dev : (plan.virt(id) ? t->z[id - 1] : t->out[id]); };
-  auto xform_of = [&](int id, tmm::XformArgs* xa) -> const tmm::XformArgs* {
+  const float* conv_in(int id) const { return id == 0 ? x_dev : (plan.virt(id) ? t->z[id - 1] : t->out[id]); }
+  const tmm::XformArgs* xform_of(int id, tmm::XformArgs* xa) const {
     if (id <= 0 || !plan.virt(id)) return nullptr;
     const LayerOff& pf = t->off[id - 1];
     *xa = tmm::XformArgs{t->mu[id - 1], t->rstd[id - 1], t->params + pf.gamma, t->params + pf.beta};
     return xa;
-  };
-  auto tensor = [&](int id) -> const float* { return id < 0 ? nullptr : (id == 0 ? x_dev : t->out[id]); };
-  auto no_kernel = [](int l, const char* what) { return rced_fail(RCED_ERR_STATE, "layer %d: the planned %s kernel was not built", l, what); };
-  auto zero_grad = [&](int id) { return hipMemsetAsync(t->G[id], 0, P * net.layer[id - 1].cout * sizeof(float), st); };
+  }
+  const float* tensor(int id) const { return id < 0 ? nullptr : (id == 0 ? x_dev : t->out[id]); }
+  static int no_kernel(int l, const char* what) { return rced_fail(RCED_ERR_STATE, "layer %d: the planned %s kernel was not built", l, what); }
+  hipError_t zero_grad(int id) const { return hipMemsetAsync(t->G[id], 0, P * net.layer[id - 1].cout * sizeof(float), st); }
 
-  // ---- weights in the layouts the direct-convolution kernels want, and the MFMA kernels' packets
-  for (int l = 0; l < L; ++l) {
-    const LayerSpec& s = net.layer[l];
-    const LayerOff& f = t->off[l];
-    if (plan.layer[l].repack_fwd) {
-      hipLaunchKernelGGL(train::repack_fwd, dim3((f.K * f.cout4 + 255) / 256), dim3(256), 0, st, t->params + f.kernel, f.K,
-                         s.cout, f.cout4, t->wf[l]);
-      hipLaunchKernelGGL(train::repack_fwd, dim3(1), dim3(64), 0, st, t->params + f.bias, 1, s.cout, f.cout4, t->bias4[l]);
-    }
-    if (plan.layer[l].repack_dgrad) {
-      const int nt = s.kh * s.kw * s.cout * f.cin4;
-      hipLaunchKernelGGL(train::repack_dgrad, dim3((nt + 255) / 256), dim3(256), 0, st, t->params + f.kernel, s.kh, s.kw,
-                         f.cin, s.cout, f.cin4, t->wt[l]);
-    }
+  // ---- the exchange point in its three forms
+  void launch_finish(const double* part, int nparts, double* sums, int mode, const FinishArgs& fa) const {
+    hipLaunchKernelGGL(bn_finish, dim3(1), dim3(1024), 0, st, part, nparts, pt.C, sums, mode, fa, (const int*)nullptr);
   }
-  for (int l = 0; l < L; ++l) {
-    const LayerSpec& s = net.layer[l];
-    const LayerOff& f = t->off[l];
-    if (plan.layer[l].fwd == plan::Fwd::X6) {
-      const int n = rced::tmd::tm_packet_x6_threads(f.cin, s.kw, s.cout);
-      hipLaunchKernelGGL(tmm::pack_packet_x6, dim3((n + 255) / 256), dim3(256), 0, st, (const float*)(t->params + f.kernel),
-                         (const float*)(t->params + f.bias), s.kw, f.cin, s.cout, rced::tmd::tm_packet_parities(s.cout), t->pk_fwd_x6[l]);
-    } else if (plan.layer[l].fwd == plan::Fwd::Mfma) {
-      const int n = (int)tm_packet_floats(f.cin, s.kw, s.cout);
-      hipLaunchKernelGGL(tmm::pack_packet, dim3((n + 255) / 256), dim3(256), 0, st, (const float*)(t->params + f.kernel),
-                         (const float*)(t->params + f.bias), s.kw, f.cin, s.cout, 0, rced::tmd::tm_packet_parities(s.cout),
-                         t->pk_fwd[l]);
-    }
-    if (plan.layer[l].pack_dgrad && t->pk_bwd_x6[l]) {
-      // the fused backward kernel of this shape runs its dgrad half in the three-part bf16 form: its packet in that form too
-      // (the fp32 packet below stays: the separate dgrad kernel takes it when the fused one is not used)
-      const int n = rced::tmd::tm_packet_x6_threads(s.cout, s.kw, f.cin);
-      hipLaunchKernelGGL(tmm::pack_packet_x6, dim3((n + 255) / 256), dim3(256), 0, st, (const float*)(t->params + f.kernel),
-                         (const float*)nullptr, s.kw, s.cout, f.cin, rced::tmd::tm_packet_parities(f.cin), t->pk_bwd_x6[l], 1);
-    }
-    if (plan.layer[l].pack_dgrad) {
-      const int n = (int)tm_packet_floats(s.cout, s.kw, f.cin);
-      hipLaunchKernelGGL(tmm::pack_packet, dim3((n + 255) / 256), dim3(256), 0, st, (const float*)(t->params + f.kernel),
-                         (const float*)nullptr, s.kw, s.cout, f.cin, 1, rced::tmd::tm_packet_parities(f.cin), t->pk_bwd[l]);
-    }
+  void point_straight() const { launch_finish(t->part, pt.nparts, pt.sums, pt.mode, pt.fa); }
+  // The records reduced in bn_finish's order, raw, into xs.  Forward: also into the layer's stash, which rced_train_apply's
+  // moving-statistics exchange reads (this shard's own sums, as in the per-shard mode).  Backward: d beta and d gamma of THIS
+  // shard -- the mode's expressions are linear in the raw sums once mu and rstd are those of all shards, so the usual sum
+  // of the shards' gradients makes them the batch's.
+  void point_out() const {
+    FinishArgs a{};
+    int mode = kFinPlain;
+    if (pt.mode != kFinStats) { a = pt.fa; mode = pt.mode; }
+    a.raw_out = xs;
+    launch_finish(t->part, pt.nparts, pt.mode == kFinStats ? t->stash + (size_t)layer * 2 * train::kMaxC : t->sums, mode, a);
   }
-  // ---- forward (is_training=True)
-  for (int l = 0; l < L; ++l) {
+  // xs holds the sum over all shards: finished as ONE record (0.0 + v = v) with the pass's pixel count bnP
+  void point_finish() const {
+    FinishArgs a = pt.fa;
+    a.g_beta = a.g_gamma = nullptr;
+    launch_finish(xs, 1, t->sums, pt.mode, a);
+  }
+
+  int begin() {
+    if (int rc = ensure_acts(t, P)) return rc;
+    if (t->det && !forward_only && !t->wpart) {
+      // Sized BEFORE the forward for the most any wgrad launcher can ask for: slices = workgroups (CUs x at most 4 resident per
+      // CU) x 8 waves x 2 pixel parities, slice stride = the net's largest kernel + bias.  A failure to allocate is therefore
+      // reported here, before this step has touched anything; growing inside tmd::wg_launch remains as a last resort (it
+      // synchronises, and if it fails the step returns RCED_ERR_ALLOC below with the moving statistics already advanced).
+      size_t maxps = 0;
+      for (int l = 0; l < L; ++l) {
+        const LayerSpec& s = net.layer[l];
+        const int cin = s.src == 0 ? 1 : (net.layer[s.src - 1].cout + 1) & ~1, cout = (s.cout + 1) & ~1;   // (R-CED V2: even-padded)
+        maxps = std::max(maxps, (size_t)s.kh * s.kw * cin * cout + cout + 4);
+      }
+      t->wpart_floats = (size_t)t->num_cus * 4 * 8 * 2 * maxps;
+      HIP_TRY(hipMalloc(&t->wpart, t->wpart_floats * sizeof(float)));
+    }
+    // deterministic weight gradients: the wgrad launchers write slices into t->wpart; otherwise fp32 atomics
+    t->wg_error = 0;
+    wd = t->det ? WgDet{&t->wpart, &t->wpart_floats, &t->wg_error} : WgDet{};
+    for (int l = 0; l < kMaxLayers; ++l) tiny[l] = t->tiny_host[l];     // as of the end of the previous step (it synchronised)
+    src_parts.assign(L, 0);
+    stage = Stage::Fwd;
+    layer = 0;
+
+    // ---- weights in the layouts the direct-convolution kernels want, and the MFMA kernels' packets
+    for (int l = 0; l < L; ++l) {
+      const LayerSpec& s = net.layer[l];
+      const LayerOff& f = t->off[l];
+      if (plan.layer[l].repack_fwd) {
+        hipLaunchKernelGGL(train::repack_fwd, dim3((f.K * f.cout4 + 255) / 256), dim3(256), 0, st, t->params + f.kernel, f.K,
+                           s.cout, f.cout4, t->wf[l]);
+        hipLaunchKernelGGL(train::repack_fwd, dim3(1), dim3(64), 0, st, t->params + f.bias, 1, s.cout, f.cout4, t->bias4[l]);
+      }
+      if (plan.layer[l].repack_dgrad) {
+        const int nt = s.kh * s.kw * s.cout * f.cin4;
+        hipLaunchKernelGGL(train::repack_dgrad, dim3((nt + 255) / 256), dim3(256), 0, st, t->params + f.kernel, s.kh, s.kw,
+                           f.cin, s.cout, f.cin4, t->wt[l]);
+      }
+    }
+    for (int l = 0; l < L; ++l) {
+      const LayerSpec& s = net.layer[l];
+      const LayerOff& f = t->off[l];
+      if (plan.layer[l].fwd == plan::Fwd::X6) {
+        const int n = rced::tmd::tm_packet_x6_threads(f.cin, s.kw, s.cout);
+        hipLaunchKernelGGL(tmm::pack_packet_x6, dim3((n + 255) / 256), dim3(256), 0, st, (const float*)(t->params + f.kernel),
+                           (const float*)(t->params + f.bias), s.kw, f.cin, s.cout, rced::tmd::tm_packet_parities(s.cout), t->pk_fwd_x6[l]);
+      } else if (plan.layer[l].fwd == plan::Fwd::Mfma) {
+        const int n = (int)tm_packet_floats(f.cin, s.kw, s.cout);
+        hipLaunchKernelGGL(tmm::pack_packet, dim3((n + 255) / 256), dim3(256), 0, st, (const float*)(t->params + f.kernel),
+                           (const float*)(t->params + f.bias), s.kw, f.cin, s.cout, 0, rced::tmd::tm_packet_parities(s.cout),
+                           t->pk_fwd[l]);
+      }
+      if (plan.layer[l].pack_dgrad && t->pk_bwd_x6[l]) {
+        // the fused backward kernel of this shape runs its dgrad half in the three-part bf16 form: its packet in that form too
+        // (the fp32 packet below stays: the separate dgrad kernel takes it when the fused one is not used)
+        const int n = rced::tmd::tm_packet_x6_threads(s.cout, s.kw, f.cin);
+        hipLaunchKernelGGL(tmm::pack_packet_x6, dim3((n + 255) / 256), dim3(256), 0, st, (const float*)(t->params + f.kernel),
+                           (const float*)nullptr, s.kw, s.cout, f.cin, rced::tmd::tm_packet_parities(f.cin), t->pk_bwd_x6[l], 1);
+      }
+      if (plan.layer[l].pack_dgrad) {
+        const int n = (int)tm_packet_floats(s.cout, s.kw, f.cin);
+        hipLaunchKernelGGL(tmm::pack_packet, dim3((n + 255) / 256), dim3(256), 0, st, (const float*)(t->params + f.kernel),
+                           (const float*)nullptr, s.kw, s.cout, f.cin, 1, rced::tmd::tm_packet_parities(f.cin), t->pk_bwd[l]);
+      }
+    }
+    return RCED_OK;
+  }
+
+  // ---- forward (is_training=True), layer l up to its statistics: *have = the layer stops at an exchange point (pt)
+  int fwd_conv(int l, bool* have) {
     const LayerSpec& s = net.layer[l];
     const LayerOff& f = t->off[l];
     const plan::LayerPlan& pl = plan.layer[l];
     const bool stats = s.use_norm != 0;
+    *have = false;
     int stat_parts = 0;   // the (sum z, sum z^2) records the conv kernel left in t->part (Stats::Conv)
     switch (pl.fwd) {
       case plan::Fwd::X6:
@@ -862,14 +949,15 @@ int train_run(rced_trainer* t, const float* x_dev, const float* y_dev, float* pr
         break;
     }
     if (stat_parts <= 0) return no_kernel(l, "forward");
-    const size_t n = P * s.cout;
     if (pl.stats == plan::Stats::Conv) {
-      FinishArgs fa{};
-      fa.P = (double)P; fa.eps = kBnEps; fa.momentum = momentum;
+      pt = FinishPoint{};
+      pt.nparts = stat_parts; pt.C = s.cout; pt.mode = kFinStats;
+      FinishArgs& fa = pt.fa;
+      fa.P = bnP; fa.eps = kBnEps; fa.momentum = momentum;
       fa.mu_out = t->mu[l]; fa.rstd_out = t->rstd[l]; fa.moving_mean = t->params + f.mmean; fa.moving_var = t->params + f.mvar;
       // (a shard keeps the layer's (S1, S2) for the exchange buffer: the kernel writes them where it is told to)
-      hipLaunchKernelGGL(bn_finish, dim3(1), dim3(1024), 0, st, (const double*)t->part, stat_parts, s.cout,
-                         shard ? t->stash + (size_t)l * 2 * train::kMaxC : t->sums, (int)kFinStats, fa, (const int*)nullptr);
+      pt.sums = shard ? t->stash + (size_t)l * 2 * train::kMaxC : t->sums;
+      *have = true;
     } else if (pl.stats == plan::Stats::Reduce) {
       if (int rc = reduce_channels(t, t->z[l], t->z[l], nullptr, nullptr, P, s.cout, st)) return rc;
       hipLaunchKernelGGL(train::bn_stats_finish, dim3(1), dim3(64), 0, st, (const double*)t->sums, (double)P, s.cout,
@@ -878,6 +966,14 @@ int train_run(rced_trainer* t, const float* x_dev, const float* y_dev, float* pr
         HIP_TRY(hipMemcpyAsync(t->stash + (size_t)l * 2 * train::kMaxC, t->sums, 2 * (size_t)s.cout * sizeof(double),
                                hipMemcpyDeviceToDevice, st));
     }
+    return RCED_OK;
+  }
+  // ... and from its statistics on: BatchNorm, skips, ReLU
+  void fwd_act(int l) {
+    const LayerSpec& s = net.layer[l];
+    const LayerOff& f = t->off[l];
+    const plan::LayerPlan& pl = plan.layer[l];
+    const size_t n = P * s.cout;
     if (pl.bn_act == plan::BnAct::Pair) {
       // a virtual post-ReLU skip source: rebuilt from its producer's z inside bn_act_fwd2
       tmm::XformArgs vs{nullptr, nullptr, nullptr, nullptr};
@@ -894,37 +990,51 @@ int train_run(rced_trainer* t, const float* x_dev, const float* y_dev, float* pr
                          tensor(s.skip_post), s.use_act, n, s.cout, t->out[l + 1]);
     }
   }
-  HIP_TRY(hipGetLastError());
-  if (forward_only) {
-    HIP_TRY(hipMemcpyAsync(pred_dev, t->out[L], P * sizeof(float), hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
+  // ---- the forward's end: the prediction out (forward only), or the loss and what the backward starts from
+  int fwd_end() {
+    HIP_TRY(hipGetLastError());
+    if (forward_only) {
+      HIP_TRY(hipMemcpyAsync(pred_dev, t->out[L], P * sizeof(float), hipMemcpyDeviceToDevice, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      return RCED_OK;
+    }
+    // ---- loss and its gradient (trainer.py:146-147,153)
+    hipLaunchKernelGGL(train::loss_fwd_bwd, dim3(kReduceGrid), dim3(train::kThreads), 0, st, (const float*)t->out[L], y_dev,
+                       P, 1.f / (float)t->batch_size, t->G[L], t->part);
+    hp.assign(kReduceGrid, 0.0);
+    HIP_TRY(hipMemcpyAsync(hp.data(), t->part, kReduceGrid * sizeof(double), hipMemcpyDeviceToHost, st));
+    // ---- backward.  G[id] collects d loss / d tensor id from every consumer (the conv reading it, skip adds); the plan says
+    // which writer stores, which add, and which tensors are zeroed first.
+    HIP_TRY(hipMemsetAsync(t->grads, 0, t->nvars * sizeof(float), st));
+    for (int id = 1; id < L; ++id)
+      if (plan.zero_first[id]) HIP_TRY(zero_grad(id));
     return RCED_OK;
   }
-  // ---- loss and its gradient (trainer.py:146-147,153)
-  hipLaunchKernelGGL(train::loss_fwd_bwd, dim3(kReduceGrid), dim3(train::kThreads), 0, st, (const float*)t->out[L], y_dev,
-                     P, 1.f / (float)t->batch_size, t->G[L], t->part);
-  std::vector<double> hp(kReduceGrid);
-  HIP_TRY(hipMemcpyAsync(hp.data(), t->part, kReduceGrid * sizeof(double), hipMemcpyDeviceToHost, st));
-  // ---- backward.  G[id] collects d loss / d tensor id from every consumer (the conv reading it, skip adds); the plan says
-  // which writer stores, which add, and which tensors are zeroed first.
-  HIP_TRY(hipMemsetAsync(t->grads, 0, t->nvars * sizeof(float), st));
-  for (int id = 1; id < L; ++id)
-    if (plan.zero_first[id]) HIP_TRY(zero_grad(id));
-  int tiny[kMaxLayers];
-  for (int l = 0; l < kMaxLayers; ++l) tiny[l] = t->tiny_host[l];     // as of the end of the previous step (it synchronised)
-  // src_parts[l]: the records of layer l's BatchNorm-backward sums that its consumer's dgrad left in t->part (Sums::DgradZ / FusedX)
-  std::vector<int> src_parts(L, 0);
-  for (int l = L - 1; l >= 0; --l) {
+
+  // the exact sums of a tiny-gamma layer again from (g, z), see kTinyGamma: bwd_route2 without outputs; returns its records
+  int tiny_recompute(int l) const {
+    const LayerSpec& s = net.layer[l];
+    const LayerOff& f = t->off[l];
+    const dim3 grid = pair_grid(s.cout);
+    hipLaunchKernelGGL(train::bwd_route2, grid, dim3(train::kThreads), 0, st, (const float2*)t->G[l + 1],
+                       (const float2*)t->z[l], (const float*)(s.use_norm ? t->mu[l] : nullptr), (const float*)t->rstd[l],
+                       (const float*)(t->params + f.gamma), (const float*)(t->params + f.beta), (const float2*)nullptr, s.use_act, P,
+                       s.cout, (float2*)nullptr, (float2*)nullptr, (float2*)nullptr, t->part, (const int*)nullptr);
+    return (int)grid.x;
+  }
+
+  // ---- backward, layer l up to its BatchNorm-backward sums: *have = the layer stops at an exchange point (pt)
+  int bwd_route(int l, bool* have) {
     const LayerSpec& s = net.layer[l];
     const LayerOff& f = t->off[l];
     const plan::LayerPlan& pl = plan.layer[l];
     const size_t n = P * s.cout;
     const float* mu = s.use_norm ? t->mu[l] : nullptr;
-    // BatchNorm backward: either applied in place on D (bn_bwd_apply*), or (fuse_dz) folded into the staging of the wgrad and
-    // dgrad kernels, which read (d_u, z) and never materialise dz (tile_commit_bnbwd).  With lazy_mask d_u is not materialised
-    // either: the consumers read the incoming gradient g and apply the ReLU mask themselves.  passthrough: d_u IS g.
-    const float* dsrc = pl.lazy_mask || pl.passthrough ? t->G[l + 1] : t->D;      // what wgrad / dgrad read as their "dz" input
-    FinishArgs fb{};
+    *have = false;
+    tiny_after = false;
+    pt = FinishPoint{};
+    pt.C = s.cout; pt.sums = t->sums;
+    FinishArgs& fb = pt.fa;
     fb.mu = mu; fb.rstd = t->rstd[l]; fb.gamma = t->params + f.gamma; fb.beta = t->params + f.beta;
     fb.g_beta = t->grads + f.beta; fb.g_gamma = t->grads + f.gamma; fb.redo = t->redo;
     float* const g_pre = s.skip_pre > 0 ? t->G[s.skip_pre] : nullptr;
@@ -937,9 +1047,10 @@ int train_run(rced_trainer* t, const float* x_dev, const float* y_dev, float* pr
                          (const float*)(t->params + f.beta), (const float2*)tensor(s.skip_pre), s.use_act, P, s.cout,
                          (float2*)g_pre, (float2*)g_post, (float2*)(pl.lazy_mask ? nullptr : t->D),
                          s.use_norm ? t->part : (double*)nullptr, (const int*)nullptr, pl.skip_first ? 1 : 0);
-      if (pl.sums == plan::Sums::Route2)
-        hipLaunchKernelGGL(bn_finish, dim3(1), dim3(1024), 0, st, (const double*)t->part, (int)grid.x, s.cout, t->sums,
-                           (int)kFinPlain, fb, (const int*)nullptr);
+      if (pl.sums == plan::Sums::Route2) {
+        pt.nparts = (int)grid.x; pt.mode = kFinPlain;
+        *have = true;
+      }
     } else if (pl.route == plan::Route::Scalar) {
       hipLaunchKernelGGL(train::bwd_route, blocks(n), dim3(train::kThreads), 0, st, (const float*)t->G[l + 1],
                          (const float*)t->z[l], mu, (const float*)t->rstd[l], (const float*)(t->params + f.gamma),
@@ -951,31 +1062,42 @@ int train_run(rced_trainer* t, const float* x_dev, const float* y_dev, float* pr
       }
     } else if (pl.sums == plan::Sums::DgradZ || pl.sums == plan::Sums::FusedX) {
       const bool from_x = pl.sums == plan::Sums::FusedX;   // (sum d_u, sum d_u * x) rather than (.., sum d_u * z)
-      hipLaunchKernelGGL(bn_finish, dim3(1), dim3(1024), 0, st, (const double*)t->part, src_parts[l], s.cout, t->sums,
-                         (int)(from_x ? kFinX : kFinZ), fb, (const int*)nullptr);
-      if (from_x && tiny[l]) {
-        // |gamma| tiny somewhere in this layer (known on the host since the previous step's tiny_gamma_scan): the sums
-        // again, exactly, from (g, z); see kTinyGamma.  Never taken in a real training run.
-        const dim3 grid = pair_grid(s.cout);
-        hipLaunchKernelGGL(train::bwd_route2, grid, dim3(train::kThreads), 0, st, (const float2*)t->G[l + 1],
-                           (const float2*)t->z[l], mu, (const float*)t->rstd[l], (const float*)(t->params + f.gamma),
-                           (const float*)(t->params + f.beta), (const float2*)nullptr, s.use_act, P, s.cout, (float2*)nullptr,
-                           (float2*)nullptr, (float2*)nullptr, t->part, (const int*)nullptr);
-        hipLaunchKernelGGL(bn_finish, dim3(1), dim3(1024), 0, st, (const double*)t->part, (int)grid.x, s.cout, t->sums,
-                           (int)kFinPlain, fb, (const int*)nullptr);
+      pt.nparts = src_parts[l]; pt.mode = from_x ? kFinX : kFinZ;
+      *have = true;
+      // |gamma| tiny somewhere in this layer (known on the host since the previous step's tiny_gamma_scan, and a matter of the
+      // variables alone: every shard decides alike): the sums again, exactly, from (g, z); see kTinyGamma.  Never taken in a
+      // real training run.  The straight paths finish the kFinX point first and the exact one over it (advance); the
+      // synchronised step exchanges the exact sums alone, which replace all that the kFinX finish would have written.
+      tiny_after = from_x && tiny[l] != 0;
+      if (tiny_after && xs) {
+        pt.nparts = tiny_recompute(l); pt.mode = kFinPlain;
+        tiny_after = false;
       }
     }
-    const tmm::BnBwdArgs ba_l{t->z[l], mu, t->rstd[l], t->params + f.gamma, t->sums, (double)P,
+    return RCED_OK;
+  }
+  // ... and from its sums (t->sums, over bnP pixels) on: BatchNorm backward, wgrad, dgrad
+  int bwd_rest(int l) {
+    const LayerSpec& s = net.layer[l];
+    const LayerOff& f = t->off[l];
+    const plan::LayerPlan& pl = plan.layer[l];
+    const size_t n = P * s.cout;
+    const float* mu = s.use_norm ? t->mu[l] : nullptr;
+    // BatchNorm backward: either applied in place on D (bn_bwd_apply*), or (fuse_dz) folded into the staging of the wgrad and
+    // dgrad kernels, which read (d_u, z) and never materialise dz (tile_commit_bnbwd).  With lazy_mask d_u is not materialised
+    // either: the consumers read the incoming gradient g and apply the ReLU mask themselves.  passthrough: d_u IS g.
+    const float* dsrc = pl.lazy_mask || pl.passthrough ? t->G[l + 1] : t->D;      // what wgrad / dgrad read as their "dz" input
+    const tmm::BnBwdArgs ba_l{t->z[l], mu, t->rstd[l], t->params + f.gamma, t->sums, bnP,
                               pl.lazy_mask ? t->params + f.beta : nullptr};
     const tmm::BnBwdArgs* ba = pl.fuse_dz ? &ba_l : nullptr;
     if (s.use_norm && !pl.fuse_dz) {
       if (s.cout % 2 == 0)
         hipLaunchKernelGGL(train::bn_bwd_apply2, pair_grid(s.cout), dim3(train::kThreads), 0, st, (float2*)t->D,
                            (const float2*)t->z[l], mu, (const float*)t->rstd[l], (const float*)(t->params + f.gamma),
-                           (const double*)t->sums, (double)P, P, s.cout);
+                           (const double*)t->sums, bnP, P, s.cout);
       else
         hipLaunchKernelGGL(train::bn_bwd_apply, blocks(n), dim3(train::kThreads), 0, st, t->D, (const float*)t->z[l], mu,
-                           (const float*)t->rstd[l], (const float*)(t->params + f.gamma), (const double*)t->sums, (double)P, n,
+                           (const float*)t->rstd[l], (const float*)(t->params + f.gamma), (const double*)t->sums, bnP, n,
                            s.cout);
     }
     // dW and dbias = sum dz (the MFMA wgrad kernels produce both)
@@ -1038,28 +1160,116 @@ int train_run(rced_trainer* t, const float* x_dev, const float* y_dev, float* pr
     }
     if (grid <= 0) return no_kernel(l, "dgrad");
     if (pl.src_sums) src_parts[pv] = grid;
+    return RCED_OK;
   }
-  if (t->wg_error) {   // (cannot happen with the up-front size above unless the runtime reports > 4 workgroups per CU)
-    (void)hipStreamSynchronize(st);   // nothing of this step is left in flight behind the error
-    return rced_fail(RCED_ERR_ALLOC, "deterministic weight gradients: the per-wave slice buffer could not be grown; the step was "
-                                     "abandoned before the optimizer ran%s",
-                     shard ? " and before the exchange buffers were written" : ", but the moving statistics have advanced by this batch");
+
+  // The two loops, to the end of the backward (the straight paths), or (xs) to the next exchange point: then the stage is
+  // FwdResume / BwdResume, and the next call finishes that layer from xs and goes on.  done(): nothing is left to run.
+  bool done() const { return stage == Stage::Done; }
+  int advance() {
+    while (stage != Stage::Done) {
+      bool have = false;
+      switch (stage) {
+        case Stage::Fwd:
+          if (layer == L) {
+            if (int rc = fwd_end()) return rc;
+            stage = forward_only ? Stage::Done : Stage::Bwd;
+            layer = L - 1;
+            break;
+          }
+          if (int rc = fwd_conv(layer, &have)) return rc;
+          if (have && xs) {
+            point_out();
+            stage = Stage::FwdResume;
+            return RCED_OK;
+          }
+          if (have) point_straight();
+          fwd_act(layer++);
+          break;
+        case Stage::FwdResume:
+          point_finish();
+          fwd_act(layer++);
+          stage = Stage::Fwd;
+          break;
+        case Stage::Bwd:
+          if (layer < 0) {
+            stage = Stage::Done;
+            break;
+          }
+          if (int rc = bwd_route(layer, &have)) return rc;
+          if (have && xs) {
+            point_out();
+            stage = Stage::BwdResume;
+            return RCED_OK;
+          }
+          if (have) point_straight();
+          if (tiny_after) {
+            pt.nparts = tiny_recompute(layer); pt.mode = kFinPlain;
+            point_straight();
+          }
+          if (int rc = bwd_rest(layer--)) return rc;
+          break;
+        case Stage::BwdResume:
+          point_finish();
+          stage = Stage::Bwd;
+          if (int rc = bwd_rest(layer--)) return rc;
+          break;
+        case Stage::Done:
+          break;
+      }
+    }
+    return RCED_OK;
   }
-  if (shard) {
-    hipLaunchKernelGGL(shard_grad_out, dim3((unsigned)((t->xvars + train::kThreads - 1) / train::kThreads)), dim3(train::kThreads), 0, st,
-                       (const float*)t->grads, (const int*)t->x2i_dev, t->xvars, g_out, accumulate);
-    hipLaunchKernelGGL(shard_stats_out, dim3(kMaxLayers), dim3(kShardThreads), 0, st, (const double*)t->stash, t->shard, (double)P, s_out,
-                       accumulate);
-  } else {
-    adam_and_scan(t, lr, st);
+
+  // g_out != nullptr (a shard): the gradient and every BatchNorm layer's (sum z, sum z^2, pixels) go into (or, accumulate,
+  // are added to) g_out / s_out.  Otherwise Adam.  The one synchronise, and the loss.
+  int end(float* g_out, double* s_out, int accumulate, double* loss_out) {
+    if (forward_only) return RCED_OK;
+    if (t->wg_error) {   // (cannot happen with the up-front size above unless the runtime reports > 4 workgroups per CU)
+      (void)hipStreamSynchronize(st);   // nothing of this step is left in flight behind the error
+      return rced_fail(RCED_ERR_ALLOC, "deterministic weight gradients: the per-wave slice buffer could not be grown; the step was "
+                                       "abandoned before the optimizer ran%s",
+                       shard ? " and before the exchange buffers were written" : ", but the moving statistics have advanced by this batch");
+    }
+    if (shard) {
+      hipLaunchKernelGGL(shard_grad_out, dim3((unsigned)((t->xvars + train::kThreads - 1) / train::kThreads)), dim3(train::kThreads), 0, st,
+                         (const float*)t->grads, (const int*)t->x2i_dev, t->xvars, g_out, accumulate);
+      hipLaunchKernelGGL(shard_stats_out, dim3(kMaxLayers), dim3(kShardThreads), 0, st, (const double*)t->stash, t->shard, (double)P, s_out,
+                         accumulate);
+    } else {
+      adam_and_scan(t, lr, st);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    double loss = 0.0;
+    for (double v : hp) loss += v;
+    if (loss_out) *loss_out = loss / (double)t->batch_size;
+    return RCED_OK;
   }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(st));
-  double loss = 0.0;
-  for (double v : hp) loss += v;
-  if (loss_out) *loss_out = loss / (double)t->batch_size;
-  return RCED_OK;
+};
+
+int train_run(rced_trainer* t, const float* x_dev, const float* y_dev, float* pred_dev, int N, int T, float lr,
+              double* loss_out, void* stream, float* g_out = nullptr, double* s_out = nullptr, int accumulate = 0) {
+  if (!t) return rced_fail(RCED_ERR_ARG, "trainer is NULL");
+  if (N <= 0 || T <= 0 || !x_dev || (!y_dev && !pred_dev)) return rced_fail(RCED_ERR_ARG, "bad batch");
+  if (int rc = refuse_pending(t, pred_dev ? "rced_train_forward" : g_out ? "rced_train_grad" : "rced_train_step")) return rc;
+  DeviceGuard g(t->device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", t->device);
+  TrainPass pass(t, x_dev, y_dev, pred_dev, N, T, lr, stream, g_out != nullptr, 0.0, nullptr);
+  if (int rc = pass.begin()) return rc;
+  if (int rc = pass.advance()) return rc;
+  return pass.end(g_out, s_out, accumulate, loss_out);
 }
+
+// out[i] = ((g[0][i] + g[1][i]) + g[2][i]) + ...: the shards' rows added in shard order, one element per thread
+__global__ void sync_reduce(const double* __restrict__ g, int shards, size_t stride, int n, double* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double v = g[i];
+  for (int s = 1; s < shards; ++s) v += g[(size_t)s * stride + i];
+  out[i] = v;
+}
+constexpr int kSyncDoubles = 2 * train::kMaxC;   // the exchange buffer of a synchronised pass: (S1, S2) of a layer's channels
 }  // namespace
 
 extern "C" {
@@ -1094,6 +1304,7 @@ int rced_train_grad(rced_trainer* t, const float* x_dev, const float* y_dev, int
 int rced_train_apply(rced_trainer* t, const float* g_dev, const double* s_dev, float lr, void* stream) {
   if (!t) return rced_fail(RCED_ERR_ARG, "trainer is NULL");
   if (!g_dev || !s_dev) return rced_fail(RCED_ERR_ARG, "an exchange buffer is NULL");
+  if (int rc = refuse_pending(t, "rced_train_apply")) return rc;
   DeviceGuard g(t->device);
   if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", t->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1104,6 +1315,113 @@ int rced_train_apply(rced_trainer* t, const float* g_dev, const double* s_dev, f
   adam_and_scan(t, lr, st);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
+  return RCED_OK;
+}
+
+// ---- the synchronised step: rced_train_grad as a pass that stops at every BatchNorm layer, in both directions ----
+int rced_train_sync_points(rced_trainer* t, int* n_points, size_t* n_doubles) {
+  if (!t || !n_points || !n_doubles) return rced_fail(RCED_ERR_ARG, "trainer or output pointer is NULL");
+  int bn = 0;
+  for (int l = 0; l < t->net->n_layers; ++l) bn += t->net->layer[l].use_norm != 0;
+  *n_points = 2 * bn;
+  *n_doubles = kSyncDoubles;
+  return RCED_OK;
+}
+
+int rced_train_sync_begin(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, double pixels_total,
+                          double* xs_dev, void* stream) {
+  if (!t) return rced_fail(RCED_ERR_ARG, "trainer is NULL");
+  if (N <= 0 || T <= 0) return rced_fail(RCED_ERR_ARG, "a shard must have N >= 1 and T >= 1 (got %d x %d)", N, T);
+  if (!x_dev || !y_dev) return rced_fail(RCED_ERR_ARG, "input or target is NULL");
+  if (!xs_dev) return rced_fail(RCED_ERR_ARG, "the exchange buffer is NULL");
+  if (!(pixels_total >= (double)N * T * kFeatureDim))
+    return rced_fail(RCED_ERR_ARG, "pixels_total = %g is less than this shard's own %g pixels", pixels_total, (double)N * T * kFeatureDim);
+  if (int rc = refuse_pending(t, "rced_train_sync_begin")) return rc;
+  for (int l = 0; l < t->net->n_layers; ++l) {   // every BatchNorm layer's sums must pass through bn_finish: the MFMA plans
+    const plan::LayerPlan& pl = t->plan.layer[l];
+    if (t->net->layer[l].use_norm && (pl.stats != plan::Stats::Conv || pl.sums == plan::Sums::RouteReduce || pl.sums == plan::Sums::None))
+      return rced_fail(RCED_ERR_STATE, "layer %d: the synchronised step needs the layer's sums as records (the chan_reduce forms "
+                                       "under RCED_TRAIN_MFMA=0 have no exchange point)", l);
+  }
+  DeviceGuard g(t->device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", t->device);
+  auto pass = std::make_shared<TrainPass>(t, x_dev, y_dev, nullptr, N, T, 0.f, stream, true, pixels_total, xs_dev);
+  if (int rc = pass->begin()) return rc;
+  if (int rc = pass->advance()) {
+    (void)hipStreamSynchronize(pass->st);
+    return rc;
+  }
+  t->pending = pass;
+  return RCED_OK;
+}
+
+int rced_train_sync_next(rced_trainer* t, int* more) {
+  if (!t || !more) return rced_fail(RCED_ERR_ARG, "trainer or output pointer is NULL");
+  *more = 0;
+  if (!t->pending) return rced_fail(RCED_ERR_STATE, "rced_train_sync_next: no synchronised pass is pending on this trainer");
+  DeviceGuard g(t->device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", t->device);
+  if (t->pending->done()) return RCED_OK;
+  if (int rc = t->pending->advance()) {   // the pass is over: nothing of it stays in flight, the handle is free again
+    (void)hipStreamSynchronize(t->pending->st);
+    t->pending.reset();
+    return rc;
+  }
+  *more = t->pending->done() ? 0 : 1;
+  return RCED_OK;
+}
+
+int rced_train_sync_end(rced_trainer* t, float* g_dev, double* s_dev, double* loss_out, int accumulate) {
+  if (!t) return rced_fail(RCED_ERR_ARG, "trainer is NULL");
+  if (!g_dev || !s_dev) return rced_fail(RCED_ERR_ARG, "an exchange buffer is NULL");
+  if (!t->pending) return rced_fail(RCED_ERR_STATE, "rced_train_sync_end: no synchronised pass is pending on this trainer");
+  if (!t->pending->done())
+    return rced_fail(RCED_ERR_STATE, "rced_train_sync_end: the pending pass has exchange points left (rced_train_sync_next until "
+                                     "*more is 0, or rced_train_sync_abort)");
+  DeviceGuard g(t->device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", t->device);
+  const std::shared_ptr<TrainPass> pass = std::move(t->pending);
+  t->pending.reset();
+  const int rc = pass->end(g_dev, s_dev, accumulate != 0, loss_out);
+  if (rc) (void)hipStreamSynchronize(pass->st);
+  return rc;
+}
+
+int rced_train_sync_abort(rced_trainer* t) {
+  if (!t) return rced_fail(RCED_ERR_ARG, "trainer is NULL");
+  if (!t->pending) return RCED_OK;
+  DeviceGuard g(t->device);
+  const std::shared_ptr<TrainPass> pass = std::move(t->pending);
+  t->pending.reset();
+  HIP_TRY(hipStreamSynchronize(pass->st));   // what the pass has launched reads the caller's batch
+  return RCED_OK;
+}
+
+int rced_train_sync_reduce(rced_trainer* t, const double* gathered_dev, int shards, size_t stride, double* xs_dev, void* stream) {
+  if (!t || !gathered_dev || !xs_dev) return rced_fail(RCED_ERR_ARG, "trainer or buffer is NULL");
+  if (shards < 1 || stride < (size_t)kSyncDoubles)
+    return rced_fail(RCED_ERR_ARG, "needs shards >= 1 and rows at least %d doubles apart (got %d, %zu)", kSyncDoubles, shards, stride);
+  DeviceGuard g(t->device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", t->device);
+  hipLaunchKernelGGL(sync_reduce, dim3(1), dim3(kSyncDoubles), 0, static_cast<hipStream_t>(stream), gathered_dev, shards, stride,
+                     kSyncDoubles, xs_dev);
+  HIP_TRY(hipGetLastError());
+  return RCED_OK;
+}
+
+int rced_train_copy_variables(rced_trainer* dst, rced_trainer* src, void* stream) {
+  if (!dst || !src) return rced_fail(RCED_ERR_ARG, "trainer is NULL");
+  if (dst == src) return RCED_OK;
+  if (dst->variant != src->variant || dst->device != src->device || dst->nvars != src->nvars)
+    return rced_fail(RCED_ERR_ARG, "the two trainers must be of one variant on one device");
+  if (int rc = refuse_pending(dst, "rced_train_copy_variables")) return rc;
+  if (int rc = refuse_pending(src, "rced_train_copy_variables")) return rc;
+  DeviceGuard g(dst->device);
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", dst->device);
+  HIP_TRY(hipMemcpyAsync(dst->params, src->params, src->nvars * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+  // which layers take the exact recomputation is a matter of the variables: src's flags are those of its last step, which
+  // synchronised
+  for (int l = 0; l < kMaxLayers; ++l) dst->tiny_host[l] = src->tiny_host[l];
   return RCED_OK;
 }
 

@@ -609,13 +609,29 @@ class DataParallelTrainer(object):
 
     If the gradient pass of any rank raises, every rank raises after the gather (the failing one its own exception, the
     others PeerTrainError) and none applies; the object and the group stay usable.  A world larger than the batch is a
-    ValueError on every rank before any GPU work.  In train() only rank 0 prints, logs and writes checkpoints -- the
+    ValueError on every rank before any GPU work.
+
+    sync_bn=True: synchronised BatchNorm.  Every BatchNorm layer normalises by, and differentiates through,
+    the statistics of the WHOLE batch: rank r runs `grad_step_sync` on its rows, and at each of its exchange points (two per
+    BatchNorm layer: 18 a step for R-CED V1, 30 for R-CED V2 and CR-CED) the ranks all_gather [status, the layer's fp64 sums] and add them
+    in rank order with one launch; the gradient and statistics gathers and `apply_step` follow as above.  The step is then
+    the unsharded train_step over the whole batch up to the rounding of a few fp64 additions, and bit for bit
+    `train_step_sharded(shards, sync_bn=True)` on one device.  Under gloo every exchange point is a stream synchronise and a
+    host all_gather.  A rank whose pass raises keeps taking part in every remaining gather of the step with zeros and
+    status 1, so that no rank is left waiting; then it raises its own exception, the others PeerTrainError, none applies,
+    and the next step works.
+
+    In train() only rank 0 prints, logs and writes checkpoints -- the
     ranks' states are identical, so its files are the run's.  valid() runs over the whole loader on every rank and gives
     identical results; sharded validation is not built."""
 
-    def __init__(self, trainer, group=None, device=None):
+    def __init__(self, trainer, group=None, device=None, sync_bn=False):
         if not dist.is_initialized():
             raise RuntimeError("torch.distributed is not initialised (one process per GPU)")
+        if sync_bn and trainer.accumulate > 1:
+            raise ValueError("sync_bn=True cannot be combined with accumulate=%d: accumulation runs its shards one after the other, "
+                             "synchronised BatchNorm needs them all at every layer" % trainer.accumulate)
+        self.sync_bn = bool(sync_bn)
         self.trainer = trainer
         self.group = group
         self.rank = dist.get_rank(group)
@@ -642,16 +658,21 @@ class DataParallelTrainer(object):
         if self.world > n:
             raise ValueError("a world of %d ranks cannot share a batch of %d rows: every rank needs at least one" % (self.world, n))
         lo, hi = shard_bounds(n, self.world)[self.rank]
-        err, loss = None, 0.0
-        try:
-            loss = self.trainer.grad_step(input_x[lo:hi], target_y[lo:hi])
-        except Exception as e:       # the gathers below still run: the other ranks are on their way into them
-            err = e
+        err, loss, peer = None, 0.0, None
+        if self.sync_bn:
+            err, loss, peer = self._grad_step_sync(input_x, target_y, lo, hi)
+        else:
+            try:
+                loss = self.trainer.grad_step(input_x[lo:hi], target_y[lo:hi])
+            except Exception as e:       # the gathers below still run: the other ranks are on their way into them
+                err = e
         g, s = self.trainer.exchange_tensors()
         head = torch.tensor([0.0 if err is None else 1.0, loss], dtype=torch.float64, device=s.device)
         ds = self._gather(torch.cat([head, s]))
         gs = self._gather(g)
         bad = [r for r in range(self.world) if float(ds[r][0].item()) != 0.0]
+        if not bad and peer is not None:
+            bad = [peer]
         if err is not None:
             raise err
         if bad:
@@ -664,6 +685,48 @@ class DataParallelTrainer(object):
             s.add_(ds[r][2:])
             total += float(ds[r][1].item())
         return total, None, self.trainer.apply_step()
+
+    def _grad_step_sync(self, input_x, target_y, lo, hi):
+        """This rank's rows through FullyCNNTrainer.grad_step_sync: at every exchange point one all_gather of [status, the
+        layer's raw sums] and their sum in rank order (one launch), written over the pass's buffer.  Every rank takes part in
+        every one of the sync_points()[0] gathers of a step whatever happens: a rank whose pass has raised sends zeros with
+        status 1 from then on, a rank that sees a peer's status 1 aborts its own pass and sends zeros too.  Returns (this
+        rank's exception or None, its loss, the first failing peer or None); the caller's last two gathers end the step."""
+        tr = self.trainer
+        n_points, n_doubles = tr.sync_points()
+        shape = input_x.shape if hasattr(input_x, "shape") else torch.as_tensor(input_x).shape
+        pixels_total = float(int(shape[0]) * int(shape[1]) * 129)        # every rank is handed the whole batch
+        err, loss, peer, xs, gen = None, 0.0, None, None, None
+        try:
+            gen = tr.grad_step_sync(input_x[lo:hi], target_y[lo:hi], pixels_total)
+            xs = next(gen)
+        except Exception as e:
+            err, gen = e, None
+        zeros = torch.zeros(n_doubles, dtype=torch.float64, device=self.device)
+        for _ in range(n_points):
+            alive = gen is not None
+            status = torch.tensor([0.0 if err is None else 1.0], dtype=torch.float64, device=self.device)
+            rows = torch.stack(self._gather(torch.cat([status, xs if alive else zeros])))
+            bad = [r for r, v in enumerate(rows[:, 0].tolist()) if v != 0.0]
+            if bad and peer is None and err is None:
+                peer = bad[0]
+            if not alive:
+                continue
+            if bad:
+                gen.close()              # aborts the pass: the handle is free for the next step
+                gen = None
+                continue
+            tr.sync_reduce(rows[:, 1:], xs, stride=rows.stride(0))
+            try:
+                xs = next(gen)
+            except StopIteration as e:
+                loss, gen = e.value, None
+            except Exception as e:
+                err, gen = e, None
+        if gen is not None:              # (a pass with more exchange points than sync_points said: not with these nets)
+            gen.close()
+            err = err or RuntimeError("the synchronised pass did not end with its last exchange point")
+        return err, loss, peer
 
     def fit_step(self, input_x, target_y):
         """train_step, then the learning rate of the next step (FullyCNNTrainer.fit_step)."""

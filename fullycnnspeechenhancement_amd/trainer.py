@@ -12,7 +12,9 @@ The step in shards: `grad_step` runs forward, loss and backward
 tensors and changes nothing else, `apply_step` updates the moving statistics and runs Adam once from them;
 `train_step_sharded` is one optimizer step over a list of shards, and `accumulate=k` makes train_step / fit_step / train
 cut every batch into k of them.  BatchNorm normalises every shard by its own statistics.  dist.DataParallelTrainer runs
-the same step with the shards on ranks.
+the same step with the shards on ranks.  Opt-in, `sync_bn=True` (train_step_sharded, DataParallelTrainer): BatchNorm over the
+union of the shards -- `grad_step_sync` is a shard's pass as a generator that stops at every BatchNorm layer, forward and
+backward, for the caller to add up the shards' sums; the step is then the unsharded one.
 """
 
 import ctypes
@@ -94,6 +96,8 @@ class FullyCNNTrainer(object):
             raise ValueError("accumulate must be a positive integer (1: the whole batch in one piece), got %r" % (accumulate,))
         self.accumulate = int(accumulate)          # train_step cuts its batch into this many shards (gradient accumulation)
         self._exch = None                          # (gradient fp32, statistics sums fp64): the sharded step's exchange tensors
+        self._sync_xs = None                       # the synchronised step's exchange tensor (grad_step_sync yields it)
+        self._replicas = []                        # train_step_sharded(sync_bn=True): one more trainer per further shard
         self.net_work = net_work
         self.variant = spec.variant_of(net_work)
         self.batch_size = int(batch_size)          # [training] batch_size: what the loss divides by
@@ -188,16 +192,118 @@ class FullyCNNTrainer(object):
         _lib.check(_lib.load().rced_train_apply(self._h, g.data_ptr(), s.data_ptr(), ctypes.c_float(self.lr), st))
         return self.global_step
 
-    def train_step_sharded(self, shards):
+    def train_step_sharded(self, shards, sync_bn=False):
         """One optimizer step over a list of (x, y) shards, each [N_s, T_s, 129, 1] (shapes may differ): the gradient is the
         fp32 sum of the shards' gradients in list order, the reported loss the sum of their losses, BatchNorm per shard.
-        One shard is train_step, bit for bit.  Returns (loss, None, global_step).  Nothing is applied if a shard fails."""
+        One shard is train_step, bit for bit.  Returns (loss, None, global_step).  Nothing is applied if a shard fails.
+
+        sync_bn=True: BatchNorm over the UNION of the shards (the synchronised step) -- the step is then the
+        unsharded train_step over all the shards' rows up to the rounding of a few fp64 additions, and it is what
+        dist.DataParallelTrainer(sync_bn=True) computes with the shards on ranks, bit for bit.  The shards' passes run in
+        lockstep, one trainer per shard (this one and cached replicas that are handed this one's variables before the step),
+        and stop together at every BatchNorm layer, forward and backward, to add up their sums in list order.  EVERY SHARD'S
+        ACTIVATIONS ARE LIVE AT ONCE: this form saves no memory over the whole batch in one piece; it states on one device
+        what a world of ranks computes.  Not with accumulate=k > 1 (ValueError): accumulation runs its shards one after the
+        other, and whole-batch statistics would need every layer's forward of every shard again."""
+        if sync_bn and self.accumulate > 1:
+            raise ValueError("sync_bn=True cannot be combined with accumulate=%d: accumulation runs its shards one after the other, "
+                             "synchronised BatchNorm needs them all at every layer" % self.accumulate)
         shards = [self._on_device(x, y) for x, y in shards]
         if not shards:
             raise ValueError("train_step_sharded needs at least one shard")
+        if sync_bn:
+            return self._train_step_sharded_sync(shards)
         loss = 0.0
         for i, (x, y) in enumerate(shards):
             loss += self.grad_step(x, y, accumulate=i > 0)
+        return loss, None, self.apply_step()
+
+    # -- the synchronised step (DESIGN.md 3.5b) ----------------------------------------------------------
+    def sync_points(self):
+        """(exchange points of one synchronised pass, doubles in the buffer that grad_step_sync yields)."""
+        n, nd = ctypes.c_int(), ctypes.c_size_t()
+        _lib.check(_lib.load().rced_train_sync_points(self._h, ctypes.byref(n), ctypes.byref(nd)))
+        return n.value, nd.value
+
+    def grad_step_sync(self, input_x, target_y, pixels_total):
+        """grad_step with BatchNorm over more than this shard, as a generator.  At every exchange point (sync_points()[0] of
+        them: each BatchNorm layer once forward, once backward) it yields ONE float64 device tensor, always the same, that
+        holds this shard's raw sums of the layer; the caller overwrites it in place with the ordered sum over all shards, on
+        the current stream, and resumes.  pixels_total: the pixels of all shards, sum N_s * T_s * 129.  The generator's
+        return value (StopIteration.value) is the shard's loss; the exchange tensors then hold the shard's gradient and
+        statistics sums as after grad_step.  Closing the generator early aborts the pass; until it has ended one way or
+        the other, every other call on this trainer raises.  With the yielded tensor left as it is and pixels_total this
+        shard's own count, the pass is grad_step bit for bit."""
+        import torch
+        x, y = self._on_device(input_x, target_y)
+        g, s = self.exchange_tensors()
+        if self._sync_xs is None:
+            self._sync_xs = torch.zeros(self.sync_points()[1], dtype=torch.float64, device="cuda:%d" % self.device)
+        xs, lib, h = self._sync_xs, _lib.load(), self._h
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        _lib.check(lib.rced_train_sync_begin(h, x.data_ptr(), y.data_ptr(), int(x.shape[0]), int(x.shape[1]),
+                                             ctypes.c_double(float(pixels_total)), xs.data_ptr(), st))
+        ended = False
+        try:
+            more = ctypes.c_int(1)
+            while more.value:
+                yield xs
+                _lib.check(lib.rced_train_sync_next(h, ctypes.byref(more)))
+            loss = ctypes.c_double()
+            _lib.check(lib.rced_train_sync_end(h, g.data_ptr(), s.data_ptr(), ctypes.byref(loss), 0))
+            ended = True
+            return loss.value
+        finally:
+            if not ended:
+                lib.rced_train_sync_abort(h)
+
+    def sync_reduce(self, rows, xs, stride=None):
+        """xs[i] = ((rows[0][i] + rows[1][i]) + ...): the ordered sum of an exchange point in one launch.  rows: float64
+        device tensor [shards, >= len(xs)], contiguous; a row's first len(xs) entries are added."""
+        import torch
+        st = torch.cuda.current_stream(xs.device).cuda_stream
+        _lib.check(_lib.load().rced_train_sync_reduce(self._h, rows.data_ptr(), int(rows.shape[0]),
+                                                      int(rows.stride(0) if stride is None else stride), xs.data_ptr(), st))
+
+    def _train_step_sharded_sync(self, shards):
+        import torch
+        while len(self._replicas) < len(shards) - 1:      # made once, from this trainer's variables; refreshed below
+            self._replicas.append(FullyCNNTrainer(self.net_work, batch_size=self.batch_size, weights=self.variables(),
+                                                  device=self.device))
+        trainers = [self] + self._replicas[:len(shards) - 1]
+        st = torch.cuda.current_stream(shards[0][0].device).cuda_stream
+        for r in trainers[1:]:
+            _lib.check(_lib.load().rced_train_copy_variables(r._h, self._h, st))
+        pixels_total = float(sum(int(x.shape[0]) * int(x.shape[1]) * spec.FEATURE_DIM for x, _ in shards))
+        passes = [tr.grad_step_sync(x, y, pixels_total) for tr, (x, y) in zip(trainers, shards)]
+        losses = [None] * len(shards)
+        try:
+            bufs = [next(p) for p in passes]
+            rows = torch.empty((len(shards), bufs[0].numel()), dtype=torch.float64, device=bufs[0].device)
+            while bufs:
+                for i, b in enumerate(bufs):
+                    rows[i].copy_(b)
+                for tr, b in zip(trainers, bufs):
+                    tr.sync_reduce(rows, b)
+                bufs = []
+                for i, p in enumerate(passes):
+                    try:
+                        bufs.append(next(p))
+                    except StopIteration as e:
+                        losses[i] = e.value
+                if bufs and len(bufs) != len(passes):
+                    raise RuntimeError("the shards' passes did not stop at the same exchange points")
+        finally:
+            for p in passes:
+                p.close()
+        g, s = self.exchange_tensors()
+        loss = 0.0
+        for tr, l in zip(trainers, losses):              # the ordered sum, as dist.DataParallelTrainer forms it
+            if tr is not self:
+                gr, sr = tr.exchange_tensors()
+                g.add_(gr)
+                s.add_(sr)
+            loss += l
         return loss, None, self.apply_step()
 
     def valid_step(self, input_x):
@@ -362,6 +468,9 @@ class FullyCNNTrainer(object):
         return self
 
     def close(self):
+        replicas, self._replicas = getattr(self, "_replicas", []), []
+        for r in replicas:
+            r.close()
         if self.model is not None:
             self.model.close()     # the model owns the handle
 

@@ -626,6 +626,43 @@ int rced_train_grad(rced_trainer* t, const float* x_dev, const float* y_dev, int
  * content.  Buffers no rced_train_grad has filled are the caller's error and are not detected.  Synchronises the stream. */
 int rced_train_apply(rced_trainer* t, const float* g_dev, const double* s_dev, float lr, void* stream);
 
+/* ---- the synchronised step: rced_train_grad with every BatchNorm layer normalising by, and differentiating through, the
+ * statistics of the UNION of the shards, so that the step over the shards is the unsharded step over the whole batch up to
+ * the rounding of a few fp64 additions.  The pass of one shard stops at every exchange point -- each BatchNorm layer once
+ * in the forward, with the raw (sum z, sum z^2) per channel, and once in the backward, with the raw (sum d_u, sum d_u z) or
+ * (sum d_u, sum d_u x) -- and leaves those sums in the caller's device buffer xs_dev (interleaved per channel of the
+ * even-padded internal layout, n_doubles doubles, the tail unused).  The caller replaces xs_dev by the sum over all shards,
+ * on the pass's stream, and resumes; the layer is then finished with pixels_total, the pixel count of all shards
+ * (sum of N_s * T_s * 129), in place of the shard's own.  Every shard of a step stops at the same points in the same order
+ * (which kernels run is a matter of the variant and the variables alone).  With one shard, pixels_total its own count and
+ * xs_dev left as it is, the pass is rced_train_grad bit for bit.
+ *
+ *   rced_train_sync_points   the exchange points of a pass (2 per BatchNorm layer) and the size of xs_dev in doubles
+ *   rced_train_sync_begin    packs the weights and runs to the first exchange point.  Asynchronous.  RCED_ERR_STATE where the
+ *                            handle's plan has a layer whose sums are not formed from records (RCED_TRAIN_MFMA=0)
+ *   rced_train_sync_next     xs_dev holds the shards' sum: finishes that point and runs to the next.  *more = 0 once the
+ *                            backward is through.  Asynchronous.  An error ends the pass
+ *   rced_train_sync_end      what the end of rced_train_grad does: the shard's own gradient -- d gamma and d beta are the
+ *                            shard's own sums, so the sum over shards makes them the batch's -- and its own (sum z, sum z^2,
+ *                            pixels) into g_dev / s_dev (accumulate as there), *loss_out = loss_s.  Synchronises the stream.
+ *                            RCED_ERR_STATE while exchange points are left
+ *   rced_train_sync_abort    leaves a pass that was begun, at any point; synchronises its stream.  Without one: RCED_OK
+ *
+ * While a pass is open, every other entry point that takes the handle and touches its state (step, forward, grad, apply,
+ * get_* / set_state, copy_variables, a second begin) returns RCED_ERR_STATE and says that a pass is pending. */
+int rced_train_sync_points(rced_trainer* t, int* n_points, size_t* n_doubles);
+int rced_train_sync_begin(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, double pixels_total,
+                          double* xs_dev, void* stream);
+int rced_train_sync_next(rced_trainer* t, int* more);
+int rced_train_sync_end(rced_trainer* t, float* g_dev, double* s_dev, double* loss_out, int accumulate);
+int rced_train_sync_abort(rced_trainer* t);
+/* xs_dev[i] = ((g[0][i] + g[1][i]) + g[2][i]) + ... for i < n_doubles, the shards' rows `stride` doubles apart in
+ * gathered_dev (stride >= n_doubles): the ordered sum of an exchange point in one launch.  Asynchronous. */
+int rced_train_sync_reduce(rced_trainer* t, const double* gathered_dev, int shards, size_t stride, double* xs_dev, void* stream);
+/* dst's variables (moving statistics included) := src's; two trainers of one variant on one device.  Adam slots and
+ * global_step stay dst's own.  Asynchronous. */
+int rced_train_copy_variables(rced_trainer* dst, rced_trainer* src, void* stream);
+
 long long rced_train_global_step(rced_trainer* t);
 /* Current variables / last gradients, in blob order (gradients of moving statistics are 0). */
 int rced_train_get_variables(rced_trainer* t, float* blob_host, size_t n_floats);

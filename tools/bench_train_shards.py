@@ -2,7 +2,7 @@
 """What the split of the training step costs: `train_step` beside `grad_step` + `apply_step` over S = 1, 2 and 4
 accumulation shards, at BASELINE config 5's size (CR-CED V3, 256 x 512 frames), all in one run.
 
-    python tools/bench_train_shards.py [--batch 256] [--frames 512] [--steps 5] [--rounds 5] [--warmup 2]
+    python tools/bench_train_shards.py [--batch 256] [--frames 512] [--steps 5] [--rounds 5] [--warmup 2] [--sync]
 
 One trainer runs every form (each is one optimizer step over the same batch).  The forms alternate: a round times `steps`
 calls of each form in turn, and the figure of a form is the median over the rounds of its per-step time, printed with the
@@ -10,6 +10,11 @@ fastest and the slowest round.  Every call ends in a device synchronise (the ste
 the calls measures the device work plus the launches.  `train_step` is the unsharded path and the yardstick; S = 1 adds to
 it the two exchange kernels of the gradient pass and the memset, scatter and moving-statistics kernels of the apply.
 S = 2 and 4 run the same pixels in 2 and 4 passes: shorter grids per pass, the weights packed once per pass.
+--sync adds the synchronised step (`train_step_sharded(cut, sync_bn=True)`) over the same S in the same
+run, as `sync_S`: S trainers on this device in lockstep, thirty stops a step, each with S small copies and S ordered-sum
+launches on the stream and no host synchronise.  It is what the stops cost on ONE device; a world of ranks under gloo adds
+a stream synchronise and a host all_gather per stop, which this tool does not measure.  The replicas hold activations of
+their own: --sync needs about twice the memory.
 Prints one JSON line.  Needs a GPU: there is no other way to take these numbers."""
 
 import argparse
@@ -31,6 +36,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--shards", type=int, nargs="*", default=[1, 2, 4])
+    ap.add_argument("--sync", action="store_true", help="also time the synchronised step over the same shard counts")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -47,6 +53,8 @@ def main():
     for s in a.shards:
         cut = [(x[lo:hi], y[lo:hi]) for lo, hi in shard_bounds(a.batch, s)]
         forms["shards_%d" % s] = (lambda cut=cut: tr.train_step_sharded(cut))
+        if a.sync:
+            forms["sync_%d" % s] = (lambda cut=cut: tr.train_step_sharded(cut, sync_bn=True))
     for fn in forms.values():              # every shape the timed window uses, before it
         for _ in range(a.warmup):
             fn()
