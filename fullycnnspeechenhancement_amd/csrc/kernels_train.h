@@ -2,8 +2,13 @@
 // graph).  Correctness-first, layer by layer, fp32 data with fp64 reductions; the convolutions reuse
 // conv_layer_generic (forward, and dgrad with flipped / transposed weights).  Not tuned: the hot path of
 // this repo is the inference forward; this exists so that config 5 (fwd + bwd + Adam) runs and is checked.
+// Also here: the small kernels every form of the step shares -- bn_finish (a layer's sums finished in one launch),
+// step_epilogue (moving statistics and the tiny-gamma scan, behind Adam), and the exchange kernels of the sharded and the
+// synchronised step.  The MFMA convolutions are in kernels_train_mfma.h.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "rced_spec.h"
 
 namespace rced {
 namespace train {
@@ -58,11 +63,8 @@ __global__ __launch_bounds__(kThreads) void chan_reduce(const float* __restrict_
 }
 
 // sums[c][2] = sum over partials.  One workgroup per output (launch with 2*C workgroups).
-// only_if: a device flag; the launch is a no-op when it is given and zero (the conditional exact recomputation behind
-// bn_finish, mode kFinX, train_api.hip).
 __global__ __launch_bounds__(kThreads) void reduce_finish(const double* __restrict__ part, int nparts, int C,
-                                                           double* __restrict__ sums, const int* __restrict__ only_if = nullptr) {
-  if (only_if && *only_if == 0) return;
+                                                           double* __restrict__ sums) {
   __shared__ double s[kThreads];
   const int tid = threadIdx.x, n = 2 * C, i = blockIdx.x;
   double t = 0.0;
@@ -76,11 +78,10 @@ __global__ __launch_bounds__(kThreads) void reduce_finish(const double* __restri
   if (tid == 0) sums[i] = s[0];
 }
 
-// Batch statistics from (sum z, sum z^2): mu, rstd = 1/sqrt(var_biased + eps); moving statistics with
-// momentum 0.99 (moving_variance takes the unbiased batch variance, as TF's fused batch norm does).
-__global__ void bn_stats_finish(const double* __restrict__ sums, double P, int C, float eps, float momentum,
-                                float* __restrict__ mu, float* __restrict__ rstd, float* __restrict__ moving_mean,
-                                float* __restrict__ moving_var) {
+// Batch statistics from (sum z, sum z^2): mu, rstd = 1/sqrt(var_biased + eps).  (The moving statistics follow behind the
+// backward: step_epilogue.)
+__global__ void bn_stats_finish(const double* __restrict__ sums, double P, int C, float eps, float* __restrict__ mu,
+                                float* __restrict__ rstd) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   const double m = sums[2 * c] / P;
@@ -88,9 +89,6 @@ __global__ void bn_stats_finish(const double* __restrict__ sums, double P, int C
   if (var < 0.0) var = 0.0;
   mu[c] = (float)m;
   rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-  const double unbiased = P > 1.0 ? var * P / (P - 1.0) : var;
-  moving_mean[c] = (float)(momentum * (double)moving_mean[c] + (1.0 - momentum) * m);
-  moving_var[c] = (float)(momentum * (double)moving_var[c] + (1.0 - momentum) * unbiased);
 }
 
 // (mean, biased variance) of the batch from (sum z, sum z^2): out[c] = mean, out[C + c] = variance -- what TF's UPDATE_OPS
@@ -103,6 +101,93 @@ __global__ void batch_mean_var(const double* __restrict__ sums, double P, int C,
   if (var < 0.0) var = 0.0;
   out[c] = (float)m;
   out[C + c] = (float)var;
+}
+
+__global__ void sums_to_float(const double* __restrict__ sums, int C, int which, float* __restrict__ dst) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < C) dst[c] = (float)sums[2 * c + which];
+}
+
+// kFinX below: the fused backward kernel leaves (sum d_u, sum d_u * x), x = relu(a z + b); where d_u != 0, z = (x - b) / a.
+// That division is exact enough only while |gamma| is not tiny (x was rounded to fp32: zhat comes back with an error of
+// eps |x| / |gamma|), and meaningless for gamma = 0 -- where S2 is still needed: it is gamma's own gradient, and TF's
+// d gamma = sum dy * zhat does not vanish with gamma.  A layer with a channel of |gamma| < kTinyGamma (step_epilogue tells
+// the host which) therefore gets its sums exactly from (g, z): bwd_route2's records, finished as kFinPlain.
+constexpr float kTinyGamma = 1e-3f;
+
+// ONE launch for what used to be three to five (reduce_finish over 2 C workgroups, then a fix-up of S2 or
+// bn_stats_finish, then two sums_to_float): a CR-CED step issued ~150 of these 5-us kernels, all on the critical path.
+// One workgroup of 1024 threads: thread (i, p) adds records p, p + 16, ... of value i < 2 C, the 16 partial sums are added
+// in order (the same bits every run), then threads c < C finish the layer:
+//   kFinPlain  sums = (S1, S2) as they are                      (bwd_route2's records)
+//   kFinZ      S2 = rstd (sum d_u z - mu S1)                    (a SUMS dgrad's records)
+//   kFinX      S2 from sum d_u x                                (the fused backward kernel's records)
+//   kFinStats  (sum z, sum z^2) -> mu, rstd                     (forward: bn_stats_finish)
+// kFinPlain / Z / X also write d beta = S1 and d gamma = S2 (g_beta / g_gamma).
+// Over ONE record the reduction is 0.0 + v = v: finishing a layer from an exchange buffer that holds the reduced sums gives
+// the bits of finishing it from the records (the synchronised step, TrainPass::point_finish).
+enum { kFinPlain = 0, kFinZ = 1, kFinX = 2, kFinStats = 3 };
+struct FinishArgs {
+  const float *mu, *rstd, *gamma, *beta;      // kFinZ / kFinX
+  float *g_beta, *g_gamma;                    // backward modes (may be null)
+  double P; float eps;                        // kFinStats
+  float *mu_out, *rstd_out;
+  double* raw_out;                            // every mode (may be null): the reduced (S1, S2) as the records gave them
+};
+__global__ __launch_bounds__(1024) void bn_finish(const double* __restrict__ part, int nparts, int C, double* __restrict__ sums,
+                                                  int mode, FinishArgs a) {
+  __shared__ double red[16][64];
+  const int i = threadIdx.x & 63, p = threadIdx.x >> 6, n = 2 * C;
+  double t = 0.0;
+  if (i < n) {
+    // four independent chains (records p, p+16, p+32, p+48 of every 64), added in a fixed order: the loads of one
+    // chain were a serial ~100 ns each, 128 of them for bwd_route2's 2048 records (14 us per launch, 40 launches)
+    double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
+    int k = p;
+    for (; k + 48 < nparts; k += 64) {
+      const double a0 = part[(size_t)k * n + i], a1 = part[(size_t)(k + 16) * n + i];
+      const double a2 = part[(size_t)(k + 32) * n + i], a3 = part[(size_t)(k + 48) * n + i];
+      t0 += a0; t1 += a1; t2 += a2; t3 += a3;
+    }
+    for (; k < nparts; k += 16) t0 += part[(size_t)k * n + i];
+    t = (t0 + t1) + (t2 + t3);
+  }
+  red[p][i] = t;
+  __syncthreads();
+  if (p == 0 && i < n) {
+    double v = red[0][i];
+#pragma unroll
+    for (int q = 1; q < 16; ++q) v += red[q][i];
+    red[0][i] = v;
+  }
+  __syncthreads();
+  const int c = threadIdx.x;
+  if (c >= C) return;
+  const double s1 = red[0][2 * c];
+  double s2 = red[0][2 * c + 1];
+  if (a.raw_out) {   // (the synchronised step's exchange buffer: what the shards add up before the layer is finished)
+    a.raw_out[2 * c] = s1;
+    a.raw_out[2 * c + 1] = s2;
+  }
+  if (mode == kFinStats) {
+    const double m = s1 / a.P;
+    double var = s2 / a.P - m * m;
+    if (var < 0.0) var = 0.0;
+    a.mu_out[c] = (float)m;
+    a.rstd_out[c] = (float)(1.0 / sqrt(var + (double)a.eps));
+  } else {
+    if (mode == kFinZ) {
+      s2 = (double)a.rstd[c] * (s2 - (double)a.mu[c] * s1);
+    } else if (mode == kFinX) {
+      const float ga = a.gamma[c] * a.rstd[c];                 // the folded forward, exactly as xform_table_fill forms it
+      const float gb = a.beta[c] - ga * a.mu[c];
+      s2 = ga != 0.f ? (double)a.rstd[c] * ((s2 - (double)gb * s1) / (double)ga - (double)a.mu[c] * s1) : 0.0;
+    }
+    if (a.g_beta) a.g_beta[c] = (float)s1;
+    if (a.g_gamma) a.g_gamma[c] = (float)s2;
+  }
+  sums[2 * c] = s1;
+  sums[2 * c + 1] = s2;
 }
 
 // ---- forward elementwise: out = act(gamma*(z-mu)*rstd + beta + skip_pre) + skip_post -------------
@@ -250,7 +335,9 @@ __global__ __launch_bounds__(kThreads) void bwd_route2(const float2* __restrict_
                                                         const int* __restrict__ only_if = nullptr, int skip_first = 0) {
   // skip_first: this launch is the FIRST writer of the skip source's gradient tensor -- it stores instead of adding, so
   // the tensor needs neither a memset nor this kernel's read of it
-  if (only_if && *only_if == 0) return;   // wave-uniform: see reduce_finish
+  // only_if: a device flag, the launch a no-op when it is given and zero.  Nobody passes one any more; the parameter stays
+  // because the compiler schedules this kernel's reduction tail differently without it.
+  if (only_if && *only_if == 0) return;   // wave-uniform
   __shared__ double red[kThreads * 4];
   const PairLane L(C, threadIdx.x);
   double acc[2][2] = {{0.0, 0.0}, {0.0, 0.0}};   // [k][S1, S2]
@@ -413,6 +500,78 @@ __global__ __launch_bounds__(kThreads) void adam_step(float* __restrict__ p, con
   m[i] = mi;
   v[i] = vi;
   p[i] -= lr_t * mi / (sqrtf(vi) + eps);
+}
+
+// ---- per-layer tables and what runs behind Adam ------------------------------------------------------
+// Where a layer's BatchNorm lives: float offsets of gamma and the moving statistics in the internal variable blob, its
+// channels in that blob (cout: even-padded) and in the reference's (xcout), and soff: the layer's first double in the fp64
+// exchange buffer of the sharded step -- (S1, S2) = (sum z, sum z^2) of the reference's channels, interleaved, then the
+// pixel count; BatchNorm layers in layer order; -1: the layer has no BatchNorm.  By value into the kernels below.
+struct LayerTable { int gamma[kMaxLayers], mmean[kMaxLayers], mvar[kMaxLayers], cout[kMaxLayers], xcout[kMaxLayers], soff[kMaxLayers]; };
+
+// THE moving-statistics update (tf.layers.batch_normalization's UPDATE_OPS): from (sum z, sum z^2) over P pixels the mean
+// and the clamped biased variance; moving_variance takes the unbiased one, as TF's fused batch norm does.  All in fp64.
+__device__ inline void moving_update(double s1, double s2, double P, float momentum, float* moving_mean, float* moving_var) {
+  const double m = s1 / P;
+  double var = s2 / P - m * m;
+  if (var < 0.0) var = 0.0;
+  const double unbiased = P > 1.0 ? var * P / (P - 1.0) : var;
+  *moving_mean = (float)((double)momentum * (double)*moving_mean + (1.0 - (double)momentum) * m);
+  *moving_var = (float)((double)momentum * (double)*moving_var + (1.0 - (double)momentum) * unbiased);
+}
+
+// Behind Adam, one workgroup of 64 threads per layer, one thread per channel.  (1) The layer's moving statistics: the only
+// place they are written.  s: the forward's stashed sums ([layer][2 * kMaxC] doubles, over P pixels: the step), or
+// (exchange) the exchange buffer with its own pixel count (rced_train_apply).  A phantom (even-padded) channel has z = 0
+// everywhere: S1 = S2 = 0.  (2) flags[l] = some channel of the layer has |gamma| < kTinyGamma, into host-mapped memory: the
+// NEXT step knows on the host which layers need their sums recomputed exactly.
+__global__ void step_epilogue(float* __restrict__ params, LayerTable a, const double* __restrict__ s, int exchange, double P,
+                              float momentum, int* __restrict__ flags) {
+  const int l = blockIdx.x, c = threadIdx.x;
+  const bool on = a.soff[l] >= 0 && c < a.cout[l];
+  if (on) {
+    const double* sl = exchange ? s + a.soff[l] : s + (size_t)l * 2 * kMaxC;
+    const bool real = c < a.xcout[l];
+    moving_update(real ? sl[2 * c] : 0.0, real ? sl[2 * c + 1] : 0.0, exchange ? sl[2 * a.xcout[l]] : P, momentum,
+                  params + a.mmean[l] + c, params + a.mvar[l] + c);
+  }
+  const int any = __syncthreads_or(on && !(fabsf(params[a.gamma[l] + c]) >= kTinyGamma));
+  if (c == 0) flags[l] = any;
+}
+
+// ---- the sharded step: one shard's gradient and statistics sums out into the caller's exchange buffers, and back ----
+// One element per thread with its own read-modify-write (no atomics): the sum over shards is formed in call order.
+constexpr int kShardThreads = 128;   // >= 2 * kMaxC + 1 entries of a layer
+static_assert(2 * kMaxC + 1 <= kShardThreads, "one thread per statistics entry of a layer");
+
+// g[e] (+)= grads[x2i[e]]: the internal (even-padded) gradient in the reference's blob order
+__global__ void shard_grad_out(const float* __restrict__ grads, const int* __restrict__ x2i, size_t n, float* __restrict__ g,
+                               int accumulate) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  const float v = grads[x2i[e]];
+  g[e] = accumulate ? g[e] + v : v;
+}
+// one workgroup per layer: s[soff + i] (+)= the layer's stashed (S1, S2) entry i < 2 xcout, the pixel count behind them
+__global__ void shard_stats_out(const double* __restrict__ stash, LayerTable a, double P, double* __restrict__ s, int accumulate) {
+  const int l = blockIdx.x, i = threadIdx.x;
+  if (a.soff[l] < 0 || i > 2 * a.xcout[l]) return;
+  const double v = i < 2 * a.xcout[l] ? stash[(size_t)l * 2 * kMaxC + i] : P;
+  double* d = s + a.soff[l] + i;
+  *d = accumulate ? *d + v : v;
+}
+// grads[x2i[e]] = g[e] (phantom entries were zeroed before)
+__global__ void shard_grad_in(const float* __restrict__ g, const int* __restrict__ x2i, size_t n, float* __restrict__ grads) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n) grads[x2i[e]] = g[e];
+}
+// out[i] = ((g[0][i] + g[1][i]) + g[2][i]) + ...: the shards' rows of a synchronised exchange point added in shard order
+__global__ void sync_reduce(const double* __restrict__ g, int shards, size_t stride, int n, double* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double v = g[i];
+  for (int s = 1; s < shards; ++s) v += g[(size_t)s * stride + i];
+  out[i] = v;
 }
 
 // ---- weight layouts for conv_layer_generic ---------------------------------------------------------

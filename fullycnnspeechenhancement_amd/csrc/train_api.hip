@@ -1,7 +1,9 @@
 // C ABI of the training step (include/rced.h, "training" section): host-side orchestration.
 // Replaces FullyCNNTrainer.creat_graph + train_step (model_utils/trainer.py:156-192): forward with
 // train-mode BatchNorm, loss = sum((target - pred)^2) / batch_size, backward, TF-form Adam, moving
-// statistics update.  Layer by layer; see kernels_train.h.
+// statistics update.  Here: the handle, TrainPass (the layer loops of every form of the step) and the C ABI.  The small
+// kernels are in kernels_train.h, the MFMA ones in kernels_train_mfma.h, their launchers in train_mfma_dispatch.h and
+// train_launch.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,11 +16,9 @@
 #include "../../include/rced.h"
 #include "kernels_generic.h"
 #include "kernels_train.h"
-#include "kernels_train_mfma.h"
-#include "kernels_final_x6.h"
-#include "train_mfma_dispatch.h"
 #include "rced_internal.h"
 #include "rced_spec.h"
+#include "train_launch.h"
 #include "train_plan.h"
 
 using namespace rced;
@@ -26,12 +26,9 @@ using namespace rced;
 namespace {
 constexpr int kReduceGrid = 512;
 using rced::tmd::kPairGrid;
-using rced::tmd::allow_lds;
 using rced::tmd::tm_packet_floats;
 using rced::tmd::WgDet;
-using rced::tms::tm_has;
-using rced::tms::first_has;
-using rced::tms::is_output_layer;
+using namespace rced::train;   // bn_finish and its modes, step_epilogue, the exchange kernels
 constexpr float kAdamB1 = 0.9f, kAdamB2 = 0.999f, kAdamEps = 1e-8f;   // tf.train.AdamOptimizer defaults
 constexpr float kBnMomentum = 0.99f;                                  // tf.layers.batch_normalization default
 
@@ -39,11 +36,6 @@ struct LayerOff {   // float offsets into the variable blob
   size_t kernel, bias, gamma, beta, mmean, mvar;
   int cin, cout, cout4, cin4, K;
 };
-// The fp64 exchange buffer of the sharded step (rced_train_grad / rced_train_apply), per BatchNorm layer in layer order:
-// (S1, S2) = (sum z, sum z^2) of the reference's channels, interleaved, then the pixel count.  soff: the layer's first
-// double, -1 without BatchNorm; xcout: the reference's channel count (cout: the even-padded one); mmean / mvar: the
-// moving statistics' float offsets in the internal blob.
-struct ShardArgs { int soff[kMaxLayers], xcout[kMaxLayers], cout[kMaxLayers], mmean[kMaxLayers], mvar[kMaxLayers]; };
 struct TrainPass;   // one run of the step's layer loops (below); the synchronised step keeps one open between its calls
 }  // namespace
 
@@ -78,22 +70,22 @@ struct rced_trainer {
   float* pk_fin = nullptr, *pk_fin_bwd = nullptr;     // Toeplitz A fragments of the 1x129 output layer (rebuilt every step)
   float* zero32 = nullptr;
   double *part = nullptr, *sums = nullptr;
-  int* redo = nullptr;         // device flag behind `sums` (same allocation), written by bn_finish's kFinX mode
   int* tiny_host = nullptr;    // [layers] pinned, host-mapped: 1 = some |gamma| of the layer is below kTinyGamma (written by
-  int* tiny_dev = nullptr;     // tiny_gamma_scan behind every Adam step, read by the host at the start of the next step)
+  int* tiny_dev = nullptr;     // step_epilogue behind every Adam step, read by the host at the start of the next step)
   // activations for P pixels
   size_t cap_px = 0;
   std::vector<float*> out, z, G;   // out/G indexed by tensor id (0 unused), z by layer
   float* D = nullptr;
   long long global_step = 0;
-  // the sharded step: x2i on the device, every BatchNorm layer's (S1, S2) of the last rced_train_grad forward
-  // ([layers][2 * kMaxC] doubles), and where they go in the fp64 exchange buffer (xstats doubles)
-  int* x2i_dev = nullptr;
+  // every BatchNorm layer's (S1, S2) = (sum z, sum z^2) of the last forward ([layers][2 * kMaxC] doubles): what the moving
+  // statistics are updated from behind Adam, and what a shard hands out.  The sharded step: x2i on the device, and where
+  // the layers' sums go in the fp64 exchange buffer (tab.soff, xstats doubles)
   double* stash = nullptr;
-  ShardArgs shard{};
+  LayerTable tab{};
+  int* x2i_dev = nullptr;
   size_t xstats = 0;
   // the synchronised step: the pass that rced_train_sync_begin opened and rced_train_sync_end / _abort has not closed yet
-  std::shared_ptr<TrainPass> pending;
+  std::unique_ptr<TrainPass> pending;
   std::vector<void*> owned;       // every device allocation made by rced_train_create
   std::vector<void*> act_bases;   // the allocations behind out / z / G / D, made for a pixel count (ensure_acts)
   template <class T>
@@ -109,13 +101,8 @@ struct rced_trainer {
     D = nullptr;
     cap_px = 0;
   }
-  ~rced_trainer() {
-    DeviceGuard g(device);
-    for (void* p : owned) (void)hipFree(p);
-    if (wpart) (void)hipFree(wpart);   // (made by the first step, regrown by tmd::wg_launch)
-    if (tiny_host) (void)hipHostFree(tiny_host);
-    free_acts();
-  }
+  rced_trainer();    // (both below TrainPass: `pending` needs the complete type)
+  ~rced_trainer();
 };
 
 namespace {
@@ -166,343 +153,13 @@ int launch_conv(const float* x, float* y, const float* w, const float* shift, co
 }
 
 int reduce_channels(rced_trainer* t, const float* a, const float* b, const float* mu, const float* rstd, size_t P, int C,
-                    hipStream_t st) {
+                    double* sums, hipStream_t st) {
   hipLaunchKernelGGL(train::chan_reduce, dim3(kReduceGrid), dim3(train::kThreads), 0, st, a, b, mu, rstd, P, C, t->part);
-  hipLaunchKernelGGL(train::reduce_finish, dim3(2 * C), dim3(train::kThreads), 0, st, (const double*)t->part, kReduceGrid, C, t->sums);
+  hipLaunchKernelGGL(train::reduce_finish, dim3(2 * C), dim3(train::kThreads), 0, st, (const double*)t->part, kReduceGrid, C, sums);
   HIP_TRY(hipGetLastError());
   return RCED_OK;
 }
 
-// ---- MFMA paths for the 1xk layers (kernels_train_mfma.h, launchers in train_mfma_dispatch.h) ----
-// the shapes of CR-CED V3 and R-CED V1 (RCED_TM_FWD / RCED_TM_BWD, train_shapes.h); R-CED V2 lives in train_mfma_v2.hip
-RCED_TM_DEFINE_DISPATCH(_main, RCED_TM_FWD, RCED_TM_BWD)
-}  // namespace
-// train_mfma_v2.hip
-int rced_tm_conv_v2(bool fwd, int cin, int taps, int cout, bool accum, bool stats, const float* in, const float* packet,
-                    float* out, int frames, int cus, double* part, const rced::tmm::XformArgs* xa,
-                    const rced::tmm::BnBwdArgs* ba, hipStream_t st, const rced::tmm::SumArgs* sa, const float* acc_from);
-int rced_tm_wgrad_v2(const rced::tmd::WgDet& wd, int cin, int taps, int cout, const float* x, const float* dz, float* dW, float* dbias, int frames, int cus,
-                     const rced::tmm::XformArgs* xa, const rced::tmm::BnBwdArgs* ba, hipStream_t st);
-namespace {
-// Returns the grid size (= number of partial-sum records when stats), 0 if no kernel was built for the request.
-int tm_conv(bool fwd, int cin, int taps, int cout, bool accum, bool stats, const float* in, const float* packet, float* out,
-            int frames, int cus, double* part, const tmm::XformArgs* xa, const tmm::BnBwdArgs* ba, hipStream_t st,
-            const tmm::SumArgs* sa = nullptr, const float* acc_from = nullptr) {
-  if (rced::tms::tm_has_main(fwd, cin, taps, cout))
-    return tm_conv_main(fwd, cin, taps, cout, accum, stats, in, packet, out, frames, cus, part, xa, ba, st, sa, acc_from);
-  return rced_tm_conv_v2(fwd, cin, taps, cout, accum, stats, in, packet, out, frames, cus, part, xa, ba, st, sa, acc_from);
-}
-int tm_wgrad(const WgDet& wd, int cin, int taps, int cout, const float* x, const float* dz, float* dW, float* dbias, int frames, int cus,
-             const tmm::XformArgs* xa, const tmm::BnBwdArgs* ba, hipStream_t st) {
-  if (rced::tms::tm_has_main(true, cin, taps, cout)) return tm_wgrad_main(wd, cin, taps, cout, x, dz, dW, dbias, frames, cus, xa, ba, st);
-  return rced_tm_wgrad_v2(wd, cin, taps, cout, x, dz, dW, dbias, frames, cus, xa, ba, st);
-}
-
-// ---- wgrad + dgrad of a layer in one kernel (tmm::bwd_fused_mfma): RCED_TM_FUSED ----
-// (x virtual, sums) must be (1, 1) or (0, 0).  Returns the grid size, 0 if no kernel was built for the request.
-int tm_bwd_fused(const WgDet& wd, int cin, int taps, int cout, bool xf_sums, const float* x, const float* du, const float* packet, float* dx,
-                 float* dW, float* dbias, int frames, int cus, double* part, const tmm::XformArgs* xa, const tmm::BnBwdArgs* ba,
-                 hipStream_t st) {
-  const tmm::XformArgs nx{nullptr, nullptr, nullptr, nullptr};
-  if (!ba || (xf_sums && !xa)) return 0;
-#define X(CI, TP, CO)                                                                                                          \
-  if (cin == CI && taps == TP && cout == CO)                                                                                   \
-    return xf_sums ? rced::tmd::tm_bwd_fused_launch<CI, TP, CO, true, true>(wd, x, du, packet, dx, dW, dbias, frames, cus, part, *xa, *ba, st) \
-                   : rced::tmd::tm_bwd_fused_launch<CI, TP, CO, false, false>(wd, x, du, packet, dx, dW, dbias, frames, cus, part, nx, *ba, st);
-  RCED_TM_FUSED(X)
-#undef X
-  return 0;
-}
-
-// ---- first layer (8 x kw on the 1-channel input, RCED_FIRST): MFMA forward and wgrad (kernels_train_mfma.h) ----
-template <int KW, int COUT>
-int first_wgrad_launch(const WgDet& wd, const float* x, const float* dz, float* dW, float* dbias, int frames, int T, int cus,
-                       const tmm::BnBwdArgs* ba, hipStream_t st) {
-  constexpr int RS = 129 + KW - 1;
-  const size_t lds = (((size_t)(tmm::kTF * 8 * RS + 32 + 3) / 4) * 4 + (size_t)(tmm::kTF * tmm::first_wgrad_fs(KW, COUT) + 4) * 32 + 4 * COUT) * sizeof(float);
-  const int ntiles = (frames + tmm::kTF - 1) / tmm::kTF;
-  const tmm::BnBwdArgs nb{nullptr, nullptr, nullptr, nullptr, nullptr, 1.0, nullptr};
-  static unsigned long long attr_t = 0, attr_f = 0;
-  static int occ_t = 0, occ_f = 0;
-  allow_lds(reinterpret_cast<const void*>(tmm::first_wgrad<KW, COUT, true>), lds, attr_t);
-  allow_lds(reinterpret_cast<const void*>(tmm::first_wgrad<KW, COUT, false>), lds, attr_f);
-  // persistent grid = what is resident (it was cus * 3 with two workgroups per CU resident: half of the second round idle)
-  const dim3 grid(std::min(ntiles, ba ? rced::tmd::resident_grid(reinterpret_cast<const void*>(tmm::first_wgrad<KW, COUT, true>), lds, cus, occ_t)
-                                      : rced::tmd::resident_grid(reinterpret_cast<const void*>(tmm::first_wgrad<KW, COUT, false>), lds, cus, occ_f)));
-  rced::tmd::wg_launch(wd, [&](float* dw, float* db, unsigned ps) {
-    if (ba) hipLaunchKernelGGL((tmm::first_wgrad<KW, COUT, true>), grid, dim3(tmm::kThreads), lds, st, x, dz, dw, db, frames, T, *ba, ps);
-    else hipLaunchKernelGGL((tmm::first_wgrad<KW, COUT, false>), grid, dim3(tmm::kThreads), lds, st, x, dz, dw, db, frames, T, nb, ps);
-  }, (int)grid.x * tmm::kWaves, 8 * KW * COUT, COUT, dW, dbias, st);
-  return 1;
-}
-int first_wgrad(const WgDet& wd, const LayerSpec& s, const float* x, const float* dz, float* dW, float* dbias, int frames, int T, int cus,
-                const tmm::BnBwdArgs* ba, hipStream_t st) {
-#define X(KW, CO) if (s.kw == KW && s.cout == CO) return first_wgrad_launch<KW, CO>(wd, x, dz, dW, dbias, frames, T, cus, ba, st);
-  RCED_FIRST(X)
-#undef X
-  return 0;
-}
-
-template <int KW, int COUT>
-int first_fwd_launch(const float* x, const float* w, const float* bias, float* packet, float* z, int frames, int T, int cus,
-                     bool stats, double* part, hipStream_t st) {
-  constexpr int MT = tmm::tm_rem(COUT) ? 1 : (COUT + 15) / 16, data = 2 * KW * MT * 64 + (tmm::tm_rem(COUT) ? 32 * 64 : 0), RS = 129 + KW - 1;
-  hipLaunchKernelGGL(tmm::pack_first, dim3((data + 32 + 255) / 256), dim3(256), 0, st, w, bias, KW, COUT, packet);
-  const size_t lds = (((size_t)(tmm::kTF * 8 * RS + 32 + 3) / 4) * 4 + data + 32) * sizeof(float);
-  const int ntiles = (frames + tmm::kTF - 1) / tmm::kTF;
-  static int occ_s = 0, occ_n = 0;
-  const int res = stats ? rced::tmd::resident_grid(reinterpret_cast<const void*>(tmm::first_fwd<KW, COUT, true>), lds, cus, occ_s)
-                        : rced::tmd::resident_grid(reinterpret_cast<const void*>(tmm::first_fwd<KW, COUT, false>), lds, cus, occ_n);
-  const int grid = std::min(ntiles, std::min(res, kPairGrid));
-  if (stats) hipLaunchKernelGGL((tmm::first_fwd<KW, COUT, true>), dim3(grid), dim3(tmm::kThreads), lds, st, x, (const float*)packet, z, frames, T, part);
-  else hipLaunchKernelGGL((tmm::first_fwd<KW, COUT, false>), dim3(grid), dim3(tmm::kThreads), lds, st, x, (const float*)packet, z, frames, T, part);
-  return grid;
-}
-// returns the grid size (= partial-sum records when stats)
-int first_fwd(const LayerSpec& s, const float* x, const float* w, const float* bias, float* packet, float* z, int frames, int T,
-              int cus, bool stats, double* part, hipStream_t st) {
-#define X(KW, CO) if (s.kw == KW && s.cout == CO) return first_fwd_launch<KW, CO>(x, w, bias, packet, z, frames, T, cus, stats, part, st);
-  RCED_FIRST(X)
-#undef X
-  return 0;
-}
-size_t first_packet_floats(const LayerSpec& s) {   // pack_first: main section, the 18-channel form's remainder section, 32 shifts
-  return (size_t)2 * s.kw * (tmm::tm_rem(s.cout) ? 1 : (s.cout + 15) / 16) * 64 + (tmm::tm_rem(s.cout) ? 32 * 64 : 0) + 32;
-}
-
-// ---- output layer (1x129, CH -> 1, RCED_FIN_CH): Toeplitz forward + MFMA wgrad (kernels_train_mfma.h) ----
-size_t fin_pack_floats(int ch) {
-#define X(CH) if (ch == CH) return tmm::FinGeo<CH>::kPack;
-  RCED_FIN_CH(X)
-#undef X
-  return 0;
-}
-// floats of the buffer that holds the output layer's packed A: the fp32 form, or the three-part bf16 form (kernels_final_x6.h)
-size_t fin_pack_alloc_floats(int ch) {
-  const size_t x6 = ((size_t)((129 * ch + 31) / 32) * 9 * 3 * 64 * 8 * sizeof(unsigned short) + 3) / 4;
-  return std::max(fin_pack_floats(ch), x6);
-}
-int fin_forward(int ch, const float* h, const float* w, const float* bias, float* pack, float* y, int frames, hipStream_t st,
-                bool use_x6) {
-  if (use_x6) {
-    // fp32 quality on the bf16 matrix pipe: every operand as three bf16 parts, six MFMAs of K = 32 per product
-    const int total6 = ((129 * ch + 31) / 32) * 9 * 64 * 8;
-    hipLaunchKernelGGL(x6::pack_final_x6_dev, dim3((total6 + 255) / 256), dim3(256), 0, st, w, ch, reinterpret_cast<unsigned short*>(pack));
-    const dim3 grid6((frames + chain::kFinFrames - 1) / chain::kFinFrames);
-#define X(CH)                                                                                                                      \
-  if (ch == CH)                                                                                                                    \
-    hipLaunchKernelGGL((x6::final_gemm_x6_kernel<CH>), grid6, dim3(chain::kFinThreads), 0, st, h,                                  \
-                       (const unsigned short*)reinterpret_cast<unsigned short*>(pack), 0.f, y, frames, bias);
-    RCED_FIN_CH(X)
-#undef X
-    return 1;
-  }
-  const int total = (int)fin_pack_floats(ch);
-  hipLaunchKernelGGL(tmm::pack_final_fwd, dim3((total + 255) / 256), dim3(256), 0, st, w, ch, pack);
-  const dim3 grid((frames + tmm::kFinFrames - 1) / tmm::kFinFrames);
-  // the inference path's output-layer GEMM with its B operand staged through LDS (kernels_fused_chain.h: 0.54 -> 0.41 ms at
-  // config 5's size against tmm::final_fwd's strided global reads); same packed A fragments, the bias read on the device
-#define X(CH)                                                                                                               \
-  if (ch == CH) {                                                                                                           \
-    static_assert(tmm::FinGeo<CH>::kPack == chain::FinalGeo<CH>::kPack && tmm::kFinFrames == chain::kFinFrames, "one pack");   \
-    hipLaunchKernelGGL((chain::final_gemm_lds_kernel<CH>), grid, dim3(chain::kFinThreads), 0, st, h, (const float*)pack, 0.f,  \
-                       y, frames, bias);                                                                                    \
-  }
-  RCED_FIN_CH(X)
-#undef X
-  return 1;
-}
-size_t fin_dgrad_pack_floats(int ch) {   // the fp32 pack, or the three-part bf16 pack of x6::final_dgrad_x6_kernel
-  const size_t mt = (size_t)((129 * ch + 15) / 16);
-  return std::max(mt * tmm::kDgSteps * 64, (mt * x6::kDgX6Steps * 3 * 64 * 8 * sizeof(unsigned short) + 3) / 4);
-}
-int fin_dgrad(int ch, const float* dz, const float* w, float* pack, float* dx, int frames, hipStream_t st, bool use_x6) {
-  if (use_x6) {
-    const int total6 = ((129 * ch + 15) / 16) * x6::kDgX6Steps * 64 * 8;
-    hipLaunchKernelGGL(x6::pack_dgrad_x6_dev, dim3((total6 + 255) / 256), dim3(256), 0, st, w, ch, reinterpret_cast<unsigned short*>(pack));
-    const dim3 grid6((frames + x6::kDgX6Frames - 1) / x6::kDgX6Frames);
-#define X(CH) \
-  if (ch == CH) hipLaunchKernelGGL((x6::final_dgrad_x6_kernel<CH>), grid6, dim3(x6::kDgX6Threads), 0, st, dz, (const unsigned short*)reinterpret_cast<unsigned short*>(pack), dx, frames);
-    RCED_FIN_CH(X)
-#undef X
-    return 1;
-  }
-  const int total = (int)(((129 * ch + 15) / 16) * tmm::kDgSteps * 64);
-  hipLaunchKernelGGL(tmm::pack_final_dgrad, dim3((total + 255) / 256), dim3(256), 0, st, w, ch, pack);
-  const dim3 grid((frames + tmm::kDgFrames - 1) / tmm::kDgFrames);
-#define X(CH) \
-  if (ch == CH) hipLaunchKernelGGL((tmm::final_dgrad<CH>), grid, dim3(tmm::kThreads), 0, st, dz, (const float*)pack, dx, frames);
-  RCED_FIN_CH(X)
-#undef X
-  return 1;
-}
-int fin_wgrad(const WgDet& wd, int ch, const float* x, const float* dz, float* dW, float* dbias, int frames, int cus, hipStream_t st) {
-  const dim3 grid(std::min((frames + tmm::kWaves - 1) / tmm::kWaves, cus * 2));
-#define X(CH)                                                                                                              \
-  if (ch == CH)                                                                                                            \
-    rced::tmd::wg_launch(wd, [&](float* dw, float* db, unsigned ps) {                                                      \
-      hipLaunchKernelGGL((tmm::final_wgrad<CH>), grid, dim3(tmm::kThreads), 0, st, x, dz, dw, db, frames, ps);             \
-    }, (int)grid.x, 129 * CH, 1, dW, dbias, st);
-  RCED_FIN_CH(X)
-#undef X
-  return 1;
-}
-
-// kFinX below: the fused backward kernel leaves (sum d_u, sum d_u * x), x = relu(a z + b); where d_u != 0, z = (x - b) / a.
-// That division is exact enough only while |gamma| is not tiny (x was rounded to fp32: zhat comes back with an error of
-// eps |x| / |gamma|), and meaningless for gamma = 0 -- where S2 is still needed: it is gamma's own gradient, and TF's
-// d gamma = sum dy * zhat does not vanish with gamma.  So that mode also raises *redo when any channel of the layer has
-// |gamma| < kTinyGamma, and the step recomputes such a layer's sums exactly from (g, z) with bwd_route2 (tiny_gamma_scan).
-constexpr float kTinyGamma = 1e-3f;
-
-__global__ void sums_to_float(const double* __restrict__ sums, int C, int which, float* __restrict__ dst) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c < C) dst[c] = (float)sums[2 * c + which];
-}
-
-// ONE launch for what used to be three to five (reduce_finish over 2 C workgroups, then a fix-up of S2 or
-// bn_stats_finish, then two sums_to_float): a CR-CED step issued ~150 of these 5-us kernels, all on the critical path.
-// One workgroup of 1024 threads: thread (i, p) adds records p, p + 16, ... of value i < 2 C, the 16 partial sums are added
-// in order (the same bits every run), then threads c < C finish the layer:
-//   kFinPlain  sums = (S1, S2) as they are                      (bwd_route2's records)
-//   kFinZ      S2 = rstd (sum d_u z - mu S1)                    (a SUMS dgrad's records)
-//   kFinX      S2 from sum d_u x, *redo on tiny gamma           (the fused backward kernel's records)
-//   kFinStats  (sum z, sum z^2) -> mu, rstd, moving statistics  (forward: bn_stats_finish)
-// kFinPlain / Z / X also write d beta = S1 and d gamma = S2 (g_beta / g_gamma).  only_if: a device flag, no-op when zero.
-// Over ONE record the reduction is 0.0 + v = v: finishing a layer from an exchange buffer that holds the reduced sums gives
-// the bits of finishing it from the records (the synchronised step, TrainPass::point_finish).
-enum { kFinPlain = 0, kFinZ = 1, kFinX = 2, kFinStats = 3 };
-struct FinishArgs {
-  const float *mu, *rstd, *gamma, *beta;      // kFinZ / kFinX
-  float *g_beta, *g_gamma;                    // backward modes (may be null)
-  int* redo;                                  // kFinX
-  double P; float eps, momentum;              // kFinStats
-  float *mu_out, *rstd_out, *moving_mean, *moving_var;
-  double* raw_out;                            // every mode (may be null): the reduced (S1, S2) as the records gave them
-};
-__global__ __launch_bounds__(1024) void bn_finish(const double* __restrict__ part, int nparts, int C, double* __restrict__ sums,
-                                                  int mode, FinishArgs a, const int* __restrict__ only_if) {
-  if (only_if && *only_if == 0) return;
-  __shared__ double red[16][64];
-  const int i = threadIdx.x & 63, p = threadIdx.x >> 6, n = 2 * C;
-  double t = 0.0;
-  if (i < n) {
-    // four independent chains (records p, p+16, p+32, p+48 of every 64), added in a fixed order: the loads of one
-    // chain were a serial ~100 ns each, 128 of them for bwd_route2's 2048 records (14 us per launch, 40 launches)
-    double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
-    int k = p;
-    for (; k + 48 < nparts; k += 64) {
-      const double a0 = part[(size_t)k * n + i], a1 = part[(size_t)(k + 16) * n + i];
-      const double a2 = part[(size_t)(k + 32) * n + i], a3 = part[(size_t)(k + 48) * n + i];
-      t0 += a0; t1 += a1; t2 += a2; t3 += a3;
-    }
-    for (; k < nparts; k += 16) t0 += part[(size_t)k * n + i];
-    t = (t0 + t1) + (t2 + t3);
-  }
-  red[p][i] = t;
-  __syncthreads();
-  if (p == 0 && i < n) {
-    double v = red[0][i];
-#pragma unroll
-    for (int q = 1; q < 16; ++q) v += red[q][i];
-    red[0][i] = v;
-  }
-  __syncthreads();
-  const int c = threadIdx.x;
-  bool tiny = false;
-  if (c < C) {
-    const double s1 = red[0][2 * c];
-    double s2 = red[0][2 * c + 1];
-    if (a.raw_out) {   // (the synchronised step's exchange buffer: what the shards add up before the layer is finished)
-      a.raw_out[2 * c] = s1;
-      a.raw_out[2 * c + 1] = s2;
-    }
-    if (mode == kFinStats) {
-      const double m = s1 / a.P;
-      double var = s2 / a.P - m * m;
-      if (var < 0.0) var = 0.0;
-      a.mu_out[c] = (float)m;
-      a.rstd_out[c] = (float)(1.0 / sqrt(var + (double)a.eps));
-      const double unbiased = a.P > 1.0 ? var * a.P / (a.P - 1.0) : var;
-      a.moving_mean[c] = (float)((double)a.momentum * (double)a.moving_mean[c] + (1.0 - (double)a.momentum) * m);
-      a.moving_var[c] = (float)((double)a.momentum * (double)a.moving_var[c] + (1.0 - (double)a.momentum) * unbiased);
-    } else {
-      if (mode == kFinZ) {
-        s2 = (double)a.rstd[c] * (s2 - (double)a.mu[c] * s1);
-      } else if (mode == kFinX) {
-        const float ga = a.gamma[c] * a.rstd[c];                 // the folded forward, exactly as xform_table_fill forms it
-        const float gb = a.beta[c] - ga * a.mu[c];
-        tiny = !(fabsf(a.gamma[c]) >= kTinyGamma);
-        s2 = ga != 0.f ? (double)a.rstd[c] * ((s2 - (double)gb * s1) / (double)ga - (double)a.mu[c] * s1) : 0.0;
-      }
-      if (a.g_beta) a.g_beta[c] = (float)s1;
-      if (a.g_gamma) a.g_gamma[c] = (float)s2;
-    }
-    sums[2 * c] = s1;
-    sums[2 * c + 1] = s2;
-  }
-  if (mode == kFinX) {
-    const int any = __syncthreads_or(tiny);
-    if (threadIdx.x == 0) *a.redo = any;
-  }
-}
-
-// One workgroup per layer: does any channel of the layer have |gamma| < kTinyGamma?  (the fused backward kernel's sums
-// cannot be trusted there: see kTinyGamma.)  Launched behind every Adam step into host-mapped memory, so that the NEXT
-// step knows on the host which layers need the exact recomputation -- instead of launching a conditional bwd_route2 +
-// finish pair for every plain layer in every step (20 no-op launches per CR-CED step).
-struct TinyScanArgs { int gamma_off[kMaxLayers]; int cout[kMaxLayers]; };
-__global__ void tiny_gamma_scan(const float* __restrict__ params, TinyScanArgs a, int* __restrict__ flags) {
-  const int l = blockIdx.x, c = threadIdx.x;
-  const bool tiny = a.gamma_off[l] >= 0 && c < a.cout[l] && !(fabsf(params[a.gamma_off[l] + c]) >= kTinyGamma);
-  const int any = __syncthreads_or(tiny);
-  if (c == 0) flags[l] = any;
-}
-
-// ---- the sharded step: one shard's gradient and statistics sums out into the caller's exchange buffers, and back ----
-// One element per thread with its own read-modify-write (no atomics): the sum over shards is formed in call order.
-constexpr int kShardThreads = 128;   // >= 2 * kMaxC + 1 entries of a layer
-static_assert(2 * train::kMaxC + 1 <= kShardThreads, "one thread per statistics entry of a layer");
-
-// g[e] (+)= grads[x2i[e]]: the internal (even-padded) gradient in the reference's blob order
-__global__ void shard_grad_out(const float* __restrict__ grads, const int* __restrict__ x2i, size_t n, float* __restrict__ g,
-                               int accumulate) {
-  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n) return;
-  const float v = grads[x2i[e]];
-  g[e] = accumulate ? g[e] + v : v;
-}
-// one workgroup per layer: s[soff + i] (+)= the layer's stashed (S1, S2) entry i < 2 xcout, the pixel count behind them
-__global__ void shard_stats_out(const double* __restrict__ stash, ShardArgs a, double P, double* __restrict__ s, int accumulate) {
-  const int l = blockIdx.x, i = threadIdx.x;
-  if (a.soff[l] < 0 || i > 2 * a.xcout[l]) return;
-  const double v = i < 2 * a.xcout[l] ? stash[(size_t)l * 2 * train::kMaxC + i] : P;
-  double* d = s + a.soff[l] + i;
-  *d = accumulate ? *d + v : v;
-}
-// grads[x2i[e]] = g[e] (phantom entries were zeroed before)
-__global__ void shard_grad_in(const float* __restrict__ g, const int* __restrict__ x2i, size_t n, float* __restrict__ grads) {
-  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < n) grads[x2i[e]] = g[e];
-}
-// one workgroup per layer, one thread per channel: the moving statistics from the summed (S1, S2, P), by bn_finish's
-// kFinStats expressions.  A phantom channel has z = 0 everywhere: S1 = S2 = 0, as the unsharded step sees it.
-__global__ void shard_moving_update(const double* __restrict__ s, ShardArgs a, float momentum, float* __restrict__ params) {
-  const int l = blockIdx.x, c = threadIdx.x;
-  if (a.soff[l] < 0 || c >= a.cout[l]) return;
-  const double* sl = s + a.soff[l];
-  const bool real = c < a.xcout[l];
-  const double P = sl[2 * a.xcout[l]];
-  const double s1 = real ? sl[2 * c] : 0.0, s2 = real ? sl[2 * c + 1] : 0.0;
-  float* moving_mean = params + a.mmean[l];
-  float* moving_var = params + a.mvar[l];
-  const double m = s1 / P;
-  double var = s2 / P - m * m;
-  if (var < 0.0) var = 0.0;
-  const double unbiased = P > 1.0 ? var * P / (P - 1.0) : var;
-  moving_mean[c] = (float)((double)momentum * (double)moving_mean[c] + (1.0 - (double)momentum) * m);
-  moving_var[c] = (float)((double)momentum * (double)moving_var[c] + (1.0 - (double)momentum) * unbiased);
-}
 }  // namespace
 
 extern "C" {
@@ -514,9 +171,8 @@ int rced_train_create(int variant, const float* blob, size_t n_floats, int batch
   if (!net) return rced_fail(RCED_ERR_ARG, "unknown variant %d", variant);
   if (!blob || n_floats != net_num_weights(*net)) return rced_fail(RCED_ERR_ARG, "blob must hold %zu floats", net_num_weights(*net));
   if (batch_size <= 0) return rced_fail(RCED_ERR_ARG, "batch_size must be positive");
-  if (int rc = check_device(device)) return rc;
-  DeviceGuard g(device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  OnDevice on(device);
+  if (on.rc) return on.rc;
   std::unique_ptr<rced_trainer> owner(new rced_trainer());   // deleted on every early return below
   rced_trainer* t = owner.get();
   t->variant = variant;
@@ -619,17 +275,17 @@ int rced_train_create(int variant, const float* blob, size_t n_floats, int batch
   HIP_TRY(t->alloc(&t->zero32, 64 * sizeof(float)));
   HIP_TRY(hipMemset(t->zero32, 0, 64 * sizeof(float)));
   HIP_TRY(t->alloc(&t->part, (size_t)std::max(kReduceGrid, kPairGrid) * train::kMaxC * 2 * sizeof(double)));
-  HIP_TRY(t->alloc(&t->sums, (train::kMaxC * 2 + 2) * sizeof(double)));
-  t->redo = reinterpret_cast<int*>(t->sums + train::kMaxC * 2);
-  HIP_TRY(hipMemset(t->redo, 0, 2 * sizeof(double)));
-  // the sharded step's exchange layout: the reference's blob order for the gradient, (S1, S2)[xcout] + P per BatchNorm layer
+  HIP_TRY(t->alloc(&t->sums, train::kMaxC * 2 * sizeof(double)));
+  // the per-layer table of the kernels behind Adam and of the sharded step, whose exchange layout is the reference's blob
+  // order for the gradient and (S1, S2)[xcout] + P per BatchNorm layer
   for (int l = 0; l < kMaxLayers; ++l) {
     const bool bn = l < L && xnet->layer[l].use_norm;
-    t->shard.soff[l] = bn ? (int)t->xstats : -1;
-    t->shard.xcout[l] = bn ? xnet->layer[l].cout : 0;
-    t->shard.cout[l] = bn ? net->layer[l].cout : 0;
-    t->shard.mmean[l] = bn ? (int)t->off[l].mmean : 0;
-    t->shard.mvar[l] = bn ? (int)t->off[l].mvar : 0;
+    t->tab.gamma[l] = bn ? (int)t->off[l].gamma : 0;
+    t->tab.mmean[l] = bn ? (int)t->off[l].mmean : 0;
+    t->tab.mvar[l] = bn ? (int)t->off[l].mvar : 0;
+    t->tab.cout[l] = bn ? net->layer[l].cout : 0;
+    t->tab.xcout[l] = bn ? xnet->layer[l].cout : 0;
+    t->tab.soff[l] = bn ? (int)t->xstats : -1;
     if (bn) t->xstats += 2 * (size_t)xnet->layer[l].cout + 1;
   }
   HIP_TRY(t->alloc(&t->x2i_dev, t->xvars * sizeof(int)));
@@ -674,11 +330,32 @@ void rced_train_destroy(rced_trainer* t) { delete t; }
 long long rced_train_global_step(rced_trainer* t) { return t ? t->global_step : -1; }
 
 namespace {
-// Between rced_train_sync_begin and rced_train_sync_end / _abort the handle's buffers belong to the open pass.
+// What an entry point does first: `Enter in(t, "rced_train_..."); if (in.rc) return in.rc;`.  The trainer is not null; no
+// synchronised pass is pending on it (between rced_train_sync_begin and rced_train_sync_end / _abort the handle's buffers
+// belong to the open pass); its device is current until the scope ends.  rc0: an earlier refusal, handed on as it is.
 int refuse_pending(const rced_trainer* t, const char* what) {
   if (!t->pending) return RCED_OK;
   return rced_fail(RCED_ERR_STATE, "%s: a synchronised pass is pending on this trainer (rced_train_sync_begin without "
                                    "rced_train_sync_end or rced_train_sync_abort)", what);
+}
+struct Enter {
+  int rc;
+  DeviceGuard g;
+  Enter(const rced_trainer* t, const char* what, int rc0 = RCED_OK) : rc(rc0) {
+    if (!rc && !t) rc = rced_fail(RCED_ERR_ARG, "trainer is NULL");
+    if (!rc) rc = refuse_pending(t, what);
+    if (rc) return;
+    g.enter(t->device);
+    if (!g.ok) rc = rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", t->device);
+  }
+};
+// ... and in front of it where a batch comes in: x [N, T, 129, 1] and its second tensor (the target; rced_train_forward: where
+// the prediction goes), decided before the handle is looked into
+int check_batch(const rced_trainer* t, const float* x_dev, const float* second, int N, int T) {
+  if (!t) return rced_fail(RCED_ERR_ARG, "trainer is NULL");
+  if (N <= 0 || T <= 0) return rced_fail(RCED_ERR_ARG, "a shard must have N >= 1 and T >= 1 (got %d x %d)", N, T);
+  if (!x_dev || !second) return rced_fail(RCED_ERR_ARG, "input or target is NULL");
+  return RCED_OK;
 }
 
 // internal (even-padded) device array -> the reference's layout on the host, and back (phantom entries become 0)
@@ -698,22 +375,22 @@ int upload_external(rced_trainer* t, const float* host, float* dev) {
 
 int rced_train_get_variables(rced_trainer* t, float* blob_host, size_t n_floats) {
   if (!t || !blob_host || n_floats != t->xvars) return rced_fail(RCED_ERR_ARG, "bad arguments");
-  if (int rc = refuse_pending(t, "rced_train_get_variables")) return rc;
-  DeviceGuard g(t->device);
+  Enter in(t, "rced_train_get_variables");
+  if (in.rc) return in.rc;
   return download_external(t, t->params, blob_host);
 }
 
 int rced_train_get_gradients(rced_trainer* t, float* blob_host, size_t n_floats) {
   if (!t || !blob_host || n_floats != t->xvars) return rced_fail(RCED_ERR_ARG, "bad arguments");
-  if (int rc = refuse_pending(t, "rced_train_get_gradients")) return rc;
-  DeviceGuard g(t->device);
+  Enter in(t, "rced_train_get_gradients");
+  if (in.rc) return in.rc;
   return download_external(t, t->grads, blob_host);
 }
 
 int rced_train_get_state(rced_trainer* t, float* m_blob_host, float* v_blob_host, size_t n_floats, long long* global_step) {
   if (!t || !m_blob_host || !v_blob_host || n_floats != t->xvars) return rced_fail(RCED_ERR_ARG, "bad arguments");
-  if (int rc = refuse_pending(t, "rced_train_get_state")) return rc;
-  DeviceGuard g(t->device);
+  Enter in(t, "rced_train_get_state");
+  if (in.rc) return in.rc;
   if (int rc = download_external(t, t->m, m_blob_host)) return rc;
   if (int rc = download_external(t, t->v, v_blob_host)) return rc;
   if (global_step) *global_step = t->global_step;
@@ -724,8 +401,8 @@ int rced_train_set_state(rced_trainer* t, const float* m_blob_host, const float*
                          long long global_step) {
   if (!t || !m_blob_host || !v_blob_host || n_floats != t->xvars || global_step < 0)
     return rced_fail(RCED_ERR_ARG, "bad arguments");
-  if (int rc = refuse_pending(t, "rced_train_set_state")) return rc;
-  DeviceGuard g(t->device);
+  Enter in(t, "rced_train_set_state");
+  if (in.rc) return in.rc;
   if (int rc = upload_external(t, m_blob_host, t->m)) return rc;
   if (int rc = upload_external(t, v_blob_host, t->v)) return rc;
   t->global_step = global_step;
@@ -735,33 +412,31 @@ int rced_train_set_state(rced_trainer* t, const float* m_blob_host, const float*
 }  // extern "C"
 
 namespace {
-// Adam (TF form, trainer.py:175-179) from t->grads, global_step += 1, and the tiny-gamma scan behind it.
+// Adam (TF form, trainer.py:175-179) from t->grads, global_step += 1, and behind it the per-layer epilogue: the moving
+// statistics from s -- the stash of this step's forward over P pixels, or (P = 0) an exchange buffer, which carries its
+// own pixel counts -- and the tiny-gamma scan.
 // global_step: the reference fetches it in the same sess.run as train_op (trainer.py:186-191); TF1 orders a read and an
 // assign_add in one run only through control dependencies, and slim.learning.create_train_op makes train_op =
 // (increment global_step, then return the loss), so the fetched value is unordered against the increment in principle.
 // This library returns the POST-increment value, deterministically: after the first step train_step returns 1 and
 // the loop's next learning rate is noam(1) (trainer.py:215, step = global_step + 1 = 2).  See DESIGN.md 3.5.
-void adam_and_scan(rced_trainer* t, float lr, hipStream_t st) {
-  const NetSpec& net = *t->net;
-  const int L = net.n_layers;
+void optimizer_step(rced_trainer* t, float lr, const double* s, double P, hipStream_t st) {
   t->global_step += 1;
   const double tt = (double)t->global_step;
   const float lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow((double)kAdamB2, tt)) / (1.0 - std::pow((double)kAdamB1, tt)));
   hipLaunchKernelGGL(train::adam_step, dim3((unsigned)((t->nvars + train::kThreads - 1) / train::kThreads)),
                      dim3(train::kThreads), 0, st, t->params, (const float*)t->grads, t->m, t->v,
                      (const unsigned char*)t->trainable, t->nvars, lr_t, kAdamB1, kAdamB2, kAdamEps);
-  TinyScanArgs ta;
-  for (int l = 0; l < kMaxLayers; ++l) {
-    ta.gamma_off[l] = l < L && net.layer[l].use_norm ? (int)t->off[l].gamma : -1;
-    ta.cout[l] = l < L ? net.layer[l].cout : 0;
-  }
-  hipLaunchKernelGGL(tiny_gamma_scan, dim3(kMaxLayers), dim3(64), 0, st, (const float*)t->params, ta, t->tiny_dev);
+  hipLaunchKernelGGL(step_epilogue, dim3(kMaxLayers), dim3(64), 0, st, t->params, t->tab, s, P == 0.0 ? 1 : 0, P, kBnMomentum,
+                     t->tiny_dev);
 }
 
 // pred_dev != nullptr: forward only (rced_train_forward) -- batch-statistics BatchNorm, nothing is updated, the
 // prediction is copied to pred_dev.  g_out != nullptr: one shard of the sharded step (rced_train_grad) -- forward, loss and
 // backward as in the step, nothing is updated either; the gradient and every BatchNorm layer's (sum z, sum z^2, pixels) go
-// into (or, accumulate, are added to) g_out / s_out.  Otherwise the full step.
+// into (or, accumulate, are added to) g_out / s_out.  Otherwise the full step.  In every form the forward leaves a BatchNorm
+// layer's (sum z, sum z^2) in t->stash and touches no variable: the moving statistics are written behind Adam, from the
+// stash (the step) or from the exchange buffer (rced_train_apply), so a pass that fails leaves the trainer as it was.
 //
 // The pass is a TrainPass: begin() packs the weights, advance() walks the forward and the backward loop, end() hands the
 // result out.  Every bn_finish call site of the two loops is an EXCHANGE POINT, described by a FinishPoint.  The straight
@@ -785,7 +460,6 @@ struct TrainPass {
   const float lr;
   const hipStream_t st;
   const bool forward_only, shard;
-  const float momentum;        // momentum 1: the moving statistics stay as they are
   const NetSpec& net;
   const plan::TrainPlan& plan;   // which launcher runs where, and who stores / accumulates / zeroes what: train_plan.h
   const int L, F, frames;
@@ -800,12 +474,11 @@ struct TrainPass {
   Stage stage = Stage::Fwd;
   int layer = 0;
   FinishPoint pt{};
-  bool tiny_after = false;     // straight paths: pt (kFinX) is followed by the exact recomputation of a tiny-gamma layer
 
   TrainPass(rced_trainer* t_, const float* x, const float* y, float* pred, int N_, int T_, float lr_, void* stream, bool shard_,
             double pixels_total, double* xs_)
       : t(t_), x_dev(x), y_dev(y), pred_dev(pred), N(N_), T(T_), lr(lr_), st(static_cast<hipStream_t>(stream)),
-        forward_only(pred != nullptr), shard(shard_), momentum(pred != nullptr || shard_ ? 1.f : kBnMomentum), net(*t_->net),
+        forward_only(pred != nullptr), shard(shard_), net(*t_->net),
         plan(t_->plan), L(t_->net->n_layers), F(kFeatureDim), frames(N_ * T_), P((size_t)N_ * T_ * kFeatureDim),
         bnP(xs_ ? pixels_total : (double)((size_t)N_ * T_ * kFeatureDim)), xs(xs_) {}
 
@@ -828,11 +501,11 @@ struct TrainPass {
 
   // ---- the exchange point in its three forms
   void launch_finish(const double* part, int nparts, double* sums, int mode, const FinishArgs& fa) const {
-    hipLaunchKernelGGL(bn_finish, dim3(1), dim3(1024), 0, st, part, nparts, pt.C, sums, mode, fa, (const int*)nullptr);
+    hipLaunchKernelGGL(bn_finish, dim3(1), dim3(1024), 0, st, part, nparts, pt.C, sums, mode, fa);
   }
   void point_straight() const { launch_finish(t->part, pt.nparts, pt.sums, pt.mode, pt.fa); }
-  // The records reduced in bn_finish's order, raw, into xs.  Forward: also into the layer's stash, which rced_train_apply's
-  // moving-statistics exchange reads (this shard's own sums, as in the per-shard mode).  Backward: d beta and d gamma of THIS
+  // The records reduced in bn_finish's order, raw, into xs.  Forward: also into the layer's stash (pt.sums), which
+  // rced_train_apply's moving statistics come from (this shard's own sums, as in the per-shard mode).  Backward: d beta and d gamma of THIS
   // shard -- the mode's expressions are linear in the raw sums once mu and rstd are those of all shards, so the usual sum
   // of the shards' gradients makes them the batch's.
   void point_out() const {
@@ -840,7 +513,7 @@ struct TrainPass {
     int mode = kFinPlain;
     if (pt.mode != kFinStats) { a = pt.fa; mode = pt.mode; }
     a.raw_out = xs;
-    launch_finish(t->part, pt.nparts, pt.mode == kFinStats ? t->stash + (size_t)layer * 2 * train::kMaxC : t->sums, mode, a);
+    launch_finish(t->part, pt.nparts, pt.sums, mode, a);
   }
   // xs holds the sum over all shards: finished as ONE record (0.0 + v = v) with the pass's pixel count bnP
   void point_finish() const {
@@ -854,8 +527,8 @@ struct TrainPass {
     if (t->det && !forward_only && !t->wpart) {
       // Sized BEFORE the forward for the most any wgrad launcher can ask for: slices = workgroups (CUs x at most 4 resident per
       // CU) x 8 waves x 2 pixel parities, slice stride = the net's largest kernel + bias.  A failure to allocate is therefore
-      // reported here, before this step has touched anything; growing inside tmd::wg_launch remains as a last resort (it
-      // synchronises, and if it fails the step returns RCED_ERR_ALLOC below with the moving statistics already advanced).
+      // reported here, before this step has launched anything; growing inside tmd::wg_launch remains as a last resort (it
+      // synchronises, and if it fails the step returns RCED_ERR_ALLOC below).
       size_t maxps = 0;
       for (int l = 0; l < L; ++l) {
         const LayerSpec& s = net.layer[l];
@@ -949,22 +622,19 @@ struct TrainPass {
         break;
     }
     if (stat_parts <= 0) return no_kernel(l, "forward");
+    double* const stash = t->stash + (size_t)l * 2 * train::kMaxC;   // the layer's (S1, S2) stay here: for step_epilogue, or a shard's exchange buffer
     if (pl.stats == plan::Stats::Conv) {
       pt = FinishPoint{};
       pt.nparts = stat_parts; pt.C = s.cout; pt.mode = kFinStats;
       FinishArgs& fa = pt.fa;
-      fa.P = bnP; fa.eps = kBnEps; fa.momentum = momentum;
-      fa.mu_out = t->mu[l]; fa.rstd_out = t->rstd[l]; fa.moving_mean = t->params + f.mmean; fa.moving_var = t->params + f.mvar;
-      // (a shard keeps the layer's (S1, S2) for the exchange buffer: the kernel writes them where it is told to)
-      pt.sums = shard ? t->stash + (size_t)l * 2 * train::kMaxC : t->sums;
+      fa.P = bnP; fa.eps = kBnEps;
+      fa.mu_out = t->mu[l]; fa.rstd_out = t->rstd[l];
+      pt.sums = stash;
       *have = true;
     } else if (pl.stats == plan::Stats::Reduce) {
-      if (int rc = reduce_channels(t, t->z[l], t->z[l], nullptr, nullptr, P, s.cout, st)) return rc;
-      hipLaunchKernelGGL(train::bn_stats_finish, dim3(1), dim3(64), 0, st, (const double*)t->sums, (double)P, s.cout,
-                         kBnEps, momentum, t->mu[l], t->rstd[l], t->params + f.mmean, t->params + f.mvar);
-      if (shard)
-        HIP_TRY(hipMemcpyAsync(t->stash + (size_t)l * 2 * train::kMaxC, t->sums, 2 * (size_t)s.cout * sizeof(double),
-                               hipMemcpyDeviceToDevice, st));
+      if (int rc = reduce_channels(t, t->z[l], t->z[l], nullptr, nullptr, P, s.cout, stash, st)) return rc;
+      hipLaunchKernelGGL(train::bn_stats_finish, dim3(1), dim3(64), 0, st, (const double*)stash, (double)P, s.cout, kBnEps,
+                         t->mu[l], t->rstd[l]);
     }
     return RCED_OK;
   }
@@ -1019,7 +689,7 @@ struct TrainPass {
     hipLaunchKernelGGL(train::bwd_route2, grid, dim3(train::kThreads), 0, st, (const float2*)t->G[l + 1],
                        (const float2*)t->z[l], (const float*)(s.use_norm ? t->mu[l] : nullptr), (const float*)t->rstd[l],
                        (const float*)(t->params + f.gamma), (const float*)(t->params + f.beta), (const float2*)nullptr, s.use_act, P,
-                       s.cout, (float2*)nullptr, (float2*)nullptr, (float2*)nullptr, t->part, (const int*)nullptr);
+                       s.cout, (float2*)nullptr, (float2*)nullptr, (float2*)nullptr, t->part);
     return (int)grid.x;
   }
 
@@ -1031,12 +701,11 @@ struct TrainPass {
     const size_t n = P * s.cout;
     const float* mu = s.use_norm ? t->mu[l] : nullptr;
     *have = false;
-    tiny_after = false;
     pt = FinishPoint{};
     pt.C = s.cout; pt.sums = t->sums;
     FinishArgs& fb = pt.fa;
     fb.mu = mu; fb.rstd = t->rstd[l]; fb.gamma = t->params + f.gamma; fb.beta = t->params + f.beta;
-    fb.g_beta = t->grads + f.beta; fb.g_gamma = t->grads + f.gamma; fb.redo = t->redo;
+    fb.g_beta = t->grads + f.beta; fb.g_gamma = t->grads + f.gamma;
     float* const g_pre = s.skip_pre > 0 ? t->G[s.skip_pre] : nullptr;
     float* const g_post = s.skip_post > 0 && !pl.skip_alias ? t->G[s.skip_post] : nullptr;
     if (pl.zero_before_skip) HIP_TRY(zero_grad(plan::skip_of(s)));
@@ -1056,7 +725,7 @@ struct TrainPass {
                          (const float*)t->z[l], mu, (const float*)t->rstd[l], (const float*)(t->params + f.gamma),
                          (const float*)(t->params + f.beta), tensor(s.skip_pre), s.use_act, n, s.cout, g_pre, g_post, t->D);
       if (pl.sums == plan::Sums::RouteReduce) {
-        if (int rc = reduce_channels(t, t->D, t->z[l], mu, t->rstd[l], P, s.cout, st)) return rc;
+        if (int rc = reduce_channels(t, t->D, t->z[l], mu, t->rstd[l], P, s.cout, t->sums, st)) return rc;
         hipLaunchKernelGGL(sums_to_float, dim3(1), dim3(64), 0, st, (const double*)t->sums, s.cout, 0, t->grads + f.beta);
         hipLaunchKernelGGL(sums_to_float, dim3(1), dim3(64), 0, st, (const double*)t->sums, s.cout, 1, t->grads + f.gamma);
       }
@@ -1064,14 +733,11 @@ struct TrainPass {
       const bool from_x = pl.sums == plan::Sums::FusedX;   // (sum d_u, sum d_u * x) rather than (.., sum d_u * z)
       pt.nparts = src_parts[l]; pt.mode = from_x ? kFinX : kFinZ;
       *have = true;
-      // |gamma| tiny somewhere in this layer (known on the host since the previous step's tiny_gamma_scan, and a matter of the
-      // variables alone: every shard decides alike): the sums again, exactly, from (g, z); see kTinyGamma.  Never taken in a
-      // real training run.  The straight paths finish the kFinX point first and the exact one over it (advance); the
-      // synchronised step exchanges the exact sums alone, which replace all that the kFinX finish would have written.
-      tiny_after = from_x && tiny[l] != 0;
-      if (tiny_after && xs) {
+      // |gamma| tiny somewhere in this layer (known on the host since the previous step's step_epilogue, and a matter of the
+      // variables alone: every shard decides alike): the sums exactly, from (g, z), in place of the fused kernel's; see
+      // kTinyGamma.  Never taken in a real training run.
+      if (from_x && tiny[l] != 0) {
         pt.nparts = tiny_recompute(l); pt.mode = kFinPlain;
-        tiny_after = false;
       }
     }
     return RCED_OK;
@@ -1116,7 +782,7 @@ struct TrainPass {
         launched = fin_wgrad(wd, f.cin, tensor(s.src), dsrc, t->grads + f.kernel, t->grads + f.bias, frames, t->num_cus, st);
         break;
       case plan::Wgrad::Generic: {
-        if (int rc = reduce_channels(t, t->D, t->D, nullptr, nullptr, P, s.cout, st)) return rc;
+        if (int rc = reduce_channels(t, t->D, t->D, nullptr, nullptr, P, s.cout, t->sums, st)) return rc;
         hipLaunchKernelGGL(sums_to_float, dim3(1), dim3(64), 0, st, (const double*)t->sums, s.cout, 0, t->grads + f.bias);
         const int fpw = 16;
         const size_t lds = ((size_t)s.kh * (F + s.kw - 1) * f.cin + (size_t)F * s.cout) * sizeof(float);
@@ -1203,10 +869,6 @@ struct TrainPass {
             return RCED_OK;
           }
           if (have) point_straight();
-          if (tiny_after) {
-            pt.nparts = tiny_recompute(layer); pt.mode = kFinPlain;
-            point_straight();
-          }
           if (int rc = bwd_rest(layer--)) return rc;
           break;
         case Stage::BwdResume:
@@ -1228,16 +890,16 @@ struct TrainPass {
     if (t->wg_error) {   // (cannot happen with the up-front size above unless the runtime reports > 4 workgroups per CU)
       (void)hipStreamSynchronize(st);   // nothing of this step is left in flight behind the error
       return rced_fail(RCED_ERR_ALLOC, "deterministic weight gradients: the per-wave slice buffer could not be grown; the step was "
-                                       "abandoned before the optimizer ran%s",
-                       shard ? " and before the exchange buffers were written" : ", but the moving statistics have advanced by this batch");
+                                       "abandoned before the optimizer ran: the variables, the moving statistics%s are as they were",
+                       shard ? " and the exchange buffers" : " and the Adam slots");
     }
     if (shard) {
       hipLaunchKernelGGL(shard_grad_out, dim3((unsigned)((t->xvars + train::kThreads - 1) / train::kThreads)), dim3(train::kThreads), 0, st,
                          (const float*)t->grads, (const int*)t->x2i_dev, t->xvars, g_out, accumulate);
-      hipLaunchKernelGGL(shard_stats_out, dim3(kMaxLayers), dim3(kShardThreads), 0, st, (const double*)t->stash, t->shard, (double)P, s_out,
+      hipLaunchKernelGGL(shard_stats_out, dim3(kMaxLayers), dim3(kShardThreads), 0, st, (const double*)t->stash, t->tab, (double)P, s_out,
                          accumulate);
     } else {
-      adam_and_scan(t, lr, st);
+      optimizer_step(t, lr, t->stash, (double)P, st);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
@@ -1248,41 +910,40 @@ struct TrainPass {
   }
 };
 
-int train_run(rced_trainer* t, const float* x_dev, const float* y_dev, float* pred_dev, int N, int T, float lr,
-              double* loss_out, void* stream, float* g_out = nullptr, double* s_out = nullptr, int accumulate = 0) {
-  if (!t) return rced_fail(RCED_ERR_ARG, "trainer is NULL");
-  if (N <= 0 || T <= 0 || !x_dev || (!y_dev && !pred_dev)) return rced_fail(RCED_ERR_ARG, "bad batch");
-  if (int rc = refuse_pending(t, pred_dev ? "rced_train_forward" : g_out ? "rced_train_grad" : "rced_train_step")) return rc;
-  DeviceGuard g(t->device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", t->device);
+// args_rc: what the entry point made of its arguments (check_batch and its own)
+int train_run(rced_trainer* t, const char* what, int args_rc, const float* x_dev, const float* y_dev, float* pred_dev, int N, int T,
+              float lr, double* loss_out, void* stream, float* g_out = nullptr, double* s_out = nullptr, int accumulate = 0) {
+  Enter in(t, what, args_rc);
+  if (in.rc) return in.rc;
   TrainPass pass(t, x_dev, y_dev, pred_dev, N, T, lr, stream, g_out != nullptr, 0.0, nullptr);
   if (int rc = pass.begin()) return rc;
   if (int rc = pass.advance()) return rc;
   return pass.end(g_out, s_out, accumulate, loss_out);
 }
 
-// out[i] = ((g[0][i] + g[1][i]) + g[2][i]) + ...: the shards' rows added in shard order, one element per thread
-__global__ void sync_reduce(const double* __restrict__ g, int shards, size_t stride, int n, double* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  double v = g[i];
-  for (int s = 1; s < shards; ++s) v += g[(size_t)s * stride + i];
-  out[i] = v;
-}
 constexpr int kSyncDoubles = 2 * train::kMaxC;   // the exchange buffer of a synchronised pass: (S1, S2) of a layer's channels
 }  // namespace
+
+rced_trainer::rced_trainer() = default;
+rced_trainer::~rced_trainer() {
+  DeviceGuard g(device);
+  pending.reset();
+  for (void* p : owned) (void)hipFree(p);
+  if (wpart) (void)hipFree(wpart);   // (made by the first step, regrown by tmd::wg_launch)
+  if (tiny_host) (void)hipHostFree(tiny_host);
+  free_acts();
+}
 
 extern "C" {
 
 int rced_train_step(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, float lr, double* loss_out,
                     void* stream) {
-  if (!y_dev) return rced_fail(RCED_ERR_ARG, "bad batch");
-  return train_run(t, x_dev, y_dev, nullptr, N, T, lr, loss_out, stream);
+  return train_run(t, "rced_train_step", check_batch(t, x_dev, y_dev, N, T), x_dev, y_dev, nullptr, N, T, lr, loss_out, stream);
 }
 
 int rced_train_forward(rced_trainer* t, const float* x_dev, float* pred_dev, int N, int T, void* stream) {
-  if (!pred_dev) return rced_fail(RCED_ERR_ARG, "bad batch");
-  return train_run(t, x_dev, nullptr, pred_dev, N, T, 0.f, nullptr, stream);
+  const int rc = pred_dev ? check_batch(t, x_dev, pred_dev, N, T) : rced_fail(RCED_ERR_ARG, "the prediction buffer is NULL");
+  return train_run(t, "rced_train_forward", rc, x_dev, nullptr, pred_dev, N, T, 0.f, nullptr, stream);
 }
 
 int rced_train_exchange_size(rced_trainer* t, size_t* n_floats, size_t* n_doubles) {
@@ -1294,25 +955,21 @@ int rced_train_exchange_size(rced_trainer* t, size_t* n_floats, size_t* n_double
 
 int rced_train_grad(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, float* g_dev, double* s_dev,
                     int accumulate, double* loss_out, void* stream) {
-  if (!t) return rced_fail(RCED_ERR_ARG, "trainer is NULL");
-  if (N <= 0 || T <= 0) return rced_fail(RCED_ERR_ARG, "a shard must have N >= 1 and T >= 1 (got %d x %d)", N, T);
-  if (!x_dev || !y_dev) return rced_fail(RCED_ERR_ARG, "input or target is NULL");
-  if (!g_dev || !s_dev) return rced_fail(RCED_ERR_ARG, "an exchange buffer is NULL");
-  return train_run(t, x_dev, y_dev, nullptr, N, T, 0.f, loss_out, stream, g_dev, s_dev, accumulate != 0);
+  int rc = check_batch(t, x_dev, y_dev, N, T);
+  if (!rc && (!g_dev || !s_dev)) rc = rced_fail(RCED_ERR_ARG, "an exchange buffer is NULL");
+  return train_run(t, "rced_train_grad", rc, x_dev, y_dev, nullptr, N, T, 0.f, loss_out, stream, g_dev, s_dev, accumulate != 0);
 }
 
 int rced_train_apply(rced_trainer* t, const float* g_dev, const double* s_dev, float lr, void* stream) {
   if (!t) return rced_fail(RCED_ERR_ARG, "trainer is NULL");
   if (!g_dev || !s_dev) return rced_fail(RCED_ERR_ARG, "an exchange buffer is NULL");
-  if (int rc = refuse_pending(t, "rced_train_apply")) return rc;
-  DeviceGuard g(t->device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", t->device);
+  Enter in(t, "rced_train_apply");
+  if (in.rc) return in.rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   HIP_TRY(hipMemsetAsync(t->grads, 0, t->nvars * sizeof(float), st));
   hipLaunchKernelGGL(shard_grad_in, dim3((unsigned)((t->xvars + train::kThreads - 1) / train::kThreads)), dim3(train::kThreads), 0, st,
                      g_dev, (const int*)t->x2i_dev, t->xvars, t->grads);
-  hipLaunchKernelGGL(shard_moving_update, dim3(kMaxLayers), dim3(64), 0, st, s_dev, t->shard, kBnMomentum, t->params);
-  adam_and_scan(t, lr, st);
+  optimizer_step(t, lr, s_dev, 0.0, st);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
   return RCED_OK;
@@ -1330,28 +987,25 @@ int rced_train_sync_points(rced_trainer* t, int* n_points, size_t* n_doubles) {
 
 int rced_train_sync_begin(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, double pixels_total,
                           double* xs_dev, void* stream) {
-  if (!t) return rced_fail(RCED_ERR_ARG, "trainer is NULL");
-  if (N <= 0 || T <= 0) return rced_fail(RCED_ERR_ARG, "a shard must have N >= 1 and T >= 1 (got %d x %d)", N, T);
-  if (!x_dev || !y_dev) return rced_fail(RCED_ERR_ARG, "input or target is NULL");
+  if (int rc = check_batch(t, x_dev, y_dev, N, T)) return rc;
   if (!xs_dev) return rced_fail(RCED_ERR_ARG, "the exchange buffer is NULL");
   if (!(pixels_total >= (double)N * T * kFeatureDim))
     return rced_fail(RCED_ERR_ARG, "pixels_total = %g is less than this shard's own %g pixels", pixels_total, (double)N * T * kFeatureDim);
-  if (int rc = refuse_pending(t, "rced_train_sync_begin")) return rc;
+  Enter in(t, "rced_train_sync_begin");
+  if (in.rc) return in.rc;
   for (int l = 0; l < t->net->n_layers; ++l) {   // every BatchNorm layer's sums must pass through bn_finish: the MFMA plans
     const plan::LayerPlan& pl = t->plan.layer[l];
     if (t->net->layer[l].use_norm && (pl.stats != plan::Stats::Conv || pl.sums == plan::Sums::RouteReduce || pl.sums == plan::Sums::None))
       return rced_fail(RCED_ERR_STATE, "layer %d: the synchronised step needs the layer's sums as records (the chan_reduce forms "
                                        "under RCED_TRAIN_MFMA=0 have no exchange point)", l);
   }
-  DeviceGuard g(t->device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", t->device);
-  auto pass = std::make_shared<TrainPass>(t, x_dev, y_dev, nullptr, N, T, 0.f, stream, true, pixels_total, xs_dev);
+  std::unique_ptr<TrainPass> pass(new TrainPass(t, x_dev, y_dev, nullptr, N, T, 0.f, stream, true, pixels_total, xs_dev));
   if (int rc = pass->begin()) return rc;
   if (int rc = pass->advance()) {
     (void)hipStreamSynchronize(pass->st);
     return rc;
   }
-  t->pending = pass;
+  t->pending = std::move(pass);
   return RCED_OK;
 }
 
@@ -1359,8 +1013,7 @@ int rced_train_sync_next(rced_trainer* t, int* more) {
   if (!t || !more) return rced_fail(RCED_ERR_ARG, "trainer or output pointer is NULL");
   *more = 0;
   if (!t->pending) return rced_fail(RCED_ERR_STATE, "rced_train_sync_next: no synchronised pass is pending on this trainer");
-  DeviceGuard g(t->device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", t->device);
+  ON_DEVICE(t->device);
   if (t->pending->done()) return RCED_OK;
   if (int rc = t->pending->advance()) {   // the pass is over: nothing of it stays in flight, the handle is free again
     (void)hipStreamSynchronize(t->pending->st);
@@ -1378,10 +1031,8 @@ int rced_train_sync_end(rced_trainer* t, float* g_dev, double* s_dev, double* lo
   if (!t->pending->done())
     return rced_fail(RCED_ERR_STATE, "rced_train_sync_end: the pending pass has exchange points left (rced_train_sync_next until "
                                      "*more is 0, or rced_train_sync_abort)");
-  DeviceGuard g(t->device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", t->device);
-  const std::shared_ptr<TrainPass> pass = std::move(t->pending);
-  t->pending.reset();
+  ON_DEVICE(t->device);
+  const std::unique_ptr<TrainPass> pass = std::move(t->pending);
   const int rc = pass->end(g_dev, s_dev, accumulate != 0, loss_out);
   if (rc) (void)hipStreamSynchronize(pass->st);
   return rc;
@@ -1391,8 +1042,7 @@ int rced_train_sync_abort(rced_trainer* t) {
   if (!t) return rced_fail(RCED_ERR_ARG, "trainer is NULL");
   if (!t->pending) return RCED_OK;
   DeviceGuard g(t->device);
-  const std::shared_ptr<TrainPass> pass = std::move(t->pending);
-  t->pending.reset();
+  const std::unique_ptr<TrainPass> pass = std::move(t->pending);
   HIP_TRY(hipStreamSynchronize(pass->st));   // what the pass has launched reads the caller's batch
   return RCED_OK;
 }
@@ -1401,8 +1051,7 @@ int rced_train_sync_reduce(rced_trainer* t, const double* gathered_dev, int shar
   if (!t || !gathered_dev || !xs_dev) return rced_fail(RCED_ERR_ARG, "trainer or buffer is NULL");
   if (shards < 1 || stride < (size_t)kSyncDoubles)
     return rced_fail(RCED_ERR_ARG, "needs shards >= 1 and rows at least %d doubles apart (got %d, %zu)", kSyncDoubles, shards, stride);
-  DeviceGuard g(t->device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", t->device);
+  ON_DEVICE(t->device);
   hipLaunchKernelGGL(sync_reduce, dim3(1), dim3(kSyncDoubles), 0, static_cast<hipStream_t>(stream), gathered_dev, shards, stride,
                      kSyncDoubles, xs_dev);
   HIP_TRY(hipGetLastError());
@@ -1414,10 +1063,9 @@ int rced_train_copy_variables(rced_trainer* dst, rced_trainer* src, void* stream
   if (dst == src) return RCED_OK;
   if (dst->variant != src->variant || dst->device != src->device || dst->nvars != src->nvars)
     return rced_fail(RCED_ERR_ARG, "the two trainers must be of one variant on one device");
-  if (int rc = refuse_pending(dst, "rced_train_copy_variables")) return rc;
   if (int rc = refuse_pending(src, "rced_train_copy_variables")) return rc;
-  DeviceGuard g(dst->device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", dst->device);
+  Enter in(dst, "rced_train_copy_variables");
+  if (in.rc) return in.rc;
   HIP_TRY(hipMemcpyAsync(dst->params, src->params, src->nvars * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
   // which layers take the exact recomputation is a matter of the variables: src's flags are those of its last step, which
   // synchronised
@@ -1436,18 +1084,17 @@ int rced_conv_bn_relu_train(const float* x, float* y, const float* kernel, const
     return rced_fail(RCED_ERR_ARG, "bad shape");
   if (N == 0 || T == 0) return RCED_OK;
   if (!x || !y || !kernel || !bias || !gamma_beta) return rced_fail(RCED_ERR_ARG, "null pointer");
-  if (int rc = check_device(device)) return rc;
-  DeviceGuard g(device);
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  OnDevice on(device);
+  if (on.rc) return on.rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int frames = N * T, K = kh * kw * cin, cout4 = (cout + 3) & ~3;
   const size_t P = (size_t)frames * F, n = P * cout;
-  // one scratch allocation: z | repacked kernel | bias4 | mu | rstd | two dummies for the moving statistics | partial sums | sums
-  const size_t fl = n + (size_t)K * cout4 + cout4 + 4 * (size_t)cout;
+  // one scratch allocation: z | repacked kernel | bias4 | mu | rstd | partial sums | sums
+  const size_t fl = n + (size_t)K * cout4 + cout4 + 2 * (size_t)cout;
   const size_t dbl = (size_t)kReduceGrid * cout * 2 + 2 * (size_t)cout;
   float* buf = nullptr;
   HIP_TRY(hipMalloc(&buf, ((fl + 1) & ~(size_t)1) * sizeof(float) + dbl * sizeof(double)));
-  float *z = buf, *wf = z + n, *b4 = wf + (size_t)K * cout4, *mu = b4 + cout4, *rstd = mu + cout, *mm = rstd + cout, *mv = mm + cout;
+  float *z = buf, *wf = z + n, *b4 = wf + (size_t)K * cout4, *mu = b4 + cout4, *rstd = mu + cout;
   double* part = reinterpret_cast<double*>(buf + ((fl + 1) & ~(size_t)1));
   double* sums = part + (size_t)kReduceGrid * cout * 2;
   int rc = RCED_OK;
@@ -1459,7 +1106,7 @@ int rced_conv_bn_relu_train(const float* x, float* y, const float* kernel, const
                        (const float*)nullptr, (const float*)nullptr, P, cout, part);
     hipLaunchKernelGGL(train::reduce_finish, dim3(2 * cout), dim3(train::kThreads), 0, st, (const double*)part, kReduceGrid, cout, sums);
     hipLaunchKernelGGL(train::bn_stats_finish, dim3((cout + 63) / 64), dim3(64), 0, st, (const double*)sums, (double)P, cout, kBnEps,
-                       1.f, mu, rstd, mm, mv);    // momentum 1: the two dummies are left alone
+                       mu, rstd);
     if (batch_mean_var_out)
       hipLaunchKernelGGL(train::batch_mean_var, dim3((cout + 63) / 64), dim3(64), 0, st, (const double*)sums, (double)P, cout,
                          batch_mean_var_out);

@@ -588,7 +588,8 @@ void rced_train_destroy(rced_trainer* t);
 
 /* sess.run([loss, global_step, train_op]) (trainer.py:181-192) with the UPDATE_OPS: forward with batch
  * statistics, loss = sum((y - pred)^2) / batch_size, backward, tf.train.AdamOptimizer(lr) step in TF's
- * form (beta1 0.9, beta2 0.999, eps 1e-8), moving mean / variance update (momentum 0.99).
+ * form (beta1 0.9, beta2 0.999, eps 1e-8), moving mean / variance update (momentum 0.99; behind Adam: a
+ * step that returns an error has changed neither).
  * x_dev, y_dev: DEVICE [N, T, 129, 1] float32.  lr: the value fed to the learning-rate placeholder.
  * *loss_out (host) receives the batch loss.  Synchronises the stream. */
 int rced_train_step(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, float lr,

@@ -76,6 +76,32 @@ def test_grad_step_changes_nothing(net_work, tag, variant, built):
     tr.close()
 
 
+def test_moving_statistics_are_written_by_the_optimizer_epilogue_alone(built):
+    """No forward writes a variable, in any form of the step: after grad_step, and after a grad_step_sync run to its end
+    with one shard, variables() -- the moving statistics among them -- are the start values bit for bit; the apply_step that
+    follows leaves the variables of a train_step on the same batch, bit for bit."""
+    from fullycnnspeechenhancement_amd import FullyCNNTrainer
+    from fullycnnspeechenhancement_amd import spec
+    w = rced_np.make_weights("FullyCNNV3", seed=7)
+    x, y = rced_np.make_input(2, 3, seed=73), rced_np.make_input(2, 3, seed=83)
+    a = FullyCNNTrainer("FullyCNNV3", weights=w, **KW)
+    b = FullyCNNTrainer("FullyCNNV3", weights=w, **KW)
+    start = a.variables()
+    assert any("moving_" in name for name in start)
+    a.grad_step(x, y)
+    same_bits(a.variables(), start, "after grad_step: variable")
+    for _ in a.grad_step_sync(x, y, 2 * 3 * spec.FEATURE_DIM):      # the yielded sums stay as they are: this shard is all there is
+        pass
+    same_bits(a.variables(), start, "after grad_step_sync: variable")
+    assert a.apply_step() == 1
+    b.train_step(x, y)
+    moved = b.variables()
+    assert any(not np.array_equal(moved[name], start[name]) for name in start if "moving_" in name)
+    same_bits(a.variables(), moved, "after apply_step: variable")
+    a.close()
+    b.close()
+
+
 def test_accumulation_is_the_ordered_sum_of_the_shards(built):
     """Shards of unequal shape, (2 rows, T = 9) and (1 row, T = 12): the applied gradient is g_0 + g_1 formed in numpy
     float32 from each shard's own grad_step on a fresh trainer, the loss is loss_0 + loss_1 in float64, both exactly."""

@@ -33,7 +33,10 @@ def kernels(text):         # name -> (body, {resource: value}): what stands betw
             out[name][1][line.split(" ")[0]] = line.partition(" ")[2]
         elif name and line and (not line.startswith(".") or re.match(r"\.L\w+:$", line)):
             line = line.replace(name, "@self")
-            out[name][0].append(re.sub(r"\.L[A-Za-z_]+\d+(_\d+)?|<L\d+>", lambda l: labels.setdefault(l.group(0), "L%d" % len(labels)), line))
+            out[name][0].append(re.sub(r"\.L[A-Za-z_]+\d+(_\d+)?|<L\d+>|\bL\d+\b", lambda l: labels.setdefault(l.group(0).strip("<>"), "L%d" % len(labels)), line))
+    for b, _ in out.values():      # a disassembled object shows the padding up to the next function's alignment as part of this one
+        while b and b[-1] == "s_nop 0":
+            b.pop()
     return {n: ("\n".join(b), r) for n, (b, r) in out.items() if r}      # kernels only: they have resource lines
 with tempfile.TemporaryDirectory() as tmp:
     A, B = kernels(asm_of(sys.argv[1], tmp)), kernels(asm_of(sys.argv[2], tmp))
