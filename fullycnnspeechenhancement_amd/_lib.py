@@ -59,6 +59,10 @@ SYMBOLS = {
                                 ctypes.c_int, _vp, ctypes.c_int, _vp]),
     "rced_wss": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp,
                                 ctypes.c_int, _vp]),
+    "rced_fwseg": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp,
+                                  ctypes.c_int, _vp]),
+    "rced_cepd": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp,
+                                 ctypes.c_int, _vp, ctypes.c_int, _vp]),
     "rced_bss_sdr": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int, _vp]),
     "rced_mix_snr": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int,
                                     ctypes.c_double, _vp, ctypes.c_int, _vp]),

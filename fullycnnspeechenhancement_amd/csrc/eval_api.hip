@@ -25,8 +25,8 @@ struct Workspace {
   double* p = nullptr;
   size_t bytes = 0;
 };
-// STOI, SI-SDR, the segmental SNR, LLR, WSS and the BSS Eval SDR keep buffers of their own: none ever moves the one another entry's captured graph reads
-enum class Ws { Slices, Stoi, SiSdr, SegSnr, Llr, Wss, Bss, Kinds };
+// STOI, SI-SDR, the segmental SNR, LLR, WSS, the BSS Eval SDR, fwSNRseg and CD keep buffers of their own: none ever moves the one another entry's captured graph reads
+enum class Ws { Slices, Stoi, SiSdr, SegSnr, Llr, Wss, Bss, FwSeg, Cepd, Kinds };
 std::map<void*, Workspace> g_ws[(int)Ws::Kinds][kMaxDevices];
 std::mutex g_mu;
 
@@ -189,27 +189,37 @@ const double kWssWidth[sepm::kBands] = {70.0,    70.0,    70.0,    70.0,    70.0
                                         95.3398, 105.411, 116.256, 127.914, 140.423, 153.823, 168.154, 183.457, 199.776,
                                         217.153, 235.631, 255.255, 276.072, 298.126, 321.465, 346.136};
 
+int sepm_dft_size(int W) {
+  int nfft = 1;
+  while (nfft < 2 * W) nfft *= 2;
+  return nfft;
+}
+
+// The DFT's columns for bins bin0 .. bin0 + kBins - 1 as sepm::dft_gemm streams them: wave w, step s, tile q, part (cos, -sin),
+// lane: B[k = 4 s + (lane >> 4)][bin = bin0 + 16 (4 w + q) + (lane & 15)]
+std::vector<double> sepm_dft_stream(int W, int bin0) {
+  const int S = W / 4, nfft = sepm_dft_size(W), nb = nfft / 2;
+  std::vector<double> coef(sepm::wss_coef_len(W));
+  size_t at = 0;
+  for (int w = 0; w < sepm::kWaves; ++w)
+    for (int s = 0; s < S; ++s)
+      for (int q = 0; q < sepm::kBinTilesPerWave; ++q)
+        for (int part = 0; part < 2; ++part)
+          for (int lane = 0; lane < 64; ++lane) {
+            const int k = 4 * s + (lane >> 4), bin = bin0 + 16 * (sepm::kBinTilesPerWave * w + q) + (lane & 15);
+            const double th = 2.0 * M_PI * (double)(((long long)bin * k) % nfft) / (double)nfft;
+            coef[at++] = bin < nb ? (part ? -std::sin(th) : std::cos(th)) : 0.0;
+          }
+  return coef;
+}
+
 int wss_tables(int device, int fs, WssTables** out) {
   std::lock_guard<std::mutex> lk(g_wss_mu);
   WssTables& t = g_wss[device][fs == 16000];
   if (!t.coef) {
-    const int W = eval::seg_window(fs), S = W / 4;
-    int nfft = 1;
-    while (nfft < 2 * W) nfft *= 2;
-    const int nb = nfft / 2;
+    const int W = eval::seg_window(fs), nb = sepm_dft_size(W) / 2;
     const double fmax = fs / 2.0;
-    // wave w, step s, tile q, part (cos, -sin), lane: B[k = 4 s + (lane >> 4)][bin = 16 (4 w + q) + (lane & 15)]
-    std::vector<double> coef(sepm::wss_coef_len(W));
-    size_t at = 0;
-    for (int w = 0; w < sepm::kWaves; ++w)
-      for (int s = 0; s < S; ++s)
-        for (int q = 0; q < sepm::kBinTilesPerWave; ++q)
-          for (int part = 0; part < 2; ++part)
-            for (int lane = 0; lane < 64; ++lane) {
-              const int k = 4 * s + (lane >> 4), bin = 16 * (sepm::kBinTilesPerWave * w + q) + (lane & 15);
-              const double th = 2.0 * M_PI * (double)(((long long)bin * k) % nfft) / (double)nfft;
-              coef[at++] = bin < nb ? (part ? -std::sin(th) : std::cos(th)) : 0.0;
-            }
+    const std::vector<double> coef = sepm_dft_stream(W, 0);
     std::vector<double> filt((size_t)sepm::kBands * sepm::kBins, 0.0);
     std::vector<int> range(2 * sepm::kBands, 0);
     const double floor_g = std::exp(-30.0 / (2.0 * 2.303));
@@ -247,7 +257,38 @@ int wss_tables(int device, int fs, WssTables** out) {
   return RCED_OK;
 }
 
-// what rced_llr and rced_wss check alike; *nfcap = the frames of the longest utterance the strides allow, at least 1
+// ---- fwSNRseg: WSS's tables, and at 16 kHz the stream of the upper 256 bins, uploaded once per device -----------------------------
+struct FwsegTables {
+  const WssTables* wss = nullptr;
+  double* coef_hi = nullptr;         // bins 256 .. 511 at 16 kHz; NULL at 8 kHz, whose 256 bins WSS's stream covers
+};
+FwsegTables g_fwseg[kMaxDevices][2];
+std::mutex g_fwseg_mu;
+
+int fwseg_tables(int device, int fs, FwsegTables** out) {
+  WssTables* w = nullptr;
+  if (int rc = wss_tables(device, fs, &w)) return rc;
+  std::lock_guard<std::mutex> lk(g_fwseg_mu);
+  FwsegTables& t = g_fwseg[device][fs == 16000];
+  if (!t.wss) {
+    const int W = eval::seg_window(fs), nb = sepm_dft_size(W) / 2;
+    if (nb != (fs == 16000 ? 2 : 1) * sepm::kBins) return rced_fail(RCED_ERR_STATE, "fwSNRseg: %d bins at %d Hz", nb, fs);
+    // the magnitudes of every bin stand in LDS: a little over 64 KB a workgroup
+    if (fs == 16000) {
+      constexpr auto kernel = sepm::fwseg_spectrum_kernel<1, 2>;
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sepm::fwseg_lds_bytes(W, 1, nb)));
+      if (int rc = upload(&t.coef_hi, sepm_dft_stream(W, sepm::kBins), "fwSNRseg tables")) return rc;
+    } else {
+      constexpr auto kernel = sepm::fwseg_spectrum_kernel<2, 1>;
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sepm::fwseg_lds_bytes(W, 2, nb)));
+    }
+    t.wss = w;
+  }
+  *out = &t;
+  return RCED_OK;
+}
+
+// what rced_llr, rced_wss, rced_fwseg and rced_cepd check alike; *nfcap = the frames of the longest utterance the strides allow, at least 1
 int sepm_args(const Pairs& p, int fs, const double* out_dev, const double* frames_out, int frames_stride, int* nfcap) {
   if (fs != 8000 && fs != 16000) return rced_fail(RCED_ERR_ARG, "sample_rate must be 8000 or 16000, got %d", fs);
   if (int rc = check_pairs(p, out_dev, eval::kMaxLen, "2^30")) return rc;
@@ -435,6 +476,72 @@ int rced_wss(const float* ref_dev, int ref_stride, const float* est_dev, int est
            energy, nfcap);
   LAUNCH(sepm::wss_slope_kernel, dim3((nfcap + sepm::kThreads - 1) / sepm::kThreads, N), dim3(sepm::kThreads), 0, st,
          (const double*)energy, lengths_dev, cap, W, nfcap, d, frames_out, frames_stride);
+  return lowest_mean(d, sorted, lengths_dev, N, cap, W, nfcap, out_dev, nf_out, st);
+}
+
+int rced_fwseg(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N,
+               int sample_rate, double* out_dev, double* frames_out, int frames_stride, int* nf_out, int device, void* stream) {
+  const Pairs p{ref_dev, ref_stride, est_dev, est_stride, N};
+  int nfcap = 0;
+  if (int rc = sepm_args(p, sample_rate, out_dev, frames_out, frames_stride, &nfcap)) return rc;
+  if (N == 0) return RCED_OK;
+  OnDevice on(device, kMaxDevices);
+  if (on.rc) return on.rc;
+  FwsegTables* t = nullptr;
+  if (int rc = fwseg_tables(device, sample_rate, &t)) return rc;
+  const int cap = p.cap(), W = eval::seg_window(sample_rate);
+  double *bands, *d;
+  Carve ws;
+  ws.take(&bands, (size_t)N * 2 * nfcap * sepm::kBands);
+  ws.take(&d, (size_t)N * nfcap);
+  if (int rc = ws.bind(device, stream, Ws::FwSeg)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  constexpr auto spectrum_16k = sepm::fwseg_spectrum_kernel<1, 2>;
+  constexpr auto spectrum_8k = sepm::fwseg_spectrum_kernel<2, 1>;
+  if (W == sepm::kMaxW)           // 16 kHz: 16 frames, 512 bins in two passes; 8 kHz: 32 frames, 256 bins in one
+    LAUNCH(spectrum_16k, dim3((nfcap + 15) / 16, 2, N), dim3(sepm::kThreads),
+           sepm::fwseg_lds_bytes(W, 1, 2 * sepm::kBins), st, ref_dev, ref_stride, est_dev, est_stride, lengths_dev, cap, W,
+           (const double*)t->wss->coef, (const double*)t->coef_hi, (const double*)t->wss->filt, (const int*)t->wss->range, bands, nfcap);
+  else
+    LAUNCH(spectrum_8k, dim3((nfcap + 31) / 32, 2, N), dim3(sepm::kThreads),
+           sepm::fwseg_lds_bytes(W, 2, sepm::kBins), st, ref_dev, ref_stride, est_dev, est_stride, lengths_dev, cap, W,
+           (const double*)t->wss->coef, (const double*)t->coef_hi, (const double*)t->wss->filt, (const int*)t->wss->range, bands, nfcap);
+  LAUNCH(sepm::fwseg_band_kernel, dim3((nfcap + sepm::kThreads - 1) / sepm::kThreads, N), dim3(sepm::kThreads), 0, st,
+         (const double*)bands, lengths_dev, cap, W, nfcap, d, frames_out, frames_stride);
+  LAUNCH(eval::seg_snr_mean_kernel, dim3(N), dim3(eval::kThreads), 0, st, (const double*)d, lengths_dev, cap, W, nfcap, out_dev, nf_out);
+  return RCED_OK;
+}
+
+int rced_cepd(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N, int sample_rate,
+              int order, double* out_dev, double* frames_out, int frames_stride, int* nf_out, int device, void* stream) {
+  const Pairs p{ref_dev, ref_stride, est_dev, est_stride, N};
+  int nfcap = 0;
+  if (int rc = sepm_args(p, sample_rate, out_dev, frames_out, frames_stride, &nfcap)) return rc;
+  if (order < 1 || order > sepm::kMaxOrder) return rced_fail(RCED_ERR_ARG, "order must lie in [1, %d], got %d", sepm::kMaxOrder, order);
+  if (N == 0) return RCED_OK;
+  OnDevice on(device, kMaxDevices);
+  if (on.rc) return on.rc;
+  const int cap = p.cap(), W = eval::seg_window(sample_rate);
+  double *lags, *d, *sorted;
+  Carve ws;
+  ws.take(&lags, (size_t)N * nfcap * 2 * sepm::kMaxLags);
+  ws.take(&d, (size_t)N * nfcap);
+  ws.take(&sorted, (size_t)N * nfcap);
+  if (int rc = ws.bind(device, stream, Ws::Cepd)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  LAUNCH(sepm::llr_frame_kernel, dim3((nfcap + sepm::kLlrFramesPerBlock - 1) / sepm::kLlrFramesPerBlock, N), dim3(sepm::kThreads), 0, st,
+         ref_dev, ref_stride, est_dev, est_stride, lengths_dev, cap, W, order, lags, nfcap);
+  const dim3 per_frame((nfcap + sepm::kThreads - 1) / sepm::kThreads, N);
+#define CEPD_ORDER(P)                                                                                                                  \
+  case P:                                                                                                                              \
+    LAUNCH(sepm::cepd_recursion_kernel<P>, per_frame, dim3(sepm::kThreads), 0, st, (const double*)lags, lengths_dev, cap, W, nfcap, d, \
+           frames_out, frames_stride);                                                                                                 \
+    break;
+  switch (order) {
+    CEPD_ORDER(1) CEPD_ORDER(2) CEPD_ORDER(3) CEPD_ORDER(4) CEPD_ORDER(5) CEPD_ORDER(6) CEPD_ORDER(7) CEPD_ORDER(8)
+    CEPD_ORDER(9) CEPD_ORDER(10) CEPD_ORDER(11) CEPD_ORDER(12) CEPD_ORDER(13) CEPD_ORDER(14) CEPD_ORDER(15) CEPD_ORDER(16)
+  }
+#undef CEPD_ORDER
   return lowest_mean(d, sorted, lengths_dev, N, cap, W, nfcap, out_dev, nf_out, st);
 }
 

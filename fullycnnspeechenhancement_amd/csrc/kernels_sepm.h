@@ -1,6 +1,8 @@
 // LLR and WSS per utterance (include/rced.h, "evaluation" section): the two spectral terms of the composite
 // measures of Hu and Loizou (2008).  Both frame the signals as the segmental SNR does (kernels_eval.h) and end in the same
-// order statistic, the mean of the lowest 95 % of the frame values.
+// order statistic, the mean of the lowest 95 % of the frame values.  The cepstral distance (CD) sits on LLR's lags and models
+// and ends in the same order statistic; the frequency-weighted segmental SNR (fwSNRseg) sits on WSS's staging, coefficient
+// stream, GEMM and filters and ends in the plain mean over the frames (eval::seg_snr_mean_kernel).
 //
 // The family's invariants hold: no atomics; every sum runs in one order fixed by positions inside the utterance (which lane,
 // which register and which workgroup an element lands in depends on its frame and sample index only); samples past a length
@@ -140,6 +142,58 @@ __global__ __launch_bounds__(kThreads) void llr_recursion_kernel(const double* _
   d[(size_t)n * nfcap + f] = v > limit ? limit : v;      // a nan stays a nan, as np.minimum leaves it
 }
 
+// ---- CD: the cepstral distance of the same two LPC models ---------------------------------------------------------------
+
+constexpr int kMaxOrder = kMaxLags - 1;    // the orders rced_cepd takes: 1 .. 16
+constexpr double kCdScale = 4.3429448190325175;   // 10 / ln 10
+constexpr double kCdMax = 10.0;
+
+// c[1 .. P] of 1 / A(z): c[1] = -A[1], c[k] = -(A[k] + (sum_{i < k} i c[i] A[k - i]) / k), the sum in ascending i
+template <int P>
+__device__ inline void lpc_cepstrum(const double (&A)[P + 1], double (&c)[P + 1]) {
+#pragma clang fp contract(off)
+  c[0] = 0.0;
+#pragma unroll
+  for (int k = 1; k <= P; ++k) {
+    double s = 0.0;
+#pragma unroll
+    for (int i = 1; i < k; ++i) s += ((double)i * c[i]) * A[k - i];
+    c[k] = -(A[k] + s / (double)k);
+  }
+}
+
+// grid (ceil(nfcap / kThreads), N): one thread per frame, on llr_frame_kernel's lags.  (10 / ln 10) sqrt(2 sum (cx - cy)^2)
+// limited to [0, 10] (a nan stays a nan): d [N][nfcap] and frames_out, NULL or [N][frames_stride], take the same value
+template <int P>
+__global__ __launch_bounds__(kThreads) void cepd_recursion_kernel(const double* __restrict__ R, const int* __restrict__ lengths,
+                                                                  int cap, int W, int nfcap, double* __restrict__ d,
+                                                                  double* __restrict__ frames_out, int frames_stride) {
+#pragma clang fp contract(off)
+  const int n = blockIdx.y, f = blockIdx.x * kThreads + threadIdx.x;
+  const int nf = eval::seg_frames(eval::clamp_len(lengths, n, cap), W);
+  if (f >= nf) return;
+  const double* src = R + ((size_t)n * nfcap + f) * 2 * kMaxLags;
+  double lags[P + 1], A[P + 1], cx[P + 1], cy[P + 1];
+#pragma unroll
+  for (int m = 0; m <= P; ++m) lags[m] = src[m];
+  lpc_model<P>(lags, A);
+  lpc_cepstrum<P>(A, cx);
+#pragma unroll
+  for (int m = 0; m <= P; ++m) lags[m] = src[kMaxLags + m];
+  lpc_model<P>(lags, A);
+  lpc_cepstrum<P>(A, cy);
+  double s = 0.0;
+#pragma unroll
+  for (int k = 1; k <= P; ++k) {
+    const double diff = cx[k] - cy[k];
+    s += diff * diff;
+  }
+  double v = kCdScale * sqrt(2.0 * s);
+  v = v < 0.0 ? 0.0 : (v > kCdMax ? kCdMax : v);
+  if (frames_out) frames_out[(size_t)n * frames_stride + f] = v;
+  d[(size_t)n * nfcap + f] = v;
+}
+
 // ---- the mean of the k smallest of nf values -----------------------------------------------------------------------
 
 // a before b in np.sort's order: nan last
@@ -199,35 +253,27 @@ __host__ __device__ inline size_t wss_lds_bytes(int W, int MT) {
 // doubles of the coefficient stream at a window of W samples
 __host__ __device__ inline size_t wss_coef_len(int W) { return (size_t)kWaves * (W / 4) * kBinTilesPerWave * 2 * 64; }
 
-// grid (ceil(nfcap / (16 MT)), 2, N), 4 waves: a tile of 16 MT frames of one signal (y = 0 clean, 1 estimate).
-// The windowed frames stand in LDS as [sample][frame]; wave w takes bin tiles 4 w .. 4 w + 3 (16 bins each) and walks K = W
-// in steps of 4: D[frame][bin] += A[frame][k] B[k][bin], once with the cos and once with the -sin columns, so that a lane
-// holds re and im of the same (frame, bin).  coef is that B stream in fragment order (wss_coef_len).  The powers replace
-// the frames in LDS; then 25 sums per frame over each filter's nonzero bins in bin order.  energy: [N][2][nfcap][25] dB.
-// Frames at or past nf are zero rows: nothing past a length is read.  Two workgroups share a CU (at most 256 registers a
-// lane, 2 x 64 KB of LDS): one stages or sums its filters while the other holds the matrix pipe.
+// The windowed frames f0 .. f0 + 16 MT - 1 of one row into LDS as [sample][frame], pitch 16 MT + 1; frames at or past nf are
+// zero rows: nothing past a length is read
 template <int MT>
-__global__ __launch_bounds__(kThreads, 2) void wss_spectrum_kernel(const float* __restrict__ ref, int ref_stride,
-                                                                const float* __restrict__ est, int est_stride,
-                                                                const int* __restrict__ lengths, int cap, int W,
-                                                                const double* __restrict__ coef, const double* __restrict__ filt,
-                                                                const int* __restrict__ range, double* __restrict__ energy,
-                                                                int nfcap) {
-  extern __shared__ double sh[];
+__device__ __forceinline__ void dft_stage(double* __restrict__ sh, const float* __restrict__ row, int f0, int nf, int W) {
   constexpr int FR = 16 * MT, LD = FR + 1;
-  const int n = blockIdx.z, which = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int H = W / 4, S = W / 4;
-  const int nf = eval::seg_frames(eval::clamp_len(lengths, n, cap), W);
-  const int f0 = blockIdx.x * FR;
-  if (f0 >= nf) return;                                  // uniform over the workgroup
-  const float* row = which ? est + (size_t)n * est_stride : ref + (size_t)n * ref_stride;
+  const int H = W / 4;
   for (int k = threadIdx.x; k < W; k += kThreads) {
     const double w = hann(k, W);
     for (int i = 0; i < FR; ++i)
       sh[k * LD + i] = f0 + i < nf ? w * (double)row[(size_t)(f0 + i) * H + k] : 0.0;   // (f0 + i) H + k < len
   }
-  __syncthreads();
-  d4 acc[kBinTilesPerWave][MT][2];
+}
+
+// D[frame][bin] = sum_k A[frame][k] B[k][bin] over the staged frames, K = W in steps of 4, once with the cos and once with the
+// -sin columns of `coef` (a stream of wss_coef_len(W) doubles in fragment order): wave w takes the stream's bin tiles
+// 4 w .. 4 w + 3, and a lane ends with re and im of the same (frame, bin)
+template <int MT>
+__device__ __forceinline__ void dft_gemm(const double* __restrict__ sh, const double* __restrict__ coef, int W,
+                                         d4 (&acc)[kBinTilesPerWave][MT][2]) {
+  constexpr int LD = 16 * MT + 1;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, S = W / 4;
 #pragma unroll
   for (int q = 0; q < kBinTilesPerWave; ++q)
 #pragma unroll
@@ -265,6 +311,32 @@ __global__ __launch_bounds__(kThreads, 2) void wss_spectrum_kernel(const float* 
       bc[q][1] = bn[q][1];
     }
   }
+}
+
+// grid (ceil(nfcap / (16 MT)), 2, N), 4 waves: a tile of 16 MT frames of one signal (y = 0 clean, 1 estimate).
+// The windowed frames stand in LDS (dft_stage); wave w takes bin tiles 4 w .. 4 w + 3 (16 bins each) of the DFT (dft_gemm).
+// The powers replace the frames in LDS; then 25 sums per frame over each filter's nonzero bins in bin order.  energy: [N][2][nfcap][25] dB.
+// Frames at or past nf are zero rows: nothing past a length is read.  Two workgroups share a CU (at most 256 registers a
+// lane, 2 x 64 KB of LDS): one stages or sums its filters while the other holds the matrix pipe.
+template <int MT>
+__global__ __launch_bounds__(kThreads, 2) void wss_spectrum_kernel(const float* __restrict__ ref, int ref_stride,
+                                                                const float* __restrict__ est, int est_stride,
+                                                                const int* __restrict__ lengths, int cap, int W,
+                                                                const double* __restrict__ coef, const double* __restrict__ filt,
+                                                                const int* __restrict__ range, double* __restrict__ energy,
+                                                                int nfcap) {
+  extern __shared__ double sh[];
+  constexpr int FR = 16 * MT;
+  const int n = blockIdx.z, which = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int arow = lane >> 4, acol = lane & 15;
+  const int nf = eval::seg_frames(eval::clamp_len(lengths, n, cap), W);
+  const int f0 = blockIdx.x * FR;
+  if (f0 >= nf) return;                                  // uniform over the workgroup
+  const float* row = which ? est + (size_t)n * est_stride : ref + (size_t)n * ref_stride;
+  dft_stage<MT>(sh, row, f0, nf, W);
+  __syncthreads();
+  d4 acc[kBinTilesPerWave][MT][2];
+  dft_gemm<MT>(sh, coef, W, acc);
   __syncthreads();                                       // every wave is done with the frames
 #pragma unroll
   for (int q = 0; q < kBinTilesPerWave; ++q) {
@@ -347,6 +419,132 @@ __global__ __launch_bounds__(kThreads) void wss_slope_kernel(const double* __res
     const double w = (wx[i] + wy[i]) / 2.0, diff = sx[i] - sy[i];
     num += w * (diff * diff);
     den += w;
+  }
+  const double v = num / den;
+  if (frames_out) frames_out[(size_t)n * frames_stride + f] = v;
+  d[(size_t)n * nfcap + f] = v;
+}
+
+// ---- fwSNRseg: the frequency-weighted segmental SNR -----------------------------------------------------------------------
+
+// LDS of fwseg_spectrum_kernel: the staged frames, then in their place the magnitudes [16 MT][nb + 1] and 16 MT sums
+__host__ __device__ inline size_t fwseg_lds_bytes(int W, int MT, int nb) {
+  const size_t a = (size_t)W * wss_frame_ld(MT), b = (size_t)16 * MT * (nb + 2);
+  return (a > b ? a : b) * sizeof(double);
+}
+
+// grid, staging, coefficient stream and GEMM of wss_spectrum_kernel; nb = kBins PASSES bins (256 at 8 kHz, 512 at 16 kHz).
+// The normalising sum takes every bin, so with PASSES = 2 the GEMM runs twice over the same staged frames: first coef (bins
+// 0 .. 255, WSS's stream), whose magnitudes wait in registers, then coef_hi (bins 256 .. 511): the accumulators of one pass at
+// a time keep two workgroups on a CU.  The magnitudes sqrt(re^2 + im^2) replace the frames in LDS; thread i < 16 MT adds
+// frame i's bins 0 .. nb - 1 in bin order; then 25 sums per frame over each filter's nonzero bins in bin order of
+// magnitude / sum.  bands: [N][2][nfcap][25], linear.  A frame of zeros gives 0 / 0 = nan in every band.
+template <int MT, int PASSES>
+__global__ __launch_bounds__(kThreads, 2) void fwseg_spectrum_kernel(const float* __restrict__ ref, int ref_stride,
+                                                                  const float* __restrict__ est, int est_stride,
+                                                                  const int* __restrict__ lengths, int cap, int W,
+                                                                  const double* __restrict__ coef, const double* __restrict__ coef_hi,
+                                                                  const double* __restrict__ filt, const int* __restrict__ range,
+                                                                  double* __restrict__ bands, int nfcap) {
+#pragma clang fp contract(off)
+  extern __shared__ double sh[];
+  constexpr int FR = 16 * MT, NB = kBins * PASSES, MLD = NB + 1;
+  const int n = blockIdx.z, which = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int arow = lane >> 4, acol = lane & 15;
+  const int nf = eval::seg_frames(eval::clamp_len(lengths, n, cap), W);
+  const int f0 = blockIdx.x * FR;
+  if (f0 >= nf) return;                                  // uniform over the workgroup
+  const float* row = which ? est + (size_t)n * est_stride : ref + (size_t)n * ref_stride;
+  dft_stage<MT>(sh, row, f0, nf, W);
+  __syncthreads();
+  d4 acc[kBinTilesPerWave][MT][2];
+  double low[PASSES > 1 ? kBinTilesPerWave : 1][MT][4];
+  dft_gemm<MT>(sh, coef, W, acc);
+  if constexpr (PASSES > 1) {
+#pragma unroll
+    for (int q = 0; q < kBinTilesPerWave; ++q)
+#pragma unroll
+      for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const double re = acc[q][m][0][r], im = acc[q][m][1][r];
+          low[q][m][r] = sqrt(re * re + im * im);
+        }
+    dft_gemm<MT>(sh, coef_hi, W, acc);
+  }
+  __syncthreads();                                       // every wave is done with the frames
+#pragma unroll
+  for (int q = 0; q < kBinTilesPerWave; ++q) {
+    const int bin = (wave * kBinTilesPerWave + q) * 16 + acol;          // < kBins
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const double re = acc[q][m][0][r], im = acc[q][m][1][r];
+        double* at = sh + (16 * m + arow + 4 * r) * MLD + bin;          // row < FR, bin + kBins (PASSES - 1) < NB
+        if constexpr (PASSES > 1) at[0] = low[q][m][r];
+        at[kBins * (PASSES - 1)] = sqrt(re * re + im * im);
+      }
+  }
+  __syncthreads();
+  double* total = sh + FR * MLD;                         // FR more doubles: fwseg_lds_bytes
+  if (threadIdx.x < FR) {
+    const double* v = sh + threadIdx.x * MLD;
+    double sum = 0.0;
+    for (int j = 0; j < NB; j += 4) {                    // four loads in flight, the additions in bin order
+      double p[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) p[u] = v[j + u];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) sum += p[u];
+    }
+    total[threadIdx.x] = sum;
+  }
+  __syncthreads();
+  double* out = bands + ((size_t)(n * 2 + which) * nfcap + f0) * kBands;
+  for (int t = threadIdx.x; t < FR * kBands; t += kThreads) {
+    const int i = t % FR, band = t / FR;
+    if (f0 + i >= nf) continue;
+    const int lo = range[2 * band], hi = range[2 * band + 1];          // 0 <= lo <= hi <= kPowLd < NB: checked where the table is built
+    const double all = total[i];
+    double sum = 0.0;
+    for (int j = lo; j < hi; j += 4) {
+      double f[4], p[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int jj = j + u < hi ? j + u : hi - 1;
+        f[u] = filt[band * kBins + jj];
+        p[u] = sh[i * MLD + jj];
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (j + u < hi) sum += (p[u] / all) * f[u];
+    }
+    out[(size_t)i * kBands + band] = sum;
+  }
+}
+
+// grid (ceil(nfcap / kThreads), N): one thread per frame.  sum(Wt snr) / sum(Wt) in band order, Wt = E_x^0.2,
+// snr = 10 log10(E_x^2 / max((E_x - E_y)^2, eps)) limited to [-10, 35]; a nan stays a nan, as np.maximum / np.minimum leave it.
+// d: [N][nfcap]; frames_out: NULL or [N][frames_stride]
+__global__ __launch_bounds__(kThreads) void fwseg_band_kernel(const double* __restrict__ bands, const int* __restrict__ lengths,
+                                                              int cap, int W, int nfcap, double* __restrict__ d,
+                                                              double* __restrict__ frames_out, int frames_stride) {
+#pragma clang fp contract(off)
+  const int n = blockIdx.y, f = blockIdx.x * kThreads + threadIdx.x;
+  const int nf = eval::seg_frames(eval::clamp_len(lengths, n, cap), W);
+  if (f >= nf) return;
+  const double* px = bands + ((size_t)(n * 2) * nfcap + f) * kBands;
+  const double* py = bands + ((size_t)(n * 2 + 1) * nfcap + f) * kBands;
+  double num = 0.0, den = 0.0;
+  for (int i = 0; i < kBands; ++i) {
+    const double ex = px[i], diff = ex - py[i], wt = pow(ex, 0.2);
+    double dd = diff * diff;
+    dd = (dd > eval::kEps64 || dd != dd) ? dd : eval::kEps64;
+    double s = 10.0 * log10(ex * ex / dd);
+    s = s < -10.0 ? -10.0 : (s > 35.0 ? 35.0 : s);
+    num += wt * s;
+    den += wt;
   }
   const double v = num / den;
   if (frames_out) frames_out[(size_t)n * frames_stride + f] = v;

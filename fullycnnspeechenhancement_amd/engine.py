@@ -3,7 +3,7 @@
 Reference: BaseTester / FullyCNNTester (model_utils/tester.py:18-90) and InferenceEngine
 (infer.py:19-52): read cfg -> creat_graph() -> _init_session() -> _load_checkpoint() ->
 test_step(ndarray[N,T,129,1]) -> ndarray[N,T,129,1], and the evaluation loop over it (tester.py:92-167):
-`evaluate_pcm` / `test` take ragged PCM through STFT -> net -> ISTFT rebuild -> SDR (and STOI, ESTOI, SI-SDR, segmental SNR, LLR, WSS, the SDR of BSS Eval on request) on the device.
+`evaluate_pcm` / `test` take ragged PCM through STFT -> net -> ISTFT rebuild -> SDR (and STOI, ESTOI, SI-SDR, segmental SNR, LLR, WSS, fwSNRseg, CD, the SDR of BSS Eval on request) on the device.
 PESQ scoring and the evaluation loop's wav files are not mirrored; the manifest-driven DataLoader is loader.DataLoader (batches built on the device).
 """
 
@@ -11,7 +11,7 @@ import numpy as np
 
 from . import model as _model, spec, weights as _weights
 from ._args import check_rebuild
-from .evaluation import ALL_EXTRA, check_extra
+from .evaluation import EVERY_EXTRA, check_extra
 from .metrics import AverageMeter
 
 
@@ -46,7 +46,7 @@ class FullyCNNTester(object):
         self._weights = weights
         self.sdr_score = AverageMeter()     # tester.py:63; test() adds to it and never resets it, as there
         self.stoi_score = AverageMeter()    # tester.py:62; filled by test(..., stoi=True)
-        self.extra_scores = {name: AverageMeter() for name in ALL_EXTRA}    # filled by test(..., extra=(names))
+        self.extra_scores = {name: AverageMeter() for name in EVERY_EXTRA}    # filled by test(..., extra=(names))
         self.creat_graph()
         self._load_checkpoint()
 
@@ -100,7 +100,8 @@ class FullyCNNTester(object):
         pinned 2e-6 of the scale), so batch_mix / batch_clean are not read.  With stoi=True every utterance's STOI goes
         into self.stoi_score as well and the line gains the reference's st_score field, in the reference's order.
         extra: names from evaluation.EXTRA_METRICS ("estoi", "si_sdr", "seg_snr") and evaluation.SPECTRAL_METRICS ("llr", limited
-        at 2, and "wss") and evaluation.PROJECTION_METRICS ("bss_sdr", BSS Eval's SDR with 512 taps); every utterance's score goes into self.extra_scores[name], and one further line with their averages follows the reference's.
+        at 2, and "wss"), evaluation.PROJECTION_METRICS ("bss_sdr", BSS Eval's SDR with 512 taps) and evaluation.SEPM_METRICS
+        ("fw_seg_snr", the frequency-weighted segmental SNR, and "cd", the cepstral distance at LLR's order); every utterance's score goes into self.extra_scores[name], and one further line with their averages follows the reference's.
         rebuild: "reference" (the rebuild the reference's scores are made with) or "ola" (weighted overlap-add: evaluate_pcm).
         The framing is valid_loader.dataset.framing where the loader has one (loader.DataSet(framing=...)), as the reference
         reads window_s from the dataset; else the default.
@@ -155,10 +156,12 @@ def evaluate_pcm(forward, mix_sig, clean_sig, nfft=512, device=0, lengths=None, 
     kernel family, as in audio.stft_batch.
     Returns (denoise: list of numpy float32, row i trimmed to its length; sdr: numpy float64 [N]); with stoi=True a third
     element, STOI per utterance (numpy float64 [N], audio.stoi_batch of the rebuilt audio against the clean rows).
-    extra: names from evaluation.EXTRA_METRICS + evaluation.SPECTRAL_METRICS + evaluation.PROJECTION_METRICS ("estoi", "si_sdr",
-    "seg_snr", "llr", "wss", "bss_sdr"; anything else is a ValueError before any device work).  With extra non-empty the tuple gains one last element, a dict
+    extra: names from evaluation.EXTRA_METRICS + evaluation.SPECTRAL_METRICS + evaluation.PROJECTION_METRICS +
+    evaluation.SEPM_METRICS ("estoi", "si_sdr", "seg_snr", "llr", "wss", "bss_sdr", "fw_seg_snr", "cd"; anything else is a ValueError
+    before any device work).  With extra non-empty the tuple gains one last element, a dict
     name -> numpy float64 [N] (audio.stoi_batch(extended=True), audio.si_sdr_batch, audio.seg_snr_batch, audio.llr_batch
-    with its limit of 2, audio.wss_batch, audio.bss_sdr_batch with 512 taps of the same pairs).
+    with its limit of 2, audio.wss_batch, audio.bss_sdr_batch with 512 taps, audio.fw_seg_snr_batch, audio.cep_dist_batch at
+    LLR's order, of the same pairs).
     rebuild: "reference" (AudioReBuild as shipped, the default) or "ola" (weighted overlap-add, audio.istft_batch: utterance i is
     rebuilt from its own num_frames(length) frames, nfft plays no part); anything else, or "ola" with kernels="f32", is a
     ValueError before any device work.

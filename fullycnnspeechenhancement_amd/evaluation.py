@@ -1,5 +1,5 @@
 """The evaluation loop's entry points on the device, over the C ABI: SDR, STOI, ESTOI, SI-SDR,
-segmental SNR, LLR, WSS and the SDR of BSS Eval per utterance, add_noise's SNR mixing in closed form, and the core of the loop, STFT -> forward -> ISTFT -> scores.  audio.py re-exports
+segmental SNR, LLR, WSS, fwSNRseg, CD and the SDR of BSS Eval per utterance, add_noise's SNR mixing in closed form, and the core of the loop, STFT -> forward -> ISTFT -> scores.  audio.py re-exports
 every public name here."""
 
 import numpy as np
@@ -112,6 +112,7 @@ def _spectral_rate(sample_rate):
 
 
 def _spectral_batch(entry, clean, estimate, lengths, sample_rate, detail, *limit):
+    """What the frame-based scores at 8 / 16 kHz share; *limit: the entry's own arguments between the rate and the outputs."""
     fs = _spectral_rate(sample_rate)
     p = _Pairs(clean, estimate, lengths)
     w = (3 * fs + 50) // 100
@@ -142,6 +143,37 @@ def wss_batch(clean, estimate, lengths=None, sample_rate=8000, detail=False):
     DFT, 25 critical-band energies in dB, their 24 slopes weighted by the nearest peak and the global maximum, the mean of
     the lowest 95 % of the frames).  Arguments and returns as in llr_batch, without the limit."""
     return _spectral_batch("rced_wss", clean, estimate, lengths, sample_rate, detail)
+
+
+def fw_seg_snr_batch(clean, estimate, lengths=None, sample_rate=8000, detail=False):
+    """Frequency-weighted segmental SNR per utterance on the device (DESIGN.md "fwSNRseg": the segmental SNR's frames, an fp64
+    DFT, each signal's magnitudes over their sum, the 25 critical-band filters of WSS on those, weights E_x ** 0.2, each
+    band's SNR limited to [-10, 35] dB, the plain mean over the frames).  Arguments as in sdr_batch; sample_rate: 8000 or
+    16000.  Returns torch.float64 [N] (dB) on the device, current stream -- nan for an utterance shorter than one frame or
+    with a digitally silent frame; with detail=True also torch.int32 [N], the frames of each utterance, and torch.float64
+    [N, F], every frame's value in frame order (0 past an utterance's frames).  Built as DESIGN.md writes it: parity with
+    pysepm is unpinned."""
+    return _spectral_batch("rced_fwseg", clean, estimate, lengths, sample_rate, detail)
+
+
+CEP_MAX_ORDER = 16
+
+
+def _cep_order(order, sample_rate):
+    if order is None:
+        return 10 if _spectral_rate(sample_rate) < 10000 else 16       # LLR's order at the rate
+    if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or not 1 <= order <= CEP_MAX_ORDER:
+        raise ValueError("order must be None or an integer in [1, %d], got %r" % (CEP_MAX_ORDER, order))
+    return int(order)
+
+
+def cep_dist_batch(clean, estimate, lengths=None, sample_rate=8000, order=None, detail=False):
+    """Cepstral distance of the two signals' LPC models per utterance on the device (DESIGN.md "CD": LLR's frames, lags and
+    Levinson-Durbin, the models' first `order` cepstral coefficients, (10 / ln 10) sqrt(2 sum (cx - cy)^2) limited to
+    [0, 10] per frame, the mean of the lowest 95 % of the frames).  Arguments as in llr_batch; order: None for LLR's order
+    at the rate (10 below 10 kHz, else 16) or an integer in [1, 16], anything else is a ValueError before any device work.
+    Returns as llr_batch does; the per-frame values are the limited ones.  Parity with pysepm is unpinned."""
+    return _spectral_batch("rced_cepd", clean, estimate, lengths, sample_rate, detail, _cep_order(order, sample_rate))
 
 
 BSS_MAX_FILTER = 512
@@ -185,15 +217,21 @@ SPECTRAL_METRICS = ("llr", "wss")       # the composite measures' two spectral t
 PROJECTION_METRICS = ("bss_sdr",)       # BSS Eval's SDR at its filter length of 512
 ALL_EXTRA = tuple(_EXTRA)
 assert ALL_EXTRA == EXTRA_METRICS + SPECTRAL_METRICS + PROJECTION_METRICS
+# The two further objective measures of Hu and Loizou (2008), a table and a tuple of their own: the six names above and the
+# tuples that hold them keep their values for the callers that pinned them.  `extra` takes names from both tables.
+_EXTRA_SEPM = {"fw_seg_snr": (fw_seg_snr_batch, {"sample_rate": SAMPLE_RATE}),
+               "cd": (cep_dist_batch, {"sample_rate": SAMPLE_RATE, "order": None})}
+SEPM_METRICS = tuple(_EXTRA_SEPM)       # fwSNRseg, and CD at LLR's order
+EVERY_EXTRA = ALL_EXTRA + SEPM_METRICS
 
 
 def check_extra(extra):
-    """The evaluation loop's `extra` argument as a tuple of names from EXTRA_METRICS + SPECTRAL_METRICS + PROJECTION_METRICS,
-    in the caller's order; ValueError for anything else.  Touches no device."""
+    """The evaluation loop's `extra` argument as a tuple of names from EXTRA_METRICS + SPECTRAL_METRICS + PROJECTION_METRICS +
+    SEPM_METRICS, in the caller's order; ValueError for anything else.  Touches no device."""
     names = (extra,) if isinstance(extra, str) else tuple(extra)
     for name in names:
-        if name not in ALL_EXTRA:
-            raise ValueError("extra names must come from %r, got %r" % (ALL_EXTRA, name))
+        if name not in EVERY_EXTRA:
+            raise ValueError("extra names must come from %r, got %r" % (EVERY_EXTRA, name))
     if len(set(names)) != len(names):
         raise ValueError("extra names must be distinct, got %r" % (names,))
     return names
@@ -265,8 +303,8 @@ def denoise_and_score(forward, mix, clean, lengths, nfft=512, kernels="x6", stoi
     """The device core of the evaluation loop (tester.py:100-146 / trainer.py:260-307 without PESQ / wav files):
     STFT of the mixtures -> forward (device [N, T, 129, 1] -> same) -> ISTFT rebuild -> SDR (and, with stoi=True, STOI) of
     every rebuilt row against its clean row over its own length.  mix, clean: torch.cuda float32 [N, L] zero-padded;
-    lengths: N sample counts.  extra: names from EXTRA_METRICS + SPECTRAL_METRICS + PROJECTION_METRICS, further scores of
-    the same pairs ("llr" is the form limited at 2, "bss_sdr" BSS Eval's SDR with 512 taps).
+    lengths: N sample counts.  extra: names from EXTRA_METRICS + SPECTRAL_METRICS + PROJECTION_METRICS + SEPM_METRICS, further
+    scores of the same pairs ("llr" is the form limited at 2, "bss_sdr" BSS Eval's SDR with 512 taps, "cd" at LLR's order).
     Returns (audio [N, (T+1)*128] on the device -- the caller trims row n to lengths[n] --, sdr torch.float64 [N]), with
     stoi=True (audio, sdr, stoi torch.float64 [N]); with extra, one more element last: a dict name -> torch.float64 [N]
     (STOI and ESTOI, asked for together, come from one rced_stoi_ex call).
@@ -288,7 +326,7 @@ def denoise_and_score(forward, mix, clean, lengths, nfft=512, kernels="x6", stoi
         scored += (st,)
     elif stoi:
         scored += (stoi_batch(clean, out, lengths, SAMPLE_RATE),)
-    for name, (batch, kw) in _EXTRA.items():
+    for name, (batch, kw) in list(_EXTRA.items()) + list(_EXTRA_SEPM.items()):
         if name in extra and name not in more:
             more[name] = batch(clean, out, lengths, **kw)
     return scored + ({name: more[name] for name in extra},) if extra else scored

@@ -9,6 +9,8 @@ utils.py:80-85) and SegSNR have the same call surface over rced_stoi_ex / rced_s
 float64 restatement of its definition in tests/ (DESIGN.md "ESTOI", "SI-SDR", "Segmental SNR"), not to pystoi or pysepm.
 LLR and WSS (rced_llr / rced_wss, pinned to tests/sepm_np.py in the same way) are the two spectral terms of the composite
 measures of Hu and Loizou (2008); `composite` turns them, the segmental SNR and a PESQ column into CSIG / CBAK / COVL.
+FwSegSNR and CepDist (rced_fwseg / rced_cepd, pinned to tests/sepm2_np.py) are the frequency-weighted segmental SNR and the
+cepstral distance of the same paper.
 BSSSDR (rced_bss_sdr, pinned to tests/bsseval_np.py) is the SDR of BSS Eval for one source: the estimate is projected onto
 the clean signal's delayed copies first, so a fixed filtering or delay is forgiven.
 PESQ is not built (the reference takes it from pypesq); everything else the composite measures need is.
@@ -190,6 +192,37 @@ class WSS(_PairMetric):
         _PairMetric.__init__(self, device, "wss", float("nan"), "wss_batch", sample_rate=self.sr)
 
     def wss(self, x, y):
+        return self._score(x, y)
+
+
+class FwSegSNR(_PairMetric):
+    """Frequency-weighted segmental SNR, `FwSegSNR(sr)(clean, processed)`: numpy 1-D in, Python float (dB) out, computed on the
+    device (rced_fwseg).  Signals shorter than one frame give nan."""
+
+    def __init__(self, sr=8000, device=0):
+        from . import audio
+        if sr not in audio.SPECTRAL_RATES:
+            raise ValueError("sr must be 8000 or 16000, got %r" % (sr,))
+        self.sr = int(sr)
+        _PairMetric.__init__(self, device, "fw_seg_snr", float("nan"), "fw_seg_snr_batch", sample_rate=self.sr)
+
+    def fw_seg_snr(self, x, y):
+        return self._score(x, y)
+
+
+class CepDist(_PairMetric):
+    """Cepstral distance of the LPC models, `CepDist(sr, order)(clean, processed)`: numpy 1-D in, Python float out, computed on
+    the device (rced_cepd).  order: None for LLR's order at the rate, or an integer in [1, 16].  Signals shorter than one
+    frame give nan."""
+
+    def __init__(self, sr=8000, order=None, device=0):
+        from . import audio, evaluation
+        if sr not in audio.SPECTRAL_RATES:
+            raise ValueError("sr must be 8000 or 16000, got %r" % (sr,))
+        self.sr, self.order = int(sr), evaluation._cep_order(order, sr)      # ValueError outside 1 .. 16
+        _PairMetric.__init__(self, device, "cd", float("nan"), "cep_dist_batch", sample_rate=self.sr, order=self.order)
+
+    def cd(self, x, y):
         return self._score(x, y)
 
 

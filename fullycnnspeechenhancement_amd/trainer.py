@@ -24,7 +24,7 @@ import time
 import numpy as np
 
 from . import _lib, model as _model, spec, weights as _weights
-from .evaluation import ALL_EXTRA, check_extra
+from .evaluation import EVERY_EXTRA, check_extra
 from .metrics import AverageMeter
 
 
@@ -107,7 +107,7 @@ class FullyCNNTrainer(object):
         self.device = int(device)
         self.sdr_score = AverageMeter()            # trainer.py:34; valid() adds to it and never resets it, as there
         self.stoi_score = AverageMeter()           # trainer.py:33; filled by valid(..., stoi=True)
-        self.extra_scores = {name: AverageMeter() for name in ALL_EXTRA}    # filled by valid(..., extra=(names))
+        self.extra_scores = {name: AverageMeter() for name in EVERY_EXTRA}    # filled by valid(..., extra=(names))
         self.train_loss = AverageMeter()           # trainer.py:29-31; train() updates the three
         self.data_time = AverageMeter()
         self.batch_time = AverageMeter()
@@ -320,7 +320,7 @@ class FullyCNNTrainer(object):
         every utterance's SDR into self.sdr_score; prints -- and logs, given a logger -- the reference's line with its
         SDR field and returns the average.  With stoi=True every utterance's STOI goes into self.stoi_score as well and
         the line gains the reference's st_score field, in the reference's order.  extra: names from
-        evaluation.EXTRA_METRICS + evaluation.SPECTRAL_METRICS + evaluation.PROJECTION_METRICS; every utterance's score goes into self.extra_scores[name], and one further line with their
+        evaluation.EXTRA_METRICS + evaluation.SPECTRAL_METRICS + evaluation.PROJECTION_METRICS + evaluation.SEPM_METRICS; every utterance's score goes into self.extra_scores[name], and one further line with their
         averages is printed and logged after the reference's.  rebuild: "reference" or "ola" (engine.evaluate_pcm).
         The framing is valid_loader.dataset.framing where there is one, else the default.
         verbose=False computes and returns the same without printing (the ranks of dist.DataParallelTrainer other than 0).

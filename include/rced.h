@@ -378,6 +378,28 @@ int rced_llr(const float* ref_dev, int ref_stride, const float* est_dev, int est
 int rced_wss(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N,
              int sample_rate, double* out_dev, double* frames_out, int frames_stride, int* nf_out, int device, void* stream);
 
+/* The frequency-weighted segmental SNR (fwSNRseg) and the cepstral distance (CD) per utterance over its own length L: the two
+ * objective measures of Hu and Loizou (2008) left beside rced_seg_snr, rced_llr and rced_wss (PESQ is not computed).  Both are
+ * built as DESIGN.md 3.4c writes them; parity with pysepm or the MATLAB originals is unpinned.  Framing, window, rates,
+ * pointers, strides, lengths_dev, frames_out, frames_stride, nf_out and their checks as in rced_llr / rced_wss; frames_out
+ * receives every frame's value after its limits.
+ *   fwSNRseg: |DFT_nfft(w frame)| on all nb = nfft / 2 bins in fp64 on the matrix pipe (WSS's coefficient stream; at 16 kHz
+ * a second pass over bins 256 .. 511), each signal's magnitudes divided by their sum over the nb bins (added in bin order),
+ * the 25 critical-band filters of WSS on those, Wt = E_x^0.2, snr = 10 log10(E_x^2 / max((E_x - E_y)^2, eps)) limited to
+ * [-10, 35], frame value sum(Wt snr) / sum(Wt) in band order; the score is the plain mean over the frames in one fixed order,
+ * nan for nf = 0.  A frame whose magnitudes sum to zero is 0 / 0 = nan, and so is its utterance.  Three launches.
+ *   CD: rced_llr's lags and Levinson-Durbin at order `order`, 1 .. 16 (anything else is RCED_ERR_ARG; LLR's own order is 10
+ * below 10 kHz, else 16); cepstra c[1] = -A[1], c[k] = -(A[k] + (sum_{i < k} i c[i] A[k - i]) / k); frame value
+ * (10 / ln 10) sqrt(2 sum_k (cx[k] - cy[k])^2) limited to [0, 10]; the score is rced_llr's aggregation, the mean of the
+ * k = (95 nf + 50) / 100 smallest frame values.  Four launches.
+ *   A workspace of its own each per (device, stream), growing only; the tables are rced_wss's, plus the second pass's
+ * coefficients, uploaded once per device.  The invariants stated above hold.  Asynchronous. */
+int rced_fwseg(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N,
+               int sample_rate, double* out_dev, double* frames_out, int frames_stride, int* nf_out, int device, void* stream);
+int rced_cepd(const float* ref_dev, int ref_stride, const float* est_dev, int est_stride, const int* lengths_dev, int N,
+              int sample_rate, int order, double* out_dev, double* frames_out, int frames_stride, int* nf_out,
+              int device, void* stream);
+
 /* The signal-to-distortion ratio of BSS Eval (Vincent, Gribonval, Fevotte 2006) for a single source, per utterance over
  * its own length L: the estimate is first projected onto the span of the clean signal delayed by 0 .. F - 1 samples,
  * F = filter_length, 1 <= F <= 512 (anything else is RCED_ERR_ARG), so a fixed linear filtering or a delay of the estimate

@@ -9,7 +9,8 @@ The further scores -- legs `estoi`, `stoi+estoi` (one rced_stoi_ex call for both
 beside their restatements (tests/estoi_np.py, tests/td_metrics_np.py) on the same 16 processes, with the ratio of `stoi+estoi`
 to rced_stoi alone in this process; `python tools/time_eval.py ext` times those alone.
 LLR and WSS (rced_llr, rced_wss) -- legs `llr`, `wss` -- run at the same shape beside their restatement (tests/sepm_np.py) on the
-same 16 processes; `python tools/time_eval.py sepm` times those alone.
+same 16 processes, and so do fwSNRseg and CD (rced_fwseg, rced_cepd; legs `fw_seg_snr`, `cd`; tests/sepm2_np.py);
+`python tools/time_eval.py sepm` times those four alone.
 The SDR of BSS Eval (rced_bss_sdr, 512 taps) -- leg `bss_sdr` -- runs at the same shape beside its restatement (tests/bsseval_np.py,
 the normal equations) on the same 16 processes; `python tools/time_eval.py bss` times it alone, with WSS and STOI from the same run.
 Prints one JSON line."""
@@ -51,9 +52,9 @@ HOST_PROCS = 16
 # leg -> (module under tests/, function, arguments after the pair): the float64 restatement a device leg is set beside
 RESTATEMENTS = {"stoi": ("stoi_np", "stoi", (8000,)), "estoi": ("estoi_np", "estoi", (8000,)), "si_sdr": ("td_metrics_np", "si_sdr", ()),
                 "seg_snr": ("td_metrics_np", "seg_snr", (8000,)), "llr": ("sepm_np", "llr", (8000,)), "wss": ("sepm_np", "wss", (8000,)),
-                "bss_sdr": ("bsseval_np", "bss_sdr", (512,))}
+                "bss_sdr": ("bsseval_np", "bss_sdr", (512,)), "fw_seg_snr": ("sepm2_np", "fwseg", (8000,)), "cd": ("sepm2_np", "cd", (8000,))}
 # command-line leg -> the restatements it runs; no leg: all of them
-HOST_LEGS = {"stoi": ("stoi",), "bss": ("bss_sdr",), "ext": ("estoi", "si_sdr", "seg_snr"), "sepm": ("llr", "wss")}
+HOST_LEGS = {"stoi": ("stoi",), "bss": ("bss_sdr",), "ext": ("estoi", "si_sdr", "seg_snr"), "sepm": ("llr", "wss", "fw_seg_snr", "cd")}
 
 
 def _host_score(job):
@@ -104,8 +105,9 @@ def ext_timings(speech, mix, host):
 
 
 def sepm_timings(speech, mix, host):
-    """LLR and WSS, each beside its restatement's wall time."""
-    out = {"llr": timed_us(lambda: audio.llr_batch(speech, mix)), "wss": timed_us(lambda: audio.wss_batch(speech, mix))}
+    """LLR, WSS, fwSNRseg and CD, each beside its restatement's wall time."""
+    out = {"llr": timed_us(lambda: audio.llr_batch(speech, mix)), "wss": timed_us(lambda: audio.wss_batch(speech, mix)),
+           "fw_seg_snr": timed_us(lambda: audio.fw_seg_snr_batch(speech, mix)), "cd": timed_us(lambda: audio.cep_dist_batch(speech, mix))}
     return beside(out, host, HOST_LEGS["sepm"])
 
 
