@@ -117,6 +117,7 @@ SYMBOLS = {
     "rced_train_sync_reduce": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_size_t, _vp, _vp]),
     "rced_train_copy_variables": (ctypes.c_int, [_vp, _vp, _vp]),
     "rced_train_global_step": (ctypes.c_longlong, [_vp]),
+    "rced_train_grid_stats": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "rced_train_get_variables": (ctypes.c_int, [_vp, _c_float_p, ctypes.c_size_t]),
     "rced_train_get_gradients": (ctypes.c_int, [_vp, _c_float_p, ctypes.c_size_t]),
     "rced_train_get_state": (ctypes.c_int, [_vp, _c_float_p, _c_float_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_longlong)]),

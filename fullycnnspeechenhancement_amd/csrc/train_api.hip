@@ -40,7 +40,12 @@ struct TrainPass;   // one run of the step's layer loops (below); the synchronis
 }  // namespace
 
 struct rced_trainer {
-  int variant = 0, device = 0, batch_size = 1, num_cus = 256;
+  int variant = 0, device = 0, batch_size = 1;
+  // what sizes the persistent grids: the device's CUs and RCED_TRAIN_MAX_GRID=n (a test knob, read at create: no tile-walking
+  // launcher gets more than n workgroups, so a small batch walks several tiles per workgroup; 0 = no cap), with the record of
+  // what the last step's launchers used (rced_train_grid_stats)
+  rced::tmd::GridSeen grid_seen{};
+  rced::tmd::Cus cus{256, 0, &grid_seen};
   // The MFMA kernels stage channel pairs, so odd channel counts (R-CED V2: 15, 19, 21, 23, 25) are trained in an
   // even-padded internal layout: `inet` = the net with every hidden cout rounded up to even.  A phantom channel has
   // zero kernel / bias / gamma / beta, so it is 0 after conv, BatchNorm and ReLU, contributes nothing downstream,
@@ -181,7 +186,7 @@ int rced_train_create(int variant, const float* blob, size_t n_floats, int batch
   t->xvars = n_floats;
   {
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess) t->num_cus = prop.multiProcessorCount;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess) t->cus.n = prop.multiProcessorCount;
     auto env = [](const char* name, bool* v) { if (const char* e = getenv(name)) *v = atoi(e) != 0; };
     env("RCED_TRAIN_MFMA", &t->sw.mfma);
     env("RCED_TRAIN_FUSE_ACT", &t->sw.fuse_act);
@@ -190,6 +195,7 @@ int rced_train_create(int variant, const float* blob, size_t n_floats, int batch
     env("RCED_TRAIN_FUSE_BWD", &t->sw.fuse_bwd);
     env("RCED_TRAIN_X6", &t->sw.x6);
     env("RCED_TRAIN_DET", &t->det);
+    if (const char* e = getenv("RCED_TRAIN_MAX_GRID")) t->cus.cap = std::max(0, atoi(e));
   }
   const NetSpec* xnet = net;     // the reference's layout (what crosses the ABI)
   t->inet = *xnet;
@@ -328,6 +334,13 @@ int rced_train_create(int variant, const float* blob, size_t n_floats, int batch
 void rced_train_destroy(rced_trainer* t) { delete t; }
 
 long long rced_train_global_step(rced_trainer* t) { return t ? t->global_step : -1; }
+
+int rced_train_grid_stats(rced_trainer* t, int* max_grid, int* max_tiles_per_workgroup) {
+  if (!t || !max_grid || !max_tiles_per_workgroup) return rced_fail(RCED_ERR_ARG, "rced_train_grid_stats: NULL argument");
+  *max_grid = t->grid_seen.max_grid;
+  *max_tiles_per_workgroup = t->grid_seen.max_walk;
+  return RCED_OK;
+}
 
 namespace {
 // What an entry point does first: `Enter in(t, "rced_train_..."); if (in.rc) return in.rc;`.  The trainer is not null; no
@@ -526,7 +539,7 @@ struct TrainPass {
     if (int rc = ensure_acts(t, P)) return rc;
     if (t->det && !forward_only && !t->wpart) {
       // Sized BEFORE the forward for the most any wgrad launcher can ask for: slices = workgroups (CUs x at most 4 resident per
-      // CU) x 8 waves x 2 pixel parities, slice stride = the net's largest kernel + bias.  A failure to allocate is therefore
+      // CU, or the cap on the grids) x 8 waves x 2 pixel parities, slice stride = the net's largest kernel + bias.  A failure to allocate is therefore
       // reported here, before this step has launched anything; growing inside tmd::wg_launch remains as a last resort (it
       // synchronises, and if it fails the step returns RCED_ERR_ALLOC below).
       size_t maxps = 0;
@@ -535,11 +548,13 @@ struct TrainPass {
         const int cin = s.src == 0 ? 1 : (net.layer[s.src - 1].cout + 1) & ~1, cout = (s.cout + 1) & ~1;   // (R-CED V2: even-padded)
         maxps = std::max(maxps, (size_t)s.kh * s.kw * cin * cout + cout + 4);
       }
-      t->wpart_floats = (size_t)t->num_cus * 4 * 8 * 2 * maxps;
+      const int max_wgs = t->cus.cap > 0 ? std::min(t->cus.n * 4, t->cus.cap) : t->cus.n * 4;
+      t->wpart_floats = (size_t)max_wgs * 8 * 2 * maxps;
       HIP_TRY(hipMalloc(&t->wpart, t->wpart_floats * sizeof(float)));
     }
     // deterministic weight gradients: the wgrad launchers write slices into t->wpart; otherwise fp32 atomics
     t->wg_error = 0;
+    t->grid_seen = {};
     wd = t->det ? WgDet{&t->wpart, &t->wpart_floats, &t->wg_error} : WgDet{};
     for (int l = 0; l < kMaxLayers; ++l) tiny[l] = t->tiny_host[l];     // as of the end of the previous step (it synchronised)
     src_parts.assign(L, 0);
@@ -600,15 +615,15 @@ struct TrainPass {
     int stat_parts = 0;   // the (sum z, sum z^2) records the conv kernel left in t->part (Stats::Conv)
     switch (pl.fwd) {
       case plan::Fwd::X6:
-        stat_parts = rced::tmd::tm_conv_x6(f.cin, s.kw, s.cout, stats, conv_in(s.src), t->pk_fwd_x6[l], t->z[l], frames, t->num_cus,
+        stat_parts = rced::tmd::tm_conv_x6(f.cin, s.kw, s.cout, stats, conv_in(s.src), t->pk_fwd_x6[l], t->z[l], frames, t->cus,
                                            t->part, xform_of(s.src, &xa_tmp), st);
         break;
       case plan::Fwd::Mfma:
-        stat_parts = tm_conv(true, f.cin, s.kw, s.cout, false, stats, conv_in(s.src), t->pk_fwd[l], t->z[l], frames, t->num_cus, t->part,
+        stat_parts = tm_conv(true, f.cin, s.kw, s.cout, false, stats, conv_in(s.src), t->pk_fwd[l], t->z[l], frames, t->cus, t->part,
                              xform_of(s.src, &xa_tmp), nullptr, st);
         break;
       case plan::Fwd::First:
-        stat_parts = first_fwd(s, x_dev, t->params + f.kernel, t->params + f.bias, t->pk_first, t->z[l], frames, T, t->num_cus, stats,
+        stat_parts = first_fwd(s, x_dev, t->params + f.kernel, t->params + f.bias, t->pk_first, t->z[l], frames, T, t->cus, stats,
                                t->part, st);
         break;
       case plan::Fwd::Output:
@@ -772,14 +787,14 @@ struct TrainPass {
       case plan::Wgrad::Fused:   // with the dgrad, below
         break;
       case plan::Wgrad::Mfma:
-        launched = tm_wgrad(wd, f.cin, s.kw, s.cout, conv_in(s.src), dsrc, t->grads + f.kernel, t->grads + f.bias, frames, t->num_cus,
+        launched = tm_wgrad(wd, f.cin, s.kw, s.cout, conv_in(s.src), dsrc, t->grads + f.kernel, t->grads + f.bias, frames, t->cus,
                             xform_of(s.src, &xa_tmp), ba, st);
         break;
       case plan::Wgrad::First:
-        launched = first_wgrad(wd, s, x_dev, dsrc, t->grads + f.kernel, t->grads + f.bias, frames, T, t->num_cus, ba, st);
+        launched = first_wgrad(wd, s, x_dev, dsrc, t->grads + f.kernel, t->grads + f.bias, frames, T, t->cus, ba, st);
         break;
       case plan::Wgrad::Output:
-        launched = fin_wgrad(wd, f.cin, tensor(s.src), dsrc, t->grads + f.kernel, t->grads + f.bias, frames, t->num_cus, st);
+        launched = fin_wgrad(wd, f.cin, tensor(s.src), dsrc, t->grads + f.kernel, t->grads + f.bias, frames, t->cus, st);
         break;
       case plan::Wgrad::Generic: {
         if (int rc = reduce_channels(t, t->D, t->D, nullptr, nullptr, P, s.cout, t->sums, st)) return rc;
@@ -804,18 +819,18 @@ struct TrainPass {
         break;
       case plan::Dgrad::Fused:
         grid = tm_bwd_fused(wd, f.cin, s.kw, s.cout, pl.src_sums, conv_in(s.src), dsrc, t->pk_bwd_x6[l] ? t->pk_bwd_x6[l] : t->pk_bwd[l],
-                            t->G[s.src], t->grads + f.kernel, t->grads + f.bias, frames, t->num_cus, t->part, xform_of(s.src, &xa_tmp), ba, st);
+                            t->G[s.src], t->grads + f.kernel, t->grads + f.bias, frames, t->cus, t->part, xform_of(s.src, &xa_tmp), ba, st);
         break;
       case plan::Dgrad::Output:
         grid = fin_dgrad(f.cin, dsrc, t->params + f.kernel, t->pk_fin_bwd, t->G[s.src], frames, st, t->sw.x6);
         break;
       case plan::Dgrad::MfmaSums:
       case plan::Dgrad::MfmaAccSums:
-        grid = tm_conv(false, s.cout, s.kw, f.cin, pl.accumulate, false, dsrc, t->pk_bwd[l], t->G[s.src], frames, t->num_cus, t->part,
+        grid = tm_conv(false, s.cout, s.kw, f.cin, pl.accumulate, false, dsrc, t->pk_bwd[l], t->G[s.src], frames, t->cus, t->part,
                        nullptr, ba, st, &sa_p, acc_from);
         break;
       case plan::Dgrad::Mfma:
-        grid = tm_conv(false, s.cout, s.kw, f.cin, pl.accumulate, false, dsrc, t->pk_bwd[l], t->G[s.src], frames, t->num_cus, nullptr,
+        grid = tm_conv(false, s.cout, s.kw, f.cin, pl.accumulate, false, dsrc, t->pk_bwd[l], t->G[s.src], frames, t->cus, nullptr,
                        nullptr, ba, st, nullptr, acc_from);
         break;
       case plan::Dgrad::Generic:

@@ -13,14 +13,15 @@
 
 // train_mfma_v2.hip
 int rced_tm_conv_v2(bool fwd, int cin, int taps, int cout, bool accum, bool stats, const float* in, const float* packet,
-                    float* out, int frames, int cus, double* part, const rced::tmm::XformArgs* xa,
+                    float* out, int frames, const rced::tmd::Cus& cus, double* part, const rced::tmm::XformArgs* xa,
                     const rced::tmm::BnBwdArgs* ba, hipStream_t st, const rced::tmm::SumArgs* sa, const float* acc_from);
-int rced_tm_wgrad_v2(const rced::tmd::WgDet& wd, int cin, int taps, int cout, const float* x, const float* dz, float* dW, float* dbias, int frames, int cus,
+int rced_tm_wgrad_v2(const rced::tmd::WgDet& wd, int cin, int taps, int cout, const float* x, const float* dz, float* dW, float* dbias, int frames, const rced::tmd::Cus& cus,
                      const rced::tmm::XformArgs* xa, const rced::tmm::BnBwdArgs* ba, hipStream_t st);
 
 namespace rced {
 namespace {
 using tmd::allow_lds;
+using tmd::Cus;
 using tmd::kPairGrid;
 using tmd::WgDet;
 
@@ -30,13 +31,13 @@ RCED_TM_DEFINE_DISPATCH(_main, RCED_TM_FWD, RCED_TM_BWD)
 
 // Returns the grid size (= number of partial-sum records when stats), 0 if no kernel was built for the request.
 int tm_conv(bool fwd, int cin, int taps, int cout, bool accum, bool stats, const float* in, const float* packet, float* out,
-            int frames, int cus, double* part, const tmm::XformArgs* xa, const tmm::BnBwdArgs* ba, hipStream_t st,
+            int frames, const Cus& cus, double* part, const tmm::XformArgs* xa, const tmm::BnBwdArgs* ba, hipStream_t st,
             const tmm::SumArgs* sa = nullptr, const float* acc_from = nullptr) {
   if (rced::tms::tm_has_main(fwd, cin, taps, cout))
     return tm_conv_main(fwd, cin, taps, cout, accum, stats, in, packet, out, frames, cus, part, xa, ba, st, sa, acc_from);
   return rced_tm_conv_v2(fwd, cin, taps, cout, accum, stats, in, packet, out, frames, cus, part, xa, ba, st, sa, acc_from);
 }
-int tm_wgrad(const WgDet& wd, int cin, int taps, int cout, const float* x, const float* dz, float* dW, float* dbias, int frames, int cus,
+int tm_wgrad(const WgDet& wd, int cin, int taps, int cout, const float* x, const float* dz, float* dW, float* dbias, int frames, const Cus& cus,
              const tmm::XformArgs* xa, const tmm::BnBwdArgs* ba, hipStream_t st) {
   if (rced::tms::tm_has_main(true, cin, taps, cout)) return tm_wgrad_main(wd, cin, taps, cout, x, dz, dW, dbias, frames, cus, xa, ba, st);
   return rced_tm_wgrad_v2(wd, cin, taps, cout, x, dz, dW, dbias, frames, cus, xa, ba, st);
@@ -45,7 +46,7 @@ int tm_wgrad(const WgDet& wd, int cin, int taps, int cout, const float* x, const
 // ---- wgrad + dgrad of a layer in one kernel (tmm::bwd_fused_mfma): RCED_TM_FUSED ----
 // (x virtual, sums) must be (1, 1) or (0, 0).  Returns the grid size, 0 if no kernel was built for the request.
 int tm_bwd_fused(const WgDet& wd, int cin, int taps, int cout, bool xf_sums, const float* x, const float* du, const float* packet, float* dx,
-                 float* dW, float* dbias, int frames, int cus, double* part, const tmm::XformArgs* xa, const tmm::BnBwdArgs* ba,
+                 float* dW, float* dbias, int frames, const Cus& cus, double* part, const tmm::XformArgs* xa, const tmm::BnBwdArgs* ba,
                  hipStream_t st) {
   const tmm::XformArgs nx{nullptr, nullptr, nullptr, nullptr};
   if (!ba || (xf_sums && !xa)) return 0;
@@ -60,7 +61,7 @@ int tm_bwd_fused(const WgDet& wd, int cin, int taps, int cout, bool xf_sums, con
 
 // ---- first layer (8 x kw on the 1-channel input, RCED_FIRST): MFMA forward and wgrad (kernels_train_mfma.h) ----
 template <int KW, int COUT>
-int first_wgrad_launch(const WgDet& wd, const float* x, const float* dz, float* dW, float* dbias, int frames, int T, int cus,
+int first_wgrad_launch(const WgDet& wd, const float* x, const float* dz, float* dW, float* dbias, int frames, int T, const Cus& cus,
                        const tmm::BnBwdArgs* ba, hipStream_t st) {
   constexpr int RS = 129 + KW - 1;
   const size_t lds = (((size_t)(tmm::kTF * 8 * RS + 32 + 3) / 4) * 4 + (size_t)(tmm::kTF * tmm::first_wgrad_fs(KW, COUT) + 4) * 32 + 4 * COUT) * sizeof(float);
@@ -71,7 +72,7 @@ int first_wgrad_launch(const WgDet& wd, const float* x, const float* dz, float* 
   allow_lds(reinterpret_cast<const void*>(tmm::first_wgrad<KW, COUT, true>), lds, attr_t);
   allow_lds(reinterpret_cast<const void*>(tmm::first_wgrad<KW, COUT, false>), lds, attr_f);
   // persistent grid = what is resident (it was cus * 3 with two workgroups per CU resident: half of the second round idle)
-  const dim3 grid(std::min(ntiles, ba ? rced::tmd::resident_grid(reinterpret_cast<const void*>(tmm::first_wgrad<KW, COUT, true>), lds, cus, occ_t)
+  const dim3 grid(cus.grid(ntiles, ba ? rced::tmd::resident_grid(reinterpret_cast<const void*>(tmm::first_wgrad<KW, COUT, true>), lds, cus, occ_t)
                                       : rced::tmd::resident_grid(reinterpret_cast<const void*>(tmm::first_wgrad<KW, COUT, false>), lds, cus, occ_f)));
   rced::tmd::wg_launch(wd, [&](float* dw, float* db, unsigned ps) {
     if (ba) hipLaunchKernelGGL((tmm::first_wgrad<KW, COUT, true>), grid, dim3(tmm::kThreads), lds, st, x, dz, dw, db, frames, T, *ba, ps);
@@ -79,7 +80,7 @@ int first_wgrad_launch(const WgDet& wd, const float* x, const float* dz, float* 
   }, (int)grid.x * tmm::kWaves, 8 * KW * COUT, COUT, dW, dbias, st);
   return 1;
 }
-int first_wgrad(const WgDet& wd, const LayerSpec& s, const float* x, const float* dz, float* dW, float* dbias, int frames, int T, int cus,
+int first_wgrad(const WgDet& wd, const LayerSpec& s, const float* x, const float* dz, float* dW, float* dbias, int frames, int T, const Cus& cus,
                 const tmm::BnBwdArgs* ba, hipStream_t st) {
 #define X(KW, CO) if (s.kw == KW && s.cout == CO) return first_wgrad_launch<KW, CO>(wd, x, dz, dW, dbias, frames, T, cus, ba, st);
   RCED_FIRST(X)
@@ -88,7 +89,7 @@ int first_wgrad(const WgDet& wd, const LayerSpec& s, const float* x, const float
 }
 
 template <int KW, int COUT>
-int first_fwd_launch(const float* x, const float* w, const float* bias, float* packet, float* z, int frames, int T, int cus,
+int first_fwd_launch(const float* x, const float* w, const float* bias, float* packet, float* z, int frames, int T, const Cus& cus,
                      bool stats, double* part, hipStream_t st) {
   constexpr int MT = tmm::tm_rem(COUT) ? 1 : (COUT + 15) / 16, data = 2 * KW * MT * 64 + (tmm::tm_rem(COUT) ? 32 * 64 : 0), RS = 129 + KW - 1;
   hipLaunchKernelGGL(tmm::pack_first, dim3((data + 32 + 255) / 256), dim3(256), 0, st, w, bias, KW, COUT, packet);
@@ -97,14 +98,14 @@ int first_fwd_launch(const float* x, const float* w, const float* bias, float* p
   static int occ_s = 0, occ_n = 0;
   const int res = stats ? rced::tmd::resident_grid(reinterpret_cast<const void*>(tmm::first_fwd<KW, COUT, true>), lds, cus, occ_s)
                         : rced::tmd::resident_grid(reinterpret_cast<const void*>(tmm::first_fwd<KW, COUT, false>), lds, cus, occ_n);
-  const int grid = std::min(ntiles, std::min(res, kPairGrid));
+  const int grid = cus.grid(ntiles, std::min(res, kPairGrid));
   if (stats) hipLaunchKernelGGL((tmm::first_fwd<KW, COUT, true>), dim3(grid), dim3(tmm::kThreads), lds, st, x, (const float*)packet, z, frames, T, part);
   else hipLaunchKernelGGL((tmm::first_fwd<KW, COUT, false>), dim3(grid), dim3(tmm::kThreads), lds, st, x, (const float*)packet, z, frames, T, part);
   return grid;
 }
 // returns the grid size (= partial-sum records when stats)
 int first_fwd(const LayerSpec& s, const float* x, const float* w, const float* bias, float* packet, float* z, int frames, int T,
-              int cus, bool stats, double* part, hipStream_t st) {
+              const Cus& cus, bool stats, double* part, hipStream_t st) {
 #define X(KW, CO) if (s.kw == KW && s.cout == CO) return first_fwd_launch<KW, CO>(x, w, bias, packet, z, frames, T, cus, stats, part, st);
   RCED_FIRST(X)
 #undef X
@@ -180,8 +181,8 @@ int fin_dgrad(int ch, const float* dz, const float* w, float* pack, float* dx, i
 #undef X
   return 1;
 }
-int fin_wgrad(const WgDet& wd, int ch, const float* x, const float* dz, float* dW, float* dbias, int frames, int cus, hipStream_t st) {
-  const dim3 grid(std::min((frames + tmm::kWaves - 1) / tmm::kWaves, cus * 2));
+int fin_wgrad(const WgDet& wd, int ch, const float* x, const float* dz, float* dW, float* dbias, int frames, const Cus& cus, hipStream_t st) {
+  const dim3 grid(cus.grid((frames + tmm::kWaves - 1) / tmm::kWaves, cus.n * 2));   // (units: rounds of kWaves frames, one per wave)
 #define X(CH)                                                                                                              \
   if (ch == CH)                                                                                                            \
     rced::tmd::wg_launch(wd, [&](float* dw, float* db, unsigned ps) {                                                      \

@@ -16,6 +16,26 @@ namespace tmd {
 
 constexpr int kPairGrid = 2048;     // workgroups of the channel-aligned elementwise kernels (and their partial sums)
 
+// What sizes a persistent grid, handed to every tile-walking launcher in place of the bare CU count: the device's CUs, the
+// trainer's cap on the workgroup count (RCED_TRAIN_MAX_GRID, a test knob: 0 = none; small batches then walk several tiles
+// per workgroup), and the trainer's record of what the step's launchers made of it (rced_train_grid_stats).
+struct GridSeen { int max_grid = 0, max_walk = 0; };   // over a step's tile-walking launches: the largest grid, the largest ceil(units / grid)
+struct Cus {
+  int n = 256;
+  int cap = 0;
+  GridSeen* seen = nullptr;
+  // the grid of a launcher that walks `units` (tiles; final_wgrad: rounds of its waves) with at most `resident` workgroups
+  int grid(int units, int resident) const {
+    int g = std::max(1, std::min(units, resident));
+    if (cap > 0) g = std::min(g, cap);
+    if (seen) {
+      seen->max_grid = std::max(seen->max_grid, g);
+      seen->max_walk = std::max(seen->max_walk, (units + g - 1) / g);
+    }
+    return g;
+  }
+};
+
 // Deterministic weight gradients (default): the wgrad kernels write per-wave slices into this buffer instead of adding to
 // dW with fp32 atomics, and tmm::wg_reduce sums the slices in a fixed order.  The training step hands every wgrad launcher
 // its trainer's buffer; part == nullptr selects atomics.
@@ -70,14 +90,14 @@ inline void allow_lds(const void* kernel, size_t lds, unsigned long long& done) 
 
 // Persistent grids are sized from the occupancy the runtime reports for the kernel (registers + LDS): cus x resident
 // workgroups per CU, so every workgroup is resident from the start and walks the same number of tiles.
-inline int resident_grid(const void* kernel, size_t lds, int cus, int& occ_cache, int threads = tmm::kThreads) {
+inline int resident_grid(const void* kernel, size_t lds, const Cus& cus, int& occ_cache, int threads = tmm::kThreads) {
   std::lock_guard<std::mutex> lock(g_launch_cache_mu);
   if (occ_cache <= 0) {
     int occ = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, threads, lds) != hipSuccess || occ < 1) occ = 1;
     occ_cache = occ;
   }
-  return cus * occ_cache;
+  return cus.n * occ_cache;
 }
 
 constexpr int tm_packet_parities(int cout) { return cout == 8 ? 2 : 1; }   // Geo::kPH
@@ -105,7 +125,7 @@ inline int tm_packet_x6_threads(int cin, int taps, int cout) {     // pack_packe
   return (int)((tm_packet_x6_floats(cin, taps, cout) - 32) / (3 * 4) * 8) + 32;
 }
 template <int CIN, int TAPS, int COUT, bool STATS, int XF>
-int tm_conv_x6_launch1(const float* in, const float* packet, float* out, int frames, int cus, double* part, tmm::XformArgs xa,
+int tm_conv_x6_launch1(const float* in, const float* packet, float* out, int frames, const Cus& cus, double* part, tmm::XformArgs xa,
                        hipStream_t st) {
   const int ntiles = (frames + tmm::kTF - 1) / tmm::kTF;
   const size_t lds = (size_t)(tmm::conv_x6_red_off<CIN, TAPS, COUT, XF>() + (STATS ? tmm::kConvRedFloats : 0)) * sizeof(float);
@@ -113,14 +133,14 @@ int tm_conv_x6_launch1(const float* in, const float* packet, float* out, int fra
   static int occ = 0;
   const void* kfn = reinterpret_cast<const void*>(tmm::conv_x6_fwd<CIN, TAPS, COUT, STATS, XF>);
   allow_lds(kfn, lds, attr);
-  const int grid = std::min(ntiles, std::min(resident_grid(kfn, lds, cus, occ), kPairGrid));
+  const int grid = cus.grid(ntiles, std::min(resident_grid(kfn, lds, cus, occ), kPairGrid));
   hipLaunchKernelGGL((tmm::conv_x6_fwd<CIN, TAPS, COUT, STATS, XF>), dim3(grid), dim3(tmm::kThreads), lds, st, in, packet, out,
                      frames, part, xa);
   return grid;
 }
 // the forward shapes built in this form: RCED_TM_X6_FWD (train_shapes.h).  Returns the grid, 0 if not built.
 using tms::tm_x6_has;
-inline int tm_conv_x6(int cin, int taps, int cout, bool stats, const float* in, const float* packet, float* out, int frames, int cus,
+inline int tm_conv_x6(int cin, int taps, int cout, bool stats, const float* in, const float* packet, float* out, int frames, const Cus& cus,
                       double* part, const tmm::XformArgs* xa, hipStream_t st) {
   const tmm::XformArgs nx{nullptr, nullptr, nullptr, nullptr};
 #define X(CI, TP, CO)                                                                                                              \
@@ -137,7 +157,7 @@ inline int tm_conv_x6(int cin, int taps, int cout, bool stats, const float* in, 
 
 constexpr tmm::SumArgs kNoSums{nullptr, nullptr, nullptr, nullptr, nullptr};
 template <int CIN, int TAPS, int COUT, bool ACCUM, bool STATS, int XF, bool SUMS = false>
-int tm_conv_launch1(const float* in, const float* packet, float* out, int frames, int cus, double* part,
+int tm_conv_launch1(const float* in, const float* packet, float* out, int frames, const Cus& cus, double* part,
                     tmm::XformArgs xa, tmm::BnBwdArgs ba, hipStream_t st, tmm::SumArgs sa = kNoSums,
                     const float* acc_from = nullptr) {
   using G = tmm::Geo<CIN, TAPS, COUT>;
@@ -151,7 +171,7 @@ int tm_conv_launch1(const float* in, const float* packet, float* out, int frames
   static int occ = 0;
   const void* kfn = reinterpret_cast<const void*>(tmm::conv1xk_mfma<CIN, TAPS, COUT, ACCUM, STATS, XF, SUMS>);
   allow_lds(kfn, lds, attr);
-  const int grid = std::min(ntiles, std::min(resident_grid(kfn, lds, cus, occ), kPairGrid));
+  const int grid = cus.grid(ntiles, std::min(resident_grid(kfn, lds, cus, occ), kPairGrid));
   hipLaunchKernelGGL((tmm::conv1xk_mfma<CIN, TAPS, COUT, ACCUM, STATS, XF, SUMS>), dim3(grid), dim3(tmm::kThreads), lds, st, in,
                      packet, out, frames, part, xa, ba, sa, acc_from);
   return grid;
@@ -166,7 +186,7 @@ int tm_conv_launch1(const float* in, const float* packet, float* out, int frames
 // 0 is returned when no such kernel exists for the shape and the caller launches again without sa.
 // acc_from (accum only): the tensor the result is added to, when that is not `out` itself (out = acc_from + conv).
 template <int CIN, int TAPS, int COUT, bool FWD>
-int tm_conv_launch(bool accum, bool stats, const float* in, const float* packet, float* out, int frames, int cus,
+int tm_conv_launch(bool accum, bool stats, const float* in, const float* packet, float* out, int frames, const Cus& cus,
                    double* part, const tmm::XformArgs* xa, const tmm::BnBwdArgs* ba, hipStream_t st,
                    const tmm::SumArgs* sa = nullptr, const float* acc_from = nullptr) {
   const tmm::XformArgs nx{nullptr, nullptr, nullptr, nullptr};
@@ -214,7 +234,7 @@ int tm_conv_launch(bool accum, bool stats, const float* in, const float* packet,
 
 
 template <int CIN, int TAPS, int COUT, bool XF, bool DZF>
-int tm_wgrad_launch1(const WgDet& wd, const float* x, const float* dz, float* dW, float* dbias, int frames, int cus, tmm::XformArgs xa,
+int tm_wgrad_launch1(const WgDet& wd, const float* x, const float* dz, float* dW, float* dbias, int frames, const Cus& cus, tmm::XformArgs xa,
                      tmm::BnBwdArgs ba, hipStream_t st) {
   using G = tmm::Geo<CIN, TAPS, COUT>;
   const int ntiles = (frames + tmm::kTF - 1) / tmm::kTF;
@@ -224,7 +244,7 @@ int tm_wgrad_launch1(const WgDet& wd, const float* x, const float* dz, float* dW
   static int occ = 0;
   const void* kfn = reinterpret_cast<const void*>(tmm::wgrad1xk_mfma<CIN, TAPS, COUT, XF, DZF, PH>);
   allow_lds(kfn, lds, attr);
-  const int grid = std::min(ntiles, resident_grid(kfn, lds, cus, occ));
+  const int grid = cus.grid(ntiles, resident_grid(kfn, lds, cus, occ));
   wg_launch(wd, [&](float* dw, float* db, unsigned ps) {
     hipLaunchKernelGGL((tmm::wgrad1xk_mfma<CIN, TAPS, COUT, XF, DZF, PH>), dim3(grid), dim3(tmm::kThreads), lds, st, x, dz, dw, db,
                        frames, xa, ba, ps);
@@ -233,7 +253,7 @@ int tm_wgrad_launch1(const WgDet& wd, const float* x, const float* dz, float* dW
 }
 // xa: x is the producer's z (see tm_conv); ba: dz is d_u, rebuilt through BatchNorm backward from (d_u, z)
 template <int CIN, int TAPS, int COUT>
-int tm_wgrad_launch(const WgDet& wd, const float* x, const float* dz, float* dW, float* dbias, int frames, int cus, const tmm::XformArgs* xa,
+int tm_wgrad_launch(const WgDet& wd, const float* x, const float* dz, float* dW, float* dbias, int frames, const Cus& cus, const tmm::XformArgs* xa,
                     const tmm::BnBwdArgs* ba, hipStream_t st) {
   const tmm::XformArgs nx{nullptr, nullptr, nullptr, nullptr};
   const tmm::BnBwdArgs nb{nullptr, nullptr, nullptr, nullptr, nullptr, 1.0, nullptr};
@@ -246,7 +266,7 @@ int tm_wgrad_launch(const WgDet& wd, const float* x, const float* dz, float* dW,
 // wgrad + dgrad of one layer in one kernel (tmm::bwd_fused_mfma).  Returns the grid size (= partial-sum records when sums).
 template <int CIN, int TAPS, int COUT, bool XF, bool SUMS>
 int tm_bwd_fused_launch(const WgDet& wd, const float* x, const float* du, const float* packet, float* dx, float* dW, float* dbias, int frames,
-                        int cus, double* part, tmm::XformArgs xa, tmm::BnBwdArgs ba, hipStream_t st) {
+                        const Cus& cus, double* part, tmm::XformArgs xa, tmm::BnBwdArgs ba, hipStream_t st) {
   using B = tmm::BwdGeo<CIN, TAPS, COUT>;
   const int ntiles = (frames + tmm::kTF - 1) / tmm::kTF;
   const size_t lds = (size_t)B::kLdsFloats * sizeof(float);
@@ -254,7 +274,7 @@ int tm_bwd_fused_launch(const WgDet& wd, const float* x, const float* du, const 
   static int occ = 0;
   const void* kfn = reinterpret_cast<const void*>(tmm::bwd_fused_mfma<CIN, TAPS, COUT, XF, SUMS>);
   allow_lds(kfn, lds, attr);
-  const int grid = std::min(ntiles, std::min(resident_grid(kfn, lds, cus, occ, tmm::kBwdThreads), kPairGrid));
+  const int grid = cus.grid(ntiles, std::min(resident_grid(kfn, lds, cus, occ, tmm::kBwdThreads), kPairGrid));
   constexpr int PH = COUT == 8 ? 2 : 1;
   wg_launch(wd, [&](float* dw, float* db, unsigned ps) {
     hipLaunchKernelGGL((tmm::bwd_fused_mfma<CIN, TAPS, COUT, XF, SUMS>), dim3(grid), dim3(tmm::kBwdThreads), lds, st, x, du, packet,
@@ -266,14 +286,14 @@ int tm_bwd_fused_launch(const WgDet& wd, const float* x, const float* du, const 
 // One list-driven dispatcher set per translation unit: TM_FWD / TM_BWD are X-macro lists of (cin, taps, cout) from train_shapes.h.
 #define RCED_TM_DEFINE_DISPATCH(SUFFIX, TM_FWD, TM_BWD)                                                                   \
   int tm_conv##SUFFIX(bool fwd, int cin, int taps, int cout, bool accum, bool stats, const float* in, const float* packet, \
-                      float* out, int frames, int cus, double* part, const tmm::XformArgs* xa, const tmm::BnBwdArgs* ba,    \
+                      float* out, int frames, const rced::tmd::Cus& cus, double* part, const tmm::XformArgs* xa, const tmm::BnBwdArgs* ba, \
                       hipStream_t st, const tmm::SumArgs* sa = nullptr, const float* acc_from = nullptr) {                  \
     TM_FWD(RCED_TM_CONV_FWD_CASE)                                                                                           \
     TM_BWD(RCED_TM_CONV_BWD_CASE)                                                                                           \
     return 0;                                                                                                               \
   }                                                                                                                         \
   int tm_wgrad##SUFFIX(const rced::tmd::WgDet& wd, int cin, int taps, int cout, const float* x, const float* dz, float* dW, float* dbias, int frames,   \
-                       int cus, const tmm::XformArgs* xa, const tmm::BnBwdArgs* ba, hipStream_t st) {                       \
+                       const rced::tmd::Cus& cus, const tmm::XformArgs* xa, const tmm::BnBwdArgs* ba, hipStream_t st) {            \
     TM_FWD(RCED_TM_WGRAD_CASE) /* the forward list: tms::tm_has(true, ...) answers from the same one */                     \
     return 0;                                                                                                               \
   }

@@ -370,6 +370,13 @@ class FullyCNNTrainer(object):
     def global_step(self):
         return int(_lib.load().rced_train_global_step(self._h))
 
+    def grid_stats(self):
+        """(largest grid, largest tiles per workgroup) over the tile-walking launchers of the last pass on the handle
+        (rced_train_grid_stats): what RCED_TRAIN_MAX_GRID made of it.  (0, 0) before the first pass and under RCED_TRAIN_MFMA=0."""
+        grid, walk = ctypes.c_int(), ctypes.c_int()
+        _lib.check(_lib.load().rced_train_grid_stats(self._h, ctypes.byref(grid), ctypes.byref(walk)))
+        return grid.value, walk.value
+
     def _blob(self, fn):
         buf = np.empty(self._blob_n, np.float32)
         _lib.check(fn(self._h, buf.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), buf.size))

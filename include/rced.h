@@ -121,7 +121,9 @@ int rced_reserve(rced_model* m, int N, int T);
  * Options are PER HANDLE.  Environment variables only supply DEFAULTS, read once when a handle is created (rced_create /
  * rced_train_create) and never afterwards: RCED_V3_L2X6, RCED_FINAL_X6, RCED_FINAL_LDS (the options of the
  * same meaning above); for rced_train_create RCED_TRAIN_MFMA=0 (direct-conv kernels only), RCED_TRAIN_FUSE_ACT=0,
- * RCED_TRAIN_FUSE_DZ=0 (materialise activations / dz), RCED_TRAIN_FUSE_SUMS, RCED_TRAIN_FUSE_BWD, RCED_TRAIN_DET, RCED_TRAIN_X6. */
+ * RCED_TRAIN_FUSE_DZ=0 (materialise activations / dz), RCED_TRAIN_FUSE_SUMS, RCED_TRAIN_FUSE_BWD, RCED_TRAIN_DET, RCED_TRAIN_X6,
+ * and the test knob RCED_TRAIN_MAX_GRID=n (n >= 1: no tile-walking training kernel is launched with more than n workgroups, so a
+ * batch of a few frames walks several tiles per workgroup; unset or 0: no cap; see rced_train_grid_stats). */
 int rced_set_option(rced_model* m, const char* key, int value);
 int rced_get_option(rced_model* m, const char* key, int* value);
 
@@ -687,6 +689,12 @@ int rced_train_sync_reduce(rced_trainer* t, const double* gathered_dev, int shar
 int rced_train_copy_variables(rced_trainer* dst, rced_trainer* src, void* stream);
 
 long long rced_train_global_step(rced_trainer* t);
+/* Read-only, no device work: over the tile-walking launchers of the last pass on the handle (step, grad, forward; the
+ * persistent MFMA kernels that walk two-frame tiles, and the output layer's wgrad, whose waves stride over frames),
+ * *max_grid = the largest workgroup count one of them was launched with and *max_tiles_per_workgroup = the largest
+ * ceil(tiles / workgroups), i.e. the longest walk.  Both 0 before the first pass and where no such launcher ran
+ * (RCED_TRAIN_MFMA=0).  What RCED_TRAIN_MAX_GRID made of a step: the tests of the tile walks assert both. */
+int rced_train_grid_stats(rced_trainer* t, int* max_grid, int* max_tiles_per_workgroup);
 /* Current variables / last gradients, in blob order (gradients of moving statistics are 0). */
 int rced_train_get_variables(rced_trainer* t, float* blob_host, size_t n_floats);
 int rced_train_get_gradients(rced_trainer* t, float* blob_host, size_t n_floats);

@@ -24,8 +24,8 @@ def kernels(text):         # name -> (body, {resource: value}): what stands betw
     for raw in text.splitlines():
         line = re.sub(r"\s+", " ", re.split(r";|//", raw)[0]).strip()
         m = re.match(r"(?:[0-9a-f]+ )?<?([A-Za-z_$][\w$.]*)>?:$", line)
-        if line.startswith(".amdgpu_metadata"):
-            name = None
+        if line.startswith(".amdgpu_metadata") or "file format elf64-amdgpu" in line:   # (a library's next code object: its
+            name = None                                                                  # path line is nobody's code)
         elif m and not re.match(r"L\d+$", m.group(1)):
             name, labels = m.group(1), {}
             out.setdefault(name, [[], {}])
