@@ -68,6 +68,8 @@ SYMBOLS = {
                                     ctypes.c_double, _vp, ctypes.c_int, _vp]),
     "rced_gather_pcm": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_longlong, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
                                        ctypes.c_int, _vp]),
+    "rced_convolve": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
+                                     ctypes.c_int, _vp]),
     "rced_resample_length": (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int]),
     "rced_resample_taps": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _c_int_p, _c_int_p, _c_int_p, _c_int_p,
                                           ctypes.POINTER(ctypes.c_double), ctypes.c_size_t]),

@@ -17,7 +17,7 @@ from . import _args, _lib
 from ._args import BINS, FRAME, SAMPLE_RATE, STEP  # noqa: F401
 # what lived here before the file was split by concern: every public name is still handed out as audio.<name>
 from .evaluation import (EXTRA_METRICS, PROJECTION_METRICS, SEPM_METRICS, SPECTRAL_METRICS, SPECTRAL_RATES, STOI_RATES, bss_sdr_batch,  # noqa: F401
-                         cep_dist_batch, fw_seg_snr_batch,
+                         CONV_MAX_TAPS, cep_dist_batch, convolve_batch, fw_seg_snr_batch,
                          denoise_and_score, gains_needed, llr_batch, mix_snr_batch, sdr_batch, seg_snr_batch, seg_snr_window, si_sdr_batch, stoi_batch, wss_batch)
 from .arena import PCM_DTYPES, gather_pcm, resample_arena, resample_batch, resample_length, resample_taps  # noqa: F401
 from .streaming import (STREAM_DELAY, STREAM_FINISH_MAX, STREAM_MAX_HOPS, StreamingDenoiser, StreamingResampler,  # noqa: F401

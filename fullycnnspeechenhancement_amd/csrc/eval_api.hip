@@ -9,6 +9,7 @@
 
 #include "../../include/rced.h"
 #include "kernels_bsseval.h"
+#include "kernels_conv.h"
 #include "kernels_eval.h"
 #include "kernels_sepm.h"
 #include "kernels_stoi.h"
@@ -632,6 +633,31 @@ int rced_gather_pcm(const void* arena_dev, int arena_dtype, long long arena_samp
     LAUNCH(eval::gather_pcm_kernel<true>, grid, block, 0, st, arena_dev, arena_samples, begin_dev, count_dev, L, rows_dev, row_stride);
   else
     LAUNCH(eval::gather_pcm_kernel<false>, grid, block, 0, st, arena_dev, arena_samples, begin_dev, count_dev, L, rows_dev, row_stride);
+  return RCED_OK;
+}
+
+int rced_convolve(const float* x_dev, int x_stride, const int* x_len_dev, const float* h_dev, int h_stride, const int* h_len_dev,
+                  const int* shift_dev, int N, int L, float* y_dev, int y_stride, int device, void* stream) {
+  static_assert(conv::kMaxTaps == RCED_CONV_MAX_TAPS, "the header's bound is the kernel's");
+  if (!x_dev) return rced_fail(RCED_ERR_ARG, "x_dev is a null pointer");
+  if (!h_dev) return rced_fail(RCED_ERR_ARG, "h_dev is a null pointer");
+  if (!y_dev) return rced_fail(RCED_ERR_ARG, "y_dev is a null pointer");
+  if (x_stride < 0) return rced_fail(RCED_ERR_ARG, "x_stride %d is negative", x_stride);
+  if (h_stride < 0) return rced_fail(RCED_ERR_ARG, "h_stride %d is negative", h_stride);
+  if (y_stride < 0) return rced_fail(RCED_ERR_ARG, "y_stride %d is negative", y_stride);
+  if (L < 0) return rced_fail(RCED_ERR_ARG, "L %d is negative", L);
+  if (L > x_stride) return rced_fail(RCED_ERR_ARG, "L %d > x_stride %d", L, x_stride);
+  if (L > y_stride) return rced_fail(RCED_ERR_ARG, "L %d > y_stride %d", L, y_stride);
+  if (L > eval::kMaxLen) return rced_fail(RCED_ERR_ARG, "L: rows longer than 2^30 samples");
+  if (!h_len_dev && h_stride > RCED_CONV_MAX_TAPS)
+    return rced_fail(RCED_ERR_ARG, "h_stride %d > RCED_CONV_MAX_TAPS = %d taps without h_len_dev", h_stride, RCED_CONV_MAX_TAPS);
+  if (N < 0 || N > 65535) return rced_fail(RCED_ERR_ARG, "N = %d outside [0, 65535] rows per call", N);
+  if (N == 0 || L == 0) return RCED_OK;
+  OnDevice on(device, kMaxDevices);
+  if (on.rc) return on.rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  LAUNCH(conv::convolve_kernel, dim3(conv::out_slices(L), N), dim3(conv::kThreads), 0, st, x_dev, x_stride, x_len_dev, h_dev, h_stride,
+         h_len_dev, shift_dev, L, y_dev, y_stride);
   return RCED_OK;
 }
 

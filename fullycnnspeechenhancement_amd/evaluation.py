@@ -1,5 +1,5 @@
 """The evaluation loop's entry points on the device, over the C ABI: SDR, STOI, ESTOI, SI-SDR,
-segmental SNR, LLR, WSS, fwSNRseg, CD and the SDR of BSS Eval per utterance, add_noise's SNR mixing in closed form, and the core of the loop, STFT -> forward -> ISTFT -> scores.  audio.py re-exports
+segmental SNR, LLR, WSS, fwSNRseg, CD and the SDR of BSS Eval per utterance, add_noise's SNR mixing in closed form, the ragged FIR behind the loader's room impulse responses (convolve_batch), and the core of the loop, STFT -> forward -> ISTFT -> scores.  audio.py re-exports
 every public name here."""
 
 import numpy as np
@@ -297,6 +297,70 @@ def mix_snr_batch(speech, noise, snr, speech_lengths=None, noise_lengths=None, s
         _lib.check(_lib.load().rced_mix_snr(speech.data_ptr(), ptr(sdev), n, Ls, noise.data_ptr(), ptr(ndev), Ln, ptr(tdev),
                                             ptr(gdev), n_gains, float(snr), mix.data_ptr(), dev.index, _args.current_stream(dev)))
     return mix
+
+
+CONV_MAX_TAPS = 8192      # rced.h: RCED_CONV_MAX_TAPS
+
+
+def _overlap(a, b):
+    """Whether the memory two tensors' elements span intersects."""
+    def span(t):
+        reach = sum((int(s) - 1) * int(st) for s, st in zip(t.shape, t.stride())) + 1 if t.numel() else 0
+        return t.data_ptr(), t.data_ptr() + reach * t.element_size()
+    (a0, a1), (b0, b1) = span(a), span(b)
+    return a0 < b1 and b0 < a1
+
+
+def convolve_batch(signal, filters, lengths=None, filter_lengths=None, shifts=None, out=None):
+    """A ragged batched FIR on the device (rced_convolve): row n of the result is np.convolve(x_n, h_n)[d_n : d_n + len_n] --
+    the signal's length is kept, tap d_n (a room impulse response's direct path) has zero delay, the tail is dropped --,
+    zeros from len_n to L.  Products and sums in fp64 on the f64 matrix pipe, one rounding at the float32 store; a row's bits
+    do not depend on the batch around it.
+    signal [N, L], filters [N, Kmax] torch.cuda float32 (a 1-D signal is one row, and comes back 1-D; rows may be views of wider
+    buffers); lengths [N] in [0, L] (None = L each), filter_lengths [N] in [0, Kmax] (None = Kmax each; at most CONV_MAX_TAPS =
+    8192), shifts [N] with 0 <= d_n < max(K_n, 1) (None = 0): lists, arrays or tensors, read on the host.
+    out: None, or a contiguous float32 [N, L] device tensor to write into (as mix_snr_batch takes it); it must not overlap
+    signal or filters.  ValueError before any device work for more than 8192 taps, a shift outside its filter, a length
+    outside its row, mismatched N or device.  Returns [N, L] float32 on the device, current stream."""
+    import torch
+    one = hasattr(signal, "dim") and signal.dim() == 1
+    if one:
+        signal = signal[None]
+        filters = filters[None] if hasattr(filters, "dim") and filters.dim() == 1 else filters
+    signal, filters = _args.rows(signal, "signal"), _args.rows(filters, "filters")
+    n, L, kmax = int(signal.shape[0]), int(signal.shape[1]), int(filters.shape[1])
+    if int(filters.shape[0]) != n or filters.device != signal.device:
+        raise ValueError("signal and filters must hold the same number of rows on one device, got %d on %s and %d on %s"
+                         % (n, signal.device, int(filters.shape[0]), filters.device))
+    if kmax < 1:
+        raise ValueError("filters must hold at least one column (filter_lengths may still say 0 taps)")
+    dev = signal.device
+    xl, hl = _args.host_ints(lengths, n, "lengths"), _args.host_ints(filter_lengths, n, "filter_lengths")
+    sh = _args.host_ints(shifts, n, "shifts")
+    if xl is not None and any(v < 0 or v > L for v in xl):
+        raise ValueError("lengths must lie in [0, %d]" % L)
+    if hl is not None and any(v < 0 or v > kmax for v in hl):
+        raise ValueError("filter_lengths must lie in [0, %d]" % kmax)
+    taps = hl if hl is not None else [kmax] * n
+    if any(v > CONV_MAX_TAPS for v in taps):
+        raise ValueError("a filter has %d taps: at most CONV_MAX_TAPS = %d are convolved" % (max(taps), CONV_MAX_TAPS))
+    if sh is not None:
+        for i, (d, k) in enumerate(zip(sh, taps)):
+            if not 0 <= d < max(k, 1):
+                raise ValueError("shifts[%d] = %d outside its filter of %d taps" % (i, d, k))
+    if hl is None and _args.row_stride(filters) != kmax:
+        hl = taps                                         # a strided view: the row's width, not its stride, bounds it
+    y = torch.empty((n, L), dtype=torch.float32, device=dev) if out is None else _args.check_out(out, n, L, dev, torch.float32, exact=True)
+    if out is not None and (_overlap(y, signal) or _overlap(y, filters)):
+        raise ValueError("out must not overlap signal or filters: the convolution does not run in place")
+    if n and L:
+        xdev = torch.tensor(xl, dtype=torch.int32, device=dev) if xl is not None else None
+        hdev = torch.tensor(hl, dtype=torch.int32, device=dev) if hl is not None else None
+        sdev = torch.tensor(sh, dtype=torch.int32, device=dev) if sh is not None else None
+        _lib.check(_lib.load().rced_convolve(signal.data_ptr(), _args.row_stride(signal), ptr(xdev), filters.data_ptr(),
+                                             _args.row_stride(filters), ptr(hdev), ptr(sdev), n, L, y.data_ptr(), L, dev.index,
+                                             _args.current_stream(dev)))
+    return y[0] if one else y
 
 
 def denoise_and_score(forward, mix, clean, lengths, nfft=512, kernels="x6", stoi=False, extra=(), rebuild="reference", framing=None):

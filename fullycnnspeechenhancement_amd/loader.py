@@ -11,7 +11,8 @@ np.random draws (as its loader runs with num_works=1), and every batch is cut ou
 the plan only: which items, which crop offsets, which gains.  Manifests are the reference's json lines; wav files are read
 with the standard library: PCM16, mono, at the corpus rate -- or, with resample=True, PCM16 of any rate and channel count,
 downmixed and resampled on the device while the corpus is uploaded (rced_resample, DESIGN.md 3.4f: what librosa's
-`load_audio` does on the host).  Not built: other sample formats (8 / 24 / 32 bit, flac), drop_last=True, worker
+`load_audio` does on the host).  Beyond the reference: `DataSet(rir=RirCorpus)` convolves the speech with room impulse
+responses on the device (rced_convolve) before the noise is mixed in.  Not built: other sample formats (8 / 24 / 32 bit, flac), drop_last=True, worker
 processes, prefetch.
 """
 
@@ -302,6 +303,111 @@ class Corpus(object):
         return audio.gather_pcm(self.arena, [int(self.index.offsets[i]) + s for i, s in zip(items, starts)], counts, L, out)
 
 
+class RirCorpus(Corpus):
+    """Room impulse responses for DataSet(rir=...) (DESIGN.md 3.4e "Reverberation"): a Corpus of float32 responses at
+    `sample_rate` plus `direct`, a host int64 index per item: the first position of max |h|, the direct path, found once
+    at build.  normalize=True (default) divides each response by h[direct], so the direct path is exactly +1 and a
+    reverberant utterance keeps its dry level and polarity.  A response longer than audio.CONV_MAX_TAPS (8192 taps, 1.02 s
+    at 8 kHz) is cut there, with one warning that names how many were; a direct path behind the cut is found in what is
+    left.  One sample past the indexed items the arena holds 1.0: the one-tap identity the rows that stay dry are
+    convolved with.  index_only=True builds everything but the arena (no GPU needed): enough for DataSet.plan."""
+
+    def __init__(self, index, arena, direct, sample_rate=8000):
+        if arena is not None and int(arena.shape[0]) != index.total + 1:
+            raise ValueError("the arena holds %d samples, the index %d and the identity tap" % (int(arena.shape[0]), index.total))
+        self.index, self.arena = index, arena
+        self.device = arena.device.index if arena is not None else None
+        self.direct = np.asarray(direct, np.int64).reshape(-1)
+        self.sample_rate = int(sample_rate)
+        if self.direct.size != len(index) or ((self.direct < 0) | (self.direct >= index.lengths)).any():
+            raise ValueError("direct must hold one position inside each response")
+
+    @staticmethod
+    def prepare(arrays, normalize=True):
+        """Host only: (responses as float32 arrays, cut and normalised as the class says; direct int64 [count])."""
+        import warnings
+        out, direct, cut = [], [], 0
+        for i, a in enumerate(arrays):
+            h = np.asarray(a)
+            if h.ndim != 1 or h.size < 1:
+                raise ValueError("response %d must be a 1-D array with at least one tap" % i)
+            h = (h.astype(np.float32) / np.float32(32768)) if h.dtype == np.int16 else h.astype(np.float32)
+            if h.size > audio.CONV_MAX_TAPS:
+                h, cut = h[:audio.CONV_MAX_TAPS], cut + 1
+            d = int(np.argmax(np.abs(h)))
+            if not np.isfinite(h).all() or h[d] == 0:
+                raise ValueError("response %d is silent or not finite" % i)
+            if normalize:
+                h = (h.astype(np.float64) / np.float64(h[d])).astype(np.float32)
+            out.append(h)
+            direct.append(d)
+        if cut:
+            warnings.warn("%d of %d impulse responses are longer than %d taps and were truncated" % (cut, len(out), audio.CONV_MAX_TAPS))
+        return out, np.asarray(direct, np.int64)
+
+    @classmethod
+    def from_arrays(cls, arrays, device=0, normalize=True, sample_rate=8000, index_only=False):
+        """int16 arrays are read as value / 32768, float arrays as they are."""
+        import torch
+        rows, direct = cls.prepare(arrays, normalize)
+        index = CorpusIndex([h.size for h in rows])
+        if index_only:
+            return cls(index, None, direct, sample_rate)
+        host = np.concatenate(rows + [np.ones(1, np.float32)])
+        return cls(index, torch.as_tensor(host, device="cuda:%d" % device), direct, sample_rate)
+
+    @classmethod
+    def from_manifest(cls, path, sample_rate, min_duration=0.0, max_duration=float("inf"), key="audio_filepath", device=0,
+                      resample=False, normalize=True, index_only=False):
+        """The wav files a manifest names, read as Corpus.from_manifest reads them (mono PCM16 at sample_rate; with
+        resample=True PCM16 of any rate and channel count, downmixed and resampled on the device to float32).  Responses
+        are short: min_duration defaults to 0."""
+        rows = []
+        for item in read_manifest(path, min_duration, max_duration):
+            if resample:
+                frames, rate = read_wav_frames(item[key])
+                out, lens = audio.resample_batch(frames[None], rate, sample_rate, dtype="float32", device=device)
+                rows.append(out[0, :lens[0]].cpu().numpy())
+            else:
+                rows.append(read_wav(item[key], sample_rate))
+        return cls.from_arrays(rows, device, normalize, sample_rate, index_only)
+
+    def early_taps(self, rid, early_ms):
+        """Taps of the direct path plus early reflections: min(K, direct + round(early_ms * sample_rate / 1000) + 1)."""
+        return min(int(self.lengths[rid]), int(self.direct[rid]) + int(round(early_ms * self.sample_rate / 1000.0)) + 1)
+
+    def filters(self, rids):
+        """The filter rows of a batch: (rows [N, Kmax] float32 on the device, taps [N], shifts [N]); a rid of None is the
+        one-tap identity [1.0] at shift 0."""
+        if self.arena is None:
+            raise ValueError("an index-only RirCorpus builds no batches")
+        begins = [int(self.index.offsets[r]) if r is not None else self.index.total for r in rids]
+        taps = [int(self.index.lengths[r]) if r is not None else 1 for r in rids]
+        return audio.gather_pcm(self.arena, begins, taps), taps, [int(self.direct[r]) if r is not None else 0 for r in rids]
+
+
+def synthetic_rirs(count, sample_rate=8000, rt60=(0.2, 0.8), seed=0):
+    """`count` made-up impulse responses as float32 arrays, for tests, benchmarks and users without recordings -- NOT a room
+    simulator: no geometry, no early-reflection pattern, no frequency-dependent absorption.  Each is zeros over a pre-delay
+    drawn from 0 .. 4 ms, a direct path of exactly 1, then Gaussian noise (sigma 0.3, clipped to +-0.9) under an exponential
+    decay that reaches -60 dB at an RT60 drawn uniformly from `rt60` seconds, where it ends (at most audio.CONV_MAX_TAPS taps).
+    Draws come from np.random.RandomState(seed): reproducible, and the global np.random is not touched."""
+    rs = np.random.RandomState(seed)
+    lo, hi = float(rt60[0]), float(rt60[1])
+    if count < 0 or sample_rate < 1 or not 0 < lo <= hi:
+        raise ValueError("need count >= 0, sample_rate >= 1 and 0 < rt60[0] <= rt60[1]")
+    out = []
+    for _ in range(int(count)):
+        t60 = rs.uniform(lo, hi) * sample_rate                       # samples to -60 dB
+        pre = int(rs.randint(0, int(0.004 * sample_rate) + 1))
+        tail = min(max(int(t60), 1), audio.CONV_MAX_TAPS - pre - 1)
+        h = np.zeros(pre + 1 + tail, np.float64)
+        h[pre] = 1.0
+        h[pre + 1:] = np.clip(0.3 * rs.standard_normal(tail), -0.9, 0.9) * 10.0 ** (-3.0 * np.arange(1, tail + 1) / t60)
+        out.append(h.astype(np.float32))
+    return out
+
+
 class PcmRows(object):
     """The `mix_sig` / `clean_sig` slot of a batch: zero-padded device rows [N, L] and their lengths.  len() and indexing
     give what the reference's lists give, as trimmed device views; engine.evaluate_pcm takes the object as it is."""
@@ -332,9 +438,28 @@ class DataSet(object):
     use_complex=True (the validation set of train.py): the reference then yields complex spectrograms that test() /
     valid() never read (they recompute them from the PCM, engine.py); here the two spectrogram slots are None.
     framing: the audio.Framing the batches' spectrograms are cut with (None: the default); kept as `.framing`, where
-    FullyCNNTester.test and FullyCNNTrainer.valid read it, as the reference reads window_s from the dataset."""
+    FullyCNNTester.test and FullyCNNTrainer.valid read it, as the reference reads window_s from the dataset.
+    rir: a RirCorpus (the reference has no reverberation; DESIGN.md 3.4e "Reverberation").  An item is then convolved, with
+    probability rir_prob, with a response drawn uniformly, aligned on its direct path, before the noise is mixed in at
+    `snr` against the reverberant speech.  target: what the clean half of a batch holds -- "reverberant" (the task stays
+    denoising), "early" (the same speech under the direct path and the reflections of the first early_ms milliseconds:
+    dereverberation) or "dry" (the speech as gathered).  With rir=None nothing changes: the same plans, draws and bits."""
 
-    def __init__(self, clean, noise=None, mix=None, snr=0, use_complex=False, framing=None):
+    TARGETS = ("reverberant", "early", "dry")
+
+    def __init__(self, clean, noise=None, mix=None, snr=0, use_complex=False, framing=None, rir=None, rir_prob=1.0,
+                 target="reverberant", early_ms=50.0):
+        if target not in self.TARGETS:
+            raise ValueError("target must be one of %r, got %r" % (self.TARGETS, target))
+        if not 0.0 <= float(rir_prob) <= 1.0:
+            raise ValueError("rir_prob must lie in [0, 1], got %r" % (rir_prob,))
+        if not float(early_ms) >= 0.0:
+            raise ValueError("early_ms must not be negative, got %r" % (early_ms,))
+        if rir is not None and mix is not None:
+            raise ValueError("rir= needs noise=: a paired corpus (mix=) holds finished mixtures, nothing is convolved or mixed")
+        if rir is not None and len(rir) < 1:
+            raise ValueError("empty rir corpus")
+        self.rir, self.rir_prob, self.target, self.early_ms = rir, float(rir_prob), target, float(early_ms)
         if framing is not None and not isinstance(framing, audio.Framing):
             raise ValueError("framing must be an audio.Framing or None, got %r" % (framing,))
         self.framing = framing
@@ -355,9 +480,16 @@ class DataSet(object):
 
     def plan(self, index):
         """The host half of DataSet.__getitem__ (data_loader.py:109-125): (clean id, noise id, start, gains) with the draws
-        add_noise makes -- or (clean id, None, 0, no gains) in the paired mode.  IndexError where the reference raises it."""
+        add_noise makes -- or (clean id, None, 0, no gains) in the paired mode.  IndexError where the reference raises it.
+        With rir= a fifth element, the response's id or None for an item that stays dry: np.random.uniform(0, 1) and
+        np.random.randint(0, len(rir)) are drawn first, always both and in that order, then add_noise's draws (they depend
+        on lengths only, which reverberation does not change); the item stays dry when the uniform draw is >= rir_prob."""
         if self.noise is not None:
             cid, nid = self.item_list[index], self.noise_list[index]
+            if self.rir is not None:
+                u, rid = np.random.uniform(0, 1), int(np.random.randint(0, len(self.rir)))
+                start, gains = plan_noise(self.clean.lengths[cid], self.noise.lengths[nid])
+                return cid, nid, start, gains, (rid if u < self.rir_prob else None)
             start, gains = plan_noise(self.clean.lengths[cid], self.noise.lengths[nid])
             return cid, nid, start, gains
         return self.item_list[index], None, 0, np.zeros(0, np.float64)
@@ -439,7 +571,10 @@ class DataLoader(object):
     def build(self, plan):
         """One batch on the device from its plan: gather the speech into rows 0..N of a [2N, Ls] buffer, the noise -- only the
         ls samples add_noise keeps where it is longer than the speech, whole where it is shorter -- into [N, <= Ls], mix
-        into rows N..2N, one STFT over the 2N rows.  Paired mode: both halves are gathered."""
+        into rows N..2N, one STFT over the 2N rows.  Paired mode: both halves are gathered.
+        With DataSet(rir=...): the gathered speech is convolved with its rows' responses at shift = direct in one launch (the
+        rows that stay dry take the one-tap identity, which returns them bit for bit), the noise is mixed into the
+        result, and rows 0..N hold what `target` names."""
         import torch
         ds = self.dataset
         n = len(plan)
@@ -455,16 +590,25 @@ class DataLoader(object):
             lm = ls
             width = (max(ls) + 3) // 4 * 4           # every row starts 16-byte aligned
             both = torch.empty((2 * n, width), dtype=torch.float32, device=ds.clean.arena.device)
-            ds.clean.gather(cids, L=width, out=both[:n])
+            if ds.rir is None:
+                speech = ds.clean.gather(cids, L=width, out=both[:n])
+            else:
+                rids = [p[4] for p in plan]
+                filt, taps, shifts = ds.rir.filters(rids)
+                dry = ds.clean.gather(cids, L=width, out=both[:n] if ds.target == "dry" else None)
+                speech = audio.convolve_batch(dry, filt, ls, taps, shifts, out=both[:n] if ds.target == "reverberant" else None)
+                if ds.target == "early":
+                    early = [ds.rir.early_taps(r, ds.early_ms) if r is not None else 1 for r in rids]
+                    audio.convolve_batch(dry, filt, ls, early, shifts, out=both[:n])
             nids, starts, counts, gains = [], [], [], []
-            for (_, nid, start, g), s in zip(plan, ls):
+            for (_, nid, start, g), s in zip([p[:4] for p in plan], ls):
                 ln = int(ds.noise.lengths[nid])
                 nids.append(nid)
                 starts.append(start if ln > s else 0)
                 counts.append(s if ln > s else ln)         # cropped to the speech: it mixes as ln == ls, start 0, no gains
                 gains.append(g)
             noise = ds.noise.gather(nids, starts, counts)
-            audio.mix_snr_batch(both[:n], noise, ds.snr, speech_lengths=ls, noise_lengths=counts, gains=gains, out=both[n:])
+            audio.mix_snr_batch(speech, noise, ds.snr, speech_lengths=ls, noise_lengths=counts, gains=gains, out=both[n:])
         clean_sig, mix_sig = PcmRows(both[:n], ls), PcmRows(both[n:], lm)
         if ds.complex:
             return None, None, mix_sig, clean_sig

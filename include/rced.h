@@ -270,6 +270,29 @@ int rced_gather_pcm(const void* arena_dev, int arena_dtype, long long arena_samp
                     const long long* begin_dev, const int* count_dev, int N, int L,
                     float* rows_dev, int row_stride, int device, void* stream);
 
+#define RCED_CONV_MAX_TAPS 8192
+/* Room impulse responses for the training loader (DESIGN.md 3.4e "Reverberation"): a ragged batched FIR.  Per row n a
+ * signal x_n of len_n samples, a filter h_n of K_n taps and a shift d_n, 0 <= d_n < max(K_n, 1):
+ *   y_n[p] = sum_{k < K_n} h_n[k] x_n[p + d_n - k]   for 0 <= p < len_n,   x_n = 0 outside [0, len_n)
+ *   y_n[p] = 0                                        for len_n <= p < L;   columns L .. y_stride are not touched
+ * -- np.convolve(x, h)[d : d + len]: the output keeps the signal's length, tap d (the direct path) has zero delay, the
+ * tail past the end is dropped; K_n = 0 gives zeros.
+ * x_dev [N, x_stride], h_dev [N, h_stride], y_dev [N, y_stride] float32; x_len_dev, h_len_dev, shift_dev [N] int32 on
+ * the device, or NULL: L each, h_stride each, 0.  A length is clamped into its row (len into [0, L], K into
+ * [0, min(h_stride, RCED_CONV_MAX_TAPS)]) and the shift into [0, max(K - 1, 0)], as the other entries clamp lengths:
+ * nothing is ever read outside a row; the Python side validates and raises.  y must not overlap x or h.
+ * Products and sums in fp64 from the stored fp32 values on the f64 matrix pipe, one rounding at the fp32 store; a
+ * row's summation order depends on positions inside the row and on K_n, d_n, len_n only, so a row's bits do not depend
+ * on N, its row index, the strides or its neighbours, and are the same run to run.  A sample of -0.0 comes back +0.0; a
+ * non-finite sample also reaches, as NaN, the outputs of its own and the neighbouring 16-sample block.  No atomics;
+ * samples past len_n and taps past K_n are never read.  One launch, grid over (output slices, N); asynchronous,
+ * allocates nothing, stream-capturable.
+ * RCED_ERR_ARG before any device work: a null x_dev, h_dev or y_dev, a negative stride or L, L > x_stride, L > y_stride,
+ * h_stride > RCED_CONV_MAX_TAPS with h_len_dev NULL, N outside [0, 65535], L > 2^30.  N = 0 is RCED_OK. */
+int rced_convolve(const float* x_dev, int x_stride, const int* x_len_dev,
+                  const float* h_dev, int h_stride, const int* h_len_dev, const int* shift_dev,
+                  int N, int L, float* y_dev, int y_stride, int device, void* stream);
+
 /* ---- resample: audio at any rate ---------------------------------------------------------------------
  * A band-limited (Kaiser-windowed sinc) interpolator with the parameters of resampy's kaiser_best, evaluated exactly:
  *   ratio = (double)sr_new / sr_orig, s = min(1, ratio), p / q = sr_new / sr_orig in lowest terms,

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Times one batch build of the device loader (loader.DataLoader.build) at BASELINE config-5 scale: 256
 utterances of 65,664 samples (512 frames), cut out of int16 arenas on the device -- gather x2, mix, one STFT over the 2N rows --
+the same build with every utterance under a room impulse response of 4096 taps (DataSet(rir=...): one rced_convolve launch more),
 beside the only way the code offered before: AudioParser.add_noise + parse_audio x2 per utterance (numpy in, numpy out: an
 upload and a download each), on the same signals, and both against the 39.6-39.8 ms training step.
 
@@ -43,6 +44,14 @@ def timed(fn, reps):
 
 build_ms, build_wall_ms = timed(lambda: dl.build(plan), REPS)
 
+# the reverberant build of the same plan: synthetic responses cut to 4096 taps, every row under one (rir_prob = 1)
+RIR_TAPS, RIR_REPS = 4096, 5
+rc = loader.RirCorpus.from_arrays([h[:RIR_TAPS] for h in loader.synthetic_rirs(8, rt60=(0.6, 0.6), seed=5)])
+assert all(int(k) == RIR_TAPS for k in rc.lengths)
+dl_rir = loader.DataLoader(loader.DataSet(cc, noise=nc, snr=0, rir=rc), N)
+plan_rir = [p + (i % len(rc),) for i, p in enumerate(plan)]
+rir_build_ms, rir_build_wall_ms = timed(lambda: dl_rir.build(plan_rir), RIR_REPS)
+
 # the stages alone, on the buffers a build uses
 ids = list(range(N))
 both = torch.empty((2 * N, LS), dtype=torch.float32, device="cuda")
@@ -50,7 +59,10 @@ starts = [p[2] if nc.lengths[p[1]] > LS else 0 for p in plan]
 counts = [LS if nc.lengths[p[1]] > LS else int(nc.lengths[p[1]]) for p in plan]
 gains = [p[3] for p in plan]
 nrows = nc.gather(ids, starts, counts)
+filt, taps, shifts = rc.filters([p[4] for p in plan_rir])
+dry = cc.gather(ids, L=LS)
 stages = {
+    "convolve_ms": timed(lambda: audio.convolve_batch(dry, filt, [LS] * N, taps, shifts, out=both[:N]), RIR_REPS)[0],
     "gather_speech_ms": timed(lambda: cc.gather(ids, L=LS, out=both[:N]), REPS)[0],
     "gather_noise_ms": timed(lambda: nc.gather(ids, starts, counts), REPS)[0],
     "mix_ms": timed(lambda: audio.mix_snr_batch(both[:N], nrows, 0, speech_lengths=[LS] * N, noise_lengths=counts, gains=gains,
@@ -81,7 +93,8 @@ torch.cuda.synchronize()
 per_utt_ms = (time.perf_counter() - t0) * 1e3
 
 row = {"utterances": N, "samples_each": LS, "batch_build_ms": build_ms, "batch_build_wall_ms": build_wall_ms,
+       "rir_taps": RIR_TAPS, "rir_batch_build_ms": rir_build_ms, "rir_batch_build_wall_ms": rir_build_wall_ms,
        "per_utterance_path_ms": per_utt_ms, "train_step_ms": list(STEP_MS),
-       "batch_build_over_step": build_ms / STEP_MS[0], "per_utterance_path_over_step": per_utt_ms / STEP_MS[0]}
+       "batch_build_over_step": build_ms / STEP_MS[0], "rir_batch_build_over_step": rir_build_ms / STEP_MS[0], "per_utterance_path_over_step": per_utt_ms / STEP_MS[0]}
 row.update(stages)
 print(json.dumps(row))
