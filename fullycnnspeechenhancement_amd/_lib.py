@@ -43,6 +43,8 @@ SYMBOLS = {
     "rced_stft_ex": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int]),
     "rced_istft_ex": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int]),
     "rced_istft_ola": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp]),
+    "rced_wave_loss": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                      ctypes.c_int, ctypes.c_double, _vp, _vp, ctypes.c_int, _vp]),
     "rced_framing_check": (ctypes.c_int, [ctypes.c_int] * 3),
     "rced_stft_num_frames_fr": (ctypes.c_int, [ctypes.c_int] * 3),
     "rced_stft_fr": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 6 + [_vp, _vp, ctypes.c_int, _vp]),
@@ -110,6 +112,10 @@ SYMBOLS = {
     "rced_train_exchange_size": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
     "rced_train_grad": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int,
                                        ctypes.POINTER(ctypes.c_double), _vp]),
+    "rced_train_step_wave": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, _vp,
+                                            ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _vp]),
+    "rced_train_grad_wave": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp,
+                                            ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _vp]),
     "rced_train_apply": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_float, _vp]),
     "rced_train_sync_points": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_size_t)]),
     "rced_train_sync_begin": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _vp, _vp]),
@@ -131,6 +137,12 @@ SYMBOLS = {
 }
 
 _lib = None
+
+
+class WaveArgs(ctypes.Structure):
+    """rced.h: rced_wave_args."""
+    _fields_ = [("w_spectral", ctypes.c_double), ("w_sse", ctypes.c_double), ("w_si_sdr", ctypes.c_double), ("skip_edges", ctypes.c_int),
+                ("phase_dev", _vp), ("clean_dev", _vp), ("clean_stride", ctypes.c_int), ("lengths_dev", _vp), ("frames_dev", _vp)]
 
 
 class RcedError(RuntimeError):

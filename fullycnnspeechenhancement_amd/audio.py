@@ -23,6 +23,7 @@ from .arena import PCM_DTYPES, gather_pcm, resample_arena, resample_batch, resam
 from .streaming import (STREAM_DELAY, STREAM_FINISH_MAX, STREAM_MAX_HOPS, StreamingDenoiser, StreamingResampler,  # noqa: F401
                         resampler_delay, stream_delay, stream_delay_fr)
 from .freerun import BlockDenoiser, FreeResampler, block_delay, free_available  # noqa: F401
+from .objective import WaveObjective, wave_loss_batch  # noqa: F401
 
 
 WINDOWS = {"hamming": 0, "hanning": 1, "blackman": 2, "bartlett": 3}     # rced.h: RCED_WINDOW_*; numpy's windows of those names

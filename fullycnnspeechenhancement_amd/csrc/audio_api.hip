@@ -15,6 +15,7 @@
 #include "kernels_audio_x6.h"
 #include "kernels_ola_x6.h"
 #include "kernels_framing.h"
+#include "kernels_wave_loss.h"
 #include "rced_internal.h"
 
 using namespace rced;
@@ -33,8 +34,12 @@ struct AudioTables {   // per device, built once
   // overlap-add (kernels_ola_x6.h): 16 M-tiles of A fragments, the single-frame factors of hops 0 and F
   unsigned short* ola_x6 = nullptr;
   float* ola_fix = nullptr;
+  // the rebuild's adjoint (kernels_wave_loss.h): the STFT's 16 M-tiles with kappa_b / 256 folded in, the reciprocal denominators [3][128]
+  unsigned short* adj_x6 = nullptr;
+  float* adj_inv = nullptr;
   void release() {   // of a build that failed half way
-    for (void* p : {(void*)stft, (void*)istft512, (void*)istft256, (void*)stft_x6, (void*)ola_x6, (void*)ola_fix}) (void)hipFree(p);
+    for (void* p : {(void*)stft, (void*)istft512, (void*)istft256, (void*)stft_x6, (void*)ola_x6, (void*)ola_fix, (void*)adj_x6, (void*)adj_inv})
+      (void)hipFree(p);
     for (int v = 0; v < 2; ++v)
       for (void* p : {(void*)istft_x6[v], (void*)cim[v], (void*)chead[v]}) (void)hipFree(p);
   }
@@ -122,6 +127,16 @@ int build_x6(AudioTables& t) {
       fix[128 + s] = (float)(den(s) / (hamming(s + 128) * hamming(s + 128)));
     }
     if (int rc = upload(&t.ola_fix, fix, kWhat)) return rc;
+    // the adjoint: G = rfft(w u) projected with kappa_b / 256 (irfft's weights: bins 0 and 128 count once); u = g_e / the denominator
+    auto adj = [](int row, int k) { return stft_coef(row, k) * (row < 2 ? 1.0 : 2.0) / audio::kFrame; };
+    if (int rc = upload(&t.adj_x6, pack_x6(audio::x6::kStftMTx, adj), kWhat)) return rc;
+    std::vector<float> inv(3 * 128);
+    for (int s = 0; s < 128; ++s) {
+      inv[s] = (float)(1.0 / den(s));
+      inv[128 + s] = (float)(1.0 / (hamming(s) * hamming(s)));
+      inv[256 + s] = (float)(1.0 / (hamming(s + 128) * hamming(s + 128)));
+    }
+    if (int rc = upload(&t.adj_inv, inv, kWhat)) return rc;
   }
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(audio::x6::istft_x6_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      audio::x6::kIstftLdsBytes);
@@ -379,6 +394,50 @@ void rced_fr_tables_unpin(int device, int window, int window_name, int ola, int 
   }
 }
 
+namespace {
+
+// ---- rced_wave_loss's workspace: per (device, stream), growing only -- a call whose shape fits allocates nothing ------------------
+struct WaveWs {
+  int* frames;            // [N]
+  float *y, *u;           // [N, (T+1)*128]: the rebuild, the scaled reverse scan
+  double *ws1, *ws2;      // [N, slices, 2]
+  double* scal;           // [N, 4]
+};
+struct WaveBuf {
+  char* p = nullptr;
+  size_t bytes = 0;
+};
+std::map<void*, WaveBuf> g_wave_ws[kMaxDevices];
+std::mutex g_wave_mu;
+
+int wave_workspace(int device, void* stream, int N, int L, int slices, WaveWs* out) {
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t sig = up((size_t)N * L * sizeof(float)), part = up((size_t)N * slices * 2 * sizeof(double));
+  const size_t scal = up((size_t)N * 4 * sizeof(double)), fr = up((size_t)N * sizeof(int));
+  const size_t bytes = 2 * sig + 2 * part + scal + fr;
+  std::lock_guard<std::mutex> lk(g_wave_mu);
+  WaveBuf& w = g_wave_ws[device][stream];
+  if (w.bytes < bytes) {
+    if (w.p) {
+      HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));   // an earlier call may still read it
+      (void)hipFree(w.p);
+      w = WaveBuf();
+    }
+    HIP_TRY(hipMalloc(&w.p, bytes));
+    w.bytes = bytes;
+  }
+  char* p = w.p;
+  out->y = reinterpret_cast<float*>(p);
+  out->u = reinterpret_cast<float*>(p + sig);
+  out->ws1 = reinterpret_cast<double*>(p + 2 * sig);
+  out->ws2 = reinterpret_cast<double*>(p + 2 * sig + part);
+  out->scal = reinterpret_cast<double*>(p + 2 * sig + 2 * part);
+  out->frames = reinterpret_cast<int*>(p + 2 * sig + 2 * part + scal);
+  return RCED_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int rced_stft_num_frames(int length) { return length > 0 ? audio::num_frames(length) : 0; }
@@ -470,6 +529,67 @@ int rced_istft_ola(const float* mag_dev, const float* phase_dev, const int* fram
   HIP_TRY(hipGetLastError());
   return RCED_OK;
 }
+
+int rced_wave_loss(const float* mag_dev, const float* phase_dev, const int* frames_dev, const float* clean_dev, int clean_stride,
+                   const int* lengths_dev, int N, int T, double w_sse, double w_si_sdr, int skip_edges, double inv_batch,
+                   double* terms_dev, float* grad_dev, int device, void* stream) {
+  return rced_wave_loss_run(mag_dev, phase_dev, frames_dev, clean_dev, clean_stride, lengths_dev, N, T, w_sse, w_si_sdr, skip_edges, inv_batch,
+                            terms_dev, grad_dev, 0, device, stream);
+}
+
+}  // extern "C"
+
+int rced_wave_loss_run(const float* mag_dev, const float* phase_dev, const int* frames_dev, const float* clean_dev, int clean_stride,
+                       const int* lengths_dev, int N, int T, double w_sse, double w_si_sdr, int skip_edges, double inv_batch,
+                       double* terms_dev, float* grad_dev, int accumulate, int device, void* stream) {
+  if (N < 0 || T < 0 || clean_stride < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
+  if (!(w_sse >= 0.0) || !(w_si_sdr >= 0.0) || !std::isfinite(w_sse) || !std::isfinite(w_si_sdr))
+    return rced_fail(RCED_ERR_ARG, "the weights must be finite and >= 0, got w_sse = %g, w_si_sdr = %g", w_sse, w_si_sdr);
+  if (!(inv_batch > 0.0) || !std::isfinite(inv_batch)) return rced_fail(RCED_ERR_ARG, "inv_batch must be finite and > 0, got %g", inv_batch);
+  if (skip_edges != 0 && skip_edges != 1) return rced_fail(RCED_ERR_ARG, "skip_edges must be 0 or 1, got %d", skip_edges);
+  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
+  if (T > (1 << 22)) return rced_fail(RCED_ERR_ARG, "T > 2^22 frames");
+  if (N == 0) return RCED_OK;
+  if (!terms_dev || !lengths_dev || (clean_stride > 0 && !clean_dev) || (T > 0 && (!mag_dev || !phase_dev)))
+    return rced_fail(RCED_ERR_ARG, "null pointer");
+  DeviceGuard g(device);
+  AudioTables* t = nullptr;
+  if (int rc = tables(device, &t)) return rc;
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  const int L = (T + 1) * audio::kStep, slices = wloss::num_slices(L);
+  WaveWs w;
+  if (int rc = wave_workspace(device, stream, N, L, slices, &w)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+#define WAVE_LAUNCH(kernel, grid, block, lds, ...)                 \
+  do {                                                             \
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, __VA_ARGS__); \
+    HIP_TRY(hipGetLastError());                                    \
+  } while (0)
+  WAVE_LAUNCH(wloss::frames_kernel, dim3((N + 255) / 256), dim3(256), 0, frames_dev, lengths_dev, N, T, w.frames);
+  WAVE_LAUNCH(audio::x6::istft_ola_x6_kernel, dim3(N), dim3(audio::x6::kThreadsX), audio::x6::kOlaLdsBytes, mag_dev, phase_dev,
+              (const int*)w.frames, (const unsigned short*)t->ola_x6, (const float*)t->ola_fix, T, w.y);
+  WAVE_LAUNCH(wloss::sums_kernel<0>, dim3(slices, N), dim3(wloss::kSumThreads), 0, (const float*)w.y, L, clean_dev, clean_stride, lengths_dev,
+              (const int*)w.frames, skip_edges, (const double*)nullptr, w.ws1, slices);
+  WAVE_LAUNCH(wloss::sums_kernel<1>, dim3(slices, N), dim3(wloss::kSumThreads), 0, (const float*)w.y, L, clean_dev, clean_stride, lengths_dev,
+              (const int*)w.frames, skip_edges, (const double*)w.ws1, w.ws2, slices);
+  WAVE_LAUNCH(wloss::terms_kernel, dim3(N), dim3(wloss::kSumThreads), 0, (const double*)w.ws1, (const double*)w.ws2, lengths_dev,
+              (const int*)w.frames, clean_stride, skip_edges, slices, terms_dev, w.scal);
+  if (grad_dev && T > 0) {
+    WAVE_LAUNCH(wloss::reverse_kernel, dim3(N), dim3(audio::x6::kThreadsX), 0, (const float*)w.y, L, clean_dev, clean_stride, lengths_dev,
+                (const int*)w.frames, skip_edges, (const double*)w.scal, 2.0 * w_sse * inv_batch, w_si_sdr * inv_batch,
+                (const float*)t->adj_inv, w.u);
+    if (accumulate)
+      WAVE_LAUNCH(wloss::adjoint_kernel<true>, dim3(N, 2, range_split(N, T)), dim3(audio::x6::kThreadsX), 0, (const float*)w.u, L,
+                  (const int*)w.frames, (const unsigned short*)t->adj_x6, phase_dev, T, grad_dev);
+    else
+      WAVE_LAUNCH(wloss::adjoint_kernel<false>, dim3(N, 2, range_split(N, T)), dim3(audio::x6::kThreadsX), 0, (const float*)w.u, L,
+                  (const int*)w.frames, (const unsigned short*)t->adj_x6, phase_dev, T, grad_dev);
+  }
+#undef WAVE_LAUNCH
+  return RCED_OK;
+}
+
+extern "C" {
 
 int rced_framing_check(int window, int stride, int window_name) { return framing_check(window, stride, window_name); }
 

@@ -90,6 +90,12 @@ struct rced_fr_tables {
 int rced_fr_tables_pin(int device, int window, int window_name, int ola, int nfft, rced_fr_tables* out);
 void rced_fr_tables_unpin(int device, int window, int window_name, int ola, int nfft);
 
+// audio_api.hip: rced_wave_loss (rced.h) with one more argument, for the training pass -- accumulate != 0: the gradient is added to
+// grad_dev (which then holds the spectral term's, written by an earlier launch on the stream) instead of written
+int rced_wave_loss_run(const float* mag_dev, const float* phase_dev, const int* frames_dev, const float* clean_dev, int clean_stride,
+                       const int* lengths_dev, int N, int T, double w_sse, double w_si_sdr, int skip_edges, double inv_batch,
+                       double* terms_dev, float* grad_dev, int accumulate, int device, void* stream);
+
 // stream_api.hip: streams created on `m` answer RCED_ERR_STATE from now on (rced_destroy calls this before the model goes)
 void rced_streams_detach(rced_model* m);
 

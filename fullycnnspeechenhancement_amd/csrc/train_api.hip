@@ -91,6 +91,9 @@ struct rced_trainer {
   size_t xstats = 0;
   // the synchronised step: the pass that rced_train_sync_begin opened and rced_train_sync_end / _abort has not closed yet
   std::unique_ptr<TrainPass> pending;
+  // the wave objective (rced_train_step_wave / _grad_wave): the per-utterance terms [rows][3] of the last such pass, growing only
+  double* wave_terms = nullptr;
+  int wave_rows = 0;
   std::vector<void*> owned;       // every device allocation made by rced_train_create
   std::vector<void*> act_bases;   // the allocations behind out / z / G / D, made for a pixel count (ensure_acts)
   template <class T>
@@ -484,6 +487,8 @@ struct TrainPass {
   int tiny[kMaxLayers] = {};
   std::vector<int> src_parts;  // [l]: the records of layer l's BatchNorm-backward sums that its consumer's dgrad left in t->part (Sums::DgradZ / FusedX)
   std::vector<double> hp;      // the loss kernel's partial sums, on the host after end()'s synchronise
+  const rced_wave_args* wave = nullptr;   // the wave objective's terms (rced.h), or nullptr: the spectral loss alone, today's pass
+  std::vector<double> hw;      // [N][3]: the wave terms per utterance, on the host after end()'s synchronise
   Stage stage = Stage::Fwd;
   int layer = 0;
   FinishPoint pt{};
@@ -683,11 +688,33 @@ struct TrainPass {
       HIP_TRY(hipStreamSynchronize(st));
       return RCED_OK;
     }
-    // ---- loss and its gradient (trainer.py:146-147,153)
-    hipLaunchKernelGGL(train::loss_fwd_bwd, dim3(kReduceGrid), dim3(train::kThreads), 0, st, (const float*)t->out[L], y_dev,
-                       P, 1.f / (float)t->batch_size, t->G[L], t->part);
+    // ---- loss and its gradient (trainer.py:146-147,153); with a wave objective the spectral term at its weight, if it has one,
+    // then the wave terms on the prediction, their gradient added to (or, without a spectral term, written as) G[L]
+    const bool spectral = !wave || wave->w_spectral > 0.0;
     hp.assign(kReduceGrid, 0.0);
-    HIP_TRY(hipMemcpyAsync(hp.data(), t->part, kReduceGrid * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (spectral) {
+      hipLaunchKernelGGL(train::loss_fwd_bwd, dim3(kReduceGrid), dim3(train::kThreads), 0, st, (const float*)t->out[L], y_dev,
+                         P, (wave ? (float)wave->w_spectral : 1.f) / (float)t->batch_size, t->G[L], t->part);
+      HIP_TRY(hipMemcpyAsync(hp.data(), t->part, kReduceGrid * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    if (wave && (wave->w_sse > 0.0 || wave->w_si_sdr > 0.0)) {
+      if (t->wave_rows < N) {
+        if (t->wave_terms) {
+          HIP_TRY(hipStreamSynchronize(st));
+          (void)hipFree(t->wave_terms);
+          t->wave_terms = nullptr;
+          t->wave_rows = 0;
+        }
+        HIP_TRY(hipMalloc(&t->wave_terms, (size_t)N * 3 * sizeof(double)));
+        t->wave_rows = N;
+      }
+      if (int rc = rced_wave_loss_run(t->out[L], wave->phase_dev, wave->frames_dev, wave->clean_dev, wave->clean_stride, wave->lengths_dev, N, T,
+                                      wave->w_sse, wave->w_si_sdr, wave->skip_edges, 1.0 / (double)t->batch_size, t->wave_terms, t->G[L],
+                                      spectral ? 1 : 0, t->device, st))
+        return rc;
+      hw.assign((size_t)N * 3, 0.0);
+      HIP_TRY(hipMemcpyAsync(hw.data(), t->wave_terms, hw.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
     // ---- backward.  G[id] collects d loss / d tensor id from every consumer (the conv reading it, skip adds); the plan says
     // which writer stores, which add, and which tensors are zeroed first.
     HIP_TRY(hipMemsetAsync(t->grads, 0, t->nvars * sizeof(float), st));
@@ -900,7 +927,7 @@ struct TrainPass {
 
   // g_out != nullptr (a shard): the gradient and every BatchNorm layer's (sum z, sum z^2, pixels) go into (or, accumulate,
   // are added to) g_out / s_out.  Otherwise Adam.  The one synchronise, and the loss.
-  int end(float* g_out, double* s_out, int accumulate, double* loss_out) {
+  int end(float* g_out, double* s_out, int accumulate, double* loss_out, double* parts_out = nullptr) {
     if (forward_only) return RCED_OK;
     if (t->wg_error) {   // (cannot happen with the up-front size above unless the runtime reports > 4 workgroups per CU)
       (void)hipStreamSynchronize(st);   // nothing of this step is left in flight behind the error
@@ -920,20 +947,51 @@ struct TrainPass {
     HIP_TRY(hipStreamSynchronize(st));
     double loss = 0.0;
     for (double v : hp) loss += v;
-    if (loss_out) *loss_out = loss / (double)t->batch_size;
+    if (!wave) {
+      if (loss_out) *loss_out = loss / (double)t->batch_size;
+      return RCED_OK;
+    }
+    double sse = 0.0, si = 0.0;   // in row order
+    for (int n = 0; n < (int)(hw.size() / 3); ++n) {
+      sse += hw[(size_t)n * 3];
+      if (hw[(size_t)n * 3 + 2] != 0.0) si += hw[(size_t)n * 3 + 1];
+    }
+    if (loss_out) *loss_out = (wave->w_spectral * loss + wave->w_sse * sse - wave->w_si_sdr * si) / (double)t->batch_size;
+    if (parts_out) {
+      parts_out[0] = loss;
+      parts_out[1] = sse;
+      parts_out[2] = si;
+    }
     return RCED_OK;
   }
 };
 
+// what rced_train_step_wave / rced_train_grad_wave refuse in their struct, before any device work
+int check_wave(const rced_wave_args* w, const float* y_dev) {
+  if (!w) return rced_fail(RCED_ERR_ARG, "the wave objective's arguments are NULL");
+  const double ws[3] = {w->w_spectral, w->w_sse, w->w_si_sdr};
+  for (double v : ws)
+    if (!(v >= 0.0) || !std::isfinite(v))
+      return rced_fail(RCED_ERR_ARG, "the objective's weights must be finite and >= 0, got %g, %g, %g", ws[0], ws[1], ws[2]);
+  if (ws[0] == 0.0 && ws[1] == 0.0 && ws[2] == 0.0) return rced_fail(RCED_ERR_ARG, "the objective's weights are all zero");
+  if (w->skip_edges != 0 && w->skip_edges != 1) return rced_fail(RCED_ERR_ARG, "skip_edges must be 0 or 1, got %d", w->skip_edges);
+  if (ws[0] > 0.0 && !y_dev) return rced_fail(RCED_ERR_ARG, "the target is NULL and the spectral term has a weight");
+  if ((ws[1] > 0.0 || ws[2] > 0.0) && (!w->phase_dev || !w->lengths_dev || w->clean_stride < 0 || (w->clean_stride > 0 && !w->clean_dev)))
+    return rced_fail(RCED_ERR_ARG, "a wave term has a weight: it needs phase_dev, clean_dev (rows of clean_stride >= 0) and lengths_dev");
+  return RCED_OK;
+}
+
 // args_rc: what the entry point made of its arguments (check_batch and its own)
 int train_run(rced_trainer* t, const char* what, int args_rc, const float* x_dev, const float* y_dev, float* pred_dev, int N, int T,
-              float lr, double* loss_out, void* stream, float* g_out = nullptr, double* s_out = nullptr, int accumulate = 0) {
+              float lr, double* loss_out, void* stream, float* g_out = nullptr, double* s_out = nullptr, int accumulate = 0,
+              const rced_wave_args* wave = nullptr, double* parts_out = nullptr) {
   Enter in(t, what, args_rc);
   if (in.rc) return in.rc;
   TrainPass pass(t, x_dev, y_dev, pred_dev, N, T, lr, stream, g_out != nullptr, 0.0, nullptr);
+  pass.wave = wave;
   if (int rc = pass.begin()) return rc;
   if (int rc = pass.advance()) return rc;
-  return pass.end(g_out, s_out, accumulate, loss_out);
+  return pass.end(g_out, s_out, accumulate, loss_out, parts_out);
 }
 
 constexpr int kSyncDoubles = 2 * train::kMaxC;   // the exchange buffer of a synchronised pass: (S1, S2) of a layer's channels
@@ -945,6 +1003,7 @@ rced_trainer::~rced_trainer() {
   pending.reset();
   for (void* p : owned) (void)hipFree(p);
   if (wpart) (void)hipFree(wpart);   // (made by the first step, regrown by tmd::wg_launch)
+  if (wave_terms) (void)hipFree(wave_terms);
   if (tiny_host) (void)hipHostFree(tiny_host);
   free_acts();
 }
@@ -973,6 +1032,23 @@ int rced_train_grad(rced_trainer* t, const float* x_dev, const float* y_dev, int
   int rc = check_batch(t, x_dev, y_dev, N, T);
   if (!rc && (!g_dev || !s_dev)) rc = rced_fail(RCED_ERR_ARG, "an exchange buffer is NULL");
   return train_run(t, "rced_train_grad", rc, x_dev, y_dev, nullptr, N, T, 0.f, loss_out, stream, g_dev, s_dev, accumulate != 0);
+}
+
+// y_dev may be NULL when the spectral term has no weight: check_batch is then given x_dev in its place
+int rced_train_step_wave(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, float lr, const rced_wave_args* wave,
+                         double* loss_out, double* parts_out, void* stream) {
+  int rc = check_wave(wave, y_dev);
+  if (!rc) rc = check_batch(t, x_dev, y_dev ? y_dev : x_dev, N, T);
+  return train_run(t, "rced_train_step_wave", rc, x_dev, y_dev, nullptr, N, T, lr, loss_out, stream, nullptr, nullptr, 0, wave, parts_out);
+}
+
+int rced_train_grad_wave(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, float* g_dev, double* s_dev,
+                         int accumulate, const rced_wave_args* wave, double* loss_out, double* parts_out, void* stream) {
+  int rc = check_wave(wave, y_dev);
+  if (!rc) rc = check_batch(t, x_dev, y_dev ? y_dev : x_dev, N, T);
+  if (!rc && (!g_dev || !s_dev)) rc = rced_fail(RCED_ERR_ARG, "an exchange buffer is NULL");
+  return train_run(t, "rced_train_grad_wave", rc, x_dev, y_dev, nullptr, N, T, 0.f, loss_out, stream, g_dev, s_dev, accumulate != 0, wave,
+                   parts_out);
 }
 
 int rced_train_apply(rced_trainer* t, const float* g_dev, const double* s_dev, float lr, void* stream) {

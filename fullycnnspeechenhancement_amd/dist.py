@@ -626,6 +626,9 @@ class DataParallelTrainer(object):
     identical results; sharded validation is not built."""
 
     def __init__(self, trainer, group=None, device=None, sync_bn=False):
+        if getattr(trainer, "has_wave_term", False):
+            raise ValueError("dist.DataParallelTrainer cannot be combined with an objective that has a wave term (%r): the ranks' steps "
+                             "have no wave form" % (trainer.objective,))
         if not dist.is_initialized():
             raise RuntimeError("torch.distributed is not initialised (one process per GPU)")
         if sync_bn and trainer.accumulate > 1:

@@ -23,8 +23,9 @@ import time
 
 import numpy as np
 
-from . import _lib, model as _model, spec, weights as _weights
+from . import _args, _lib, model as _model, spec, weights as _weights
 from .evaluation import EVERY_EXTRA, check_extra
+from .objective import WaveObjective
 from .metrics import AverageMeter
 
 
@@ -60,11 +61,14 @@ def run_epochs(tr, fit_step, train_loader, valid_loader, epochs, logger, checkpo
         train_batch_id = 0
         train_loader.shuffle()
         start_time = time.time()
-        for batch_mix, batch_clean, _, _ in train_loader:
+        for batch_mix, batch_clean, mix_sig, clean_sig in train_loader:
             train_batch_id += 1
             tr.data_time.update(time.time() - start_time)
             start_time = time.time()
-            batch_loss, _, global_step = fit_step(batch_mix, batch_clean)
+            if tr.has_wave_term:
+                batch_loss, _, global_step = fit_step(batch_mix, batch_clean, wave=wave_of_batch(train_loader, batch_mix, mix_sig, clean_sig))
+            else:
+                batch_loss, _, global_step = fit_step(batch_mix, batch_clean)
             tr.train_loss.update(batch_loss, n=1)
             tr.batch_time.update(time.time() - start_time)
             if root and train_batch_id % num_iter_print == 0:
@@ -87,11 +91,32 @@ def run_epochs(tr, fit_step, train_loader, valid_loader, epochs, logger, checkpo
     return global_step
 
 
+def wave_of_batch(loader, batch_mix, mix_sig, clean_sig):
+    """The `wave` argument of a step from a loader's 4-tuple: (the mixture's unit phase [N, T, 129] complex64, the clean rows, the
+    samples scored per utterance: min(len(mix), len(clean))).  The phase is audio.stft_batch's of the mixture's rows, whose
+    magnitudes are the loader's batch_mix bit for bit.  mix_sig, clean_sig: loader.PcmRows (the device loader's batches)."""
+    from . import audio
+    from .engine import loader_framing
+    fr = loader_framing(loader)
+    if fr is not None and not fr.is_default:
+        raise ValueError("an objective with a wave term (wave_sse or si_sdr) cannot be combined with a loader whose framing is %r: the "
+                         "differentiable rebuild exists for the default framing, 256 / 128 / hamming, only" % (fr,))
+    if not (hasattr(mix_sig, "rows") and hasattr(clean_sig, "rows")) or len(mix_sig) != len(clean_sig):
+        raise ValueError("an objective with a wave term needs the loader's mix_sig and clean_sig as device rows (loader.PcmRows), one pair "
+                         "per utterance")
+    _, phase = audio.stft_batch(mix_sig.rows, mix_sig.lengths, frames=int(batch_mix.shape[1]), with_phase=True)
+    return phase, clean_sig.rows, [min(a, b) for a, b in zip(mix_sig.lengths, clean_sig.lengths)]
+
+
 class FullyCNNTrainer(object):
     model = None
 
     def __init__(self, net_work="FullyCNNV3", batch_size=1, lr=1e-3, warmup_steps=4000.0, weights=None, device=0,
-                 seed=None, accumulate=1):
+                 seed=None, accumulate=1, objective=None):
+        if objective is not None and not isinstance(objective, WaveObjective):
+            raise ValueError("objective must be an audio.WaveObjective or None (the spectral loss), got %r" % (objective,))
+        self.objective = objective                 # None: sum((target - pred)^2) / batch_size, the reference's loss
+        self.loss_parts = None                     # the last step's unweighted (spectral, wave_sse, si_sdr) sums, with an objective
         if isinstance(accumulate, bool) or int(accumulate) != accumulate or int(accumulate) < 1:
             raise ValueError("accumulate must be a positive integer (1: the whole batch in one piece), got %r" % (accumulate,))
         self.accumulate = int(accumulate)          # train_step cuts its batch into this many shards (gradient accumulation)
@@ -144,17 +169,73 @@ class FullyCNNTrainer(object):
             raise ValueError("input and target must both be [N, T, 129, 1]")
         return x, y
 
-    def train_step(self, input_x, target_y):
+    # -- the objective ----------------------------------------------------------------
+    @property
+    def has_wave_term(self):
+        return self.objective is not None and self.objective.has_wave_term
+
+    @property
+    def _plain(self):
+        """The reference's loss, through the entries that have always computed it: no objective, or the spectral term alone at weight 1."""
+        o = self.objective
+        return o is None or (not o.has_wave_term and o.spectral == 1.0)
+
+    def _wave_args(self, wave, x):
+        """rced_wave_args for a step over x [N, T, 129, 1] from wave = (phase [N, T, 129] complex, clean rows [N, >= max length],
+        N lengths), and the tensors it points into."""
+        import torch
+        o = self.objective
+        if o is None or not o.has_wave_term:
+            if wave is not None:
+                raise ValueError("wave=... was given, but the trainer's objective %r has no wave term" % (o,))
+        a = _lib.WaveArgs(o.spectral, o.wave_sse, o.si_sdr, int(o.skip_edges), None, None, 0, None, None)
+        if not o.has_wave_term:
+            return a, ()
+        if wave is None:
+            raise ValueError("the trainer's objective %r has a wave term (wave_sse or si_sdr) and the step was given wave=None: it needs "
+                             "wave=(phase, clean_rows, lengths)" % (o,))
+        phase, clean, lengths = wave
+        n, t = int(x.shape[0]), int(x.shape[1])
+        if not (hasattr(phase, "is_cuda") and phase.is_cuda and phase.device == x.device and tuple(phase.shape) == (n, t, spec.FEATURE_DIM)):
+            raise ValueError("wave[0], the phase, must be a complex [N = %d, T = %d, 129] tensor on %s" % (n, t, x.device))
+        ph = torch.view_as_real(phase.to(torch.complex64).contiguous()).contiguous()
+        clean = _args.rows(clean, "wave[1], the clean rows,")
+        if int(clean.shape[0]) != n or clean.device != x.device:
+            raise ValueError("wave[1], the clean rows, must hold N = %d rows on %s" % (n, x.device))
+        lens = _args.host_ints(lengths, n, "wave[2], the lengths,")
+        if any(v < 0 or v > int(clean.shape[1]) for v in lens):
+            raise ValueError("wave[2], the lengths, must lie in [0, %d]" % int(clean.shape[1]))
+        ldev = torch.tensor(lens, dtype=torch.int32, device=x.device)
+        a.phase_dev, a.clean_dev, a.clean_stride, a.lengths_dev = ph.data_ptr(), clean.data_ptr(), _args.row_stride(clean), ldev.data_ptr()
+        return a, (ph, clean, ldev)
+
+    @staticmethod
+    def _wave_rows(wave, a, b):
+        return None if wave is None else (wave[0][a:b], wave[1][a:b], list(_args.host_ints(wave[2]))[a:b])
+
+    def train_step(self, input_x, target_y, wave=None):
         """trainer.py:181-192: returns (batch_loss, summary (None here), global_step).  With accumulate=k > 1 the batch is
-        cut into k contiguous row ranges (accumulation_slices) and the step is train_step_sharded over them."""
+        cut into k contiguous row ranges (accumulation_slices) and the step is train_step_sharded over them.
+        With an objective that has a wave term, wave = (phase, clean_rows, lengths): the mixture's unit phase [N, T, 129] complex,
+        the clean signals as device rows and the samples scored per utterance (audio.wave_loss_batch); accumulate=k cuts it by
+        the same rows.  self.loss_parts then holds the step's unweighted (spectral, wave_sse, si_sdr) sums."""
         import torch
         x, y = self._on_device(input_x, target_y)
         if self.accumulate > 1:
-            return self.train_step_sharded([(x[a:b], y[a:b]) for a, b in accumulation_slices(x.shape[0], self.accumulate)])
+            return self.train_step_sharded([(x[a:b], y[a:b], self._wave_rows(wave, a, b))
+                                            for a, b in accumulation_slices(x.shape[0], self.accumulate)])
         loss = ctypes.c_double()
         st = torch.cuda.current_stream(x.device).cuda_stream
-        _lib.check(_lib.load().rced_train_step(self._h, x.data_ptr(), y.data_ptr(), int(x.shape[0]), int(x.shape[1]),
-                                               ctypes.c_float(self.lr), ctypes.byref(loss), st))
+        if self._plain and wave is None:
+            _lib.check(_lib.load().rced_train_step(self._h, x.data_ptr(), y.data_ptr(), int(x.shape[0]), int(x.shape[1]),
+                                                   ctypes.c_float(self.lr), ctypes.byref(loss), st))
+            return loss.value, None, self.global_step
+        args, keep = self._wave_args(wave, x)
+        parts = (ctypes.c_double * 3)()
+        _lib.check(_lib.load().rced_train_step_wave(self._h, x.data_ptr(), y.data_ptr(), int(x.shape[0]), int(x.shape[1]),
+                                                    ctypes.c_float(self.lr), ctypes.byref(args), ctypes.byref(loss), parts, st))
+        self.loss_parts = tuple(parts)
+        del keep
         return loss.value, None, self.global_step
 
     # -- the step in shards (DESIGN.md 3.5b) ----------------------------------------------------------
@@ -170,17 +251,26 @@ class FullyCNNTrainer(object):
             self._exch = (torch.zeros(nf.value, dtype=torch.float32, device=dev), torch.zeros(nd.value, dtype=torch.float64, device=dev))
         return self._exch
 
-    def grad_step(self, input_x, target_y, accumulate=False):
+    def grad_step(self, input_x, target_y, accumulate=False, wave=None):
         """One shard: forward (BatchNorm with THIS shard's statistics), loss = sum((y - pred)^2) / batch_size, backward.
         The gradient and the statistics sums overwrite the exchange tensors, or (accumulate) are added to them; variables,
-        Adam slots, moving statistics and global_step stay as they are.  Returns the shard's loss."""
+        Adam slots, moving statistics and global_step stay as they are.  Returns the shard's loss.  wave: as in train_step;
+        self.loss_parts then holds this shard's sums (every term is a sum over utterances, divided by batch_size: shards add up)."""
         import torch
         x, y = self._on_device(input_x, target_y)
         g, s = self.exchange_tensors()
         loss = ctypes.c_double()
         st = torch.cuda.current_stream(x.device).cuda_stream
-        _lib.check(_lib.load().rced_train_grad(self._h, x.data_ptr(), y.data_ptr(), int(x.shape[0]), int(x.shape[1]), g.data_ptr(),
-                                               s.data_ptr(), 1 if accumulate else 0, ctypes.byref(loss), st))
+        if self._plain and wave is None:
+            _lib.check(_lib.load().rced_train_grad(self._h, x.data_ptr(), y.data_ptr(), int(x.shape[0]), int(x.shape[1]), g.data_ptr(),
+                                                   s.data_ptr(), 1 if accumulate else 0, ctypes.byref(loss), st))
+            return loss.value
+        args, keep = self._wave_args(wave, x)
+        parts = (ctypes.c_double * 3)()
+        _lib.check(_lib.load().rced_train_grad_wave(self._h, x.data_ptr(), y.data_ptr(), int(x.shape[0]), int(x.shape[1]), g.data_ptr(),
+                                                    s.data_ptr(), 1 if accumulate else 0, ctypes.byref(args), ctypes.byref(loss), parts, st))
+        self.loss_parts = tuple(parts)
+        del keep
         return loss.value
 
     def apply_step(self):
@@ -208,14 +298,22 @@ class FullyCNNTrainer(object):
         if sync_bn and self.accumulate > 1:
             raise ValueError("sync_bn=True cannot be combined with accumulate=%d: accumulation runs its shards one after the other, "
                              "synchronised BatchNorm needs them all at every layer" % self.accumulate)
-        shards = [self._on_device(x, y) for x, y in shards]
+        if sync_bn and self.has_wave_term:
+            raise ValueError("sync_bn=True cannot be combined with an objective that has a wave term (%r): the synchronised pass has no "
+                             "wave form" % (self.objective,))
+        waves = [sh[2] if len(sh) > 2 else None for sh in shards]     # a shard: (x, y) or (x, y, wave)
+        shards = [self._on_device(sh[0], sh[1]) for sh in shards]
         if not shards:
             raise ValueError("train_step_sharded needs at least one shard")
         if sync_bn:
             return self._train_step_sharded_sync(shards)
-        loss = 0.0
-        for i, (x, y) in enumerate(shards):
-            loss += self.grad_step(x, y, accumulate=i > 0)
+        loss, parts = 0.0, None
+        for i, ((x, y), w) in enumerate(zip(shards, waves)):
+            loss += self.grad_step(x, y, accumulate=i > 0, wave=w)
+            if self.loss_parts is not None and not (self._plain and w is None):
+                parts = self.loss_parts if parts is None else tuple(p + q for p, q in zip(parts, self.loss_parts))
+        if parts is not None:
+            self.loss_parts = parts
         return loss, None, self.apply_step()
 
     # -- the synchronised step ----------------------------------------------------------
@@ -350,9 +448,9 @@ class FullyCNNTrainer(object):
                 logger.info(more)
         return self.sdr_score.avg
 
-    def fit_step(self, input_x, target_y):
-        """One iteration of the loop body of trainer.py:212-215: step, then set lr for the next step."""
-        out = self.train_step(input_x, target_y)
+    def fit_step(self, input_x, target_y, wave=None):
+        """One iteration of the loop body of trainer.py:212-215: step, then set lr for the next step.  wave: as in train_step."""
+        out = self.train_step(input_x, target_y, wave=wave) if wave is not None else self.train_step(input_x, target_y)
         self.lr = self.noam_scheme(out[2], self.warmup_steps)
         return out
 

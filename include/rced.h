@@ -183,6 +183,34 @@ int rced_istft_ex(const float* mag_dev, const float* phase_dev, int N, int T, in
 int rced_istft_ola(const float* mag_dev, const float* phase_dev, const int* frames_dev, int N, int T, float* audio_dev,
                    int device, void* stream);
 
+/* Waveform terms of a training objective on the overlap-add rebuild, and their gradient with respect to the magnitudes.  Default
+ * framing only (256 / 128 / hamming, 8 kHz).  Per utterance n: M = mag[n] [T,129], P = phase[n] [T,129,2] (unit phase of the
+ * mixture), F frames, c = the clean row of l = lengths_dev[n] samples (clamped into [0, clean_stride]).
+ *   The rebuild.  y = rced_istft_ola(M, P, F), exactly as defined above: x_t = irfft(M_t P_t, 256); e = sum_t w x_t / sum_t w^2 over
+ *     the frames that cover a sample; y[i] = e[i] + 0.97 y[i-1].
+ *   The range R = [lo, hi).  skip_edges = 1: lo = 128, hi = min(l, 128 F) -- only the hops two frames cover are scored; hops 0 and
+ *     F divide by one frame's w^2, down to 0.0064, and would weight sample 0 about 156 times over the middle of the signal.
+ *     skip_edges = 0: lo = 0, hi = min(l, 128 (F + 1)), the range rced_si_sdr scores.  An empty range contributes nothing to any term
+ *     and has zero gradient.
+ *   The terms.  wave_sse = sum_R (y - c)^2;  si_sdr = 10 log10((|alpha c|^2 + eps) / (|y - alpha c|^2 + eps)), alpha = <y,c> / <c,c>,
+ *     every sum over R, in two passes (alpha first), fp64 from the fp32 signals; eps = 1e-8 is this project's choice.  If <c,c> = 0
+ *     or R is empty the SI-SDR term is INVALID: it counts 0, its gradient is 0, and the validity column says so.
+ *   terms_dev [N,3] double = (wave_sse, si_sdr, valid 1.0 / 0.0), unweighted.
+ *   The gradient of  w_sse * inv_batch * sum_n wave_sse_n  -  w_si_sdr * inv_batch * sum_valid si_sdr_n  (inv_batch = 1 / B, B the
+ *     trainer's batch size).  With k = 10 / ln 10, r = y - alpha c:
+ *       g_y = w_sse inv_batch 2 (y - c) - w_si_sdr inv_batch k (2 alpha c / (|alpha c|^2 + eps) - 2 r / (|r|^2 + eps)) on R, 0 outside;
+ *       g_e[i] = g_y[i] + 0.97 g_e[i+1] (the de-emphasis transposed);  u = g_e / sum w^2;  G_t = rfft(w u[128t : 128t + 256]);
+ *       dM_t[b] = (kappa_b / 256)(P_re G_re + P_im G_im), kappa = 1 at bins 0 and 128 and 2 elsewhere.
+ *     grad_dev: NULL (terms only) or [N,T,129] float32, every element written; frames t >= F as zeros.
+ * frames_dev [N] int32 or NULL (= rced_stft_num_frames(length)); either is clamped into [0, T].  Frames t >= F of mag and phase and
+ * samples >= l of the clean rows are never read.  No atomics: bit-identical run to run, and a row's bits do not depend on N, T, its
+ * row index or its neighbours.  The weights must be finite and >= 0, inv_batch finite and > 0, skip_edges 0 or 1: anything else is
+ * RCED_ERR_ARG before any device work.  Seven launches with a gradient, five without; a workspace of its own per (device, stream),
+ * growing only: after the first call at a shape nothing is allocated.  Asynchronous. */
+int rced_wave_loss(const float* mag_dev, const float* phase_dev, const int* frames_dev, const float* clean_dev, int clean_stride,
+                   const int* lengths_dev, int N, int T, double w_sse, double w_si_sdr, int skip_edges, double inv_batch,
+                   double* terms_dev, float* grad_dev, int device, void* stream);
+
 /* ---- any framing: the same three transforms with the window length W, the stride S and the window's name as arguments.
  * 2 <= W <= 256 (rfft(256) would crop a longer frame), 1 <= S <= W; the window is numpy's hamming / hanning / blackman / bartlett at
  * length W, evaluated in double on the host.  These entries always run the general kernels (kernels_framing.h), at 256 / 128 / hamming
@@ -668,6 +696,33 @@ int rced_train_exchange_size(rced_trainer* t, size_t* n_floats, size_t* n_double
  * Synchronises the stream. */
 int rced_train_grad(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, float* g_dev, double* s_dev,
                     int accumulate, double* loss_out, void* stream);
+
+/* rced_train_step / rced_train_grad with the objective
+ *   loss = w_spectral * sum((target - M)^2) / B + w_sse * sum_n wave_sse_n / B - w_si_sdr * sum_valid si_sdr_n / B,
+ * M the net's prediction, B the trainer's batch_size, wave_sse_n and si_sdr_n rced_wave_loss's terms of utterance n on the rebuilt
+ * prediction (default framing only; the definition is there).  The weights are finite, >= 0 and not all zero; (1, 0, 0) is
+ * rced_train_step's loss.  Pure SI-SDR leaves the output's scale free while inference uses the mask as a magnitude: that is why
+ * the terms mix.  phase_dev [N,T,129,2] float32: the mixture's unit phase; clean_dev: N rows of clean_stride floats; lengths_dev
+ * [N] int32: samples per utterance; frames_dev [N] int32 or NULL (= rced_stft_num_frames(length)); all DEVICE memory, read by this
+ * call only, and needed only where w_sse or w_si_sdr has a weight.  y_dev may be NULL when w_spectral = 0.  Anything else is
+ * RCED_ERR_ARG before any device work.  The pass is rced_train_step's up to the loss: there the spectral term's
+ * kernel runs at w_spectral / B (if it has a weight), then rced_wave_loss's launches on the prediction, their gradient added to the
+ * spectral term's; everything behind is unchanged.  *loss_out (host): the objective; parts_out: NULL or 3 doubles (host) receiving
+ * the unweighted sums sum((target - M)^2), sum_n wave_sse_n, sum_valid si_sdr_n of this call's rows.  Deterministic as the step
+ * is.  The synchronised pass (rced_train_sync_*) has no such form. */
+typedef struct rced_wave_args {
+  double w_spectral, w_sse, w_si_sdr;
+  int skip_edges; /* 1: score only the hops two frames cover; 0: the whole rebuilt signal */
+  const float* phase_dev;
+  const float* clean_dev;
+  int clean_stride;
+  const int* lengths_dev;
+  const int* frames_dev;
+} rced_wave_args;
+int rced_train_step_wave(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, float lr,
+                         const rced_wave_args* wave, double* loss_out, double* parts_out, void* stream);
+int rced_train_grad_wave(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, float* g_dev, double* s_dev,
+                         int accumulate, const rced_wave_args* wave, double* loss_out, double* parts_out, void* stream);
 
 /* The moving-statistics update from s_dev (momentum 0.99, unbiased variance, by the step's expressions), then the Adam
  * step from g_dev with the fed learning rate; global_step += 1.  Afterwards rced_train_get_gradients returns g_dev's

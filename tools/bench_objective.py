@@ -1,0 +1,84 @@
+#!/usr/bin/env python3
+"""Times the wave objective at BASELINE config-3 scale (256 utterances x 512 frames = 65,664 samples each), in one run:
+line 1: audio.wave_loss_batch's entry (rced_wave_loss, with and without the gradient) beside audio.stft_batch and
+        audio.istft_batch(rebuild="ola") on the same signals, alternating, the median of five windows of 50 calls;
+line 2: the CR-CED training step with the spectral loss beside the step with each objective, one trainer, alternating, the
+        median of three windows of 10 steps (the learning rate is 0: every window steps the same variables).
+--entries: line 1 only (what a kernel trace of the added launches is taken from)."""
+import json, os, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch
+from fullycnnspeechenhancement_amd import FullyCNNTrainer, _args, _lib, audio
+from fullycnnspeechenhancement_amd import weights as _weights
+
+N, T = 256, 512
+L = (T - 1) * 128 + 256
+torch.manual_seed(0)
+clean = torch.randn((N, L), device="cuda") * 0.1
+pcm = clean + torch.randn((N, L), device="cuda") * 0.03
+lengths = [L] * N
+
+
+def window(fn, reps):
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def alternating(fns, windows, reps, warm=3):
+    """name -> the median over `windows` windows of `reps` calls, the candidates taking turns."""
+    for fn in fns.values():
+        for _ in range(warm):
+            fn()
+    times = {k: [] for k in fns}
+    for _ in range(windows):
+        for k, fn in fns.items():
+            times[k].append(window(fn, reps))
+    return {k: sorted(v)[len(v) // 2] for k, v in times.items()}, times
+
+
+mag, ph = audio.stft_batch(pcm)
+assert mag.shape[1] == T
+lib, stream = _lib.load(), _args.current_stream(pcm.device)
+phr = torch.view_as_real(ph).contiguous()
+m3 = mag.squeeze(-1).contiguous()
+ldev = torch.tensor(lengths, dtype=torch.int32, device="cuda")
+terms = torch.empty((N, 3), dtype=torch.float64, device="cuda")
+grad = torch.empty((N, T, 129), dtype=torch.float32, device="cuda")
+
+
+def wave(with_grad):
+    _lib.check(lib.rced_wave_loss(m3.data_ptr(), phr.data_ptr(), None, clean.data_ptr(), L, ldev.data_ptr(), N, T, 0.5, 1.0, 1, 1.0 / N,
+                                  terms.data_ptr(), grad.data_ptr() if with_grad else None, 0, stream))
+
+
+med, _ = alternating({"stft_ms": lambda: audio.stft_batch(pcm), "istft_ola_ms": lambda: audio.istft_batch(mag, ph, rebuild="ola"),
+                      "wave_loss_terms_ms": lambda: wave(False), "wave_loss_ms": lambda: wave(True)}, 5, 50)
+med["reverse_and_adjoint_ms"] = med["wave_loss_ms"] - med["wave_loss_terms_ms"]
+med["sums_ms"] = med["wave_loss_terms_ms"] - med["istft_ola_ms"]
+print(json.dumps(dict({"utterances": N, "frames": T, "samples": L}, **med)))
+if "--entries" in sys.argv[1:]:
+    sys.exit(0)
+
+tr = FullyCNNTrainer("FullyCNNV3", batch_size=N, lr=0.0, weights=_weights.synthetic_weights(3, seed=42))
+target, _ = audio.stft_batch(clean)
+wave_args = (ph, clean, lengths)
+OBJECTIVES = {"spectral": None, "spectral+wave_sse": audio.WaveObjective(1, 1, 0), "spectral+si_sdr": audio.WaveObjective(1, 0, 1),
+              "spectral+wave_sse+si_sdr": audio.WaveObjective(1, 0.5, 1), "si_sdr": audio.WaveObjective(0, 0, 1)}
+
+
+def step(objective):
+    tr.objective = objective
+    tr.train_step(mag, target, wave=wave_args if objective is not None else None)
+
+
+med, all_windows = alternating({k: (lambda o=o: step(o)) for k, o in OBJECTIVES.items()}, 3, 10, warm=2)
+print(json.dumps({"net": "FullyCNNV3", "utterances": N, "frames": T, "step_ms": med,
+                  "added_ms": {k: v - med["spectral"] for k, v in med.items() if k != "spectral"}, "step_ms_windows": all_windows}))
+tr.close()
