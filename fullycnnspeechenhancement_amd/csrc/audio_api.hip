@@ -1,7 +1,6 @@
 // C ABI of the STFT front-end / ISTFT rebuild (include/rced.h, "audio" section): host side.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cmath>
 #include <map>
 #include <mutex>
@@ -11,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "host_ws.h"
 #include "kernels_audio.h"
 #include "kernels_audio_x6.h"
 #include "kernels_ola_x6.h"
@@ -37,6 +37,7 @@ struct AudioTables {   // per device, built once
   // the rebuild's adjoint (kernels_wave_loss.h): the STFT's 16 M-tiles with kappa_b / 256 folded in, the reciprocal denominators [3][128]
   unsigned short* adj_x6 = nullptr;
   float* adj_inv = nullptr;
+  bool built() const { return stft; }   // the first one uploaded: a published entry has all of them, and the LDS attributes
   void release() {   // of a build that failed half way
     for (void* p : {(void*)stft, (void*)istft512, (void*)istft256, (void*)stft_x6, (void*)ola_x6, (void*)ola_fix, (void*)adj_x6, (void*)adj_inv})
       (void)hipFree(p);
@@ -44,8 +45,7 @@ struct AudioTables {   // per device, built once
       for (void* p : {(void*)istft_x6[v], (void*)cim[v], (void*)chead[v]}) (void)hipFree(p);
   }
 };
-AudioTables g_tab[kMaxDevices];
-std::mutex g_mu;
+DeviceOnce<AudioTables> g_tab;
 
 double hamming(int k) { return 0.54 - 0.46 * std::cos(2.0 * M_PI * k / (audio::kFrame - 1)); }   // np.hamming(256)
 
@@ -138,16 +138,10 @@ int build_x6(AudioTables& t) {
     }
     if (int rc = upload(&t.adj_inv, inv, kWhat)) return rc;
   }
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(audio::x6::istft_x6_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     audio::x6::kIstftLdsBytes);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(audio::x6::istft_ola_x6_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            audio::x6::kOlaLdsBytes);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(audio::x6::istft_x6_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            audio::x6::kIstftLdsBytes);
-  if (e != hipSuccess) return rced_fail(RCED_ERR_HIP, "hipFuncSetAttribute(istft LDS): %s", hipGetErrorString(e));
-  return RCED_OK;
+  return set_dynamic_lds({{kernel_ptr(audio::x6::istft_x6_kernel<true>), audio::x6::kIstftLdsBytes},
+                          {kernel_ptr(audio::x6::istft_ola_x6_kernel), audio::x6::kOlaLdsBytes},
+                          {kernel_ptr(audio::x6::istft_x6_kernel<false>), audio::x6::kIstftLdsBytes}},
+                         "istft LDS");
 }
 
 // frame-range split of an utterance over workgroups: enough workgroups for every CU when the batch is small
@@ -165,24 +159,28 @@ int build_tables(AudioTables& t) {
   return build_x6(t);
 }
 
-// A device's tables are built into a local and published last: g_tab[device].stft != nullptr means "all of them, and the LDS
-// attributes"; a failure half way frees what was built and leaves the entry empty for the next call to try again.
-int tables(int device, AudioTables** out) {
-  if (int rc = check_device(device, kMaxDevices)) return rc;
-  std::lock_guard<std::mutex> lk(g_mu);
-  AudioTables& pub = g_tab[device];
-  if (!pub.stft) {
-    AudioTables t;
-    if (int rc = build_tables(t)) {
-      t.release();
-      return rc;
-    }
-    pub = t;
-  }
-  *out = &pub;
+// What the STFT and rebuild entries refuse alike, in the order each of them refuses it.  skip_T0: a call without frames has nothing
+// to do (an overlap-add rebuild still zeroes its output); pointers: the ones the call will read or write are there; nfft, L: of the
+// entries that take one.  kNothingToDo: the caller returns RCED_OK without a launch.
+constexpr int kNothingToDo = -1;
+int audio_args(int N, int T, bool skip_T0, bool pointers, int nfft = 512, int L = 1) {
+  if (N < 0 || L < 0 || T < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
+  if (nfft != 512 && nfft != 256) return rced_fail(RCED_ERR_ARG, "nfft must be 512 (reference default) or 256");
+  if (N == 0 || (skip_T0 && T == 0)) return kNothingToDo;
+  if (L == 0) return rced_fail(RCED_ERR_ARG, "empty signals (L = 0) with T > 0");
+  if (!pointers) return rced_fail(RCED_ERR_ARG, "null pointer");
+  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
   return RCED_OK;
 }
 
+// The device's tables (built on first use: host_ws.h), with the device current for as long as `g` lives
+int tables(int device, DeviceGuard& g, AudioTables** out) {
+  g.enter(device);
+  if (int rc = check_device(device, kMaxDevices)) return rc;
+  if (int rc = g_tab.get(device, 0, build_tables, out)) return rc;
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  return RCED_OK;
+}
 
 // ---- any framing (kernels_framing.h) ----------------------------------------------------------------------------------------------
 // numpy's hamming / hanning / blackman / bartlett at length W >= 2, as numpy evaluates them (over n = 1 - W + 2k), in double
@@ -265,12 +263,10 @@ int fr_key(int kind, int W, int name) { return (kind * 4 + name) * 512 + W; }
 int fr_pack(int device, int kind, int W, int name, FrPack* out) {   // g_fr_mu held
   if (int rc = check_device(device, kMaxDevices)) return rc;
   if (!g_fr_attr[device]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(audio::fr::stft_fr_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       audio::fr::kStftFrLdsBytes);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(audio::fr::frames_fr_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              audio::fr::kFramesFrLdsBytes);
-    if (e != hipSuccess) return rced_fail(RCED_ERR_HIP, "hipFuncSetAttribute(framing LDS): %s", hipGetErrorString(e));
+    if (int rc = set_dynamic_lds({{kernel_ptr(audio::fr::stft_fr_kernel), audio::fr::kStftFrLdsBytes},
+                                  {kernel_ptr(audio::fr::frames_fr_kernel), audio::fr::kFramesFrLdsBytes}},
+                                 "framing LDS"))
+      return rc;
     g_fr_attr[device] = true;
   }
   std::map<int, FrPack>& m = g_fr[device];
@@ -300,28 +296,9 @@ int fr_pack(int device, int kind, int W, int name, FrPack* out) {   // g_fr_mu h
   return RCED_OK;
 }
 
-// The frames between the two steps of a rebuild, [N, T, 256] fp32: one buffer per (device, stream) that only grows, as eval_api.hip
-// keeps its slice partials -- launches on one stream are ordered, and a call whose shape fits allocates nothing.
-struct FrScratch {
-  float* p = nullptr;
-  size_t bytes = 0;
-};
-std::map<void*, FrScratch> g_fr_scratch[kMaxDevices];
-
-int fr_scratch(int device, void* stream, size_t bytes, float** out) {   // g_fr_mu held
-  FrScratch& w = g_fr_scratch[device][stream];
-  if (w.bytes < bytes) {
-    if (w.p) {
-      HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));   // an earlier call may still read it
-      (void)hipFree(w.p);
-      w = FrScratch();
-    }
-    HIP_TRY(hipMalloc(&w.p, bytes));
-    w.bytes = bytes;
-  }
-  *out = w.p;
-  return RCED_OK;
-}
+// The frames between the two steps of a rebuild, [N, T, 256] fp32: the stream's workspace (host_ws.h), one family for both rebuilds
+StreamWorkspace g_fr_frames;
+StreamWorkspace g_wave_ws;   // rced_wave_loss's workspace, carved in rced_wave_loss_run
 
 // frames_fr_kernel, then rebuild_fr_kernel<OLA>
 template <bool OLA>
@@ -335,26 +312,23 @@ int rebuild_fr(const float* mag_dev, const float* phase_dev, const int* frames_d
   hipStream_t st = static_cast<hipStream_t>(stream);
   float* Y = nullptr;
   if (T > 0) {
-    if (int rc = fr_scratch(device, stream, (size_t)N * T * audio::kFrame * sizeof(float), &Y)) return rc;
+    if (int rc = g_fr_frames.get(device, stream, (size_t)N * T * audio::kFrame * sizeof(float), &Y)) return rc;
     const int nblk = (T + audio::kFramesPerWg - 1) / audio::kFramesPerWg;
     if (nblk > 65535) return rced_fail(RCED_ERR_ARG, "T > 65535 * 64 frames per call");
-    hipLaunchKernelGGL(audio::fr::frames_fr_kernel, dim3(N, 2, nblk), dim3(audio::x6::kThreadsX), audio::fr::kFramesFrLdsBytes, st, mag_dev, phase_dev,
-                       frames_dev, (const unsigned short*)p.pack, (const float*)p.aux, T, W, Y);
-    HIP_TRY(hipGetLastError());
+    LAUNCH(audio::fr::frames_fr_kernel, dim3(N, 2, nblk), dim3(audio::x6::kThreadsX), audio::fr::kFramesFrLdsBytes, st, mag_dev, phase_dev,
+           frames_dev, (const unsigned short*)p.pack, (const float*)p.aux, T, W, Y);
   }
-  hipLaunchKernelGGL(audio::fr::rebuild_fr_kernel<OLA>, dim3(N), dim3(audio::x6::kThreadsX), 0, st, (const float*)Y, frames_dev, (const float*)p.aux + audio::kFrame, T, W, S,
-                     audio_dev);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(audio::fr::rebuild_fr_kernel<OLA>, dim3(N), dim3(audio::x6::kThreadsX), 0, st, (const float*)Y, frames_dev,
+         (const float*)p.aux + audio::kFrame, T, W, S, audio_dev);
   return RCED_OK;
 }
 
 }  // namespace
 
 int rced_audio_x6_tables_get(int device, int nfft, rced_audio_x6_tables* out) {
-  DeviceGuard g(device);
+  DeviceGuard g;
   AudioTables* t = nullptr;
-  if (int rc = tables(device, &t)) return rc;
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  if (int rc = tables(device, g, &t)) return rc;
   const int v = nfft == 512;
   out->stft = t->stft_x6;
   out->istft = t->istft_x6[v];
@@ -394,50 +368,6 @@ void rced_fr_tables_unpin(int device, int window, int window_name, int ola, int 
   }
 }
 
-namespace {
-
-// ---- rced_wave_loss's workspace: per (device, stream), growing only -- a call whose shape fits allocates nothing ------------------
-struct WaveWs {
-  int* frames;            // [N]
-  float *y, *u;           // [N, (T+1)*128]: the rebuild, the scaled reverse scan
-  double *ws1, *ws2;      // [N, slices, 2]
-  double* scal;           // [N, 4]
-};
-struct WaveBuf {
-  char* p = nullptr;
-  size_t bytes = 0;
-};
-std::map<void*, WaveBuf> g_wave_ws[kMaxDevices];
-std::mutex g_wave_mu;
-
-int wave_workspace(int device, void* stream, int N, int L, int slices, WaveWs* out) {
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t sig = up((size_t)N * L * sizeof(float)), part = up((size_t)N * slices * 2 * sizeof(double));
-  const size_t scal = up((size_t)N * 4 * sizeof(double)), fr = up((size_t)N * sizeof(int));
-  const size_t bytes = 2 * sig + 2 * part + scal + fr;
-  std::lock_guard<std::mutex> lk(g_wave_mu);
-  WaveBuf& w = g_wave_ws[device][stream];
-  if (w.bytes < bytes) {
-    if (w.p) {
-      HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));   // an earlier call may still read it
-      (void)hipFree(w.p);
-      w = WaveBuf();
-    }
-    HIP_TRY(hipMalloc(&w.p, bytes));
-    w.bytes = bytes;
-  }
-  char* p = w.p;
-  out->y = reinterpret_cast<float*>(p);
-  out->u = reinterpret_cast<float*>(p + sig);
-  out->ws1 = reinterpret_cast<double*>(p + 2 * sig);
-  out->ws2 = reinterpret_cast<double*>(p + 2 * sig + part);
-  out->scal = reinterpret_cast<double*>(p + 2 * sig + 2 * part);
-  out->frames = reinterpret_cast<int*>(p + 2 * sig + 2 * part + scal);
-  return RCED_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int rced_stft_num_frames(int length) { return length > 0 ? audio::num_frames(length) : 0; }
@@ -450,24 +380,18 @@ int rced_stft(const float* pcm_dev, const int* lengths_dev, int N, int L, int T,
 int rced_stft_ex(const float* pcm_dev, const int* lengths_dev, int N, int L, int T, float* mag_dev, float* phase_dev,
                  int device, void* stream, int kernels) {
   if (kernels != RCED_AUDIO_X6 && kernels != RCED_AUDIO_F32) return rced_fail(RCED_ERR_ARG, "kernels must be RCED_AUDIO_X6 (1) or RCED_AUDIO_F32 (0), got %d", kernels);
-  if (N < 0 || L < 0 || T < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
-  if (N == 0 || T == 0) return RCED_OK;
-  if (L == 0) return rced_fail(RCED_ERR_ARG, "empty signals (L = 0) with T > 0");
-  if (!pcm_dev || !mag_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
-  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
-  DeviceGuard g(device);
+  if (int rc = audio_args(N, T, true, pcm_dev && mag_dev, 512, L)) return rc == kNothingToDo ? RCED_OK : rc;
+  DeviceGuard g;
   AudioTables* t = nullptr;
-  if (int rc = tables(device, &t)) return rc;
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  if (int rc = tables(device, g, &t)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
   if (kernels == RCED_AUDIO_X6) {
-    hipLaunchKernelGGL(audio::x6::stft_x6_kernel, dim3(N, 2, range_split(N, T)), dim3(audio::x6::kThreadsX), 0, static_cast<hipStream_t>(stream),
-                       pcm_dev, lengths_dev, (const unsigned short*)t->stft_x6, L, T, mag_dev, phase_dev);
+    LAUNCH(audio::x6::stft_x6_kernel, dim3(N, 2, range_split(N, T)), dim3(audio::x6::kThreadsX), 0, st, pcm_dev, lengths_dev,
+           (const unsigned short*)t->stft_x6, L, T, mag_dev, phase_dev);
   } else {
     const dim3 grid((T + audio::kFramesPerWg - 1) / audio::kFramesPerWg, N);
-    hipLaunchKernelGGL(audio::stft_kernel, grid, dim3(audio::kThreads), 0, static_cast<hipStream_t>(stream), pcm_dev,
-                       lengths_dev, (const float*)t->stft, L, T, mag_dev, phase_dev);
+    LAUNCH(audio::stft_kernel, grid, dim3(audio::kThreads), 0, st, pcm_dev, lengths_dev, (const float*)t->stft, L, T, mag_dev, phase_dev);
   }
-  HIP_TRY(hipGetLastError());
   return RCED_OK;
 }
 
@@ -479,54 +403,40 @@ int rced_istft(const float* mag_dev, const float* phase_dev, int N, int T, int n
 int rced_istft_ex(const float* mag_dev, const float* phase_dev, int N, int T, int nfft, float* audio_dev, int device,
                   void* stream, int kernels) {
   if (kernels != RCED_AUDIO_X6 && kernels != RCED_AUDIO_F32) return rced_fail(RCED_ERR_ARG, "kernels must be RCED_AUDIO_X6 (1) or RCED_AUDIO_F32 (0), got %d", kernels);
-  if (N < 0 || T < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
-  if (nfft != 512 && nfft != 256) return rced_fail(RCED_ERR_ARG, "nfft must be 512 (reference default) or 256");
-  if (N == 0 || T == 0) return RCED_OK;
-  if (!mag_dev || !phase_dev || !audio_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
-  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
-  DeviceGuard g(device);
+  if (int rc = audio_args(N, T, true, mag_dev && phase_dev && audio_dev, nfft)) return rc == kNothingToDo ? RCED_OK : rc;
+  DeviceGuard g;
   AudioTables* t = nullptr;
-  if (int rc = tables(device, &t)) return rc;
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  if (int rc = tables(device, g, &t)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (kernels == RCED_AUDIO_X6) {
     const int v = nfft == 512, split = range_split(N, T);
     if (split == 1) {   // one workgroup per utterance: de_frame and de_emphasis inside the kernel
-      hipLaunchKernelGGL(audio::x6::istft_x6_kernel<true>, dim3(N, 1, 1), dim3(audio::x6::kThreadsX), audio::x6::kIstftLdsBytes, st, mag_dev, phase_dev,
-                         (const unsigned short*)t->istft_x6[v], (const float*)t->cim[v], (const float*)t->chead[v], T, audio_dev);
-      HIP_TRY(hipGetLastError());
+      LAUNCH(audio::x6::istft_x6_kernel<true>, dim3(N, 1, 1), dim3(audio::x6::kThreadsX), audio::x6::kIstftLdsBytes, st, mag_dev, phase_dev,
+             (const unsigned short*)t->istft_x6[v], (const float*)t->cim[v], (const float*)t->chead[v], T, audio_dev);
       return RCED_OK;
     }
-    hipLaunchKernelGGL(audio::x6::istft_x6_kernel<false>, dim3(N, 1, split), dim3(audio::x6::kThreadsX), audio::x6::kIstftLdsBytes, st, mag_dev,
-                       phase_dev, (const unsigned short*)t->istft_x6[v], (const float*)t->cim[v], (const float*)t->chead[v], T, audio_dev);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(audio::x6::istft_head_kernel, dim3(N), dim3(audio::kStep), 0, st, mag_dev, phase_dev, (const float*)t->chead[v], T, audio_dev);
+    // (every launch of this entry was followed by a check of its own before: the head's was the one after the else)
+    LAUNCH(audio::x6::istft_x6_kernel<false>, dim3(N, 1, split), dim3(audio::x6::kThreadsX), audio::x6::kIstftLdsBytes, st, mag_dev, phase_dev,
+           (const unsigned short*)t->istft_x6[v], (const float*)t->cim[v], (const float*)t->chead[v], T, audio_dev);
+    LAUNCH(audio::x6::istft_head_kernel, dim3(N), dim3(audio::kStep), 0, st, mag_dev, phase_dev, (const float*)t->chead[v], T, audio_dev);
   } else {
     const dim3 grid((T + audio::kFramesPerWg - 1) / audio::kFramesPerWg, N);
-    hipLaunchKernelGGL(audio::istft_frames_kernel, grid, dim3(audio::kThreads), 0, st, mag_dev, phase_dev,
-                       (const float*)(nfft == 512 ? t->istft512 : t->istft256), T, audio_dev);
+    LAUNCH(audio::istft_frames_kernel, grid, dim3(audio::kThreads), 0, st, mag_dev, phase_dev,
+           (const float*)(nfft == 512 ? t->istft512 : t->istft256), T, audio_dev);
   }
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(audio::deemphasis_kernel, dim3(N), dim3(audio::kThreads), 0, st, audio_dev,
-                     (T + 1) * audio::kStep);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(audio::deemphasis_kernel, dim3(N), dim3(audio::kThreads), 0, st, audio_dev, (T + 1) * audio::kStep);
   return RCED_OK;
 }
 
 int rced_istft_ola(const float* mag_dev, const float* phase_dev, const int* frames_dev, int N, int T, float* audio_dev, int device,
                    void* stream) {
-  if (N < 0 || T < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
-  if (N == 0) return RCED_OK;
-  if (!audio_dev || (T > 0 && (!mag_dev || !phase_dev))) return rced_fail(RCED_ERR_ARG, "null pointer");
-  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
-  DeviceGuard g(device);
+  if (int rc = audio_args(N, T, false, audio_dev && (T == 0 || (mag_dev && phase_dev)))) return rc == kNothingToDo ? RCED_OK : rc;
+  DeviceGuard g;
   AudioTables* t = nullptr;
-  if (int rc = tables(device, &t)) return rc;
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  if (int rc = tables(device, g, &t)) return rc;
   // one workgroup per utterance walks its blocks: the add across frames, the seam, the de-emphasis and the zero tail in one launch
-  hipLaunchKernelGGL(audio::x6::istft_ola_x6_kernel, dim3(N), dim3(audio::x6::kThreadsX), audio::x6::kOlaLdsBytes, static_cast<hipStream_t>(stream),
-                     mag_dev, phase_dev, frames_dev, (const unsigned short*)t->ola_x6, (const float*)t->ola_fix, T, audio_dev);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(audio::x6::istft_ola_x6_kernel, dim3(N), dim3(audio::x6::kThreadsX), audio::x6::kOlaLdsBytes, static_cast<hipStream_t>(stream),
+         mag_dev, phase_dev, frames_dev, (const unsigned short*)t->ola_x6, (const float*)t->ola_fix, T, audio_dev);
   return RCED_OK;
 }
 
@@ -552,40 +462,43 @@ int rced_wave_loss_run(const float* mag_dev, const float* phase_dev, const int* 
   if (N == 0) return RCED_OK;
   if (!terms_dev || !lengths_dev || (clean_stride > 0 && !clean_dev) || (T > 0 && (!mag_dev || !phase_dev)))
     return rced_fail(RCED_ERR_ARG, "null pointer");
-  DeviceGuard g(device);
+  DeviceGuard g;
   AudioTables* t = nullptr;
-  if (int rc = tables(device, &t)) return rc;
-  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  if (int rc = tables(device, g, &t)) return rc;
   const int L = (T + 1) * audio::kStep, slices = wloss::num_slices(L);
-  WaveWs w;
-  if (int rc = wave_workspace(device, stream, N, L, slices, &w)) return rc;
+  float *y, *u;        // [N, (T+1)*128]: the rebuild, the scaled reverse scan
+  double *ws1, *ws2;   // [N, slices, 2]
+  double* scal;        // [N, 4]
+  int* frames;         // [N]
+  Carve ws;
+  ws.take(&y, (size_t)N * L);
+  ws.take(&u, (size_t)N * L);
+  ws.take(&ws1, (size_t)N * slices * 2);
+  ws.take(&ws2, (size_t)N * slices * 2);
+  ws.take(&scal, (size_t)N * 4);
+  ws.take(&frames, (size_t)N);
+  if (int rc = ws.bind(device, stream, g_wave_ws)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-#define WAVE_LAUNCH(kernel, grid, block, lds, ...)                 \
-  do {                                                             \
-    hipLaunchKernelGGL(kernel, grid, block, lds, st, __VA_ARGS__); \
-    HIP_TRY(hipGetLastError());                                    \
-  } while (0)
-  WAVE_LAUNCH(wloss::frames_kernel, dim3((N + 255) / 256), dim3(256), 0, frames_dev, lengths_dev, N, T, w.frames);
-  WAVE_LAUNCH(audio::x6::istft_ola_x6_kernel, dim3(N), dim3(audio::x6::kThreadsX), audio::x6::kOlaLdsBytes, mag_dev, phase_dev,
-              (const int*)w.frames, (const unsigned short*)t->ola_x6, (const float*)t->ola_fix, T, w.y);
-  WAVE_LAUNCH(wloss::sums_kernel<0>, dim3(slices, N), dim3(wloss::kSumThreads), 0, (const float*)w.y, L, clean_dev, clean_stride, lengths_dev,
-              (const int*)w.frames, skip_edges, (const double*)nullptr, w.ws1, slices);
-  WAVE_LAUNCH(wloss::sums_kernel<1>, dim3(slices, N), dim3(wloss::kSumThreads), 0, (const float*)w.y, L, clean_dev, clean_stride, lengths_dev,
-              (const int*)w.frames, skip_edges, (const double*)w.ws1, w.ws2, slices);
-  WAVE_LAUNCH(wloss::terms_kernel, dim3(N), dim3(wloss::kSumThreads), 0, (const double*)w.ws1, (const double*)w.ws2, lengths_dev,
-              (const int*)w.frames, clean_stride, skip_edges, slices, terms_dev, w.scal);
+  LAUNCH(wloss::frames_kernel, dim3((N + 255) / 256), dim3(256), 0, st, frames_dev, lengths_dev, N, T, frames);
+  LAUNCH(audio::x6::istft_ola_x6_kernel, dim3(N), dim3(audio::x6::kThreadsX), audio::x6::kOlaLdsBytes, st, mag_dev, phase_dev,
+         (const int*)frames, (const unsigned short*)t->ola_x6, (const float*)t->ola_fix, T, y);
+  LAUNCH(wloss::sums_kernel<0>, dim3(slices, N), dim3(wloss::kSumThreads), 0, st, (const float*)y, L, clean_dev, clean_stride, lengths_dev,
+         (const int*)frames, skip_edges, (const double*)nullptr, ws1, slices);
+  LAUNCH(wloss::sums_kernel<1>, dim3(slices, N), dim3(wloss::kSumThreads), 0, st, (const float*)y, L, clean_dev, clean_stride, lengths_dev,
+         (const int*)frames, skip_edges, (const double*)ws1, ws2, slices);
+  LAUNCH(wloss::terms_kernel, dim3(N), dim3(wloss::kSumThreads), 0, st, (const double*)ws1, (const double*)ws2, lengths_dev,
+         (const int*)frames, clean_stride, skip_edges, slices, terms_dev, scal);
   if (grad_dev && T > 0) {
-    WAVE_LAUNCH(wloss::reverse_kernel, dim3(N), dim3(audio::x6::kThreadsX), 0, (const float*)w.y, L, clean_dev, clean_stride, lengths_dev,
-                (const int*)w.frames, skip_edges, (const double*)w.scal, 2.0 * w_sse * inv_batch, w_si_sdr * inv_batch,
-                (const float*)t->adj_inv, w.u);
+    LAUNCH(wloss::reverse_kernel, dim3(N), dim3(audio::x6::kThreadsX), 0, st, (const float*)y, L, clean_dev, clean_stride, lengths_dev,
+           (const int*)frames, skip_edges, (const double*)scal, 2.0 * w_sse * inv_batch, w_si_sdr * inv_batch,
+           (const float*)t->adj_inv, u);
     if (accumulate)
-      WAVE_LAUNCH(wloss::adjoint_kernel<true>, dim3(N, 2, range_split(N, T)), dim3(audio::x6::kThreadsX), 0, (const float*)w.u, L,
-                  (const int*)w.frames, (const unsigned short*)t->adj_x6, phase_dev, T, grad_dev);
+      LAUNCH(wloss::adjoint_kernel<true>, dim3(N, 2, range_split(N, T)), dim3(audio::x6::kThreadsX), 0, st, (const float*)u, L,
+             (const int*)frames, (const unsigned short*)t->adj_x6, phase_dev, T, grad_dev);
     else
-      WAVE_LAUNCH(wloss::adjoint_kernel<false>, dim3(N, 2, range_split(N, T)), dim3(audio::x6::kThreadsX), 0, (const float*)w.u, L,
-                  (const int*)w.frames, (const unsigned short*)t->adj_x6, phase_dev, T, grad_dev);
+      LAUNCH(wloss::adjoint_kernel<false>, dim3(N, 2, range_split(N, T)), dim3(audio::x6::kThreadsX), 0, st, (const float*)u, L,
+             (const int*)frames, (const unsigned short*)t->adj_x6, phase_dev, T, grad_dev);
   }
-#undef WAVE_LAUNCH
   return RCED_OK;
 }
 
@@ -606,30 +519,21 @@ int rced_stft_num_frames_fr(int length, int window, int stride) {
 int rced_stft_fr(const float* pcm_dev, const int* lengths_dev, int N, int L, int T, int window, int stride, int window_name, float* mag_dev,
                  float* phase_dev, int device, void* stream) {
   if (int rc = framing_check(window, stride, window_name)) return rc;
-  if (N < 0 || L < 0 || T < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
-  if (N == 0 || T == 0) return RCED_OK;
-  if (L == 0) return rced_fail(RCED_ERR_ARG, "empty signals (L = 0) with T > 0");
-  if (!pcm_dev || !mag_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
-  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
+  if (int rc = audio_args(N, T, true, pcm_dev && mag_dev, 512, L)) return rc == kNothingToDo ? RCED_OK : rc;
   DeviceGuard g(device);
   std::lock_guard<std::mutex> lk(g_fr_mu);
   FrPack p;
   if (int rc = fr_pack(device, kFrStft, window, window_name, &p)) return rc;
   if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
-  hipLaunchKernelGGL(audio::fr::stft_fr_kernel, dim3(N, 2, range_split(N, T)), dim3(audio::x6::kThreadsX), audio::fr::kStftFrLdsBytes,
-                     static_cast<hipStream_t>(stream), pcm_dev, lengths_dev, (const unsigned short*)p.pack, L, T, window, stride, mag_dev, phase_dev);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(audio::fr::stft_fr_kernel, dim3(N, 2, range_split(N, T)), dim3(audio::x6::kThreadsX), audio::fr::kStftFrLdsBytes,
+         static_cast<hipStream_t>(stream), pcm_dev, lengths_dev, (const unsigned short*)p.pack, L, T, window, stride, mag_dev, phase_dev);
   return RCED_OK;
 }
 
 int rced_istft_fr(const float* mag_dev, const float* phase_dev, int N, int T, int nfft, int window, int stride, float* audio_dev, int device,
                   void* stream) {
   if (int rc = framing_check(window, stride, RCED_WINDOW_HAMMING)) return rc;
-  if (N < 0 || T < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
-  if (nfft != 512 && nfft != 256) return rced_fail(RCED_ERR_ARG, "nfft must be 512 (reference default) or 256");
-  if (N == 0 || T == 0) return RCED_OK;
-  if (!mag_dev || !phase_dev || !audio_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
-  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
+  if (int rc = audio_args(N, T, true, mag_dev && phase_dev && audio_dev, nfft)) return rc == kNothingToDo ? RCED_OK : rc;
   return rebuild_fr<false>(mag_dev, phase_dev, nullptr, N, T, nfft == 512 ? kFrRef512 : kFrRef256, window, stride, RCED_WINDOW_HAMMING, audio_dev,
                            device, stream);
 }
@@ -637,10 +541,7 @@ int rced_istft_fr(const float* mag_dev, const float* phase_dev, int N, int T, in
 int rced_istft_ola_fr(const float* mag_dev, const float* phase_dev, const int* frames_dev, int N, int T, int window, int stride, int window_name,
                       float* audio_dev, int device, void* stream) {
   if (int rc = framing_check(window, stride, window_name)) return rc;
-  if (N < 0 || T < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
-  if (N == 0) return RCED_OK;
-  if (!audio_dev || (T > 0 && (!mag_dev || !phase_dev))) return rced_fail(RCED_ERR_ARG, "null pointer");
-  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
+  if (int rc = audio_args(N, T, false, audio_dev && (T == 0 || (mag_dev && phase_dev)))) return rc == kNothingToDo ? RCED_OK : rc;
   return rebuild_fr<true>(mag_dev, phase_dev, frames_dev, N, T, kFrOla, window, stride, window_name, audio_dev, device, stream);
 }
 

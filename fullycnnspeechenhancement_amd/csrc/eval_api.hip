@@ -1,13 +1,11 @@
 // C ABI of the evaluation loop's device pieces (include/rced.h, "evaluation" section): host side.
 #include <hip/hip_runtime.h>
 
-#include <cassert>
 #include <cmath>
-#include <map>
-#include <mutex>
 #include <vector>
 
 #include "../../include/rced.h"
+#include "host_ws.h"
 #include "kernels_bsseval.h"
 #include "kernels_conv.h"
 #include "kernels_eval.h"
@@ -19,59 +17,9 @@ using namespace rced;
 
 namespace {
 
-// Slice partials [N, slices, 2] double, one buffer per (device, stream): launches on one stream are ordered, so the buffer
-// of a stream is never shared by two calls in flight.  It only grows; a call whose shape fits allocates nothing, so the
-// entries can be stream-captured after one warm-up call of the shape.
-struct Workspace {
-  double* p = nullptr;
-  size_t bytes = 0;
-};
-// STOI, SI-SDR, the segmental SNR, LLR, WSS, the BSS Eval SDR, fwSNRseg and CD keep buffers of their own: none ever moves the one another entry's captured graph reads
-enum class Ws { Slices, Stoi, SiSdr, SegSnr, Llr, Wss, Bss, FwSeg, Cepd, Kinds };
-std::map<void*, Workspace> g_ws[(int)Ws::Kinds][kMaxDevices];
-std::mutex g_mu;
-
-int workspace(int device, void* stream, Ws which, size_t bytes, double** out) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  Workspace& w = g_ws[(int)which][device][stream];
-  if (w.bytes < bytes) {
-    if (w.p) {
-      HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));   // an earlier call may still read it
-      (void)hipFree(w.p);
-      w = Workspace();
-    }
-    HIP_TRY(hipMalloc(&w.p, bytes));
-    w.bytes = bytes;
-  }
-  *out = w.p;
-  return RCED_OK;
-}
-
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// An entry's workspace, carved: take() books `count` elements of T at the next 256-byte boundary, in the order of the calls;
-// bind() gets the whole from workspace() and points every booked pointer at its part.  At most 8 buffers.
-struct Carve {
-  void* slot[8];
-  size_t at[8], bytes = 0;
-  int n = 0;
-  template <class T>
-  void take(T** p, size_t count) {
-    assert(n < 8);
-    slot[n] = p;
-    at[n++] = bytes;
-    bytes += align256(count * sizeof(T));
-  }
-  int bind(int device, void* stream, Ws which) {
-    double* base = nullptr;
-    if (int rc = workspace(device, stream, which, bytes, &base)) return rc;
-    for (int i = 0; i < n; ++i) {
-      char* p = reinterpret_cast<char*>(base) + at[i];
-      memcpy(slot[i], &p, sizeof p);
-    }
-    return RCED_OK;
-  }
-};
+// One buffer family (host_ws.h) per score, and one for the slice partials [N, slices, 2] double of rced_sdr and rced_mix_snr: none
+// ever moves the buffer another entry's captured graph reads.
+StreamWorkspace g_ws_slices, g_ws_stoi, g_ws_si_sdr, g_ws_seg_snr, g_ws_llr, g_ws_wss, g_ws_bss, g_ws_fwseg, g_ws_cepd;
 
 // Two padded row matrices scored pair by pair, row n of `ref` against row n of `est`: what every score's entry takes first
 struct Pairs {
@@ -91,19 +39,17 @@ int check_pairs(const Pairs& p, bool outputs, int max_len, const char* max_text)
   return RCED_OK;
 }
 
-#define LAUNCH(kernel, grid, block, lds, st, ...)                         \
-  do {                                                                    \
-    hipLaunchKernelGGL(kernel, grid, block, lds, st, __VA_ARGS__);        \
-    HIP_TRY(hipGetLastError());                                           \
-  } while (0)
-
 // ---- STOI tables: built on the host once per process, uploaded once per device ---------------------------------------------------
 struct StoiTables {
   double* tab = nullptr;             // resampler taps [0, 365), first window [368, 624)
   unsigned short* apack = nullptr;   // the windowed DFT matrix, three bf16 parts, MFMA fragment order
+  bool built() const { return tab; }
+  void release() {
+    (void)hipFree(tab);
+    (void)hipFree(apack);
+  }
 };
-StoiTables g_stoi[kMaxDevices];
-std::mutex g_stoi_mu;
+DeviceOnce<StoiTables> g_stoi;
 
 double bessel_i0(double x) {         // power series: converges to the last bit in < 30 terms for x <= 6
   double s = 1.0, t = 1.0;
@@ -150,9 +96,7 @@ double stoi_coef(int row, int k) {
 }
 
 int stoi_tables(int device, StoiTables** out) {
-  std::lock_guard<std::mutex> lk(g_stoi_mu);
-  StoiTables& t = g_stoi[device];
-  if (!t.tab) {
+  return g_stoi.get(device, 0, [](StoiTables& t) -> int {
     std::vector<double> tab(stoi::kTabLen, 0.0);
     const std::vector<double> taps = stoi_taps();
     std::copy(taps.begin(), taps.end(), tab.begin());
@@ -160,18 +104,9 @@ int stoi_tables(int device, StoiTables** out) {
     const std::vector<unsigned short> pack = x6dft::pack_x6(stoi::kMTiles, stoi_coef);
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(stoi::band_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 stoi::kBandLdsBytes));
-    double* dt = nullptr;
-    unsigned short* dp = nullptr;
-    if (int rc = upload(&dt, tab, "STOI tables")) return rc;
-    if (int rc = upload(&dp, pack, "STOI tables")) {
-      (void)hipFree(dt);
-      return rc;
-    }
-    t.apack = dp;
-    t.tab = dt;
-  }
-  *out = &t;
-  return RCED_OK;
+    if (int rc = upload(&t.tab, tab, "STOI tables")) return rc;
+    return upload(&t.apack, pack, "STOI tables");
+  }, out);
 }
 
 // ---- WSS tables: built on the host in fp64 once per process and rate, uploaded once per device -----------------------------------
@@ -179,9 +114,12 @@ struct WssTables {
   double* coef = nullptr;            // the DFT's cos / -sin columns in MFMA fragment order (sepm::wss_coef_len)
   double* filt = nullptr;            // [25][kBins] critical-band filters
   int* range = nullptr;              // [25][2]: a filter's nonzero bins [lo, hi)
+  bool built() const { return coef; }
+  void release() {
+    for (void* p : {(void*)coef, (void*)filt, (void*)range}) (void)hipFree(p);
+  }
 };
-WssTables g_wss[kMaxDevices][2];     // [device][fs == 16000]
-std::mutex g_wss_mu;
+DeviceOnce<WssTables, 2> g_wss;      // [device][fs == 16000]
 
 const double kWssCentre[sepm::kBands] = {50.0,    120.0,   190.0,   260.0,   330.0,   400.0,   470.0,   540.0,   617.372,
                                          703.378, 798.717, 904.128, 1020.38, 1148.30, 1288.72, 1442.54, 1610.70, 1794.16,
@@ -215,9 +153,7 @@ std::vector<double> sepm_dft_stream(int W, int bin0) {
 }
 
 int wss_tables(int device, int fs, WssTables** out) {
-  std::lock_guard<std::mutex> lk(g_wss_mu);
-  WssTables& t = g_wss[device][fs == 16000];
-  if (!t.coef) {
+  return g_wss.get(device, fs == 16000, [fs](WssTables& t) -> int {
     const int W = eval::seg_window(fs), nb = sepm_dft_size(W) / 2;
     const double fmax = fs / 2.0;
     const std::vector<double> coef = sepm_dft_stream(W, 0);
@@ -238,40 +174,25 @@ int wss_tables(int device, int fs, WssTables** out) {
       range[2 * i] = lo < hi ? lo : 0;
       range[2 * i + 1] = hi;
     }
-    double *dc = nullptr, *df = nullptr;
-    int* dr = nullptr;
-    if (int rc = upload(&dc, coef, "WSS tables")) return rc;
-    if (int rc = upload(&df, filt, "WSS tables")) {
-      (void)hipFree(dc);
-      return rc;
-    }
-    if (int rc = upload(&dr, range, "WSS tables")) {
-      (void)hipFree(dc);
-      (void)hipFree(df);
-      return rc;
-    }
-    t.filt = df;
-    t.range = dr;
-    t.coef = dc;
-  }
-  *out = &t;
-  return RCED_OK;
+    if (int rc = upload(&t.coef, coef, "WSS tables")) return rc;
+    if (int rc = upload(&t.filt, filt, "WSS tables")) return rc;
+    return upload(&t.range, range, "WSS tables");
+  }, out);
 }
 
 // ---- fwSNRseg: WSS's tables, and at 16 kHz the stream of the upper 256 bins, uploaded once per device -----------------------------
 struct FwsegTables {
   const WssTables* wss = nullptr;
   double* coef_hi = nullptr;         // bins 256 .. 511 at 16 kHz; NULL at 8 kHz, whose 256 bins WSS's stream covers
+  bool built() const { return wss; }
+  void release() { (void)hipFree(coef_hi); }
 };
-FwsegTables g_fwseg[kMaxDevices][2];
-std::mutex g_fwseg_mu;
+DeviceOnce<FwsegTables, 2> g_fwseg;
 
 int fwseg_tables(int device, int fs, FwsegTables** out) {
   WssTables* w = nullptr;
-  if (int rc = wss_tables(device, fs, &w)) return rc;
-  std::lock_guard<std::mutex> lk(g_fwseg_mu);
-  FwsegTables& t = g_fwseg[device][fs == 16000];
-  if (!t.wss) {
+  if (int rc = wss_tables(device, fs, &w)) return rc;   // outside g_fwseg's lock
+  return g_fwseg.get(device, fs == 16000, [fs, w](FwsegTables& t) -> int {
     const int W = eval::seg_window(fs), nb = sepm_dft_size(W) / 2;
     if (nb != (fs == 16000 ? 2 : 1) * sepm::kBins) return rced_fail(RCED_ERR_STATE, "fwSNRseg: %d bins at %d Hz", nb, fs);
     // the magnitudes of every bin stand in LDS: a little over 64 KB a workgroup
@@ -284,9 +205,8 @@ int fwseg_tables(int device, int fs, FwsegTables** out) {
       HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sepm::fwseg_lds_bytes(W, 2, nb)));
     }
     t.wss = w;
-  }
-  *out = &t;
-  return RCED_OK;
+    return RCED_OK;
+  }, out);
 }
 
 // what rced_llr, rced_wss, rced_fwseg and rced_cepd check alike; *nfcap = the frames of the longest utterance the strides allow, at least 1
@@ -342,7 +262,7 @@ int rced_stoi_ex(const float* ref_dev, int ref_stride, const float* est_dev, int
   ws.take(&dseg_ext, (size_t)N * mcap);      // extended
   ws.take(&kept, (size_t)N * fcap);
   ws.take(&cnt, (size_t)N * 4);
-  if (int rc = ws.bind(device, stream, Ws::Stoi)) return rc;
+  if (int rc = ws.bind(device, stream, g_ws_stoi)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (l10 > 0)
     LAUNCH(stoi::resample_kernel, dim3((l10 + 255) / 256, 2, N), dim3(256), 0, st, ref_dev, ref_stride, est_dev, est_stride, lengths_dev,
@@ -386,7 +306,7 @@ int rced_si_sdr(const float* ref_dev, int ref_stride, const float* est_dev, int 
   const int cap = p.cap(), slices = eval::num_slices(cap) > 0 ? eval::num_slices(cap) : 1;
   const size_t pass = (size_t)N * slices * 2;            // doubles per pass: [N, slices, 2]; the two passes lie back to back, unpadded
   double* ws1 = nullptr;
-  if (int rc = workspace(device, stream, Ws::SiSdr, 2 * pass * sizeof(double), &ws1)) return rc;
+  if (int rc = g_ws_si_sdr.get(device, stream, 2 * pass * sizeof(double), &ws1)) return rc;
   double* ws2 = ws1 + pass;
   hipStream_t st = static_cast<hipStream_t>(stream);
   LAUNCH(eval::si_sdr_dot_kernel, dim3(slices, N), dim3(eval::kThreads), 0, st, ref_dev, ref_stride, est_dev, est_stride, lengths_dev,
@@ -411,7 +331,7 @@ int rced_seg_snr(const float* ref_dev, int ref_stride, const float* est_dev, int
   const int cap = p.cap(), nfcap = eval::seg_frames(cap, W) > 0 ? eval::seg_frames(cap, W) : 1;
   const int blocks = (nfcap + eval::kSegFramesPerBlock - 1) / eval::kSegFramesPerBlock;
   double* snr = nullptr;
-  if (int rc = workspace(device, stream, Ws::SegSnr, (size_t)N * nfcap * sizeof(double), &snr)) return rc;
+  if (int rc = g_ws_seg_snr.get(device, stream, (size_t)N * nfcap * sizeof(double), &snr)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   LAUNCH(eval::seg_snr_frame_kernel, dim3(blocks, N), dim3(eval::kThreads), 0, st, ref_dev, ref_stride, est_dev, est_stride,
          lengths_dev, cap, W, snr, nfcap);
@@ -435,7 +355,7 @@ int rced_llr(const float* ref_dev, int ref_stride, const float* est_dev, int est
   ws.take(&lags, (size_t)N * nfcap * 2 * sepm::kMaxLags);
   ws.take(&d, (size_t)N * nfcap);
   ws.take(&sorted, (size_t)N * nfcap);
-  if (int rc = ws.bind(device, stream, Ws::Llr)) return rc;
+  if (int rc = ws.bind(device, stream, g_ws_llr)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   LAUNCH(sepm::llr_frame_kernel, dim3((nfcap + sepm::kLlrFramesPerBlock - 1) / sepm::kLlrFramesPerBlock, N), dim3(sepm::kThreads), 0, st,
          ref_dev, ref_stride, est_dev, est_stride, lengths_dev, cap, W, P, lags, nfcap);
@@ -465,7 +385,7 @@ int rced_wss(const float* ref_dev, int ref_stride, const float* est_dev, int est
   ws.take(&energy, (size_t)N * 2 * nfcap * sepm::kBands);
   ws.take(&d, (size_t)N * nfcap);
   ws.take(&sorted, (size_t)N * nfcap);
-  if (int rc = ws.bind(device, stream, Ws::Wss)) return rc;
+  if (int rc = ws.bind(device, stream, g_ws_wss)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (W == sepm::kMaxW)           // 16 kHz: 16 frames of 480 samples fill the LDS; 8 kHz: 32 frames of 240
     LAUNCH(sepm::wss_spectrum_kernel<1>, dim3((nfcap + 15) / 16, 2, N), dim3(sepm::kThreads), sepm::wss_lds_bytes(W, 1), st, ref_dev,
@@ -495,7 +415,7 @@ int rced_fwseg(const float* ref_dev, int ref_stride, const float* est_dev, int e
   Carve ws;
   ws.take(&bands, (size_t)N * 2 * nfcap * sepm::kBands);
   ws.take(&d, (size_t)N * nfcap);
-  if (int rc = ws.bind(device, stream, Ws::FwSeg)) return rc;
+  if (int rc = ws.bind(device, stream, g_ws_fwseg)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   constexpr auto spectrum_16k = sepm::fwseg_spectrum_kernel<1, 2>;
   constexpr auto spectrum_8k = sepm::fwseg_spectrum_kernel<2, 1>;
@@ -528,7 +448,7 @@ int rced_cepd(const float* ref_dev, int ref_stride, const float* est_dev, int es
   ws.take(&lags, (size_t)N * nfcap * 2 * sepm::kMaxLags);
   ws.take(&d, (size_t)N * nfcap);
   ws.take(&sorted, (size_t)N * nfcap);
-  if (int rc = ws.bind(device, stream, Ws::Cepd)) return rc;
+  if (int rc = ws.bind(device, stream, g_ws_cepd)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   LAUNCH(sepm::llr_frame_kernel, dim3((nfcap + sepm::kLlrFramesPerBlock - 1) / sepm::kLlrFramesPerBlock, N), dim3(sepm::kThreads), 0, st,
          ref_dev, ref_stride, est_dev, est_stride, lengths_dev, cap, W, order, lags, nfcap);
@@ -562,7 +482,7 @@ int rced_bss_sdr(const float* ref_dev, int ref_stride, const float* est_dev, int
   ws.take(&part, (size_t)N * 2 * slices * F);
   ws.take(&c, (size_t)N * F);
   ws.take(&pws, (size_t)N * pslices * 2);
-  if (int rc = ws.bind(device, stream, Ws::Bss)) return rc;
+  if (int rc = ws.bind(device, stream, g_ws_bss)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   LAUNCH(bss::correlate_kernel, dim3(slices, 2, N), dim3(bss::kThreads), 0, st, ref_dev, ref_stride, est_dev, est_stride, lengths_dev,
          cap, F, part, slices);
@@ -582,7 +502,7 @@ int rced_sdr(const float* ref_dev, int ref_stride, const float* est_dev, int est
   if (on.rc) return on.rc;
   const int cap = p.cap(), slices = eval::num_slices(cap) > 0 ? eval::num_slices(cap) : 1;
   double* ws = nullptr;
-  if (int rc = workspace(device, stream, Ws::Slices, (size_t)N * slices * 2 * sizeof(double), &ws)) return rc;
+  if (int rc = g_ws_slices.get(device, stream, (size_t)N * slices * 2 * sizeof(double), &ws)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   LAUNCH(eval::sdr_partial_kernel, dim3(slices, N), dim3(eval::kThreads), 0, st, ref_dev, ref_stride, est_dev, est_stride, lengths_dev,
          cap, ws, slices);
@@ -604,7 +524,7 @@ int rced_mix_snr(const float* speech_dev, const int* speech_len_dev, int N, int 
   if (on.rc) return on.rc;
   const int slices = eval::num_slices(Ls);
   double* ws = nullptr;
-  if (int rc = workspace(device, stream, Ws::Slices, (size_t)N * slices * 2 * sizeof(double), &ws)) return rc;
+  if (int rc = g_ws_slices.get(device, stream, (size_t)N * slices * 2 * sizeof(double), &ws)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   LAUNCH(eval::mix_partial_kernel, dim3(slices, N), dim3(eval::kThreads), 0, st, speech_dev, speech_len_dev, Ls, noise_dev,
          noise_len_dev, Ln, start_dev, gains_dev, n_gains, ws, slices);

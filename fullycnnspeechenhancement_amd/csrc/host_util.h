@@ -6,7 +6,9 @@
 #include <climits>
 #include <cstddef>
 #include <cstring>
+#include <initializer_list>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/rced.h"
@@ -20,6 +22,15 @@ int rced_fail(int code, const char* fmt, ...);   // rced_api.hip: sets the threa
       return rced_fail(e_ == hipErrorOutOfMemory ? RCED_ERR_ALLOC : RCED_ERR_HIP, "%s: %s", #expr, \
                        hipGetErrorString(e_));                                                 \
   } while (0)
+
+// A launch on `st`, then the error it may have left: the pair every entry is made of
+#define LAUNCH(kernel, grid, block, lds, st, ...)                  \
+  do {                                                             \
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, __VA_ARGS__); \
+    HIP_TRY(hipGetLastError());                                    \
+  } while (0)
+
+constexpr int kMaxDevices = 16;   // the length of every per-device table of the library (check_device's limit)
 
 struct DeviceGuard {  // run on the given device, restore the caller's current device after
   int prev = -1;
@@ -73,6 +84,18 @@ int reset_lanes(T* state, size_t per_lane, int lanes, int lane, int device, hipS
   return RCED_OK;
 }
 
+template <class... A>
+const void* kernel_ptr(void (*kernel)(A...)) { return reinterpret_cast<const void*>(kernel); }
+
+// Each {kernel_ptr(kernel), bytes} may ask for that much dynamic LDS from now on; stops at the first failure.  `what`: "istft LDS"
+inline int set_dynamic_lds(std::initializer_list<std::pair<const void*, int>> kernels, const char* what) {
+  for (const auto& k : kernels) {
+    const hipError_t e = hipFuncSetAttribute(k.first, hipFuncAttributeMaxDynamicSharedMemorySize, k.second);
+    if (e != hipSuccess) return rced_fail(RCED_ERR_HIP, "hipFuncSetAttribute(%s): %s", what, hipGetErrorString(e));
+  }
+  return RCED_OK;
+}
+
 // The refusals of a PCM format, in the words every resampling entry uses
 inline int check_rates(int sr_in, int sr_out) {
   return sr_in <= 0 || sr_out <= 0 ? rced_fail(RCED_ERR_ARG, "sample rates must be positive, got %d -> %d", sr_in, sr_out) : RCED_OK;
@@ -88,14 +111,15 @@ inline int check_pcm_dtypes(int src_dtype, int out_dtype) {
   return RCED_OK;
 }
 
-// f(SRC_F32, OUT_F32) with the two PCM types as std::true_type / std::false_type: a kernel template's <SRC_F32, OUT_F32> from dtypes
+// f(SRC_F32, OUT_F32) with the two PCM types as std::true_type / std::false_type: a kernel template's <SRC_F32, OUT_F32> from dtypes;
+// what f returns (the code of its launch)
 template <class F>
-void with_pcm_types(int src_dtype, int out_dtype, F f) {
+int with_pcm_types(int src_dtype, int out_dtype, F f) {
   const bool sf = src_dtype == RCED_PCM_F32, of = out_dtype == RCED_PCM_F32;
-  if (sf && of) f(std::true_type(), std::true_type());
-  else if (sf) f(std::true_type(), std::false_type());
-  else if (of) f(std::false_type(), std::true_type());
-  else f(std::false_type(), std::false_type());
+  if (sf && of) return f(std::true_type(), std::true_type());
+  if (sf) return f(std::true_type(), std::false_type());
+  if (of) return f(std::false_type(), std::true_type());
+  return f(std::false_type(), std::false_type());
 }
 
 // A host vector as a fresh device allocation.  *dev is written only after the copy succeeded (a caller may test it for "built");

@@ -8,8 +8,6 @@
 #include "host_util.h"
 #include "rced_spec.h"
 
-constexpr int kMaxDevices = 16;   // the length of every per-device table of the library (check_device's limit)
-
 // kernel kinds for the built-in HIP-event profiler ("profile" option)
 enum {
   RCED_K_GENERIC = 0,   // conv_layer_generic (layerwise path)

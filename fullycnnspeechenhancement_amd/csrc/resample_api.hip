@@ -189,11 +189,10 @@ int rced_resample(const void* src_dev, int src_dtype, int channels, long long sr
   P.L = L;
   const dim3 grid((L + P.tile - 1) / P.tile, N), block(resample::kThreads);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  with_pcm_types(src_dtype, out_dtype, [&](auto sf, auto of) {
-    hipLaunchKernelGGL((resample::resample_kernel<decltype(sf)::value, decltype(of)::value>), grid, block, 0, st, P);
+  return with_pcm_types(src_dtype, out_dtype, [&](auto sf, auto of) -> int {
+    LAUNCH((resample::resample_kernel<decltype(sf)::value, decltype(of)::value>), grid, block, 0, st, P);
+    return RCED_OK;
   });
-  HIP_TRY(hipGetLastError());
-  return RCED_OK;
 }
 
 }  // extern "C"

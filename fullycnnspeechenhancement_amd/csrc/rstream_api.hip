@@ -87,11 +87,10 @@ rced_lanes format_of(int sr_in, int sr_out, int channels, int src_dtype, int out
   return f;
 }
 
-// one workgroup a lane: kernel(sf, of) launches the family's kernel for the handle's two PCM types on `st`
+// one workgroup a lane: kernel(sf, of) launches the family's kernel for the handle's two PCM types on `st` and returns the launch's code
 template <class Kernel>
 int launch_lanes(rced_lanes* h, hipStream_t st, Kernel kernel) {
-  with_pcm_types(h->src_dtype, h->out_dtype, kernel);
-  HIP_TRY(hipGetLastError());
+  if (int rc = with_pcm_types(h->src_dtype, h->out_dtype, kernel)) return rc;
   h->last = st;
   return RCED_OK;
 }
@@ -122,8 +121,9 @@ int launch(rced_rstream* h, const void* in, int in_frames, const int* flags, int
   P.out = out;
   P.out_cols = out_cols;
   P.out_counts = out_counts;
-  return launch_lanes(h, st, [&](auto sf, auto of) {
-    hipLaunchKernelGGL((rstream::rstream_kernel<decltype(sf)::value, decltype(of)::value>), dim3(h->lanes), dim3(rstream::kThreads), 0, st, P);
+  return launch_lanes(h, st, [&](auto sf, auto of) -> int {
+    LAUNCH((rstream::rstream_kernel<decltype(sf)::value, decltype(of)::value>), dim3(h->lanes), dim3(rstream::kThreads), 0, st, P);
+    return RCED_OK;
   });
 }
 
@@ -165,8 +165,9 @@ int launch(rced_rfree* h, const void* in, int in_cols, const int* counts, const 
   P.out = out;
   P.out_cols = out_cols;
   P.out_counts = out_counts;
-  return launch_lanes(h, st, [&](auto sf, auto of) {
-    hipLaunchKernelGGL((rfree::rfree_kernel<decltype(sf)::value, decltype(of)::value>), dim3(h->lanes), dim3(rfree::kThreads), 0, st, P);
+  return launch_lanes(h, st, [&](auto sf, auto of) -> int {
+    LAUNCH((rfree::rfree_kernel<decltype(sf)::value, decltype(of)::value>), dim3(h->lanes), dim3(rfree::kThreads), 0, st, P);
+    return RCED_OK;
   });
 }
 
@@ -217,9 +218,7 @@ int rced_rstream_started(rced_rstream* h, const int* active_dev, int* started_de
   if (!started_dev) return rced_fail(RCED_ERR_ARG, "null pointer");
   ON_DEVICE(h->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(rstream::started_kernel, dim3((h->lanes + 255) / 256), dim3(256), 0, st, (const long long*)h->state, h->words, active_dev,
-                     h->lanes, started_dev);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(rstream::started_kernel, dim3((h->lanes + 255) / 256), dim3(256), 0, st, (const long long*)h->state, h->words, active_dev, h->lanes, started_dev);
   h->last = st;
   return RCED_OK;
 }

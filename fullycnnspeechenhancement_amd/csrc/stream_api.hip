@@ -62,20 +62,16 @@ void release(rced_stream* s) {
 int run_fr(rced_stream* s, const float* in, const int* flags, int finish, int K, float* out, int* out_counts, hipStream_t st) {
   const int S = s->lanes, W = s->window, hop = s->stride;
   const dim3 grid((S * K + audio::kFramesPerWg - 1) / audio::kFramesPerWg, 2), block(audio::x6::kThreadsX);
-  hipLaunchKernelGGL(af::stream_fr_stft_kernel, grid, block, af::kStftLds, st, in, flags, finish, s->ft.stft, (const float*)s->state, S, K, W, hop,
-                     s->win, s->phw);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(af::stream_fr_stft_kernel, grid, block, af::kStftLds, st, in, flags, finish, s->ft.stft, (const float*)s->state, S, K, W, hop, s->win, s->phw);
   if (int rc = rced_forward(s->model, s->win, s->masks, S, as::kKeep + K, st)) return rc;
-  hipLaunchKernelGGL(af::stream_fr_frames_kernel, grid, block, af::kFramesLds, st, (const float*)s->masks, (const float*)s->phw, flags, finish,
-                     s->ft.rebuild, s->ft.cim, (const float*)s->state, S, K, window_hops(s), W, hop, s->frames);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(af::stream_fr_frames_kernel, grid, block, af::kFramesLds, st, (const float*)s->masks, (const float*)s->phw, flags, finish, s->ft.rebuild,
+         s->ft.cim, (const float*)s->state, S, K, window_hops(s), W, hop, s->frames);
   if (s->rebuild == RCED_STREAM_REBUILD_OLA)
-    hipLaunchKernelGGL(af::stream_fr_rebuild_kernel<true>, dim3(S), block, 0, st, (const float*)s->frames, s->ft.w2, in, flags, finish,
-                       (const float*)s->win, (const float*)s->phw, s->state, K, window_hops(s), W, hop, out, out_counts);
+    LAUNCH(af::stream_fr_rebuild_kernel<true>, dim3(S), block, 0, st, (const float*)s->frames, s->ft.w2, in, flags, finish, (const float*)s->win,
+           (const float*)s->phw, s->state, K, window_hops(s), W, hop, out, out_counts);
   else
-    hipLaunchKernelGGL(af::stream_fr_rebuild_kernel<false>, dim3(S), block, 0, st, (const float*)s->frames, s->ft.w2, in, flags, finish,
-                       (const float*)s->win, (const float*)s->phw, s->state, K, window_hops(s), W, hop, out, out_counts);
-  HIP_TRY(hipGetLastError());
+    LAUNCH(af::stream_fr_rebuild_kernel<false>, dim3(S), block, 0, st, (const float*)s->frames, s->ft.w2, in, flags, finish, (const float*)s->win,
+           (const float*)s->phw, s->state, K, window_hops(s), W, hop, out, out_counts);
   s->last = st;
   return RCED_OK;
 }
@@ -84,20 +80,16 @@ int run_fr(rced_stream* s, const float* in, const int* flags, int finish, int K,
 int run(rced_stream* s, const float* in, const int* flags, int finish, int K, float* out, int* out_counts, hipStream_t st) {
   if (s->fr) return run_fr(s, in, flags, finish, K, out, out_counts, st);
   const int S = s->lanes;
-  hipLaunchKernelGGL(as::stream_stft_kernel, dim3((S * K + audio::kFramesPerWg - 1) / audio::kFramesPerWg, 2), dim3(audio::x6::kThreadsX),
-                     as::kStreamStftLds, st, in, flags, finish, s->tab.stft, (const float*)s->state, S, K, s->win, s->phw);
-  HIP_TRY(hipGetLastError());
+  LAUNCH(as::stream_stft_kernel, dim3((S * K + audio::kFramesPerWg - 1) / audio::kFramesPerWg, 2), dim3(audio::x6::kThreadsX), as::kStreamStftLds, st,
+         in, flags, finish, s->tab.stft, (const float*)s->state, S, K, s->win, s->phw);
   if (int rc = rced_forward(s->model, s->win, s->masks, S, as::kKeep + K, st)) return rc;
   const int lpw = audio::kFramesPerWg / K;
   if (s->rebuild == RCED_STREAM_REBUILD_OLA)
-    hipLaunchKernelGGL(as::stream_istft_ola_kernel, dim3((S + lpw - 1) / lpw), dim3(audio::x6::kThreadsX), as::kStreamOlaLds, st,
-                       (const float*)s->masks, (const float*)s->win, (const float*)s->phw, in, flags, finish, s->tab.ola, s->tab.ola_fix,
-                       s->state, S, K, out, out_counts);
+    LAUNCH(as::stream_istft_ola_kernel, dim3((S + lpw - 1) / lpw), dim3(audio::x6::kThreadsX), as::kStreamOlaLds, st, (const float*)s->masks,
+           (const float*)s->win, (const float*)s->phw, in, flags, finish, s->tab.ola, s->tab.ola_fix, s->state, S, K, out, out_counts);
   else
-    hipLaunchKernelGGL(as::stream_istft_kernel, dim3((S + lpw - 1) / lpw), dim3(audio::x6::kThreadsX), as::kStreamIstftLds, st,
-                       (const float*)s->masks, (const float*)s->win, (const float*)s->phw, in, flags, finish, s->tab.istft, s->tab.cim,
-                       s->tab.chead, s->state, S, K, out, out_counts);
-  HIP_TRY(hipGetLastError());
+    LAUNCH(as::stream_istft_kernel, dim3((S + lpw - 1) / lpw), dim3(audio::x6::kThreadsX), as::kStreamIstftLds, st, (const float*)s->masks,
+           (const float*)s->win, (const float*)s->phw, in, flags, finish, s->tab.istft, s->tab.cim, s->tab.chead, s->state, S, K, out, out_counts);
   s->last = st;
   return RCED_OK;
 }
@@ -149,19 +141,11 @@ int create(rced_model* m, int lanes, int max_hops, int nfft, int rebuild, bool f
   alloc(&s->masks, rows);
   if (fr) alloc(&s->frames, (size_t)lanes * window_hops(s) * audio::kFrame);
   if (!rc && hipMemset(s->state, 0, (size_t)lanes * s->state_floats * sizeof(float)) != hipSuccess) rc = rced_fail(RCED_ERR_HIP, "hipMemset(stream state)");
-  if (!rc && fr) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(af::stream_fr_stft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, af::kStftLds);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(af::stream_fr_frames_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, af::kFramesLds);
-    if (e != hipSuccess) rc = rced_fail(RCED_ERR_HIP, "hipFuncSetAttribute(stream LDS): %s", hipGetErrorString(e));
-  } else if (!rc) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(as::stream_stft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, as::kStreamStftLds);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(as::stream_istft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, as::kStreamIstftLds);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(as::stream_istft_ola_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, as::kStreamOlaLds);
-    if (e != hipSuccess) rc = rced_fail(RCED_ERR_HIP, "hipFuncSetAttribute(stream LDS): %s", hipGetErrorString(e));
-  }
+  if (!rc && fr)
+    rc = set_dynamic_lds({{kernel_ptr(af::stream_fr_stft_kernel), af::kStftLds}, {kernel_ptr(af::stream_fr_frames_kernel), af::kFramesLds}}, "stream LDS");
+  else if (!rc)
+    rc = set_dynamic_lds({{kernel_ptr(as::stream_stft_kernel), as::kStreamStftLds}, {kernel_ptr(as::stream_istft_kernel), as::kStreamIstftLds},
+                          {kernel_ptr(as::stream_istft_ola_kernel), as::kStreamOlaLds}}, "stream LDS");
   if (!rc) rc = rced_reserve(m, lanes, as::kKeep + window_hops(s));   // the forward of a push allocates nothing
   if (rc) {
     release(s);

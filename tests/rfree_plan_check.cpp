@@ -1,6 +1,6 @@
 // Stand-alone check of the free-running resampler lanes' plan (csrc/rfree_plan.h): the outputs emitted after F frames, the history,
 // the tiling, the ring and buffer sizes and the refusals, for the table geometries of the usual ratios and a sweep of others.  Built
-// and run by test_rfree_host.py with the host compiler and -fsanitize=address,undefined; exits non-zero if any property fails.
+// and run by test_rfree_host.py with the host compiler and AddressSanitizer and UBSan; exits non-zero if any property fails.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>

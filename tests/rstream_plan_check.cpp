@@ -1,6 +1,6 @@
 // Stand-alone check of the resampler lanes' plan (csrc/rstream_plan.h): delay, history, tiling, buffer sizes and refusals, for the
 // table geometries of the usual ratios and a sweep of others.  Built and run by test_rstream_host.py with the host compiler and
-// -fsanitize=address,undefined; exits non-zero if any property fails.
+// AddressSanitizer and UBSan; exits non-zero if any property fails.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>

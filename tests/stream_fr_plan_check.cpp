@@ -1,5 +1,5 @@
 // The arithmetic of csrc/stream_fr_plan.h as a program of its own (tests/test_stream_fr_host.py compiles it with the host compiler
-// under -fsanitize=address,undefined and runs it): a sweep over (W, S, L, K) of the delay, the frames complete and still to come, what a
+// under AddressSanitizer and UBSan and runs it): a sweep over (W, S, L, K) of the delay, the frames complete and still to come, what a
 // finish owes and where it finds it, the state's layout, and a lane walked push by push with the plan's index functions -- every frame
 // that covers an output sample is in the pending sum or in the push, exactly once, and every index stays inside its array.
 // Arguments: groups of (W, S, delay, finish_max) as the library reports them.

@@ -255,6 +255,69 @@ def test_general_kernels_agree_with_the_specialised_ones_at_the_default_framing(
     assert a.shape == b.shape and err <= REBUILD_BOUND
 
 
+# ---- 5b. the frame buffer between a rebuild's two launches: nothing allocated once it fits, grown when it does not ---------------------
+
+def test_rebuilds_replay_from_a_captured_graph_and_the_frame_buffer_grows(built):
+    """A call that allocated, or synchronised, could not be captured: after the first call at a shape on a stream nothing is
+    allocated.  Both rebuilds share the stream's frame buffer; a longer batch grows it, and the call that grew it is still right."""
+    import torch
+    from fullycnnspeechenhancement_amd import _lib
+    lib = _lib.load()
+    N, T, T2, W, S = 2, 5, 9, 160, 80
+    smag, sph = seeded_spectra(N, T2, 77)
+    omag, oph = seeded_spectra(N, T, 78)
+
+    def spectra(m, p, t):
+        return dev(m[:, :t]), torch.view_as_real(dev(p[:, :t])).contiguous()
+
+    def entry(which, mag, phr, t, out, stream):
+        if which == "ola":
+            return lambda: _lib.check(lib.rced_istft_ola_fr(mag.data_ptr(), phr.data_ptr(), None, N, t, W, S, fnp.CODES["hamming"],
+                                                            out.data_ptr(), 0, stream))
+        return lambda: _lib.check(lib.rced_istft_fr(mag.data_ptr(), phr.data_ptr(), N, t, 512, W, S, out.data_ptr(), 0, stream))
+
+    side = torch.cuda.Stream()
+    for which in ("ola", "ref512"):
+        mag, phr = spectra(smag, sph, T)
+        mag2, phr2 = spectra(omag, oph, T)
+        out = torch.zeros((N, fnp.width(T, W, S)), dtype=torch.float32, device="cuda")
+        side.wait_stream(torch.cuda.current_stream())
+        call = entry(which, mag, phr, T, out, side.cuda_stream)
+        call()                                             # sizes the stream's frame buffer
+        call()
+        side.synchronize()
+        eager = out.clone()
+        assert eager.abs().max() > 0
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):         # one stream, a linear chain, no parallel branches
+            call()
+        out.zero_()
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(out, eager), which
+        mag.copy_(mag2)                                    # other inputs at the same addresses
+        phr.copy_(phr2)
+        torch.cuda.synchronize()
+        call()
+        side.synchronize()
+        eager2 = out.clone()
+        assert not torch.equal(eager2, eager)
+        out.zero_()
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(out, eager2), which
+        del graph
+    for which in ("ola", "ref512"):                        # T = 9: the first of the two grows the buffer (no graph is replayed after)
+        mag, phr = spectra(smag, sph, T2)
+        grown = torch.zeros((N, fnp.width(T2, W, S)), dtype=torch.float32, device="cuda")
+        plain = torch.zeros_like(grown)
+        torch.cuda.synchronize()
+        entry(which, mag, phr, T2, grown, side.cuda_stream)()
+        entry(which, mag, phr, T2, plain, torch.cuda.current_stream().cuda_stream)()
+        torch.cuda.synchronize()
+        assert plain.abs().max() > 0 and torch.equal(grown, plain), which
+
+
 # ---- 6. the framing's way through the engine -------------------------------------------------------------------------------------------
 
 def test_denoise_pcm_and_evaluate_pcm_at_a_framing(built):

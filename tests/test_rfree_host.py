@@ -6,14 +6,13 @@ csrc/rfree_plan.h as a program of its own under AddressSanitizer and UBSan.  Not
 
 import ctypes
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import resample_np as R
 import rfree_np as S
+import host_cxx
 from conftest import ROOT
 
 RATIOS = [(44100, 8000), (8000, 44100), (48000, 8000), (8000, 48000), (16000, 8000), (8000, 16000), (22050, 8000), (8000, 8000)]
@@ -184,14 +183,7 @@ def test_symbols_are_declared_exported_and_bound(built):
 
 
 def test_plan_arithmetic_as_a_stand_alone_program(tmp_path, built):
-    cxx = shutil.which(os.environ.get("CXX") or "g++") or shutil.which("c++") or shutil.which("clang++")
-    if not cxx:
-        pytest.fail("no host C++ compiler found")
-    exe = str(tmp_path / "rfree_plan_check")
-    cc = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                         "-fno-sanitize-recover=undefined", "-o", exe, os.path.join(ROOT, "tests", "rfree_plan_check.cpp")],
-                        capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-4000:]
+    exe = host_cxx.build(tmp_path, "rfree_plan_check")
     # its own sweep, then the geometry and the sizes the library reports for the lanes a BlockDenoiser makes of this file's blocks
     from fullycnnspeechenhancement_amd import _lib, audio
     from fullycnnspeechenhancement_amd.freerun import _block_plan
@@ -205,7 +197,4 @@ def test_plan_arithmetic_as_a_stand_alone_program(tmp_path, built):
             assert lib.rced_rfree_plan(sr_in, sr_out, _lib.PCM_F32, 4, max_frames, max_take, prefill, *[ctypes.byref(x) for x in v]) == 0
             args += [sr_in, sr_out, p, q, left, table.shape[1], max_frames, max_take, prefill] + [x.value for x in v]
             groups += 1
-    run = subprocess.run([exe] + [str(v) for v in args], capture_output=True, text=True)
-    print("\n" + run.stdout[-8000:] + run.stderr[-4000:])
-    assert run.returncode == 0, run.stdout[-4000:] + run.stderr[-4000:]
-    assert "%d plans, 0 failures" % (14 + groups) in run.stdout
+    assert "%d plans, 0 failures" % (14 + groups) in host_cxx.run(exe, args)

@@ -5,16 +5,13 @@ tests/rstream_plan_check.cpp, the plan arithmetic of csrc/rstream_plan.h as a pr
 UBSan.  Nothing here needs a GPU."""
 
 import ctypes
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_cxx
 import resample_np as R
 import rstream_np as S
-from conftest import ROOT
 
 # (sr_in, sr_out, unit_in, unit_out): unit 128 on the 8 kHz side; 44.1 kHz with the smallest units, all 80 phases
 CONVERSIONS = [(16000, 8000, 256, 128), (48000, 8000, 768, 128), (12000, 8000, 192, 128), (8000, 16000, 128, 256),
@@ -140,21 +137,11 @@ def test_python_refusals(built):
 
 
 def test_plan_arithmetic_as_a_stand_alone_program(tmp_path, built):
-    cxx = shutil.which(os.environ.get("CXX") or "g++") or shutil.which("c++") or shutil.which("clang++")
-    if not cxx:
-        pytest.fail("no host C++ compiler found")
-    exe = str(tmp_path / "rstream_plan_check")
-    cc = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                         "-fno-sanitize-recover=undefined", "-o", exe, os.path.join(ROOT, "tests", "rstream_plan_check.cpp")],
-                        capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-4000:]
+    exe = host_cxx.build(tmp_path, "rstream_plan_check")
     # its own sweep, then the geometry the library reports for the conversions of this file
     from fullycnnspeechenhancement_amd import audio
     args = []
     for sr_in, sr_out, unit_in, unit_out in CONVERSIONS:
         p, q, left, table = audio.resample_taps(sr_in, sr_out)
         args += [sr_in, sr_out, p, q, left, table.shape[1], unit_in, unit_out]
-    run = subprocess.run([exe] + [str(v) for v in args], capture_output=True, text=True)
-    print("\n" + run.stdout[-6000:] + run.stderr[-4000:])
-    assert run.returncode == 0, run.stdout[-4000:] + run.stderr[-4000:]
-    assert "%d plans, 0 failures" % (17 + len(CONVERSIONS)) in run.stdout
+    assert "%d plans, 0 failures" % (17 + len(CONVERSIONS)) in host_cxx.run(exe, args, tail=6000)

@@ -6,8 +6,6 @@ csrc/stream_fr_plan.h as a program of its own under AddressSanitizer and UBSan. 
 
 import ctypes
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +14,7 @@ import framing_np as fnp
 import stream_fr_np as sfr
 import stream_np
 import stream_ola_np
+import host_cxx
 from conftest import ROOT
 from oracle import rced_np
 
@@ -196,21 +195,11 @@ def test_symbols_are_declared_exported_and_bound(built):
 
 
 def test_plan_arithmetic_as_a_stand_alone_program(tmp_path, built):
-    cxx = shutil.which(os.environ.get("CXX") or "g++") or shutil.which("c++") or shutil.which("clang++")
-    if not cxx:
-        pytest.fail("no host C++ compiler found")
-    exe = str(tmp_path / "stream_fr_plan_check")
-    cc = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                         "-fno-sanitize-recover=undefined", "-o", exe, os.path.join(ROOT, "tests", "stream_fr_plan_check.cpp")],
-                        capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr[-4000:]
+    exe = host_cxx.build(tmp_path, "stream_fr_plan_check")
     # its own sweep, then what the library reports for this file's framings: (W, S, delay, finish_max) each
     from fullycnnspeechenhancement_amd import _lib
     lib = _lib.load()
     args = []
     for W, S, _ in FRAMINGS:
         args += [W, S, lib.rced_stream_delay_fr(W, S), lib.rced_stream_finish_max_fr(W, S)]
-    run = subprocess.run([exe] + [str(v) for v in args], capture_output=True, text=True)
-    print("\n" + run.stdout[-8000:] + run.stderr[-4000:])
-    assert run.returncode == 0, run.stdout[-4000:] + run.stderr[-4000:]
-    assert "%d framings of the library, 0 failures" % len(FRAMINGS) in run.stdout
+    assert "%d framings of the library, 0 failures" % len(FRAMINGS) in host_cxx.run(exe, args)

@@ -1,6 +1,6 @@
 // Stand-alone check of the training step's launch plan (csrc/train_plan.h): the three nets (R-CED V2 in its even-padded
 // internal form) under all 64 combinations of the six plan switches.  Built and run by test_train_plan_host.py with the
-// host compiler and -fsanitize=address,undefined; exits non-zero if any property fails.
+// host compiler and AddressSanitizer and UBSan; exits non-zero if any property fails.
 #include <cstdio>
 #include <vector>
 
