@@ -45,6 +45,8 @@ SYMBOLS = {
     "rced_istft_ola": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp]),
     "rced_wave_loss": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                       ctypes.c_int, ctypes.c_double, _vp, _vp, ctypes.c_int, _vp]),
+    "rced_wave_loss_fr": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _vp] + [ctypes.c_int] * 5 + [ctypes.c_double, ctypes.c_double,
+                                         ctypes.c_int, ctypes.c_double, _vp, _vp, ctypes.c_int, _vp]),
     "rced_framing_check": (ctypes.c_int, [ctypes.c_int] * 3),
     "rced_stft_num_frames_fr": (ctypes.c_int, [ctypes.c_int] * 3),
     "rced_stft_fr": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 6 + [_vp, _vp, ctypes.c_int, _vp]),
@@ -116,6 +118,10 @@ SYMBOLS = {
                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _vp]),
     "rced_train_grad_wave": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp,
                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _vp]),
+    "rced_train_step_wave_fr": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, _vp] + [ctypes.c_int] * 3 +
+                                [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _vp]),
+    "rced_train_grad_wave_fr": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp] + [ctypes.c_int] * 3 +
+                                [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _vp]),
     "rced_train_apply": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_float, _vp]),
     "rced_train_sync_points": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_size_t)]),
     "rced_train_sync_begin": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _vp, _vp]),

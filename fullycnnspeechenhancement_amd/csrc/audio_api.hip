@@ -16,6 +16,7 @@
 #include "kernels_ola_x6.h"
 #include "kernels_framing.h"
 #include "kernels_wave_loss.h"
+#include "kernels_wave_loss_fr.h"
 #include "rced_internal.h"
 
 using namespace rced;
@@ -214,10 +215,10 @@ int reference_rebuild_check(int name) {
 }
 
 // One pack per (kind, window length, window name) and device, with the fp32 table that goes with it; the stride enters no pack.
-enum { kFrStft = 0, kFrOla = 1, kFrRef256 = 2, kFrRef512 = 3 };
+enum { kFrStft = 0, kFrOla = 1, kFrRef256 = 2, kFrRef512 = 3, kFrAdjoint = 4 };
 struct FrPack {
   unsigned short* pack = nullptr;
-  float* aux = nullptr;   // rebuilds: [2][256], the coefficients of im(bin 128) (row scale folded in), then w^2; kFrStft: none
+  float* aux = nullptr;   // rebuilds: [2][256], the coefficients of im(bin 128) (row scale folded in), then w^2; kFrStft, kFrAdjoint: none
   int pins = 0;           // streams at this framing (rced_fr_tables_pin): a pinned pack is never dropped
 };
 std::map<int, FrPack> g_fr[kMaxDevices];
@@ -237,12 +238,14 @@ double irfft_coef(int nfft, int n, int b, int c) {   // istft_coef without a win
 int build_fr(FrPack& e, int kind, int W, int name) {
   std::vector<double> w(audio::kFrame, 0.0);
   for (int k = 0; k < W; ++k) w[k] = window_at(name, W, k);
-  if (kind == kFrStft) {
+  if (kind == kFrStft || kind == kFrAdjoint) {
+    // kFrAdjoint (kernels_wave_loss_fr.h): the rebuild's adjoint, G = rfft(w u) with irfft's weights kappa_b / 256 folded in
     auto coef = [&](int row, int k) {
       const int b = row == 1 ? 128 : row >> 1;
       const bool im = row >= 2 && (row & 1);
       const double th = 2.0 * M_PI * ((b * k) % audio::kFrame) / audio::kFrame;
-      return w[k] * (im ? -std::sin(th) : std::cos(th));
+      const double scale = kind == kFrAdjoint ? (row < 2 ? 1.0 : 2.0) / audio::kFrame : 1.0;
+      return w[k] * scale * (im ? -std::sin(th) : std::cos(th));
     };
     return upload(&e.pack, pack_x6(audio::fr::kFrMT, coef), kWhat);
   }
@@ -264,7 +267,9 @@ int fr_pack(int device, int kind, int W, int name, FrPack* out) {   // g_fr_mu h
   if (int rc = check_device(device, kMaxDevices)) return rc;
   if (!g_fr_attr[device]) {
     if (int rc = set_dynamic_lds({{kernel_ptr(audio::fr::stft_fr_kernel), audio::fr::kStftFrLdsBytes},
-                                  {kernel_ptr(audio::fr::frames_fr_kernel), audio::fr::kFramesFrLdsBytes}},
+                                  {kernel_ptr(audio::fr::frames_fr_kernel), audio::fr::kFramesFrLdsBytes},
+                                  {kernel_ptr(wloss::fr::adjoint_kernel<true>), audio::fr::kStftFrLdsBytes},
+                                  {kernel_ptr(wloss::fr::adjoint_kernel<false>), audio::fr::kStftFrLdsBytes}},
                                  "framing LDS"))
       return rc;
     g_fr_attr[device] = true;
@@ -299,6 +304,7 @@ int fr_pack(int device, int kind, int W, int name, FrPack* out) {   // g_fr_mu h
 // The frames between the two steps of a rebuild, [N, T, 256] fp32: the stream's workspace (host_ws.h), one family for both rebuilds
 StreamWorkspace g_fr_frames;
 StreamWorkspace g_wave_ws;   // rced_wave_loss's workspace, carved in rced_wave_loss_run
+StreamWorkspace g_wave_fr_ws;   // rced_wave_loss_fr's, carved in rced_wave_loss_fr_run
 
 // frames_fr_kernel, then rebuild_fr_kernel<OLA>
 template <bool OLA>
@@ -319,7 +325,7 @@ int rebuild_fr(const float* mag_dev, const float* phase_dev, const int* frames_d
            frames_dev, (const unsigned short*)p.pack, (const float*)p.aux, T, W, Y);
   }
   LAUNCH(audio::fr::rebuild_fr_kernel<OLA>, dim3(N), dim3(audio::x6::kThreadsX), 0, st, (const float*)Y, frames_dev,
-         (const float*)p.aux + audio::kFrame, T, W, S, audio_dev);
+         (const float*)p.aux + audio::kFrame, T, W, S, (long long)(W - S) + (long long)T * S, audio_dev);
   return RCED_OK;
 }
 
@@ -449,9 +455,9 @@ int rced_wave_loss(const float* mag_dev, const float* phase_dev, const int* fram
 
 }  // extern "C"
 
-int rced_wave_loss_run(const float* mag_dev, const float* phase_dev, const int* frames_dev, const float* clean_dev, int clean_stride,
-                       const int* lengths_dev, int N, int T, double w_sse, double w_si_sdr, int skip_edges, double inv_batch,
-                       double* terms_dev, float* grad_dev, int accumulate, int device, void* stream) {
+// What rced_wave_loss and rced_wave_loss_fr refuse alike, before any device work; kNothingToDo for N = 0
+static int wave_loss_args(const float* mag_dev, const float* phase_dev, const float* clean_dev, int clean_stride, const int* lengths_dev, int N,
+                          int T, double w_sse, double w_si_sdr, int skip_edges, double inv_batch, const double* terms_dev) {
   if (N < 0 || T < 0 || clean_stride < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
   if (!(w_sse >= 0.0) || !(w_si_sdr >= 0.0) || !std::isfinite(w_sse) || !std::isfinite(w_si_sdr))
     return rced_fail(RCED_ERR_ARG, "the weights must be finite and >= 0, got w_sse = %g, w_si_sdr = %g", w_sse, w_si_sdr);
@@ -459,9 +465,74 @@ int rced_wave_loss_run(const float* mag_dev, const float* phase_dev, const int* 
   if (skip_edges != 0 && skip_edges != 1) return rced_fail(RCED_ERR_ARG, "skip_edges must be 0 or 1, got %d", skip_edges);
   if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
   if (T > (1 << 22)) return rced_fail(RCED_ERR_ARG, "T > 2^22 frames");
-  if (N == 0) return RCED_OK;
+  if (N == 0) return kNothingToDo;
   if (!terms_dev || !lengths_dev || (clean_stride > 0 && !clean_dev) || (T > 0 && (!mag_dev || !phase_dev)))
     return rced_fail(RCED_ERR_ARG, "null pointer");
+  return RCED_OK;
+}
+
+int rced_wave_loss_fr_run(const float* mag_dev, const float* phase_dev, const int* frames_dev, const float* clean_dev, int clean_stride,
+                          const int* lengths_dev, int N, int T, int W, int S, int name, double w_sse, double w_si_sdr, int skip_edges,
+                          double inv_batch, double* terms_dev, float* grad_dev, int accumulate, int device, void* stream) {
+  if (int rc = framing_check(W, S, name)) return rc;
+  if (int rc = wave_loss_args(mag_dev, phase_dev, clean_dev, clean_stride, lengths_dev, N, T, w_sse, w_si_sdr, skip_edges, inv_batch, terms_dev))
+    return rc == kNothingToDo ? RCED_OK : rc;
+  const int nblk = (T + audio::kFramesPerWg - 1) / audio::kFramesPerWg;
+  if (nblk > 65535) return rced_fail(RCED_ERR_ARG, "T > 65535 * 64 frames per call");
+  DeviceGuard g(device);
+  std::lock_guard<std::mutex> lk(g_fr_mu);
+  FrPack ola, adj;
+  // (a look-up may drop every pack that no stream has pinned, once: the third one finds, or rebuilds, the first)
+  if (int rc = fr_pack(device, kFrOla, W, name, &ola)) return rc;
+  if (int rc = fr_pack(device, kFrAdjoint, W, name, &adj)) return rc;
+  if (int rc = fr_pack(device, kFrOla, W, name, &ola)) return rc;
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  const long long L = wloss::fr::row_stride(T, W, S);   // floats per row of y and u: whole 16-byte groups
+  const int slices = wloss::num_slices((int)L);         // (L < 2^31: T <= 2^22, S <= 256)
+  float *y, *u, *Y;    // [N, L]: the rebuild, the scaled reverse scan; [N, T, 256]: the frames between the rebuild's two steps
+  double *ws1, *ws2;   // [N, slices, 2]
+  double* scal;        // [N, 4]
+  int* frames;         // [N]
+  Carve ws;
+  ws.take(&y, (size_t)N * L);
+  ws.take(&u, (size_t)N * L);
+  ws.take(&Y, (size_t)N * T * audio::kFrame);
+  ws.take(&ws1, (size_t)N * slices * 2);
+  ws.take(&ws2, (size_t)N * slices * 2);
+  ws.take(&scal, (size_t)N * 4);
+  ws.take(&frames, (size_t)N);
+  if (int rc = ws.bind(device, stream, g_wave_fr_ws)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const float* w2 = ola.aux + audio::kFrame;
+  LAUNCH(wloss::fr::counts_kernel, dim3((N + 255) / 256), dim3(256), 0, st, frames_dev, lengths_dev, N, T, W, S, frames);
+  if (T > 0)
+    LAUNCH(audio::fr::frames_fr_kernel, dim3(N, 2, nblk), dim3(audio::x6::kThreadsX), audio::fr::kFramesFrLdsBytes, st, mag_dev, phase_dev,
+           (const int*)frames, (const unsigned short*)ola.pack, (const float*)ola.aux, T, W, Y);
+  LAUNCH(audio::fr::rebuild_fr_kernel<true>, dim3(N), dim3(audio::x6::kThreadsX), 0, st, (const float*)Y, (const int*)frames, w2, T, W, S, L, y);
+  LAUNCH(wloss::sums_kernel<0>, dim3(slices, N), dim3(wloss::kSumThreads), 0, st, (const float*)y, (int)L, clean_dev, clean_stride, lengths_dev,
+         (const int*)frames, skip_edges, W, S, (const double*)nullptr, ws1, slices);
+  LAUNCH(wloss::sums_kernel<1>, dim3(slices, N), dim3(wloss::kSumThreads), 0, st, (const float*)y, (int)L, clean_dev, clean_stride, lengths_dev,
+         (const int*)frames, skip_edges, W, S, (const double*)ws1, ws2, slices);
+  LAUNCH(wloss::terms_kernel, dim3(N), dim3(wloss::kSumThreads), 0, st, (const double*)ws1, (const double*)ws2, lengths_dev,
+         (const int*)frames, clean_stride, skip_edges, W, S, slices, terms_dev, scal);
+  if (grad_dev && T > 0) {
+    LAUNCH(wloss::fr::reverse_kernel, dim3(N), dim3(audio::x6::kThreadsX), 0, st, (const float*)y, L, clean_dev, clean_stride, lengths_dev,
+           (const int*)frames, skip_edges, W, S, (const double*)scal, 2.0 * w_sse * inv_batch, w_si_sdr * inv_batch, w2, u);
+    if (accumulate)
+      LAUNCH(wloss::fr::adjoint_kernel<true>, dim3(N, 2, range_split(N, T)), dim3(audio::x6::kThreadsX), audio::fr::kStftFrLdsBytes, st,
+             (const float*)u, L, (const int*)frames, (const unsigned short*)adj.pack, phase_dev, T, W, S, grad_dev);
+    else
+      LAUNCH(wloss::fr::adjoint_kernel<false>, dim3(N, 2, range_split(N, T)), dim3(audio::x6::kThreadsX), audio::fr::kStftFrLdsBytes, st,
+             (const float*)u, L, (const int*)frames, (const unsigned short*)adj.pack, phase_dev, T, W, S, grad_dev);
+  }
+  return RCED_OK;
+}
+
+int rced_wave_loss_run(const float* mag_dev, const float* phase_dev, const int* frames_dev, const float* clean_dev, int clean_stride,
+                       const int* lengths_dev, int N, int T, double w_sse, double w_si_sdr, int skip_edges, double inv_batch,
+                       double* terms_dev, float* grad_dev, int accumulate, int device, void* stream) {
+  if (int rc = wave_loss_args(mag_dev, phase_dev, clean_dev, clean_stride, lengths_dev, N, T, w_sse, w_si_sdr, skip_edges, inv_batch, terms_dev))
+    return rc == kNothingToDo ? RCED_OK : rc;
   DeviceGuard g;
   AudioTables* t = nullptr;
   if (int rc = tables(device, g, &t)) return rc;
@@ -483,11 +554,11 @@ int rced_wave_loss_run(const float* mag_dev, const float* phase_dev, const int* 
   LAUNCH(audio::x6::istft_ola_x6_kernel, dim3(N), dim3(audio::x6::kThreadsX), audio::x6::kOlaLdsBytes, st, mag_dev, phase_dev,
          (const int*)frames, (const unsigned short*)t->ola_x6, (const float*)t->ola_fix, T, y);
   LAUNCH(wloss::sums_kernel<0>, dim3(slices, N), dim3(wloss::kSumThreads), 0, st, (const float*)y, L, clean_dev, clean_stride, lengths_dev,
-         (const int*)frames, skip_edges, (const double*)nullptr, ws1, slices);
+         (const int*)frames, skip_edges, audio::kFrame, audio::kStep, (const double*)nullptr, ws1, slices);
   LAUNCH(wloss::sums_kernel<1>, dim3(slices, N), dim3(wloss::kSumThreads), 0, st, (const float*)y, L, clean_dev, clean_stride, lengths_dev,
-         (const int*)frames, skip_edges, (const double*)ws1, ws2, slices);
+         (const int*)frames, skip_edges, audio::kFrame, audio::kStep, (const double*)ws1, ws2, slices);
   LAUNCH(wloss::terms_kernel, dim3(N), dim3(wloss::kSumThreads), 0, st, (const double*)ws1, (const double*)ws2, lengths_dev,
-         (const int*)frames, clean_stride, skip_edges, slices, terms_dev, scal);
+         (const int*)frames, clean_stride, skip_edges, audio::kFrame, audio::kStep, slices, terms_dev, scal);
   if (grad_dev && T > 0) {
     LAUNCH(wloss::reverse_kernel, dim3(N), dim3(audio::x6::kThreadsX), 0, st, (const float*)y, L, clean_dev, clean_stride, lengths_dev,
            (const int*)frames, skip_edges, (const double*)scal, 2.0 * w_sse * inv_batch, w_si_sdr * inv_batch,
@@ -543,6 +614,13 @@ int rced_istft_ola_fr(const float* mag_dev, const float* phase_dev, const int* f
   if (int rc = framing_check(window, stride, window_name)) return rc;
   if (int rc = audio_args(N, T, false, audio_dev && (T == 0 || (mag_dev && phase_dev)))) return rc == kNothingToDo ? RCED_OK : rc;
   return rebuild_fr<true>(mag_dev, phase_dev, frames_dev, N, T, kFrOla, window, stride, window_name, audio_dev, device, stream);
+}
+
+int rced_wave_loss_fr(const float* mag_dev, const float* phase_dev, const int* frames_dev, const float* clean_dev, int clean_stride,
+                      const int* lengths_dev, int N, int T, int window, int stride, int window_name, double w_sse, double w_si_sdr,
+                      int skip_edges, double inv_batch, double* terms_dev, float* grad_dev, int device, void* stream) {
+  return rced_wave_loss_fr_run(mag_dev, phase_dev, frames_dev, clean_dev, clean_stride, lengths_dev, N, T, window, stride, window_name, w_sse,
+                               w_si_sdr, skip_edges, inv_batch, terms_dev, grad_dev, 0, device, stream);
 }
 
 }  // extern "C"

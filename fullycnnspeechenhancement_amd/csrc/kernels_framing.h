@@ -130,14 +130,16 @@ __global__ __launch_bounds__(kThreadsX) void frames_fr_kernel(const float* __res
   }
 }
 
-// Y [N, T, 256] (frames_fr_kernel) -> y [N, (W - S) + T S], every column written.  grid (N).
+// Y [N, T, 256] (frames_fr_kernel) -> y [N, (W - S) + T S], every column written; rows `ystride` floats apart (>= that width: the
+// wave objective's rows are padded to whole 16-byte groups, kernels_wave_loss_fr.h).  grid (N).
 // OLA:  e[i] = sum_t Y[t][i - tS] / sum_t w2[i - tS] over the frames t < F that cover i (0 where the denominator is at most 1e-10,
 //       scipy.signal.istft's rule), i < (F - 1) S + W; zeros from there on.  w2: 256 floats, w^2.  frames as above.
 // !OLA: de_frame (utils.py:139-147): the first W - S samples of frame 0, then the last S samples of every frame (F = T).
 // Then y[i] = e[i] + 0.97 y[i-1], y[0] = e[0].
 template <bool OLA>
 __global__ __launch_bounds__(kThreadsX) void rebuild_fr_kernel(const float* __restrict__ Y, const int* __restrict__ frames,
-                                                                const float* __restrict__ w2, int T, int W, int S, float* __restrict__ y) {
+                                                                const float* __restrict__ w2, int T, int W, int S, long long ystride,
+                                                                float* __restrict__ y) {
   __shared__ __attribute__((aligned(16))) float obuf[kFramesPerWg * kORow];   // a chunk in time order, rows of 128 (deemph_scan's layout)
   __shared__ float sa[kThreadsX], sb[kThreadsX];
   const int tid = threadIdx.x, utt = blockIdx.x;
@@ -145,7 +147,7 @@ __global__ __launch_bounds__(kThreadsX) void rebuild_fr_kernel(const float* __re
   const long long width = (long long)(W - S) + (long long)T * S;
   const long long n_out = F > 0 ? (long long)(F - 1) * S + W : 0;
   const float* Yu = Y + (size_t)utt * T * kFrame;
-  float* yo = y + (size_t)utt * width;
+  float* yo = y + (size_t)utt * ystride;
   float carry = 0.f;   // y just before the chunk
   for (long long base = 0; base < n_out; base += kChunk) {
     __syncthreads();   // the previous chunk's reads of obuf, sa, sb are done

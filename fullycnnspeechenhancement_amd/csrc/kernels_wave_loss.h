@@ -1,5 +1,6 @@
 // Waveform and SI-SDR terms on the overlap-add rebuild, and their gradient with respect to the magnitudes (include/rced.h,
-// rced_wave_loss).  Default framing only: 256 / 128 / hamming.  Per utterance, with y = rced_istft_ola(M, P, F)
+// rced_wave_loss).  Default framing: 256 / 128 / hamming (any other: kernels_wave_loss_fr.h, which reuses the sums, the
+// terms and project_store from here with the scored range as a function of (W, S)).  Per utterance, with y = rced_istft_ola(M, P, F)
 // (istft_ola_x6_kernel, unchanged, into a workspace), c the clean row of l samples and R = [lo, hi) the scored range:
 //   sums     <y,c>, <c,c>, then with alpha = <y,c> / <c,c>:  |y - alpha c|^2, |y - c|^2, all over R, fp64, in slices (the mapping of
 //            kernels_eval.h: a sum's order depends on the sample's index inside its utterance only), no atomics;
@@ -39,14 +40,19 @@ __host__ __device__ inline int num_slices(int hi) { return (hi + kSlice - 1) / k
 struct Range {
   int lo, hi;
 };
+// at a framing (W, S): with skip_edges the samples whose covering frames are limited neither by t >= 0 nor by t <= F - 1
 __device__ __forceinline__ Range range_of(const int* __restrict__ lengths, const int* __restrict__ frames, int n, int clean_stride,
-                                          int skip_edges) {
+                                          int skip_edges, int W, int S) {
   const int len = min(max(lengths[n], 0), clean_stride), F = frames[n];
   Range r;
-  r.lo = skip_edges ? kStep : 0;
-  r.hi = min(len, kStep * (skip_edges ? F : F + 1));
+  r.lo = skip_edges ? W - S : 0;
+  r.hi = min(len, skip_edges ? F * S : (F - 1) * S + W);
   if (F <= 0 || r.hi <= r.lo) r.hi = 0;
   return r;
+}
+__device__ __forceinline__ Range range_of(const int* __restrict__ lengths, const int* __restrict__ frames, int n, int clean_stride,
+                                          int skip_edges) {
+  return range_of(lengths, frames, n, clean_stride, skip_edges, audio::kFrame, kStep);
 }
 
 // grid (ceil(N / 256)): the frame counts every later launch reads.  given: [N] or null (= num_frames(length)); clamped into [0, T]
@@ -95,17 +101,17 @@ __device__ __forceinline__ void sum_partials(const double* __restrict__ ws, int 
   block_sum2(a, b, sh);
 }
 
-// grid (slices, N).  PASS 0: ws1[n][s] = (<y,c>, <c,c>) over R in slice s; PASS 1: ws2[n][s] = (|y - alpha c|^2, |y - c|^2), every
+// grid (slices, N); (W, S): the framing of the scored range.  PASS 0: ws1[n][s] = (<y,c>, <c,c>) over R in slice s; PASS 1: ws2[n][s] = (|y - alpha c|^2, |y - c|^2), every
 // workgroup summing pass 0's partials itself, in slice order (one alpha everywhere).  y: the rebuild, rows of `ystride` (a multiple of
 // four floats on a 16-byte base); c: rows of `clean_stride`, any alignment, read one float at a time below hi only.
 template <int PASS>
 __global__ __launch_bounds__(kSumThreads) void sums_kernel(const float* __restrict__ y, int ystride, const float* __restrict__ clean,
                                                             int clean_stride, const int* __restrict__ lengths,
-                                                            const int* __restrict__ frames, int skip_edges,
+                                                            const int* __restrict__ frames, int skip_edges, int W, int S,
                                                             const double* __restrict__ ws1, double* __restrict__ out, int slices) {
   __shared__ double red[kSumWaves][2];
   const int n = blockIdx.y, s = blockIdx.x;
-  const Range R = range_of(lengths, frames, n, clean_stride, skip_edges);
+  const Range R = range_of(lengths, frames, n, clean_stride, skip_edges, W, S);
   const int base = s * kSlice;
   if (base >= R.hi) return;
   double alpha = 0.0;
@@ -146,11 +152,11 @@ __global__ __launch_bounds__(kSumThreads) void sums_kernel(const float* __restri
 // last two zero for an invalid row: what the reverse pass forms g_y from
 __global__ __launch_bounds__(kSumThreads) void terms_kernel(const double* __restrict__ ws1, const double* __restrict__ ws2,
                                                              const int* __restrict__ lengths, const int* __restrict__ frames,
-                                                             int clean_stride, int skip_edges, int slices, double* __restrict__ terms,
-                                                             double* __restrict__ scal) {
+                                                             int clean_stride, int skip_edges, int W, int S, int slices,
+                                                             double* __restrict__ terms, double* __restrict__ scal) {
   __shared__ double red[kSumWaves][2];
   const int n = blockIdx.x;
-  const int nsl = num_slices(range_of(lengths, frames, n, clean_stride, skip_edges).hi);
+  const int nsl = num_slices(range_of(lengths, frames, n, clean_stride, skip_edges, W, S).hi);
   double yc, cc, rr, sse;
   sum_partials(ws1, n, slices, nsl, yc, cc, red);
   sum_partials(ws2, n, slices, nsl, rr, sse, red);

@@ -93,6 +93,10 @@ void rced_fr_tables_unpin(int device, int window, int window_name, int ola, int 
 int rced_wave_loss_run(const float* mag_dev, const float* phase_dev, const int* frames_dev, const float* clean_dev, int clean_stride,
                        const int* lengths_dev, int N, int T, double w_sse, double w_si_sdr, int skip_edges, double inv_batch,
                        double* terms_dev, float* grad_dev, int accumulate, int device, void* stream);
+// ... and rced_wave_loss_fr likewise: the same pass at a framing (W, S, window name), always through the general kernels
+int rced_wave_loss_fr_run(const float* mag_dev, const float* phase_dev, const int* frames_dev, const float* clean_dev, int clean_stride,
+                          const int* lengths_dev, int N, int T, int W, int S, int name, double w_sse, double w_si_sdr, int skip_edges,
+                          double inv_batch, double* terms_dev, float* grad_dev, int accumulate, int device, void* stream);
 
 // stream_api.hip: streams created on `m` answer RCED_ERR_STATE from now on (rced_destroy calls this before the model goes)
 void rced_streams_detach(rced_model* m);

@@ -488,6 +488,7 @@ struct TrainPass {
   std::vector<int> src_parts;  // [l]: the records of layer l's BatchNorm-backward sums that its consumer's dgrad left in t->part (Sums::DgradZ / FusedX)
   std::vector<double> hp;      // the loss kernel's partial sums, on the host after end()'s synchronise
   const rced_wave_args* wave = nullptr;   // the wave objective's terms (rced.h), or nullptr: the spectral loss alone, today's pass
+  const int* wave_fr = nullptr;           // (window, stride, window name) of the _fr entries: the wave terms through the general kernels
   std::vector<double> hw;      // [N][3]: the wave terms per utterance, on the host after end()'s synchronise
   Stage stage = Stage::Fwd;
   int layer = 0;
@@ -708,9 +709,13 @@ struct TrainPass {
         HIP_TRY(hipMalloc(&t->wave_terms, (size_t)N * 3 * sizeof(double)));
         t->wave_rows = N;
       }
-      if (int rc = rced_wave_loss_run(t->out[L], wave->phase_dev, wave->frames_dev, wave->clean_dev, wave->clean_stride, wave->lengths_dev, N, T,
-                                      wave->w_sse, wave->w_si_sdr, wave->skip_edges, 1.0 / (double)t->batch_size, t->wave_terms, t->G[L],
-                                      spectral ? 1 : 0, t->device, st))
+      if (int rc = wave_fr ? rced_wave_loss_fr_run(t->out[L], wave->phase_dev, wave->frames_dev, wave->clean_dev, wave->clean_stride,
+                                                   wave->lengths_dev, N, T, wave_fr[0], wave_fr[1], wave_fr[2], wave->w_sse, wave->w_si_sdr,
+                                                   wave->skip_edges, 1.0 / (double)t->batch_size, t->wave_terms, t->G[L], spectral ? 1 : 0,
+                                                   t->device, st)
+                           : rced_wave_loss_run(t->out[L], wave->phase_dev, wave->frames_dev, wave->clean_dev, wave->clean_stride,
+                                                wave->lengths_dev, N, T, wave->w_sse, wave->w_si_sdr, wave->skip_edges,
+                                                1.0 / (double)t->batch_size, t->wave_terms, t->G[L], spectral ? 1 : 0, t->device, st))
         return rc;
       hw.assign((size_t)N * 3, 0.0);
       HIP_TRY(hipMemcpyAsync(hw.data(), t->wave_terms, hw.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -984,11 +989,12 @@ int check_wave(const rced_wave_args* w, const float* y_dev) {
 // args_rc: what the entry point made of its arguments (check_batch and its own)
 int train_run(rced_trainer* t, const char* what, int args_rc, const float* x_dev, const float* y_dev, float* pred_dev, int N, int T,
               float lr, double* loss_out, void* stream, float* g_out = nullptr, double* s_out = nullptr, int accumulate = 0,
-              const rced_wave_args* wave = nullptr, double* parts_out = nullptr) {
+              const rced_wave_args* wave = nullptr, double* parts_out = nullptr, const int* wave_fr = nullptr) {
   Enter in(t, what, args_rc);
   if (in.rc) return in.rc;
   TrainPass pass(t, x_dev, y_dev, pred_dev, N, T, lr, stream, g_out != nullptr, 0.0, nullptr);
   pass.wave = wave;
+  pass.wave_fr = wave_fr;
   if (int rc = pass.begin()) return rc;
   if (int rc = pass.advance()) return rc;
   return pass.end(g_out, s_out, accumulate, loss_out, parts_out);
@@ -1049,6 +1055,27 @@ int rced_train_grad_wave(rced_trainer* t, const float* x_dev, const float* y_dev
   if (!rc && (!g_dev || !s_dev)) rc = rced_fail(RCED_ERR_ARG, "an exchange buffer is NULL");
   return train_run(t, "rced_train_grad_wave", rc, x_dev, y_dev, nullptr, N, T, 0.f, loss_out, stream, g_dev, s_dev, accumulate != 0, wave,
                    parts_out);
+}
+
+int rced_train_step_wave_fr(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, float lr, const rced_wave_args* wave,
+                            int window, int stride, int window_name, double* loss_out, double* parts_out, void* stream) {
+  const int fr[3] = {window, stride, window_name};
+  int rc = rced_framing_check(window, stride, window_name);
+  if (!rc) rc = check_wave(wave, y_dev);
+  if (!rc) rc = check_batch(t, x_dev, y_dev ? y_dev : x_dev, N, T);
+  return train_run(t, "rced_train_step_wave_fr", rc, x_dev, y_dev, nullptr, N, T, lr, loss_out, stream, nullptr, nullptr, 0, wave, parts_out, fr);
+}
+
+int rced_train_grad_wave_fr(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, float* g_dev, double* s_dev,
+                            int accumulate, const rced_wave_args* wave, int window, int stride, int window_name, double* loss_out,
+                            double* parts_out, void* stream) {
+  const int fr[3] = {window, stride, window_name};
+  int rc = rced_framing_check(window, stride, window_name);
+  if (!rc) rc = check_wave(wave, y_dev);
+  if (!rc) rc = check_batch(t, x_dev, y_dev ? y_dev : x_dev, N, T);
+  if (!rc && (!g_dev || !s_dev)) rc = rced_fail(RCED_ERR_ARG, "an exchange buffer is NULL");
+  return train_run(t, "rced_train_grad_wave_fr", rc, x_dev, y_dev, nullptr, N, T, 0.f, loss_out, stream, g_dev, s_dev, accumulate != 0, wave,
+                   parts_out, fr);
 }
 
 int rced_train_apply(rced_trainer* t, const float* g_dev, const double* s_dev, float lr, void* stream) {

@@ -57,11 +57,13 @@ class WaveObjective(object):
         return "WaveObjective(spectral=%r, wave_sse=%r, si_sdr=%r, skip_edges=%r)" % self._key()
 
 
-def wave_loss_batch(mag, phase, clean, lengths, objective, batch_size, frames=None, grad=True):
-    """The waveform terms of `objective` for a batch and their gradient, on the device (rced_wave_loss).
+def wave_loss_batch(mag, phase, clean, lengths, objective, batch_size, frames=None, grad=True, framing=None):
+    """The waveform terms of `objective` for a batch and their gradient, on the device (rced_wave_loss; at a framing other than
+    the default, rced_wave_loss_fr).
     mag [N, T, 129(,1)] float32 (the prediction), phase [N, T, 129] complex64 (the mixture's unit phase), clean [N, >= max length]
     float32 with contiguous rows (a view of a wider buffer is fine), all torch.cuda; lengths: N sample counts in [0, clean's width];
-    frames: N frame counts (list / tensor, clamped into [0, T]) or None (= audio.num_frames(length)); batch_size: B >= 1.
+    frames: N frame counts (list / tensor, clamped into [0, T]) or None (= audio.num_frames(length, framing)); batch_size: B >= 1.
+    framing: an audio.Framing, or None for Framing() -- both of which run the entry specialised for 256 / 128 / hamming.
     Returns (terms, grad): terms torch.float64 [N, 3] = (wave_sse, si_sdr, valid) per utterance, unweighted; grad float32
     [N, T, 129] = d(wave_sse / B * sum wave_sse_n - si_sdr / B * sum_valid si_sdr_n) / d mag, or None with grad=False.  The
     spectral weight plays no part here.  Current stream, asynchronous."""
@@ -70,6 +72,8 @@ def wave_loss_batch(mag, phase, clean, lengths, objective, batch_size, frames=No
         raise ValueError("objective must be an audio.WaveObjective, got %r" % (objective,))
     if int(batch_size) != batch_size or batch_size < 1:
         raise ValueError("batch_size must be a whole number >= 1, got %r" % (batch_size,))
+    from .audio import _general
+    fr = _general(framing)
     if not (hasattr(mag, "is_cuda") and mag.is_cuda):
         raise ValueError("mag must be a CUDA/HIP tensor [N, T, 129]")
     if mag.dim() == 4:
@@ -97,7 +101,13 @@ def wave_loss_batch(mag, phase, clean, lengths, objective, batch_size, frames=No
             fdev = torch.tensor(_args.host_ints(frames, n, "frames"), dtype=torch.int32, device=dev)
     terms = torch.empty((n, 3), dtype=torch.float64, device=dev)
     g = torch.empty((n, t, BINS), dtype=torch.float32, device=dev) if grad else None
-    if n:
+    if n and fr is not None:
+        _lib.check(_lib.load().rced_wave_loss_fr(mag.data_ptr() if t else None, ph.data_ptr() if t else None, _args.ptr(fdev),
+                                                 clean.data_ptr(), _args.row_stride(clean), ldev.data_ptr(), n, t, fr.window, fr.stride,
+                                                 fr.code, objective.wave_sse, objective.si_sdr, int(objective.skip_edges),
+                                                 1.0 / float(batch_size), terms.data_ptr(), _args.ptr(g), dev.index,
+                                                 _args.current_stream(dev)))
+    elif n:
         _lib.check(_lib.load().rced_wave_loss(mag.data_ptr() if t else None, ph.data_ptr() if t else None, _args.ptr(fdev),
                                               clean.data_ptr(), _args.row_stride(clean), ldev.data_ptr(),
                                               n, t, objective.wave_sse, objective.si_sdr, int(objective.skip_edges),

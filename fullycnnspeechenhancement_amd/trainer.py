@@ -66,7 +66,13 @@ def run_epochs(tr, fit_step, train_loader, valid_loader, epochs, logger, checkpo
             tr.data_time.update(time.time() - start_time)
             start_time = time.time()
             if tr.has_wave_term:
-                batch_loss, _, global_step = fit_step(batch_mix, batch_clean, wave=wave_of_batch(train_loader, batch_mix, mix_sig, clean_sig))
+                from .engine import loader_framing
+                fr = loader_framing(train_loader)
+                wave = wave_of_batch(train_loader, batch_mix, mix_sig, clean_sig)
+                if fr is None or fr.is_default:     # today's call, for a fit_step that knows no framing
+                    batch_loss, _, global_step = fit_step(batch_mix, batch_clean, wave=wave)
+                else:
+                    batch_loss, _, global_step = fit_step(batch_mix, batch_clean, wave=wave, framing=fr)
             else:
                 batch_loss, _, global_step = fit_step(batch_mix, batch_clean)
             tr.train_loss.update(batch_loss, n=1)
@@ -93,18 +99,17 @@ def run_epochs(tr, fit_step, train_loader, valid_loader, epochs, logger, checkpo
 
 def wave_of_batch(loader, batch_mix, mix_sig, clean_sig):
     """The `wave` argument of a step from a loader's 4-tuple: (the mixture's unit phase [N, T, 129] complex64, the clean rows, the
-    samples scored per utterance: min(len(mix), len(clean))).  The phase is audio.stft_batch's of the mixture's rows, whose
-    magnitudes are the loader's batch_mix bit for bit.  mix_sig, clean_sig: loader.PcmRows (the device loader's batches)."""
+    samples scored per utterance: min(len(mix), len(clean))).  The phase is audio.stft_batch's of the mixture's rows at the loader's
+    framing (engine.loader_framing), whose magnitudes are the loader's batch_mix bit for bit.  mix_sig, clean_sig: loader.PcmRows
+    (the device loader's batches)."""
     from . import audio
     from .engine import loader_framing
     fr = loader_framing(loader)
-    if fr is not None and not fr.is_default:
-        raise ValueError("an objective with a wave term (wave_sse or si_sdr) cannot be combined with a loader whose framing is %r: the "
-                         "differentiable rebuild exists for the default framing, 256 / 128 / hamming, only" % (fr,))
     if not (hasattr(mix_sig, "rows") and hasattr(clean_sig, "rows")) or len(mix_sig) != len(clean_sig):
+        at = "" if fr is None or fr.is_default else " (a loader whose framing is %r)" % (fr,)
         raise ValueError("an objective with a wave term needs the loader's mix_sig and clean_sig as device rows (loader.PcmRows), one pair "
-                         "per utterance")
-    _, phase = audio.stft_batch(mix_sig.rows, mix_sig.lengths, frames=int(batch_mix.shape[1]), with_phase=True)
+                         "per utterance%s" % at)
+    _, phase = audio.stft_batch(mix_sig.rows, mix_sig.lengths, frames=int(batch_mix.shape[1]), with_phase=True, framing=fr)
     return phase, clean_sig.rows, [min(a, b) for a, b in zip(mix_sig.lengths, clean_sig.lengths)]
 
 
@@ -213,17 +218,25 @@ class FullyCNNTrainer(object):
     def _wave_rows(wave, a, b):
         return None if wave is None else (wave[0][a:b], wave[1][a:b], list(_args.host_ints(wave[2]))[a:b])
 
-    def train_step(self, input_x, target_y, wave=None):
+    @staticmethod
+    def _wave_framing(framing):
+        """None for framing=None and Framing() (the specialised entries), else the Framing (the _fr entries)."""
+        from .audio import _general
+        return _general(framing)
+
+    def train_step(self, input_x, target_y, wave=None, framing=None):
         """trainer.py:181-192: returns (batch_loss, summary (None here), global_step).  With accumulate=k > 1 the batch is
         cut into k contiguous row ranges (accumulation_slices) and the step is train_step_sharded over them.
         With an objective that has a wave term, wave = (phase, clean_rows, lengths): the mixture's unit phase [N, T, 129] complex,
         the clean signals as device rows and the samples scored per utterance (audio.wave_loss_batch); accumulate=k cuts it by
-        the same rows.  self.loss_parts then holds the step's unweighted (spectral, wave_sse, si_sdr) sums."""
+        the same rows.  self.loss_parts then holds the step's unweighted (spectral, wave_sse, si_sdr) sums.
+        framing: the audio.Framing the wave terms are rebuilt at (the one `wave`'s phase was taken at); None is Framing()."""
         import torch
+        fr = self._wave_framing(framing)
         x, y = self._on_device(input_x, target_y)
         if self.accumulate > 1:
             return self.train_step_sharded([(x[a:b], y[a:b], self._wave_rows(wave, a, b))
-                                            for a, b in accumulation_slices(x.shape[0], self.accumulate)])
+                                            for a, b in accumulation_slices(x.shape[0], self.accumulate)], framing=fr)
         loss = ctypes.c_double()
         st = torch.cuda.current_stream(x.device).cuda_stream
         if self._plain and wave is None:
@@ -232,8 +245,13 @@ class FullyCNNTrainer(object):
             return loss.value, None, self.global_step
         args, keep = self._wave_args(wave, x)
         parts = (ctypes.c_double * 3)()
-        _lib.check(_lib.load().rced_train_step_wave(self._h, x.data_ptr(), y.data_ptr(), int(x.shape[0]), int(x.shape[1]),
-                                                    ctypes.c_float(self.lr), ctypes.byref(args), ctypes.byref(loss), parts, st))
+        if fr is not None:
+            _lib.check(_lib.load().rced_train_step_wave_fr(self._h, x.data_ptr(), y.data_ptr(), int(x.shape[0]), int(x.shape[1]),
+                                                           ctypes.c_float(self.lr), ctypes.byref(args), fr.window, fr.stride, fr.code,
+                                                           ctypes.byref(loss), parts, st))
+        else:
+            _lib.check(_lib.load().rced_train_step_wave(self._h, x.data_ptr(), y.data_ptr(), int(x.shape[0]), int(x.shape[1]),
+                                                        ctypes.c_float(self.lr), ctypes.byref(args), ctypes.byref(loss), parts, st))
         self.loss_parts = tuple(parts)
         del keep
         return loss.value, None, self.global_step
@@ -251,12 +269,14 @@ class FullyCNNTrainer(object):
             self._exch = (torch.zeros(nf.value, dtype=torch.float32, device=dev), torch.zeros(nd.value, dtype=torch.float64, device=dev))
         return self._exch
 
-    def grad_step(self, input_x, target_y, accumulate=False, wave=None):
+    def grad_step(self, input_x, target_y, accumulate=False, wave=None, framing=None):
         """One shard: forward (BatchNorm with THIS shard's statistics), loss = sum((y - pred)^2) / batch_size, backward.
         The gradient and the statistics sums overwrite the exchange tensors, or (accumulate) are added to them; variables,
         Adam slots, moving statistics and global_step stay as they are.  Returns the shard's loss.  wave: as in train_step;
-        self.loss_parts then holds this shard's sums (every term is a sum over utterances, divided by batch_size: shards add up)."""
+        self.loss_parts then holds this shard's sums (every term is a sum over utterances, divided by batch_size: shards add up).
+        framing: as in train_step."""
         import torch
+        fr = self._wave_framing(framing)
         x, y = self._on_device(input_x, target_y)
         g, s = self.exchange_tensors()
         loss = ctypes.c_double()
@@ -267,8 +287,13 @@ class FullyCNNTrainer(object):
             return loss.value
         args, keep = self._wave_args(wave, x)
         parts = (ctypes.c_double * 3)()
-        _lib.check(_lib.load().rced_train_grad_wave(self._h, x.data_ptr(), y.data_ptr(), int(x.shape[0]), int(x.shape[1]), g.data_ptr(),
-                                                    s.data_ptr(), 1 if accumulate else 0, ctypes.byref(args), ctypes.byref(loss), parts, st))
+        if fr is not None:
+            _lib.check(_lib.load().rced_train_grad_wave_fr(self._h, x.data_ptr(), y.data_ptr(), int(x.shape[0]), int(x.shape[1]), g.data_ptr(),
+                                                           s.data_ptr(), 1 if accumulate else 0, ctypes.byref(args), fr.window, fr.stride,
+                                                           fr.code, ctypes.byref(loss), parts, st))
+        else:
+            _lib.check(_lib.load().rced_train_grad_wave(self._h, x.data_ptr(), y.data_ptr(), int(x.shape[0]), int(x.shape[1]), g.data_ptr(),
+                                                        s.data_ptr(), 1 if accumulate else 0, ctypes.byref(args), ctypes.byref(loss), parts, st))
         self.loss_parts = tuple(parts)
         del keep
         return loss.value
@@ -282,10 +307,11 @@ class FullyCNNTrainer(object):
         _lib.check(_lib.load().rced_train_apply(self._h, g.data_ptr(), s.data_ptr(), ctypes.c_float(self.lr), st))
         return self.global_step
 
-    def train_step_sharded(self, shards, sync_bn=False):
+    def train_step_sharded(self, shards, sync_bn=False, framing=None):
         """One optimizer step over a list of (x, y) shards, each [N_s, T_s, 129, 1] (shapes may differ): the gradient is the
         fp32 sum of the shards' gradients in list order, the reported loss the sum of their losses, BatchNorm per shard.
         One shard is train_step, bit for bit.  Returns (loss, None, global_step).  Nothing is applied if a shard fails.
+        framing: the audio.Framing of every shard's wave terms, as in train_step.
 
         sync_bn=True: BatchNorm over the UNION of the shards (the synchronised step) -- the step is then the
         unsharded train_step over all the shards' rows up to the rounding of a few fp64 additions, and it is what
@@ -301,6 +327,7 @@ class FullyCNNTrainer(object):
         if sync_bn and self.has_wave_term:
             raise ValueError("sync_bn=True cannot be combined with an objective that has a wave term (%r): the synchronised pass has no "
                              "wave form" % (self.objective,))
+        fr = self._wave_framing(framing)
         waves = [sh[2] if len(sh) > 2 else None for sh in shards]     # a shard: (x, y) or (x, y, wave)
         shards = [self._on_device(sh[0], sh[1]) for sh in shards]
         if not shards:
@@ -309,7 +336,7 @@ class FullyCNNTrainer(object):
             return self._train_step_sharded_sync(shards)
         loss, parts = 0.0, None
         for i, ((x, y), w) in enumerate(zip(shards, waves)):
-            loss += self.grad_step(x, y, accumulate=i > 0, wave=w)
+            loss += self.grad_step(x, y, accumulate=i > 0, wave=w, framing=fr)
             if self.loss_parts is not None and not (self._plain and w is None):
                 parts = self.loss_parts if parts is None else tuple(p + q for p, q in zip(parts, self.loss_parts))
         if parts is not None:
@@ -448,9 +475,12 @@ class FullyCNNTrainer(object):
                 logger.info(more)
         return self.sdr_score.avg
 
-    def fit_step(self, input_x, target_y, wave=None):
-        """One iteration of the loop body of trainer.py:212-215: step, then set lr for the next step.  wave: as in train_step."""
-        out = self.train_step(input_x, target_y, wave=wave) if wave is not None else self.train_step(input_x, target_y)
+    def fit_step(self, input_x, target_y, wave=None, framing=None):
+        """One iteration of the loop body of trainer.py:212-215: step, then set lr for the next step.  wave, framing: as in train_step."""
+        if framing is not None:
+            out = self.train_step(input_x, target_y, wave=wave, framing=framing)
+        else:
+            out = self.train_step(input_x, target_y, wave=wave) if wave is not None else self.train_step(input_x, target_y)
         self.lr = self.noam_scheme(out[2], self.warmup_steps)
         return out
 

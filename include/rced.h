@@ -250,6 +250,29 @@ int rced_istft_fr_check(int window, int stride, int window_name);
 int rced_istft_ola_fr(const float* mag_dev, const float* phase_dev, const int* frames_dev, int N, int T, int window, int stride,
                       int window_name, float* audio_dev, int device, void* stream);
 
+/* rced_wave_loss at a framing: the same terms, validity, eps, objective and g_y, with W = window, S = stride and w = numpy's window of
+ * that name at length W in place of 256, 128 and hamming.  Per utterance: M [T,129] the prediction, P the mixture's unit phase, F its
+ * frame count, c the clean row of l samples.
+ *   The rebuild.  y = rced_istft_ola_fr(M, P, F), exactly as defined above: x_t = irfft(M_t P_t, 256)[:W];
+ *     D[i] = sum_t w[i - tS]^2 and e[i] = sum_t w[i - tS] x_t[i - tS] / D[i] over the frames t < F that cover i; e[i] = 0 where
+ *     D[i] <= 1e-10; y[i] = e[i] + 0.97 y[i-1]; n_out = (F - 1) S + W.
+ *   The range R = [lo, hi).  skip_edges = 1: lo = W - S, hi = min(l, F S) -- exactly the samples whose covering frames are limited
+ *     neither by t >= 0 nor by t <= F - 1; in there D is periodic in S.  At 256 / 128 this is rced_wave_loss's [128, 128 F).
+ *     skip_edges = 0: lo = 0, hi = min(l, n_out).  F <= 0 or hi <= lo gives an empty range: no contribution, zero gradient, the SI-SDR
+ *     term invalid.
+ *   The gradient.  g_e[i] = g_y[i] + 0.97 g_e[i+1] for i < n_out; u[i] = g_e[i] / D[i], and u[i] = 0 where D[i] <= 1e-10 -- decided
+ *     with the expression the rebuild uses (an fp32 sum of w[r]^2 in ascending frame order), so the forward's zero set and the
+ *     gradient's are the same set; G_t = rfft_256(w u[tS : tS + W]), zero-padded to 256;
+ *     dM_t[b] = (kappa_b / 256)(P_re G_re + P_im G_im) for t < F, exact zeros for t >= F.
+ * frames_dev [N] int32 or NULL (= rced_stft_num_frames_fr(length, W, S)); either is clamped into [0, T].  Like the other _fr entries
+ * this one always runs the general kernels, at 256 / 128 / hamming too.  A framing rced_framing_check refuses is RCED_ERR_ARG before
+ * any device work; everything else about arguments, reads, determinism and the workspace (one of its own per (device, stream),
+ * growing only: the second call at a shape allocates nothing and can be captured) as rced_wave_loss.  Eight launches with a
+ * gradient, six without. */
+int rced_wave_loss_fr(const float* mag_dev, const float* phase_dev, const int* frames_dev, const float* clean_dev, int clean_stride,
+                      const int* lengths_dev, int N, int T, int window, int stride, int window_name, double w_sse, double w_si_sdr,
+                      int skip_edges, double inv_batch, double* terms_dev, float* grad_dev, int device, void* stream);
+
 /* ---- evaluation loop (tester.py:92-167, trainer.py:252-338): the two numpy pieces around the rebuilt audio, for a
  * ragged batch.  Streaming reductions without atomics: results are bit-identical run to run, and utterance n's result
  * does not depend on N, on its neighbours, on its row index or on the row strides (kernels_eval.h).  Both keep a slice
@@ -723,6 +746,16 @@ int rced_train_step_wave(rced_trainer* t, const float* x_dev, const float* y_dev
                          const rced_wave_args* wave, double* loss_out, double* parts_out, void* stream);
 int rced_train_grad_wave(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, float* g_dev, double* s_dev,
                          int accumulate, const rced_wave_args* wave, double* loss_out, double* parts_out, void* stream);
+
+/* ... at a framing: the wave terms are rced_wave_loss_fr's at (window, stride, window_name), frames_dev = NULL meaning
+ * rced_stft_num_frames_fr(length, window, stride); the pass differs at the same one place.  They always run the general kernels, at
+ * 256 / 128 / hamming too.  A framing rced_framing_check refuses is RCED_ERR_ARG before anything else is looked at. */
+int rced_train_step_wave_fr(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, float lr,
+                            const rced_wave_args* wave, int window, int stride, int window_name, double* loss_out,
+                            double* parts_out, void* stream);
+int rced_train_grad_wave_fr(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, float* g_dev, double* s_dev,
+                            int accumulate, const rced_wave_args* wave, int window, int stride, int window_name, double* loss_out,
+                            double* parts_out, void* stream);
 
 /* The moving-statistics update from s_dev (momentum 0.99, unbiased variance, by the step's expressions), then the Adam
  * step from g_dev with the fed learning rate; global_step += 1.  Afterwards rced_train_get_gradients returns g_dev's

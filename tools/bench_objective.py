@@ -4,7 +4,10 @@ line 1: audio.wave_loss_batch's entry (rced_wave_loss, with and without the grad
         audio.istft_batch(rebuild="ola") on the same signals, alternating, the median of five windows of 50 calls;
 line 2: the CR-CED training step with the spectral loss beside the step with each objective, one trainer, alternating, the
         median of three windows of 10 steps (the learning rate is 0: every window steps the same variables).
---entries: line 1 only (what a kernel trace of the added launches is taken from)."""
+--entries: line 1 only (what a kernel trace of the added launches is taken from).
+--framing W S name: line 1 also times, in the same alternating run and on the same signals, rced_wave_loss_fr at that framing (with
+        and without the gradient) beside audio.stft_batch(framing=) and audio.istft_batch(rebuild="ola", framing=) -- the general
+        kernels (kernels_framing.h, kernels_wave_loss_fr.h) next to the specialised ones; the keys end in _fr."""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -58,11 +61,33 @@ def wave(with_grad):
                                   terms.data_ptr(), grad.data_ptr() if with_grad else None, 0, stream))
 
 
-med, _ = alternating({"stft_ms": lambda: audio.stft_batch(pcm), "istft_ola_ms": lambda: audio.istft_batch(mag, ph, rebuild="ola"),
-                      "wave_loss_terms_ms": lambda: wave(False), "wave_loss_ms": lambda: wave(True)}, 5, 50)
+fns = {"stft_ms": lambda: audio.stft_batch(pcm), "istft_ola_ms": lambda: audio.istft_batch(mag, ph, rebuild="ola"),
+       "wave_loss_terms_ms": lambda: wave(False), "wave_loss_ms": lambda: wave(True)}
+shape = {"utterances": N, "frames": T, "samples": L}
+if "--framing" in sys.argv[1:]:
+    at = sys.argv.index("--framing")
+    fr = audio.Framing(int(sys.argv[at + 1]), int(sys.argv[at + 2]), sys.argv[at + 3])
+    mag_fr, ph_fr = audio.stft_batch(pcm, framing=fr)
+    T_fr = int(mag_fr.shape[1])
+    phr_fr, m3_fr = torch.view_as_real(ph_fr).contiguous(), mag_fr.squeeze(-1).contiguous()
+    grad_fr = torch.empty((N, T_fr, 129), dtype=torch.float32, device="cuda")
+
+    def wave_fr(with_grad):
+        _lib.check(lib.rced_wave_loss_fr(m3_fr.data_ptr(), phr_fr.data_ptr(), None, clean.data_ptr(), L, ldev.data_ptr(), N, T_fr, fr.window,
+                                         fr.stride, fr.code, 0.5, 1.0, 1, 1.0 / N, terms.data_ptr(),
+                                         grad_fr.data_ptr() if with_grad else None, 0, stream))
+
+    fns.update({"stft_fr_ms": lambda: audio.stft_batch(pcm, framing=fr),
+                "istft_ola_fr_ms": lambda: audio.istft_batch(mag_fr, ph_fr, rebuild="ola", framing=fr),
+                "wave_loss_terms_fr_ms": lambda: wave_fr(False), "wave_loss_fr_ms": lambda: wave_fr(True)})
+    shape.update({"framing": [fr.window, fr.stride, fr.windows_name], "frames_fr": T_fr})
+med, _ = alternating(fns, 5, 50)
 med["reverse_and_adjoint_ms"] = med["wave_loss_ms"] - med["wave_loss_terms_ms"]
 med["sums_ms"] = med["wave_loss_terms_ms"] - med["istft_ola_ms"]
-print(json.dumps(dict({"utterances": N, "frames": T, "samples": L}, **med)))
+if "wave_loss_fr_ms" in med:
+    med["reverse_and_adjoint_fr_ms"] = med["wave_loss_fr_ms"] - med["wave_loss_terms_fr_ms"]
+    med["sums_fr_ms"] = med["wave_loss_terms_fr_ms"] - med["istft_ola_fr_ms"]
+print(json.dumps(dict(shape, **med)))
 if "--entries" in sys.argv[1:]:
     sys.exit(0)
 
