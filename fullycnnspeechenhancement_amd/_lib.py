@@ -47,6 +47,10 @@ SYMBOLS = {
                                       ctypes.c_int, ctypes.c_double, _vp, _vp, ctypes.c_int, _vp]),
     "rced_wave_loss_fr": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _vp] + [ctypes.c_int] * 5 + [ctypes.c_double, ctypes.c_double,
                                          ctypes.c_int, ctypes.c_double, _vp, _vp, ctypes.c_int, _vp]),
+    "rced_mr_stft_check": (ctypes.c_int, [_vp]),
+    "rced_mr_stft": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_double, _vp, _vp, ctypes.c_int, _vp]),
+    "rced_wave_loss_mr": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, _vp] + [ctypes.c_int] * 5 + [ctypes.c_double, ctypes.c_double,
+                                         ctypes.c_int, ctypes.c_double, _vp, _vp, _vp, ctypes.c_int, _vp]),
     "rced_framing_check": (ctypes.c_int, [ctypes.c_int] * 3),
     "rced_stft_num_frames_fr": (ctypes.c_int, [ctypes.c_int] * 3),
     "rced_stft_fr": (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 6 + [_vp, _vp, ctypes.c_int, _vp]),
@@ -122,6 +126,10 @@ SYMBOLS = {
                                 [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _vp]),
     "rced_train_grad_wave_fr": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp] + [ctypes.c_int] * 3 +
                                 [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _vp]),
+    "rced_train_step_wave_mr": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, _vp] + [ctypes.c_int] * 3 +
+                                [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _vp]),
+    "rced_train_grad_wave_mr": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp] + [ctypes.c_int] * 3 +
+                                [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _vp]),
     "rced_train_apply": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_float, _vp]),
     "rced_train_sync_points": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_size_t)]),
     "rced_train_sync_begin": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _vp, _vp]),
@@ -149,6 +157,12 @@ class WaveArgs(ctypes.Structure):
     """rced.h: rced_wave_args."""
     _fields_ = [("w_spectral", ctypes.c_double), ("w_sse", ctypes.c_double), ("w_si_sdr", ctypes.c_double), ("skip_edges", ctypes.c_int),
                 ("phase_dev", _vp), ("clean_dev", _vp), ("clean_stride", ctypes.c_int), ("lengths_dev", _vp), ("frames_dev", _vp)]
+
+
+class MrArgs(ctypes.Structure):
+    """rced.h: rced_mr_args."""
+    _fields_ = [("w_mr", ctypes.c_double), ("n_res", ctypes.c_int), ("window", ctypes.c_int * 4), ("stride", ctypes.c_int * 4),
+                ("window_name", ctypes.c_int * 4)]
 
 
 class RcedError(RuntimeError):

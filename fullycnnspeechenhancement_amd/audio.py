@@ -23,7 +23,7 @@ from .arena import PCM_DTYPES, gather_pcm, resample_arena, resample_batch, resam
 from .streaming import (STREAM_DELAY, STREAM_FINISH_MAX, STREAM_MAX_HOPS, StreamingDenoiser, StreamingResampler,  # noqa: F401
                         resampler_delay, stream_delay, stream_delay_fr)
 from .freerun import BlockDenoiser, FreeResampler, block_delay, free_available  # noqa: F401
-from .objective import WaveObjective, wave_loss_batch  # noqa: F401
+from .objective import WaveObjective, mr_stft_batch, wave_loss_batch  # noqa: F401
 
 
 WINDOWS = {"hamming": 0, "hanning": 1, "blackman": 2, "bartlett": 3}     # rced.h: RCED_WINDOW_*; numpy's windows of those names
@@ -93,6 +93,15 @@ class Framing(object):
     def width(self, frames):
         """Columns of a rebuild of `frames` frames: (W - S) + T * S."""
         return (self.window - self.stride) + int(frames) * self.stride
+
+
+def __getattr__(name):
+    """MR_STFT_8K, the default resolutions of the multi-resolution STFT term at 8 kHz, made on first use (a Framing asks the library)."""
+    if name == "MR_STFT_8K":
+        value = (Framing(256, 64, "hanning"), Framing(128, 32, "hanning"), Framing(64, 16, "hanning"))
+        globals()[name] = value
+        return value
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
 def _general(framing):

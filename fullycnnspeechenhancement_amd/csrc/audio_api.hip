@@ -17,6 +17,7 @@
 #include "kernels_framing.h"
 #include "kernels_wave_loss.h"
 #include "kernels_wave_loss_fr.h"
+#include "kernels_mr_stft.h"
 #include "rced_internal.h"
 
 using namespace rced;
@@ -215,7 +216,7 @@ int reference_rebuild_check(int name) {
 }
 
 // One pack per (kind, window length, window name) and device, with the fp32 table that goes with it; the stride enters no pack.
-enum { kFrStft = 0, kFrOla = 1, kFrRef256 = 2, kFrRef512 = 3, kFrAdjoint = 4 };
+enum { kFrStft = 0, kFrOla = 1, kFrRef256 = 2, kFrRef512 = 3, kFrAdjoint = 4, kFrMrSynth = 5 };
 struct FrPack {
   unsigned short* pack = nullptr;
   float* aux = nullptr;   // rebuilds: [2][256], the coefficients of im(bin 128) (row scale folded in), then w^2; kFrStft, kFrAdjoint: none
@@ -249,6 +250,17 @@ int build_fr(FrPack& e, int kind, int W, int name) {
     };
     return upload(&e.pack, pack_x6(audio::fr::kFrMT, coef), kWhat);
   }
+  if (kind == kFrMrSynth) {
+    // kernels_mr_stft.h: the transpose of the STFT's pack -- rows = samples, K slot 2b + c, slot 1 = re of bin 128 (the imaginary parts
+    // of bins 0 and 128 are zero), w[row](cos, -sin), zero rows past W; no 1 / 256 and no kappa: it is the analysis' adjoint
+    auto coef = [&](int row, int k) {
+      const int b = k == 1 ? 128 : k >> 1;
+      const bool im = k >= 2 && (k & 1);
+      const double th = 2.0 * M_PI * ((b * row) % audio::kFrame) / audio::kFrame;
+      return w[row] * (im ? -std::sin(th) : std::cos(th));
+    };
+    return upload(&e.pack, pack_x6(audio::fr::kFrMT, coef), kWhat);
+  }
   const int nfft = kind == kFrRef512 ? 512 : 256;
   auto scale = [&](int r) { return r >= W ? 0.0 : kind == kFrOla ? w[r] : 1.0 / w[r]; };
   auto coef = [&](int row, int k) { return scale(row) * (k == 1 ? irfft_coef(nfft, row, 128, 0) : irfft_coef(nfft, row, k >> 1, k & 1)); };
@@ -269,7 +281,9 @@ int fr_pack(int device, int kind, int W, int name, FrPack* out) {   // g_fr_mu h
     if (int rc = set_dynamic_lds({{kernel_ptr(audio::fr::stft_fr_kernel), audio::fr::kStftFrLdsBytes},
                                   {kernel_ptr(audio::fr::frames_fr_kernel), audio::fr::kFramesFrLdsBytes},
                                   {kernel_ptr(wloss::fr::adjoint_kernel<true>), audio::fr::kStftFrLdsBytes},
-                                  {kernel_ptr(wloss::fr::adjoint_kernel<false>), audio::fr::kStftFrLdsBytes}},
+                                  {kernel_ptr(wloss::fr::adjoint_kernel<false>), audio::fr::kStftFrLdsBytes},
+                                  {kernel_ptr(mrstft::analysis_kernel), audio::fr::kStftFrLdsBytes},
+                                  {kernel_ptr(mrstft::synth_kernel), audio::fr::kStftFrLdsBytes}},
                                  "framing LDS"))
       return rc;
     g_fr_attr[device] = true;
@@ -514,10 +528,11 @@ int rced_wave_loss_fr_run(const float* mag_dev, const float* phase_dev, const in
   LAUNCH(wloss::sums_kernel<1>, dim3(slices, N), dim3(wloss::kSumThreads), 0, st, (const float*)y, (int)L, clean_dev, clean_stride, lengths_dev,
          (const int*)frames, skip_edges, W, S, (const double*)ws1, ws2, slices);
   LAUNCH(wloss::terms_kernel, dim3(N), dim3(wloss::kSumThreads), 0, st, (const double*)ws1, (const double*)ws2, lengths_dev,
-         (const int*)frames, clean_stride, skip_edges, W, S, slices, terms_dev, scal);
+         (const int*)frames, clean_stride, skip_edges, W, S, slices, terms_dev, 3, scal);
   if (grad_dev && T > 0) {
-    LAUNCH(wloss::fr::reverse_kernel, dim3(N), dim3(audio::x6::kThreadsX), 0, st, (const float*)y, L, clean_dev, clean_stride, lengths_dev,
-           (const int*)frames, skip_edges, W, S, (const double*)scal, 2.0 * w_sse * inv_batch, w_si_sdr * inv_batch, w2, u);
+    LAUNCH(wloss::fr::reverse_kernel<false>, dim3(N), dim3(audio::x6::kThreadsX), 0, st, (const float*)y, L, clean_dev, clean_stride, lengths_dev,
+           (const int*)frames, skip_edges, W, S, (const double*)scal, 2.0 * w_sse * inv_batch, w_si_sdr * inv_batch, w2, (const float*)nullptr,
+           u);
     if (accumulate)
       LAUNCH(wloss::fr::adjoint_kernel<true>, dim3(N, 2, range_split(N, T)), dim3(audio::x6::kThreadsX), audio::fr::kStftFrLdsBytes, st,
              (const float*)u, L, (const int*)frames, (const unsigned short*)adj.pack, phase_dev, T, W, S, grad_dev);
@@ -558,7 +573,7 @@ int rced_wave_loss_run(const float* mag_dev, const float* phase_dev, const int* 
   LAUNCH(wloss::sums_kernel<1>, dim3(slices, N), dim3(wloss::kSumThreads), 0, st, (const float*)y, L, clean_dev, clean_stride, lengths_dev,
          (const int*)frames, skip_edges, audio::kFrame, audio::kStep, (const double*)ws1, ws2, slices);
   LAUNCH(wloss::terms_kernel, dim3(N), dim3(wloss::kSumThreads), 0, st, (const double*)ws1, (const double*)ws2, lengths_dev,
-         (const int*)frames, clean_stride, skip_edges, audio::kFrame, audio::kStep, slices, terms_dev, scal);
+         (const int*)frames, clean_stride, skip_edges, audio::kFrame, audio::kStep, slices, terms_dev, 3, scal);
   if (grad_dev && T > 0) {
     LAUNCH(wloss::reverse_kernel, dim3(N), dim3(audio::x6::kThreadsX), 0, st, (const float*)y, L, clean_dev, clean_stride, lengths_dev,
            (const int*)frames, skip_edges, (const double*)scal, 2.0 * w_sse * inv_batch, w_si_sdr * inv_batch,
@@ -569,6 +584,191 @@ int rced_wave_loss_run(const float* mag_dev, const float* phase_dev, const int* 
     else
       LAUNCH(wloss::adjoint_kernel<false>, dim3(N, 2, range_split(N, T)), dim3(audio::x6::kThreadsX), 0, st, (const float*)u, L,
              (const int*)frames, (const unsigned short*)t->adj_x6, phase_dev, T, grad_dev);
+  }
+  return RCED_OK;
+}
+
+// ---- the multi-resolution STFT term (kernels_mr_stft.h) ----------------------------------------------------------
+static StreamWorkspace g_mr_ws;           // rced_mr_stft's workspace
+static StreamWorkspace g_wave_mr_ws;      // rced_wave_loss_mr's: the rebuild's part, carved as rced_wave_loss_fr's
+static StreamWorkspace g_wave_mr_ws2;     // ... and the term's part, carved by mr_take
+
+static int mr_check(const rced_mr_args* mr) {
+  if (!mr) return rced_fail(RCED_ERR_ARG, "the multi-resolution arguments are NULL");
+  if (!(mr->w_mr >= 0.0) || !std::isfinite(mr->w_mr)) return rced_fail(RCED_ERR_ARG, "w_mr must be finite and >= 0, got %g", mr->w_mr);
+  if (mr->n_res < 1 || mr->n_res > mrstft::kMaxRes) return rced_fail(RCED_ERR_ARG, "n_res must lie in [1, 4] resolutions, got %d", mr->n_res);
+  for (int r = 0; r < mr->n_res; ++r)
+    if (int rc = framing_check(mr->window[r], mr->stride[r], mr->window_name[r])) return rc;
+  return RCED_OK;
+}
+
+struct MrPlan {
+  mrstft::Params P;
+  FrPack ana[mrstft::kMaxRes], syn[mrstft::kMaxRes];
+  int Jmx = 0, nslmax = 1;   // the most frames of any resolution, and its 64-frame slices
+  size_t scratch = 0;        // floats of the frame scratch, every resolution
+  float *ysp = nullptr, *ym = nullptr, *cm = nullptr, *frsc = nullptr, *gmr = nullptr;
+  double* part = nullptr;
+  int2* rng = nullptr;
+};
+
+// The shapes for N rows whose ranges are at most Lmax samples wide
+static void mr_shape(const rced_mr_args* mr, long long Lmax, int N, MrPlan& pl) {
+  pl.P.K = mr->n_res;
+  for (int r = 0; r < mr->n_res; ++r) {
+    const int W = mr->window[r], S = mr->stride[r], Wp = (W + 15) & ~15;
+    const int Jmax = Lmax >= W ? (int)((Lmax - W) / S) + 1 : 0;
+    pl.P.r[r] = mrstft::Res{W, S, Wp, Jmax, (long long)pl.scratch};
+    pl.scratch += (size_t)N * Jmax * Wp;
+    pl.Jmx = std::max(pl.Jmx, Jmax);
+  }
+  pl.nslmax = std::max(1, (pl.Jmx + audio::kFramesPerWg - 1) / audio::kFramesPerWg);
+}
+
+// seven buffers: a Carve of their own.  gmr_floats: the fp32 row set the gather writes when the caller's gradient is not that row set
+static void mr_take(Carve& ws, MrPlan& pl, int N, bool grad, size_t gmr_floats) {
+  const size_t bins = (size_t)N * pl.Jmx * audio::kBins;
+  ws.take(&pl.ysp, 2 * bins);
+  ws.take(&pl.ym, bins);
+  ws.take(&pl.cm, bins);
+  ws.take(&pl.part, (size_t)N * pl.P.K * pl.nslmax * 3);
+  ws.take(&pl.rng, (size_t)N);
+  ws.take(&pl.frsc, grad ? pl.scratch : 0);
+  ws.take(&pl.gmr, gmr_floats);
+}
+
+// the packs of every resolution (g_fr_mu held).  A look-up may drop every pack that no stream has pinned, once: the second round
+// finds, or rebuilds, what the first one lost
+static int mr_packs(const rced_mr_args* mr, int device, bool grad, MrPlan& pl) {
+  for (int round = 0; round < 2; ++round)
+    for (int r = 0; r < mr->n_res; ++r) {
+      if (int rc = fr_pack(device, kFrStft, mr->window[r], mr->window_name[r], &pl.ana[r])) return rc;
+      if (grad)
+        if (int rc = fr_pack(device, kFrMrSynth, mr->window[r], mr->window_name[r], &pl.syn[r])) return rc;
+    }
+  return RCED_OK;
+}
+
+static int mr_split(int N, int Jmax) {
+  const int nblk = (Jmax + audio::kFramesPerWg - 1) / audio::kFramesPerWg;
+  int s = 1;
+  while (s < nblk && (long long)N * s < 512) s *= 2;
+  return std::max(1, std::min(s, nblk));
+}
+
+// Per resolution analysis, sums and -- with a gradient -- synthesis, before the next resolution reuses the spectra; then the terms and
+// the gather: 2 K + 1 launches, 3 K + 2 with a gradient.  pl.rng holds the ranges.  g [N, gstride]: columns below gwidth are written.
+static int mr_run(const MrPlan& pl, const float* est, long long est_stride, const float* ref, long long ref_stride, int N, double scale,
+                  double* out, int out_stride, int detail, float* g, long long gwidth, long long gstride, hipStream_t st) {
+  const size_t pstride = (size_t)pl.P.K * pl.nslmax * 3;
+  for (int r = 0; r < pl.P.K; ++r) {
+    const mrstft::Res& q = pl.P.r[r];
+    if (q.Jmax == 0) continue;   // no row is as long as this window
+    double* part = pl.part + (size_t)r * pl.nslmax * 3;
+    LAUNCH(mrstft::analysis_kernel, dim3(2 * N, 2, mr_split(2 * N, q.Jmax)), dim3(audio::x6::kThreadsX), audio::fr::kStftFrLdsBytes, st, est,
+           est_stride, ref, ref_stride, (const int2*)pl.rng, (const unsigned short*)pl.ana[r].pack, N, q.W, q.S, q.Jmax, pl.ysp, pl.ym, pl.cm);
+    LAUNCH(mrstft::sums_kernel, dim3((q.Jmax + audio::kFramesPerWg - 1) / audio::kFramesPerWg, N), dim3(mrstft::kSumThreads), 0, st,
+           (const int2*)pl.rng, q.W, q.S, q.Jmax, (const float*)pl.ym, (const float*)pl.cm, part, pstride);
+    if (g)
+      LAUNCH(mrstft::synth_kernel, dim3(N, 2, mr_split(N, q.Jmax)), dim3(audio::x6::kThreadsX), audio::fr::kStftFrLdsBytes, st,
+             (const int2*)pl.rng, (const unsigned short*)pl.syn[r].pack, (const float*)pl.ysp, (const float*)pl.ym, (const float*)pl.cm,
+             (const double*)part, pstride, scale / pl.P.K, q.W, q.S, q.Wp, q.Jmax, pl.frsc + q.off);
+  }
+  LAUNCH(mrstft::terms_kernel, dim3(N), dim3(64), 0, st, (const int2*)pl.rng, pl.P, (const double*)pl.part, pl.nslmax, out, out_stride, detail);
+  if (g && gwidth > 0)
+    LAUNCH(mrstft::gather_kernel, dim3((unsigned)((gwidth + 255) / 256), N), dim3(256), 0, st, (const int2*)pl.rng, pl.P,
+           (const float*)pl.frsc, gwidth, gstride, g);
+  return RCED_OK;
+}
+
+static int mr_stft_run(const float* est_dev, int est_stride, const float* ref_dev, int ref_stride, const int* lengths_dev, int N,
+                       const rced_mr_args* mr, double inv_batch, double* terms_dev, float* grad_dev, int device, void* stream) {
+  if (int rc = mr_check(mr)) return rc;
+  if (N < 0 || est_stride < 0 || ref_stride < 0) return rced_fail(RCED_ERR_ARG, "negative shape");
+  if (!(inv_batch > 0.0) || !std::isfinite(inv_batch)) return rced_fail(RCED_ERR_ARG, "inv_batch must be finite and > 0, got %g", inv_batch);
+  if (N > 65535) return rced_fail(RCED_ERR_ARG, "N > 65535 utterances per call");
+  if (N == 0) return RCED_OK;
+  if (!terms_dev || !lengths_dev || (est_stride > 0 && !est_dev) || (ref_stride > 0 && !ref_dev)) return rced_fail(RCED_ERR_ARG, "null pointer");
+  DeviceGuard g(device);
+  std::lock_guard<std::mutex> lk(g_fr_mu);
+  MrPlan pl;
+  if (int rc = mr_packs(mr, device, grad_dev != nullptr, pl)) return rc;
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  const int width = std::min(est_stride, ref_stride);
+  mr_shape(mr, width, N, pl);
+  Carve ws;
+  mr_take(ws, pl, N, grad_dev != nullptr, 0);
+  if (int rc = ws.bind(device, stream, g_mr_ws)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  LAUNCH(mrstft::ranges_kernel, dim3((N + 255) / 256), dim3(256), 0, st, lengths_dev, N, width, pl.rng);
+  return mr_run(pl, est_dev, est_stride, ref_dev, ref_stride, N, mr->w_mr * inv_batch, terms_dev, 2 + 3 * mr->n_res, 1, grad_dev, est_stride,
+                est_stride, st);
+}
+
+int rced_wave_loss_mr_run(const float* mag_dev, const float* phase_dev, const int* frames_dev, const float* clean_dev, int clean_stride,
+                          const int* lengths_dev, int N, int T, int W, int S, int name, double w_sse, double w_si_sdr, int skip_edges,
+                          double inv_batch, const rced_mr_args* mr, double* terms_dev, float* grad_dev, int accumulate, int device,
+                          void* stream) {
+  if (int rc = framing_check(W, S, name)) return rc;
+  if (int rc = mr_check(mr)) return rc;
+  if (int rc = wave_loss_args(mag_dev, phase_dev, clean_dev, clean_stride, lengths_dev, N, T, w_sse, w_si_sdr, skip_edges, inv_batch, terms_dev))
+    return rc == kNothingToDo ? RCED_OK : rc;
+  const int nblk = (T + audio::kFramesPerWg - 1) / audio::kFramesPerWg;
+  if (nblk > 65535) return rced_fail(RCED_ERR_ARG, "T > 65535 * 64 frames per call");
+  const bool grad = grad_dev && T > 0;
+  DeviceGuard g(device);
+  std::lock_guard<std::mutex> lk(g_fr_mu);
+  FrPack ola, adj;
+  MrPlan pl;
+  for (int round = 0; round < 2; ++round) {   // (the second round finds, or rebuilds, what a dropping look-up of the first one lost)
+    if (int rc = fr_pack(device, kFrOla, W, name, &ola)) return rc;
+    if (int rc = fr_pack(device, kFrAdjoint, W, name, &adj)) return rc;
+    if (int rc = mr_packs(mr, device, grad, pl)) return rc;
+  }
+  if (!g.ok) return rced_fail(RCED_ERR_HIP, "hipSetDevice(%d) failed", device);
+  const long long L = wloss::fr::row_stride(T, W, S);   // floats per row of y, u and g_mr: whole 16-byte groups
+  const int slices = wloss::num_slices((int)L);
+  float *y, *u, *Y;
+  double *ws1, *ws2, *scal;
+  int* frames;
+  Carve ws;
+  ws.take(&y, (size_t)N * L);
+  ws.take(&u, (size_t)N * L);
+  ws.take(&Y, (size_t)N * T * audio::kFrame);
+  ws.take(&ws1, (size_t)N * slices * 2);
+  ws.take(&ws2, (size_t)N * slices * 2);
+  ws.take(&scal, (size_t)N * 4);
+  ws.take(&frames, (size_t)N);
+  if (int rc = ws.bind(device, stream, g_wave_mr_ws)) return rc;
+  mr_shape(mr, std::min<long long>(L, clean_stride), N, pl);   // R lies below the clean row's end and below n_out <= L
+  Carve ws2c;
+  mr_take(ws2c, pl, N, grad, grad ? (size_t)N * L : 0);
+  if (int rc = ws2c.bind(device, stream, g_wave_mr_ws2)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const float* w2 = ola.aux + audio::kFrame;
+  LAUNCH(wloss::fr::counts_kernel, dim3((N + 255) / 256), dim3(256), 0, st, frames_dev, lengths_dev, N, T, W, S, frames);
+  if (T > 0)
+    LAUNCH(audio::fr::frames_fr_kernel, dim3(N, 2, nblk), dim3(audio::x6::kThreadsX), audio::fr::kFramesFrLdsBytes, st, mag_dev, phase_dev,
+           (const int*)frames, (const unsigned short*)ola.pack, (const float*)ola.aux, T, W, Y);
+  LAUNCH(audio::fr::rebuild_fr_kernel<true>, dim3(N), dim3(audio::x6::kThreadsX), 0, st, (const float*)Y, (const int*)frames, w2, T, W, S, L, y);
+  LAUNCH(wloss::sums_kernel<0>, dim3(slices, N), dim3(wloss::kSumThreads), 0, st, (const float*)y, (int)L, clean_dev, clean_stride, lengths_dev,
+         (const int*)frames, skip_edges, W, S, (const double*)nullptr, ws1, slices);
+  LAUNCH(wloss::sums_kernel<1>, dim3(slices, N), dim3(wloss::kSumThreads), 0, st, (const float*)y, (int)L, clean_dev, clean_stride, lengths_dev,
+         (const int*)frames, skip_edges, W, S, (const double*)ws1, ws2, slices);
+  LAUNCH(wloss::terms_kernel, dim3(N), dim3(wloss::kSumThreads), 0, st, (const double*)ws1, (const double*)ws2, lengths_dev,
+         (const int*)frames, clean_stride, skip_edges, W, S, slices, terms_dev, 5, scal);
+  LAUNCH(mrstft::wave_ranges_kernel, dim3((N + 255) / 256), dim3(256), 0, st, lengths_dev, (const int*)frames, N, clean_stride, skip_edges, W, S,
+         pl.rng);
+  if (int rc = mr_run(pl, y, L, clean_dev, clean_stride, N, mr->w_mr * inv_batch, terms_dev + 3, 5, 0, grad ? pl.gmr : nullptr, L, L, st)) return rc;
+  if (grad) {
+    LAUNCH(wloss::fr::reverse_kernel<true>, dim3(N), dim3(audio::x6::kThreadsX), 0, st, (const float*)y, L, clean_dev, clean_stride, lengths_dev,
+           (const int*)frames, skip_edges, W, S, (const double*)scal, 2.0 * w_sse * inv_batch, w_si_sdr * inv_batch, w2, (const float*)pl.gmr, u);
+    if (accumulate)
+      LAUNCH(wloss::fr::adjoint_kernel<true>, dim3(N, 2, range_split(N, T)), dim3(audio::x6::kThreadsX), audio::fr::kStftFrLdsBytes, st,
+             (const float*)u, L, (const int*)frames, (const unsigned short*)adj.pack, phase_dev, T, W, S, grad_dev);
+    else
+      LAUNCH(wloss::fr::adjoint_kernel<false>, dim3(N, 2, range_split(N, T)), dim3(audio::x6::kThreadsX), audio::fr::kStftFrLdsBytes, st,
+             (const float*)u, L, (const int*)frames, (const unsigned short*)adj.pack, phase_dev, T, W, S, grad_dev);
   }
   return RCED_OK;
 }
@@ -614,6 +814,21 @@ int rced_istft_ola_fr(const float* mag_dev, const float* phase_dev, const int* f
   if (int rc = framing_check(window, stride, window_name)) return rc;
   if (int rc = audio_args(N, T, false, audio_dev && (T == 0 || (mag_dev && phase_dev)))) return rc == kNothingToDo ? RCED_OK : rc;
   return rebuild_fr<true>(mag_dev, phase_dev, frames_dev, N, T, kFrOla, window, stride, window_name, audio_dev, device, stream);
+}
+
+int rced_mr_stft_check(const rced_mr_args* mr) { return mr_check(mr); }
+
+int rced_mr_stft(const float* est_dev, int est_stride, const float* ref_dev, int ref_stride, const int* lengths_dev, int N,
+                 const rced_mr_args* mr, double inv_batch, double* terms_dev, float* grad_dev, int device, void* stream) {
+  return mr_stft_run(est_dev, est_stride, ref_dev, ref_stride, lengths_dev, N, mr, inv_batch, terms_dev, grad_dev, device, stream);
+}
+
+int rced_wave_loss_mr(const float* mag_dev, const float* phase_dev, const int* frames_dev, const float* clean_dev, int clean_stride,
+                      const int* lengths_dev, int N, int T, int window, int stride, int window_name, double w_sse, double w_si_sdr,
+                      int skip_edges, double inv_batch, const rced_mr_args* mr, double* terms_dev, float* grad_dev, int device,
+                      void* stream) {
+  return rced_wave_loss_mr_run(mag_dev, phase_dev, frames_dev, clean_dev, clean_stride, lengths_dev, N, T, window, stride, window_name, w_sse,
+                               w_si_sdr, skip_edges, inv_batch, mr, terms_dev, grad_dev, 0, device, stream);
 }
 
 int rced_wave_loss_fr(const float* mag_dev, const float* phase_dev, const int* frames_dev, const float* clean_dev, int clean_stride,

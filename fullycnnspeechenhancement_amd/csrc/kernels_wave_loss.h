@@ -148,12 +148,12 @@ __global__ __launch_bounds__(kSumThreads) void sums_kernel(const float* __restri
   if (threadIdx.x == 0) *reinterpret_cast<double2*>(out + ((size_t)n * slices + s) * 2) = make_double2(a, b);
 }
 
-// grid (N): terms[n] = (wave_sse, si_sdr, valid); scal[n] = (alpha, 2 k alpha / (|alpha c|^2 + eps), 2 k / (|r|^2 + eps), 0), the
+// grid (N): terms[n] = (wave_sse, si_sdr, valid), rows tstride doubles apart; scal[n] = (alpha, 2 k alpha / (|alpha c|^2 + eps), 2 k / (|r|^2 + eps), 0), the
 // last two zero for an invalid row: what the reverse pass forms g_y from
 __global__ __launch_bounds__(kSumThreads) void terms_kernel(const double* __restrict__ ws1, const double* __restrict__ ws2,
                                                              const int* __restrict__ lengths, const int* __restrict__ frames,
                                                              int clean_stride, int skip_edges, int W, int S, int slices,
-                                                             double* __restrict__ terms, double* __restrict__ scal) {
+                                                             double* __restrict__ terms, int tstride, double* __restrict__ scal) {
   __shared__ double red[kSumWaves][2];
   const int n = blockIdx.x;
   const int nsl = num_slices(range_of(lengths, frames, n, clean_stride, skip_edges, W, S).hi);
@@ -164,9 +164,9 @@ __global__ __launch_bounds__(kSumThreads) void terms_kernel(const double* __rest
     const bool valid = nsl > 0 && cc > 0.0;
     const double alpha = valid ? yc / cc : 0.0;
     const double target = alpha * alpha * cc;
-    terms[(size_t)n * 3] = sse;
-    terms[(size_t)n * 3 + 1] = valid ? 10.0 * log10((target + kEps) / (rr + kEps)) : 0.0;
-    terms[(size_t)n * 3 + 2] = valid ? 1.0 : 0.0;
+    terms[(size_t)n * tstride] = sse;
+    terms[(size_t)n * tstride + 1] = valid ? 10.0 * log10((target + kEps) / (rr + kEps)) : 0.0;
+    terms[(size_t)n * tstride + 2] = valid ? 1.0 : 0.0;
     scal[(size_t)n * 4] = alpha;
     scal[(size_t)n * 4 + 1] = valid ? 2.0 * kDb * alpha / (target + kEps) : 0.0;
     scal[(size_t)n * 4 + 2] = valid ? 2.0 * kDb / (rr + kEps) : 0.0;

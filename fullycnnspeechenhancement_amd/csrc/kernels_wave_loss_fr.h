@@ -52,12 +52,15 @@ constexpr int kRevLdsFloats = kFramesPerWg * kORow + 2 * kThreadsX + audio::kFra
 // 8192 c + 8176 - 16 i .. + 15 of chunk c; position p = 8191 - q of the mirrored chunk is deemph_scan's time order, the carry (g_e of
 // the later chunk's first sample) in a register: wloss::reverse_kernel's walk.  g_y as there, in fp64, rounded once.
 // y, u [N, ystride], ystride a multiple of four floats; w2: 256 floats, w^2 (zero past W).  Every column of u is written: g_e / D below
-// n_out, zeros from there on.
+// n_out, zeros from there on.  ADD: gadd [N, ystride] (the multi-resolution STFT term's gradient with respect to y, kernels_mr_stft.h) is
+// added to g_y on R in fp64, before the rounding and the scan; without it the instantiation is the kernel as it has always been.
+template <bool ADD>
 __global__ __launch_bounds__(kThreadsX) void reverse_kernel(const float* __restrict__ y, long long ystride, const float* __restrict__ clean,
                                                              int clean_stride, const int* __restrict__ lengths,
                                                              const int* __restrict__ frames, int skip_edges, int W, int S,
                                                              const double* __restrict__ scal, double a2, double wsi,
-                                                             const float* __restrict__ w2, float* __restrict__ u) {
+                                                             const float* __restrict__ w2, const float* __restrict__ gadd,
+                                                             float* __restrict__ u) {
   __shared__ __attribute__((aligned(16))) float lds[kRevLdsFloats];
   float* obuf = lds;
   float* sa = obuf + kFramesPerWg * kORow;
@@ -91,7 +94,8 @@ __global__ __launch_bounds__(kThreadsX) void reverse_kernel(const float* __restr
         for (int k = 0; k < 4; ++k)
           if (g + k >= R.lo && g + k < R.hi) {
             const double yy = yv[k], cc = cr[g + k];
-            o[k] = (float)(a2 * (yy - cc) + (q2 * (yy - alpha * cc) - q1 * cc));
+            const double gy = a2 * (yy - cc) + (q2 * (yy - alpha * cc) - q1 * cc);
+            o[k] = ADD ? (float)(gy + (double)gadd[(size_t)n * ystride + g + k]) : (float)gy;
           }
       }
       *reinterpret_cast<f32x4*>(mine + 4 * j4) = f32x4{o[3], o[2], o[1], o[0]};

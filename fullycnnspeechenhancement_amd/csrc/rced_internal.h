@@ -97,6 +97,12 @@ int rced_wave_loss_run(const float* mag_dev, const float* phase_dev, const int* 
 int rced_wave_loss_fr_run(const float* mag_dev, const float* phase_dev, const int* frames_dev, const float* clean_dev, int clean_stride,
                           const int* lengths_dev, int N, int T, int W, int S, int name, double w_sse, double w_si_sdr, int skip_edges,
                           double inv_batch, double* terms_dev, float* grad_dev, int accumulate, int device, void* stream);
+// ... and rced_wave_loss_mr: the same with the multi-resolution STFT term on the rebuilt signal; terms_dev [N, 5]
+struct rced_mr_args;
+int rced_wave_loss_mr_run(const float* mag_dev, const float* phase_dev, const int* frames_dev, const float* clean_dev, int clean_stride,
+                          const int* lengths_dev, int N, int T, int W, int S, int name, double w_sse, double w_si_sdr, int skip_edges,
+                          double inv_batch, const rced_mr_args* mr, double* terms_dev, float* grad_dev, int accumulate, int device,
+                          void* stream);
 
 // stream_api.hip: streams created on `m` answer RCED_ERR_STATE from now on (rced_destroy calls this before the model goes)
 void rced_streams_detach(rced_model* m);

@@ -489,7 +489,8 @@ struct TrainPass {
   std::vector<double> hp;      // the loss kernel's partial sums, on the host after end()'s synchronise
   const rced_wave_args* wave = nullptr;   // the wave objective's terms (rced.h), or nullptr: the spectral loss alone, today's pass
   const int* wave_fr = nullptr;           // (window, stride, window name) of the _fr entries: the wave terms through the general kernels
-  std::vector<double> hw;      // [N][3]: the wave terms per utterance, on the host after end()'s synchronise
+  const rced_mr_args* wave_mr = nullptr;  // the _mr entries: the multi-resolution STFT term next to them (then with wave_fr)
+  std::vector<double> hw;      // [N][3], with wave_mr [N][5]: the wave terms per utterance, on the host after end()'s synchronise
   Stage stage = Stage::Fwd;
   int layer = 0;
   FinishPoint pt{};
@@ -698,7 +699,7 @@ struct TrainPass {
                          P, (wave ? (float)wave->w_spectral : 1.f) / (float)t->batch_size, t->G[L], t->part);
       HIP_TRY(hipMemcpyAsync(hp.data(), t->part, kReduceGrid * sizeof(double), hipMemcpyDeviceToHost, st));
     }
-    if (wave && (wave->w_sse > 0.0 || wave->w_si_sdr > 0.0)) {
+    if (wave && (wave->w_sse > 0.0 || wave->w_si_sdr > 0.0 || (wave_mr && wave_mr->w_mr > 0.0))) {
       if (t->wave_rows < N) {
         if (t->wave_terms) {
           HIP_TRY(hipStreamSynchronize(st));
@@ -706,10 +707,14 @@ struct TrainPass {
           t->wave_terms = nullptr;
           t->wave_rows = 0;
         }
-        HIP_TRY(hipMalloc(&t->wave_terms, (size_t)N * 3 * sizeof(double)));
+        HIP_TRY(hipMalloc(&t->wave_terms, (size_t)N * 5 * sizeof(double)));   // (3 columns, 5 with the multi-resolution term)
         t->wave_rows = N;
       }
-      if (int rc = wave_fr ? rced_wave_loss_fr_run(t->out[L], wave->phase_dev, wave->frames_dev, wave->clean_dev, wave->clean_stride,
+      if (int rc = wave_mr ? rced_wave_loss_mr_run(t->out[L], wave->phase_dev, wave->frames_dev, wave->clean_dev, wave->clean_stride,
+                                                   wave->lengths_dev, N, T, wave_fr[0], wave_fr[1], wave_fr[2], wave->w_sse, wave->w_si_sdr,
+                                                   wave->skip_edges, 1.0 / (double)t->batch_size, wave_mr, t->wave_terms, t->G[L],
+                                                   spectral ? 1 : 0, t->device, st)
+               : wave_fr ? rced_wave_loss_fr_run(t->out[L], wave->phase_dev, wave->frames_dev, wave->clean_dev, wave->clean_stride,
                                                    wave->lengths_dev, N, T, wave_fr[0], wave_fr[1], wave_fr[2], wave->w_sse, wave->w_si_sdr,
                                                    wave->skip_edges, 1.0 / (double)t->batch_size, t->wave_terms, t->G[L], spectral ? 1 : 0,
                                                    t->device, st)
@@ -717,7 +722,7 @@ struct TrainPass {
                                                 wave->lengths_dev, N, T, wave->w_sse, wave->w_si_sdr, wave->skip_edges,
                                                 1.0 / (double)t->batch_size, t->wave_terms, t->G[L], spectral ? 1 : 0, t->device, st))
         return rc;
-      hw.assign((size_t)N * 3, 0.0);
+      hw.assign((size_t)N * (wave_mr ? 5 : 3), 0.0);
       HIP_TRY(hipMemcpyAsync(hw.data(), t->wave_terms, hw.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     }
     // ---- backward.  G[id] collects d loss / d tensor id from every consumer (the conv reading it, skip adds); the plan says
@@ -956,12 +961,18 @@ struct TrainPass {
       if (loss_out) *loss_out = loss / (double)t->batch_size;
       return RCED_OK;
     }
-    double sse = 0.0, si = 0.0;   // in row order
-    for (int n = 0; n < (int)(hw.size() / 3); ++n) {
-      sse += hw[(size_t)n * 3];
-      if (hw[(size_t)n * 3 + 2] != 0.0) si += hw[(size_t)n * 3 + 1];
+    double sse = 0.0, si = 0.0, mr = 0.0;   // in row order
+    const size_t cols = wave_mr ? 5 : 3;
+    for (int n = 0; n < (int)(hw.size() / cols); ++n) {
+      sse += hw[(size_t)n * cols];
+      if (hw[(size_t)n * cols + 2] != 0.0) si += hw[(size_t)n * cols + 1];
+      if (wave_mr && hw[(size_t)n * cols + 4] != 0.0) mr += hw[(size_t)n * cols + 3];
     }
-    if (loss_out) *loss_out = (wave->w_spectral * loss + wave->w_sse * sse - wave->w_si_sdr * si) / (double)t->batch_size;
+    if (loss_out) {
+      if (wave_mr) *loss_out = (wave->w_spectral * loss + wave->w_sse * sse - wave->w_si_sdr * si + wave_mr->w_mr * mr) / (double)t->batch_size;
+      else *loss_out = (wave->w_spectral * loss + wave->w_sse * sse - wave->w_si_sdr * si) / (double)t->batch_size;
+    }
+    if (parts_out && wave_mr) parts_out[3] = mr;
     if (parts_out) {
       parts_out[0] = loss;
       parts_out[1] = sse;
@@ -972,16 +983,17 @@ struct TrainPass {
 };
 
 // what rced_train_step_wave / rced_train_grad_wave refuse in their struct, before any device work
-int check_wave(const rced_wave_args* w, const float* y_dev) {
+// w_mr: the multi-resolution term's weight (checked by rced_mr_stft_check), 0 for the entries without one
+int check_wave(const rced_wave_args* w, const float* y_dev, double w_mr = 0.0) {
   if (!w) return rced_fail(RCED_ERR_ARG, "the wave objective's arguments are NULL");
   const double ws[3] = {w->w_spectral, w->w_sse, w->w_si_sdr};
   for (double v : ws)
     if (!(v >= 0.0) || !std::isfinite(v))
       return rced_fail(RCED_ERR_ARG, "the objective's weights must be finite and >= 0, got %g, %g, %g", ws[0], ws[1], ws[2]);
-  if (ws[0] == 0.0 && ws[1] == 0.0 && ws[2] == 0.0) return rced_fail(RCED_ERR_ARG, "the objective's weights are all zero");
+  if (ws[0] == 0.0 && ws[1] == 0.0 && ws[2] == 0.0 && w_mr == 0.0) return rced_fail(RCED_ERR_ARG, "the objective's weights are all zero");
   if (w->skip_edges != 0 && w->skip_edges != 1) return rced_fail(RCED_ERR_ARG, "skip_edges must be 0 or 1, got %d", w->skip_edges);
   if (ws[0] > 0.0 && !y_dev) return rced_fail(RCED_ERR_ARG, "the target is NULL and the spectral term has a weight");
-  if ((ws[1] > 0.0 || ws[2] > 0.0) && (!w->phase_dev || !w->lengths_dev || w->clean_stride < 0 || (w->clean_stride > 0 && !w->clean_dev)))
+  if ((ws[1] > 0.0 || ws[2] > 0.0 || w_mr > 0.0) && (!w->phase_dev || !w->lengths_dev || w->clean_stride < 0 || (w->clean_stride > 0 && !w->clean_dev)))
     return rced_fail(RCED_ERR_ARG, "a wave term has a weight: it needs phase_dev, clean_dev (rows of clean_stride >= 0) and lengths_dev");
   return RCED_OK;
 }
@@ -989,12 +1001,14 @@ int check_wave(const rced_wave_args* w, const float* y_dev) {
 // args_rc: what the entry point made of its arguments (check_batch and its own)
 int train_run(rced_trainer* t, const char* what, int args_rc, const float* x_dev, const float* y_dev, float* pred_dev, int N, int T,
               float lr, double* loss_out, void* stream, float* g_out = nullptr, double* s_out = nullptr, int accumulate = 0,
-              const rced_wave_args* wave = nullptr, double* parts_out = nullptr, const int* wave_fr = nullptr) {
+              const rced_wave_args* wave = nullptr, double* parts_out = nullptr, const int* wave_fr = nullptr,
+              const rced_mr_args* wave_mr = nullptr) {
   Enter in(t, what, args_rc);
   if (in.rc) return in.rc;
   TrainPass pass(t, x_dev, y_dev, pred_dev, N, T, lr, stream, g_out != nullptr, 0.0, nullptr);
   pass.wave = wave;
   pass.wave_fr = wave_fr;
+  pass.wave_mr = wave_mr;
   if (int rc = pass.begin()) return rc;
   if (int rc = pass.advance()) return rc;
   return pass.end(g_out, s_out, accumulate, loss_out, parts_out);
@@ -1076,6 +1090,31 @@ int rced_train_grad_wave_fr(rced_trainer* t, const float* x_dev, const float* y_
   if (!rc && (!g_dev || !s_dev)) rc = rced_fail(RCED_ERR_ARG, "an exchange buffer is NULL");
   return train_run(t, "rced_train_grad_wave_fr", rc, x_dev, y_dev, nullptr, N, T, 0.f, loss_out, stream, g_dev, s_dev, accumulate != 0, wave,
                    parts_out, fr);
+}
+
+int rced_train_step_wave_mr(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, float lr, const rced_wave_args* wave,
+                            int window, int stride, int window_name, const rced_mr_args* mr, double* loss_out, double* parts_out,
+                            void* stream) {
+  const int fr[3] = {window, stride, window_name};
+  int rc = rced_framing_check(window, stride, window_name);
+  if (!rc) rc = rced_mr_stft_check(mr);
+  if (!rc) rc = check_wave(wave, y_dev, mr->w_mr);
+  if (!rc) rc = check_batch(t, x_dev, y_dev ? y_dev : x_dev, N, T);
+  return train_run(t, "rced_train_step_wave_mr", rc, x_dev, y_dev, nullptr, N, T, lr, loss_out, stream, nullptr, nullptr, 0, wave, parts_out, fr,
+                   mr);
+}
+
+int rced_train_grad_wave_mr(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, float* g_dev, double* s_dev,
+                            int accumulate, const rced_wave_args* wave, int window, int stride, int window_name, const rced_mr_args* mr,
+                            double* loss_out, double* parts_out, void* stream) {
+  const int fr[3] = {window, stride, window_name};
+  int rc = rced_framing_check(window, stride, window_name);
+  if (!rc) rc = rced_mr_stft_check(mr);
+  if (!rc) rc = check_wave(wave, y_dev, mr->w_mr);
+  if (!rc) rc = check_batch(t, x_dev, y_dev ? y_dev : x_dev, N, T);
+  if (!rc && (!g_dev || !s_dev)) rc = rced_fail(RCED_ERR_ARG, "an exchange buffer is NULL");
+  return train_run(t, "rced_train_grad_wave_mr", rc, x_dev, y_dev, nullptr, N, T, 0.f, loss_out, stream, g_dev, s_dev, accumulate != 0, wave,
+                   parts_out, fr, mr);
 }
 
 int rced_train_apply(rced_trainer* t, const float* g_dev, const double* s_dev, float lr, void* stream) {

@@ -121,7 +121,7 @@ class FullyCNNTrainer(object):
         if objective is not None and not isinstance(objective, WaveObjective):
             raise ValueError("objective must be an audio.WaveObjective or None (the spectral loss), got %r" % (objective,))
         self.objective = objective                 # None: sum((target - pred)^2) / batch_size, the reference's loss
-        self.loss_parts = None                     # the last step's unweighted (spectral, wave_sse, si_sdr) sums, with an objective
+        self.loss_parts = None                     # the last step's unweighted (spectral, wave_sse, si_sdr[, mr_stft]) sums, with an objective
         if isinstance(accumulate, bool) or int(accumulate) != accumulate or int(accumulate) < 1:
             raise ValueError("accumulate must be a positive integer (1: the whole batch in one piece), got %r" % (accumulate,))
         self.accumulate = int(accumulate)          # train_step cuts its batch into this many shards (gradient accumulation)
@@ -224,12 +224,24 @@ class FullyCNNTrainer(object):
         from .audio import _general
         return _general(framing)
 
+    def _mr_args(self):
+        """rced_mr_args of an objective with mr_stft > 0 (the _mr entries, loss_parts of 4), else None."""
+        o = self.objective
+        return o.mr_args() if o is not None and o.mr_stft > 0.0 else None
+
+    @staticmethod
+    def _mr_framing(fr):
+        """The framing the _mr entries rebuild at: they take one always, the default included."""
+        from .audio import Framing
+        return fr if fr is not None else Framing()
+
     def train_step(self, input_x, target_y, wave=None, framing=None):
         """trainer.py:181-192: returns (batch_loss, summary (None here), global_step).  With accumulate=k > 1 the batch is
         cut into k contiguous row ranges (accumulation_slices) and the step is train_step_sharded over them.
         With an objective that has a wave term, wave = (phase, clean_rows, lengths): the mixture's unit phase [N, T, 129] complex,
         the clean signals as device rows and the samples scored per utterance (audio.wave_loss_batch); accumulate=k cuts it by
-        the same rows.  self.loss_parts then holds the step's unweighted (spectral, wave_sse, si_sdr) sums.
+        the same rows.  self.loss_parts then holds the step's unweighted (spectral, wave_sse, si_sdr) sums, and a fourth, mr_stft,
+        with an objective whose mr_stft > 0.
         framing: the audio.Framing the wave terms are rebuilt at (the one `wave`'s phase was taken at); None is Framing()."""
         import torch
         fr = self._wave_framing(framing)
@@ -244,8 +256,14 @@ class FullyCNNTrainer(object):
                                                    ctypes.c_float(self.lr), ctypes.byref(loss), st))
             return loss.value, None, self.global_step
         args, keep = self._wave_args(wave, x)
-        parts = (ctypes.c_double * 3)()
-        if fr is not None:
+        mr = self._mr_args()
+        parts = (ctypes.c_double * (4 if mr is not None else 3))()
+        if mr is not None:
+            at = self._mr_framing(fr)
+            _lib.check(_lib.load().rced_train_step_wave_mr(self._h, x.data_ptr(), y.data_ptr(), int(x.shape[0]), int(x.shape[1]),
+                                                           ctypes.c_float(self.lr), ctypes.byref(args), at.window, at.stride, at.code,
+                                                           ctypes.byref(mr), ctypes.byref(loss), parts, st))
+        elif fr is not None:
             _lib.check(_lib.load().rced_train_step_wave_fr(self._h, x.data_ptr(), y.data_ptr(), int(x.shape[0]), int(x.shape[1]),
                                                            ctypes.c_float(self.lr), ctypes.byref(args), fr.window, fr.stride, fr.code,
                                                            ctypes.byref(loss), parts, st))
@@ -286,8 +304,14 @@ class FullyCNNTrainer(object):
                                                    s.data_ptr(), 1 if accumulate else 0, ctypes.byref(loss), st))
             return loss.value
         args, keep = self._wave_args(wave, x)
-        parts = (ctypes.c_double * 3)()
-        if fr is not None:
+        mr = self._mr_args()
+        parts = (ctypes.c_double * (4 if mr is not None else 3))()
+        if mr is not None:
+            at = self._mr_framing(fr)
+            _lib.check(_lib.load().rced_train_grad_wave_mr(self._h, x.data_ptr(), y.data_ptr(), int(x.shape[0]), int(x.shape[1]), g.data_ptr(),
+                                                           s.data_ptr(), 1 if accumulate else 0, ctypes.byref(args), at.window, at.stride,
+                                                           at.code, ctypes.byref(mr), ctypes.byref(loss), parts, st))
+        elif fr is not None:
             _lib.check(_lib.load().rced_train_grad_wave_fr(self._h, x.data_ptr(), y.data_ptr(), int(x.shape[0]), int(x.shape[1]), g.data_ptr(),
                                                            s.data_ptr(), 1 if accumulate else 0, ctypes.byref(args), fr.window, fr.stride,
                                                            fr.code, ctypes.byref(loss), parts, st))

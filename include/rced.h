@@ -273,6 +273,59 @@ int rced_wave_loss_fr(const float* mag_dev, const float* phase_dev, const int* f
                       const int* lengths_dev, int N, int T, int window, int stride, int window_name, double w_sse, double w_si_sdr,
                       int skip_edges, double inv_batch, double* terms_dev, float* grad_dev, int device, void* stream);
 
+/* ---- the multi-resolution STFT term: a spectral-convergence part and a log-magnitude part per resolution (Yamamoto et al. 2020,
+ * Defossez et al. 2020), between a signal y and a clean signal c.  All sums are fp64, taken from the fp32 signals.  For one utterance,
+ * [lo, hi) the scored range and K resolutions (W_r, S_r, name_r), 1 <= K <= 4, each one rced_framing_check accepts:
+ *   J_r = floor((hi - lo - W_r) / S_r) + 1 if hi - lo >= W_r, else 0: only whole frames inside the range, no padding, nothing outside
+ *     [lo, hi) is read, and the samples behind the last whole frame play no part at that resolution.
+ *   X_j = rfft_256(w_r x[lo + j S_r : lo + j S_r + W_r]), zero-padded to 256, no pre-emphasis; w_r = numpy's window of that name at
+ *     length W_r, in double, on the host.
+ *   |X|_eps = sqrt(re^2 + im^2 + eps), eps = 1e-8 (this project's choice, as for SI-SDR).
+ *   A_r = sum (|C|_eps - |Y|_eps)^2, B_r = sum |C|_eps^2 over j < J_r and 129 bins;  sc_r = sqrt(A_r / B_r);
+ *   lsd_r = sum (ln|C|_eps - ln|Y|_eps)^2 / (129 J_r): the mean SQUARED log-magnitude difference, not the published L1 -- an L1
+ *     term's gradient jumps where two magnitudes tie, and an fp32 device cannot be held to a derived bar across a sign flip.
+ *   term = sum_{r: J_r > 0} (sc_r + lsd_r) / K;  mr_valid = 1 if any J_r > 0, else 0: an invalid term counts 0 and has zero gradient.
+ *   The gradient with respect to y.  Per bin, d = ln|C|_eps - ln|Y|_eps:
+ *     g = -(|C|_eps - |Y|_eps) / (sqrt(A_r) sqrt(B_r)) - 2 d / (129 J_r |Y|_eps), the first part exactly 0 where A_r = 0;
+ *     G = g Y / |Y|_eps;  d/dy[lo + j S_r + k] += w_r[k] sum_b (G_re cos(2 pi b k / 256) - G_im sin(2 pi b k / 256));
+ *     divided by K, times w_mr inv_batch; summed over frames in ascending j, then over resolutions in ascending r.  No kappa factor:
+ *     the loss sums 129 bins, not 256.
+ * No model has been trained to convergence with this term. */
+typedef struct rced_mr_args {
+  double w_mr;        /* the term's weight, finite and >= 0 */
+  int n_res;          /* K, 1 .. 4 */
+  int window[4];      /* W_r, S_r, RCED_WINDOW_* of resolution r < K */
+  int stride[4];
+  int window_name[4];
+} rced_mr_args;
+
+/* RCED_OK or RCED_ERR_ARG (the reason in rced_last_error): NULL, a weight that is negative or not finite, n_res outside [1, 4], a
+ * resolution rced_framing_check refuses.  Touches no device. */
+int rced_mr_stft_check(const rced_mr_args* mr);
+
+/* The term between two ragged row sets over [0, l_n), l_n = lengths_dev[n] clamped into [0, min(est_stride, ref_stride)].
+ * est_dev, ref_dev: N rows of est_stride / ref_stride floats, any alignment.  terms_dev [N, 2 + 3 K] double = (term, valid, then
+ * sc_r, lsd_r, J_r per resolution), unweighted.  grad_dev: NULL, or [N, est_stride] float32 = d(w_mr inv_batch sum_n term_n) / d est,
+ * every column written, zeros from l_n on.  What rced_mr_stft_check refuses, a negative shape, inv_batch not finite or <= 0,
+ * N > 65535 and a missing pointer are RCED_ERR_ARG before any device work.  No atomics: bit-identical run to run, and a row's bits do
+ * not depend on N, its row index or its neighbours.  A workspace per (device, stream), growing only (Y, |Y|, |C| of the resolution
+ * with the most frames, and with a gradient a frame scratch [N, J_r, W_r] per resolution): the second call at a shape allocates
+ * nothing and can be captured.  2 K + 2 launches, 3 K + 3 with a gradient.  Asynchronous. */
+int rced_mr_stft(const float* est_dev, int est_stride, const float* ref_dev, int ref_stride, const int* lengths_dev, int N,
+                 const rced_mr_args* mr, double inv_batch, double* terms_dev, float* grad_dev, int device, void* stream);
+
+/* rced_wave_loss_fr plus the term on its rebuilt y against the clean rows, over its R (the same skip_edges rule).
+ * terms_dev [N, 5] double = (wave_sse, si_sdr, valid, mr_stft, mr_valid), unweighted.  grad_dev: NULL or [N, T, 129] float32, the
+ * gradient of  w_sse inv_batch sum wave_sse - w_si_sdr inv_batch sum_valid si_sdr + w_mr inv_batch sum_valid mr_stft  with respect to
+ * mag: the term's gradient with respect to y is added to g_y in fp64, before the de-emphasis' transposed scan; everything behind
+ * that place is rced_wave_loss_fr's.  The same kernels as rced_mr_stft, with R as the per-utterance range.  It always runs the
+ * general kernels, at 256 / 128 / hamming too.  Arguments, reads, determinism and workspaces as rced_wave_loss_fr and rced_mr_stft.
+ * 8 + 2 K launches, 11 + 3 K with a gradient. */
+int rced_wave_loss_mr(const float* mag_dev, const float* phase_dev, const int* frames_dev, const float* clean_dev, int clean_stride,
+                      const int* lengths_dev, int N, int T, int window, int stride, int window_name, double w_sse, double w_si_sdr,
+                      int skip_edges, double inv_batch, const rced_mr_args* mr, double* terms_dev, float* grad_dev, int device,
+                      void* stream);
+
 /* ---- evaluation loop (tester.py:92-167, trainer.py:252-338): the two numpy pieces around the rebuilt audio, for a
  * ragged batch.  Streaming reductions without atomics: results are bit-identical run to run, and utterance n's result
  * does not depend on N, on its neighbours, on its row index or on the row strides (kernels_eval.h).  Both keep a slice
@@ -756,6 +809,18 @@ int rced_train_step_wave_fr(rced_trainer* t, const float* x_dev, const float* y_
 int rced_train_grad_wave_fr(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, float* g_dev, double* s_dev,
                             int accumulate, const rced_wave_args* wave, int window, int stride, int window_name, double* loss_out,
                             double* parts_out, void* stream);
+
+/* ... with the multi-resolution STFT term (rced_wave_loss_mr) on the rebuilt prediction:
+ *   loss = w_spectral sum((target - M)^2) / B + w_sse sum_n wave_sse_n / B - w_si_sdr sum_valid si_sdr_n / B + w_mr sum_valid mr_stft_n / B.
+ * The _fr entries with the resolutions and 4 doubles in parts_out (the fourth: sum_valid mr_stft_n).  The four weights must not all
+ * be zero; phase_dev, clean_dev and lengths_dev are needed where w_sse, w_si_sdr or w_mr has a weight; y_dev may be NULL when
+ * w_spectral = 0.  What rced_framing_check or rced_mr_stft_check refuses is RCED_ERR_ARG before anything else is looked at. */
+int rced_train_step_wave_mr(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, float lr,
+                            const rced_wave_args* wave, int window, int stride, int window_name, const rced_mr_args* mr,
+                            double* loss_out, double* parts_out, void* stream);
+int rced_train_grad_wave_mr(rced_trainer* t, const float* x_dev, const float* y_dev, int N, int T, float* g_dev, double* s_dev,
+                            int accumulate, const rced_wave_args* wave, int window, int stride, int window_name,
+                            const rced_mr_args* mr, double* loss_out, double* parts_out, void* stream);
 
 /* The moving-statistics update from s_dev (momentum 0.99, unbiased variance, by the step's expressions), then the Adam
  * step from g_dev with the fed learning rate; global_step += 1.  Afterwards rced_train_get_gradients returns g_dev's

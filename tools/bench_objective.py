@@ -7,7 +7,10 @@ line 2: the CR-CED training step with the spectral loss beside the step with eac
 --entries: line 1 only (what a kernel trace of the added launches is taken from).
 --framing W S name: line 1 also times, in the same alternating run and on the same signals, rced_wave_loss_fr at that framing (with
         and without the gradient) beside audio.stft_batch(framing=) and audio.istft_batch(rebuild="ola", framing=) -- the general
-        kernels (kernels_framing.h, kernels_wave_loss_fr.h) next to the specialised ones; the keys end in _fr."""
+        kernels (kernels_framing.h, kernels_wave_loss_fr.h) next to the specialised ones; the keys end in _fr.
+Line 1 always times rced_wave_loss_mr with audio.MR_STFT_8K (kernels_mr_stft.h) beside rced_wave_loss_fr at the same framing --
+        256 / 128 / hamming through the general kernels -- with and without the gradient: the keys wave_loss_fr256_* and wave_loss_mr_*;
+        line 2 the step with the multi-resolution STFT term beside the steps without it."""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -61,8 +64,25 @@ def wave(with_grad):
                                   terms.data_ptr(), grad.data_ptr() if with_grad else None, 0, stream))
 
 
+mr_args = audio.WaveObjective(1, 0, 0, True, 0.5).mr_args()
+terms5 = torch.empty((N, 5), dtype=torch.float64, device="cuda")
+
+
+def wave_fr256(with_grad):
+    _lib.check(lib.rced_wave_loss_fr(m3.data_ptr(), phr.data_ptr(), None, clean.data_ptr(), L, ldev.data_ptr(), N, T, 256, 128, 0, 0.5, 1.0, 1,
+                                     1.0 / N, terms.data_ptr(), grad.data_ptr() if with_grad else None, 0, stream))
+
+
+def wave_mr(with_grad):
+    import ctypes
+    _lib.check(lib.rced_wave_loss_mr(m3.data_ptr(), phr.data_ptr(), None, clean.data_ptr(), L, ldev.data_ptr(), N, T, 256, 128, 0, 0.5, 1.0, 1,
+                                     1.0 / N, ctypes.byref(mr_args), terms5.data_ptr(), grad.data_ptr() if with_grad else None, 0, stream))
+
+
 fns = {"stft_ms": lambda: audio.stft_batch(pcm), "istft_ola_ms": lambda: audio.istft_batch(mag, ph, rebuild="ola"),
-       "wave_loss_terms_ms": lambda: wave(False), "wave_loss_ms": lambda: wave(True)}
+       "wave_loss_terms_ms": lambda: wave(False), "wave_loss_ms": lambda: wave(True),
+       "wave_loss_fr256_terms_ms": lambda: wave_fr256(False), "wave_loss_fr256_ms": lambda: wave_fr256(True),
+       "wave_loss_mr_terms_ms": lambda: wave_mr(False), "wave_loss_mr_ms": lambda: wave_mr(True)}
 shape = {"utterances": N, "frames": T, "samples": L}
 if "--framing" in sys.argv[1:]:
     at = sys.argv.index("--framing")
@@ -84,6 +104,8 @@ if "--framing" in sys.argv[1:]:
 med, _ = alternating(fns, 5, 50)
 med["reverse_and_adjoint_ms"] = med["wave_loss_ms"] - med["wave_loss_terms_ms"]
 med["sums_ms"] = med["wave_loss_terms_ms"] - med["istft_ola_ms"]
+med["mr_term_ms"] = med["wave_loss_mr_terms_ms"] - med["wave_loss_fr256_terms_ms"]
+med["mr_term_and_gradient_ms"] = med["wave_loss_mr_ms"] - med["wave_loss_fr256_ms"]
 if "wave_loss_fr_ms" in med:
     med["reverse_and_adjoint_fr_ms"] = med["wave_loss_fr_ms"] - med["wave_loss_terms_fr_ms"]
     med["sums_fr_ms"] = med["wave_loss_terms_fr_ms"] - med["istft_ola_fr_ms"]
@@ -95,7 +117,9 @@ tr = FullyCNNTrainer("FullyCNNV3", batch_size=N, lr=0.0, weights=_weights.synthe
 target, _ = audio.stft_batch(clean)
 wave_args = (ph, clean, lengths)
 OBJECTIVES = {"spectral": None, "spectral+wave_sse": audio.WaveObjective(1, 1, 0), "spectral+si_sdr": audio.WaveObjective(1, 0, 1),
-              "spectral+wave_sse+si_sdr": audio.WaveObjective(1, 0.5, 1), "si_sdr": audio.WaveObjective(0, 0, 1)}
+              "spectral+wave_sse+si_sdr": audio.WaveObjective(1, 0.5, 1), "si_sdr": audio.WaveObjective(0, 0, 1),
+              "spectral+wave_sse+si_sdr@fr256": audio.WaveObjective(1, 0.5, 1),
+              "spectral+wave_sse+si_sdr+mr_stft": audio.WaveObjective(1, 0.5, 1, True, 0.5), "spectral+mr_stft": audio.WaveObjective(1, 0, 0, True, 0.5)}
 
 
 def step(objective):
@@ -103,7 +127,18 @@ def step(objective):
     tr.train_step(mag, target, wave=wave_args if objective is not None else None)
 
 
-med, all_windows = alternating({k: (lambda o=o: step(o)) for k, o in OBJECTIVES.items()}, 3, 10, warm=2)
+def step_fr256(objective):
+    """The same objective through rced_train_step_wave_fr: the general kernels the _mr entries run, without the term."""
+    import ctypes
+    tr.objective = objective
+    args, keep = tr._wave_args(wave_args, mag)
+    loss, parts = ctypes.c_double(), (ctypes.c_double * 3)()
+    _lib.check(lib.rced_train_step_wave_fr(tr._h, mag.data_ptr(), target.data_ptr(), N, T, ctypes.c_float(0.0), ctypes.byref(args), 256, 128, 0,
+                                           ctypes.byref(loss), parts, stream))
+
+
+med, all_windows = alternating({k: (lambda o=o, k=k: step_fr256(o) if k.endswith("@fr256") else step(o)) for k, o in OBJECTIVES.items()}, 3, 10,
+                               warm=2)
 print(json.dumps({"net": "FullyCNNV3", "utterances": N, "frames": T, "step_ms": med,
                   "added_ms": {k: v - med["spectral"] for k, v in med.items() if k != "spectral"}, "step_ms_windows": all_windows}))
 tr.close()
